@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- end-to-end frames/s of the detect+refine path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5]
+  python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR]
       N = 1: runs in this process.  N > 1 from a bare shell (no RANK/WORLD_SIZE): starts its own N ranks under
       torch.distributed.run on 127.0.0.1 at a free port (self_launch) and relays rank 0's JSON line + the exit code.
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...     (ranks started by the caller)
@@ -157,6 +157,27 @@ def cpu_baseline(oracle, name, frames_u8, budget_s=24.0):
                        ", ".join(f"{c} thr: {v:.1f} fps" for c, v in batch.items()) + f"]; host has {ncpu} logical CPUs")}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, results):
+    """--dump-outputs: what the timed path handed back for its LAST step, as float64 .npy files, so that two builds of the
+    project can be compared array for array on identical inputs.  results: one entry per frame of the step (rank-major at
+    N > 1), in infer_image's format: (K,3) rows [x, y, id], np.array([]) for no corner, None if the frame overflowed the pool.
+      corners.npy            (sum K, 3)  the rows of every frame, concatenated in frame order
+      corners_per_frame.npy  (frames,)   K of each frame (NaN: overflowed the pool)
+    If the two would exceed DUMP_LIMIT_BYTES, corners.npy holds a fixed, seeded sample of the rows (in order) instead."""
+    rows = [r for r in results if r is not None and r.ndim == 2]
+    corners = np.concatenate(rows).astype(np.float64) if rows else np.zeros((0, 3), np.float64)
+    counts = np.array([np.nan if r is None else (r.shape[0] if r.ndim == 2 else 0) for r in results], np.float64)
+    if corners.nbytes + counts.nbytes > DUMP_LIMIT_BYTES:
+        n_keep = (DUMP_LIMIT_BYTES - counts.nbytes) // corners[:1].nbytes
+        corners = corners[np.sort(np.random.default_rng(0).choice(len(corners), n_keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "corners.npy"), corners)
+    np.save(os.path.join(out_dir, "corners_per_frame.npy"), counts)
+
+
 class Ctx:
     pass
 
@@ -180,8 +201,9 @@ def fetch_profile(L, total_patches):
 
 
 def run_config(cx, name, batch, height, width, kmax, frames_kind, fixed_k, steps, warmup, profile, n_check,
-               want_cpu_baseline=False):
-    """One measured configuration on every rank.  Returns (rank 0) the dict for the JSON line."""
+               want_cpu_baseline=False, dump_dir=None):
+    """One measured configuration on every rank.  Returns (rank 0) the dict for the JSON line.  dump_dir: rank 0 writes the
+    last timed step's results there (dump_outputs)."""
     L, dev, rank, world, dist = cx.L, cx.dev, cx.rank, cx.world, cx.dist
     B, H, Wd = batch, height, width
     seed0 = FRAME_SEED + rank * 100000
@@ -351,6 +373,8 @@ def run_config(cx, name, batch, height, width, kmax, frames_kind, fixed_k, steps
         pool = (len(local) - 2 * B) // 6
     res_local, counts_local = unpack_results(local, B, pool, True)
     total_patches = float(min(int(counts_local.astype(np.int64).sum()), pool))
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, [f for p in per_rank for f in unpack_results(p, B, pool, True)[0]])
 
     timed_hdr = None
     if profile:
@@ -681,7 +705,12 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the product path); gloo only to smoke-test the multi-process flow "
                          "with several ranks on one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (every frame's corner rows, float64) as "
+                         "DIR/<name>.npy; the inputs are seeded, so runs with the same arguments are comparable array for array")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args.gpus, args.backend, sys.argv[1:]))
@@ -729,7 +758,7 @@ def main():
             p[k_] = v
     main_res = run_config(cx, args.config, p["batch"], p["height"], p["width"], p["kmax"], p["frames"], p["fixed_k"],
                           args.steps, args.warmup, not args.no_profile, args.parity_frames,
-                          want_cpu_baseline=(world == 1 and not args.no_cpu_baseline))
+                          want_cpu_baseline=(world == 1 and not args.no_cpu_baseline), dump_dir=args.dump_outputs)
 
     others = {}
     if not args.no_extras:

@@ -1,9 +1,13 @@
 """Worker of tests/test_gpu_sharded.py: one rank of the N>1 PRODUCT path (real HIP kernels) on the GPU box.
 
 Launched with `python -m torch.distributed.run --nproc-per-node R ... sharded_gpu_worker.py <backend> <out.json>`.
-backend "gloo": R ranks share the one visible GPU (exchange through host memory); "nccl": one GPU per rank (RCCL).
+backend "gloo": R ranks share the one visible GPU (exchange through host memory); "nccl": RCCL, one GPU per rank when there are
+R GPUs.  With fewer GPUs than RCCL ranks the ranks share GPUs: RCCL refuses two ranks of one host on one device ("Duplicate GPU
+detected"), so every rank announces its own host id (NCCL_HOSTID) and RCCL connects the ranks like separate nodes, through its
+socket transport on the loopback interface -- the same RCCL collectives on device buffers, another transport than xGMI.
 Every rank runs `infer_frames_sharded` (ragged split) and the pipelined `infer_batches_sharded` (side-stream gather,
 double-buffered) through the HIP pipeline; rank 0 compares every frame with the oracle and writes the verdict."""
+import datetime
 import json
 import os
 import sys
@@ -27,10 +31,17 @@ def main():
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
     local = int(os.environ.get("LOCAL_RANK", "0"))
     ndev = torch.cuda.device_count()
-    dev = torch.device("cuda", local % ndev if backend == "gloo" else local)
+    shared_gpu = world > ndev
+    dev = torch.device("cuda", local % ndev if backend == "gloo" or shared_gpu else local)
     torch.cuda.set_device(dev)
     if backend == "nccl":
-        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+        if shared_gpu:
+            os.environ["NCCL_HOSTID"] = f"dcx-test-rank{rank}"
+            os.environ.setdefault("NCCL_SOCKET_IFNAME", "lo")
+            os.environ.setdefault("NCCL_IB_DISABLE", "1")
+        # a collective that cannot complete is aborted by the process group's watchdog after this long (well inside the test's
+        # own limit), which also stops RCCL's kernels instead of leaving them waiting on the GPU
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev, timeout=datetime.timedelta(minutes=3))
     else:
         dist.init_process_group("gloo", rank=rank, world_size=world)
 
@@ -72,7 +83,7 @@ def main():
         for s, res in enumerate(res_pipe):
             order = np.roll(np.arange(n_frames), s)
             bad_pipe += sum(not same(res[i], exp[order[i]]) for i in range(n_frames))
-        verdict = dict(backend=backend, world=world, devices=ndev, frames=n_frames,
+        verdict = dict(backend=backend, world=world, devices=ndev, shared_gpu=shared_gpu, frames=n_frames,
                        split=[shard_range(n_frames, r, world) for r in range(world)],
                        corners=int(sum(e.shape[0] for e in exp if e.ndim == 2)),
                        mismatched_single=int(bad_single), mismatched_pipelined=int(bad_pipe),

@@ -1,14 +1,14 @@
-"""Worker of tests/test_gpu_sharded.py::test_world8_*: one rank of an EIGHT-rank run of the product path (real HIP kernels).
+"""Worker of tests/test_gpu_sharded.py::test_world8_*: one rank of a multi-rank run of the product path (real HIP kernels).
 
 BASELINE configs[3] (bs=1024 320x240 over 8 GPUs) and configs[4] (bs=256 1280x960, 16 corners per frame, over 8 GPUs) at
-their true world size, as far as one GPU allows: eight gloo ranks time-slice the one visible GPU (RCCL needs one GPU per
-rank; with >= 8 GPUs visible pass backend "nccl").  Modes:
+their full global batch: eight RCCL ranks (backend "nccl") when eight GPUs are visible; on fewer GPUs the test starts four
+gloo ranks that time-slice one GPU, each with twice the per-GPU share.  Modes (per-rank counts at world 8 / world 4):
 
-  cfg4   every rank runs `infer_batches_sharded` on 1,024 frames of 320x240 (128 per rank = the per-GPU load of
-         configs[3]), two batches in flight, then on a ragged 1,021-frame batch (128 x5 + 127 x3);
-  cfg5   32 frames of 1280x960 with exactly 16 corners each, kmax = 16 (4 per rank: configs[4] reduced 8x in batch only);
-  cfg5full   configs[4] at its full size: 256 frames of 1280x960 (32 per rank, 12.6 GB of workspace per rank), exactly 16
-         corners in every frame, two batches in flight.
+  cfg4   every rank runs `infer_batches_sharded` on 1,024 frames of 320x240 (128 / 256 per rank), two batches in flight,
+         then on a ragged 1,021-frame batch (128 x5 + 127 x3 / 256 + 255 x3);
+  cfg5   32 frames of 1280x960 with exactly 16 corners each, kmax = 16 (4 / 8 per rank: configs[4] reduced 8x in batch only);
+  cfg5full   configs[4] at its full size: 256 frames of 1280x960 (32 / 64 per rank, 12.6 / 25 GB of workspace per rank),
+         exactly 16 corners in every frame, two batches in flight.
 
 Rank 0 compares frames of EVERY rank's shard (first, last and two inner frames; for the ragged batch the frames on both
 sides of every shard boundary) with the oracle and writes the verdict.  Frame i of a batch depends only on (kind, seed + i),
@@ -62,8 +62,9 @@ def main():
     sd_rn = W.synthetic_state_dict("refinenet", 1235)
     verdict = dict(mode=mode, backend=backend, world=world, devices=ndev)
     if mode == "cfg4":
-        n, h, w, kmax = 128 * world, 240, 320, 64      # the bench preset's pool (128 x 64 slots per rank): among 3,000 board frames a
-                                                       # few fire > 64 cells (up to ~100) -- no per-frame cap, they are refined like the rest
+        n, h, w, kmax = 1024, 240, 320, 64             # configs[3]'s global batch; 64 slots per frame of a rank's shard: among 3,000
+                                                       # board frames a few fire > 64 cells (up to ~100) -- no per-frame cap, they are
+                                                       # refined like the rest
         calib = torch.from_numpy(W.synthetic_frames("board", SEED, 32, h, w)).to(dev)      # same frames on every rank
         sd_dc = WL.calibrate_dustbin(W.synthetic_state_dict("detector", 1234), calib, dev)
         dc, rn = lModel(dcModel(16, sd_dc, dev)), lRefineNet(RefineNet(sd_rn, dev))
@@ -71,10 +72,10 @@ def main():
         # two full batches in flight (the second = frames of seed + 5000), then the ragged one as its own call
         full2 = local_batch("board", SEED + 5000, n, h, w, rank, world)
         res_a, res_b = list(infer_batches_sharded([full, full2], 16, dc, rn, kmax=kmax))
-        n_rag = n - 3                                                    # 1,021 at world 8: 128 x5 + 127 x3
+        n_rag = n - 3                                                    # 1,021: 128 x5 + 127 x3 at world 8
         rag = local_batch("board", SEED + 9000, n_rag, h, w, rank, world)
         (res_r,) = list(infer_batches_sharded([rag], 16, dc, rn, kmax=kmax))
-        # every rank's pool far too small (128 frames x 2 slots): all ranks see it in the gathered counts and repeat the batch
+        # every rank's pool far too small (its shard's frames x 2 slots): all ranks see it in the gathered counts and repeat the batch
         # collectively with the pool the first pass reported -- complete results, no exception
         (res_small,) = list(infer_batches_sharded([rag], 16, dc, rn, kmax=2))
         rerun_same = len(res_small) == len(res_r) and all(same(a, b) for a, b in zip(res_small, res_r))
@@ -108,21 +109,21 @@ def main():
             bad += not same(res_a[busiest], e)
             verdict.update(busiest_frame=dict(index=busiest, corners=int(counts[busiest]), identical=bool(same(res_a[busiest], e)),
                                               frames_over_64=int(sum(c > 64 for c in counts))),
-                           pool_per_rank=128 * kmax, overflow_rerun_identical=bool(rerun_same))
+                           pool_per_rank=n // world * kmax, overflow_rerun_identical=bool(rerun_same))
             verdict.update(frames=n, frames_ragged=n_rag, split=[shard_range(n, r, world) for r in range(world)],
                            split_ragged=[shard_range(n_rag, r, world) for r in range(world)],
                            results_returned=[len(res_a), len(res_b), len(res_r)], frames_checked=checked, corners_checked=corners,
                            mismatched=int(bad), mismatched_per_rank=per_rank,
                            mean_corners_per_frame=float(np.mean(counts)), max_corners=int(max(counts)))
     elif mode in ("cfg5", "cfg5full"):
-        per, h, w, kmax = (32 if mode == "cfg5full" else 4), 960, 1280, 16      # cfg5full: 8 x 32 = 256 frames = configs[4] itself
-        n = per * world
+        n, h, w, kmax = (256 if mode == "cfg5full" else 32), 960, 1280, 16      # cfg5full: 256 frames = configs[4] itself
+        per = n // world
         calib = torch.from_numpy(W.synthetic_frames("board4", SEED, 8, h, w)).to(dev)
         sd_dc = WL.calibrate_dustbin(W.synthetic_state_dict("detector", 1234), calib, dev)
         del calib
         dc, rn = lModel(dcModel(16, sd_dc, dev)), lRefineNet(RefineNet(sd_rn, dev))
         seed_of = lambda r: SEED + 100000 * (r + 1)
-        mine, kept = WL.select_fixed_k_frames("board4", seed_of(rank), per, h, w, 16, dc, dev, chunk=8 if per == 4 else 32,
+        mine, kept = WL.select_fixed_k_frames("board4", seed_of(rank), per, h, w, 16, dc, dev, chunk=8 if mode == "cfg5" else 32,
                                                  max_candidates=20000)
         kept_all = [None] * world
         dist.all_gather_object(kept_all, [int(k) for k in kept])       # candidate numbers every rank kept (frame = f(kind, seed + j))

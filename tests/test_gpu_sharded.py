@@ -1,12 +1,14 @@
 """The N>1 product path with REAL kernels: ranks launched with torch.distributed.run run
 `sharding.infer_frames_sharded` / `infer_batches_sharded` through the HIP pipeline and rank 0 compares every frame with
-the oracle.  gloo: two ranks share the one visible GPU; nccl (RCCL): one GPU per rank, skipped on a 1-GPU box."""
+the oracle.  gloo: two ranks share the one visible GPU; nccl (RCCL): one GPU per rank, or on a 1-GPU box two ranks on the one
+GPU joined by RCCL's socket transport."""
 import json
 import os
 import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -38,13 +40,19 @@ def _launch(backend, world, tmp_path):
     return v
 
 
+# Eight RCCL ranks (one per GPU) when eight GPUs are visible.  Otherwise four gloo ranks time-slice one GPU, so that together
+# with this test's own process no more than five processes hold that GPU at once.  The worker keeps the configs' global
+# batches, so each of the four ranks gets twice the per-GPU share.
+WORLD8 = 8 if torch.cuda.device_count() >= 8 else 4
+
+
 def _launch8(mode, tmp_path, timeout=700):
-    """Eight ranks; gloo on a 1-GPU box (the ranks time-slice the GPU), RCCL when eight GPUs are visible."""
-    backend = "nccl" if torch.cuda.device_count() >= 8 else "gloo"
+    """WORLD8 ranks: RCCL when eight GPUs are visible, else gloo (the ranks time-slice the GPU)."""
+    backend = "nccl" if WORLD8 == 8 else "gloo"
     out = str(tmp_path / f"world8_{mode}.json")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     env.pop("DCX_FORCE_CFG", None)
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8",
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={WORLD8}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(REPO, "tests", "sharded_world8_worker.py"), mode, backend, out]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
@@ -61,34 +69,38 @@ def _launch8(mode, tmp_path, timeout=700):
 
 
 def test_world8_cfg4_full_size_every_rank_checked(tmp_path):
-    """BASELINE configs[3] at its true world size: 1,024 frames of 320x240 over EIGHT ranks (128 each) through
+    """BASELINE configs[3] at its full size: 1,024 frames of 320x240 over WORLD8 ranks (128 each at eight ranks) through
     infer_batches_sharded, two batches in flight, plus the ragged 1,021-frame split; frames of every rank's shard vs the oracle."""
     v = _launch8("cfg4", tmp_path)
-    assert v["world"] == 8 and v["frames"] == 1024 and v["results_returned"] == [1024, 1024, 1021]
-    assert [b - a for a, b in v["split"]] == [128] * 8
-    assert [b - a for a, b in v["split_ragged"]] == [128] * 5 + [127] * 3
-    assert v["mismatched"] == 0 and v["mismatched_per_rank"] == [0] * 8 and v["frames_checked"] >= 8 * 10
+    world, per = WORLD8, 1024 // WORLD8
+    assert v["world"] == world and v["frames"] == 1024 and v["results_returned"] == [1024, 1024, 1021]
+    assert [b - a for a, b in v["split"]] == [per] * world
+    assert [b - a for a, b in v["split_ragged"]] == [per] * (world - 3) + [per - 1] * 3
+    assert v["mismatched"] == 0 and v["mismatched_per_rank"] == [0] * world and v["frames_checked"] >= world * 10
     assert v["corners_checked"] > 500
     # round 5: the pool is sized for 64 corners per frame on average and has no per-frame cap: the busiest of the 1,024 frames
     # (some fire more than 64 cells) is complete and identical to the oracle; pools that are far too small are repeated collectively
-    assert v["pool_per_rank"] == 128 * 64 and v["busiest_frame"]["identical"] and v["busiest_frame"]["corners"] == v["max_corners"]
+    assert v["pool_per_rank"] == per * 64 and v["busiest_frame"]["identical"] and v["busiest_frame"]["corners"] == v["max_corners"]
     assert v["overflow_rerun_identical"]
 
 
 def test_world8_cfg5_reduced_every_rank_checked(tmp_path):
-    """BASELINE configs[4] reduced in batch only: 8 ranks x 4 frames of 1280x960, exactly 16 corners per frame, kmax = 16."""
+    """BASELINE configs[4] reduced in batch only: 32 frames of 1280x960 over WORLD8 ranks, exactly 16 corners per frame, kmax = 16."""
     v = _launch8("cfg5", tmp_path)
-    assert v["world"] == 8 and v["frames"] == 32 and v["all_frames_have_16"] and v["corners_per_frame_seen"] == [16]
-    assert v["mismatched"] == 0 and v["mismatched_per_rank"] == [0] * 8 and v["frames_checked"] >= 16
+    world = WORLD8
+    assert v["world"] == world and v["frames"] == 32 and v["all_frames_have_16"] and v["corners_per_frame_seen"] == [16]
+    assert v["mismatched"] == 0 and v["mismatched_per_rank"] == [0] * world and v["frames_checked"] >= 2 * world
 
 
 def test_world8_cfg5_full_size_every_rank_checked(tmp_path):
-    """BASELINE configs[4] at its FULL size: 256 frames of 1280x960 over eight ranks (32 each; 8 x 12.6 GB of workspace on the
-    one 288 GB GPU), exactly 16 corners in every frame, kmax = 16, two batches in flight; three frames of EVERY rank's shard vs the
-    oracle."""
+    """BASELINE configs[4] at its FULL size: 256 frames of 1280x960 over WORLD8 ranks (32 each at eight ranks: 12.6 GB of workspace
+    per rank; 64 each at four ranks on one GPU: 4 x 25 GB of its 288 GB), exactly 16 corners in every frame, kmax = 16, two batches
+    in flight; three frames of EVERY rank's shard vs the oracle."""
     v = _launch8("cfg5full", tmp_path, timeout=1500)
-    assert v["world"] == 8 and v["frames"] == 256 and v["all_frames_have_16"] and v["corners_per_frame_seen"] == [16]
-    assert v["mismatched"] == 0 and v["mismatched_per_rank"] == [0] * 8 and v["frames_checked"] == 24 and v["corners_checked"] == 24 * 16
+    world = WORLD8
+    assert v["world"] == world and v["frames"] == 256 and v["all_frames_have_16"] and v["corners_per_frame_seen"] == [16]
+    assert v["mismatched"] == 0 and v["mismatched_per_rank"] == [0] * world and v["frames_checked"] == 3 * world
+    assert v["corners_checked"] == 3 * world * 16
 
 
 def test_two_ranks_on_one_gpu_gloo_real_kernels(tmp_path):
@@ -97,9 +109,11 @@ def test_two_ranks_on_one_gpu_gloo_real_kernels(tmp_path):
     assert v["mismatched_single"] == 0 and v["mismatched_pipelined"] == 0 and v["mismatched_bgr"] == 0 and v["one_frame_ok"] and v["corners"] > 50
 
 
-@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="RCCL needs one GPU per rank; this box has one")
 def test_two_ranks_rccl_real_kernels(tmp_path):
+    """Two RCCL ranks through the product path.  One GPU per rank when two are visible; on a 1-GPU box both ranks compute on the
+    one GPU and RCCL joins them through its socket transport on the loopback interface (tests/sharded_gpu_worker.py)."""
     v = _launch("nccl", 2, tmp_path)
+    assert v["world"] == 2 and v["split"] == [[0, 6], [6, 11]] and v["shared_gpu"] == (torch.cuda.device_count() < 2)
     assert v["mismatched_single"] == 0 and v["mismatched_pipelined"] == 0 and v["mismatched_bgr"] == 0 and v["one_frame_ok"]
 
 
@@ -163,3 +177,22 @@ def test_bench_single_gpu_line_has_no_rank_block():
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and "ranks" not in line and "gather_overlapped" not in line and "roofline" in line
+
+
+def test_bench_dump_outputs_are_reproducible_and_steps_are_timed(tmp_path):
+    """--dump-outputs writes the corner lists of the last timed step (float64 .npy); the inputs are seeded, so two runs write the
+    same arrays -- here with different --steps, and each run times exactly the steps it was asked for (one GPU time per batch)."""
+    dumps = []
+    for steps in (3, 7):
+        d = tmp_path / f"steps{steps}"
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                            "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(d)], env=_bare_env(), capture_output=True,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == steps and line["step_breakdown"]["gpu_ms_per_batch"]["n"] == steps
+        corners, counts = np.load(d / "corners.npy"), np.load(d / "corners_per_frame.npy")
+        assert corners.dtype == np.float64 and counts.dtype == np.float64 and counts.shape == (line["config"]["batch_per_gpu"],)
+        assert corners.shape == (int(counts.sum()), 3) and corners.shape[0] > 8 * counts.shape[0]
+        dumps.append((corners, counts))
+    assert all(np.array_equal(a, b) for a, b in zip(*dumps))

@@ -132,6 +132,26 @@ def test_unpack_results_sorting_and_dtypes():
     assert res[0].dtype == np.int64 and np.array_equal(res[0], [[16, 17, 2], [8, 9, 5], [24, 25, 5]])
 
 
+def test_bench_dump_outputs_layout(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last timed step's per-frame corner rows as float64 .npy files (rows concatenated in frame
+    order + the count of every frame, NaN for a frame that overflowed the pool); over the size limit, a fixed seeded sample."""
+    import bench
+    res = [np.array([[1.5, 2.25, 3.0], [4.0, 5.0, 7.0]]), np.array([]), None, np.array([[8.0, 9.5, 0.0]])]
+    bench.dump_outputs(str(tmp_path / "a"), res)
+    assert sorted(os.listdir(tmp_path / "a")) == ["corners.npy", "corners_per_frame.npy"]
+    corners, counts = np.load(tmp_path / "a" / "corners.npy"), np.load(tmp_path / "a" / "corners_per_frame.npy")
+    assert corners.dtype == np.float64 and np.array_equal(corners, [[1.5, 2.25, 3], [4, 5, 7], [8, 9.5, 0]])
+    assert counts.dtype == np.float64 and np.array_equal(counts, [2, 0, np.nan, 1], equal_nan=True)
+    big = [np.arange(3000, dtype=np.float64).reshape(1000, 3) + 3000 * i for i in range(4)]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 24 * 100 + 4 * 8)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    s = np.load(tmp_path / "b" / "corners.npy")
+    assert s.shape == (100, 3) and np.array_equal(s, np.load(tmp_path / "c" / "corners.npy"))       # fixed seed: same rows
+    assert np.all(np.diff(s[:, 0]) > 0) and np.all(s[:, 0] % 3 == 0)                                 # whole rows, in order
+    assert np.array_equal(np.load(tmp_path / "b" / "corners_per_frame.npy"), [1000] * 4)
+
+
 def test_bgr2gray_host():
     from deepcharuco_amd.imgproc import bgr2gray
     d = np.load(os.path.join(REPO, "tests", "golden", "bgr2gray_formula.npz"))
@@ -387,16 +407,15 @@ def test_c_restatement_agrees_with_torch_fp32():
             assert np.abs(got - ref.numpy()).max() <= 2e-5, (fam, cin, cout)
 
 
-def test_conv_kernels_do_not_spill():
+def test_conv_kernels_do_not_spill(tmp_path):
     """The Winograd kernels are written around hipcc's register allocation (accumulators pinned to AGPRs with inline asm,
     one basic block per unit): a change that makes hipcc shuffle accumulators or spill shows up as a large slowdown only
     on the GPU.  This guards the budget at build time: no VGPR spills in any MFMA kernel of the dispatch table, and no
     scratch / accumulator moves inside the unit loops of the Winograd kernels."""
     import re
     import subprocess
-    import tempfile
     src = os.path.join(REPO, "deepcharuco_amd", "csrc", "dcx_conv_mfma.hip")
-    out = os.path.join(tempfile.gettempdir(), "dcx_conv_budget.s")
+    out = str(tmp_path / "dcx_conv_budget.s")      # per run: a fixed name in the shared temp dir may belong to another user
     subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-mllvm",
                     "-pragma-unroll-threshold=200000", "-S", src, "-o", out], check=True, capture_output=True)
     asm = open(out).read()
