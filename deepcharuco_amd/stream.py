@@ -8,7 +8,9 @@ copied back; the host only ever waits on the oldest batch's completion event.  R
 arrays ``infer_batch`` returns (frames are independent).  With ``pnp=dict(col_count=, row_count=, square_len=,
 camera_matrix=, dist_coeffs=)`` the pipeline gets the reference callers' last stage too (pose_estimation.py:61-63):
 when a batch is retired its frames' ``solve_pnp`` calls are submitted to host threads and run while the GPU works on
-the next batches; ``run`` then yields ``(ticket, results, poses)``.
+the next batches; ``run`` then yields ``(ticket, results, poses)``.  ``pnp_device=True`` solves the poses on the GPU instead
+(``pnp.solve_pnp_pool``, no OpenCV): the kernel reads the batch's corner pool on the compute stream right after the pipeline and
+the poses come back through pinned memory with the corners.
 """
 from __future__ import annotations
 
@@ -20,16 +22,19 @@ import numpy as np
 import torch
 
 from .inference import DEFAULT_KMAX, infer_batch, infer_batch_device, packed_len, solve_pnp_submit, unpack_results
+from .pnp import POSE_WORDS, solve_pnp_batch_device, solve_pnp_pool, unpack_poses
 
 
 class FrameStream:
     def __init__(self, dust_bin_ids: int, deepc, refinenet=None, batch: int = 32, height: int = 240,
                  width: int = 320, kmax: int = DEFAULT_KMAX, depth: int = 2, pnp: Optional[dict] = None,
-                 compute_streams: int = 1, bgr: bool = False, h2d_on_compute: Optional[bool] = None):
+                 compute_streams: int = 1, bgr: bool = False, h2d_on_compute: Optional[bool] = None, pnp_device: bool = False):
         """``bgr=True``: the stream is fed (n,H,W,3) BGR frames, as the reference's callers hold them (pose_estimation.py:53-59);
         the colour conversion of inference.py:40 happens on the device inside the first layer's load.  ``kmax``: the AVERAGE
         number of corners per frame the buffers are sized for -- the corner pool of a batch holds ``batch * kmax`` corners and a
-        single frame may use any share of it."""
+        single frame may use any share of it.  ``pnp_device=True`` (with ``pnp``): the poses are solved on the GPU
+        (``solve_pnp_pool`` enqueued behind the pipeline on the same stream, into a per-slot buffer copied to pinned memory before
+        the batch's completion event) and handed out resolved, without OpenCV; the default keeps the host-thread stage."""
         det = deepc.model if hasattr(deepc, "model") else deepc
         self.dev = det.device
         self.dust_bin_ids, self.deepc, self.refinenet = dust_bin_ids, deepc, refinenet
@@ -40,6 +45,7 @@ class FrameStream:
         # that mode); with one compute stream the separate copy stream is 0.7 % ahead (profiles/experiments/r05_two_streams_with_uploads.md)
         self.h2d_on_compute = compute_streams > 1 if h2d_on_compute is None else bool(h2d_on_compute)
         self.pnp = pnp
+        self.pnp_device = bool(pnp_device) and pnp is not None
         if not (1 <= compute_streams <= depth):
             raise ValueError("compute_streams must be between 1 and depth")
         n_out = packed_len(batch, self.pool)
@@ -59,6 +65,11 @@ class FrameStream:
             self.ev_h2d = [torch.cuda.Event() for _ in range(depth)]
             self.ev_free = [torch.cuda.Event() for _ in range(depth)]     # compute finished reading dev_in[s]
             self.ev_done = [torch.cuda.Event() for _ in range(depth)]
+            if self.pnp_device:
+                self.dev_pnp = [(torch.empty((batch,), dtype=torch.int32, device=self.dev),
+                                 torch.empty((batch, POSE_WORDS), dtype=torch.float64, device=self.dev)) for _ in range(depth)]
+                self.pin_pnp = [(torch.empty((batch,), dtype=torch.int32).pin_memory(),
+                                 torch.empty((batch, POSE_WORDS), dtype=torch.float64).pin_memory()) for _ in range(depth)]
         self._pending: List[Optional[Tuple[int, int, np.ndarray]]] = [None] * depth   # (ticket, n_frames, host frames)
         self._ticket = 0
 
@@ -72,6 +83,11 @@ class FrameStream:
         if need > self.pool:         # rare: the batch fired more cells than its pool holds -> exact re-run with the pool it asked for
             warnings.warn(f"a batch produced {need} corners > pool={self.pool} (batch x kmax); re-running it with pool={need}")
             res = infer_batch(frames, self.dust_bin_ids, self.deepc, self.refinenet, pool=need)
+            if self.pnp_device:      # the device poses of this slot were solved on the truncated pool
+                return ticket, res, solve_pnp_batch_device(res, device=self.dev, **self.pnp)
+        if self.pnp_device:
+            st, pose = self.pin_pnp[slot]
+            return ticket, res, unpack_poses(st.numpy()[:n], pose.numpy()[:n])
         if self.pnp is not None:     # host stage: futures now, resolved when the batch is handed out
             return ticket, res, solve_pnp_submit(res, **self.pnp)
         return ticket, res
@@ -105,15 +121,20 @@ class FrameStream:
                 infer_batch_device(self.dev_in[slot], self.dust_bin_ids, self.deepc, self.refinenet, out=self.dev_out[slot],
                                    pool=self.pool)
                 self.ev_free[slot].record(compute)
+                if self.pnp_device:
+                    solve_pnp_pool(self.dev_out[slot], self.batch, self.pool, self.refinenet is not None, out=self.dev_pnp[slot],
+                                   **self.pnp)
                 self.pin_out[slot].copy_(self.dev_out[slot], non_blocking=True)
+                if self.pnp_device:
+                    for h, d in zip(self.pin_pnp[slot], self.dev_pnp[slot]):
+                        h.copy_(d, non_blocking=True)
                 self.ev_done[slot].record(compute)
         self._pending[slot] = (self._ticket, n, frames_gray)
         self._ticket += 1
         return retired
 
-    @staticmethod
-    def _resolve(r):
-        return r if len(r) == 2 else (r[0], r[1], [f.result() for f in r[2]])
+    def _resolve(self, r):
+        return r if len(r) == 2 or self.pnp_device else (r[0], r[1], [f.result() for f in r[2]])
 
     def flush(self) -> Iterator[Tuple]:
         order = sorted((p[0], s) for s, p in enumerate(self._pending) if p is not None)

@@ -180,6 +180,32 @@ int dcx_infer_batch(const dcx_detector* det, const dcx_refiner* rf,
                     void* d_ws, size_t ws_bytes,
                     int32_t* d_counts, int32_t* d_starts, int32_t* d_rows, float* d_xy, float* d_conf, void* stream);
 
+/* ---- solve_pnp inference.py:15-29 (cv2.solvePnP, default flags = SOLVEPNP_ITERATIVE) on the device, per frame of a pool --
+ * Reads a corner pool in place, in the layout dcx_infer_batch writes (or a caller-built one: counts / starts + the id column of
+ * rows + xy): frame b's points are the slots [d_starts[b], d_starts[b] + d_counts[b]); object point of id i =
+ * ((1 + i % (row_count-1)) * square_len, (1 + i / (row_count-1)) * square_len, 0) rounded to float32 like the reference's
+ * np.float32 table (inference.py:20-26; square_len is a double so that the rounding matches); image point = d_xy (RefineNet's
+ * corners) or, with d_xy == NULL, the integer x, y of d_rows (inference.py:27).  All arithmetic fp64: undistortPoints (5 rounds),
+ * planar DLT homography + OpenCV's decomposition, Levenberg-Marquardt on the pixel reprojection error (<= 20 steps, stop at
+ * |dp|/|p| < FLT_EPSILON); deepcharuco_amd/pnp.py restates the steps (solve_pnp_host).  One wavefront per frame, grid = batch.
+ * h_camera9: K row major, K[0][1] must be 0 (DCX_E_ARG otherwise); h_dist: n_dist = 0, 4, 5 or 8 OpenCV coefficients
+ * (12 / 14 -> DCX_E_ARG).  Both are copied into the kernel arguments at the call (a captured hipGraph keeps them).
+ * d_status int32 [B]: DCX_PNP_*.  d_pose f64 [B][8] = rvec(3), tvec(3), rms reprojection error (px), accepted LM steps; zeros
+ * unless DCX_PNP_OK.  Unlike cv2.solvePnP, collinear points, a rank-deficient homography, a point behind the camera or a
+ * non-finite result give DCX_PNP_DEGENERATE / DCX_PNP_NONFINITE instead of a pose.                                        */
+#define DCX_PNP_OK          0
+#define DCX_PNP_TOO_FEW     1   /* fewer than 4 points (inference.py:16-17) */
+#define DCX_PNP_TRUNCATED   2   /* starts[b] + counts[b] > pool: the frame's corners did not all fit the pool */
+#define DCX_PNP_BAD_ID      3   /* an id outside [0, (col_count-1)*(row_count-1)): the reference raises IndexError */
+#define DCX_PNP_DEGENERATE  4
+#define DCX_PNP_NONFINITE   5
+int dcx_solve_pnp_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows,
+                       const float* d_xy /* NULL = use integer rows x,y */, int batch, int pool,
+                       int col_count, int row_count, double square_len,
+                       const double* h_camera9, const double* h_dist, int n_dist,
+                       int32_t* d_status, double* d_pose /* [B][8] = rvec3, tvec3, rms_px, iterations */,
+                       void* stream);
+
 /* ---- stage-level entry point for kernel tests / roofline measurement -------------------
  * One 3x3 (or 1x1) convolution + bias [+ eval-BN + ReLU] [+ 2x2 max-pool] on C4 tensors
  * using the same MFMA kernel the networks use.  h_* are host arrays in PyTorch layout;
