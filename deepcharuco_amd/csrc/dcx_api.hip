@@ -299,6 +299,7 @@ extern "C" int dcx_detector_create(dcx_detector** out, const float* const* t, in
     if (n_tensors != 64) return DCX_E_ARG;   // 10 conv+BN (6 tensors) + 2 raw convs (2 tensors)
     for (int i = 0; i < n_tensors; ++i)
         if (!t[i]) return DCX_E_ARG;
+    if (const int rc = dcx_xcd_init()) return rc;   // the launchers only read the device's XCD table: it must exist first
     dcx_detector* d = new (std::nothrow) dcx_detector();
     if (!d) return (int)hipErrorOutOfMemory;
     d->n_ids = n_ids;
@@ -445,6 +446,7 @@ extern "C" int dcx_refiner_create(dcx_refiner** out, const float* const* t, int 
     if (n_tensors != 68) return DCX_E_ARG;   // 11 conv+BN (6 tensors) + convPb (2 tensors)
     for (int i = 0; i < n_tensors; ++i)
         if (!t[i]) return DCX_E_ARG;
+    if (const int rc = dcx_xcd_init()) return rc;
     dcx_refiner* r = new (std::nothrow) dcx_refiner();
     if (!r) return (int)hipErrorOutOfMemory;
     auto hc = [&](int base) { return HostConv{t[base], t[base + 1], t[base + 2], t[base + 3], t[base + 4], t[base + 5]}; };
@@ -656,6 +658,8 @@ extern "C" int dcx_infer_batch(const dcx_detector* det, const dcx_refiner* rf, c
                        d_counts, d_starts, d_rows, d_xy, d_conf, s, true);
 }
 
+extern "C" int dcx_stream_synchronize(void* stream) { return (int)hipStreamSynchronize((hipStream_t)stream); }
+
 extern "C" int dcx_set_timing(int enabled) { g_timing = enabled != 0; return 0; }
 extern "C" int dcx_get_timing(void) { return g_timing ? 1 : 0; }
 
@@ -678,6 +682,7 @@ extern "C" int dcx_conv_layer(const float* d_in, int n, int cin, int hin, int wi
     const bool bn = h_g != nullptr;
     if (bn != (relu != 0)) return DCX_E_ARG;   // kernels implement conv+BN+ReLU or raw conv+bias
     if (bn && (!h_be || !h_mu || !h_var)) return DCX_E_ARG;
+    if (const int rc = dcx_xcd_init()) return rc;
     DevLayer l;
     int rc = make_layer(HostConv{h_w, h_b, h_g, h_be, h_mu, h_var}, cin, cout, ksize, &l, ups != 0);
     if (rc) return rc;

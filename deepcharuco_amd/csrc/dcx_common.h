@@ -73,6 +73,9 @@ struct DcxConvArgs {
 // Picks a tile configuration for (ho, wo, cout_pad, pool, epi, ks) and launches.
 // Returns 0 / DCX_E_SHAPE / hipError_t.
 int dcx_launch_conv_mfma(DcxConvArgs a, int ks, int pool, int epi, hipStream_t stream);
+// Creates the current device's XCD share table (equal shares) if it does not exist yet: allocates and copies synchronously, so it
+// runs at set-up (dcx_detector_create / dcx_refiner_create), never inside a launcher.  Returns 0 / hipError_t.
+int dcx_xcd_init();
 // Rounds cout up to what dcx_launch_conv_mfma needs for cout_pad.
 int dcx_conv_cout_pad(int cout);
 // Number of partial arg-max slots per image the DCX_EPI_HEAT launch will write for an (ho, wo) heat-map (size of part_*);

@@ -593,7 +593,7 @@ constexpr int DCX_MAX_DEVICES = 64;
 int dcx_current_device();    // hipGetDevice() clamped to [0, DCX_MAX_DEVICES)
 int dcx_occupancy_override();
 int dcx_xcd_walk_enabled();   // DCX_XCD_WALK=0 keeps the flat item walk (A/B runs)
-void dcx_fill_xcd_cum(DcxConvArgs& a);   // the current device's cumulative XCD weights (dcx_conv_mfma.hip)
+int dcx_fill_xcd_cum(DcxConvArgs& a);    // the current device's cumulative XCD weights (dcx_conv_mfma.hip); 0 / hipError_t
 
 template <class C>
 static int dcx_conv_launch_cfg(DcxConvArgs a, hipStream_t stream) {
@@ -606,7 +606,7 @@ static int dcx_conv_launch_cfg(DcxConvArgs a, hipStream_t stream) {
     const long resident = (long)dcx_device_cu_count() * (occ_env > 0 && occ_env < C::OCC ? occ_env : C::OCC);   // persistent workgroups
     const long blocks = items < resident ? items : resident;
     a.xcd_walk = dcx_xcd_walk_enabled() && blocks == resident && (resident & 7) == 0 ? 1 : 0;
-    dcx_fill_xcd_cum(a);
+    if (const int rc = dcx_fill_xcd_cum(a)) return rc;
     static bool attr_set[DCX_MAX_DEVICES] = {};      // the attribute is per device (multi-GPU processes)
     const int dev_i = dcx_current_device();
     if (!attr_set[dev_i]) {

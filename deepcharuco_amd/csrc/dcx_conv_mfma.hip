@@ -8,6 +8,8 @@
 
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
+#include <mutex>
 #include <vector>
 
 namespace {
@@ -342,12 +344,14 @@ namespace {
 // Device tables of cumulative shares, [kXcdTables][16] ints per device, used round robin: a table is written ONCE (before any launch
 // can read it) and never modified afterwards, so every workgroup of a launch -- and every replay of a hipGraph captured with it -- sees
 // one partition even while the host installs new weights; a slot is only reused after kXcdTables further weight changes.
+// Everything but g_xcd_cur is touched only under g_xcd_mutex; the launchers read g_xcd_cur alone, without the lock.
 constexpr int kXcdTables = 256;
+std::mutex g_xcd_mutex;
 int* g_xcd_tab[DCX_MAX_DEVICES] = {};
 int g_xcd_next[DCX_MAX_DEVICES] = {};
-const int* g_xcd_cur[DCX_MAX_DEVICES] = {};
+std::atomic<const int*> g_xcd_cur[DCX_MAX_DEVICES] = {};
 float g_xcd_w[DCX_MAX_DEVICES][8];
-int xcd_set(int dev, const float* w8) {
+int xcd_set_locked(int dev, const float* w8) {
     if (g_xcd_tab[dev] == nullptr)
         DCX_CHECK_HIP(hipMalloc((void**)&g_xcd_tab[dev], sizeof(int) * 16 * kXcdTables));
     double sum = 0.0;
@@ -361,16 +365,24 @@ int xcd_set(int dev, const float* w8) {
     }
     int* slot = g_xcd_tab[dev] + 16 * (g_xcd_next[dev]++ % kXcdTables);
     DCX_CHECK_HIP(hipMemcpy(slot, cum, sizeof(cum), hipMemcpyHostToDevice));      // synchronous: complete before any launch that uses it
-    g_xcd_cur[dev] = slot;
+    g_xcd_cur[dev].store(slot, std::memory_order_release);
     return 0;
+}
+int xcd_set(int dev, const float* w8) {
+    std::lock_guard<std::mutex> lk(g_xcd_mutex);
+    return xcd_set_locked(dev, w8);
 }
 }  // namespace
 
-void dcx_fill_xcd_cum(DcxConvArgs& a) {
+int dcx_xcd_init() {
     const int dev = dcx_current_device();
-    if (g_xcd_cur[dev] == nullptr) (void)xcd_set(dev, nullptr);      // first launch on this device (never under graph capture: the
-                                                                      // callers warm up eagerly first)
-    a.xcd_cum = g_xcd_cur[dev];
+    std::lock_guard<std::mutex> lk(g_xcd_mutex);
+    return g_xcd_cur[dev].load(std::memory_order_relaxed) != nullptr ? 0 : xcd_set_locked(dev, nullptr);
+}
+
+int dcx_fill_xcd_cum(DcxConvArgs& a) {
+    a.xcd_cum = g_xcd_cur[dcx_current_device()].load(std::memory_order_acquire);
+    return a.xcd_cum != nullptr ? 0 : (int)hipErrorNotInitialized;      // dcx_xcd_init has not run on this device
 }
 
 // w8: relative speeds of XCD 0..7 of the CURRENT device (any positive scale; NULL = equal).  Weights further than 25 % from equal
@@ -385,8 +397,10 @@ extern "C" int dcx_set_xcd_weights(const float* w8) {
 }
 extern "C" int dcx_get_xcd_weights(float* w8) {
     if (!w8) return DCX_E_ARG;
+    const int rc = dcx_xcd_init();
+    if (rc) return rc;
     const int dev = dcx_current_device();
-    if (g_xcd_cur[dev] == nullptr) { const int rc = xcd_set(dev, nullptr); if (rc) return rc; }
+    std::lock_guard<std::mutex> lk(g_xcd_mutex);
     for (int x = 0; x < 8; ++x) w8[x] = 8.0f * g_xcd_w[dev][x];      // 1.0 = an equal share
     return 0;
 }
@@ -433,8 +447,12 @@ extern "C" int dcx_calibrate_xcd(int rounds, float* w8_out, void* stream) {
     a.out_cq_total = c / 4; a.cout_pad = c; a.cout_quads = c / 4; a.cout_real = c;
     const int dev = dcx_current_device();
     float keep[8];
-    for (int x = 0; x < 8; ++x) keep[x] = g_xcd_cur[dev] != nullptr ? g_xcd_w[dev][x] : 0.125f;
-    (void)xcd_set(dev, nullptr);                             // measure with equal shares
+    {
+        std::lock_guard<std::mutex> lk(g_xcd_mutex);
+        for (int x = 0; x < 8; ++x) keep[x] = g_xcd_cur[dev].load(std::memory_order_relaxed) != nullptr ? g_xcd_w[dev][x] : 0.125f;
+        const int rc = xcd_set_locked(dev, nullptr);         // measure with equal shares
+        if (rc) { cleanup(); return rc; }
+    }
     double speed[8] = {};
     int rc = 0, used = 0;
     for (int r = 0; r < rounds + 2 && rc == 0; ++r) {

@@ -626,7 +626,7 @@ static int dcx_conv_wino2h_launch_cfg(DcxConvArgs a, hipStream_t stream) {
     const long resident = (occ_env == 1 ? 1L : 2L) * dcx_device_cu_count();
     const long blocks = items < resident ? items : resident;
     a.xcd_walk = dcx_xcd_walk_enabled() && blocks == resident && (resident & 7) == 0 ? 1 : 0;
-    dcx_fill_xcd_cum(a);
+    if (const int rc = dcx_fill_xcd_cum(a)) return rc;
     {   // cout tile outermost where the layer's transformed weights would otherwise thrash the XCDs' L2 (DCX_CT_OUTER=0/1 forces it)
         static int force = -2;
         if (force == -2) { const char* e = getenv("DCX_CT_OUTER"); force = e ? atoi(e) : -1; }

@@ -391,7 +391,7 @@ static int dcx_conv_wino2hs_launch_cfg(DcxConvArgs a, hipStream_t stream) {
     const long resident = (long)C::OCC * dcx_device_cu_count();
     const long blocks = items < resident ? items : resident;
     a.xcd_walk = dcx_xcd_walk_enabled() && blocks == resident && (resident & 7) == 0 ? 1 : 0;
-    dcx_fill_xcd_cum(a);
+    if (const int rc = dcx_fill_xcd_cum(a)) return rc;
     a.ct_outer = 0;
     static bool attr_set[DCX_MAX_DEVICES] = {};
     const int dev_i = dcx_current_device();

@@ -8,8 +8,10 @@ H2D of the frame from pinned memory, BGR->gray on the device (``dcx_bgr2gray``),
 and replays it per call: one launch from the host instead of ~30.  Results are those of ``infer_batch`` (same kernels,
 same order); a call whose frames fire more cells than the captured corner pool holds falls back to the eager path, which
 re-runs with a pool of the right size.  BGR frames are converted inside the first layer's load (``DCX_PIX_BGR8``), so the graph
-holds no separate colour-conversion node.  A pipeline owns its pinned / device buffers and its stream.  Locking is PER DEVICE:
-replays on one GPU are serialised by that GPU's lock (concurrent ``infer_image`` callers never share staging buffers
+holds no separate colour-conversion node.  A pipeline owns its pinned / device buffers, its stream and the models' weights its
+launches read (``NativeWeights``): a model that is reloaded, moved or destroyed retires its pipelines, and the weights they were
+captured with are destroyed only with their graph, under the locks of all devices -- never while a replay is in flight.
+Locking is PER DEVICE: replays on one GPU are serialised by that GPU's lock (concurrent ``infer_image`` callers never share staging buffers
 mid-flight), replays on different GPUs of one process run concurrently; a CAPTURE (and the destruction of a graph) takes the
 locks of all devices, because capturing while another thread replays hung the HIP runtime in testing -- callers that want
 concurrency on one GPU across threads use ``infer_batch_device`` on their own streams.  The graph freezes the kernel
@@ -30,6 +32,7 @@ import torch
 
 from . import _lib
 from .inference import DEFAULT_KMAX, PIXEL_FORMATS, infer_batch, launch_pipeline, packed_len, unpack_results
+from .models._handles import unwrap
 
 
 class _DeviceLocks:
@@ -112,18 +115,17 @@ _locks = _DeviceLocks()
 class GraphedPipeline:
     def __init__(self, dust_bin_ids: int, deepc, refinenet=None, batch: int = 1, height: int = 240, width: int = 320,
                  kmax: int = DEFAULT_KMAX, bgr: bool = True, zero_copy: Optional[int] = None):
-        det = deepc.model if hasattr(deepc, "model") else deepc
-        ref = None if refinenet is None else (refinenet.model if hasattr(refinenet, "model") else refinenet)
+        det, ref = unwrap(deepc), unwrap(refinenet)
         self.dev = det.device
         self.dust_bin_ids = dust_bin_ids
         # weak references to the inner models: the pipeline lives in a cache ON the detector, a strong reference back would be a
         # cycle that only the cyclic GC frees (~25 MB of workspace + pinned buffers per shape); with weak ones the graphs die with
         # the model by reference count
         self._det, self._ref = weakref.ref(det), (None if ref is None else weakref.ref(ref))
-        # the C handles the graph's kernel arguments point into: a replay first checks that the models still own exactly these
-        # (a reload / .to() / destruction frees the weights the captured launches read)
-        self._det_handle = det.handle.value
-        self._ref_handle = None if ref is None else ref.handle.value
+        # the native handles the graph's kernel arguments point into, as their owners (NativeWeights), held strongly: a reload /
+        # .to() / destruction of a model only drops the model's reference, so they live until the pipeline is closed and drained
+        self._det_handle = det._weights
+        self._ref_handle = None if ref is None else ref._weights
         self.batch, self.h, self.w, self.kmax, self.bgr = batch, height, width, kmax, bgr
         self.pool = batch * kmax
         self.zero_copy = int(os.environ.get("DCX_GRAPH_ZEROCOPY", "2")) if zero_copy is None else int(zero_copy)
@@ -159,15 +161,16 @@ class GraphedPipeline:
         self._rows_np = o[2 * b:2 * b + 4 * pool].reshape(pool, 4)
         self._xy_np = o[2 * b + 4 * pool:2 * b + 6 * pool].view(np.float32).reshape(pool, 2)
         with _cache_lock:
-            _live.add(self)           # every pipeline that exists, cached or evicted-but-still-held (drop_graphs_of_* close them all)
+            _live.add(self)           # every pipeline that exists, cached or evicted-but-still-held (drop_graphs_of closes them all)
 
     def _models_unchanged(self) -> bool:
+        """The models still hold the weights this graph was captured with (not reloaded, moved or destroyed since)."""
         det = self._det()
-        if det is None or det._handle is None or det._handle.value != self._det_handle:
+        if det is None or det._weights is not self._det_handle:
             return False
         if self._ref is not None:
             ref = self._ref()
-            if ref is None or ref._handle is None or ref._handle.value != self._ref_handle:
+            if ref is None or ref._weights is not self._ref_handle:
                 return False
         return True
 
@@ -209,7 +212,7 @@ class GraphedPipeline:
             graph, in_np, out_np = self.graph, self._in_np, self._out_np
             if graph is None:
                 raise ReferenceError("this GraphedPipeline has been closed (its models were released)")
-            if not self._models_unchanged():      # reloaded / moved / destroyed since the capture: the graph points at freed weights
+            if not self._models_unchanged():      # reloaded / moved / destroyed since the capture: stale weights
                 self.close()
                 raise ReferenceError("the models this graph was captured with have been released or reloaded")
             if frames.shape != in_np.shape or frames.dtype != np.uint8:
@@ -246,15 +249,16 @@ class GraphedPipeline:
 
     def close(self) -> None:
         """Retire the pipeline: later ``run`` calls raise ReferenceError.  Never blocks and never destroys anything itself -- the
-        hipGraph and the buffers move to a graveyard that is emptied only by a thread holding the locks of ALL devices
-        (``_drain``), so hipGraphExecDestroy / hipFree can not overlap a replay or a capture, whichever thread drops the last
-        reference (``__del__`` comes here too) and whatever that thread is in the middle of."""
+        hipGraph, the buffers and the models' weights it was captured with move to a graveyard that is emptied only by a thread
+        holding the locks of ALL devices (``_drain``), so hipGraphExecDestroy / hipFree / dcx_*_destroy can not overlap a replay or
+        a capture, whichever thread drops the last reference (``__del__`` comes here too) and whatever that thread is doing."""
         graph = getattr(self, "graph", None)
         if graph is None:
             return
         self.graph = None
-        _graveyard.append((graph, self.ws, self.dev_in, self.out_dev, self.pin_in, self.pin_out, self.stream))
-        self.ws = self.dev_in = self.out_dev = self.pin_in = self.pin_out = None
+        _graveyard.append((graph, self.ws, self.dev_in, self.out_dev, self.pin_in, self.pin_out, self.stream, self._det_handle,
+                           self._ref_handle))
+        self.ws = self.dev_in = self.out_dev = self.pin_in = self.pin_out = self._det_handle = self._ref_handle = None
 
     def __del__(self):
         try:
@@ -264,33 +268,15 @@ class GraphedPipeline:
 
 
 # ---- host-latency helpers of the one-frame path (a call is ~0.3 ms: every microsecond of interpreter work is 0.3 % of it) ----------
-_hip = None
-
-
 def _sync_current_stream(dev_index: int) -> None:
     """hipStreamSynchronize on torch's CURRENT stream of the device (what ``torch.cuda.current_stream().synchronize()`` does, without
-    building a Stream object: 3.7 -> ~1 us per call, tools/bs1_host_probe2.py).  Falls back to the public API if torch's raw-stream
-    accessor or the HIP runtime's symbol is not where this build of torch has them."""
-    global _hip
-    if _hip is False:
-        torch.cuda.current_stream(dev_index).synchronize()
-        return
+    building a Stream object: 3.7 -> ~1 us per call, tools/bs1_host_probe2.py), through the library: it waits in the HIP runtime the
+    library is linked against, the one torch's streams belong to."""
     try:
         raw = torch._C._cuda_getCurrentRawStream(dev_index)
-        if _hip is None:
-            import ctypes
-            lib = ctypes.CDLL("libamdhip64.so")            # the runtime torch has already loaded (same SONAME: same handle)
-            lib.hipStreamSynchronize.argtypes = [ctypes.c_void_p]
-            lib.hipStreamSynchronize.restype = ctypes.c_int
-            _hip = lib
-        if _hip.hipStreamSynchronize(raw) == 0:
-            return
-    except (AttributeError, OSError):
-        pass
-    # the shortcut is not usable in this process (no raw-stream accessor, no symbol, or a runtime that does not know torch's stream
-    # handle): the public API from here on -- it also raises a proper error if the stream itself is in trouble
-    _hip = False
-    torch.cuda.current_stream(dev_index).synchronize()
+    except AttributeError:
+        raw = torch.cuda.current_stream(dev_index).cuda_stream
+    _lib.check(_lib.lib().dcx_stream_synchronize(raw), "dcx_stream_synchronize")
 
 
 def _current_device() -> int:
@@ -303,7 +289,7 @@ def _current_device() -> int:
 _CACHE_MAX = 8        # per detector: graphs pin ~25 MB of workspace per 320x240 shape
 _cache_lock = threading.RLock()         # re-entrant: dropping a pipeline may run model destructors that come back here
 _graph_lock = _locks.all                # `with _graph_lock():` = every device's lock (capture, destruction, cache surgery)
-_graveyard: list = []                   # hipGraphs / buffers of closed pipelines; list.append / pop are atomic
+_graveyard: list = []                   # hipGraphs / buffers / weights of closed pipelines; list.append / pop are atomic
 _caches: "weakref.WeakSet" = weakref.WeakSet()     # the per-detector caches that exist (for clear_graph_cache())
 _live: "weakref.WeakSet" = weakref.WeakSet()       # every GraphedPipeline that exists (cached, or evicted but still held by a thread)
 
@@ -337,8 +323,7 @@ def clear_graph_cache(deepc=None) -> None:
         victims = []
         with _cache_lock:
             if deepc is not None:
-                det = deepc.model if hasattr(deepc, "model") else deepc
-                caches = [getattr(det, "_graph_cache", None)]
+                caches = [getattr(unwrap(deepc), "_graph_cache", None)]
             else:
                 caches = list(_caches)
             for c in caches:
@@ -351,7 +336,7 @@ def clear_graph_cache(deepc=None) -> None:
 
 
 def _try_drain() -> None:
-    """Empty the graveyard if nobody is replaying or capturing right now; never waits (see ``drop_graphs_of_detector``)."""
+    """Empty the graveyard if nobody is replaying or capturing right now; never waits (see ``_close_pipelines_of``)."""
     if not _graveyard:
         return
     held = _locks.try_all()
@@ -366,9 +351,10 @@ def _close_pipelines_of(match) -> None:
     """Retire every pipeline -- cached or evicted-but-still-held -- for which ``match(pipeline)`` holds.  Takes ONLY the cache lock
     (re-entrant) and never waits for a device lock: this runs from model destructors, i.e. possibly from the garbage collector in
     the middle of any critical section of this module (a destructor that took the device locks while its thread already held the
-    cache lock deadlocked against a capturing thread: ADVICE r5).  ``close`` itself is lock-free; what it leaves behind is destroyed
-    by the next holder of all device locks (a capture, ``clear_graph_cache``) or right here if nobody is replaying.  A thread that
-    is about to replay a retired pipeline is stopped by ``run``'s own check of the models' C handles."""
+    cache lock deadlocked against a capturing thread: ADVICE r5).  ``close`` itself is lock-free and hands the graph, its buffers and
+    the weights it was captured with to the graveyard; they are destroyed by the next holder of all device locks (a capture,
+    ``clear_graph_cache``) or right here if nobody is replaying.  So a thread that is replaying a retired pipeline right now -- it
+    passed ``run``'s check before the retirement -- finishes on weights that are still alive, and a later ``run`` refuses."""
     with _cache_lock:
         victims = [p for p in list(_live) if match(p)]
         for c in list(_caches):
@@ -379,15 +365,9 @@ def _close_pipelines_of(match) -> None:
     _try_drain()
 
 
-def drop_graphs_of_detector(det) -> None:
-    """Called when a detector releases its C handle: its graphs hold pointers into the freed weights."""
-    _close_pipelines_of(lambda p: p._det() is det or p._det() is None)
-
-
-def drop_graphs_of_refiner(ref) -> None:
-    """Called when a RefineNet releases its C handle (reload / ``to(device)`` / destruction): graphs captured with it hold
-    pointers into the freed weights."""
-    _close_pipelines_of(lambda p: p._ref is not None and (p._ref() is ref or p._ref() is None))
+def drop_graphs_of(weights) -> None:
+    """Called when a model lets go of its weights (reload / ``to(device)`` / destruction): retires the graphs captured with them."""
+    _close_pipelines_of(lambda p: p._det_handle is weights or p._ref_handle is weights)
 
 
 def cached_pipeline(dust_bin_ids: int, deepc, refinenet, height: int, width: int, bgr: bool,
@@ -397,8 +377,7 @@ def cached_pipeline(dust_bin_ids: int, deepc, refinenet, height: int, width: int
     instead of pinning it in a module-global table, and a re-allocated model can never alias a cached graph of a freed one.
     A hit costs one dictionary operation under the cache lock; only a miss (capture) takes the locks of all devices.  An evicted
     pipeline that another thread is still holding keeps working until that thread lets go of it."""
-    det = deepc.model if hasattr(deepc, "model") else deepc
-    ref = None if refinenet is None else (refinenet.model if hasattr(refinenet, "model") else refinenet)
+    det, ref = unwrap(deepc), unwrap(refinenet)
     key = (None if ref is None else (id(ref), ref.handle.value), dust_bin_ids, height, width, bgr, kmax,
            int(_lib.lib().dcx_get_deterministic()))
 

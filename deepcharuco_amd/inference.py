@@ -18,7 +18,7 @@ import torch
 
 from . import _lib
 from .imgproc import _opencv, bgr2gray
-from .models._handles import require_cuda
+from .models._handles import require_cuda, unwrap
 from .models.model_utils import extract_patches, pre_bgr_image, pred_to_keypoints
 from .models.net import dcModel, lModel
 from .models.refinenet import RefineNet, lRefineNet
@@ -158,14 +158,6 @@ def get_xcd_weights(device="cuda") -> List[float]:
     return [float(v) for v in w]
 
 
-def _unwrap(deepc, refinenet):
-    det = deepc.model if hasattr(deepc, "model") else deepc
-    ref = None
-    if refinenet is not None:
-        ref = refinenet.model if hasattr(refinenet, "model") else refinenet
-    return det, ref
-
-
 PIXEL_FORMATS = {"gray": 0, "opencv4": 1, "legacy14": 2}       # DCX_PIX_GRAY8 / DCX_PIX_BGR8 / DCX_PIX_BGR8_LEGACY14
 
 
@@ -212,7 +204,7 @@ def infer_batch_device(frames: torch.Tensor, dust_bin_ids: int, deepc, refinenet
     at least ``dcx_pipeline_workspace_bytes`` bytes) to manage it yourself.  ``out`` (optional) must be a contiguous
     int32 tensor of exactly ``packed_len(B, pool, conf)`` elements on the model's GPU.
     """
-    det, ref = _unwrap(deepc, refinenet)
+    det, ref = unwrap(deepc), unwrap(refinenet)
     dev = det.device
     if (not isinstance(frames, torch.Tensor) or frames.device != dev or frames.dtype != torch.uint8 or not frames.is_contiguous()
             or not (frames.ndim == 3 or (frames.ndim == 4 and frames.shape[3] == 3))):
@@ -306,7 +298,7 @@ def infer_batch(frames, dust_bin_ids: int, deepc, refinenet=None, kmax: int = DE
     number of cells; only if the WHOLE batch fires more than ``pool`` (default ``B * kmax``) cells is it run a second time, with
     a pool of exactly the size the first pass reported (never silently truncated).  BGR frames are converted on the device with
     the fixed-point formula of the OpenCV generation the reference pins (``bgr_variant``, see imgproc.py)."""
-    det, _ = _unwrap(deepc, refinenet)
+    det = unwrap(deepc)
     d_frames = _to_device_frames(frames, det.device)
     b = d_frames.shape[0]
     if pool is None:

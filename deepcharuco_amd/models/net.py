@@ -6,80 +6,31 @@ Only the inference surface exists: ``forward`` / ``__call__`` / ``infer_image`` 
 from __future__ import annotations
 
 import ctypes as C
-import sys
 from typing import Optional, Tuple
 
 import torch
 
 from .. import _lib
 from ..weights import StateDict, state_dict_from_checkpoint
-from ._handles import Workspace, check_dev_tensor, require_cuda, tensor_pointer_array
+from ._handles import NativeModel, NativeWrapper, check_dev_tensor
 
 
-class dcModel:
+class dcModel(NativeModel):
     """DeepCharuco detector (net.py:9-80) running as hand-written gfx950 kernels."""
+
+    _kind = "detector"
 
     def __init__(self, n_ids: int, state_dict: Optional[StateDict] = None, device="cuda"):
         self.n_ids = n_ids
-        self._handle = None
-        self._device: Optional[torch.device] = None
-        self._ws = Workspace()
-        self._sd = None
-        if state_dict is not None:
-            self.load_state_dict(state_dict, device)
+        super().__init__(state_dict, device)
 
-    # -- weights ------------------------------------------------------------------------------
-    def load_state_dict(self, state_dict: StateDict, device="cuda") -> "dcModel":
-        dev = require_cuda(device)
-        arr, keep = tensor_pointer_array(state_dict, "detector", self.n_ids)
-        self._release()
-        h = C.c_void_p()
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().dcx_detector_create(C.byref(h), arr, len(keep), self.n_ids), "dcx_detector_create")
-        self._handle, self._device, self._sd = h, dev, state_dict
-        return self
-
-    def to(self, device) -> "dcModel":
-        dev = require_cuda(device)
-        if self._sd is not None and dev != self._device:
-            self.load_state_dict(self._sd, dev)
-        return self
-
-    def eval(self) -> "dcModel":   # BN is always evaluated with running statistics (inference.py:75)
-        return self
+    def _create(self, arr, n_tensors: int):
+        L, h = _lib.lib(), C.c_void_p()
+        _lib.check(L.dcx_detector_create(C.byref(h), arr, n_tensors, self.n_ids), "dcx_detector_create")
+        return h, L.dcx_detector_destroy
 
     def parameters(self):
         raise NotImplementedError("weights live in the HIP library's packed layout; use state_dict from weights.py")
-
-    @property
-    def handle(self) -> C.c_void_p:
-        if self._handle is None:
-            raise RuntimeError("dcModel has no weights loaded (call load_state_dict / load_models)")
-        return self._handle
-
-    @property
-    def device(self) -> torch.device:
-        if self._device is None:
-            raise RuntimeError("dcModel has no weights loaded")
-        return self._device
-
-    def _release(self):
-        if self._handle is not None:
-            try:
-                # hipGraphs captured with this handle's weights (graph.py).  sys.modules, not an import: this runs from __del__,
-                # possibly during interpreter shutdown, where an import can fail -- and the handle must be freed regardless
-                g = sys.modules.get("deepcharuco_amd.graph")
-                if g is not None:
-                    g.drop_graphs_of_detector(self)          # device locks first, then the cache lock (same order as everywhere)
-            finally:
-                _lib.lib().dcx_detector_destroy(self._handle)
-                self._handle = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
 
     # -- forward (net.py:50-80) ---------------------------------------------------------------
     def forward(self, x: torch.Tensor):
@@ -124,7 +75,7 @@ class dcModel:
         return out["loc"], out["ids"]
 
 
-class lModel:
+class lModel(NativeWrapper):
     """Mirror of the Lightning wrapper (net.py:118-128): ``.model`` + ``infer_image``."""
 
     def __init__(self, dcModel: dcModel):  # noqa: N803  (keyword name used by the reference, inference.py:74)
@@ -138,20 +89,5 @@ class lModel:
             dcModel.load_state_dict(sd, map_location)
         return cls(dcModel)
 
-    def forward(self, x):
-        return self.model(x)
-
-    __call__ = forward
-
     def infer_image(self, img):
         return self.model.infer_image(img)
-
-    def eval(self):
-        self.model.eval()
-        return self
-
-    def to(self, device):
-        if self.model._sd is None:
-            raise RuntimeError("no weights loaded")
-        self.model.load_state_dict(self.model._sd, device)
-        return self

@@ -7,64 +7,17 @@ from typing import Optional, Tuple
 import torch
 
 from .. import _lib
-from ..weights import StateDict, state_dict_from_checkpoint
-from ._handles import Workspace, check_dev_tensor, require_cuda, tensor_pointer_array
+from ..weights import state_dict_from_checkpoint
+from ._handles import NativeModel, NativeWrapper, check_dev_tensor
 
 
-class RefineNet:
-    def __init__(self, state_dict: Optional[StateDict] = None, device="cuda"):
-        self._handle = None
-        self._device: Optional[torch.device] = None
-        self._ws = Workspace()
-        self._sd = None
-        if state_dict is not None:
-            self.load_state_dict(state_dict, device)
+class RefineNet(NativeModel):
+    _kind = "refinenet"
 
-    def load_state_dict(self, state_dict: StateDict, device="cuda") -> "RefineNet":
-        dev = require_cuda(device)
-        arr, keep = tensor_pointer_array(state_dict, "refinenet", 16)
-        self._release()
-        h = C.c_void_p()
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().dcx_refiner_create(C.byref(h), arr, len(keep)), "dcx_refiner_create")
-        self._handle, self._device, self._sd = h, dev, state_dict
-        return self
-
-    def to(self, device) -> "RefineNet":
-        dev = require_cuda(device)
-        if self._sd is not None and dev != self._device:
-            self.load_state_dict(self._sd, dev)
-        return self
-
-    def eval(self) -> "RefineNet":
-        return self
-
-    @property
-    def handle(self) -> C.c_void_p:
-        if self._handle is None:
-            raise RuntimeError("RefineNet has no weights loaded")
-        return self._handle
-
-    @property
-    def device(self) -> torch.device:
-        if self._device is None:
-            raise RuntimeError("RefineNet has no weights loaded")
-        return self._device
-
-    def _release(self):
-        if self._handle is not None:
-            import sys
-            g = sys.modules.get("deepcharuco_amd.graph")     # only if a hipGraph may have been captured with this handle
-            if g is not None:
-                g.drop_graphs_of_refiner(self)
-            _lib.lib().dcx_refiner_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
+    def _create(self, arr, n_tensors: int):
+        L, h = _lib.lib(), C.c_void_p()
+        _lib.check(L.dcx_refiner_create(C.byref(h), arr, n_tensors), "dcx_refiner_create")
+        return h, L.dcx_refiner_destroy
 
     def _run(self, patches: torch.Tensor, want_heat: bool, keypoints: Optional[torch.Tensor] = None):
         dev = self.device
@@ -108,7 +61,7 @@ class RefineNet:
         return corners_og, corners32.to(torch.int64)
 
 
-class lRefineNet:
+class lRefineNet(NativeWrapper):
     def __init__(self, refinenet: RefineNet):
         self.model = refinenet
 
@@ -120,19 +73,5 @@ class lRefineNet:
             refinenet.load_state_dict(sd, map_location)
         return cls(refinenet)
 
-    def forward(self, x):
-        return self.model(x)
-
-    __call__ = forward
-
     def infer_patches(self, patches, keypoints):
         return self.model.infer_patches(patches, keypoints)
-
-    def eval(self):
-        return self
-
-    def to(self, device):
-        if self.model._sd is None:
-            raise RuntimeError("no weights loaded")
-        self.model.load_state_dict(self.model._sd, device)
-        return self

@@ -20,6 +20,7 @@ import torch
 import torch.distributed as dist
 
 from .inference import packed_len, unpack_results  # noqa: F401  (packed_len is re-exported: callers size buffers with it)
+from .models._handles import unwrap
 
 
 def shard_range(n_frames: int, rank: int, world: int) -> Tuple[int, int]:
@@ -203,7 +204,7 @@ def infer_frames_sharded(frames_gray: np.ndarray, dust_bin_ids: int, deepc, refi
     if pool is None:
         pool = max(1, batch_max * kmax)
     if run_local is None:
-        det = deepc.model if hasattr(deepc, "model") else deepc
+        det = unwrap(deepc)
 
         def run_local(fr, pool_):
             d = torch.from_numpy(np.ascontiguousarray(fr)).to(det.device)
@@ -237,7 +238,7 @@ def infer_batches_sharded(batches, dust_bin_ids: int, deepc, refinenet=None, kma
     from .inference import infer_batch_device  # local import: needs the GPU library
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     backend = backend or dist.get_backend(group)
-    det = deepc.model if hasattr(deepc, "model") else deepc
+    det = unwrap(deepc)
     dev = det.device
     og = None
     pending = []          # (step index, frames)

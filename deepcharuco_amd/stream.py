@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .inference import DEFAULT_KMAX, infer_batch, infer_batch_device, packed_len, solve_pnp_submit, unpack_results
+from .models._handles import unwrap
 from .pnp import POSE_WORDS, solve_pnp_batch_device, solve_pnp_pool, unpack_poses
 
 
@@ -35,7 +36,7 @@ class FrameStream:
         single frame may use any share of it.  ``pnp_device=True`` (with ``pnp``): the poses are solved on the GPU
         (``solve_pnp_pool`` enqueued behind the pipeline on the same stream, into a per-slot buffer copied to pinned memory before
         the batch's completion event) and handed out resolved, without OpenCV; the default keeps the host-thread stage."""
-        det = deepc.model if hasattr(deepc, "model") else deepc
+        det = unwrap(deepc)
         self.dev = det.device
         self.dust_bin_ids, self.deepc, self.refinenet = dust_bin_ids, deepc, refinenet
         self.batch, self.h, self.w, self.kmax, self.depth = batch, height, width, kmax, depth
@@ -196,7 +197,7 @@ class ResidentStream:
         holds, per retired batch, the time from the moment the stream reached the batch to its last byte in pinned memory
         (bench.py's step_breakdown).  The host-side counters ``host_enqueue_s`` (time spent inside ``submit`` launching work) and
         ``host_wait_s`` (time blocked on the oldest batch's completion event) are always kept."""
-        det = deepc.model if hasattr(deepc, "model") else deepc
+        det = unwrap(deepc)
         self.dev = det.device
         self.dust_bin_ids, self.deepc, self.refinenet = dust_bin_ids, deepc, refinenet
         self.batch, self.h, self.w, self.kmax = batch, height, width, kmax

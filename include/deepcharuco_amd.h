@@ -179,6 +179,10 @@ int dcx_infer_batch(const dcx_detector* det, const dcx_refiner* rf,
                     int batch, int height, int width, int dust_bin, int pool,
                     void* d_ws, size_t ws_bytes,
                     int32_t* d_counts, int32_t* d_starts, int32_t* d_rows, float* d_xy, float* d_conf, void* stream);
+/* hipStreamSynchronize(stream) -> the hipError_t.  Waits in the HIP runtime this library was linked against, which is the one
+ * whose streams the caller passes here (torch's, in the Python package): a second copy of the runtime loaded beside it would not
+ * know those streams, and its synchronisation of the default stream would return without waiting.                           */
+int dcx_stream_synchronize(void* stream);
 
 /* ---- solve_pnp inference.py:15-29 (cv2.solvePnP, default flags = SOLVEPNP_ITERATIVE) on the device, per frame of a pool --
  * Reads a corner pool in place, in the layout dcx_infer_batch writes (or a caller-built one: counts / starts + the id column of
@@ -262,7 +266,9 @@ int dcx_get_tail_fence(void);
  * dcx_calibrate_xcd measures them (`rounds` ~0.8 ms launches of the dominant kernel on a synthetic conv1b-sized layer; synchronous,
  * set-up code: GPU warm, outside timed regions and hipGraph capture) and sets the shares accordingly; dcx_set_xcd_weights sets
  * them by hand (8 relative speeds, NULL = equal; more than 25 % from equal is refused with DCX_E_ARG); dcx_get_xcd_weights returns
- * them (1.0 = an equal share).  Per device (the current one), process-global; hipGraphs keep the shares they were captured with. */
+ * them (1.0 = an equal share).  Per device (the current one), process-global; hipGraphs keep the shares they were captured with:
+ * the shares live in a ring of 256 device tables per device, so a graph captured through this API must be re-captured before
+ * its device's shares are set 256 more times.                                                                                      */
 int dcx_calibrate_xcd(int rounds, float* w8_out, void* stream);
 int dcx_set_xcd_weights(const float* w8);
 int dcx_get_xcd_weights(float* w8);

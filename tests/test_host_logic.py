@@ -435,7 +435,7 @@ def test_conv_kernels_do_not_spill(tmp_path):
 
 def test_graph_cache_clear_is_reentrant():
     """A cached GraphedPipeline may hold the LAST reference to a model pair; dropping it (clear_graph_cache, e.g. from
-    set_deterministic) then runs RefineNet._release -> drop_graphs_of_refiner, which comes back to the cache lock on the same
+    set_deterministic) then runs RefineNet._release -> drop_graphs_of, which comes back to the cache lock on the same
     thread.  Found as a hang of the GPU suite in round 3; reproduced here without a GPU, under a watchdog."""
     import threading
     from deepcharuco_amd import graph as G
@@ -448,7 +448,7 @@ def test_graph_cache_clear_is_reentrant():
             pass
 
         def __del__(self):
-            G.drop_graphs_of_refiner(self.ref)
+            G.drop_graphs_of(self.ref)
 
     class Det:
         pass
@@ -466,6 +466,74 @@ def test_graph_cache_clear_is_reentrant():
     t.start()
     t.join(20)
     assert done == [1, 2] and len(cache) == 0
+
+
+def test_graph_weights_outlive_a_replay_in_flight():
+    """a model reloaded or destroyed while another thread replays a graph captured with its weights must not free
+    those weights under the replay.  The graph holds them; retiring it hands them to the graveyard, which is emptied only under
+    the locks of all devices.  A model with no graph still frees its weights at once."""
+    import ctypes
+    import gc
+    import threading
+    from deepcharuco_amd import graph as G
+    from deepcharuco_amd.models._handles import NativeModel, NativeWeights
+
+    destroyed = []
+
+    def model_with_weights(h):          # no GPU: the weights are a fake handle whose destroy records it
+        m = NativeModel()
+        m._weights = NativeWeights(ctypes.c_void_p(h), None, lambda hd: destroyed.append(hd.value))
+        return m
+
+    class Pipe(G.GraphedPipeline):
+        def __init__(self, weights):    # what close() hands on, without a GPU: no graph, buffers or stream
+            self.graph = object()
+            self.ws = self.dev_in = self.out_dev = self.pin_in = self.pin_out = self.stream = None
+            self._det_handle, self._ref_handle = weights, None
+            G._live.add(self)
+
+    # (a) thread B releases the weights (as a reload or the destructor does) while thread A holds the device lock, as a replay does
+    m = model_with_weights(1)
+    pipe = Pipe(m._weights)
+    in_replay, replay_done = threading.Event(), threading.Event()
+
+    def replay():
+        with G._locks.device(0):
+            in_replay.set()
+            replay_done.wait(20)
+    a = threading.Thread(target=replay, daemon=True)
+    a.start()
+    assert in_replay.wait(20)
+    b = threading.Thread(target=lambda: (m._release(), destroyed.append("released")), daemon=True)
+    b.start()
+    b.join(20)
+    assert destroyed == ["released"], "the model's release waited for the replay or destroyed the weights under it"
+    assert pipe.graph is None                        # retired: a later run() refuses
+    del m
+    gc.collect()
+    assert destroyed == ["released"]
+    replay_done.set()
+    a.join(20)
+    assert not a.is_alive()
+    G.clear_graph_cache()                            # drains the graveyard under every device lock
+    assert destroyed == ["released", 1]
+    G.clear_graph_cache()
+    del pipe
+    gc.collect()
+    assert destroyed == ["released", 1]              # exactly once
+
+    # (b) no graph holds them: freed right away, by a reload as by the destructor
+    m = model_with_weights(2)
+    m._release()
+    assert destroyed[-1] == 2 and m._weights is None
+    m = model_with_weights(3)
+    del m
+    assert destroyed[-1] == 3
+    w = NativeWeights(ctypes.c_void_p(4), None, lambda hd: destroyed.append(hd.value))
+    w.free()
+    w.free()
+    del w
+    assert destroyed == ["released", 1, 2, 3, 4]
 
 
 def test_missing_native_library_fails_loudly(monkeypatch, tmp_path):
