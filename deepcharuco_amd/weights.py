@@ -149,6 +149,39 @@ def diverse_ids_bias_shift(ids_logits: np.ndarray, loc_argmax: np.ndarray, n_ids
     return (best_b - best_b.mean()).astype(np.float32), int(best_d)
 
 
+def loc_nocorner_bias_shift(loc_logits: np.ndarray, frac_lo: float = 0.85, frac_hi: float = 0.95, min_margin: float = 1e-4) -> float:
+    """Shift delta for ``convPb.bias[64]`` that makes the no-corner class 64 win on a fraction of cells in [frac_lo, frac_hi], the
+    regime of trained checkpoints (most cells say "no corner"), where ``pred_argmax``'s rule ``where(loc_argmax == 64, dust_bin,
+    ids_argmax)`` (model_utils.py:72-77) hides the ids head's answer on most cells.  Random-init heads put class 64 on ~0 % of cells.
+
+    With d = max_{c<64} loc_c - loc_64 per cell, class 64 wins exactly where d < delta.  delta is the midpoint of a gap between
+    consecutive sorted d values, so every cell's loc top-2 margin afterwards is at least min(gap / 2, its own top-2 margin among
+    classes 0..63 if it still loses); among the gaps whose fraction lies in the window, the one with the largest such minimum is
+    taken.  Raises ValueError if none reaches ``min_margin``.
+
+    loc_logits: (65, ...cells) for one frame or (B, 65, h, w) for a batch -- whoever calls this decides whose logits they are
+    (oracle/make_golden.py: the reference's)."""
+    z = np.asarray(loc_logits, dtype=np.float64)
+    z = np.moveaxis(z, 1, 0) if z.ndim == 4 else z
+    assert z.shape[0] == 65, z.shape
+    z = z.reshape(65, -1)
+    top2 = np.sort(z[:64], axis=0)[-2:]
+    d = top2[1] - z[64]
+    own = top2[1] - top2[0]                       # top-2 margin among classes 0..63 (what a cell keeps if class 64 still loses)
+    order = np.argsort(d, kind="stable")
+    ds, own_s = d[order], own[order]
+    n = ds.size
+    suffix_own = np.minimum.accumulate(own_s[::-1])[::-1]
+    i = np.arange(1, n)                           # delta between ds[i-1] and ds[i]: class 64 wins on exactly i cells
+    frac = i / n
+    margin = np.minimum((ds[i] - ds[i - 1]) / 2, suffix_own[i])
+    ok = (frac >= frac_lo) & (frac <= frac_hi) & (margin >= min_margin)
+    if not ok.any():
+        raise ValueError(f"no gap in [{frac_lo}, {frac_hi}] of the cells keeps a loc top-2 margin >= {min_margin}")
+    j = int(i[ok][np.argmax(margin[ok])])
+    return float((ds[j - 1] + ds[j]) / 2)
+
+
 def state_dict_sha256(sd: StateDict, kind: str, n_ids: int = 16) -> str:
     h = hashlib.sha256()
     for k in state_dict_keys(kind, n_ids):

@@ -185,6 +185,18 @@ def equalise_ids(dc, sd_dc, frame_u8, n_ids, target):
         dc.model.convDb.bias[:n_ids] = torch.from_numpy(sd_dc["convDb.bias"][:n_ids].copy())
 
 
+def shift_loc_nocorner(dc, sd_dc, frame_u8):
+    """Shift convPb.bias[64] (weights.loc_nocorner_bias_shift on the REFERENCE's logits) so that the no-corner class wins on 85-95 %
+    of this frame's cells, as trained checkpoints do; returns the shift."""
+    x = torch.tensor(O.pre_bgr_image(frame_u8))
+    loc, _ = dc.infer_image(x)
+    delta = W.loc_nocorner_bias_shift(loc[0].numpy())
+    sd_dc["convPb.bias"][64] = np.float32(sd_dc["convPb.bias"][64] + np.float32(delta))
+    with torch.no_grad():
+        dc.model.convPb.bias[64] = float(sd_dc["convPb.bias"][64])
+    return delta
+
+
 CASES = [
     # name, weight seed, frame kind, frame seed, H, W, target K, keep full logits
     dict(name="tiny_noise_64x96", wseed=3, kind="noise", fseed=5, H=64, W=96, K=6, full=True),
@@ -202,7 +214,17 @@ CASES = [
     # fixture (data); its gray version is what the stubbed cv2.cvtColor (= the oracle's OpenCV-4.x fixed-point formula) produced.
     dict(name="img7412_240x320", wseed=1234, kind="img7412", fseed=0, H=240, W=320, K=16, full=True),
     dict(name="img7412_diverse_240x320", wseed=7, kind="img7412", fseed=0, H=240, W=320, K=16, full=False, diverse=True, min_ids=8),
+    # Trained-checkpoint regime: convPb.bias[64] shifted so that the no-corner class wins on 85-95 % of the cells, with margin
+    # (shift_loc_nocorner), BEFORE the ids equalisation and the dust-bin calibration.  Every case has >= 20 "masked" cells: loc
+    # arg-max 64 while the raw ids arg-max is not the dust bin, i.e. cells that only the where(loc_argmax == 64, ...) rule of
+    # pred_argmax (model_utils.py:76) keeps from firing.  The other fixtures have none.
+    dict(name="trainedlike_board_240x320", wseed=1234, kind="board", fseed=1, H=240, W=320, K=16, full=True, trained=True),
+    dict(name="trainedlike_img7412_240x320", wseed=7, kind="img7412", fseed=0, H=240, W=320, K=16, full=False, diverse=True, trained=True),
+    dict(name="trainedlike_board_480x640", wseed=7, kind="board", fseed=2, H=480, W=640, K=16, full=False, trained=True),
 ]
+LOC64_FRAC = (0.85, 0.95)
+MIN_LOC_MARGIN_TRAINED = 1e-4
+MIN_MASKED_CELLS = 20
 IMG7412 = "/root/reference/src/reference/samples_test/IMG_7412.png"
 
 
@@ -251,6 +273,8 @@ def main():
             assert not np.array_equal(frame, photo[..., 1])                  # a real colour image, not gray x3
         else:
             frame = W.synthetic_frames(c["kind"], c["fseed"], 1, c["H"], c["W"])[0]
+        if c.get("trained"):
+            shift_loc_nocorner(dc, sd_dc, frame)
         if c.get("diverse"):
             equalise_ids(dc, sd_dc, frame, N_IDS, c["K"])
         dust_bias = calibrate_dustbin(dc, sd_dc, frame, N_IDS, c["K"])
@@ -265,6 +289,14 @@ def main():
         assert kpts.shape[0] == c["K"], (name, kpts.shape)
         if c.get("diverse"):
             assert len(set(ids_found.tolist())) >= c.get("min_ids", 12), (name, ids_found)
+        loc64 = la[0] == 64
+        loc64_frac = float(loc64.double().mean())
+        masked = loc64 & (ids.argmax(1)[0] != N_IDS)
+        if c.get("trained"):
+            assert LOC64_FRAC[0] <= loc64_frac <= LOC64_FRAC[1], (name, loc64_frac)
+            assert float(O.top2_margin(loc).min()) >= MIN_LOC_MARGIN_TRAINED, name
+            assert int(masked.sum()) >= MIN_MASKED_CELLS, (name, int(masked.sum()))
+            assert bool((ia[0][masked] == N_IDS).all())            # the reference's own pred_argmax hides every one of them
         patches = ref_mu.extract_patches(x, kpts)
         with torch.no_grad():
             heat = rn(patches[:, None])
@@ -323,6 +355,10 @@ def main():
             heat_first2=heat[:2, 0].numpy(),
             final_rn=final_rn, final_norn=final_norn,
         )
+        if c.get("trained"):
+            fx["convPb_bias"] = sd_dc["convPb.bias"].astype(np.float32).copy()     # the whole loc-head bias the case ran with
+            fx["masked_cells"] = np.array(int(masked.sum()))
+            fx["loc64_frac"] = np.float64(loc64_frac)
         if photo is not None:
             fx["bgr_image"] = photo
         if c["full"]:
@@ -344,9 +380,12 @@ def main():
                                    min_loc_margin=float(fx["loc_margin"].min()),
                                    min_ids_margin=float(fx["ids_margin"].min()),
                                    min_heat_margin=float(fx["heat_margin"].min())))
+        if c.get("trained"):
+            index["cases"][-1].update(masked_cells=int(masked.sum()), loc64_frac=loc64_frac)
         print(f"[golden] {name}: K={kpts.shape[0]} dust_bias={dust_bias:.6f} "
               f"min margins loc {fx['loc_margin'].min():.2e} ids {fx['ids_margin'].min():.2e} "
-              f"heat {fx['heat_margin'].min():.2e}; oracle == reference")
+              f"heat {fx['heat_margin'].min():.2e}; loc==64 on {loc64_frac:.1%}, masked cells {int(masked.sum())}; "
+              f"oracle == reference")
 
     # BGR -> gray restatement on colour pixels (cv2 absent: parity unpinned, formulas only).  `gray` = the OpenCV 4.x 8-bit
     # formula (15-bit constants; the range the reference pins), `gray_legacy14` = the older 14-bit one; `bgr_differ` are pixels

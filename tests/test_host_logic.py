@@ -645,3 +645,22 @@ def test_draw_inner_corners_semantics(monkeypatch):
     monkeypatch.setitem(sys.modules, "cv2", None)
     with pytest.raises(ImportError, match="OpenCV"):
         I.draw_inner_corners(img, corners, np.array([7, 12, 1, 2]))
+
+
+def test_loc_nocorner_bias_shift_window_margin_and_refusal():
+    """weights.loc_nocorner_bias_shift: after the shift class 64 wins on a share of cells inside the window, every cell's loc top-2
+    margin is >= min_margin, and it refuses when no gap can give that margin."""
+    rng = np.random.default_rng(5)
+    loc = rng.standard_normal((2, 65, 30, 40)).astype(np.float32)
+    d = W.loc_nocorner_bias_shift(loc)
+    z = loc.astype(np.float64).copy()
+    z[:, 64] += d
+    win = z.argmax(1) == 64
+    assert 0.85 <= win.mean() <= 0.95
+    top = np.sort(z, axis=1)
+    assert (top[:, -1] - top[:, -2]).min() >= 1e-4
+    one = W.loc_nocorner_bias_shift(loc[0], 0.5, 0.6, 0.0)               # (65, h, w): one frame
+    assert 0.5 <= ((loc[0, :64].max(0) - loc[0, 64]) < one).mean() <= 0.6
+    flat = np.zeros((65, 8, 8), np.float32)                               # every cell ties: no gap anywhere
+    with pytest.raises(ValueError):
+        W.loc_nocorner_bias_shift(flat)

@@ -2,9 +2,11 @@
 (oracle/make_golden.py), stage by stage.  Integer outputs exact; logits within fp32 re-ordering
 noise (the reference's own oneDNN result moves by ~2e-6 between 1 and 8 threads)."""
 import numpy as np
+import pytest
 import torch
 
 from oracle import deepcharuco_oracle as O
+from trainedlike import MIN_MASKED_CELLS, TRAINED_CASES, trained_case
 
 LOGIT_ATOL = 2e-5
 
@@ -38,7 +40,16 @@ def test_bgr2gray_formula():
         assert np.array_equal(O.bgr2gray(np.repeat(g[..., None], 3, 2), v), g)   # gray in -> same gray out, either variant
 
 
+@pytest.fixture(params=TRAINED_CASES)
+def trained(request):
+    return trained_case(request.param)
+
+
 def test_detector_stages(golden):
+    _check_detector_stages(golden)
+
+
+def _check_detector_stages(golden):
     fx = golden.fx
     sd = O.to_torch_state_dict(golden.sd_dc)
     x = torch.tensor(O.pre_bgr_image(golden.frame))
@@ -56,6 +67,10 @@ def test_detector_stages(golden):
 
 
 def test_patches_and_refinenet(golden):
+    _check_patches_and_refinenet(golden)
+
+
+def _check_patches_and_refinenet(golden):
     fx = golden.fx
     x = torch.tensor(O.pre_bgr_image(golden.frame))
     kpts = torch.from_numpy(fx["kpts"])
@@ -74,6 +89,10 @@ def test_patches_and_refinenet(golden):
 
 
 def test_infer_image_end_to_end(golden):
+    _check_infer_image_end_to_end(golden)
+
+
+def _check_infer_image_end_to_end(golden):
     fx = golden.fx
     sd_dc, sd_rn = O.to_torch_state_dict(golden.sd_dc), O.to_torch_state_dict(golden.sd_rn)
     a = O.infer_image(golden.bgr, golden.n_ids, sd_dc, sd_rn)
@@ -81,6 +100,41 @@ def test_infer_image_end_to_end(golden):
     b = O.infer_image(golden.bgr, golden.n_ids, sd_dc, None)
     assert b.dtype == np.int64 and np.array_equal(b, fx["final_norn"])
     assert np.all(np.diff(a[:, 2]) >= 0)   # sorted by id
+
+
+# ---- trained-regime cases (tests/trainedlike.py): class 64 wins on 85-95 % of the cells, >= 20 of them hide a firing id
+
+def test_detector_stages_trainedlike(trained):
+    _check_detector_stages(trained)
+
+
+def test_patches_and_refinenet_trainedlike(trained):
+    _check_patches_and_refinenet(trained)
+
+
+def test_infer_image_end_to_end_trainedlike(trained):
+    _check_infer_image_end_to_end(trained)
+
+
+def test_trainedlike_masked_cells(trained):
+    """The loc == 64 rule is live: cells with loc arg-max 64 whose raw ids arg-max would fire, recomputed from the stored arg-max
+    maps, match the stored count; the stored (masked) ids arg-max is the dust bin on each of them; the oracle agrees (on cells whose
+    ids top-2 gap exceeds the thread-count noise of the logits)."""
+    fx = trained.fx
+    n = trained.masked_cells()
+    assert n == int(fx["masked_cells"]) and n >= MIN_MASKED_CELLS
+    masked = (fx["loc_argmax"] == 64) & (fx["ids_argmax_raw"] != trained.n_ids)
+    assert np.all(fx["ids_argmax"][masked] == trained.n_ids)
+    assert 0.85 <= float(fx["loc64_frac"]) <= 0.95 and float(fx["loc64_frac"]) == float((fx["loc_argmax"] == 64).mean())
+    assert float(fx["loc_margin"].min()) >= 1e-4
+    x = torch.tensor(O.pre_bgr_image(trained.frame))
+    loc, ids = O.detector_infer_image(O.to_torch_state_dict(trained.sd_dc), x)
+    la, ia = O.pred_argmax(loc, ids, trained.n_ids)
+    o_masked = ((la[0] == 64) & (ids.argmax(1)[0] != trained.n_ids)).numpy()
+    safe = fx["ids_margin"] > 1e-4
+    assert np.array_equal(la[0].numpy(), fx["loc_argmax"].astype(np.int64))
+    assert np.array_equal(o_masked[safe], masked[safe]) and int(o_masked.sum()) >= MIN_MASKED_CELLS
+    assert bool((ia[0].numpy()[o_masked] == trained.n_ids).all())
 
 
 def test_no_corner_returns_empty(golden_tiny):
