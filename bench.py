@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- end-to-end frames/s of the detect+refine path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--config cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR] [--full]
       N = 1: runs in this process.  N > 1 from a bare shell (no RANK/WORLD_SIZE): starts its own N ranks under
       torch.distributed.run on 127.0.0.1 at a free port (self_launch) and relays rank 0's JSON line + the exit code.
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...     (ranks started by the caller)
@@ -13,13 +13,16 @@ result into pinned host memory.  Weak scaling: every rank processes the same num
 (32 by default = BASELINE configs[1] per GPU), so the driver's 1/2/4/8-GPU values form a true weak-scaling curve.
 The K timed steps go through the product's non-blocking caller for HBM-resident frames (stream.ResidentStream; at N>1
 the same launches under sharding.OverlappedGather's side-stream gather) on ONE HIP stream.  `--streams S` alternates
-consecutive steps between S streams (S batches in flight); the roofline block is then measured in a second pass of the
-same K steps on one stream (`single_stream`).  Rounds 2-5 reported "+6 ... +15 % with two batches in flight": that was a
-measurement artifact -- the second batch of that comparison came from another seed and fired 38 % fewer corners; with
-equal work in every batch a second stream LOSES 1-4 % (profiles/experiments/r05_batches_in_flight_equal_work.txt).
+consecutive steps between S streams (S batches in flight); with --full the roofline block is then measured in a second
+pass of the same K steps on one stream (`single_stream`).  Rounds 2-5 reported "+6 ... +15 % with two batches in flight":
+that was a measurement artifact -- the second batch of that comparison came from another seed and fired 38 % fewer
+corners; with equal work in every batch a second stream LOSES 1-4 % (profiles/experiments/r05_batches_in_flight_equal_work.txt).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with
-  roofline        dominant kernel, hipEvent-timed inside the timed region;
+Rank 0 prints ONE JSON line: metric, value (frames/s of the K timed steps), unit, ms_per_step, higher_is_better, dtype and
+the workload's config.  A plain run does only that: set-up, settle phase, W warm-up steps, the K timed steps, --dump-outputs,
+the line.  `--full` adds everything else the benchmark measures or checks:
+  roofline        dominant kernel, hipEvent-timed inside the timed region, + per-kernel table and step_breakdown from 3 extra
+                  fully bracketed steps;
   parity          frames of the TIMED batch compared with the oracle (ids, cells, sub-pixel xy identical); any
                   mismatch makes the process exit non-zero;
   cpu_baseline    (N=1) the oracle timed on the host cores;
@@ -201,9 +204,10 @@ def fetch_profile(L, total_patches):
 
 
 def run_config(cx, name, batch, height, width, kmax, frames_kind, fixed_k, steps, warmup, profile, n_check,
-               want_cpu_baseline=False, dump_dir=None):
+               want_cpu_baseline=False, dump_dir=None, full=True):
     """One measured configuration on every rank.  Returns (rank 0) the dict for the JSON line.  dump_dir: rank 0 writes the
-    last timed step's results there (dump_outputs)."""
+    last timed step's results there (dump_outputs).  full=False (a plain run): no roofline block, no parity, no CPU baseline --
+    the timed steps themselves are the same either way."""
     L, dev, rank, world, dist = cx.L, cx.dev, cx.rank, cx.world, cx.dist
     B, H, Wd = batch, height, width
     seed0 = FRAME_SEED + rank * 100000
@@ -342,6 +346,11 @@ def run_config(cx, name, batch, height, width, kmax, frames_kind, fixed_k, steps
         return el
 
     elapsed = timed_pass(steps)              # THE timed region: `value`
+    # A plain run keeps the sampled brackets inside the timed region (they have always been part of what `value` measures)
+    # but reads nothing back: the roofline block and the runs it takes of its own are --full only
+    roof = profile and full
+    if profile and not full:
+        L.dcx_profile_enable(0)
     per_rank_info = None
     if dist_on:
         # every rank's own clock and its exchange step, so that a multi-GPU line is diagnosable in one shot: ms_per_step of the
@@ -377,11 +386,11 @@ def run_config(cx, name, batch, height, width, kmax, frames_kind, fixed_k, steps
         dump_outputs(dump_dir, [f for p in per_rank for f in unpack_results(p, B, pool, True)[0]])
 
     timed_hdr = None
-    if profile:
+    if roof:
         timed_hdr = fetch_profile(L, total_patches)      # the dominant kernel as sampled INSIDE the timed region
         L.dcx_profile_enable(0)
     elapsed_1s = None
-    if S > 1 and profile:
+    if S > 1 and roof:
         # Per-kernel durations only mean something when nothing else shares the GPU: the roofline block is taken from a second
         # pass of the SAME K steps on ONE stream (its throughput is reported beside `value` as single_stream)
         state["S"] = 1
@@ -392,7 +401,7 @@ def run_config(cx, name, batch, height, width, kmax, frames_kind, fixed_k, steps
     el_roof = elapsed_1s if elapsed_1s is not None else elapsed
 
     roofline = None
-    if profile:
+    if roof:
         timed = fetch_profile(L, total_patches)
         L.dcx_profile_enable(0)
         L.dcx_profile_filter(-1)
@@ -506,32 +515,34 @@ def run_config(cx, name, batch, height, width, kmax, frames_kind, fixed_k, steps
     fps = world * B * steps / elapsed
     gflop_frame = DET_GFLOP_240x320 * (H * Wd) / (240 * 320) + REF_GFLOP_PER_PATCH * mean_k
 
-    # ---- parity of the timed batch: rank 0's own frames, and (N>1) frames of the LAST rank out of the gathered buffer
-    oracle = Oracle(sd_dc, sd_rn)
-    torch.set_num_threads(min(os.cpu_count() or 1, 16))
-    cpu = cpu_baseline(oracle, name, frames) if want_cpu_baseline else None     # also fills the oracle's result cache
-    pick = list(range(min(n_check, B)))
-    busiest = int(np.argmax(counts_local))           # the frame of the timed batch with the most corners is always checked
-    if busiest not in pick:
-        pick.append(busiest)
-    if os.environ.get("DCX_BENCH_CORRUPT_PARITY"):   # test hook: prove that the gate gates (first checked frame that has corners)
-        for b in pick:
-            if res_local[b] is not None and res_local[b].ndim == 2:
-                res_local[b] = res_local[b].copy(); res_local[b][0, 0] += 1.0
-                break
-    checks = [((name, 0, b), frames[b], res_local[b]) for b in pick]
-    if dist_on:
-        # frames of EVERY other rank out of the gathered buffer (2 per rank; the last rank gets as many as rank 0 / 2)
-        for r in range(1, world):
-            res_r = unpack_results(per_rank[r], B, pool, True)[0]
-            n_r = max(2, n_check // 2) if r == world - 1 else 2
-            for b in ([0, B - 1] if n_r == 2 else pick[:n_r]):
-                if fixed_k:
-                    fr = W.synthetic_frames(frames_kind, FRAME_SEED + r * 100000 + kept_all[r][b], 1, H, Wd)[0]   # frame b of rank r's batch
-                else:
-                    fr = frames[(b + r) % B]                                      # rank r runs rank 0's frames rotated by r
-                checks.append(((name, r, b), fr, res_r[b]))
-    parity = parity_block(oracle, checks)
+    cpu = parity = None
+    if full:
+        # ---- parity of the timed batch: rank 0's own frames, and (N>1) frames of the LAST rank out of the gathered buffer
+        oracle = Oracle(sd_dc, sd_rn)
+        torch.set_num_threads(min(os.cpu_count() or 1, 16))
+        cpu = cpu_baseline(oracle, name, frames) if want_cpu_baseline else None     # also fills the oracle's result cache
+        pick = list(range(min(n_check, B)))
+        busiest = int(np.argmax(counts_local))           # the frame of the timed batch with the most corners is always checked
+        if busiest not in pick:
+            pick.append(busiest)
+        if os.environ.get("DCX_BENCH_CORRUPT_PARITY"):   # test hook: prove that the gate gates (first checked frame that has corners)
+            for b in pick:
+                if res_local[b] is not None and res_local[b].ndim == 2:
+                    res_local[b] = res_local[b].copy(); res_local[b][0, 0] += 1.0
+                    break
+        checks = [((name, 0, b), frames[b], res_local[b]) for b in pick]
+        if dist_on:
+            # frames of EVERY other rank out of the gathered buffer (2 per rank; the last rank gets as many as rank 0 / 2)
+            for r in range(1, world):
+                res_r = unpack_results(per_rank[r], B, pool, True)[0]
+                n_r = max(2, n_check // 2) if r == world - 1 else 2
+                for b in ([0, B - 1] if n_r == 2 else pick[:n_r]):
+                    if fixed_k:
+                        fr = W.synthetic_frames(frames_kind, FRAME_SEED + r * 100000 + kept_all[r][b], 1, H, Wd)[0]   # frame b of rank r's batch
+                    else:
+                        fr = frames[(b + r) % B]                                      # rank r runs rank 0's frames rotated by r
+                    checks.append(((name, r, b), fr, res_r[b]))
+        parity = parity_block(oracle, checks)
 
     out = {
         "value": round(fps, 2), "unit": "frames/s", "ms_per_step": round(1e3 * elapsed / steps, 4), "steps": steps,
@@ -545,7 +556,6 @@ def run_config(cx, name, batch, height, width, kmax, frames_kind, fixed_k, steps
                    "corner_pool_per_gpu": pool, "corner_pool_note": "no per-frame cap: every firing cell of every frame is refined, as in the reference; the pool is shared by the batch",
                    "frames": frames_kind, "mean_corners_per_frame": round(mean_k, 2), "truncated_frames": truncated,
                    "corners_per_frame_min_max": [int(counts.min()), int(counts.max())],
-                   "busiest_frame_checked": {"frame": busiest, "corners": int(counts_local[busiest])},
                    "distinct_ids_in_batch": len(ids_seen),
                    "weights": "numpy-seeded synthetic (seed 1234/1235), ids-head biases equalised per class (all ids fire), dust-bin bias calibrated to ~16 corners/frame"
                               + (f"; frames selected by the workload generator so that exactly {fixed_k} cells fire in each" if fixed_k else ""),
@@ -555,8 +565,10 @@ def run_config(cx, name, batch, height, width, kmax, frames_kind, fixed_k, steps
                    # the layers AS WRITTEN / peak: > 1 is possible because the Winograd families execute 4/9 (1/4) of those MACs;
                    # the executed fraction of the whole step is roofline.e2e_executed_frac
                    "e2e_algorithmic_over_peak": round(fps * gflop_frame / 1e3 / (PEAK_F32_MFMA_TFLOPS * world), 4)},
-        "parity": parity,
     }
+    if parity is not None:
+        out["config"]["busiest_frame_checked"] = {"frame": busiest, "corners": int(counts_local[busiest])}
+        out["parity"] = parity
     if elapsed_1s is not None:
         out["single_stream"] = {"value": round(world * B * steps / elapsed_1s, 2), "unit": "frames/s",
                                 "ms_per_step": round(1e3 * elapsed_1s / steps, 4), "steps": steps,
@@ -690,15 +702,20 @@ def main():
     ap.add_argument("--fixed-k", type=int, default=None, help="select frames with exactly this many corners (cfg5: 16)")
     ap.add_argument("--streams", type=int, default=1,
                     help="batches in flight per GPU: consecutive steps alternate between this many HIP streams (stream.ResidentStream). "
-                         "Default 1: with EQUAL work in every batch a second stream gains nothing (-1 ... -4 %, "
-                         "profiles/experiments/r05_batches_in_flight_equal_work.txt); > 1 adds a single-stream pass for the roofline block")
+                         "Default 1: with EQUAL work in every batch a second stream gains nothing (-1 ... -4 %%, "
+                         "profiles/experiments/r05_batches_in_flight_equal_work.txt); > 1 with --full adds a single-stream pass for the roofline block")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the benchmark measures or checks: roofline block and step_breakdown, "
+                         "parity against the oracle (exit 3 on a mismatch), CPU baseline, other_configs")
     ap.add_argument("--parity-frames", type=int, default=8)
     ap.add_argument("--settle", type=float, default=None,
                     help=f"seconds of untimed steps ahead of the warm-up steps (default {SETTLE_S}; 0 = none: the cold A/B that shows the "
                          "GPU's clock ramp inside the timed region)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip other_configs (the other BASELINE configs, bs=1 protocol)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true",
+                    help="no hipEvent brackets inside the timed region (and with --full no roofline block)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full without other_configs (the other BASELINE configs, bs=1 protocol)")
     ap.add_argument("--force-dist", action="store_true",
                     help="run the N>1 code path (process group, side-stream all-gather, barrier, MAX all-reduce) even with one rank: "
                          "RCCL self-check on a 1-GPU box")
@@ -758,10 +775,11 @@ def main():
             p[k_] = v
     main_res = run_config(cx, args.config, p["batch"], p["height"], p["width"], p["kmax"], p["frames"], p["fixed_k"],
                           args.steps, args.warmup, not args.no_profile, args.parity_frames,
-                          want_cpu_baseline=(world == 1 and not args.no_cpu_baseline), dump_dir=args.dump_outputs)
+                          want_cpu_baseline=(world == 1 and not args.no_cpu_baseline), dump_dir=args.dump_outputs,
+                          full=args.full)
 
     others = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # the other BASELINE configs at their per-GPU size, short runs (5 warm-up protocol of src/benchmark.py kept)
         todo = [n for n in ("cfg3", "cfg4", "cfg5") if n != args.config] if world == 1 else \
                [n for n in ("cfg4", "cfg5") if n != args.config]
@@ -793,9 +811,10 @@ def main():
         # its bs=1 infer_image loop on a GTX1080Ti -- the like-for-like ratio is other_configs.bs1_reference_protocol
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": dict(main_res["config"], vs_baseline_note="null: BASELINE.json publishes nothing for bs=32; the reference README's "
-                       "'>200 fps' (GTX1080Ti, bs=1, src/benchmark.py) is compared like for like in other_configs.bs1_reference_protocol"),
-        "parity": main_res["parity"],
+                       "'>200 fps' (GTX1080Ti, bs=1, src/benchmark.py) is compared like for like in other_configs.bs1_reference_protocol (--full)"),
     }
+    if "parity" in main_res:
+        line["parity"] = main_res["parity"]
     if dist_on:
         line["ranks"] = cx.ranks_seen
     for k_ in ("settle", "batches_in_flight", "single_stream", "gather_overlapped", "per_rank", "step_breakdown", "roofline", "cpu_baseline"):
@@ -808,7 +827,7 @@ def main():
     except Exception:                  # line is the LAST line of stdout (a driver that reads the last line must find it)
         pass
     print(json.dumps(line), flush=True)
-    bad = main_res["parity"]["mismatched_frames"] + sum(v.get("parity", {}).get("mismatched_frames", 0) for v in others.values())
+    bad = sum(v.get("parity", {}).get("mismatched_frames", 0) for v in [main_res, *others.values()])
     if dist_on:
         cx.dist.barrier()
         cx.dist.destroy_process_group()

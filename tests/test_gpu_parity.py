@@ -1436,8 +1436,8 @@ def test_bench_script_emits_parity_block_and_exit_code(dev):
     import sys
     env = dict(os.environ)
     env.pop("DCX_FORCE_CFG", None)
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline",
-           "--parity-frames", "3"]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-extras",
+           "--no-cpu-baseline", "--parity-frames", "3"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -129,7 +129,7 @@ def test_bench_n_gt_1_code_path_with_one_rccl_rank(tmp_path):
     barrier + MAX all-reduce around the timed region, parity of frames taken out of the gathered buffer) with one rank."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
     env.pop("DCX_FORCE_CFG", None)
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--force-dist", "--steps", "4", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--force-dist", "--steps", "4", "--warmup", "2", "--full",
                         "--no-cpu-baseline", "--no-extras", "--parity-frames", "4"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -151,7 +151,7 @@ def test_bench_self_launches_its_ranks_from_a_bare_shell():
     ranks' timed batches are identical to the oracle, exit code 0.  gloo because the box has one GPU (RCCL when it has two)."""
     backend = "nccl" if torch.cuda.device_count() >= 2 else "gloo"
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", backend, "--steps", "2",
-                        "--warmup", "1", "--no-extras"], env=_bare_env(), capture_output=True, text=True, timeout=900)
+                        "--warmup", "1", "--full", "--no-extras"], env=_bare_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines
@@ -173,26 +173,32 @@ def test_bench_refuses_rccl_with_fewer_gpus_than_ranks():
 def test_bench_single_gpu_line_has_no_rank_block():
     """--gpus 1 stays a single in-process run: no process group, no `ranks` block, n_gpus = 1."""
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--no-extras", "--no-cpu-baseline"], env=_bare_env(), capture_output=True, text=True, timeout=600)
+                        "--full", "--no-extras", "--no-cpu-baseline"], env=_bare_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and "ranks" not in line and "gather_overlapped" not in line and "roofline" in line
 
 
 def test_bench_dump_outputs_are_reproducible_and_steps_are_timed(tmp_path):
-    """--dump-outputs writes the corner lists of the last timed step (float64 .npy); the inputs are seeded, so two runs write the
-    same arrays -- here with different --steps, and each run times exactly the steps it was asked for (one GPU time per batch)."""
+    """--dump-outputs writes the corner lists of the last timed step (float64 .npy); the inputs are seeded, so every run writes the
+    same arrays -- here with different --steps, with and without --full, and each --full run shows that it timed exactly the steps
+    it was asked for (one GPU time per batch).  A plain run prints the headline and none of what --full adds."""
     dumps = []
-    for steps in (3, 7):
+    for steps, full in ((3, True), (7, True), (5, False)):
         d = tmp_path / f"steps{steps}"
         r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
-                            "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(d)], env=_bare_env(), capture_output=True,
-                           text=True, timeout=600)
+                            *(["--full", "--no-extras", "--no-cpu-baseline"] if full else []), "--dump-outputs", str(d)],
+                           env=_bare_env(), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
         line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-        assert line["steps"] == steps and line["step_breakdown"]["gpu_ms_per_batch"]["n"] == steps
+        assert line["steps"] == steps and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 1000
+        if full:
+            assert line["step_breakdown"]["gpu_ms_per_batch"]["n"] == steps
+        else:
+            assert {"metric", "unit", "higher_is_better", "dtype"} <= line.keys()
+            assert not {"parity", "roofline", "step_breakdown", "cpu_baseline", "other_configs"} & line.keys()
         corners, counts = np.load(d / "corners.npy"), np.load(d / "corners_per_frame.npy")
         assert corners.dtype == np.float64 and counts.dtype == np.float64 and counts.shape == (line["config"]["batch_per_gpu"],)
         assert corners.shape == (int(counts.sum()), 3) and corners.shape[0] > 8 * counts.shape[0]
         dumps.append((corners, counts))
-    assert all(np.array_equal(a, b) for a, b in zip(*dumps))
+    assert all(np.array_equal(a, b) for other in dumps[1:] for a, b in zip(dumps[0], other))

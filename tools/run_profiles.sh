@@ -11,10 +11,10 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out
 if [ "$MODE" = collect ]; then
     mkdir -p "$OUT"; export TMPDIR=/tmp
-    (cd "$ROOT" && timeout 700 python bench.py --steps 50 --warmup 5 > "$OUT/bench.log" 2>&1; echo "bench exit $?" >> "$OUT/bench.log")
+    (cd "$ROOT" && timeout 700 python bench.py --full --steps 50 --warmup 5 > "$OUT/bench.log" 2>&1; echo "bench exit $?" >> "$OUT/bench.log")
     cd /tmp
     rm -rf "$OUT"/prof_r${R}*
-    B="python $ROOT/bench.py --no-cpu-baseline --no-extras"
+    B="python $ROOT/bench.py --full --no-cpu-baseline --no-extras"
     timeout 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_r${R}" -o r${R} -- $B --steps 10 --warmup 3 > "$OUT/rocprof.log" 2>&1
     timeout 300 rocprofv3 --pmc FETCH_SIZE -d "$OUT/prof_r${R}_fetch" -o fetch -- $B --steps 4 --warmup 2 --no-profile > "$OUT/rocprof_fetch.log" 2>&1
     timeout 300 rocprofv3 --pmc WRITE_SIZE -d "$OUT/prof_r${R}_write" -o write -- $B --steps 4 --warmup 2 --no-profile > "$OUT/rocprof_write.log" 2>&1

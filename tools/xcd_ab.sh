@@ -2,7 +2,7 @@ set -u
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; export TMPDIR=/tmp
 cd $R
 python -m pytest tests -m gpu -x -q -k "conv or golden or soak or parity_128" 2>&1 | tail -3
-for m in 1 0 1 0; do DCX_XCD_WALK=$m python bench.py --no-extras --no-cpu-baseline --steps 30 --warmup 5 > $O/xcd_$m.json 2>/dev/null; python tools/bench_summary.py $O/xcd_$m.json | head -4; done
+for m in 1 0 1 0; do DCX_XCD_WALK=$m python bench.py --full --no-extras --no-cpu-baseline --steps 30 --warmup 5 > $O/xcd_$m.json 2>/dev/null; python tools/bench_summary.py $O/xcd_$m.json | head -4; done
 cd /tmp
 for m in 1 0; do
   rm -rf $O/prof_xcd${m}_fetch $O/prof_xcd${m}_write
