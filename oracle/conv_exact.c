@@ -14,6 +14,7 @@
  *                                          beta2 = fmaf(bias, alpha, beta)  (conv bias folded into the BN shift; fp32)
  *   (raw 1x1 heads: y = acc + bias;  Cin = 1 first layers: y = max(fmaf(acc + bias, alpha, beta), 0))
  * For cin == 1 (first layers) the order is simply tap 0..8.
+ * dcx_oracle_heat_exact (end of file) restates the RefineNet head of both kernel families.
  * Build: gcc -O2 -ffp-contract=off -fopenmp -shared -fPIC   (see oracle/Makefile)
  */
 #include <math.h>
@@ -158,8 +159,8 @@ void dcx_oracle_conv_wino2h_exact(const float* x, int n, int cin, int h, int w, 
  *     m[p = 3 xi + nu] = 0; for chunk c0 (16 cin) / j in 0..3 / g in 0..3: m = fmaf(U[ci], v[ci], m), ci = c0 + 4 g + j;
  *     y_k (k = 2 i + j) = 0; for p in 0..8: y_k = fmaf(AT[i][xi] * AT[j][nu], m[p], y_k), AT = [[1,1,0],[0,1,1]];
  *     out[2 (y0 + i) + a][2 (x0 + j) + b] = max(fmaf(y_k, alpha, fmaf(bias, alpha, beta)), 0). */
-void dcx_oracle_conv_ups2w_exact(const float* x, int n, int cin, int h, int w, const float* wt, const float* bias,
-                                 const float* alpha, const float* beta, int cout, float* y) {
+static void ups2w_core(const float* x, int n, int cin, int h, int w, const float* wt, const float* bias,
+                       const float* alpha, const float* beta, int cout, int raw, float* y) {
     static const int lo[2][2] = {{0, 1}, {0, 2}}, hi[2][2] = {{0, 2}, {1, 2}};
     static const float AT[2][3] = {{1.f, 1.f, 0.f}, {0.f, 1.f, 1.f}};
     const int ho = 2 * h, wo = 2 * w;
@@ -230,11 +231,82 @@ void dcx_oracle_conv_ups2w_exact(const float* x, int n, int cin, int h, int w, c
                                 const int ly = y0 + i, lx = x0 + j;
                                 if (ly < h && lx < w)
                                     y[(((size_t)b * cout + co) * ho + 2 * ly + pa) * wo + 2 * lx + pb] =
-                                        fmaxf(fmaf(yk, alpha[co], fmaf(bias[co], alpha[co], beta[co])), 0.0f);
+                                        raw ? yk : fmaxf(fmaf(yk, alpha[co], fmaf(bias[co], alpha[co], beta[co])), 0.0f);
                             }
                     }
                 }
             free(V);
         }
     free(U);
+}
+
+void dcx_oracle_conv_ups2w_exact(const float* x, int n, int cin, int h, int w, const float* wt, const float* bias,
+                                 const float* alpha, const float* beta, int cout, float* y) {
+    ups2w_core(x, n, cin, h, w, wt, bias, alpha, beta, cout, 0, y);
+}
+
+/* RefineNet head (refinenet.py:78-81: convPa 3x3 pad 1 over the x2 up-sampled 32x32 map + bnPa + ReLU, then convPb 1x1 to ONE
+ * channel) as the DCX_EPI_HEAT epilogues compute it; cout = 64 (16 channel quads cq, couts 4 cq + i, i = 0..3), x is the
+ * LOW-RESOLUTION input [n][cin][h][w], heat is [n][2h][2w].  r(co) = max(fmaf(e(co), alpha, fmaf(bias, alpha, beta)), 0) with e
+ * the layer's pre-BN output in the family's own order; every partial sum below starts from +0.
+ *   order 0, direct (dcx_conv_mfma.h, DcxConvCfg<1,4,2,2,...,HEAT>: WM = 1, MT = 2, so a lane's channel quads are
+ *            cq = mt * 8 + 2 g + half, mt = 0..1, g = 0..3; e = dcx_oracle_conv_exact's chain over the up-sampled input):
+ *            s[half] = fmaf chain over cq in that (mt, g) order, couts i = 0..3 within each quad:  s = fmaf(r, head_w, s);
+ *            heat = (s[0] + s[1]) + head_b            (the __shfl_xor(hsum, 32) of the two half-waves, then the bias)
+ *   order 1, w2p (dcx_conv_wino2p.h, DcxWino2pCfg<8,16,HEAT,1>: wave wm owns cq = 4 wm + g, g = lane >> 4; e = the phase x
+ *            F(2x2,2x2) output of dcx_oracle_conv_ups2w_exact before BN):
+ *            q[cq] = fmaf chain over i = 0..3;  w[wm] = (q[4wm] + q[4wm+1]) + (q[4wm+2] + q[4wm+3])   (xor 16, then xor 32)
+ *            heat = ((w[0] + w[1]) + (w[2] + w[3])) + head_b      (the wm == 0 wave's read of the four waves' LDS partials) */
+void dcx_oracle_heat_exact(const float* x, int n, int cin, int h, int w, const float* wt, const float* bias, const float* alpha,
+                           const float* beta, const float* head_w, float head_b, int order, float* heat) {
+    const int ho = 2 * h, wo = 2 * w;
+    const size_t plane = (size_t)ho * wo;
+    float* e = (float*)malloc(sizeof(float) * (size_t)n * 64 * plane);
+    if (order == 1) {
+        ups2w_core(x, n, cin, h, w, wt, bias, alpha, beta, 64, 1, e);
+    } else {
+        float* xu = (float*)malloc(sizeof(float) * (size_t)n * cin * plane);
+        for (size_t bc = 0; bc < (size_t)n * cin; ++bc)
+            for (int yy = 0; yy < ho; ++yy)
+                for (int xx = 0; xx < wo; ++xx) xu[bc * plane + (size_t)yy * wo + xx] = x[(bc * h + yy / 2) * w + xx / 2];
+        float* zero = (float*)calloc(64, sizeof(float));      /* alpha = NULL: the raw chain + 0 (the bias is folded below) */
+        dcx_oracle_conv_exact(xu, n, cin, ho, wo, wt, zero, NULL, NULL, 64, 3, 1, e);
+        free(zero); free(xu);
+    }
+#pragma omp parallel for collapse(2) schedule(static)
+    for (int b = 0; b < n; ++b)
+        for (size_t px = 0; px < plane; ++px) {
+            float r[64];
+            for (int co = 0; co < 64; ++co)
+                r[co] = fmaxf(fmaf(e[((size_t)b * 64 + co) * plane + px], alpha[co], fmaf(bias[co], alpha[co], beta[co])), 0.0f);
+            float v;
+            if (order == 1) {
+                float wsum[4];
+                for (int wm = 0; wm < 4; ++wm) {
+                    float q[4];
+                    for (int g = 0; g < 4; ++g) {
+                        const int cq = 4 * wm + g;
+                        float acc = 0.0f;
+                        for (int i = 0; i < 4; ++i) acc = fmaf(r[4 * cq + i], head_w[4 * cq + i], acc);
+                        q[g] = acc;
+                    }
+                    wsum[wm] = (q[0] + q[1]) + (q[2] + q[3]);
+                }
+                v = ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])) + head_b;
+            } else {
+                float s[2];
+                for (int half = 0; half < 2; ++half) {
+                    float acc = 0.0f;
+                    for (int mt = 0; mt < 2; ++mt)
+                        for (int g = 0; g < 4; ++g) {
+                            const int cq = mt * 8 + 2 * g + half;
+                            for (int i = 0; i < 4; ++i) acc = fmaf(r[4 * cq + i], head_w[4 * cq + i], acc);
+                        }
+                    s[half] = acc;
+                }
+                v = (s[0] + s[1]) + head_b;
+            }
+            heat[(size_t)b * plane + px] = v;
+        }
+    free(e);
 }

@@ -64,3 +64,27 @@ def conv_exact(x, wt, bias, bn=None, pad=1, ups=False, pool=False, family="direc
     if pool:
         y = y[:, :, :ho // 2 * 2, :wo // 2 * 2].reshape(n, cout, ho // 2, 2, wo // 2, 2).max(axis=(3, 5))
     return y
+
+
+HEAD_ORDERS = ("direct", "w2p")
+
+
+def heat_exact(x, wt, bias, bn, head_w, head_b, order):
+    """RefineNet head (convPa 3x3 pad 1 over the x2 up-sampled x + bnPa + ReLU + convPb 1x1 -> 1 channel) in the exact fp32 order
+    of one DCX_EPI_HEAT kernel (conv_exact.c: dcx_oracle_heat_exact).  x NCHW float32 at LOW resolution (64 channels); returns
+    the heat-map logits (N, 1, 2H, 2W) float32."""
+    assert order in HEAD_ORDERS, order
+    x = np.ascontiguousarray(x, np.float32)
+    wt = np.ascontiguousarray(wt, np.float32)
+    bias = np.ascontiguousarray(bias, np.float32)
+    hw = np.ascontiguousarray(np.asarray(head_w, np.float32).reshape(-1))
+    n, cin, h, w = x.shape
+    assert wt.shape == (64, cin, 3, 3) and hw.shape == (64,) and cin % 16 == 0
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    g, be, mu, var = [np.ascontiguousarray(t, np.float32) for t in bn]
+    alpha, beta = np.empty(64, np.float32), np.empty(64, np.float32)
+    lib().dcx_oracle_fold_bn(p(g), p(be), p(mu), p(var), 64, p(alpha), p(beta))
+    heat = np.empty((n, 1, 2 * h, 2 * w), np.float32)
+    lib().dcx_oracle_heat_exact(p(x), n, cin, h, w, p(wt), p(bias), p(alpha), p(beta), p(hw), C.c_float(float(np.float32(head_b))),
+                                HEAD_ORDERS.index(order), p(heat))
+    return heat
