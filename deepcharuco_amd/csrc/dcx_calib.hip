@@ -1,0 +1,760 @@
+// dcx_calib.hip -- cv2.calibrateCamera (default flags) for a planar board, on the device, read straight from the corner pool
+// dcx_infer_batch writes (the views of a ChArUco board: id-labelled corners).  The steps (all fp64) are restated readably in
+// deepcharuco_amd/calib.py (calibrate_camera_host_full), which is the pin of these kernels:
+//   per-view checks -> initIntrinsicParams2D (principal point at the centre, per-view DLT homography, two rows per view in
+//   (1/fx^2, 1/fy^2), least squares) -> every view's pose by the PnP solver (solve(), K0, no distortion) -> joint
+//   Levenberg-Marquardt over theta = (fx, fy, cx, cy, k1, k2, p1, p2, k3) and every used view's (rvec, tvec), CvLevMarq's rules,
+//   at most 30 accepted steps, stop at |dp| / |p| < DBL_EPSILON.
+//
+// The normal matrix is block-sparse: a view's 6 pose parameters couple only to the 9 intrinsics.  Per view, [J_theta | J_pose | r]
+// (16 columns) gives a symmetric 16x16 [V_i W_i g_a,i; W_i^T U_i g_b,i; . . cost_i], 136 packed entries.  Each LM attempt
+// eliminates the 6x6 blocks (Schur complement) and solves one damped 9x9 system:
+//   S = V* - sum W_i U_i*^-1 W_i^T,  dtheta = S^-1 (g_a - sum W_i U_i*^-1 g_b,i),  dpose_i = U_i*^-1 g_b,i - U_i*^-1 W_i^T dtheta.
+//
+// Launches (one 64-lane wave per view unless noted; grid = batch):
+//   init_views      per-view checks, the view's homography, its two init rows
+//   init_reduce     (one workgroup) the rows reduced, the 2x2 least squares -> K0
+//   init_poses      solve() with K0 and zero distortion
+//   evaluate        after init and after each accepted step: the view's 136 entries.  The per-point rows of [J | r] are staged
+//                   in LDS, 64 points at a time, and lane l sums the entries l, l + 64, l + 128 over them in point order
+//                   (a 136-value butterfly would not fit the registers)
+//   schur           per attempt: damping, 6x6 Cholesky of U_i*, U_i*^-1 [W_i^T | g_b,i], the view's part of S and of the rhs
+//   reduce_solve    (one workgroup) the parts summed in a fixed order, diag(sum V) damped, 9x9 Cholesky -> dtheta
+//   trial           the view's dpose, trial pose and trial cost, its share of |dp|^2 and |p|^2
+//   decide          (one workgroup) accept or reject, lg, the stop test; a state word for the host, the outputs when done
+// The LM loop runs on the host: it reads the state word after every attempt (the number of attempts depends on the data), so
+// the call synchronises its stream and cannot be captured in a graph.  Every sum has a fixed order (no atomics): two calls on
+// the same input give the same bits.  Nothing is allocated: the caller passes the workspace.
+#include "dcx_pnp_dev.h"
+
+namespace {
+
+constexpr int kCalibMaxIter = 30;
+constexpr double kCalibEps = 2.220446049250313e-16;      // DBL_EPSILON
+constexpr int kRedThreads = 1024;                         // one-workgroup reductions over views
+constexpr int kSlices = kRedThreads / 128;                // reduce_solve: 8 view slices x 128 entry slots
+constexpr int kEntries = 136;                             // packed 16x16: [J_theta (9) | J_pose (6) | r]
+constexpr int kCost = 135;                                // pk<16>(15, 15)
+
+enum : int { kNextEvaluate = 0, kNextSchur = 1, kFinished = 2 };
+
+struct CalibState {
+    double theta[9], theta_trial[9], dtheta[9];
+    double prev_cost;
+    double result[16];       // h_result
+    int lg, iters, attempts, code;
+};
+
+// per-view workspace, in doubles
+constexpr int kRows = 6;                 // the two init rows (a0, a1, b) x 2
+constexpr int kYZ = 60;                  // U*^-1 W^T (6 x 9, row major) and U*^-1 g_b (6)
+constexpr int kSC = 54;                  // the view's part of S (45 packed) and of the rhs (9)
+constexpr int kState = 512;              // bytes reserved for CalibState
+static_assert(sizeof(CalibState) <= kState, "state");
+
+struct Ws {
+    CalibState* st;
+    double *rows, *m, *yz, *sc, *pose, *trial_pose, *trial;   // trial = {cost, |dp|^2, |p|^2}
+    int* fail;
+
+    __host__ __device__ Ws(void* base, int batch) {
+        char* p = (char*)base;
+        st = (CalibState*)p;
+        double* d = (double*)(p + kState);
+        rows = d;            d += (size_t)batch * kRows;
+        m = d;               d += (size_t)batch * kEntries;
+        yz = d;              d += (size_t)batch * kYZ;
+        sc = d;              d += (size_t)batch * kSC;
+        pose = d;            d += (size_t)batch * 6;
+        trial_pose = d;      d += (size_t)batch * 6;
+        trial = d;           d += (size_t)batch * 3;
+        fail = (int*)d;
+    }
+};
+
+size_t ws_bytes(int batch) {
+    if (batch <= 0) return 0;
+    return (size_t)kState + (size_t)batch * (kRows + kEntries + kYZ + kSC + 6 + 6 + 3) * sizeof(double) +
+           (((size_t)batch * sizeof(int) + 7) & ~(size_t)7);
+}
+
+struct Pool {
+    const int32_t* counts;
+    const int32_t* starts;
+    const int32_t* rows;
+    const float* xy;
+    int rm1;
+    double square_len;
+
+    __device__ Frame frame(int b) const {
+        const long long s0 = starts[b];
+        return Frame{rows + 4 * s0, xy ? xy + 2 * s0 : nullptr, counts[b], rm1, square_len};
+    }
+};
+
+__device__ __forceinline__ PnpCamera camera_of(const double* th) {
+    PnpCamera c;
+    c.fx = th[0]; c.fy = th[1]; c.cx = th[2]; c.cy = th[3];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) c.k[i] = i < 5 ? th[4 + i] : 0.0;
+    return c;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- init
+
+__global__ __launch_bounds__(kLanes) void calib_init_views_kernel(Pool pl, int pool, int n_ids, double cx, double cy,
+                                                                  int32_t* __restrict__ status, double* __restrict__ pose, Ws ws) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int n = pl.counts[b], s0 = pl.starts[b];
+    double r[6] = {0, 0, 0, 0, 0, 0};
+    int st;
+    if (n <= 0) {
+        st = DCX_PNP_TOO_FEW;
+    } else if (s0 < 0 || (long long)s0 + n > (long long)pool) {
+        st = DCX_PNP_TRUNCATED;               // (its slots are not read)
+    } else if (n < 4) {
+        st = DCX_PNP_TOO_FEW;
+    } else {
+        bool bad = false;
+        for (int i = lane; i < n; i += kLanes) {
+            const int id = pl.rows[4 * ((long long)s0 + i) + 2];
+            bad |= id < 0 || id >= n_ids;
+        }
+        if (__any(bad)) {
+            st = DCX_PNP_BAD_ID;
+        } else {
+            // the DLT on the pixels themselves: undistort() with fx = fy = 1, cx = cy = 0 and no distortion is the identity
+            PnpCamera ident;
+            ident.fx = ident.fy = 1.0;
+            ident.cx = ident.cy = 0.0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) ident.k[i] = 0.0;
+            double H[9], mcx, mcy;
+            st = homography(pl.frame(b), ident, false, H, mcx, mcy);
+            if (st == DCX_PNP_OK) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {        // the principal point subtracted
+                    H[j] -= H[6 + j] * cx;
+                    H[3 + j] -= H[6 + j] * cy;
+                }
+                double h[3], v[3], d1[3], d2[3], nn[4] = {0, 0, 0, 0};
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    h[j] = H[3 * j];
+                    v[j] = H[3 * j + 1];
+                    d1[j] = (h[j] + v[j]) * 0.5;
+                    d2[j] = (h[j] - v[j]) * 0.5;
+                }
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    nn[0] += h[j] * h[j]; nn[1] += v[j] * v[j]; nn[2] += d1[j] * d1[j]; nn[3] += d2[j] * d2[j];
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) nn[j] = 1.0 / sqrt(nn[j]);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    h[j] *= nn[0]; v[j] *= nn[1]; d1[j] *= nn[2]; d2[j] *= nn[3];
+                }
+                r[0] = h[0] * v[0]; r[1] = h[1] * v[1]; r[2] = -h[2] * v[2];
+                r[3] = d1[0] * d2[0]; r[4] = d1[1] * d2[1]; r[5] = -d1[2] * d2[2];
+#pragma unroll
+                for (int j = 0; j < 6; ++j)
+                    if (!isfinite(r[j])) st = DCX_PNP_NONFINITE;
+                if (st != DCX_PNP_OK) {
+#pragma unroll
+                    for (int j = 0; j < 6; ++j) r[j] = 0.0;
+                }
+            }
+        }
+    }
+    if (lane == 0) {
+        status[b] = st;
+#pragma unroll
+        for (int i = 0; i < 7; ++i) pose[8 * (long long)b + i] = 0.0;
+        pose[8 * (long long)b + 7] = (double)n;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) ws.rows[(long long)b * kRows + i] = r[i];
+    }
+}
+
+// Fixed-order tree over the kRedThreads partials in s (LDS), NV values per thread; the totals end in s[0..NV).
+template <int NV>
+__device__ __forceinline__ void block_tree(double (*s)[NV]) {
+    const int t = threadIdx.x;
+    for (int h = kRedThreads / 2; h >= 1; h >>= 1) {
+        __syncthreads();
+        if (t < h) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) s[t][j] += s[t + h][j];
+        }
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kRedThreads) void calib_init_reduce_kernel(int batch, double cx, double cy,
+                                                                        const int32_t* __restrict__ status,
+                                                                        const double* __restrict__ pose, Ws ws) {
+    __shared__ double s[kRedThreads][7];    // a00 a01 a11 b0 b1, views, points
+    const int t = threadIdx.x;
+    double a[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (int b = t; b < batch; b += kRedThreads) {
+        if (status[b] != DCX_PNP_OK) continue;
+        const double* r = ws.rows + (long long)b * kRows;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const double a0 = r[3 * k], a1 = r[3 * k + 1], bb = r[3 * k + 2];
+            a[0] += a0 * a0; a[1] += a0 * a1; a[2] += a1 * a1; a[3] += a0 * bb; a[4] += a1 * bb;
+        }
+        a[5] += 1.0;
+        a[6] += pose[8 * (long long)b + 7];
+    }
+#pragma unroll
+    for (int j = 0; j < 7; ++j) s[t][j] = a[j];
+    block_tree<7>(s);
+    if (t != 0) return;
+    CalibState* st = ws.st;
+    const double a00 = s[0][0], a01 = s[0][1], a11 = s[0][2], b0 = s[0][3], b1 = s[0][4];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) st->result[i] = 0.0;
+    st->lg = -3;
+    st->iters = 0;
+    st->attempts = 0;
+    st->result[12] = s[0][5];
+    st->result[13] = s[0][6];
+    if (s[0][5] == 0.0) {
+        st->result[14] = DCX_CALIB_NO_VIEWS;
+        st->code = kFinished;
+        return;
+    }
+    const double det = a00 * a11 - a01 * a01;
+    const double f0 = (a11 * b0 - a01 * b1) / det, f1 = (a00 * b1 - a01 * b0) / det;
+    const double fx = f0 != 0.0 ? sqrt(fabs(1.0 / f0)) : INFINITY, fy = f1 != 0.0 ? sqrt(fabs(1.0 / f1)) : INFINITY;
+    if (!(det > 1e-12 * a00 * a11) || !(isfinite(fx) && isfinite(fy) && fx > 0 && fy > 0)) {
+        st->result[14] = DCX_CALIB_DEGENERATE;
+        st->code = kFinished;
+        return;
+    }
+    const double th[9] = {fx, fy, cx, cy, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < 9; ++i) st->theta[i] = th[i];
+    st->code = kNextEvaluate;
+}
+
+__global__ __launch_bounds__(kLanes) void calib_init_poses_kernel(Pool pl, int32_t* __restrict__ status, Ws ws) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (ws.st->code == kFinished || status[b] != DCX_PNP_OK) return;
+    const PnpCamera cam = camera_of(ws.st->theta);       // K0, zero distortion
+    double out[8];
+    const int st = solve(pl.frame(b), cam, out);
+    if (lane == 0) {
+        if (st != DCX_PNP_OK) status[b] = st;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) ws.pose[(long long)b * 6 + i] = st == DCX_PNP_OK ? out[i] : 0.0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- LM
+
+// One point's projection at (theta, pose) -> residual (ru, rv); with JAC its two rows of [J_theta | J_pose] (pnp._project's pose
+// columns, calib._project_full's intrinsic columns).  false if the point is not in front of the camera.
+template <bool JAC>
+__device__ __forceinline__ bool project_point(const PnpCamera& cam, const double* p, const double* R, const double (*G)[9], double mx,
+                                              double my, double u, double v, double& ru, double& rv, double* ju, double* jv) {
+    const double X = R[0] * mx + R[1] * my + p[3];
+    const double Y = R[3] * mx + R[4] * my + p[4];
+    const double Z = R[6] * mx + R[7] * my + p[5];
+    if (!(Z > 0)) return false;
+    const double* k = cam.k;
+    const double iz = 1.0 / Z, x = X * iz, y = Y * iz;
+    const double r2 = x * x + y * y;
+    const double num = 1 + r2 * (k[0] + r2 * (k[1] + r2 * k[4]));
+    const double den = 1 + r2 * (k[5] + r2 * (k[6] + r2 * k[7]));
+    const double g = num / den;
+    const double xd = x * g + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x);
+    const double yd = y * g + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y;
+    ru = cam.fx * xd + cam.cx - u;
+    rv = cam.fy * yd + cam.cy - v;
+    if (!JAC) return true;
+    const double r4 = r2 * r2, r6 = r2 * r2 * r2;
+    ju[0] = xd;  ju[1] = 0.0; ju[2] = 1.0; ju[3] = 0.0;
+    jv[0] = 0.0; jv[1] = yd;  jv[2] = 0.0; jv[3] = 1.0;
+    ju[4] = cam.fx * (x * r2);            jv[4] = cam.fy * (y * r2);
+    ju[5] = cam.fx * (x * r4);            jv[5] = cam.fy * (y * r4);
+    ju[6] = cam.fx * (2 * x * y);         jv[6] = cam.fy * (r2 + 2 * y * y);
+    ju[7] = cam.fx * (r2 + 2 * x * x);    jv[7] = cam.fy * (2 * x * y);
+    ju[8] = cam.fx * (x * r6);            jv[8] = cam.fy * (y * r6);
+    const double dg = ((k[0] + r2 * (2 * k[1] + 3 * k[4] * r2)) * den - num * (k[5] + r2 * (2 * k[6] + 3 * k[7] * r2))) / (den * den);
+    const double dxd_dx = g + 2 * x * x * dg + 2 * k[2] * y + 6 * k[3] * x;
+    const double dxd_dy = 2 * x * y * dg + 2 * k[2] * x + 2 * k[3] * y;
+    const double dyd_dx = dxd_dy;
+    const double dyd_dy = g + 2 * y * y * dg + 6 * k[2] * y + 2 * k[3] * x;
+    const double a0 = cam.fx * dxd_dx, a1 = cam.fx * dxd_dy, b0 = cam.fy * dyd_dx, b1 = cam.fy * dyd_dy;
+    const double du[3] = {a0 * iz, a1 * iz, -(a0 * x + a1 * y) * iz};
+    const double dv[3] = {b0 * iz, b1 * iz, -(b0 * x + b1 * y) * iz};
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        double su = 0.0, sv = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double dX = mx * G[0][c * 3 + j] + my * G[1][c * 3 + j];
+            su += du[c] * dX;
+            sv += dv[c] * dX;
+        }
+        ju[9 + j] = su;
+        jv[9 + j] = sv;
+        ju[12 + j] = du[j];
+        jv[12 + j] = dv[j];
+    }
+    return true;
+}
+
+// R(p) and G[c] = -R [e_c]x Jr(p): d(R m)/dr for the board point m = e_c (the board has z = 0)
+__device__ __forceinline__ void pose_basis(const double* p, double* R, double (*G)[9]) {
+    double Jr[9];
+    rodrigues(p, R);
+    right_jacobian(p, Jr);
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        double E[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // [e_c]x
+        if (c == 0) { E[5] = -1.0; E[7] = 1.0; } else { E[2] = 1.0; E[6] = -1.0; }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                double s = 0.0;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    double ej = 0.0;
+#pragma unroll
+                    for (int l = 0; l < 3; ++l) ej += E[k * 3 + l] * Jr[l * 3 + j];
+                    s += R[i * 3 + k] * ej;
+                }
+                G[c][i * 3 + j] = -s;
+            }
+    }
+}
+
+constexpr int kLdsStride = 17;     // 16 values per row, padded
+
+__global__ __launch_bounds__(kLanes) void calib_evaluate_kernel(Pool pl, const int32_t* __restrict__ status, Ws ws) {
+    __shared__ double sj[2 * kLanes][kLdsStride];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (ws.st->code != kNextEvaluate || status[b] != DCX_PNP_OK) return;
+    const Frame f = pl.frame(b);
+    const PnpCamera cam = camera_of(ws.st->theta);
+    double p[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) p[i] = ws.pose[(long long)b * 6 + i];
+    double R[9], G[2][9];
+    pose_basis(p, R, G);
+    // the entries this lane owns: e = lane + 64 q, (ea, eb) its row and column in the packed 16 x 16
+    int ea[3], eb[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        ea[q] = eb[q] = -1;
+        const int e = lane + kLanes * q;
+        if (e >= kEntries) continue;
+        int a = 0, first = 0;
+        while (first + (16 - a) <= e) { first += 16 - a; ++a; }
+        ea[q] = a;
+        eb[q] = a + (e - first);
+    }
+    double acc[3] = {0, 0, 0};
+    bool behind = false;
+    for (int c0 = 0; c0 < f.n; c0 += kLanes) {
+        const int i = c0 + lane;
+        double ju[16], jv[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) ju[j] = jv[j] = 0.0;
+        if (i < f.n) {
+            double mx, my, u, v, ru, rv;
+            f.load(i, mx, my, u, v);
+            if (project_point<true>(cam, p, R, G, mx, my, u, v, ru, rv, ju, jv)) {
+                ju[15] = ru;
+                jv[15] = rv;
+            } else {
+                behind = true;
+#pragma unroll
+                for (int j = 0; j < 16; ++j) ju[j] = jv[j] = 0.0;
+            }
+        }
+        __syncthreads();                     // the previous chunk's rows have been read
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            sj[2 * lane][j] = ju[j];
+            sj[2 * lane + 1][j] = jv[j];
+        }
+        __syncthreads();
+        const int rows = 2 * min(kLanes, f.n - c0);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            if (ea[q] < 0) continue;
+            double s = acc[q];
+            for (int r = 0; r < rows; ++r) s += sj[r][ea[q]] * sj[r][eb[q]];
+            acc[q] = s;
+        }
+    }
+    const bool inf = __any(behind);
+    double* m = ws.m + (long long)b * kEntries;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int e = lane + kLanes * q;
+        if (e < kEntries) m[e] = (e == kCost && inf) ? INFINITY : acc[q];
+    }
+}
+
+// 6x6 Cholesky of u (packed) with its diagonal scaled by `scale` -> L (packed); false if not positive definite
+__device__ __forceinline__ bool cholesky6(const double* u, double scale, double* L) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            double s = u[pk<6>(i, j)] * (i == j ? scale : 1.0);
+#pragma unroll
+            for (int k = 0; k < j; ++k) s -= L[pk<6>(i, k)] * L[pk<6>(j, k)];
+            if (i == j) {
+                if (!(s > 0)) return false;
+                L[pk<6>(i, i)] = sqrt(s);
+            } else {
+                L[pk<6>(i, j)] = s / L[pk<6>(j, j)];
+            }
+        }
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(kLanes) void calib_schur_kernel(const int32_t* __restrict__ status, Ws ws) {
+    __shared__ double sy[10][6];             // U*^-1 W^T's 9 columns, then U*^-1 g_b
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (ws.st->code == kFinished || status[b] != DCX_PNP_OK) return;
+    const double scale = 1.0 + pow(10.0, (double)ws.st->lg);
+    const double* m = ws.m + (long long)b * kEntries;
+    double u[21], L[21];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) u[pk<6>(i, j)] = m[pk<16>(9 + i, 9 + j)];
+    const bool ok = cholesky6(u, scale, L);
+    if (lane == 0) ws.fail[b] = ok ? 0 : 1;
+    double* sc = ws.sc + (long long)b * kSC;
+    if (!ok) {
+        if (lane < kSC) sc[lane] = 0.0;
+        return;
+    }
+    if (lane < 10) {                         // lane j < 9: column j of U*^-1 W^T (rhs = row j of W); lane 9: U*^-1 g_b
+        double rhs[6], y[6], x[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) rhs[k] = lane < 9 ? m[pk<16>(lane, 9 + k)] : m[pk<16>(9 + k, 15)];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            double s = rhs[i];
+#pragma unroll
+            for (int k = 0; k < i; ++k) s -= L[pk<6>(i, k)] * y[k];
+            y[i] = s / L[pk<6>(i, i)];
+        }
+#pragma unroll
+        for (int i = 5; i >= 0; --i) {
+            double s = y[i];
+#pragma unroll
+            for (int k = i + 1; k < 6; ++k) s -= L[pk<6>(k, i)] * x[k];
+            x[i] = s / L[pk<6>(i, i)];
+        }
+        double* yz = ws.yz + (long long)b * kYZ;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            sy[lane][k] = x[k];
+            if (lane < 9) yz[k * 9 + lane] = x[k];
+            else yz[54 + k] = x[k];
+        }
+    }
+    __syncthreads();
+    if (lane < kSC) {                        // entries 0..44: S_i = W U*^-1 W^T (packed 9x9); 45..53: W U*^-1 g_b
+        int a, c;
+        if (lane < 45) {
+            a = 0;
+            int first = 0;
+            while (first + (9 - a) <= lane) { first += 9 - a; ++a; }
+            c = a + (lane - first);
+        } else {
+            a = lane - 45;
+            c = 9;
+        }
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s += m[pk<16>(a, 9 + k)] * sy[c][k];
+        sc[lane] = s;
+    }
+}
+
+// the step could not be solved: the outputs stay zero but for the counts
+__device__ __forceinline__ void fail(CalibState* st, int status) {
+    st->result[10] = st->iters;
+    st->result[11] = st->attempts;
+    st->result[14] = status;
+    st->code = kFinished;
+}
+
+__global__ __launch_bounds__(kRedThreads) void calib_reduce_solve_kernel(int batch, const int32_t* __restrict__ status, Ws ws) {
+    constexpr int kTot = 108;                // sum V (45), sum g_a (9), sum S_i (45), sum W U*^-1 g_b (9)
+    __shared__ double part[kSlices][kTot];
+    __shared__ int bad[kSlices];
+    // thread 0's small dense solve, indexed in loops: kept in LDS rather than in (scratch-backed) private arrays
+    __shared__ double tot[kTot], S[45], L[45], rhs[9], y[9], x[9];
+    CalibState* st = ws.st;
+    if (st->code == kFinished) return;
+    const int t = threadIdx.x, e = t % 128, sl = t / 128;
+    if (e < kTot) {
+        int src;                             // where entry e lives: in the view's 136 (m) or in its Schur part (sc)
+        if (e < 45) {
+            int a = 0, first = 0;
+            while (first + (9 - a) <= e) { first += 9 - a; ++a; }
+            src = pk<16>(a, a + (e - first));
+        } else if (e < 54) {
+            src = pk<16>(e - 45, 15);
+        } else {
+            src = e - 54;
+        }
+        double s = 0.0;
+        int f = 0;
+        for (int b = sl; b < batch; b += kSlices) {
+            if (status[b] != DCX_PNP_OK) continue;
+            s += e < 54 ? ws.m[(long long)b * kEntries + src] : ws.sc[(long long)b * kSC + src];
+            if (e == 0) f |= ws.fail[b];
+        }
+        part[sl][e] = s;
+        if (e == 0) bad[sl] = f;
+    }
+    __syncthreads();
+    if (t != 0) return;
+    int anybad = 0;
+    for (int i = 0; i < kTot; ++i) {
+        double s = 0.0;
+        for (int k = 0; k < kSlices; ++k) s += part[k][i];
+        tot[i] = s;
+    }
+    for (int k = 0; k < kSlices; ++k) anybad |= bad[k];
+    if (anybad) {
+        fail(st, DCX_CALIB_DEGENERATE);
+        return;
+    }
+    const double scale = 1.0 + pow(10.0, (double)st->lg);
+    for (int a = 0; a < 9; ++a) {
+        for (int c = a; c < 9; ++c) S[pk<9>(a, c)] = tot[pk<9>(a, c)] * (a == c ? scale : 1.0) - tot[54 + pk<9>(a, c)];
+        rhs[a] = tot[45 + a] - tot[99 + a];
+    }
+    for (int i = 0; i < 9; ++i) {
+        for (int j = 0; j <= i; ++j) {
+            double s = S[pk<9>(i, j)];
+            for (int k = 0; k < j; ++k) s -= L[pk<9>(i, k)] * L[pk<9>(j, k)];
+            if (i == j) {
+                if (!(s > 0)) {
+                    fail(st, DCX_CALIB_DEGENERATE);
+                    return;
+                }
+                L[pk<9>(i, i)] = sqrt(s);
+            } else {
+                L[pk<9>(i, j)] = s / L[pk<9>(j, j)];
+            }
+        }
+    }
+    for (int i = 0; i < 9; ++i) {
+        double s = rhs[i];
+        for (int k = 0; k < i; ++k) s -= L[pk<9>(i, k)] * y[k];
+        y[i] = s / L[pk<9>(i, i)];
+    }
+    for (int i = 8; i >= 0; --i) {
+        double s = y[i];
+        for (int k = i + 1; k < 9; ++k) s -= L[pk<9>(k, i)] * x[k];
+        x[i] = s / L[pk<9>(i, i)];
+    }
+    for (int i = 0; i < 9; ++i) {
+        st->dtheta[i] = x[i];
+        st->theta_trial[i] = st->theta[i] - x[i];
+    }
+}
+
+__global__ __launch_bounds__(kLanes) void calib_trial_kernel(Pool pl, const int32_t* __restrict__ status, Ws ws) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (ws.st->code == kFinished || status[b] != DCX_PNP_OK) return;
+    const double* yz = ws.yz + (long long)b * kYZ;
+    double p0[6], p[6];
+    double dn = 0.0, pn = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        double s = yz[54 + k];
+#pragma unroll
+        for (int j = 0; j < 9; ++j) s -= yz[k * 9 + j] * ws.st->dtheta[j];
+        p0[k] = ws.pose[(long long)b * 6 + k];
+        p[k] = p0[k] - s;
+        dn += (p[k] - p0[k]) * (p[k] - p0[k]);
+        pn += p0[k] * p0[k];
+    }
+    const PnpCamera cam = camera_of(ws.st->theta_trial);
+    const Frame f = pl.frame(b);
+    double R[9];
+    rodrigues(p, R);
+    double c[1] = {0.0};
+    for (int i = lane; i < f.n; i += kLanes) {
+        double mx, my, u, v, ru, rv;
+        f.load(i, mx, my, u, v);
+        if (!project_point<false>(cam, p, R, nullptr, mx, my, u, v, ru, rv, nullptr, nullptr)) {
+            c[0] = INFINITY;
+            continue;
+        }
+        c[0] += ru * ru + rv * rv;
+    }
+    wave_sum(c);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) ws.trial_pose[(long long)b * 6 + k] = p[k];
+        ws.trial[(long long)b * 3 + 0] = c[0];
+        ws.trial[(long long)b * 3 + 1] = dn;
+        ws.trial[(long long)b * 3 + 2] = pn;
+    }
+}
+
+// init = 1: after the first evaluate (the initial cost); init = 0: after a trial
+__global__ __launch_bounds__(kRedThreads) void calib_decide_kernel(int batch, int init, const int32_t* __restrict__ status,
+                                                                   double* __restrict__ pose, Ws ws) {
+    __shared__ double s[kRedThreads][6];     // cost, |dp|^2, |p|^2, views, points, non-finite poses
+    __shared__ int verdict;                  // 0: nothing to commit, 1: commit and continue, 2: commit and finish
+    CalibState* st = ws.st;
+    if (st->code == kFinished) return;
+    const int t = threadIdx.x;
+    double a[6] = {0, 0, 0, 0, 0, 0};
+    for (int b = t; b < batch; b += kRedThreads) {
+        if (status[b] != DCX_PNP_OK) continue;
+        if (init) {
+            a[0] += ws.m[(long long)b * kEntries + kCost];
+        } else {
+            const double* tr = ws.trial + (long long)b * 3;
+            a[0] += tr[0]; a[1] += tr[1]; a[2] += tr[2];
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+                if (!isfinite(ws.trial_pose[(long long)b * 6 + k])) a[5] = 1.0;
+        }
+        a[3] += 1.0;
+        a[4] += pose[8 * (long long)b + 7];
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) s[t][j] = a[j];
+    block_tree<6>(s);
+    const double cost = s[0][0], views = s[0][3], points = s[0][4];
+    if (t == 0) {
+        verdict = 0;
+        st->result[12] = views;
+        st->result[13] = points;
+        if (init) {
+            if (views == 0.0) {
+                st->result[14] = DCX_CALIB_NO_VIEWS;
+                st->code = kFinished;
+            } else if (!isfinite(cost)) {
+                st->result[14] = DCX_CALIB_DEGENERATE;
+                st->code = kFinished;
+            } else {
+                st->prev_cost = cost;
+                st->code = kNextSchur;
+            }
+        } else {
+            st->attempts += 1;
+            bool forced = false;
+            if (!(cost <= st->prev_cost)) {  // (a point behind the camera: cost = inf, rejected like an increase)
+                if (++st->lg <= 16) {
+                    st->code = kNextSchur;   // retry from the same point with more damping
+                } else {
+                    forced = true;
+                }
+            } else {
+                forced = true;
+            }
+            if (forced) {
+                st->lg = max(st->lg - 1, -16);
+                st->iters += 1;
+                double dn = s[0][1], pn = s[0][2];
+                bool bad = s[0][5] != 0.0;
+                for (int i = 0; i < 9; ++i) {
+                    const double d = st->theta_trial[i] - st->theta[i];
+                    dn += d * d;
+                    pn += st->theta[i] * st->theta[i];
+                    st->theta[i] = st->theta_trial[i];
+                    bad |= !isfinite(st->theta[i]);
+                }
+                if (st->iters >= kCalibMaxIter || sqrt(dn) < kCalibEps * sqrt(pn)) {
+                    int res = DCX_CALIB_OK;
+                    if (bad || isnan(cost)) res = DCX_CALIB_NONFINITE;
+                    else if (!isfinite(cost)) res = DCX_CALIB_DEGENERATE;
+                    if (res == DCX_CALIB_OK) {
+                        for (int i = 0; i < 9; ++i) st->result[i] = st->theta[i];
+                        st->result[9] = sqrt(cost / points);
+                    }
+                    st->result[10] = st->iters;
+                    st->result[11] = st->attempts;
+                    st->result[14] = res;
+                    st->code = kFinished;
+                    verdict = res == DCX_CALIB_OK ? 2 : 1;
+                } else {
+                    st->prev_cost = cost;
+                    st->code = kNextEvaluate;
+                    verdict = 1;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (verdict == 0) return;
+    for (int b = t; b < batch; b += kRedThreads) {
+        if (status[b] != DCX_PNP_OK) continue;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) ws.pose[(long long)b * 6 + k] = ws.trial_pose[(long long)b * 6 + k];
+        if (verdict == 2) {
+            double* o = pose + 8 * (long long)b;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) o[k] = ws.trial_pose[(long long)b * 6 + k];
+            o[6] = sqrt(ws.trial[(long long)b * 3] / o[7]);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" size_t dcx_calibrate_workspace_bytes(int batch) { return ws_bytes(batch); }
+
+extern "C" int dcx_calibrate_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows, const float* d_xy,
+                                  int batch, int pool, int col_count, int row_count, double square_len, int image_width,
+                                  int image_height, void* d_workspace, size_t workspace_bytes, int32_t* d_view_status,
+                                  double* d_pose, double* h_result, void* stream) {
+    if (!d_counts || !d_starts || !d_rows || !d_workspace || !d_view_status || !d_pose || !h_result) return DCX_E_ARG;
+    if (batch <= 0 || pool < 0 || col_count < 2 || row_count < 2 || image_width <= 0 || image_height <= 0) return DCX_E_ARG;
+    if ((long long)(col_count - 1) * (row_count - 1) > 0x7fffffffLL) return DCX_E_ARG;
+    if (!isfinite(square_len)) return DCX_E_ARG;
+    if (workspace_bytes < ws_bytes(batch)) return DCX_E_WS;
+    hipStream_t s = (hipStream_t)stream;
+    const Ws ws(d_workspace, batch);
+    const Pool pl{d_counts, d_starts, d_rows, d_xy, row_count - 1, square_len};
+    const double cx = (image_width - 1) * 0.5, cy = (image_height - 1) * 0.5;
+    const dim3 views((unsigned)batch), wave(kLanes), one(1), red(kRedThreads);
+    hipLaunchKernelGGL(calib_init_views_kernel, views, wave, 0, s, pl, pool, (col_count - 1) * (row_count - 1), cx, cy, d_view_status,
+                       d_pose, ws);
+    hipLaunchKernelGGL(calib_init_reduce_kernel, one, red, 0, s, batch, cx, cy, d_view_status, d_pose, ws);
+    hipLaunchKernelGGL(calib_init_poses_kernel, views, wave, 0, s, pl, d_view_status, ws);
+    hipLaunchKernelGGL(calib_evaluate_kernel, views, wave, 0, s, pl, d_view_status, ws);
+    hipLaunchKernelGGL(calib_decide_kernel, one, red, 0, s, batch, 1, d_view_status, d_pose, ws);
+    DCX_CHECK_HIP(hipGetLastError());
+    // every attempt ends in decide, which increments `attempts` or finishes: at most 30 accepted steps, each after at most
+    // 20 rejections (lg from -3 climbs to 17), so the loop below always ends by the state word
+    for (int guard = 0; guard < kCalibMaxIter * 40; ++guard) {
+        int code = kFinished;
+        DCX_CHECK_HIP(hipMemcpyAsync(&code, &ws.st->code, sizeof(int), hipMemcpyDeviceToHost, s));
+        DCX_CHECK_HIP(hipStreamSynchronize(s));
+        if (code == kFinished) break;
+        if (code == kNextEvaluate) hipLaunchKernelGGL(calib_evaluate_kernel, views, wave, 0, s, pl, d_view_status, ws);
+        hipLaunchKernelGGL(calib_schur_kernel, views, wave, 0, s, d_view_status, ws);
+        hipLaunchKernelGGL(calib_reduce_solve_kernel, one, red, 0, s, batch, d_view_status, ws);
+        hipLaunchKernelGGL(calib_trial_kernel, views, wave, 0, s, pl, d_view_status, ws);
+        hipLaunchKernelGGL(calib_decide_kernel, one, red, 0, s, batch, 0, d_view_status, d_pose, ws);
+        DCX_CHECK_HIP(hipGetLastError());
+    }
+    DCX_CHECK_HIP(hipMemcpyAsync(h_result, ws.st->result, 16 * sizeof(double), hipMemcpyDeviceToHost, s));
+    DCX_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}

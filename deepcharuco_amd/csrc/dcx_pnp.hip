@@ -12,513 +12,9 @@
 // redundantly and takes the same branches: no LDS, no barrier.  The exception is the 9x9 Jacobi's eigenvector matrix: lane j keeps
 // row j of V (a rotation mixes two entries of every row, so no lane needs another's data), which keeps it out of 81 registers.
 // K and the distortion coefficients are kernel arguments (captured by value in a hipGraph); no allocation, no synchronisation.
-#include "dcx_common.h"
-
-#include <math.h>
+#include "dcx_pnp_dev.h"
 
 namespace {
-
-constexpr int kLanes = 64;
-constexpr int kLmMaxIter = 20;
-constexpr double kLmEps = 1.1920928955078125e-07;   // FLT_EPSILON
-constexpr int kUndistortIters = 5;
-constexpr int kJacobiMaxSweeps = 16;
-
-struct PnpCamera {
-    double fx, fy, cx, cy;
-    double k[8];            // k1 k2 p1 p2 k3 k4 k5 k6, zero padded
-};
-
-// packed upper triangle of a symmetric N x N matrix, row major
-template <int N>
-__device__ constexpr int pk(int i, int j) {
-    return i <= j ? i * N - i * (i - 1) / 2 + (j - i) : j * N - j * (j - 1) / 2 + (i - j);
-}
-
-template <int N>
-__device__ __forceinline__ void wave_sum(double (&a)[N]) {
-#pragma unroll
-    for (int m = kLanes / 2; m >= 1; m >>= 1) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) a[i] += __shfl_xor(a[i], m, kLanes);
-    }
-}
-
-// Cyclic Jacobi on the packed symmetric a (eigenvalues end on its diagonal).  v holds NR rows of V (a = V diag V^T); the caller
-// initialises them.  Same rotation formulas and order as pnp._jacobi.
-template <int N, int NR>
-__device__ __forceinline__ void jacobi(double (&a)[N * (N + 1) / 2], double (&v)[NR][N]) {
-#pragma unroll 1
-    for (int sweep = 0; sweep < kJacobiMaxSweeps; ++sweep) {
-        double off = 0.0, dia = 0.0;
-#pragma unroll
-        for (int p = 0; p < N; ++p) {
-            dia += a[pk<N>(p, p)] * a[pk<N>(p, p)];
-#pragma unroll
-            for (int q = p + 1; q < N; ++q) off += a[pk<N>(p, q)] * a[pk<N>(p, q)];
-        }
-        if (!(off > 1e-30 * dia)) break;
-#pragma unroll
-        for (int p = 0; p < N; ++p) {
-#pragma unroll
-            for (int q = p + 1; q < N; ++q) {
-                const double apq = a[pk<N>(p, q)], app = a[pk<N>(p, p)], aqq = a[pk<N>(q, q)];
-                double t = 0.0;
-                if (apq != 0.0) {
-                    const double theta = (aqq - app) / (2.0 * apq);
-                    t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    if (theta < 0) t = -t;
-                }
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                // columns p, q, then rows p, q (the 2x2 block in two steps, as the host does on the full matrix)
-                const double bpp = c * app - s * apq, bpq = s * app + c * apq;
-                const double bqp = c * apq - s * aqq, bqq = s * apq + c * aqq;
-#pragma unroll
-                for (int r = 0; r < N; ++r) {
-                    if (r == p || r == q) continue;
-                    const double arp = a[pk<N>(r, p)], arq = a[pk<N>(r, q)];
-                    a[pk<N>(r, p)] = c * arp - s * arq;
-                    a[pk<N>(r, q)] = s * arp + c * arq;
-                }
-                a[pk<N>(p, p)] = c * bpp - s * bqp;
-                a[pk<N>(q, q)] = s * bpq + c * bqq;
-                a[pk<N>(p, q)] = 0.0;
-#pragma unroll
-                for (int r = 0; r < NR; ++r) {
-                    const double vp = v[r][p], vq = v[r][q];
-                    v[r][p] = c * vp - s * vq;
-                    v[r][q] = s * vp + c * vq;
-                }
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ void rodrigues(const double* r, double* R) {
-    const double th = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-    if (!(th >= 1e-300)) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
-        return;
-    }
-    const double kx = r[0] / th, ky = r[1] / th, kz = r[2] / th;
-    const double sn = sin(th), cs = 1.0 - cos(th);
-    // I + sin K + (1 - cos) K^2,  K^2 = k k^T - I
-    R[0] = 1.0 + cs * (kx * kx - 1.0); R[1] = -sn * kz + cs * kx * ky; R[2] = sn * ky + cs * kx * kz;
-    R[3] = sn * kz + cs * kx * ky;     R[4] = 1.0 + cs * (ky * ky - 1.0); R[5] = -sn * kx + cs * ky * kz;
-    R[6] = -sn * ky + cs * kx * kz;    R[7] = sn * kx + cs * ky * kz;     R[8] = 1.0 + cs * (kz * kz - 1.0);
-}
-
-// rotation vector of an orthonormal matrix: cvRodrigues2's matrix -> vector branch after its SVD
-__device__ __forceinline__ void rvec_of(const double* R, double* r) {
-    const double rx = R[7] - R[5], ry = R[2] - R[6], rz = R[3] - R[1];
-    const double s = sqrt((rx * rx + ry * ry + rz * rz) * 0.25);
-    const double c = fmin(fmax((R[0] + R[4] + R[8] - 1.0) * 0.5, -1.0), 1.0);
-    const double theta = acos(c);
-    if (s < 1e-5) {
-        if (c > 0) { r[0] = r[1] = r[2] = 0.0; return; }
-        double x = sqrt(fmax((R[0] + 1.0) * 0.5, 0.0));
-        double y = sqrt(fmax((R[4] + 1.0) * 0.5, 0.0)) * (R[1] < 0 ? -1.0 : 1.0);
-        double z = sqrt(fmax((R[8] + 1.0) * 0.5, 0.0)) * (R[2] < 0 ? -1.0 : 1.0);
-        if (fabs(x) < fabs(y) && fabs(x) < fabs(z) && ((R[5] > 0) != (y * z > 0))) z = -z;
-        const double f = M_PI / sqrt(x * x + y * y + z * z);
-        r[0] = x * f; r[1] = y * f; r[2] = z * f;
-        return;
-    }
-    const double f = theta / (2.0 * s);
-    r[0] = rx * f; r[1] = ry * f; r[2] = rz * f;
-}
-
-// right Jacobian of SO(3): d(R(r) u)/dr = -R [u]x Jr(r)
-__device__ __forceinline__ void right_jacobian(const double* r, double* J) {
-    const double th2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-    double a, b;
-    if (th2 < 1e-8) {
-        a = 0.5 - th2 / 24.0;
-        b = 1.0 / 6.0 - th2 / 120.0;
-    } else {
-        const double th = sqrt(th2);
-        a = (1.0 - cos(th)) / th2;
-        b = (th - sin(th)) / (th2 * th);
-    }
-    const double S[9] = {0.0, -r[2], r[1], r[2], 0.0, -r[0], -r[1], r[0], 0.0};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double s2 = 0.0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) s2 += S[i * 3 + k] * S[k * 3 + j];
-            J[i * 3 + j] = (i == j ? 1.0 : 0.0) - a * S[i * 3 + j] + b * s2;
-        }
-}
-
-struct Frame {
-    const int32_t* rows;     // this frame's rows (x, y, id, cell), n of them
-    const float* xy;         // this frame's refined xy, or null
-    int n;
-    int rm1;                 // row_count - 1
-    double square_len;
-
-    // board point (float32-rounded as inference.py:20-26's np.float32 table) and image point (float32, inference.py:27)
-    __device__ __forceinline__ void load(int i, double& X, double& Y, double& u, double& v) const {
-        const int id = rows[4 * i + 2];
-        X = (double)__double2float_rn((double)(1 + id % rm1) * square_len);
-        Y = (double)__double2float_rn((double)(1 + id / rm1) * square_len);
-        if (xy) {
-            u = (double)xy[2 * i];
-            v = (double)xy[2 * i + 1];
-        } else {
-            u = (double)(float)rows[4 * i];
-            v = (double)(float)rows[4 * i + 1];
-        }
-    }
-};
-
-__device__ __forceinline__ void undistort(const PnpCamera& cam, bool dist, double u, double v, double& x, double& y) {
-    const double x0 = (u - cam.cx) / cam.fx, y0 = (v - cam.cy) / cam.fy;
-    x = x0;
-    y = y0;
-    if (!dist) return;
-    const double* k = cam.k;
-    for (int it = 0; it < kUndistortIters; ++it) {
-        const double r2 = x * x + y * y;
-        const double icdist = (1 + ((k[7] * r2 + k[6]) * r2 + k[5]) * r2) / (1 + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2);
-        if (icdist < 0) {
-            x = x0;
-            y = y0;
-            break;
-        }
-        const double dx = 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x);
-        const double dy = k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y;
-        x = (x0 - dx) * icdist;
-        y = (y0 - dy) * icdist;
-    }
-}
-
-// Sum over the frame's points of the squared reprojection error at pose p (+inf if a point is not in front of the camera) and,
-// with JAC, of JtJ (21, packed) and Jtr (6).  acc = {cost, JtJ[21], Jtr[6]} on return, identical in every lane.
-template <bool JAC>
-__device__ __forceinline__ void evaluate(const Frame& f, const PnpCamera& cam, const double* p, double (&acc)[28]) {
-    double R[9], G[2][9];           // G[c] = -R [e_c]x Jr: d(R m)/dr for the board point m = e_c (the board has z = 0)
-    rodrigues(p, R);
-    if (JAC) {
-        double Jr[9];
-        right_jacobian(p, Jr);
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            double E[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // [e_c]x
-            if (c == 0) { E[5] = -1.0; E[7] = 1.0; } else { E[2] = 1.0; E[6] = -1.0; }
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    double s = 0.0;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        double ej = 0.0;
-#pragma unroll
-                        for (int l = 0; l < 3; ++l) ej += E[k * 3 + l] * Jr[l * 3 + j];
-                        s += R[i * 3 + k] * ej;
-                    }
-                    G[c][i * 3 + j] = -s;
-                }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 28; ++i) acc[i] = 0.0;
-    const double* k = cam.k;
-    for (int i = threadIdx.x; i < f.n; i += kLanes) {
-        double mx, my, u, v;
-        f.load(i, mx, my, u, v);
-        const double X = R[0] * mx + R[1] * my + p[3];
-        const double Y = R[3] * mx + R[4] * my + p[4];
-        const double Z = R[6] * mx + R[7] * my + p[5];
-        if (!(Z > 0)) {
-            acc[0] = INFINITY;
-            continue;
-        }
-        const double iz = 1.0 / Z, x = X * iz, y = Y * iz;
-        const double r2 = x * x + y * y;
-        const double num = 1 + r2 * (k[0] + r2 * (k[1] + r2 * k[4]));
-        const double den = 1 + r2 * (k[5] + r2 * (k[6] + r2 * k[7]));
-        const double g = num / den;
-        const double xd = x * g + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x);
-        const double yd = y * g + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y;
-        const double ru = cam.fx * xd + cam.cx - u, rv = cam.fy * yd + cam.cy - v;
-        acc[0] += ru * ru + rv * rv;
-        if (!JAC) continue;
-        const double dg = ((k[0] + r2 * (2 * k[1] + 3 * k[4] * r2)) * den - num * (k[5] + r2 * (2 * k[6] + 3 * k[7] * r2))) / (den * den);
-        const double dxd_dx = g + 2 * x * x * dg + 2 * k[2] * y + 6 * k[3] * x;
-        const double dxd_dy = 2 * x * y * dg + 2 * k[2] * x + 2 * k[3] * y;
-        const double dyd_dx = dxd_dy;
-        const double dyd_dy = g + 2 * y * y * dg + 6 * k[2] * y + 2 * k[3] * x;
-        // d(u, v)/d(X, Y, Z)
-        const double a0 = cam.fx * dxd_dx, a1 = cam.fx * dxd_dy, b0 = cam.fy * dyd_dx, b1 = cam.fy * dyd_dy;
-        const double du[3] = {a0 * iz, a1 * iz, -(a0 * x + a1 * y) * iz};
-        const double dv[3] = {b0 * iz, b1 * iz, -(b0 * x + b1 * y) * iz};
-        double ju[6], jv[6];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double su = 0.0, sv = 0.0;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const double dX = mx * G[0][c * 3 + j] + my * G[1][c * 3 + j];
-                su += du[c] * dX;
-                sv += dv[c] * dX;
-            }
-            ju[j] = su;
-            jv[j] = sv;
-            ju[3 + j] = du[j];
-            jv[3 + j] = dv[j];
-        }
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-#pragma unroll
-            for (int b = a; b < 6; ++b) acc[1 + pk<6>(a, b)] += ju[a] * ju[b] + jv[a] * jv[b];
-            acc[22 + a] += ju[a] * ru + jv[a] * rv;
-        }
-    }
-    wave_sum(acc);
-}
-
-// (JtJ with its diagonal scaled by 1 + lambda) x = Jtr by Cholesky; false if not positive definite
-__device__ __forceinline__ bool cholesky_solve(const double* jtj, const double* jtr, double scale, double* x) {
-    double L[21];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-            double s = jtj[pk<6>(i, j)] * (i == j ? scale : 1.0);
-#pragma unroll
-            for (int k = 0; k < j; ++k) s -= L[pk<6>(i, k)] * L[pk<6>(j, k)];
-            if (i == j) {
-                if (!(s > 0)) return false;
-                L[pk<6>(i, i)] = sqrt(s);
-            } else {
-                L[pk<6>(i, j)] = s / L[pk<6>(j, j)];
-            }
-        }
-    }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double s = jtr[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) s -= L[pk<6>(i, k)] * y[k];
-        y[i] = s / L[pk<6>(i, i)];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) s -= L[pk<6>(k, i)] * x[k];
-        x[i] = s / L[pk<6>(i, i)];
-    }
-    return true;
-}
-
-// Planar initialisation (pnp._init_pose) -> status; p0 = rvec, tvec
-__device__ __forceinline__ int init_pose(const Frame& f, const PnpCamera& cam, bool dist, double* p0) {
-    const int lane = threadIdx.x;
-    const double n = (double)f.n;
-    // centroids of the board points and of the normalised image points
-    double s1[4] = {0, 0, 0, 0};
-    for (int i = lane; i < f.n; i += kLanes) {
-        double mx, my, u, v, x, y;
-        f.load(i, mx, my, u, v);
-        undistort(cam, dist, u, v, x, y);
-        s1[0] += mx; s1[1] += my; s1[2] += x; s1[3] += y;
-    }
-    wave_sum(s1);
-    const double mcx = s1[0] / n, mcy = s1[1] / n, icx = s1[2] / n, icy = s1[3] / n;
-    // second moments of the centred board points (collinearity) and mean distances (Hartley scales)
-    double s2[5] = {0, 0, 0, 0, 0};
-    for (int i = lane; i < f.n; i += kLanes) {
-        double mx, my, u, v, x, y;
-        f.load(i, mx, my, u, v);
-        undistort(cam, dist, u, v, x, y);
-        const double X = mx - mcx, Y = my - mcy;
-        s2[0] += X * X; s2[1] += X * Y; s2[2] += Y * Y;
-        s2[3] += sqrt(X * X + Y * Y);
-        s2[4] += sqrt((x - icx) * (x - icx) + (y - icy) * (y - icy));
-    }
-    wave_sum(s2);
-    {
-        const double tr = s2[0] + s2[2], df = s2[0] - s2[2];
-        const double rt = sqrt(df * df + 4.0 * s2[1] * s2[1]);
-        const double e1 = 0.5 * (tr + rt), e0 = 0.5 * (tr - rt);
-        if (!(e0 > 1e-10 * e1)) return DCX_PNP_DEGENERATE;       // collinear board points
-    }
-    const double d1 = s2[3] / n, d2 = s2[4] / n;
-    const double sc1 = d1 > 0 ? M_SQRT2 / d1 : 0.0, sc2 = d2 > 0 ? M_SQRT2 / d2 : 0.0;
-    // DLT normal matrix of the Hartley-normalised correspondences
-    double M[45];
-#pragma unroll
-    for (int i = 0; i < 45; ++i) M[i] = 0.0;
-    for (int i = lane; i < f.n; i += kLanes) {
-        double mx, my, u, v, x, y;
-        f.load(i, mx, my, u, v);
-        undistort(cam, dist, u, v, x, y);
-        const double X = sc1 * (mx - mcx), Y = sc1 * (my - mcy);
-        const double xu = sc2 * (x - icx), yv = sc2 * (y - icy);
-        const double r1[9] = {X, Y, 1.0, 0.0, 0.0, 0.0, -xu * X, -xu * Y, -xu};
-        const double r2[9] = {0.0, 0.0, 0.0, X, Y, 1.0, -yv * X, -yv * Y, -yv};
-#pragma unroll
-        for (int a = 0; a < 9; ++a)
-#pragma unroll
-            for (int b = a; b < 9; ++b) M[pk<9>(a, b)] += r1[a] * r1[b] + r2[a] * r2[b];
-    }
-    wave_sum(M);
-    double vrow[1][9];               // row `lane` of the eigenvector matrix (lanes >= 9 carry a zero row)
-#pragma unroll
-    for (int c = 0; c < 9; ++c) vrow[0][c] = (c == lane) ? 1.0 : 0.0;
-    jacobi<9, 1>(M, vrow);
-    // smallest eigenvalue (first on ties), its eigenvector's entry in this lane's row, the next smallest and the largest |w|
-    int kmin = 0;
-    double wmin = M[pk<9>(0, 0)], wmax = fabs(wmin), e = vrow[0][0];
-#pragma unroll
-    for (int c = 1; c < 9; ++c) {
-        const double w = M[pk<9>(c, c)];
-        if (w < wmin) { wmin = w; kmin = c; e = vrow[0][c]; }
-        wmax = fmax(wmax, fabs(w));
-    }
-    double w2 = INFINITY;
-#pragma unroll
-    for (int c = 0; c < 9; ++c)
-        if (c != kmin) w2 = fmin(w2, M[pk<9>(c, c)]);
-    if (!(w2 > 1e-12 * wmax)) return DCX_PNP_DEGENERATE;           // two (near) null directions
-    double hn[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) hn[i] = __shfl(e, i, kLanes);
-    // H = T2^-1 Hn T1, T1 = diag(sc1, sc1, 1) on the centred board points, T2 = Hartley of the image points
-    double H[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const double ri0 = hn[i * 3 + 0] * sc1, ri1 = hn[i * 3 + 1] * sc1, ri2 = hn[i * 3 + 2];
-        H[i * 3 + 0] = ri0; H[i * 3 + 1] = ri1; H[i * 3 + 2] = ri2;
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const double h2 = H[6 + j];
-        H[0 + j] = H[0 + j] / sc2 + icx * h2;
-        H[3 + j] = H[3 + j] / sc2 + icy * h2;
-    }
-    double hmax = 0.0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) hmax = fmax(hmax, fabs(H[i]));
-    if (!(fabs(H[8]) > 1e-12 * hmax)) return DCX_PNP_DEGENERATE;
-    const double h22 = H[8];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) H[i] /= h22;
-    // OpenCV's decomposition (cvFindExtrinsicCameraParams2, planar branch)
-    const double n1 = sqrt(H[0] * H[0] + H[3] * H[3] + H[6] * H[6]);
-    const double n2 = sqrt(H[1] * H[1] + H[4] * H[4] + H[7] * H[7]);
-    const double i1 = 1.0 / fmax(n1, 2.2e-16), i2 = 1.0 / fmax(n2, 2.2e-16), it = 2.0 / fmax(n1 + n2, 2.2e-16);
-    double Rr[9];
-    Rr[0] = H[0] * i1; Rr[3] = H[3] * i1; Rr[6] = H[6] * i1;
-    Rr[1] = H[1] * i2; Rr[4] = H[4] * i2; Rr[7] = H[7] * i2;
-    Rr[2] = Rr[3] * Rr[7] - Rr[6] * Rr[4];
-    Rr[5] = Rr[6] * Rr[1] - Rr[0] * Rr[7];
-    Rr[8] = Rr[0] * Rr[4] - Rr[3] * Rr[1];
-    double t[3] = {H[2] * it, H[5] * it, H[8] * it};
-    // polar factor Rr (Rr^T Rr)^-1/2
-    double S[6], W[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = a; b < 3; ++b) S[pk<3>(a, b)] = Rr[a] * Rr[b] + Rr[3 + a] * Rr[3 + b] + Rr[6 + a] * Rr[6 + b];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) W[a][b] = a == b ? 1.0 : 0.0;
-    jacobi<3, 3>(S, W);
-    double iw[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double w = S[pk<3>(c, c)];
-        if (!(w > 0)) return DCX_PNP_DEGENERATE;
-        iw[c] = 1.0 / sqrt(w);
-    }
-    double P[9], Q[9];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) P[a * 3 + b] = W[a][0] * iw[0] * W[b][0] + W[a][1] * iw[1] * W[b][1] + W[a][2] * iw[2] * W[b][2];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) Q[a * 3 + b] = Rr[a * 3 + 0] * P[b] + Rr[a * 3 + 1] * P[3 + b] + Rr[a * 3 + 2] * P[6 + b];
-    rvec_of(Q, p0);
-    double R[9];
-    rodrigues(p0, R);
-    p0[3] = t[0] - (R[0] * mcx + R[1] * mcy);
-    p0[4] = t[1] - (R[3] * mcx + R[4] * mcy);
-    p0[5] = t[2] - (R[6] * mcx + R[7] * mcy);
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-        if (!isfinite(p0[i])) return DCX_PNP_NONFINITE;
-    return DCX_PNP_OK;
-}
-
-__device__ __forceinline__ int solve(const Frame& f, const PnpCamera& cam, double* pose) {
-    bool dist = false;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) dist |= cam.k[i] != 0.0;
-    double p[6];
-    int st = init_pose(f, cam, dist, p);
-    if (st != DCX_PNP_OK) return st;
-    double acc[28];
-    evaluate<true>(f, cam, p, acc);
-    if (!isfinite(acc[0])) return DCX_PNP_DEGENERATE;
-    double jtj[21], jtr[6];
-    double prev_cost = acc[0], cost = acc[0];
-    int lg = -3, iters = 0;
-#pragma unroll 1
-    while (true) {
-#pragma unroll
-        for (int i = 0; i < 21; ++i) jtj[i] = acc[1 + i];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) jtr[i] = acc[22 + i];
-        double prev[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) prev[i] = p[i];
-#pragma unroll 1
-        while (true) {
-            double x[6];
-            if (!cholesky_solve(jtj, jtr, 1.0 + pow(10.0, (double)lg), x)) return DCX_PNP_DEGENERATE;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) p[i] = prev[i] - x[i];
-            evaluate<false>(f, cam, p, acc);
-            cost = acc[0];
-            if (!(cost <= prev_cost)) {
-                if (++lg <= 16) continue;
-            }
-            break;
-        }
-        lg = max(lg - 1, -16);
-        ++iters;
-        double dn = 0.0, pn = 0.0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            dn += (p[i] - prev[i]) * (p[i] - prev[i]);
-            pn += prev[i] * prev[i];
-        }
-        if (iters >= kLmMaxIter || sqrt(dn) < kLmEps * sqrt(pn)) break;
-        prev_cost = cost;
-        evaluate<true>(f, cam, p, acc);
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) pose[i] = p[i];
-    pose[6] = sqrt(cost / (double)f.n);
-    pose[7] = (double)iters;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-        if (!isfinite(p[i])) return DCX_PNP_NONFINITE;
-    if (isnan(cost)) return DCX_PNP_NONFINITE;
-    if (!isfinite(cost)) return DCX_PNP_DEGENERATE;
-    return DCX_PNP_OK;
-}
 
 __global__ __launch_bounds__(kLanes) void dcx_solve_pnp_kernel(const int32_t* __restrict__ counts, const int32_t* __restrict__ starts,
                                                                const int32_t* __restrict__ rows, const float* __restrict__ xy, int pool,

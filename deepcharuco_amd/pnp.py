@@ -233,15 +233,16 @@ def _project(obj: np.ndarray, img: np.ndarray, p: np.ndarray, K: np.ndarray, k: 
     return res, cost, J.reshape(2 * n, 6)
 
 
-def _init_pose(obj: np.ndarray, mn: np.ndarray) -> Tuple[int, Optional[np.ndarray]]:
-    """Planar initialisation (board points obj, normalised image points mn) -> (status, p0)."""
+def _homography(obj: np.ndarray, mn: np.ndarray) -> Tuple[int, Optional[np.ndarray], np.ndarray]:
+    """Planar DLT (board points obj, image points mn) -> (status, H, mc): H maps the centred board points (obj xy - mc) to mn,
+    normalised to h33 = 1."""
     n = obj.shape[0]
     mc, ic = obj[:, :2].mean(0), mn.mean(0)
     mxy, ixy = obj[:, :2] - mc, mn - ic                # plane frame: the board's own z = 0 plane, origin at the centroid
     sxx, sxy, syy = (mxy[:, 0] ** 2).sum(), (mxy[:, 0] * mxy[:, 1]).sum(), (mxy[:, 1] ** 2).sum()
     tr, rt = sxx + syy, math.sqrt((sxx - syy) ** 2 + 4 * sxy * sxy)
     if not 0.5 * (tr - rt) > 1e-10 * 0.5 * (tr + rt):    # collinear board points: no homography
-        return PNP_DEGENERATE, None
+        return PNP_DEGENERATE, None, mc
     # Hartley normalisation: centred, mean distance sqrt(2)
     d1, d2 = np.sqrt((mxy ** 2).sum(1)).sum() / n, np.sqrt((ixy ** 2).sum(1)).sum() / n
     sc1 = math.sqrt(2.0) / d1 if d1 > 0 else 0.0
@@ -255,14 +256,21 @@ def _init_pose(obj: np.ndarray, mn: np.ndarray) -> Tuple[int, Optional[np.ndarra
     w, V = _jacobi(M)
     order = np.argsort(w, kind="stable")
     if not w[order[1]] > 1e-12 * np.abs(w).max():       # two (near) null directions: rank-deficient homography
-        return PNP_DEGENERATE, None
+        return PNP_DEGENERATE, None, mc
     # H = T2^-1 Hn T1 with T1 = diag(sc1, sc1, 1), T2^-1 = [[1/sc2, 0, icx], [0, 1/sc2, icy], [0, 0, 1]]
     H = V[:, order[0]].reshape(3, 3) * np.array([sc1, sc1, 1.0])
     H[0] = H[0] / sc2 + ic[0] * H[2]
     H[1] = H[1] / sc2 + ic[1] * H[2]
     if not abs(H[2, 2]) > 1e-12 * np.abs(H).max():
-        return PNP_DEGENERATE, None
-    H = H / H[2, 2]
+        return PNP_DEGENERATE, None, mc
+    return PNP_OK, H / H[2, 2], mc
+
+
+def _init_pose(obj: np.ndarray, mn: np.ndarray) -> Tuple[int, Optional[np.ndarray]]:
+    """Planar initialisation (board points obj, normalised image points mn) -> (status, p0)."""
+    st, H, mc = _homography(obj, mn)
+    if st != PNP_OK:
+        return st, None
     # OpenCV's decomposition (cvFindExtrinsicCameraParams2, planar branch)
     h1, h2, h3 = H[:, 0], H[:, 1], H[:, 2]
     n1, n2 = math.sqrt(float(h1 @ h1)), math.sqrt(float(h2 @ h2))

@@ -210,6 +210,34 @@ int dcx_solve_pnp_pool(const int32_t* d_counts, const int32_t* d_starts, const i
                        int32_t* d_status, double* d_pose /* [B][8] = rvec3, tvec3, rms_px, iterations */,
                        void* stream);
 
+/* ---- camera calibration from the views of a ChArUco board in a pool (cv2.calibrateCamera with default flags, planar target) --
+ * The camera model solve_pnp needs (calib_intrinsics.py:44, cv2.calibrateCamera) from the corners of
+ * `batch` views, read in place from a corner pool laid out as for dcx_solve_pnp_pool (same object points, same image points, same
+ * per-view checks and DCX_PNP_* codes in d_view_status).  All fp64: OpenCV's initIntrinsicParams2D (principal point at
+ * ((w-1)/2, (h-1)/2), per-view DLT homography, least squares for fx, fy), every view's pose by the PnP solver with that K and no
+ * distortion, then joint Levenberg-Marquardt over fx, fy, cx, cy, k1, k2, p1, p2, k3 (skew 0) and every used view's pose (<= 30
+ * accepted steps, stop at |dp|/|p| < DBL_EPSILON), each step by block elimination of the views' 6x6 pose blocks;
+ * deepcharuco_amd/calib.py restates the steps (calibrate_camera_host_full).  A view that fails its checks is left out and reported.
+ * UNLIKE every other entry point, this one SYNCHRONISES `stream`: the LM loop runs on the host and reads a state word from the
+ * device after every attempt (their number depends on the data), so the call cannot be captured in a graph.
+ * d_workspace: dcx_calibrate_workspace_bytes(batch) bytes of device memory (DCX_E_WS if smaller); nothing is allocated.
+ * d_pose f64 [B][8] = rvec(3), tvec(3), the view's rms reprojection error at the solution (px), its point count (counts[b]);
+ * every view gets its point count, the other words are zero unless the view was used and the calibration succeeded.
+ * h_result f64 [16] = fx, fy, cx, cy, k1, k2, p1, p2, k3, rms (sqrt(sum |r|^2 / points used), cv2's return value), accepted LM
+ * steps, attempts, views used, points used, DCX_CALIB_* status, 0; the first ten are zero unless DCX_CALIB_OK.
+ * No atomics: two calls on the same input give the same bits.                                                               */
+#define DCX_CALIB_OK          0
+#define DCX_CALIB_NO_VIEWS    1   /* no view passed its checks */
+#define DCX_CALIB_DEGENERATE  2   /* the init's 2x2 system or a damped step is singular, or the cost is not finite */
+#define DCX_CALIB_NONFINITE   3
+size_t dcx_calibrate_workspace_bytes(int batch);
+int dcx_calibrate_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows,
+                       const float* d_xy /* NULL = use integer rows x,y */, int batch, int pool,
+                       int col_count, int row_count, double square_len, int image_width, int image_height,
+                       void* d_workspace, size_t workspace_bytes,
+                       int32_t* d_view_status /* [B] DCX_PNP_* */, double* d_pose /* [B][8] */,
+                       double* h_result /* [16] */, void* stream);
+
 /* ---- stage-level entry point for kernel tests / roofline measurement -------------------
  * One 3x3 (or 1x1) convolution + bias [+ eval-BN + ReLU] [+ 2x2 max-pool] on C4 tensors
  * using the same MFMA kernel the networks use.  h_* are host arrays in PyTorch layout;

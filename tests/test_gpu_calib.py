@@ -1,0 +1,190 @@
+"""The device calibration (csrc/dcx_calib.hip through deepcharuco_amd/calib.py) against its host definition
+calibrate_camera_host_full: seeded view sets, a hand-built corner pool with every view status, the corner pool
+infer_batch_device leaves in HBM, determinism, and 4,096 views.
+
+The two differ only in fp64 summation order.  The gates: intrinsics 1e-8 relative (to fx), distortion 1e-8 absolute, poses 1e-8
+relative, rms 1e-12 relative.  As in test_gpu_pnp.py, the last LM steps are decided by rounding: calibrateCamera's stop test
+(|dp| / |p| < DBL_EPSILON) is rarely met on noisy views, so both run to the 30-step cap while the minimum is already reached to
+rounding; whether a step at that level is accepted is decided by the summation order.  The gates hold above that level; every
+test prints the gaps it measured."""
+import numpy as np
+import pytest
+import torch
+
+from conftest import GoldenCase
+from deepcharuco_amd import calib, pnp
+from test_calib_host import BOARD, DIST_TRUE, K_TRUE, SIZE, make_views
+
+pytestmark = pytest.mark.gpu
+
+REL_K, ABS_DIST, REL_POSE, REL_RMS = 1e-8, 1e-8, 1e-8, 1e-12
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda", 0)
+
+
+def _kps(imgs, ids_l):
+    return [np.c_[m.astype(np.float64), i] for m, i in zip(imgs, ids_l)]
+
+
+def _gaps(d, h):
+    """Device vs host CalibResult -> the measured gaps (used views only)."""
+    used = np.flatnonzero(h.view_status == pnp.PNP_OK)
+    def rel(a, b):
+        return float(np.max(np.linalg.norm(a - b, axis=1) / np.linalg.norm(b, axis=1))) if len(b) else 0.0
+    return {"K": float(np.abs(d.camera_matrix - h.camera_matrix).max() / h.camera_matrix[0, 0]),
+            "dist": float(np.abs(d.dist_coeffs - h.dist_coeffs).max()),
+            "rvec": rel(d.rvecs[used], h.rvecs[used]), "tvec": rel(d.tvecs[used], h.tvecs[used]),
+            "rms": abs(d.rms - h.rms) / h.rms if h.rms else abs(d.rms),
+            "view_rms": float(np.max(np.abs(d.view_rms[used] - h.view_rms[used]) / np.maximum(h.view_rms[used], 1e-300)))}
+
+
+def _check(d, h, name, rms_floor=0.0):
+    """-> (gaps, whether the rms needed the absolute floor rms_floor px instead of REL_RMS)."""
+    assert d.view_status.tolist() == h.view_status.tolist(), name
+    assert d.status == h.status == calib.CALIB_OK, (name, d.status, h.status)
+    assert (d.views_used, d.points_used) == (h.views_used, h.points_used)
+    assert d.view_points.tolist() == h.view_points.tolist()
+    g = _gaps(d, h)
+    print(f"{name}: device - host gaps {g}; steps / attempts device {d.iterations} / {d.attempts}, host {h.iterations} / "
+          f"{h.attempts}")
+    assert g["K"] <= REL_K and g["dist"] <= ABS_DIST, (name, g)
+    assert g["rvec"] <= REL_POSE and g["tvec"] <= REL_POSE, (name, g)
+    floor = g["rms"] > REL_RMS
+    assert not floor or abs(d.rms - h.rms) <= rms_floor, (name, g, d.rms, h.rms)
+    unused = np.flatnonzero(d.view_status != pnp.PNP_OK)
+    assert not d.rvecs[unused].any() and not d.tvecs[unused].any() and not d.view_rms[unused].any()
+    return g, floor
+
+
+@pytest.mark.parametrize("seed,n_views,sigma", [(101, 8, 0.0), (102, 64, 0.3), (103, 512, 0.5)])
+def test_device_matches_host(dev, seed, n_views, sigma):
+    objs, imgs, ids_l, _ = make_views(seed, n_views, sigma=sigma)
+    h = calib.calibrate_camera_host_full(objs, imgs, SIZE)
+    d = calib.calibrate_charuco_device(_kps(imgs, ids_l), *BOARD, SIZE)
+    # Noise-free views: the rms (~5e-6 px) is the float32 rounding of the image points, and every residual is a difference of
+    # two ~300 px values, so its fp64 rounding is ~300 * 2^-52 ~ 7e-14 px: 1e-8 of the rms, not 1e-12.  Measured: 4.5e-16 px
+    # (9e-11 relative) on the 8-view set.  Only that set gets the absolute gate of 1e-12 px, and the test says when it is used.
+    _, floor = _check(d, h, f"{n_views} views sigma {sigma}", rms_floor=1e-12 if sigma == 0.0 else 0.0)
+    print(f"{n_views} views sigma {sigma}: rms gate", "absolute 1e-12 px (float32 floor)" if floor else "relative 1e-12")
+
+
+def _hand_built_pool(seed):
+    """Views in scrambled pool order with gaps between them: OK views, 3 points, an empty view, a bad id, collinear points and
+    a view cut by the end of the pool."""
+    objs, imgs, ids_l, _ = make_views(seed, 12, sigma=0.3)
+    kps = _kps(imgs, ids_l)
+    col = np.arange(7) * 7                                                             # a board column: collinear
+    kps.insert(2, kps[0][:3].copy())                                                   # TOO_FEW
+    kps.insert(4, np.zeros((0, 3)))                                                    # TOO_FEW (empty)
+    bad = kps[5].copy()
+    bad[1, 2] = 49                                                                     # BAD_ID (outside the 49 ids)
+    kps.insert(6, bad)
+    kps.insert(8, np.c_[np.linspace(20, 300, 7), np.linspace(30, 200, 7), col])        # DEGENERATE
+    trunc = kps[9].copy()                                                              # TRUNCATED: placed last, cut
+    kps.append(trunc)
+    B = len(kps)
+    order = list(np.random.default_rng(seed).permutation(B - 1)) + [B - 1]
+    gap = 5
+    pool = sum(len(k) + gap for k in kps) - gap - 4
+    packed = np.zeros(2 * B + 6 * pool, np.int32)
+    rows = packed[2 * B:2 * B + 4 * pool].reshape(pool, 4)
+    xy = packed[2 * B + 4 * pool:].view(np.float32).reshape(pool, 2)
+    rows[:] = -9
+    s = 0
+    for b in order:
+        kp = kps[b]
+        packed[b], packed[B + b] = len(kp), s
+        k = min(len(kp), pool - s)
+        if k > 0:
+            rows[s:s + k, 0:2] = np.rint(kp[:k, :2])
+            rows[s:s + k, 2] = kp[:k, 2]
+            xy[s:s + k] = kp[:k, :2]
+        s += len(kp) + gap
+    expect = [pnp.PNP_OK] * B
+    expect[2] = expect[4] = pnp.PNP_TOO_FEW
+    expect[6], expect[8], expect[B - 1] = pnp.PNP_BAD_ID, pnp.PNP_DEGENERATE, pnp.PNP_TRUNCATED
+    return kps, packed, B, pool, expect
+
+
+@pytest.mark.parametrize("refined", [True, False])
+def test_pool_hand_built_every_status(dev, refined):
+    kps, packed, B, pool, expect = _hand_built_pool(7)
+    d = calib.calibrate_charuco_pool(torch.from_numpy(packed).to(dev), B, pool, refined, *BOARD, SIZE)
+    assert d.view_status.tolist() == expect
+    assert d.view_points.tolist() == [len(k) for k in kps]
+    use = [b for b in range(B) if expect[b] in (pnp.PNP_OK, pnp.PNP_DEGENERATE, pnp.PNP_TOO_FEW)]   # what the host can take
+    objs = [pnp.object_points(kps[b][:, 2], *BOARD) for b in use]
+    imgs = [kps[b][:, :2].astype(np.float32) if refined else np.rint(kps[b][:, :2]).astype(np.float32) for b in use]
+    h = calib.calibrate_camera_host_full(objs, imgs, SIZE)
+    assert h.view_status.tolist() == [expect[b] for b in use]
+    sel = np.array(use)
+    sub = d._replace(view_status=d.view_status[sel], rvecs=d.rvecs[sel], tvecs=d.tvecs[sel], view_rms=d.view_rms[sel],
+                     view_points=d.view_points[sel])
+    _check(sub, h, f"hand-built pool refined={refined}")
+    assert not d.rvecs[[2, 4, 6, 8, B - 1]].any()
+
+
+def test_real_detections_pool_addressing(dev):
+    """The unmodified tensor infer_batch_device returns, straight into the calibration: the per-view point counts are the pool's
+    counts and TOO_FEW marks exactly the frames with fewer than 4 corners.  (Synthetic weights give no real geometry, so only the
+    pool addressing is pinned.)"""
+    from deepcharuco_amd.inference import infer_batch_device
+    from deepcharuco_amd.models.net import dcModel, lModel
+    from deepcharuco_amd.models.refinenet import RefineNet, lRefineNet
+    case = GoldenCase("diverse_ids_240x320")
+    dc, rn = lModel(dcModel(case.n_ids, case.sd_dc, dev)), lRefineNet(RefineNet(case.sd_rn, dev))
+    f = case.frame
+    frames = np.stack([f, f[::-1], f[:, ::-1], f[::-1, ::-1], np.zeros_like(f), np.roll(f, 40, axis=1)])
+    pool = 64 * len(frames)
+    packed = infer_batch_device(torch.from_numpy(np.ascontiguousarray(frames)).to(dev), case.n_ids, dc, rn, pool=pool)
+    r = calib.calibrate_charuco_pool(packed, len(frames), pool, True, 5, 5, 0.01, (320, 240))
+    counts = packed[:len(frames)].cpu().numpy()
+    print("counts", counts.tolist(), "view status", r.view_status.tolist(), "calibration status", r.status)
+    assert r.view_points.tolist() == counts.tolist()
+    assert ((r.view_status == pnp.PNP_TOO_FEW) == (counts < 4)).all()
+    assert counts.max() >= 4
+    assert not np.isin(r.view_status, [pnp.PNP_TRUNCATED, pnp.PNP_BAD_ID]).any()
+
+
+def test_two_calls_give_the_same_bits(dev):
+    objs, imgs, ids_l, _ = make_views(104, 96, sigma=0.5)
+    a = calib.calibrate_charuco_device(_kps(imgs, ids_l), *BOARD, SIZE)
+    b = calib.calibrate_charuco_device(_kps(imgs, ids_l), *BOARD, SIZE)
+    assert a.status == calib.CALIB_OK
+    for x, y in zip(a, b):
+        if isinstance(x, np.ndarray):
+            assert x.dtype == y.dtype and np.array_equal(x.view(np.uint8), y.view(np.uint8))
+        else:
+            assert x == y
+
+
+def test_4096_views_recover_the_truth(dev):
+    """Noise-free float32 views: the tolerance of test_calib_host.test_truth_recovery_float32."""
+    objs, imgs, ids_l, poses = make_views(105, 4096)
+    d = calib.calibrate_charuco_device(_kps(imgs, ids_l), *BOARD, SIZE)
+    print("4096 views: rms", d.rms, "steps / attempts", d.iterations, d.attempts)
+    assert d.status == calib.CALIB_OK and (d.view_status == pnp.PNP_OK).all() and d.views_used == 4096
+    assert np.abs(d.camera_matrix - K_TRUE).max() <= 1e-5 * 400
+    assert np.abs(d.dist_coeffs.ravel() - DIST_TRUE).max() <= 1e-5
+    assert np.all(np.linalg.norm(d.rvecs - poses[:, :3], axis=1) <= 1e-5 * np.linalg.norm(poses[:, :3], axis=1))
+    assert np.all(np.linalg.norm(d.tvecs - poses[:, 3:], axis=1) <= 1e-5 * np.linalg.norm(poses[:, 3:], axis=1))
+    assert d.rms <= 2e-5
+
+
+def test_device_argument_errors(dev):
+    objs, imgs, ids_l, _ = make_views(106, 4)
+    kps = _kps(imgs, ids_l)
+    bad = [k.copy() for k in kps]
+    bad[2][0, 2] = 49
+    with pytest.raises(IndexError):
+        calib.calibrate_charuco_device(bad, *BOARD, SIZE)
+    with pytest.raises(ValueError):
+        calib.calibrate_charuco_device(kps, *BOARD, (0, 240))
+    with pytest.raises(ValueError):
+        calib.calibrate_charuco_device([], *BOARD, SIZE)
+    r = calib.calibrate_charuco_device([k[:3] for k in kps], *BOARD, SIZE)
+    assert r.status == calib.CALIB_NO_VIEWS and (r.view_status == pnp.PNP_TOO_FEW).all() and r.rms == 0.0
