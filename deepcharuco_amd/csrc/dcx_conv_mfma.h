@@ -35,14 +35,11 @@
 //   its full ~8 cycles -- the f32 MFMA runs on the vector FMA datapath -- while memory, LDS, scalar
 //   instructions and s_nop are free.  The k-loop therefore contains (almost) no VALU instruction, and the
 //   epilogue is written for minimum VALU count (packed FMA, fused DPP max).  See DESIGN.md section 3.1.
+//
+// What this kernel shares with the Winograd kernels -- packed helpers, the buffer load, the work item and its decode, the persistent
+// XCD-aware item walk, the clock probes, the launcher -- lives in dcx_conv_shared.h.
 #pragma once
-#include "dcx_common.h"
-
-typedef float dcx_f32x16 __attribute__((ext_vector_type(16)));
-typedef float dcx_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int dcx_u32x4 __attribute__((ext_vector_type(4)));
-
-#define DCX_CCH 16  // input channels per LDS chunk ("unit" of the software pipeline)
+#include "dcx_conv_shared.h"
 
 template <int WM_, int WN_, int MT_, int NT_, int TH_, int TW_, int KS_, bool POOL_, int EPI_>
 struct DcxConvCfg {
@@ -80,51 +77,6 @@ struct DcxConvCfg {
     static_assert(KS == 3 || KS == 1, "3x3 or 1x1");
 };
 
-__device__ __forceinline__ float4 dcx_f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-
-// One v_max_f32.  fmaxf() makes hipcc emit an extra canonicalising v_max per operand (sNaN quieting);
-// activations here are finite, and the epilogue runs with the matrix pipe idle, so every VALU counts.
-__device__ __forceinline__ float dcx_vmax(float x, float y) {
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
-    return r;
-}
-typedef float dcx_f32x2 __attribute__((ext_vector_type(2)));
-// one v_pk_add_f32 (hipcc scalarises float2 +/- into two v_add_f32; every VALU instruction in a k-loop costs matrix time)
-__device__ __forceinline__ dcx_f32x2 dcx_pk_add(dcx_f32x2 x, dcx_f32x2 y) {
-    dcx_f32x2 r;
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
-    return r;
-}
-__device__ __forceinline__ dcx_f32x2 dcx_pk_sub(dcx_f32x2 x, dcx_f32x2 y) {
-    dcx_f32x2 r;
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(x), "v"(y));
-    return r;
-}
-// y = x * al + be on 4 channels as two v_pk_fma_f32 (packed fp32: 2 results per VALU instruction)
-__device__ __forceinline__ float4 dcx_fma4(float4 x, float4 al, float4 be) {
-    const dcx_f32x2 lo = __builtin_elementwise_fma(dcx_f32x2{x.x, x.y}, dcx_f32x2{al.x, al.y}, dcx_f32x2{be.x, be.y});
-    const dcx_f32x2 hi = __builtin_elementwise_fma(dcx_f32x2{x.z, x.w}, dcx_f32x2{al.z, al.w}, dcx_f32x2{be.z, be.w});
-    return make_float4(lo.x, lo.y, hi.x, hi.y);
-}
-// ReLU + 2x2 max-pool of one float4 as 12 VALU instructions (v_max_f32 with a DPP source = exchange + max in one)
-// and NO s_nop: the "VALU write -> DPP read" hazard needs 2 wait states, which hipcc does not pad inside asm.  All 12
-// statements are volatile (their order is kept) and each DPP reads a register written >= 3 instructions earlier
-// (x, y, z, w round-robin), so the distance holds by construction.  quad_perm [1,0,3,2] = lane^1, [2,3,0,1] = lane^2.
-#define DCX_VMAX0(x) asm volatile("v_max_f32 %0, 0, %0" : "+v"(x))
-#define DCX_MAX_DPP(x, PERM) asm volatile("v_max_f32_dpp %0, %0, %0 quad_perm:" PERM " row_mask:0xf bank_mask:0xf" : "+v"(x))
-__device__ __forceinline__ float4 dcx_relu_quad_max(float4 v) {
-    DCX_VMAX0(v.x); DCX_VMAX0(v.y); DCX_VMAX0(v.z); DCX_VMAX0(v.w);
-    DCX_MAX_DPP(v.x, "[1,0,3,2]"); DCX_MAX_DPP(v.y, "[1,0,3,2]"); DCX_MAX_DPP(v.z, "[1,0,3,2]"); DCX_MAX_DPP(v.w, "[1,0,3,2]");
-    DCX_MAX_DPP(v.x, "[2,3,0,1]"); DCX_MAX_DPP(v.y, "[2,3,0,1]"); DCX_MAX_DPP(v.z, "[2,3,0,1]"); DCX_MAX_DPP(v.w, "[2,3,0,1]");
-    return v;
-}
-
-struct DcxItem {   // one work item = (image, cout tile, [phase,] spatial tile); all fields wave-uniform
-    int n, ct, ty, tx;
-    int ph;            // dcx_conv_wino2p.h only: output phase 2a + b
-};
-
 // Persistent, software-pipelined kernel.
 //   work item  = (image n, cout tile, spatial tile);   unit = (work item, 16-channel chunk)
 //   Each workgroup walks its items (blockIdx.x, +gridDim.x, ...) unit by unit.  While the MFMAs of
@@ -133,17 +85,6 @@ struct DcxItem {   // one work item = (image, cout tile, [phase,] spatial tile);
 //   (u+1)&1 one step later, so global-memory latency and the staging index math hide behind
 //   16 MFMAs (1024 cycles) per step.  Only the first unit of a workgroup is staged synchronously.
 //   One barrier per unit.  Weights (A) and LDS reads (B) are fetched one k-step ahead.
-// First work item of XCD x's share: the equal eighth, moved by the weighted deviation in WHOLE CU-ROUNDS (32 items = one item for each
-// of an XCD's 32 CUs), rounded to the nearest.  A launch lasts as long as its busiest CU, so a share that is not a multiple of 32 only
-// adds a round to a few CUs: with near-equal weights or few items per XCD the deviation rounds to 0 and the split is exactly the equal
-// one (a launch of 5 items per workgroup must not become one of 6 for three workgroups: measured -5.5 % on the whole step with
-// unquantised shares); a 1.25 % weight moves a boundary of conv1b (2,400 items per XCD) by one round.
-__device__ __forceinline__ int dcx_xcd_bound(int total, int x, int cum) {
-    const int eq = (int)(((long)total * x) >> 3);
-    const int dev = (int)(((long)total * (cum - (x << 13))) >> 16);
-    return eq + ((dev + (dev >= 0 ? 16 : -16)) / 32) * 32;
-}
-
 template <class C>
 __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_mfma_kernel(const DcxConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float4 sB[];
@@ -161,36 +102,15 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_mfma_kernel(cons
     // ---- work list --------------------------------------------------------------------------
     const int tiles = a.tiles_x * a.tiles_y;
     const int n_ct = a.cout_pad / C::COUT_TILE;
-    int n_eff = a.n;
-    if (a.n_limit != nullptr) n_eff = min(n_eff, *a.n_limit);
+    const int n_eff = dcx_n_eff(a);
     const int total = n_eff * n_ct * tiles;     // images are the slowest index: skipped ones are at the end
-    // XCD-aware item walk: block b runs on XCD b % 8 (observed; used for speed only), so the blocks
-    // of one XCD walk one contiguous eighth of the item list and share halos / repeated inputs through their L2
-    int w = blockIdx.x, w_end = total, gstride = gridDim.x;
-    if (a.xcd_walk && (gridDim.x & 7) == 0) {
-        const int x = blockIdx.x & 7;
-        const int lo = dcx_xcd_bound(total, x, a.xcd_cum[x]);           // equal eighths unless the launcher re-weighted the XCDs
-        w_end = dcx_xcd_bound(total, x + 1, a.xcd_cum[x + 1]);
-        gstride = gridDim.x >> 3;
-        w = lo + (blockIdx.x >> 3);
-    }
+    const DcxWalk wk = dcx_item_walk(a, total);
+    int w = wk.w;
+    const int w_end = wk.w_end, gstride = wk.gstride;
     if (w >= w_end) return;
-    if (a.clk_probe != nullptr && blockIdx.x == 0 && tid == 0) {
-        a.clk_probe[0] = __builtin_amdgcn_s_memtime();
-        a.clk_probe[1] = __builtin_amdgcn_s_memrealtime();
-    }
+    dcx_probe_ends(a, tid, 0);
     const int nch = a.cin / DCX_CCH;
-    auto decode = [&](int wi) {
-        DcxItem it;
-        it.tx = wi % a.tiles_x; wi /= a.tiles_x;
-        it.ty = wi % a.tiles_y; wi /= a.tiles_y;
-        it.ph = 0;
-        it.ct = wi % n_ct;
-        it.n = wi / n_ct;
-        return it;
-    };
-    auto pad_y = [&](const DcxItem&) { return a.pad; };
-    auto pad_x = [&](const DcxItem&) { return a.pad; };
+    auto decode = [&](int wi) { return dcx_decode_item(wi, a.tiles_x, a.tiles_y, n_ct); };
 
     const int hl = a.hin << a.ups, wl = a.win << a.ups;  // logical (up-sampled) input size
 
@@ -243,8 +163,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_mfma_kernel(cons
         const unsigned soff = wbase + (unsigned)tap * w_tap_stride + (unsigned)s * w_s_stride;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            const dcx_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, w_lane_off + mt * 512, soff, 0);
-            dst[mt] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+            dst[mt] = dcx_buffer_load_f4(w_rsrc, w_lane_off + mt * 512, soff);
         }
     };
     auto load_b = [&](int buf, int step, float4 (&dst)[NT]) {
@@ -272,29 +191,25 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_mfma_kernel(cons
         p_hy[pi] = hp / HW;
         p_hx[pi] = hp - p_hy[pi] * HW;
         const int prow = ((p_hy[pi] - a.pad) >> a.ups) + a.pad, pcol = ((p_hx[pi] - a.pad) >> a.ups) + a.pad;
-        p_rel[pi] = idx < LDSF ? (unsigned)((cq * a.hin + prow) * a.win + pcol) * 16u : 0x80000000u;
+        p_rel[pi] = idx < LDSF ? (unsigned)((cq * a.hin + prow) * a.win + pcol) * 16u : DCX_OOB;
     }
-    auto unit_rsrc = [&](const DcxItem& it, int c) {
+    auto unit_rsrc = [&](const DcxItem& it, int c) {      // (one per kernel: a shared helper changed the register allocation)
         // element (row (ty*TH>>ups) - pad, col (tx*TW>>ups) - pad) of the unit's first channel quad; for tiles on the
         // top/left border this points before the tensor, but those lanes are masked and never dereferenced
-        const long tile_off = (long)(((it.ty * C::TH) >> a.ups) - pad_y(it)) * a.win + (((it.tx * C::TW) >> a.ups) - pad_x(it));
+        const long tile_off = (long)(((it.ty * C::TH) >> a.ups) - a.pad) * a.win + (((it.tx * C::TW) >> a.ups) - a.pad);
         const float* base = a.in + (((size_t)it.n * a.in_cq_total + a.in_cq_off + (size_t)c * CQC) * (size_t)a.hin * a.win
                                     + tile_off) * 4;
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), (short)0, 0x7fffffff, 0x00020000);
     };
     // a tile is "interior" when its whole halo lies inside the (logical) image: no predicate needed at all
     auto tile_interior = [&](const DcxItem& it) {
-        const int sy0 = it.ty * C::TH - pad_y(it), sx0 = it.tx * C::TW - pad_x(it);
+        const int sy0 = it.ty * C::TH - a.pad, sx0 = it.tx * C::TW - a.pad;
         return sy0 >= 0 && sx0 >= 0 && sy0 + C::HH <= hl && sx0 + C::HW <= wl;
     };
     auto stage_off = [&](int sy0, int sx0, int pi) {   // general (border / overhanging tile) form
         const int ly = sy0 + p_hy[pi], lx = sx0 + p_hx[pi];
         const bool inb = (unsigned)ly < (unsigned)hl && (unsigned)lx < (unsigned)wl;
-        return inb ? p_rel[pi] : 0x80000000u;   // out of range -> the buffer load returns zeros
-    };
-    auto stage_fetch = [&](__amdgpu_buffer_rsrc_t rsrc, unsigned off) {
-        const dcx_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
-        return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+        return inb ? p_rel[pi] : DCX_OOB;   // out of range -> the buffer load returns zeros
     };
     auto stage_store = [&](int buf, int pi, const float4& v) {
         const int idx = tid + pi * C::NTHREADS;
@@ -336,10 +251,10 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_mfma_kernel(cons
         load_a(wb, 0, a_c0);
         load_a(wb, 1, a_c1);
         const __amdgpu_buffer_rsrc_t r0 = unit_rsrc(cur, 0);
-        const int sy0 = cur.ty * C::TH - pad_y(cur), sx0 = cur.tx * C::TW - pad_x(cur);
+        const int sy0 = cur.ty * C::TH - a.pad, sx0 = cur.tx * C::TW - a.pad;
         float4 v[ITER];
 #pragma unroll
-        for (int pi = 0; pi < ITER; ++pi) v[pi] = stage_fetch(r0, stage_off(sy0, sx0, pi));
+        for (int pi = 0; pi < ITER; ++pi) v[pi] = dcx_buffer_load_f4(r0, stage_off(sy0, sx0, pi));
 #pragma unroll
         for (int pi = 0; pi < ITER; ++pi) stage_store(0, pi, v[pi]);
     }
@@ -354,12 +269,14 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_mfma_kernel(cons
             else { has_next = false; cn = c; }   // nothing follows: harmlessly re-stage the current chunk
         }
         const int buf = u & 1;
+        // (per-unit stamps: this kernel's window starts at unit 0 -- it does not read probe_u0 -- and the lines stay spelled out here
+        //  and in the Winograd kernels: behind a shared helper every direct kernel gained SGPR spills, dcx_conv_shared.h)
         if (a.clk_probe != nullptr && blockIdx.x == 0 && tid == 0 && u < 20) a.clk_probe[4 + 3 * u] = __builtin_amdgcn_s_memtime();
         __syncthreads();   // unit u's tile is complete in sB[buf]; everyone is done reading sB[buf ^ 1]
         if (a.clk_probe != nullptr && blockIdx.x == 0 && tid == 0 && u < 20) a.clk_probe[5 + 3 * u] = __builtin_amdgcn_s_memtime();
 
         const __amdgpu_buffer_rsrc_t rs_n = unit_rsrc(nxt, cn);
-        const int nsy0 = nxt.ty * C::TH - pad_y(nxt), nsx0 = nxt.tx * C::TW - pad_x(nxt);
+        const int nsy0 = nxt.ty * C::TH - a.pad, nsx0 = nxt.tx * C::TW - a.pad;
         const unsigned wb_cur = unit_wbase(cur, c);
         const unsigned wb_nxt = unit_wbase(nxt, cn);
         // Software pipeline of one unit (everything below is ONE basic block, fully unrolled):
@@ -420,7 +337,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_mfma_kernel(cons
 #pragma unroll
                 for (int k = 0; k < PPS; ++k) {
                     const int pi = step * PPS + k;
-                    if (pi < ITER) pv[step][k] = stage_fetch(rs_n, poff[pi]);
+                    if (pi < ITER) pv[step][k] = dcx_buffer_load_f4(rs_n, poff[pi]);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -576,10 +493,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_mfma_kernel(cons
         }
 
         if (!has_next) {
-            if (a.clk_probe != nullptr && blockIdx.x == 0 && tid == 0) {
-                a.clk_probe[2] = __builtin_amdgcn_s_memtime();
-                a.clk_probe[3] = __builtin_amdgcn_s_memrealtime();
-            }
+            dcx_probe_ends(a, tid, 2);
             break;
         }
         if (cn == 0) w += gstride;
@@ -588,34 +502,12 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_mfma_kernel(cons
     }
 }
 
-int dcx_device_cu_count();   // dcx_conv_mfma.hip: CUs of the CURRENT device (cached per device)
-constexpr int DCX_MAX_DEVICES = 64;
-int dcx_current_device();    // hipGetDevice() clamped to [0, DCX_MAX_DEVICES)
-int dcx_occupancy_override();
-int dcx_xcd_walk_enabled();   // DCX_XCD_WALK=0 keeps the flat item walk (A/B runs)
-int dcx_fill_xcd_cum(DcxConvArgs& a);    // the current device's cumulative XCD weights (dcx_conv_mfma.hip); 0 / hipError_t
-
 template <class C>
 static int dcx_conv_launch_cfg(DcxConvArgs a, hipStream_t stream) {
     a.tiles_x = (a.wo + C::TW - 1) / C::TW;
     a.tiles_y = (a.ho + C::TH - 1) / C::TH;
     if (a.cout_pad % C::COUT_TILE != 0 || a.cin % DCX_CCH != 0) return DCX_E_SHAPE;
     const long items = (long)a.n * (a.cout_pad / C::COUT_TILE) * a.tiles_x * a.tiles_y;
-    if (items <= 0 || items > 0x7fffffffL) return DCX_E_SHAPE;
-    const int occ_env = dcx_occupancy_override();                      // tuning knob (DCX_OCC), 0 = default
-    const long resident = (long)dcx_device_cu_count() * (occ_env > 0 && occ_env < C::OCC ? occ_env : C::OCC);   // persistent workgroups
-    const long blocks = items < resident ? items : resident;
-    a.xcd_walk = dcx_xcd_walk_enabled() && blocks == resident && (resident & 7) == 0 ? 1 : 0;
-    if (const int rc = dcx_fill_xcd_cum(a)) return rc;
-    static bool attr_set[DCX_MAX_DEVICES] = {};      // the attribute is per device (multi-GPU processes)
-    const int dev_i = dcx_current_device();
-    if (!attr_set[dev_i]) {
-        DCX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dcx_conv_mfma_kernel<C>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)(C::LDS_BYTES + 8192)));
-        attr_set[dev_i] = true;
-    }
     const size_t lds = C::LDS_BYTES + (size_t)a.cout_pad * 16;   // halo double buffer + 4 per-channel parameter arrays
-    if (lds > 160 * 1024) return DCX_E_SHAPE;
-    hipLaunchKernelGGL((dcx_conv_mfma_kernel<C>), dim3((unsigned)blocks), dim3(C::NTHREADS), lds, stream, a);
-    return (int)hipGetLastError();
+    return dcx_launch_persistent<&dcx_conv_mfma_kernel<C>>(a, items, C::NTHREADS, C::OCC, true, lds, (int)(C::LDS_BYTES + 8192), stream);
 }

@@ -60,16 +60,16 @@ struct CfgEntry {
       &dcx_conv_wino2p_launch_cfg<DcxWino2pCfg<TH, TW, EPI, G>>,                                           \
       "dcx_conv_wino2p_kernel<DcxWino2pCfg<" #TH "," #TW "," #EPI "," #G ">>" }
 
-// Direct-kernel wave layouts:  A = 1x4 waves, 64 couts x 256 px   S / P = 2x2 waves, 64 couts x 64 / 256 px
-// (Round 4 trimmed the direct family from 18 to 6 instantiations: on the default path it only runs the raw 1x1 heads; the 3x3
-//  tiles below are what deterministic mode -- the A/B reference of the Winograd families -- needs to run every layer shape, not a
-//  tuned set: the 12x20 / 6x40 / 16x16 / 10x20 / 6x18 / 8x16 / 4x1-wave variants were speed-ups of a mode no BASELINE config uses.)
 // ... and its small-launch shape (dcx_conv_wino2ps.h): 9 positions split over 3 CG waves, 16 CG couts x 16 low-resolution tiles per item
 #define DCX_W2PSCFG(CG)                                                                               \
     { 16 * CG, 64, 8, 8, 3, 0, DCX_EPI_BNRELU, 1, 0, 1, FAM_W2P,                                             \
       &dcx_conv_wino2ps_launch_cfg<DcxWino2psCfg<CG>>,                                                     \
       "dcx_conv_wino2ps_kernel<DcxWino2psCfg<" #CG ">>" }
 
+// Direct-kernel wave layouts:  A = 1x4 waves, 64 couts x 256 px   S / P = 2x2 waves, 64 couts x 64 / 256 px
+// (Round 4 trimmed the direct family from 18 to 6 instantiations: on the default path it only runs the raw 1x1 heads; the 3x3
+//  tiles below are what deterministic mode -- the A/B reference of the Winograd families -- needs to run every layer shape, not a
+//  tuned set: the 12x20 / 6x40 / 16x16 / 10x20 / 6x18 / 8x16 / 4x1-wave variants were speed-ups of a mode no BASELINE config uses.)
 const CfgEntry kCfgs[] = {
     // ---- direct family: the 1x1 heads, deterministic mode (every layer), cin < 32
     // 3x3 + BN + ReLU
@@ -103,7 +103,7 @@ const CfgEntry kCfgs[] = {
 // of the layers as written is executed (the A/B reference for the Winograd families, ~0.5x the throughput).
 int g_deterministic = -1;
 int dcx_deterministic_enabled() {
-    if (g_deterministic < 0) { const char* e = getenv("DCX_DETERMINISTIC"); g_deterministic = (e && atoi(e)) ? 1 : 0; }
+    if (g_deterministic < 0) g_deterministic = dcx_env_knob(DCX_KNOB_DETERMINISTIC) ? 1 : 0;
     return g_deterministic;
 }
 
@@ -143,10 +143,14 @@ const CfgEntry* pick(int n, int cin, int ho, int wo, int cout_pad, int ks, int p
     const int units = cin / DCX_CCH;
     for (const CfgEntry& c : kCfgs) {
         if (c.fam != fam || !can_run(c)) continue;
+        // work items of the launch (the phase family cuts the LOW-RESOLUTION map into tiles, x4 phases; group > 1: whole maps) and
+        // rounds = items that run one after the other on the busiest CU
+        const int ph = c.fam == FAM_W2P ? 2 : 1;
+        const long tiles = (long)((ho / ph + c.th - 1) / c.th) * ((wo / ph + c.tw - 1) / c.tw);
+        const long items = (long)((n + c.group - 1) / c.group) * (cout_pad / c.cout_tile) * tiles * (ph * ph);
+        const double rounds = (double)((items + n_cu - 1) / n_cu);
         double cost;
         if (c.fam == FAM_W2H) {
-            const long ht = (long)((ho + c.th - 1) / c.th) * ((wo + c.tw - 1) / c.tw);
-            const long items = (long)((n + c.group - 1) / c.group) * (cout_pad / c.cout_tile) * ht;
             // per item: 128 MFMAs of 32 cycles per unit + the transform's serial VALU + half an epilogue; stalls are hidden by the
             // co-resident workgroup (measured, tools/unit_probe.py); the 6x20 tile's transform reads are 2-way bank-conflicted
             double item_cost = (double)units * (64 * 64.0 + (c.tw == 20 ? 700.0 : 560.0)) + 2600.0;
@@ -158,35 +162,28 @@ const CfgEntry* pick(int n, int cin, int ho, int wo, int cout_pad, int ks, int p
             if (c.acc_tiles == 1) {      // dcx_conv_wino2hs.h: a wave's chain is 4 positions; the cout_tile / 16 waves of a SIMD interleave theirs.
                                          // Only where every item gets a CU of its own (a launch = one item's chain): the smallest cout tile
                                          // that still fits wins.  DCX_W2HS=<mask> restricts the choice (0: none; A/B runs)
-                static int w2hs = -1;     // bit mask of the cout-group counts in the choice (1 | 2 | 4)
-                if (w2hs < 0) { const char* e = getenv("DCX_W2HS"); w2hs = e ? atoi(e) : 7; }
-                static int w2hs_rounds = -1;      // DCX_W2HS_ROUNDS (experiments): launches of up to this many items per CU may use these kernels
-                if (w2hs_rounds < 0) { const char* e = getenv("DCX_W2HS_ROUNDS"); w2hs_rounds = e ? atoi(e) : 1; }
+                const int w2hs = dcx_env_knob(DCX_KNOB_W2HS);     // bit mask of the cout-group counts in the choice (1 | 2 | 4)
+                const int w2hs_rounds = dcx_env_knob(DCX_KNOB_W2HS_ROUNDS);      // (experiments): launches of up to this many items per CU may use these kernels
                 if (!(w2hs & (c.cout_tile / 16)) || items > (long)w2hs_rounds * n_cu) continue;
                 item_cost = (double)units * (8 * 64.0 * (c.cout_tile / 16) + 400.0) + 1200.0;
                 if (w2hs_rounds > 1 && items > n_cu) item_cost *= 0.8;      // (experiment: prefer them wherever they are allowed)
             }
-            cost = (double)((items + n_cu - 1) / n_cu) * item_cost * (1.0 + 1e-6 * (double)items);   // ties: fewer work items
+            cost = rounds * item_cost * (1.0 + 1e-6 * (double)items);   // ties: fewer work items
         } else if (c.fam == FAM_W2P) {   // 9 x 8 MFMAs of 32 cycles per unit; tiles are low-resolution, x4 phases
-            const long wt = (long)((ho / 2 + c.th - 1) / c.th) * ((wo / 2 + c.tw - 1) / c.tw);
-            const long items = (long)((n + c.group - 1) / c.group) * (cout_pad / c.cout_tile) * wt * 4;
             double item_cost = (double)units * (72 * 32.0 + 500.0) + 2400.0;
             if (c.acc_tiles == 1) {      // dcx_conv_wino2ps.h: a wave's chain is 3 positions; 3 cout_tile / 16 waves share four SIMDs.  As for
                                          // dcx_conv_wino2hs.h: only where every item gets a CU of its own (DCX_W2PS=<mask of cout groups>, 0 = off)
-                static int w2ps = -1;
-                if (w2ps < 0) { const char* e = getenv("DCX_W2PS"); w2ps = e ? atoi(e) : 7; }
+                const int w2ps = dcx_env_knob(DCX_KNOB_W2PS);
                 if (!(w2ps & (c.cout_tile / 16)) || items > n_cu) continue;
                 item_cost = (double)units * (12 * 32.0 * ((3 * (c.cout_tile / 16) + 3) / 4) + 400.0) + 1200.0;
             }
-            cost = (double)((items + n_cu - 1) / n_cu) * item_cost * (1.0 + 1e-6 * (double)items);
+            cost = rounds * item_cost * (1.0 + 1e-6 * (double)items);
         } else {
-            const long tiles = (long)((ho + c.th - 1) / c.th) * ((wo + c.tw - 1) / c.tw);
-            const long items = (long)n * (cout_pad / c.cout_tile) * tiles;
             const int steps = ks * ks * (DCX_CCH / 8);
             // per-unit overhead: barrier + first LDS wait + bookkeeping (520); epilogue ~40 (60 pooled, 35 in-lane) cycles per register
             const double item_cost = (double)units * steps * (4 * c.acc_tiles) * 64.0 + units * 520.0
                                    + c.acc_tiles * 16 * (c.inlane ? 35.0 : (pool ? 60.0 : 40.0));
-            cost = (double)((items + n_cu - 1) / n_cu) * item_cost;
+            cost = rounds * item_cost;
             if (c.cout_tile == 64 && c.cap == 256) cost *= 0.999;   // deterministic tie-break towards the A layout
         }
         if (best == nullptr || cost < best_cost) { best_cost = cost; best = &c; }
@@ -330,10 +327,21 @@ int dcx_device_cu_count() {
     return cus[dev];
 }
 
-int dcx_xcd_walk_enabled() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("DCX_XCD_WALK"); v = (e && !atoi(e)) ? 0 : 1; }
-    return v;
+// Environment knobs of the convolution launchers: each is read ONCE, at its first use, as atoi(value), or its default when unset.
+// (DCX_FORCE_CFG is not one of them: pick() re-reads it on every call.)
+int dcx_env_knob(DcxKnob k) {
+    static struct { const char* name; int unset; bool read; int value; } knobs[DCX_KNOB_COUNT] = {
+        {"DCX_DETERMINISTIC", 0},     // 1: every layer on the direct family
+        {"DCX_XCD_WALK", 1},          // 0 keeps the flat item walk (A/B runs)
+        {"DCX_OCC", 0},               // workgroups per CU, where a launcher honours it; 0 = the kernel's own figure
+        {"DCX_CT_OUTER", -1},         // 0 / 1 forces the item order of the 2-D Winograd kernels; -1 = by layer
+        {"DCX_W2HS", 7},              // dcx_conv_wino2hs.h: mask of the cout-group counts in the choice, 0 = off
+        {"DCX_W2HS_ROUNDS", 1},
+        {"DCX_W2PS", 7},              // dcx_conv_wino2ps.h: the same
+        {"DCX_PROBE_U0", 0},          // first unit of the per-unit probe window
+    };
+    if (!knobs[k].read) { const char* e = getenv(knobs[k].name); knobs[k].value = e ? atoi(e) : knobs[k].unset; knobs[k].read = true; }
+    return knobs[k].value;
 }
 
 // ---- per-XCD item-range weights -------------------------------------------------------------------------------------------------
@@ -486,12 +494,6 @@ extern "C" int dcx_calibrate_xcd(int rounds, float* w8_out, void* stream) {
     return rc;
 }
 
-int dcx_occupancy_override() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("DCX_OCC"); v = e ? atoi(e) : 0; }
-    return v;
-}
-
 int dcx_conv_heat_tiles(int ho, int wo, int ups) {
     const CfgEntry* c = pick(1 << 20, 64, ho, wo, 64, 3, 0, DCX_EPI_HEAT, 1, ups);
     if (c == nullptr) return 0;
@@ -525,7 +527,7 @@ int dcx_launch_conv_mfma(DcxConvArgs a, int ks, int pool, int epi, hipStream_t s
         else (void)hipMemset(g_clk_dev, 0, sizeof(unsigned long long) * kClkWords * kClkSlots);
     }
     if (g_clk_dev != nullptr && r.slot < kClkSlots) a.clk_probe = g_clk_dev + (size_t)kClkWords * r.slot;
-    { static int u0 = -1; if (u0 < 0) { const char* e = getenv("DCX_PROBE_U0"); u0 = e ? atoi(e) : 0; } a.probe_u0 = u0; }
+    a.probe_u0 = dcx_env_knob(DCX_KNOB_PROBE_U0);
     if (!r.e0 || !r.e1) return (int)hipErrorOutOfMemory;
     DCX_CHECK_HIP(hipEventRecord(r.e0, stream));
     const int rc = c->launch(a, stream);

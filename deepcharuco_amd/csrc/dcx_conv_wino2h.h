@@ -2,7 +2,8 @@
 // fp32 matrix cores: 16 products per 2x2 output tile and input channel instead of 36, i.e. 4/9 of the direct convolution's
 // MFMAs.  THE kernel family of every 3x3 + BN + ReLU layer that does not read through an up-sampling (those: dcx_conv_wino2p.h);
 // the family is chosen from the layer shape alone (dcx_conv_mfma.hip: pick), so a frame's results do not depend on the batch it
-// travels in.  Read dcx_conv_mfma.h first; layouts and the persistent work walk are the same.
+// travels in.  Read dcx_conv_mfma.h first; layouts are the same, and the persistent work walk, the launcher and the
+// transform helpers are the shared ones of dcx_conv_shared.h.
 //
 //   per 2x2 output tile (rows 2ty, 2ty+1; columns 2tx, 2tx+1) and input channel, d = the 4x4 input window whose top-left
 //   pixel is (2ty - pad, 2tx - pad):
@@ -157,25 +158,16 @@ __global__ __launch_bounds__(256, 2) void dcx_conv_wino2h_kernel(const DcxConvAr
     const int wm = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave = 16-cout group
     const int g4 = lane >> 4, l15 = lane & 15;                      // lane's channel quad of the chunk / row-or-column
 
-    // ---- work list (persistent, XCD-aware walk: see the header comment) ------------------------------------------
+    // ---- work list (persistent, XCD-aware walk: dcx_conv_shared.h) ------------------------------------------------
     const int tiles = a.tiles_x * a.tiles_y;
     const int n_ct = a.cout_pad / C::COUT_TILE;
-    int n_eff = a.n;
-    if (a.n_limit != nullptr) n_eff = min(n_eff, *a.n_limit);
+    const int n_eff = dcx_n_eff(a);
     const int total = ((n_eff + C::G - 1) / C::G) * n_ct * tiles;      // G > 1: one work item covers G images (tiles == 1)
-    int w = blockIdx.x, w_end = total, gstride = gridDim.x;
-    if (a.xcd_walk && (gridDim.x & 7) == 0) {
-        const int x = blockIdx.x & 7;
-        const int lo = dcx_xcd_bound(total, x, a.xcd_cum[x]);           // equal eighths unless the launcher re-weighted the XCDs
-        w_end = dcx_xcd_bound(total, x + 1, a.xcd_cum[x + 1]);
-        gstride = gridDim.x >> 3;
-        w = lo + (blockIdx.x >> 3);
-    }
+    const DcxWalk wk = dcx_item_walk(a, total);
+    int w = wk.w;
+    const int w_end = wk.w_end, gstride = wk.gstride;
     if (w >= w_end) return;
-    if (a.clk_probe != nullptr && blockIdx.x == 0 && tid == 0) {
-        a.clk_probe[0] = __builtin_amdgcn_s_memtime();
-        a.clk_probe[1] = __builtin_amdgcn_s_memrealtime();
-    }
+    dcx_probe_ends(a, tid, 0);
     // calibration launches (dcx_calibrate_xcd) run the dominant kernel's instantiation only: the other instantiations carry no
     // code for it (the unpooled ones sit at the SGPR limit: one more live pointer spilled a VGPR)
     constexpr bool XSTAT = C::POOL && C::TW == 16 && C::TB == 2 && C::G == 1;
@@ -184,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void dcx_conv_wino2h_kernel(const DcxConvAr
     if (a.clk_probe != nullptr && tid == 0) a.clk_probe[64 + 2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
 #endif
     const int nch = a.cin / DCX_CCH;
-    auto decode = [&](int wi) {
+    auto decode = [&](int wi) {      // dcx_decode_item + ct_outer; kept here: as a shared helper it reordered the next item's decode in the unit loop
         DcxItem it;
         it.tx = wi % a.tiles_x; wi /= a.tiles_x;
         it.ty = wi % a.tiles_y; wi /= a.tiles_y;
@@ -210,8 +202,7 @@ __global__ __launch_bounds__(256, 2) void dcx_conv_wino2h_kernel(const DcxConvAr
         return (unsigned)((c * CQC) * a.cout_pad + it.ct * C::COUT_TILE) * 16u;
     };
     auto load_a = [&](unsigned wbase, int pos) {
-        const dcx_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, w_lane_off, wbase + (unsigned)pos * w_pos_stride, 0);
-        return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+        return dcx_buffer_load_f4(w_rsrc, w_lane_off, wbase + (unsigned)pos * w_pos_stride);
     };
     // transformed activations sV[buf][pos][cq][tile]: lane (n = l15, g = g4) reads tile tb*16 + n, channel quad g
     const int tile_b = g4 * 32 + l15;
@@ -232,12 +223,12 @@ __global__ __launch_bounds__(256, 2) void dcx_conv_wino2h_kernel(const DcxConvAr
         const int hy = hp / RW, hx = hp - hy * RW;
         r_hyx[k] = hy << 16 | hx;
         const int prow = ((hy - a.pad) >> a.ups) + a.pad, pcol = ((hx - a.pad) >> a.ups) + a.pad;
-        r_rel[k] = idx < C::RAW ? ((unsigned)img * in_img_stride + (unsigned)((cq * a.hin + prow) * a.win + pcol)) * 16u : 0x80000000u;
+        r_rel[k] = idx < C::RAW ? ((unsigned)img * in_img_stride + (unsigned)((cq * a.hin + prow) * a.win + pcol)) * 16u : DCX_OOB;
         r_slot[k] = idx < C::RAW ? C::raw_slot(img, cq, hy, hx) : RP - 1;
         if (C::G > 1) {
             // a grouped tile always starts at pixel (0, 0) of its images: the zero-padding predicate is a per-piece constant
             const int ly = hy - a.pad, lx = hx - a.pad;
-            if (!((unsigned)ly < (unsigned)(a.hin << a.ups) && (unsigned)lx < (unsigned)(a.win << a.ups))) r_rel[k] = 0x80000000u;
+            if (!((unsigned)ly < (unsigned)(a.hin << a.ups) && (unsigned)lx < (unsigned)(a.win << a.ups))) r_rel[k] = DCX_OOB;
             r_hyx[k] = img;     // what the per-unit check needs: which image of the group the piece reads
         }
     }
@@ -256,13 +247,13 @@ __global__ __launch_bounds__(256, 2) void dcx_conv_wino2h_kernel(const DcxConvAr
     // rows of the half-piece, branch-free: first xi = row A - row B, second xi = row B + sgn * row C
     //   h = 0: xi 0 = d0 - d2 (A = 0, B = 2), xi 1 = d1 + d2 (C = 1, sgn = +1);  h = 1: xi 2 = d2 - d1 (A = 2, B = 1), xi 3 = d1 - d3 (C = 3, sgn = -1)
     // rows of the quarter-piece: xi = row A + sgn * row B:  xi 0 = d0 - d2, xi 1 = d1 + d2, xi 2 = d2 - d1, xi 3 = d1 - d3
-    const int x_ia = QP ? (x_r == 0 ? 0 : x_r == 2 ? 2 : 1) : (x_h ? 2 : 0);
-    const int x_ib = QP ? (x_r == 2 ? 1 : x_r == 3 ? 3 : 2) : (x_h ? 1 : 2);
+    const int x_ia = QP ? dcx_f23_a(x_r) : (x_h ? 2 : 0);
+    const int x_ib = QP ? dcx_f23_b(x_r) : (x_h ? 1 : 2);
     const int x_ic = x_h ? 3 : 1;
     // raw slots of the window's left pixel (column 2 tx, always even) in the rows this piece needs
     const int x_ra = C::raw_slot(x_img, x_cq, 2 * x_ty + x_ia, 2 * x_tx), x_rb = C::raw_slot(x_img, x_cq, 2 * x_ty + x_ib, 2 * x_tx),
               x_rc = C::raw_slot(x_img, x_cq, 2 * x_ty + x_ic, 2 * x_tx);
-    const float x_sg = QP ? (x_r == 1 ? 1.f : -1.f) : (x_h ? -1.f : 1.f);
+    const float x_sg = QP ? dcx_f23_sgn(x_r) : (x_h ? -1.f : 1.f);
     const dcx_f32x2 x_sgn = {x_sg, x_sg};
     const int x_dst = QP ? (4 * x_r) * VPLANE + x_cq * 32 + x_tile
                          : (8 * x_h) * VPLANE + x_cq * 32 + x_tile;         // + local position * VPLANE
@@ -277,29 +268,12 @@ __global__ __launch_bounds__(256, 2) void dcx_conv_wino2h_kernel(const DcxConvAr
         const int sy0 = it.ty * C::TH - a.pad, sx0 = it.tx * C::TW - a.pad;
         return sy0 >= 0 && sx0 >= 0 && sy0 + C::HH <= hl && sx0 + RW <= wl;
     };
-    auto stage_fetch = [&](__amdgpu_buffer_rsrc_t rsrc, unsigned off) {
-        const dcx_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
-        return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-    };
-    auto sub4 = [](const float4& x, const float4& y) {
-        const dcx_f32x2 lo = dcx_pk_sub(dcx_f32x2{x.x, x.y}, dcx_f32x2{y.x, y.y}), hi = dcx_pk_sub(dcx_f32x2{x.z, x.w}, dcx_f32x2{y.z, y.w});
-        return make_float4(lo.x, lo.y, hi.x, hi.y);
-    };
-    auto add4 = [](const float4& x, const float4& y) {
-        const dcx_f32x2 lo = dcx_pk_add(dcx_f32x2{x.x, x.y}, dcx_f32x2{y.x, y.y}), hi = dcx_pk_add(dcx_f32x2{x.z, x.w}, dcx_f32x2{y.z, y.w});
-        return make_float4(lo.x, lo.y, hi.x, hi.y);
-    };
     // Half-piece transform as 12 events (x = 0..11).  Rows needed: h = 0: xi 0 = d0 - d2, xi 1 = d1 + d2;  h = 1: xi 2 = d2 - d1, xi 3 = d1 - d3.
     //   event 0: read the two rows of the first xi (8 ds_read_b128)      event 1: read the third row
     //   event 3 + ms (ms = 0..7, local position = 4 * (xi - 2h) + nu): at nu == 0 form t (4 float4 ops), then the position
     //   (1 float4 op); its LDS write goes out one event later           event 11: last write
     // Quarter-piece (TB = 1): event 0 reads its two rows, events 3 .. 6 form the row's four positions, the last write is event 7.
     float4 xa[4], xb[4], xc[4], xt[4], xv;
-    auto fma4s = [&](const float4& x, const float4& y) {      // y + sgn * x as two v_pk_fma_f32 (sgn = +-1: exactly y +- x)
-        const dcx_f32x2 lo = __builtin_elementwise_fma(dcx_f32x2{x.x, x.y}, x_sgn, dcx_f32x2{y.x, y.y});
-        const dcx_f32x2 hi = __builtin_elementwise_fma(dcx_f32x2{x.z, x.w}, x_sgn, dcx_f32x2{y.z, y.w});
-        return make_float4(lo.x, lo.y, hi.x, hi.y);
-    };
     auto xform_event = [&](float4* vbuf, int x) {
         if (QP) {
             if (x == 0) {
@@ -310,9 +284,9 @@ __global__ __launch_bounds__(256, 2) void dcx_conv_wino2h_kernel(const DcxConvAr
                 if (nu > 0) vbuf[x_dst + (nu - 1) * VPLANE] = xv;
                 if (nu == 0) {
 #pragma unroll
-                    for (int cidx = 0; cidx < 4; ++cidx) xt[cidx] = fma4s(xb[cidx], xa[cidx]);      // row A + sgn * row B
+                    for (int cidx = 0; cidx < 4; ++cidx) xt[cidx] = dcx_fmas4(xb[cidx], x_sgn, xa[cidx]);      // row A + sgn * row B
                 }
-                if (nu < 4) xv = nu == 0 ? sub4(xt[0], xt[2]) : nu == 1 ? add4(xt[1], xt[2]) : nu == 2 ? sub4(xt[2], xt[1]) : sub4(xt[1], xt[3]);
+                if (nu < 4) xv = nu == 0 ? dcx_sub4(xt[0], xt[2]) : nu == 1 ? dcx_add4(xt[1], xt[2]) : nu == 2 ? dcx_sub4(xt[2], xt[1]) : dcx_sub4(xt[1], xt[3]);
             }
             return;
         }
@@ -329,9 +303,9 @@ __global__ __launch_bounds__(256, 2) void dcx_conv_wino2h_kernel(const DcxConvAr
                 const int xl = ms >> 2, nu = ms & 3;
                 if (nu == 0) {
 #pragma unroll
-                    for (int cidx = 0; cidx < 4; ++cidx) xt[cidx] = xl == 0 ? sub4(xa[cidx], xb[cidx]) : fma4s(xc[cidx], xb[cidx]);
+                    for (int cidx = 0; cidx < 4; ++cidx) xt[cidx] = xl == 0 ? dcx_sub4(xa[cidx], xb[cidx]) : dcx_fmas4(xc[cidx], x_sgn, xb[cidx]);
                 }
-                xv = nu == 0 ? sub4(xt[0], xt[2]) : nu == 1 ? add4(xt[1], xt[2]) : nu == 2 ? sub4(xt[2], xt[1]) : sub4(xt[1], xt[3]);
+                xv = nu == 0 ? dcx_sub4(xt[0], xt[2]) : nu == 1 ? dcx_add4(xt[1], xt[2]) : nu == 2 ? dcx_sub4(xt[2], xt[1]) : dcx_sub4(xt[1], xt[3]);
             }
         }
     };
@@ -340,9 +314,7 @@ __global__ __launch_bounds__(256, 2) void dcx_conv_wino2h_kernel(const DcxConvAr
     float* sT = reinterpret_cast<float*>(sB + 2 * LDSF + C::RAW_LDS);
     if (tid < 64) {
         const int k = tid >> 4, p = tid & 15, i = k >> 1, j = k & 1, xi = p >> 2, nu = p & 3;
-        const int ci = i == 0 ? (xi < 3 ? 1 : 0) : (xi == 0 ? 0 : xi == 1 ? 1 : -1);
-        const int cj = j == 0 ? (nu < 3 ? 1 : 0) : (nu == 0 ? 0 : nu == 1 ? 1 : -1);
-        sT[tid] = (float)(ci * cj);
+        sT[tid] = (float)(dcx_at23<int>(i, xi) * dcx_at23<int>(j, nu));
     }
     const int hs = C::POOL ? (a.ho >> 1) : a.ho, ws = C::POOL ? (a.wo >> 1) : a.wo;
 
@@ -365,7 +337,7 @@ __global__ __launch_bounds__(256, 2) void dcx_conv_wino2h_kernel(const DcxConvAr
             const int ly = sy0 + (r_hyx[k] >> 16), lx = sx0 + (r_hyx[k] & 0xffff);
             const bool inb = C::G > 1 ? (cur.n * C::G + r_hyx[k] < n_eff)
                                       : ((unsigned)ly < (unsigned)hl && (unsigned)lx < (unsigned)wl);
-            sR[r_slot[k]] = stage_fetch(r0, inb ? r_rel[k] : 0x80000000u);
+            sR[r_slot[k]] = dcx_buffer_load_f4(r0, inb ? r_rel[k] : DCX_OOB);
         }
         __syncthreads();
 #pragma unroll
@@ -423,7 +395,7 @@ __global__ __launch_bounds__(256, 2) void dcx_conv_wino2h_kernel(const DcxConvAr
                 const int ly = nsy0 + (r_hyx[k] >> 16), lx = nsx0 + (r_hyx[k] & 0xffff);
                 const bool inb = C::G > 1 ? (nxt.n * C::G + r_hyx[k] < n_eff)
                                           : ((unsigned)ly < (unsigned)hl && (unsigned)lx < (unsigned)wl);
-                roff[k] = inb ? r_rel[k] : 0x80000000u;
+                roff[k] = inb ? r_rel[k] : DCX_OOB;
             }
         }
         // one position = 4 TB MFMAs (j = 0..3) in two slots of 2 TB; each slot is preceded by one staging event; the slot that
@@ -453,7 +425,7 @@ __global__ __launch_bounds__(256, 2) void dcx_conv_wino2h_kernel(const DcxConvAr
                     }
                 }
                 {
-                    if (e >= C::E_RAW_LOAD && e < C::E_RAW_LOAD + ITER_R) rv[e - C::E_RAW_LOAD] = stage_fetch(rs_n, roff[e - C::E_RAW_LOAD]);
+                    if (e >= C::E_RAW_LOAD && e < C::E_RAW_LOAD + ITER_R) rv[e - C::E_RAW_LOAD] = dcx_buffer_load_f4(rs_n, roff[e - C::E_RAW_LOAD]);
                     if (e >= C::E_RAW_STORE && e < C::E_RAW_STORE + ITER_R) sR[r_slot[e - C::E_RAW_STORE]] = rv[e - C::E_RAW_STORE];
                     if (e >= C::E_XFORM && e < C::E_XFORM + C::XF_EVENTS) xform_event(vnext, e - C::E_XFORM);
                 }
@@ -592,10 +564,7 @@ __global__ __launch_bounds__(256, 2) void dcx_conv_wino2h_kernel(const DcxConvAr
 #ifdef DCX_W2H_BLOCKTIMES
             if (a.clk_probe != nullptr && tid == 0) a.clk_probe[65 + 2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
 #endif
-            if (a.clk_probe != nullptr && blockIdx.x == 0 && tid == 0) {
-                a.clk_probe[2] = __builtin_amdgcn_s_memtime();
-                a.clk_probe[3] = __builtin_amdgcn_s_memrealtime();
-            }
+            dcx_probe_ends(a, tid, 2);
             return false;
         }
         if (cn == 0) w += gstride;
@@ -621,25 +590,11 @@ static int dcx_conv_wino2h_launch_cfg(DcxConvArgs a, hipStream_t stream) {
     if (a.cout_pad % C::COUT_TILE != 0 || a.cin % DCX_CCH != 0 || a.cin < 2 * DCX_CCH) return DCX_E_SHAPE;   // >= 2 units per work item
     if (C::G > 1 && (a.tiles_x != 1 || a.tiles_y != 1 || a.ups != 0)) return DCX_E_SHAPE;                   // grouped tiles: whole maps
     const long items = (long)((a.n + C::G - 1) / C::G) * (a.cout_pad / C::COUT_TILE) * a.tiles_x * a.tiles_y;
-    if (items <= 0 || items > 0x7fffffffL) return DCX_E_SHAPE;
-    const int occ_env = dcx_occupancy_override();                        // tuning knob (DCX_OCC = 1: one workgroup per CU)
-    const long resident = (occ_env == 1 ? 1L : 2L) * dcx_device_cu_count();
-    const long blocks = items < resident ? items : resident;
-    a.xcd_walk = dcx_xcd_walk_enabled() && blocks == resident && (resident & 7) == 0 ? 1 : 0;
-    if (const int rc = dcx_fill_xcd_cum(a)) return rc;
-    {   // cout tile outermost where the layer's transformed weights would otherwise thrash the XCDs' L2 (DCX_CT_OUTER=0/1 forces it)
-        static int force = -2;
-        if (force == -2) { const char* e = getenv("DCX_CT_OUTER"); force = e ? atoi(e) : -1; }
-        const size_t w_bytes = (size_t)16 * a.cin * a.cout_pad * 4;
-        a.ct_outer = force >= 0 ? force : (a.xcd_walk && a.n_limit == nullptr && a.cout_pad / C::COUT_TILE >= 4 && w_bytes > (size_t)(2u << 20)) ? 1 : 0;
-    }
-    static bool attr_set[DCX_MAX_DEVICES] = {};
-    const int dev_i = dcx_current_device();
-    if (!attr_set[dev_i]) {
-        DCX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dcx_conv_wino2h_kernel<C>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-        attr_set[dev_i] = true;
-    }
-    hipLaunchKernelGGL((dcx_conv_wino2h_kernel<C>), dim3((unsigned)blocks), dim3(C::NTHREADS), C::LDS_BYTES, stream, a);
-    return (int)hipGetLastError();
+    // two workgroups per CU (DCX_OCC = 1: one); once the walk is known: cout tile outermost where the layer's transformed weights
+    // would otherwise thrash the XCDs' L2 (DCX_CT_OUTER=0/1 forces it)
+    return dcx_launch_persistent<&dcx_conv_wino2h_kernel<C>>(a, items, C::NTHREADS, 2, true, C::LDS_BYTES, 80 * 1024, stream, [](DcxConvArgs& l) {
+        const int force = dcx_env_knob(DCX_KNOB_CT_OUTER);
+        const size_t w_bytes = (size_t)16 * l.cin * l.cout_pad * 4;
+        l.ct_outer = force >= 0 ? force : (l.xcd_walk && l.n_limit == nullptr && l.cout_pad / C::COUT_TILE >= 4 && w_bytes > (size_t)(2u << 20)) ? 1 : 0;
+    });
 }

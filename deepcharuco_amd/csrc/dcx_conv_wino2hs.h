@@ -28,8 +28,8 @@
 // unit ahead of their use and every 512-cycle unit waited for both (bs=1 protocol 2,800 -> 2,855 calls/s; with the ring -> 3,060;
 // U = 2, 3, 4 measure the same: profiles/experiments/r06_bs1_split_positions.txt).  CG = 4 (128 registers per wave) keeps one weight set and refills a position
 // pair's registers as soon as its MFMAs are issued.  Work items are independent: prologue, nch units, epilogue, nothing carried
-// over (a cross-item pipeline was built and measured slower for these launches).  Layouts, item walk and zero padding by buffer
-// range are dcx_conv_wino2h.h's.
+// over (a cross-item pipeline was built and measured slower for these launches).  Layouts and zero padding by buffer range are
+// dcx_conv_wino2h.h's; item walk, launcher and transform helpers are the shared ones of dcx_conv_shared.h.
 #pragma once
 #include "dcx_conv_wino2h.h"
 
@@ -85,35 +85,18 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_wino2hs_kernel(c
     const int cg = wv >> 2;                                         // the wave's cout group
     const int g4 = lane >> 4, l15 = lane & 15;
 
-    // ---- work list (dcx_conv_wino2h.h) -----------------------------------------------------------------------------
+    // ---- work list (dcx_conv_shared.h) -----------------------------------------------------------------------------
     const int tiles = a.tiles_x * a.tiles_y;
     const int n_ct = a.cout_pad / C::COUT_TILE;
-    int n_eff = a.n;
-    if (a.n_limit != nullptr) n_eff = min(n_eff, *a.n_limit);
+    const int n_eff = dcx_n_eff(a);
     const int total = n_eff * n_ct * tiles;
-    int w = blockIdx.x, w_end = total, gstride = gridDim.x;
-    if (a.xcd_walk && (gridDim.x & 7) == 0) {
-        const int x = blockIdx.x & 7;
-        const int lo = dcx_xcd_bound(total, x, a.xcd_cum[x]);
-        w_end = dcx_xcd_bound(total, x + 1, a.xcd_cum[x + 1]);
-        gstride = gridDim.x >> 3;
-        w = lo + (blockIdx.x >> 3);
-    }
+    const DcxWalk wk = dcx_item_walk(a, total);
+    int w = wk.w;
+    const int w_end = wk.w_end, gstride = wk.gstride;
     if (w >= w_end) return;
-    if (a.clk_probe != nullptr && blockIdx.x == 0 && tid == 0) {
-        a.clk_probe[0] = __builtin_amdgcn_s_memtime();
-        a.clk_probe[1] = __builtin_amdgcn_s_memrealtime();
-    }
+    dcx_probe_ends(a, tid, 0);
     const int nch = a.cin / DCX_CCH;
-    auto decode = [&](int wi) {
-        DcxItem it;
-        it.tx = wi % a.tiles_x; wi /= a.tiles_x;
-        it.ty = wi % a.tiles_y; wi /= a.tiles_y;
-        it.ct = wi % n_ct;
-        it.n = wi / n_ct;
-        it.ph = 0;
-        return it;
-    };
+    auto decode = [&](int wi) { return dcx_decode_item(wi, a.tiles_x, a.tiles_y, n_ct); };
     const int hl = a.hin << a.ups, wl = a.win << a.ups;
 
     // ---- operands ----------------------------------------------------------------------------------------------------
@@ -126,8 +109,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_wino2hs_kernel(c
         return (unsigned)((c * CQC) * a.cout_pad + it.ct * C::COUT_TILE) * 16u + (unsigned)(4 * pgp) * w_pos_stride;
     };
     auto load_a = [&](unsigned wbase, int pp) {
-        const dcx_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, w_lane_off, wbase + (unsigned)pp * w_pos_stride, 0);
-        return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+        return dcx_buffer_load_f4(w_rsrc, w_lane_off, wbase + (unsigned)pp * w_pos_stride);
     };
     // transformed activations sV[buf][pos][cq][tile]: lane (n = l15, g = g4) reads tile n, channel quad g
     auto load_b = [&](int buf, int pp) { return sB[buf * LDSV + (4 * pgp + pp) * VPLANE + lane]; };
@@ -143,17 +125,13 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_wino2hs_kernel(c
         const int hy = hp / RW, hx = hp - hy * RW;
         r_hyx[k] = hy << 16 | hx;
         const int prow = ((hy - a.pad) >> a.ups) + a.pad, pcol = ((hx - a.pad) >> a.ups) + a.pad;
-        r_rel[k] = idx < C::RAW ? (unsigned)((cq * a.hin + prow) * a.win + pcol) * 16u : 0x80000000u;
+        r_rel[k] = idx < C::RAW ? (unsigned)((cq * a.hin + prow) * a.win + pcol) * 16u : DCX_OOB;
         r_slot[k] = idx < C::RAW ? C::raw_slot(cq, hy, hx) : C::RP - 1;      // slot RP - 1 of row 0 is free: dump slot
     }
     auto unit_rsrc = [&](const DcxItem& it, int c) {
         const long tile_off = (long)(((it.ty * C::TH) >> a.ups) - a.pad) * a.win + (((it.tx * C::TW) >> a.ups) - a.pad);
         const float* base = a.in + (((size_t)it.n * a.in_cq_total + a.in_cq_off + (size_t)c * CQC) * (size_t)a.hin * a.win + tile_off) * 4;
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), (short)0, 0x7fffffff, 0x00020000);
-    };
-    auto stage_fetch = [&](__amdgpu_buffer_rsrc_t rsrc, unsigned off) {
-        const dcx_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
-        return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
     };
     auto raw_offsets = [&](const DcxItem& it, unsigned (&roff)[ITER_R]) {
         const int sy0 = it.ty * C::TH - a.pad, sx0 = it.tx * C::TW - a.pad;
@@ -163,7 +141,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_wino2hs_kernel(c
             roff[k] = r_rel[k];
             if (!interior) {
                 const int ly = sy0 + (r_hyx[k] >> 16), lx = sx0 + (r_hyx[k] & 0xffff);
-                if (!((unsigned)ly < (unsigned)hl && (unsigned)lx < (unsigned)wl)) roff[k] = 0x80000000u;
+                if (!((unsigned)ly < (unsigned)hl && (unsigned)lx < (unsigned)wl)) roff[k] = DCX_OOB;
             }
         }
     };
@@ -174,15 +152,15 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_wino2hs_kernel(c
     const int x_tile = tid & 15, x_cq = (tid >> 4) & 3;
     const int x_xi = __builtin_amdgcn_readfirstlane((tid >> 6) & 3), x_ng = __builtin_amdgcn_readfirstlane(tid >> 8);
     const int x_ty = x_tile >> 2, x_tx = x_tile & 3;
-    const int x_ia = x_xi == 0 ? 0 : x_xi == 2 ? 2 : 1, x_ib = x_xi == 2 ? 1 : x_xi == 3 ? 3 : 2;
-    const float x_srf = x_xi == 1 ? 1.f : -1.f;
+    const int x_ia = dcx_f23_a(x_xi), x_ib = dcx_f23_b(x_xi);
+    const float x_srf = dcx_f23_sgn(x_xi);
     const dcx_f32x2 x_sr = {x_srf, x_srf};
     // columns read: NUP = 4: 0..3;  NUP = 2: nu group 0 -> 0, 1, 2 (nu 0, 1), group 1 -> 1, 2, 3 (nu 2, 3);  NUP = 1: the two columns of nu
     constexpr int NC = NUP == 4 ? 4 : NUP == 2 ? 3 : 2;
     int x_col[NC];
     if (NUP == 4) { for (int i = 0; i < NC; ++i) x_col[i] = i; }
     else if (NUP == 2) { for (int i = 0; i < NC; ++i) x_col[i] = x_ng + i; }
-    else { x_col[0] = x_ng == 0 ? 0 : x_ng == 2 ? 2 : 1; x_col[1] = x_ng == 2 ? 1 : x_ng == 3 ? 3 : 2; }
+    else { x_col[0] = dcx_f23_a(x_ng); x_col[1] = dcx_f23_b(x_ng); }
     int x_ra[NC], x_rb[NC];
 #pragma unroll
     for (int i = 0; i < NC; ++i) {
@@ -192,19 +170,6 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_wino2hs_kernel(c
     const float x_scf = (NUP == 1 && x_ng == 1) ? 1.f : -1.f;
     const dcx_f32x2 x_sc = {x_scf, x_scf};
     const int x_dst = (4 * x_xi + x_ng * NUP) * VPLANE + x_cq * 16 + x_tile;       // + local nu * VPLANE
-    auto fmas = [](const float4& x, const dcx_f32x2 s, const float4& y) {          // y + s * x (s = +-1: exactly y +- x)
-        const dcx_f32x2 lo = __builtin_elementwise_fma(dcx_f32x2{x.x, x.y}, s, dcx_f32x2{y.x, y.y});
-        const dcx_f32x2 hi = __builtin_elementwise_fma(dcx_f32x2{x.z, x.w}, s, dcx_f32x2{y.z, y.w});
-        return make_float4(lo.x, lo.y, hi.x, hi.y);
-    };
-    auto sub4 = [](const float4& x, const float4& y) {
-        const dcx_f32x2 lo = dcx_pk_sub(dcx_f32x2{x.x, x.y}, dcx_f32x2{y.x, y.y}), hi = dcx_pk_sub(dcx_f32x2{x.z, x.w}, dcx_f32x2{y.z, y.w});
-        return make_float4(lo.x, lo.y, hi.x, hi.y);
-    };
-    auto add4 = [](const float4& x, const float4& y) {
-        const dcx_f32x2 lo = dcx_pk_add(dcx_f32x2{x.x, x.y}, dcx_f32x2{y.x, y.y}), hi = dcx_pk_add(dcx_f32x2{x.z, x.w}, dcx_f32x2{y.z, y.w});
-        return make_float4(lo.x, lo.y, hi.x, hi.y);
-    };
     float4 xa[NC], xb[NC];
     auto xform_read = [&]() {
 #pragma unroll
@@ -213,22 +178,22 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_wino2hs_kernel(c
     auto xform_write = [&](float4* vbuf) {
         float4 t[NC];
 #pragma unroll
-        for (int i = 0; i < NC; ++i) t[i] = fmas(xb[i], x_sr, xa[i]);
+        for (int i = 0; i < NC; ++i) t[i] = dcx_fmas4(xb[i], x_sr, xa[i]);
         if constexpr (NUP == 4) {
-            vbuf[x_dst] = sub4(t[0], t[2]);
-            vbuf[x_dst + VPLANE] = add4(t[1], t[2]);
-            vbuf[x_dst + 2 * VPLANE] = sub4(t[2], t[1]);
-            vbuf[x_dst + 3 * VPLANE] = sub4(t[1], t[3]);
+            vbuf[x_dst] = dcx_sub4(t[0], t[2]);
+            vbuf[x_dst + VPLANE] = dcx_add4(t[1], t[2]);
+            vbuf[x_dst + 2 * VPLANE] = dcx_sub4(t[2], t[1]);
+            vbuf[x_dst + 3 * VPLANE] = dcx_sub4(t[1], t[3]);
         } else if constexpr (NUP == 2) {
             if (x_ng == 0) {            // columns 0, 1, 2: nu 0 = t0 - t2, nu 1 = t1 + t2
-                vbuf[x_dst] = sub4(t[0], t[2]);
-                vbuf[x_dst + VPLANE] = add4(t[1], t[2]);
+                vbuf[x_dst] = dcx_sub4(t[0], t[2]);
+                vbuf[x_dst + VPLANE] = dcx_add4(t[1], t[2]);
             } else {                    // columns 1, 2, 3: nu 2 = t2 - t1, nu 3 = t1 - t3
-                vbuf[x_dst] = sub4(t[1], t[0]);
-                vbuf[x_dst + VPLANE] = sub4(t[0], t[2]);
+                vbuf[x_dst] = dcx_sub4(t[1], t[0]);
+                vbuf[x_dst + VPLANE] = dcx_sub4(t[0], t[2]);
             }
         } else {
-            vbuf[x_dst] = fmas(t[1], x_sc, t[0]);       // nu 0: t0 - t2, 1: t1 + t2, 2: t2 - t1, 3: t1 - t3
+            vbuf[x_dst] = dcx_fmas4(t[1], x_sc, t[0]);       // nu 0: t0 - t2, 1: t1 + t2, 2: t2 - t1, 3: t1 - t3
         }
     };
 
@@ -255,12 +220,12 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_wino2hs_kernel(c
             float4 r0[ITER_R];
             const __amdgpu_buffer_rsrc_t rs0 = unit_rsrc(cur, 0);
 #pragma unroll
-            for (int k = 0; k < ITER_R; ++k) r0[k] = stage_fetch(rs0, roff[k]);
+            for (int k = 0; k < ITER_R; ++k) r0[k] = dcx_buffer_load_f4(rs0, roff[k]);
 #pragma unroll
             for (int i = 0; i < U - 1; ++i) {
                 const __amdgpu_buffer_rsrc_t rs = unit_rsrc(cur, i + 1 < nch ? i + 1 : nch - 1);
 #pragma unroll
-                for (int k = 0; k < ITER_R; ++k) rq[(i + 1) % U][k] = stage_fetch(rs, roff[k]);
+                for (int k = 0; k < ITER_R; ++k) rq[(i + 1) % U][k] = dcx_buffer_load_f4(rs, roff[k]);
                 if (i < UW - 1 || (UW == 1 && i == 0)) {
 #pragma unroll
                     for (int pp = 0; pp < 4; ++pp) aq[i % UW][pp] = load_a(wb0 + (unsigned)(i < nch ? i : nch - 1) * w_unit, pp);
@@ -293,7 +258,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_wino2hs_kernel(c
                 }
                 const __amdgpu_buffer_rsrc_t rs = unit_rsrc(cur, c + U < nch ? c + U : nch - 1);
 #pragma unroll
-                for (int k = 0; k < ITER_R; ++k) rq[K][k] = stage_fetch(rs, roff[k]);      // (the slot of this unit's own raw tile: stored a unit ago)
+                for (int k = 0; k < ITER_R; ++k) rq[K][k] = dcx_buffer_load_f4(rs, roff[k]);      // (the slot of this unit's own raw tile: stored a unit ago)
             }
             float4 bq[4];
 #pragma unroll
@@ -341,8 +306,8 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_wino2hs_kernel(c
         float e_ci[4], e_cj[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            e_ci[q] = (e_k >> 1) == 0 ? (q < 3 ? 1.f : 0.f) : (q == 0 ? 0.f : q == 1 ? 1.f : -1.f);
-            e_cj[q] = (e_k & 1) == 0 ? (q < 3 ? 1.f : 0.f) : (q == 0 ? 0.f : q == 1 ? 1.f : -1.f);
+            e_ci[q] = dcx_at23<float>(e_k >> 1, q);
+            e_cj[q] = dcx_at23<float>(e_k & 1, q);
         }
         dcx_f32x2 y01, y23;
 #pragma unroll
@@ -374,10 +339,7 @@ __global__ __launch_bounds__(C::NTHREADS, C::OCC) void dcx_conv_wino2hs_kernel(c
         }
         __syncthreads();                         // sR / sV / sX are free for the next item
     }
-    if (a.clk_probe != nullptr && blockIdx.x == 0 && tid == 0) {
-        a.clk_probe[2] = __builtin_amdgcn_s_memtime();
-        a.clk_probe[3] = __builtin_amdgcn_s_memrealtime();
-    }
+    dcx_probe_ends(a, tid, 2);
 }
 
 template <class C>
@@ -387,19 +349,7 @@ static int dcx_conv_wino2hs_launch_cfg(DcxConvArgs a, hipStream_t stream) {
     if (a.w_wino2 == nullptr || a.alpha == nullptr || a.beta == nullptr || a.out == nullptr) return DCX_E_ARG;
     if (a.cout_pad % C::COUT_TILE != 0 || a.cin % DCX_CCH != 0 || a.cin < 2 * DCX_CCH) return DCX_E_SHAPE;
     const long items = (long)a.n * (a.cout_pad / C::COUT_TILE) * a.tiles_x * a.tiles_y;
-    if (items <= 0 || items > 0x7fffffffL) return DCX_E_SHAPE;
-    const long resident = (long)C::OCC * dcx_device_cu_count();
-    const long blocks = items < resident ? items : resident;
-    a.xcd_walk = dcx_xcd_walk_enabled() && blocks == resident && (resident & 7) == 0 ? 1 : 0;
-    if (const int rc = dcx_fill_xcd_cum(a)) return rc;
     a.ct_outer = 0;
-    static bool attr_set[DCX_MAX_DEVICES] = {};
-    const int dev_i = dcx_current_device();
-    if (!attr_set[dev_i]) {
-        DCX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dcx_conv_wino2hs_kernel<C>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES));
-        attr_set[dev_i] = true;
-    }
-    hipLaunchKernelGGL((dcx_conv_wino2hs_kernel<C>), dim3((unsigned)blocks), dim3(C::NTHREADS), C::LDS_BYTES, stream, a);
-    return (int)hipGetLastError();
+    // DCX_OCC is not honoured: these launches give every item a CU of its own
+    return dcx_launch_persistent<&dcx_conv_wino2hs_kernel<C>>(a, items, C::NTHREADS, C::OCC, false, C::LDS_BYTES, (int)C::LDS_BYTES, stream);
 }

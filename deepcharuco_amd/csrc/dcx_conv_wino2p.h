@@ -14,7 +14,8 @@
 //       y[i][j] = sum_{xi, nu} AT[i][xi] AT[j][nu] m[xi][nu],  AT = [[1, 1, 0], [0, 1, 1]]       (output transform)
 //   All transform constants are 0 / +-1: the error growth is that of the direct sum.
 //
-// Kernel = dcx_conv_wino2h.h with 9 positions instead of 16 and the phase as a work-item dimension: workgroup = 4 waves = 64
+// Kernel = dcx_conv_wino2h.h with 9 positions instead of 16 and the phase as a work-item dimension (item walk, launcher and
+// helpers: dcx_conv_shared.h): workgroup = 4 waves = 64
 // couts x 32 2x2-tiles (8x16 low-resolution pixels of one phase); wave wm owns couts 16 wm .. 16 wm + 15 for all 32 tiles and
 // all 9 positions: 9 x 2 x 4 = 72 accumulator registers (AGPRs).  v_mfma_f32_16x16x4_f32, operands and summation order as there:
 //       m = 0;  for chunk c (16 cin) / j in 0..3 / g in 0..3:  m = fmaf(u[16c + 4g + j], v[16c + 4g + j], m)
@@ -96,35 +97,18 @@ __global__ __launch_bounds__(256, DCX_W2P_OCC) DCX_W2P_ATTR void dcx_conv_wino2p
     const int wm = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave = 16-cout group (and the channel quad it transforms)
     const int g4 = lane >> 4, l15 = lane & 15;
 
-    // ---- work list (persistent, XCD-aware walk: see the header comment); the four phases of a tile are neighbours --------
+    // ---- work list (persistent, XCD-aware walk: dcx_conv_shared.h); the four phases of a tile are neighbours --------
     const int tiles = a.tiles_x * a.tiles_y;
     const int n_ct = a.cout_pad / C::COUT_TILE;
-    int n_eff = a.n;
-    if (a.n_limit != nullptr) n_eff = min(n_eff, *a.n_limit);
+    const int n_eff = dcx_n_eff(a);
     const int total = ((n_eff + C::G - 1) / C::G) * n_ct * tiles * 4;      // G > 1: one work item covers G images (tiles == 1)
-    int w = blockIdx.x, w_end = total, gstride = gridDim.x;
-    if (a.xcd_walk && (gridDim.x & 7) == 0) {
-        const int x = blockIdx.x & 7;
-        const int lo = dcx_xcd_bound(total, x, a.xcd_cum[x]);           // equal eighths unless the launcher re-weighted the XCDs
-        w_end = dcx_xcd_bound(total, x + 1, a.xcd_cum[x + 1]);
-        gstride = gridDim.x >> 3;
-        w = lo + (blockIdx.x >> 3);
-    }
+    const DcxWalk wk = dcx_item_walk(a, total);
+    int w = wk.w;
+    const int w_end = wk.w_end, gstride = wk.gstride;
     if (w >= w_end) return;
-    if (a.clk_probe != nullptr && blockIdx.x == 0 && tid == 0) {
-        a.clk_probe[0] = __builtin_amdgcn_s_memtime();
-        a.clk_probe[1] = __builtin_amdgcn_s_memrealtime();
-    }
+    dcx_probe_ends(a, tid, 0);
     const int nch = a.cin / DCX_CCH;
-    auto decode = [&](int wi) {
-        DcxItem it;
-        it.ph = wi & 3; wi >>= 2;
-        it.tx = wi % a.tiles_x; wi /= a.tiles_x;
-        it.ty = wi % a.tiles_y; wi /= a.tiles_y;
-        it.ct = wi % n_ct;
-        it.n = wi / n_ct;
-        return it;
-    };
+    auto decode = [&](int wi) { return dcx_decode_item_phases(wi, a.tiles_x, a.tiles_y, n_ct); };
 
     // ---- operand fetch -----------------------------------------------------------------------------------------
     // weights [phase][pos][cin/4][cout_pad][4]: lane (r = l15, g = g4) reads cout wm*16 + r, channel quad g of the chunk
@@ -136,8 +120,7 @@ __global__ __launch_bounds__(256, DCX_W2P_OCC) DCX_W2P_ATTR void dcx_conv_wino2p
         return (unsigned)((c * CQC) * a.cout_pad + it.ct * C::COUT_TILE) * 16u + (unsigned)(it.ph * NP) * w_pos_stride;
     };
     auto load_a = [&](unsigned wbase, int pos) {
-        const dcx_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, w_lane_off, wbase + (unsigned)pos * w_pos_stride, 0);
-        return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+        return dcx_buffer_load_f4(w_rsrc, w_lane_off, wbase + (unsigned)pos * w_pos_stride);
     };
     const int tile_b = g4 * 32 + l15;
     auto load_b = [&](int buf, int pos, int tb) { return sB[buf * LDSF + pos * VPLANE + tile_b + tb * 16]; };
@@ -156,7 +139,7 @@ __global__ __launch_bounds__(256, DCX_W2P_OCC) DCX_W2P_ATTR void dcx_conv_wino2p
         const int hp = rem - cq * (C::HH * RW);
         const int hy = hp / RW, hx = hp - hy * RW;
         r_hyx |= (img << 9 | hy << 5 | hx) << (10 * k);
-        r_rel[k] = idx < C::RAW ? ((unsigned)img * in_img_stride + (unsigned)((cq * a.hin + hy) * a.win + hx)) * 16u : 0x80000000u;
+        r_rel[k] = idx < C::RAW ? ((unsigned)img * in_img_stride + (unsigned)((cq * a.hin + hy) * a.win + hx)) * 16u : DCX_OOB;
         r_slot[k] = idx < C::RAW ? ((img * CQC + cq) * C::HH + hy) * RP + hx + rowoff(hy) : RP - 1;
     }
     float4* sR = sB + 2 * LDSF;
@@ -191,10 +174,6 @@ __global__ __launch_bounds__(256, DCX_W2P_OCC) DCX_W2P_ATTR void dcx_conv_wino2p
         if (C::G > 1) return false;        // whole maps: every tile touches the zero border (and the last group may be short)
         const int sy0 = it.ty * C::TH - pad_y(it), sx0 = it.tx * C::TW - pad_x(it);
         return sy0 >= 0 && sx0 >= 0 && sy0 + C::HH <= a.hin && sx0 + RW <= a.win;
-    };
-    auto stage_fetch = [&](__amdgpu_buffer_rsrc_t rsrc, unsigned off) {
-        const dcx_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
-        return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
     };
     // Transform as 7 events (x = 0..6):
     //   0: read d[0][*], d[1][*]     1: read d[2][*]     2: t0 = d0 - d1, v[0][0], v[0][2]     3: write v[0][*]; v[1][0], v[1][2]
@@ -259,7 +238,7 @@ __global__ __launch_bounds__(256, DCX_W2P_OCC) DCX_W2P_ATTR void dcx_conv_wino2p
             const int ly = sy0 + ((r_hyx >> (10 * k + 5)) & 15), lx = sx0 + ((r_hyx >> (10 * k)) & 31);
             const bool inb = (unsigned)ly < (unsigned)a.hin && (unsigned)lx < (unsigned)a.win
                           && (C::G == 1 || cur.n * C::G + ((r_hyx >> (10 * k + 9)) & 1) < n_eff);
-            sR[r_slot[k]] = stage_fetch(r0, inb ? r_rel[k] : 0x80000000u);
+            sR[r_slot[k]] = dcx_buffer_load_f4(r0, inb ? r_rel[k] : DCX_OOB);
         }
         __syncthreads();
 #pragma unroll
@@ -306,7 +285,7 @@ __global__ __launch_bounds__(256, DCX_W2P_OCC) DCX_W2P_ATTR void dcx_conv_wino2p
                 const int ly = nsy0 + ((r_hyx >> (10 * k + 5)) & 15), lx = nsx0 + ((r_hyx >> (10 * k)) & 31);
                 const bool inb = (unsigned)ly < (unsigned)a.hin && (unsigned)lx < (unsigned)a.win
                               && (C::G == 1 || nxt.n * C::G + ((r_hyx >> (10 * k + 9)) & 1) < n_eff);
-                roff[k] = inb ? r_rel[k] : 0x80000000u;
+                roff[k] = inb ? r_rel[k] : DCX_OOB;
             }
         }
         // one position = 8 MFMAs (tb 0 / 1 alternating, j = 0..3) in two slots of four; each slot is preceded by one staging
@@ -325,7 +304,7 @@ __global__ __launch_bounds__(256, DCX_W2P_OCC) DCX_W2P_ATTR void dcx_conv_wino2p
                 }
                 {
                     const int e = p * 2 + slot;          // staging event 0 .. 17
-                    if (e >= C::E_RAW_LOAD && e < C::E_RAW_LOAD + ITER_R) rv[e - C::E_RAW_LOAD] = stage_fetch(rs_n, roff[e - C::E_RAW_LOAD]);
+                    if (e >= C::E_RAW_LOAD && e < C::E_RAW_LOAD + ITER_R) rv[e - C::E_RAW_LOAD] = dcx_buffer_load_f4(rs_n, roff[e - C::E_RAW_LOAD]);
                     if (e >= C::E_RAW_STORE && e < C::E_RAW_STORE + ITER_R) sR[r_slot[e - C::E_RAW_STORE]] = rv[e - C::E_RAW_STORE];
                     if (e >= C::E_XFORM && e < C::E_XFORM + 6) xform_event(vnext, e - C::E_XFORM);
                 }
@@ -504,10 +483,7 @@ __global__ __launch_bounds__(256, DCX_W2P_OCC) DCX_W2P_ATTR void dcx_conv_wino2p
         }
 
         if (!has_next) {
-            if (a.clk_probe != nullptr && blockIdx.x == 0 && tid == 0) {
-                a.clk_probe[2] = __builtin_amdgcn_s_memtime();
-                a.clk_probe[3] = __builtin_amdgcn_s_memrealtime();
-            }
+            dcx_probe_ends(a, tid, 2);
             return false;
         }
         if (cn == 0) w += gstride;
@@ -537,21 +513,7 @@ static int dcx_conv_wino2p_launch_cfg(DcxConvArgs a, hipStream_t stream) {
     if (C::EPI == DCX_EPI_HEAT && a.cout_pad != C::COUT_TILE) return DCX_E_SHAPE;     // the head sums over ONE cout tile
     if (C::G > 1 && (a.tiles_x != 1 || a.tiles_y != 1)) return DCX_E_SHAPE;                          // grouped: whole maps only
     const long items = (long)((a.n + C::G - 1) / C::G) * (a.cout_pad / C::COUT_TILE) * a.tiles_x * a.tiles_y * 4;
-    if (items <= 0 || items > 0x7fffffffL) return DCX_E_SHAPE;
     const size_t lds = C::LDS_BYTES + (size_t)a.cout_pad * (C::EPI == DCX_EPI_HEAT ? 12 : 8) + 256;
     if (DCX_W2P_OCC * lds > 160 * 1024) return DCX_E_SHAPE;
-    const int occ_env = dcx_occupancy_override();
-    const long resident = (long)(occ_env >= 1 && occ_env < DCX_W2P_OCC ? occ_env : DCX_W2P_OCC) * dcx_device_cu_count();
-    const long blocks = items < resident ? items : resident;
-    a.xcd_walk = dcx_xcd_walk_enabled() && blocks == resident && (resident & 7) == 0 ? 1 : 0;
-    if (const int rc = dcx_fill_xcd_cum(a)) return rc;
-    static bool attr_set[DCX_MAX_DEVICES] = {};
-    const int dev_i = dcx_current_device();
-    if (!attr_set[dev_i]) {
-        DCX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dcx_conv_wino2p_kernel<C>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-        attr_set[dev_i] = true;
-    }
-    hipLaunchKernelGGL((dcx_conv_wino2p_kernel<C>), dim3((unsigned)blocks), dim3(C::NTHREADS), lds, stream, a);
-    return (int)hipGetLastError();
+    return dcx_launch_persistent<&dcx_conv_wino2p_kernel<C>>(a, items, C::NTHREADS, DCX_W2P_OCC, true, lds, 80 * 1024, stream);
 }

@@ -12,6 +12,7 @@
 //   coefficients included, runs on the vector ALU as the same fmaf chain dcx_conv_wino2p.h runs on v_mfma_f32_4x4x1; then
 //   max(fmaf(y, alpha, beta2), 0), stored at stride 2 (phase (a, b): low-resolution pixel (y, x) -> output pixel (2 y + a, 2 x + b)).
 //   BN + ReLU layers only (the fused RefineNet head fills the chip at 16 patches and stays on dcx_conv_wino2p.h).
+//   Item walk, launcher and helpers: dcx_conv_shared.h.
 #pragma once
 #include "dcx_conv_wino2p.h"
 
@@ -56,35 +57,18 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void dcx_conv_wino2ps_kernel(const 
     const int cg = wv / 3;                                          // the wave's cout group
     const int g4 = lane >> 4, l15 = lane & 15;
 
-    // ---- work list (dcx_conv_wino2p.h: the four phases of a tile are neighbours) ---------------------------------------
+    // ---- work list (dcx_conv_shared.h; as in dcx_conv_wino2p.h the four phases of a tile are neighbours) ---------------------------------------
     const int tiles = a.tiles_x * a.tiles_y;
     const int n_ct = a.cout_pad / C::COUT_TILE;
-    int n_eff = a.n;
-    if (a.n_limit != nullptr) n_eff = min(n_eff, *a.n_limit);
+    const int n_eff = dcx_n_eff(a);
     const int total = n_eff * n_ct * tiles * 4;
-    int w = blockIdx.x, w_end = total, gstride = gridDim.x;
-    if (a.xcd_walk && (gridDim.x & 7) == 0) {
-        const int x = blockIdx.x & 7;
-        const int lo = dcx_xcd_bound(total, x, a.xcd_cum[x]);
-        w_end = dcx_xcd_bound(total, x + 1, a.xcd_cum[x + 1]);
-        gstride = gridDim.x >> 3;
-        w = lo + (blockIdx.x >> 3);
-    }
+    const DcxWalk wk = dcx_item_walk(a, total);
+    int w = wk.w;
+    const int w_end = wk.w_end, gstride = wk.gstride;
     if (w >= w_end) return;
-    if (a.clk_probe != nullptr && blockIdx.x == 0 && tid == 0) {
-        a.clk_probe[0] = __builtin_amdgcn_s_memtime();
-        a.clk_probe[1] = __builtin_amdgcn_s_memrealtime();
-    }
+    dcx_probe_ends(a, tid, 0);
     const int nch = a.cin / DCX_CCH;
-    auto decode = [&](int wi) {
-        DcxItem it;
-        it.ph = wi & 3; wi >>= 2;
-        it.tx = wi % a.tiles_x; wi /= a.tiles_x;
-        it.ty = wi % a.tiles_y; wi /= a.tiles_y;
-        it.ct = wi % n_ct;
-        it.n = wi / n_ct;
-        return it;
-    };
+    auto decode = [&](int wi) { return dcx_decode_item_phases(wi, a.tiles_x, a.tiles_y, n_ct); };
 
     // ---- operands ----------------------------------------------------------------------------------------------------
     // weights [phase][pos][cin/4][cout_pad][4]: lane (r = l15, g = g4) reads cout ct * COUT_TILE + cg * 16 + r, channel quad g of the chunk
@@ -93,8 +77,7 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void dcx_conv_wino2ps_kernel(const 
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(a.w_ups2w), (short)0, (int)(4u * NP * w_pos_stride), 0x00020000);
     auto load_a = [&](unsigned wbase, int pp) {
-        const dcx_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, w_lane_off, wbase + (unsigned)pp * w_pos_stride, 0);
-        return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+        return dcx_buffer_load_f4(w_rsrc, w_lane_off, wbase + (unsigned)pp * w_pos_stride);
     };
     // transformed activations sV[buf][pos][cq][tile]: lane (n = l15, g = g4) reads tile n, channel quad g
     auto load_b = [&](int buf, int pp) { return sB[buf * LDSV + (3 * pgp + pp) * VPLANE + lane]; };
@@ -109,13 +92,9 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void dcx_conv_wino2ps_kernel(const 
         const int hp = idx - cq * (HH * RW);
         const int hy = hp / RW, hx = hp - hy * RW;
         r_hyx[k] = hy << 16 | hx;
-        r_rel[k] = idx < C::RAW ? (unsigned)((cq * a.hin + hy) * a.win + hx) * 16u : 0x80000000u;
+        r_rel[k] = idx < C::RAW ? (unsigned)((cq * a.hin + hy) * a.win + hx) * 16u : DCX_OOB;
         r_slot[k] = idx < C::RAW ? C::raw_slot(cq, hy, hx) : C::RP - 1;      // slot RP - 1 of row 0 is free: dump slot
     }
-    auto stage_fetch = [&](__amdgpu_buffer_rsrc_t rsrc, unsigned off) {
-        const dcx_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
-        return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-    };
 
     // ---- staging: input transform.  Threads 0 .. 191 = (tile, cq, xi): t[s] = d[0][s] - d[1][s] | d[1][s] | d[2][s] - d[1][s], then
     // v[xi][0] = t[0] - t[1], v[xi][1] = t[1], v[xi][2] = t[2] - t[1] -- the exact fp32 differences dcx_conv_wino2p.h forms ------------
@@ -126,10 +105,6 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void dcx_conv_wino2ps_kernel(const 
     const int x_ra = C::raw_slot(x_cq, 2 * x_ty + (x_xi == 2 ? 2 : x_xi == 1 ? 1 : 0), 2 * x_tx);     // row A: d0 | d1 | d2
     const int x_rb = C::raw_slot(x_cq, 2 * x_ty + 1, 2 * x_tx);                                        // row B: d1
     const int x_dst = (3 * x_xi) * VPLANE + x_cq * 16 + x_tile;       // + nu * VPLANE
-    auto sub4 = [](const float4& x, const float4& y) {
-        const dcx_f32x2 lo = dcx_pk_sub(dcx_f32x2{x.x, x.y}, dcx_f32x2{y.x, y.y}), hi = dcx_pk_sub(dcx_f32x2{x.z, x.w}, dcx_f32x2{y.z, y.w});
-        return make_float4(lo.x, lo.y, hi.x, hi.y);
-    };
     float4 xa[3], xb[3];
     auto xform_read = [&]() {
         if (x_on) {
@@ -141,10 +116,10 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void dcx_conv_wino2ps_kernel(const 
         if (x_on) {
             float4 t[3];
 #pragma unroll
-            for (int s = 0; s < 3; ++s) t[s] = x_xi != 1 ? sub4(xa[s], xb[s]) : xa[s];
-            vbuf[x_dst] = sub4(t[0], t[1]);
+            for (int s = 0; s < 3; ++s) t[s] = x_xi != 1 ? dcx_sub4(xa[s], xb[s]) : xa[s];
+            vbuf[x_dst] = dcx_sub4(t[0], t[1]);
             vbuf[x_dst + VPLANE] = t[1];
-            vbuf[x_dst + 2 * VPLANE] = sub4(t[2], t[1]);
+            vbuf[x_dst + 2 * VPLANE] = dcx_sub4(t[2], t[1]);
         }
     };
 
@@ -167,7 +142,7 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void dcx_conv_wino2ps_kernel(const 
 #pragma unroll
         for (int k = 0; k < ITER_R; ++k) {
             const int ly = sy0 + (r_hyx[k] >> 16), lx = sx0 + (r_hyx[k] & 0xffff);
-            roff[k] = ((unsigned)ly < (unsigned)a.hin && (unsigned)lx < (unsigned)a.win) ? r_rel[k] : 0x80000000u;
+            roff[k] = ((unsigned)ly < (unsigned)a.hin && (unsigned)lx < (unsigned)a.win) ? r_rel[k] : DCX_OOB;
         }
         auto unit_rsrc = [&](int c) {
             const long tile_off = (long)sy0 * a.win + sx0;
@@ -180,12 +155,12 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void dcx_conv_wino2ps_kernel(const 
             float4 r0[ITER_R];
             const __amdgpu_buffer_rsrc_t rs0 = unit_rsrc(0);
 #pragma unroll
-            for (int k = 0; k < ITER_R; ++k) r0[k] = stage_fetch(rs0, roff[k]);
+            for (int k = 0; k < ITER_R; ++k) r0[k] = dcx_buffer_load_f4(rs0, roff[k]);
 #pragma unroll
             for (int i = 0; i < U - 1; ++i) {
                 const __amdgpu_buffer_rsrc_t rs = unit_rsrc(i + 1 < nch ? i + 1 : nch - 1);
 #pragma unroll
-                for (int k = 0; k < ITER_R; ++k) rq[(i + 1) % U][k] = stage_fetch(rs, roff[k]);
+                for (int k = 0; k < ITER_R; ++k) rq[(i + 1) % U][k] = dcx_buffer_load_f4(rs, roff[k]);
 #pragma unroll
                 for (int pp = 0; pp < 3; ++pp) aq[i][pp] = load_a(wb0 + (unsigned)(i < nch ? i : nch - 1) * w_unit, pp);
             }
@@ -214,7 +189,7 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void dcx_conv_wino2ps_kernel(const 
                 for (int pp = 0; pp < 3; ++pp) aq[(K + U - 1) % U][pp] = load_a(wb0 + (unsigned)cw * w_unit, pp);
                 const __amdgpu_buffer_rsrc_t rs = unit_rsrc(c + U < nch ? c + U : nch - 1);
 #pragma unroll
-                for (int k = 0; k < ITER_R; ++k) rq[K][k] = stage_fetch(rs, roff[k]);      // (the slot of this unit's own raw tile: stored a unit ago)
+                for (int k = 0; k < ITER_R; ++k) rq[K][k] = dcx_buffer_load_f4(rs, roff[k]);      // (the slot of this unit's own raw tile: stored a unit ago)
             }
             float4 bq[3];
 #pragma unroll
@@ -285,10 +260,7 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void dcx_conv_wino2ps_kernel(const 
         }
         __syncthreads();                         // sR / sV / sX are free for the next item
     }
-    if (a.clk_probe != nullptr && blockIdx.x == 0 && tid == 0) {
-        a.clk_probe[2] = __builtin_amdgcn_s_memtime();
-        a.clk_probe[3] = __builtin_amdgcn_s_memrealtime();
-    }
+    dcx_probe_ends(a, tid, 2);
 }
 
 template <class C>
@@ -299,18 +271,6 @@ static int dcx_conv_wino2ps_launch_cfg(DcxConvArgs a, hipStream_t stream) {
     if (a.cout_pad % C::COUT_TILE != 0 || a.cin % DCX_CCH != 0 || a.cin < 2 * DCX_CCH) return DCX_E_SHAPE;
     if (a.ups != 1 || a.pad != 1 || a.ho != 2 * a.hin || a.wo != 2 * a.win) return DCX_E_SHAPE;
     const long items = (long)a.n * (a.cout_pad / C::COUT_TILE) * a.tiles_x * a.tiles_y * 4;
-    if (items <= 0 || items > 0x7fffffffL) return DCX_E_SHAPE;
-    const long resident = (long)dcx_device_cu_count();
-    const long blocks = items < resident ? items : resident;
-    a.xcd_walk = dcx_xcd_walk_enabled() && blocks == resident && (resident & 7) == 0 ? 1 : 0;
-    if (const int rc = dcx_fill_xcd_cum(a)) return rc;
-    static bool attr_set[DCX_MAX_DEVICES] = {};
-    const int dev_i = dcx_current_device();
-    if (!attr_set[dev_i]) {
-        DCX_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&dcx_conv_wino2ps_kernel<C>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES));
-        attr_set[dev_i] = true;
-    }
-    hipLaunchKernelGGL((dcx_conv_wino2ps_kernel<C>), dim3((unsigned)blocks), dim3(C::NTHREADS), C::LDS_BYTES, stream, a);
-    return (int)hipGetLastError();
+    // one workgroup per CU; DCX_OCC is not honoured
+    return dcx_launch_persistent<&dcx_conv_wino2ps_kernel<C>>(a, items, C::NTHREADS, 1, false, C::LDS_BYTES, (int)C::LDS_BYTES, stream);
 }

@@ -1,0 +1,81 @@
+"""Refactoring aid: is the gfx950 device code of this tree the same as REV's?  Compiles the named translation units of
+deepcharuco_amd/csrc (default dcx_conv_mfma.hip) to assembly with the Makefile's flags, once from this tree and once from
+`git archive REV`, and compares kernel by kernel after dropping the __hip_cuid_ lines (a hash of the source text).  No GPU.
+usage: python tools/isa_same.py REV [file.hip ...]      exit status 0 only if every kernel is identical"""
+import collections, os, re, subprocess, sys, tempfile
+from concurrent.futures import ThreadPoolExecutor
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = "deepcharuco_amd/csrc"
+HIPCC = os.environ.get("HIPCC") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+FIGS = (".vgpr_count", ".agpr_count", ".sgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size",
+        ".group_segment_fixed_size")
+
+
+def git(*args):
+    return subprocess.run(("git", "-C", ROOT) + args, check=True, capture_output=True, text=True).stdout.strip()
+
+
+def compile_s(tree, unit, out):
+    mk = open(os.path.join(tree, CSRC, "Makefile")).read()
+    flags = re.search(r"^CXXFLAGS\s*:=\s*(.*)$", mk, re.M).group(1).replace("$(ARCH)", "gfx950").split()
+    r = subprocess.run([HIPCC] + flags + ["--cuda-device-only", "-S", os.path.join(tree, CSRC, unit), "-o", out], capture_output=True, text=True)
+    if r.returncode != 0:
+        sys.exit("hipcc failed on %s of %s:\n%s" % (unit, tree, r.stderr[-4000:]))
+    return "".join(l for l in open(out) if "__hip_cuid_" not in l)
+
+
+def kernels(s):
+    """name -> (function body + kernel descriptor, resource figures, instruction count)"""
+    meta = {}
+    for item in re.split(r"\n  - (?=\.)", s[s.index("amdhsa.kernels:"):] if "amdhsa.kernels:" in s else ""):
+        name = re.search(r"\.name:\s+(\S+)", item)
+        if name:
+            meta[name.group(1)] = {f: int(m.group(1)) for f in FIGS for m in [re.search(re.escape(f) + r":\s+(\d+)", item)] if m}
+    res = collections.OrderedDict()
+    for m in re.finditer(r"^\t\.amdhsa_kernel (\S+)\n.*?\.end_amdhsa_kernel\n", s, re.M | re.S):
+        sym = m.group(1)
+        start = re.search(r"^%s:[^\n]*\n" % re.escape(sym), s, re.M).end()
+        body = s[start:s.index(".Lfunc_end", start)]
+        n_ins = sum(1 for l in body.split("\n") if l.startswith("\t") and not l.strip().startswith((".", ";")))
+        res[sym] = (body + m.group(0), meta.get(sym, {}), n_ins)
+    return res
+
+
+def main():
+    if len(sys.argv) < 2:
+        sys.exit(__doc__)
+    rev, units = sys.argv[1], sys.argv[2:] or ["dcx_conv_mfma.hip"]
+    dirty = git("status", "--porcelain", "--", CSRC, "include") != ""
+    print("base  %s (%s)" % (git("rev-parse", rev), rev))
+    print("this  %s%s" % (git("rev-parse", "HEAD"), " + working-tree changes" if dirty else ""))
+    print(subprocess.run([HIPCC, "--version"], check=True, capture_output=True, text=True).stdout.split("\n")[0])
+    n_same = n_all = 0
+    with tempfile.TemporaryDirectory() as tmp:
+        base = os.path.join(tmp, "base")
+        os.mkdir(base)
+        tar = subprocess.run(["git", "-C", ROOT, "archive", rev, CSRC, "include"], check=True, capture_output=True).stdout
+        subprocess.run(["tar", "-x", "-C", base], input=tar, check=True)
+        for unit in units:
+            with ThreadPoolExecutor(2) as ex:
+                fa = ex.submit(compile_s, base, unit, os.path.join(tmp, "a.s"))
+                fb = ex.submit(compile_s, ROOT, unit, os.path.join(tmp, "b.s"))
+                ka, kb = kernels(fa.result()), kernels(fb.result())
+            print("%s: %d kernels at the base, %d here" % (unit, len(ka), len(kb)))
+            for sym in list(ka) + [k for k in kb if k not in ka]:
+                n_all += 1
+                if sym not in ka or sym not in kb:
+                    print("  ONLY %s  %s" % ("base" if sym in ka else "here", sym))
+                elif ka[sym][0] == kb[sym][0]:
+                    n_same += 1
+                    print("  identical  %s" % sym)
+                else:
+                    figs = "same" if ka[sym][1] == kb[sym][1] else " ".join(
+                        "%s %d->%d" % (f, ka[sym][1].get(f, -1), kb[sym][1].get(f, -1)) for f in FIGS if ka[sym][1].get(f) != kb[sym][1].get(f))
+                    print("  DIFFERS    %s   resource figures: %s   instructions: %d -> %d (%+d)"
+                          % (sym, figs, ka[sym][2], kb[sym][2], kb[sym][2] - ka[sym][2]))
+    print("%d of %d kernels identical" % (n_same, n_all))
+    sys.exit(0 if n_same == n_all and n_all > 0 else 1)
+
+
+if __name__ == "__main__":
+    main()
