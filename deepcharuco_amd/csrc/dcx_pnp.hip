@@ -62,19 +62,8 @@ extern "C" int dcx_solve_pnp_pool(const int32_t* d_counts, const int32_t* d_star
     if (!d_counts || !d_starts || !d_rows || !h_camera9 || !d_status || !d_pose) return DCX_E_ARG;
     if (batch <= 0 || pool < 0 || col_count < 2 || row_count < 2) return DCX_E_ARG;
     if ((long long)(col_count - 1) * (row_count - 1) > 0x7fffffffLL) return DCX_E_ARG;
-    if (!(n_dist == 0 || n_dist == 4 || n_dist == 5 || n_dist == 8) || (n_dist > 0 && !h_dist)) return DCX_E_ARG;
-    if (h_camera9[1] != 0.0) return DCX_E_ARG;                     // skew is not supported
     PnpCamera cam;
-    cam.fx = h_camera9[0];
-    cam.fy = h_camera9[4];
-    cam.cx = h_camera9[2];
-    cam.cy = h_camera9[5];
-    if (!(isfinite(cam.fx) && isfinite(cam.fy) && isfinite(cam.cx) && isfinite(cam.cy)) || cam.fx == 0.0 || cam.fy == 0.0)
-        return DCX_E_ARG;
-    for (int i = 0; i < 8; ++i) {
-        cam.k[i] = i < n_dist ? h_dist[i] : 0.0;
-        if (!isfinite(cam.k[i])) return DCX_E_ARG;
-    }
+    if (!pnp_camera(h_camera9, h_dist, n_dist, cam)) return DCX_E_ARG;
     if (!isfinite(square_len)) return DCX_E_ARG;
     hipLaunchKernelGGL(dcx_solve_pnp_kernel, dim3((unsigned)batch), dim3(kLanes), 0, (hipStream_t)stream, d_counts, d_starts, d_rows,
                        d_xy, pool, (col_count - 1) * (row_count - 1), row_count - 1, square_len, cam, d_status, d_pose);

@@ -1,6 +1,7 @@
 // dcx_pnp_dev.h -- the fp64 device steps of the PnP solver (dcx_pnp.hip) that the camera calibration (dcx_calib.hip) reuses:
 // packed symmetric storage, the wave butterfly, cyclic Jacobi, Rodrigues both ways, the SO(3) right Jacobian, the pool reader
-// (Frame), undistortPoints, the 6x6 Cholesky, the planar DLT homography, the planar pose init and the PnP Levenberg-Marquardt.
+// (Frame), undistortPoints, the 6x6 Cholesky, the planar DLT homography, the planar pose init and the PnP Levenberg-Marquardt; dcx_pnp_ransac.hip runs the
+// last three over an index list of a frame's rows (the frame type is a template parameter).
 // deepcharuco_amd/pnp.py restates every step (its functions of the same names).  Everything is force-inlined and has internal
 // linkage, so each translation unit compiles its own copy.
 #pragma once
@@ -20,6 +21,23 @@ struct PnpCamera {
     double fx, fy, cx, cy;
     double k[8];            // k1 k2 p1 p2 k3 k4 k5 k6, zero padded
 };
+
+// K (row major, no skew) and 0 / 4 / 5 / 8 distortion coefficients from the host -> the kernel argument; false if refused
+inline bool pnp_camera(const double* h_camera9, const double* h_dist, int n_dist, PnpCamera& cam) {
+    if (!h_camera9 || !(n_dist == 0 || n_dist == 4 || n_dist == 5 || n_dist == 8) || (n_dist > 0 && !h_dist)) return false;
+    if (h_camera9[1] != 0.0) return false;                         // skew is not supported
+    cam.fx = h_camera9[0];
+    cam.fy = h_camera9[4];
+    cam.cx = h_camera9[2];
+    cam.cy = h_camera9[5];
+    if (!(isfinite(cam.fx) && isfinite(cam.fy) && isfinite(cam.cx) && isfinite(cam.cy)) || cam.fx == 0.0 || cam.fy == 0.0)
+        return false;
+    for (int i = 0; i < 8; ++i) {
+        cam.k[i] = i < n_dist ? h_dist[i] : 0.0;
+        if (!isfinite(cam.k[i])) return false;
+    }
+    return true;
+}
 
 // packed upper triangle of a symmetric N x N matrix, row major
 template <int N>
@@ -167,6 +185,15 @@ struct Frame {
     }
 };
 
+// The rows of a frame picked by an index list (the RANSAC refit over the inlier slots): row i of this frame is row idx[i] of base.
+struct IndexedFrame {
+    Frame base;
+    const int32_t* idx;
+    int n;
+
+    __device__ __forceinline__ void load(int i, double& X, double& Y, double& u, double& v) const { base.load(idx[i], X, Y, u, v); }
+};
+
 __device__ __forceinline__ void undistort(const PnpCamera& cam, bool dist, double u, double v, double& x, double& y) {
     const double x0 = (u - cam.cx) / cam.fx, y0 = (v - cam.cy) / cam.fy;
     x = x0;
@@ -190,8 +217,8 @@ __device__ __forceinline__ void undistort(const PnpCamera& cam, bool dist, doubl
 
 // Sum over the frame's points of the squared reprojection error at pose p (+inf if a point is not in front of the camera) and,
 // with JAC, of JtJ (21, packed) and Jtr (6).  acc = {cost, JtJ[21], Jtr[6]} on return, identical in every lane.
-template <bool JAC>
-__device__ __forceinline__ void evaluate(const Frame& f, const PnpCamera& cam, const double* p, double (&acc)[28]) {
+template <bool JAC, class F>
+__device__ __forceinline__ void evaluate(const F& f, const PnpCamera& cam, const double* p, double (&acc)[28]) {
     double R[9], G[2][9];           // G[c] = -R [e_c]x Jr: d(R m)/dr for the board point m = e_c (the board has z = 0)
     rodrigues(p, R);
     if (JAC) {
@@ -312,7 +339,8 @@ __device__ __forceinline__ bool cholesky_solve(const double* jtj, const double* 
 
 // Planar DLT (pnp._homography) of the board points to the (undistorted) image points -> status; H (row major, h33 = 1) maps
 // the centred board points (X - mcx, Y - mcy) to the image points.
-__device__ __forceinline__ int homography(const Frame& f, const PnpCamera& cam, bool dist, double* H, double& mc_x, double& mc_y) {
+template <class F>
+__device__ __forceinline__ int homography(const F& f, const PnpCamera& cam, bool dist, double* H, double& mc_x, double& mc_y) {
     const int lane = threadIdx.x;
     const double n = (double)f.n;
     // centroids of the board points and of the normalised image points
@@ -408,12 +436,13 @@ __device__ __forceinline__ int homography(const Frame& f, const PnpCamera& cam, 
     return DCX_PNP_OK;
 }
 
-// Planar initialisation (pnp._init_pose) -> status; p0 = rvec, tvec
-__device__ __forceinline__ int init_pose(const Frame& f, const PnpCamera& cam, bool dist, double* p0) {
+// Planar initialisation (pnp._init_pose) -> status; p0 = rvec, tvec.  homography() is found by the frame's type: a frame of exactly
+// four rows may bring its own (dcx_pnp_ransac.hip); everything after it is per lane.
+template <class F>
+__device__ __forceinline__ int init_pose(const F& f, const PnpCamera& cam, bool dist, double* p0) {
     double H[9], mcx, mcy;
     const int st = homography(f, cam, dist, H, mcx, mcy);
     if (st != DCX_PNP_OK) return st;
-    // OpenCV's decomposition (cvFindExtrinsicCameraParams2, planar branch)
     const double n1 = sqrt(H[0] * H[0] + H[3] * H[3] + H[6] * H[6]);
     const double n2 = sqrt(H[1] * H[1] + H[4] * H[4] + H[7] * H[7]);
     const double i1 = 1.0 / fmax(n1, 2.2e-16), i2 = 1.0 / fmax(n2, 2.2e-16), it = 2.0 / fmax(n1 + n2, 2.2e-16);
@@ -463,7 +492,8 @@ __device__ __forceinline__ int init_pose(const Frame& f, const PnpCamera& cam, b
     return DCX_PNP_OK;
 }
 
-__device__ __forceinline__ int solve(const Frame& f, const PnpCamera& cam, double* pose) {
+template <class F>
+__device__ __forceinline__ int solve(const F& f, const PnpCamera& cam, double* pose) {
     bool dist = false;
 #pragma unroll
     for (int i = 0; i < 8; ++i) dist |= cam.k[i] != 0.0;

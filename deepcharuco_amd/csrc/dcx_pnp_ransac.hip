@@ -1,0 +1,328 @@
+// dcx_pnp_ransac.hip -- the PnP solver of dcx_pnp.hip behind a consensus search (cv2.solvePnPRansac's role), read in place from the
+// corner pool.  deepcharuco_amd/pnp.py restates every step (solve_pnp_ransac_host_full), which is the pin of these kernels.
+//
+// Two launches on the caller's stream, all fp64:
+//   hypotheses  grid (frame, block of 64 hypotheses), one LANE per hypothesis: an integer counter hash of (seed, n, h, draw) picks
+//               four rows with distinct ids and no collinear triple, the homography through them comes in closed form (H = B adj(A)
+//               of the two projective bases: four points determine it, so the 9x9 eigenproblem of the DLT has nothing to add and its
+//               81-double eigenvector matrix would not fit a lane), init_pose's decomposition turns it into a pose, and a serial loop over
+//               the frame's rows (every lane reads the same row) counts those within reproj_error px.  Score (-1: no hypothesis)
+//               and pose go to the workspace.
+//   select      one wave per frame: first maximum of the scores in a fixed order, the winner's mask recomputed and written, its
+//               slots compacted in order into an index list, then the unchanged solve() (init + LM) over that list.
+// The sampler never looks at the frame's position in the batch, nothing is allocated, no atomics, no early exit: the work is fixed,
+// two runs give the same bits and the call can be captured in a hipGraph.
+#include "dcx_pnp_dev.h"
+
+namespace {
+
+constexpr int kMaxIterations = 4096; // hypotheses per frame (pnp.RANSAC_MAX_ITERATIONS)
+constexpr int kSampleTries = 8;      // complete 4-samples per hypothesis (pnp.RANSAC_SAMPLE_TRIES)
+constexpr int kMaxDraws = 256;       // slot draws per hypothesis, redraws included (pnp.RANSAC_MAX_DRAWS)
+
+// The per-frame checks of dcx_solve_pnp_kernel, in its order -> DCX_PNP_OK if the frame's rows can be read and solved.  Wave-wide.
+__device__ __forceinline__ int frame_status(const int32_t* counts, const int32_t* starts, const int32_t* rows, int b, int pool,
+                                            int n_ids, int& n, int& s0) {
+    n = counts[b];
+    s0 = starts[b];
+    if (n <= 0) return DCX_PNP_TOO_FEW;
+    if (s0 < 0 || (long long)s0 + n > (long long)pool) return DCX_PNP_TRUNCATED;      // (its slots are not read)
+    if (n < 4) return DCX_PNP_TOO_FEW;
+    bool bad = false;
+    for (int i = threadIdx.x; i < n; i += kLanes) {
+        const int id = rows[4 * ((long long)s0 + i) + 2];
+        bad |= id < 0 || id >= n_ids;
+    }
+    return __any(bad) ? DCX_PNP_BAD_ID : DCX_PNP_OK;
+}
+
+__device__ __forceinline__ uint32_t mix32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7FEB352Du;
+    x ^= x >> 15;
+    x *= 0x846CA68Bu;
+    return x ^ (x >> 16);
+}
+
+// draw c of hypothesis h of a frame with n rows -> a slot in [0, n)  (pnp._ransac_draw)
+__device__ __forceinline__ int ransac_draw(uint32_t seed, uint32_t n, uint32_t h, uint32_t c) {
+    const uint32_t r = mix32(seed ^ mix32(n * 0x9E3779B9u + mix32(h * 0x85EBCA6Bu + c)));
+    return (int)(((uint64_t)r * n) >> 32);
+}
+
+__device__ __forceinline__ bool on_a_line(const int* gx, const int* gy, int a, int b, int c) {
+    return (long long)(gx[b] - gx[a]) * (gy[c] - gy[a]) - (long long)(gy[b] - gy[a]) * (gx[c] - gx[a]) == 0;
+}
+
+// pnp._ransac_sample: four distinct slots whose ids are distinct and hold no collinear triple on the id grid; false if none came
+__device__ __forceinline__ bool ransac_sample(const int32_t* rows, uint32_t seed, int n, int h, int rm1, int (&s)[4]) {
+    uint32_t c = 0;
+#pragma unroll 1
+    for (int attempt = 0; attempt < kSampleTries; ++attempt) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            while (true) {
+                if (c >= (uint32_t)kMaxDraws) return false;
+                const int i = ransac_draw(seed, (uint32_t)n, (uint32_t)h, c++);
+                bool held = false;
+#pragma unroll
+                for (int j = 0; j < k; ++j) held |= s[j] == i;
+                if (!held) {
+                    s[k] = i;
+                    break;
+                }
+            }
+        }
+        int id[4], gx[4], gy[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            id[k] = rows[4 * s[k] + 2];
+            gx[k] = id[k] % rm1;
+            gy[k] = id[k] / rm1;
+        }
+        const bool shared = id[0] == id[1] || id[0] == id[2] || id[0] == id[3] || id[1] == id[2] || id[1] == id[3] || id[2] == id[3];
+        if (!shared && !on_a_line(gx, gy, 1, 2, 3) && !on_a_line(gx, gy, 0, 2, 3) && !on_a_line(gx, gy, 0, 1, 3) &&
+            !on_a_line(gx, gy, 0, 1, 2))
+            return true;
+    }
+    return false;
+}
+
+// adjugate of a row-major 3x3
+__device__ __forceinline__ void adjugate(const double* m, double* a) {
+    a[0] = m[4] * m[8] - m[5] * m[7]; a[1] = m[2] * m[7] - m[1] * m[8]; a[2] = m[1] * m[5] - m[2] * m[4];
+    a[3] = m[5] * m[6] - m[3] * m[8]; a[4] = m[0] * m[8] - m[2] * m[6]; a[5] = m[2] * m[3] - m[0] * m[5];
+    a[6] = m[3] * m[7] - m[4] * m[6]; a[7] = m[1] * m[6] - m[0] * m[7]; a[8] = m[0] * m[4] - m[1] * m[3];
+}
+
+// pnp._projective_basis: the 3x3 that sends e1, e2, e3, (1,1,1) to the four points, each up to scale
+__device__ __forceinline__ void projective_basis(const double* x, const double* y, double* A) {
+    const double m[9] = {x[0], x[1], x[2], y[0], y[1], y[2], 1.0, 1.0, 1.0};
+    double a[9];
+    adjugate(m, a);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double lam = a[j * 3] * x[3] + a[j * 3 + 1] * y[3] + a[j * 3 + 2];
+        A[j] = m[j] * lam;
+        A[3 + j] = m[3 + j] * lam;
+        A[6 + j] = lam;
+    }
+}
+
+// squared reprojection error (px^2) of one row at the pose (R, t) through the full distortion model; +inf if the point is not in
+// front of the camera (evaluate()'s projection, per row)
+__device__ __forceinline__ double row_error2(const double* R, const double* t, const PnpCamera& cam, double mx, double my, double u,
+                                             double v) {
+    const double X = R[0] * mx + R[1] * my + t[0];
+    const double Y = R[3] * mx + R[4] * my + t[1];
+    const double Z = R[6] * mx + R[7] * my + t[2];
+    if (!(Z > 0)) return INFINITY;
+    const double* k = cam.k;
+    const double iz = 1.0 / Z, x = X * iz, y = Y * iz;
+    const double r2 = x * x + y * y;
+    const double num = 1 + r2 * (k[0] + r2 * (k[1] + r2 * k[4]));
+    const double den = 1 + r2 * (k[5] + r2 * (k[6] + r2 * k[7]));
+    const double g = num / den;
+    const double xd = x * g + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x);
+    const double yd = y * g + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y;
+    const double ru = cam.fx * xd + cam.cx - u, rv = cam.fy * yd + cam.cy - v;
+    return ru * ru + rv * rv;
+}
+
+// Four sampled rows of a frame, held by one lane: board points and undistorted image points.
+struct Sample {
+    double mx[4], my[4], x[4], y[4];
+};
+
+// pnp._homography4: the homography through exactly four points in closed form, H = B adj(A) with A, B the projective bases of the
+// centred board points and of the image points.  init_pose() picks this overload for a Sample; no cross-lane step.
+__device__ __forceinline__ int homography(const Sample& q, const PnpCamera&, bool, double* H, double& mc_x, double& mc_y) {
+    const double mcx = (q.mx[0] + q.mx[1] + q.mx[2] + q.mx[3]) / 4.0, mcy = (q.my[0] + q.my[1] + q.my[2] + q.my[3]) / 4.0;
+    double cx[4], cy[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        cx[k] = q.mx[k] - mcx;
+        cy[k] = q.my[k] - mcy;
+    }
+    double A[9], B[9], Aa[9];
+    projective_basis(cx, cy, A);
+    projective_basis(q.x, q.y, B);
+    adjugate(A, Aa);
+    double hmax = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            H[i * 3 + j] = B[i * 3] * Aa[j] + B[i * 3 + 1] * Aa[3 + j] + B[i * 3 + 2] * Aa[6 + j];
+            hmax = fmax(hmax, fabs(H[i * 3 + j]));
+        }
+    if (!(fabs(H[8]) > 1e-12 * hmax)) return DCX_PNP_DEGENERATE;
+    const double h22 = H[8];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) H[i] /= h22;
+    mc_x = mcx;
+    mc_y = mcy;
+    return DCX_PNP_OK;
+}
+
+// hypothesis h of frame f in this lane -> its score, or -1 if it has none; p0 = its pose
+__device__ __forceinline__ int hypothesis(const Frame& f, const PnpCamera& cam, bool dist, uint32_t seed, int h, double thr2, double* p0) {
+    int s[4];
+    if (!ransac_sample(f.rows, seed, f.n, h, f.rm1, s)) return -1;
+    Sample q;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        double u, v;
+        f.load(s[k], q.mx[k], q.my[k], u, v);
+        undistort(cam, dist, u, v, q.x[k], q.y[k]);
+    }
+    if (init_pose(q, cam, dist, p0) != DCX_PNP_OK) return -1;
+    double R[9];
+    rodrigues(p0, R);
+    int score = 0;
+    for (int i = 0; i < f.n; ++i) {
+        double bx, by, u, v;
+        f.load(i, bx, by, u, v);
+        score += row_error2(R, p0 + 3, cam, bx, by, u, v) <= thr2 ? 1 : 0;
+    }
+    return score;
+}
+
+__device__ __forceinline__ bool has_distortion(const PnpCamera& cam) {
+    bool dist = false;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) dist |= cam.k[i] != 0.0;
+    return dist;
+}
+
+__global__ __launch_bounds__(kLanes) void dcx_pnp_ransac_hypotheses_kernel(
+    const int32_t* __restrict__ counts, const int32_t* __restrict__ starts, const int32_t* __restrict__ rows,
+    const float* __restrict__ xy, int pool, int n_ids, int rm1, double square_len, PnpCamera cam, int iterations, double thr2,
+    uint32_t seed, int32_t* __restrict__ scores, double* __restrict__ poses) {
+    const int b = blockIdx.x, h = blockIdx.y * kLanes + threadIdx.x;
+    int n, s0;
+    if (frame_status(counts, starts, rows, b, pool, n_ids, n, s0) != DCX_PNP_OK) return;   // select reports it and reads no score
+    if (h >= iterations) return;
+    const Frame f{rows + 4 * (long long)s0, xy ? xy + 2 * (long long)s0 : nullptr, n, rm1, square_len};
+    double p0[6] = {0, 0, 0, 0, 0, 0};
+    const int score = hypothesis(f, cam, has_distortion(cam), seed, h, thr2, p0);
+    const long long at = (long long)b * iterations + h;
+    scores[at] = score;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) poses[6 * at + i] = p0[i];
+}
+
+__global__ __launch_bounds__(kLanes) void dcx_pnp_ransac_select_kernel(
+    const int32_t* __restrict__ counts, const int32_t* __restrict__ starts, const int32_t* __restrict__ rows,
+    const float* __restrict__ xy, int pool, int n_ids, int rm1, double square_len, PnpCamera cam, int iterations, double thr2,
+    int min_inliers, const int32_t* __restrict__ scores, const double* __restrict__ poses, int32_t* idx,
+    int32_t* __restrict__ status, double* __restrict__ pose, int32_t* __restrict__ info, uint8_t* __restrict__ inliers) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    int n, s0;
+    int st = frame_status(counts, starts, rows, b, pool, n_ids, n, s0);
+    double out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int winner = -1, count = 0;
+    if (st == DCX_PNP_OK) {
+        // the highest score, the lowest h among equals: ascending h in each lane, then a butterfly with the same rule
+        int best = -1, bh = 0x7fffffff;
+        for (int h = lane; h < iterations; h += kLanes) {
+            const int sc = scores[(long long)b * iterations + h];
+            if (sc > best) {
+                best = sc;
+                bh = h;
+            }
+        }
+#pragma unroll
+        for (int m = kLanes / 2; m >= 1; m >>= 1) {
+            const int ob = __shfl_xor(best, m, kLanes), oh = __shfl_xor(bh, m, kLanes);
+            if (ob > best || (ob == best && oh < bh)) {
+                best = ob;
+                bh = oh;
+            }
+        }
+        if (best < 0) {
+            st = DCX_PNP_DEGENERATE;
+        } else {
+            winner = bh;
+            const Frame f{rows + 4 * (long long)s0, xy ? xy + 2 * (long long)s0 : nullptr, n, rm1, square_len};
+            double p[6], R[9];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) p[i] = poses[6 * ((long long)b * iterations + winner) + i];
+            rodrigues(p, R);
+            int32_t* list = idx + s0;                      // this frame's share of the index list: its own slots
+            for (int base = 0; base < n; base += kLanes) {
+                const int i = base + lane;
+                bool in = false;
+                if (i < n) {
+                    double bx, by, u, v;
+                    f.load(i, bx, by, u, v);
+                    in = row_error2(R, p + 3, cam, bx, by, u, v) <= thr2;
+                    if (inliers) inliers[(long long)s0 + i] = in ? 1 : 0;
+                }
+                const unsigned long long m = __ballot(in);
+                if (in) list[count + __popcll(m & ((1ull << lane) - 1ull))] = i;
+                count += __popcll(m);
+            }
+            __syncthreads();                               // one wave: the list is read below by other lanes than wrote it
+            if (count < max(min_inliers, 4)) {
+                st = DCX_PNP_NO_CONSENSUS;
+            } else {
+                const IndexedFrame g{f, list, count};
+                st = solve(g, cam, out);
+            }
+        }
+    }
+    if (st != DCX_PNP_OK) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) out[i] = 0.0;
+        count = 0;
+        // no pose, no inliers: every slot of the frame that lies in the pool (the lane that wrote a slot above rewrites it)
+        if (inliers && n > 0 && s0 >= 0)
+            for (long long i = lane; i < n && s0 + i < pool; i += kLanes) inliers[s0 + i] = 0;
+    }
+    if (lane == 0) {
+        status[b] = st;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) pose[8 * (long long)b + i] = out[i];
+        info[2 * (long long)b] = count;
+        info[2 * (long long)b + 1] = winner;
+    }
+}
+
+}  // namespace
+
+// workspace: poses f64 [B][iterations][6] | scores int32 [B][iterations] | inlier index list int32 [pool]
+extern "C" size_t dcx_solve_pnp_ransac_workspace_bytes(int batch, int pool, int iterations) {
+    if (batch <= 0 || pool < 0 || iterations < 1 || iterations > kMaxIterations) return 0;
+    const size_t hyp = (size_t)batch * (size_t)iterations;
+    return (hyp * (6 * sizeof(double) + sizeof(int32_t)) + (size_t)pool * sizeof(int32_t) + 7) & ~(size_t)7;
+}
+
+extern "C" int dcx_solve_pnp_ransac_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows, const float* d_xy,
+                                         int batch, int pool, int col_count, int row_count, double square_len,
+                                         const double* h_camera9, const double* h_dist, int n_dist, int iterations,
+                                         double reproj_error, int min_inliers, unsigned seed, void* d_workspace,
+                                         size_t workspace_bytes, int32_t* d_status, double* d_pose, int32_t* d_info,
+                                         uint8_t* d_inliers, void* stream) {
+    if (!d_counts || !d_starts || !d_rows || !h_camera9 || !d_status || !d_pose || !d_info || !d_workspace) return DCX_E_ARG;
+    if (batch <= 0 || pool < 0 || col_count < 2 || row_count < 2) return DCX_E_ARG;
+    if ((long long)(col_count - 1) * (row_count - 1) > 0x7fffffffLL) return DCX_E_ARG;
+    PnpCamera cam;
+    if (!pnp_camera(h_camera9, h_dist, n_dist, cam)) return DCX_E_ARG;
+    if (!isfinite(square_len)) return DCX_E_ARG;
+    if (iterations < 1 || iterations > kMaxIterations || !isfinite(reproj_error) || !(reproj_error > 0)) return DCX_E_ARG;
+    if (workspace_bytes < dcx_solve_pnp_ransac_workspace_bytes(batch, pool, iterations) || ((uintptr_t)d_workspace & 7)) return DCX_E_ARG;
+    const size_t hyp = (size_t)batch * (size_t)iterations;
+    double* poses = (double*)d_workspace;
+    int32_t* scores = (int32_t*)(poses + 6 * hyp);
+    int32_t* idx = scores + hyp;
+    const int n_ids = (col_count - 1) * (row_count - 1), rm1 = row_count - 1;
+    const double thr2 = reproj_error * reproj_error;
+    hipLaunchKernelGGL(dcx_pnp_ransac_hypotheses_kernel, dim3((unsigned)batch, (unsigned)((iterations + kLanes - 1) / kLanes)),
+                       dim3(kLanes), 0, (hipStream_t)stream, d_counts, d_starts, d_rows, d_xy, pool, n_ids, rm1, square_len, cam,
+                       iterations, thr2, (uint32_t)seed, scores, poses);
+    hipLaunchKernelGGL(dcx_pnp_ransac_select_kernel, dim3((unsigned)batch), dim3(kLanes), 0, (hipStream_t)stream, d_counts, d_starts,
+                       d_rows, d_xy, pool, n_ids, rm1, square_len, cam, iterations, thr2, min_inliers, scores, poses, idx, d_status,
+                       d_pose, d_info, d_inliers);
+    return (int)hipGetLastError();
+}

@@ -1,6 +1,7 @@
 """Drop-in for /root/reference/src/inference.py: ``load_models`` (:73-84), ``infer_image`` (:32-70),
 ``solve_pnp`` (:15-29) with the reference's signatures, plus the batched ``infer_batch``; the OpenCV-free PnP solvers of
-``pnp.py`` (``solve_pnp_device`` and its batch / corner-pool forms) are re-exported here.
+``pnp.py`` (``solve_pnp_device`` and its batch / corner-pool forms, and their RANSAC counterparts ``solve_pnp_ransac_*``) are
+re-exported here.
 
 ``infer_image`` runs the library's sync-free batch pipeline with B = 1 (one H2D of the gray frame,
 one D2H of the packed corner list).  ``infer_image_staged`` follows the reference statement by
@@ -22,12 +23,14 @@ from .models._handles import require_cuda, unwrap
 from .models.model_utils import extract_patches, pre_bgr_image, pred_to_keypoints
 from .models.net import dcModel, lModel
 from .models.refinenet import RefineNet, lRefineNet
-from .pnp import solve_pnp_batch_device, solve_pnp_device, solve_pnp_host, solve_pnp_pool, unpack_poses
+from .pnp import (solve_pnp_batch_device, solve_pnp_device, solve_pnp_host, solve_pnp_pool, solve_pnp_ransac_batch_device,
+                  solve_pnp_ransac_device, solve_pnp_ransac_host, solve_pnp_ransac_pool, unpack_poses, unpack_ransac)
 
 __all__ = ["load_models", "infer_image", "infer_image_staged", "infer_batch", "infer_batch_device", "unpack_results", "packed_len",
            "solve_pnp", "solve_pnp_batch", "solve_pnp_submit", "set_deterministic", "InferenceModel", "calibrate_xcd",
            "set_xcd_weights", "get_xcd_weights", "solve_pnp_host", "solve_pnp_device", "solve_pnp_batch_device", "solve_pnp_pool",
-           "unpack_poses"]
+           "unpack_poses", "solve_pnp_ransac_host", "solve_pnp_ransac_device", "solve_pnp_ransac_batch_device",
+           "solve_pnp_ransac_pool", "unpack_ransac"]
 
 DEFAULT_KMAX = 64
 

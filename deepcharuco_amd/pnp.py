@@ -22,6 +22,11 @@ neither is bit-identical to OpenCV (its internal summation orders and its homogr
 Deviation from ``cv2.solvePnP``: input the reference never meets -- collinear points, a rank-deficient homography, a point
 behind the camera, a non-finite result -- is reported as ``ret = False`` (status DEGENERATE / NONFINITE) instead of a
 meaningless pose.  A step of the refinement that would put a point behind the camera counts as a rejected step.
+
+``solve_pnp_ransac_*`` put a consensus search in front of that solver (``cv2.solvePnPRansac``'s role: a corner with a wrong id
+sits a board square away from its label, and a least-squares pose has no defence).  ``solve_pnp_ransac_host_full`` is the
+definition and carries the steps; ``solve_pnp_ransac_pool`` / ``_batch_device`` / ``_device`` run them in csrc/dcx_pnp_ransac.hip.
+The discrete results (winner, mask) are equal on host and device wherever no row stands within rounding of the threshold.
 """
 from __future__ import annotations
 
@@ -33,16 +38,22 @@ import numpy as np
 
 # per-frame status (include/deepcharuco_amd.h)
 PNP_OK, PNP_TOO_FEW, PNP_TRUNCATED, PNP_BAD_ID, PNP_DEGENERATE, PNP_NONFINITE = range(6)
+PNP_NO_CONSENSUS = 6            # RANSAC: the best hypothesis has fewer than max(min_inliers, 4) inliers
 POSE_WORDS = 8                 # pose[b] = rvec(3), tvec(3), rms reprojection error (px), accepted LM steps
 
 LM_MAX_ITER = 20
 LM_EPS = float(np.finfo(np.float32).eps)
 UNDISTORT_ITERS = 5
 JACOBI_MAX_SWEEPS = 16
+RANSAC_MAX_ITERATIONS = 4096
+RANSAC_SAMPLE_TRIES = 8        # complete 4-samples drawn per hypothesis before it is given up
+RANSAC_MAX_DRAWS = 256         # single slot draws per hypothesis, redraws included
+_M32 = 0xFFFFFFFF
 
 __all__ = ["solve_pnp_host", "solve_pnp_host_full", "solve_pnp_device", "solve_pnp_batch_device", "solve_pnp_pool",
            "unpack_poses", "object_points", "PNP_OK", "PNP_TOO_FEW", "PNP_TRUNCATED", "PNP_BAD_ID", "PNP_DEGENERATE",
-           "PNP_NONFINITE"]
+           "PNP_NONFINITE", "PNP_NO_CONSENSUS", "solve_pnp_ransac_host", "solve_pnp_ransac_host_full", "solve_pnp_ransac_device",
+           "solve_pnp_ransac_batch_device", "solve_pnp_ransac_pool", "ransac_workspace_bytes", "unpack_ransac"]
 
 
 # ------------------------------------------------------------------------------------------------ arguments
@@ -266,12 +277,9 @@ def _homography(obj: np.ndarray, mn: np.ndarray) -> Tuple[int, Optional[np.ndarr
     return PNP_OK, H / H[2, 2], mc
 
 
-def _init_pose(obj: np.ndarray, mn: np.ndarray) -> Tuple[int, Optional[np.ndarray]]:
-    """Planar initialisation (board points obj, normalised image points mn) -> (status, p0)."""
-    st, H, mc = _homography(obj, mn)
-    if st != PNP_OK:
-        return st, None
-    # OpenCV's decomposition (cvFindExtrinsicCameraParams2, planar branch)
+def _pose_of_homography(H: np.ndarray, mc: np.ndarray) -> Tuple[int, Optional[np.ndarray]]:
+    """OpenCV's decomposition (cvFindExtrinsicCameraParams2, planar branch) of H (centred board points -> normalised image
+    points, h33 = 1), orthonormalised, with the board centroid mc composed back in -> (status, p0)."""
     h1, h2, h3 = H[:, 0], H[:, 1], H[:, 2]
     n1, n2 = math.sqrt(float(h1 @ h1)), math.sqrt(float(h2 @ h2))
     h1 = h1 * (1.0 / max(n1, 2.2e-16))
@@ -288,6 +296,14 @@ def _init_pose(obj: np.ndarray, mn: np.ndarray) -> Tuple[int, Optional[np.ndarra
     if not np.isfinite(p0).all():
         return PNP_NONFINITE, None
     return PNP_OK, p0
+
+
+def _init_pose(obj: np.ndarray, mn: np.ndarray) -> Tuple[int, Optional[np.ndarray]]:
+    """Planar initialisation (board points obj, normalised image points mn) -> (status, p0)."""
+    st, H, mc = _homography(obj, mn)
+    if st != PNP_OK:
+        return st, None
+    return _pose_of_homography(H, mc)
 
 
 def _cholesky_solve(A: np.ndarray, b: np.ndarray) -> Optional[np.ndarray]:
@@ -376,6 +392,173 @@ def solve_pnp_host(keypoints, col_count, row_count, square_len, camera_matrix, d
     (False, None, None) for fewer than 4 points or input the solver refuses (module docstring); IndexError for an id outside
     the board, ValueError for 12 / 14 distortion coefficients or a skewed camera matrix."""
     return _as_cv2(*solve_pnp_host_full(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs))
+
+
+# ------------------------------------------------------------------------------------------------ RANSAC: the definition
+
+def _mix32(x: int) -> int:
+    x &= _M32
+    x ^= x >> 16
+    x = (x * 0x7FEB352D) & _M32
+    x ^= x >> 15
+    x = (x * 0x846CA68B) & _M32
+    return x ^ (x >> 16)
+
+
+def _ransac_draw(seed: int, n: int, h: int, c: int) -> int:
+    """Draw ``c`` of hypothesis ``h`` of a frame with ``n`` rows -> a slot in [0, n).  32-bit integer arithmetic only; nothing
+    but (seed, n, h, c) enters, so a frame draws the same samples wherever it stands in a batch."""
+    r = _mix32((seed & _M32) ^ _mix32(n * 0x9E3779B9 + _mix32(h * 0x85EBCA6B + c)))
+    return (r * n) >> 32
+
+
+def _ransac_sample_ok(ids, rm1: int) -> bool:
+    """Four ids make a usable sample: all distinct and no three of their grid points (id % rm1, id // rm1) on a line."""
+    if len(set(ids)) < 4:
+        return False
+    g = [(i % rm1, i // rm1) for i in ids]
+    for a, b, c in ((1, 2, 3), (0, 2, 3), (0, 1, 3), (0, 1, 2)):
+        if (g[b][0] - g[a][0]) * (g[c][1] - g[a][1]) - (g[b][1] - g[a][1]) * (g[c][0] - g[a][0]) == 0:
+            return False
+    return True
+
+
+def _ransac_sample(seed: int, n: int, h: int, ids, rm1: int):
+    """The four slots of hypothesis ``h``, or None.  Slots are drawn one by one (a slot already held is redrawn); a complete
+    draw whose ids ``_ransac_sample_ok`` refuses is redrawn, 8 draws at most; the draw counter runs on through all of them and
+    stops the hypothesis at RANSAC_MAX_DRAWS."""
+    c = 0
+    for _ in range(RANSAC_SAMPLE_TRIES):
+        out = []
+        while len(out) < 4:
+            if c >= RANSAC_MAX_DRAWS:
+                return None
+            i = _ransac_draw(seed, n, h, c)
+            c += 1
+            if i not in out:
+                out.append(i)
+        if _ransac_sample_ok([int(ids[i]) for i in out], rm1):
+            return out
+    return None
+
+
+def _adjugate(m: np.ndarray) -> np.ndarray:
+    return np.array([[m[1, 1] * m[2, 2] - m[1, 2] * m[2, 1], m[0, 2] * m[2, 1] - m[0, 1] * m[2, 2], m[0, 1] * m[1, 2] - m[0, 2] * m[1, 1]],
+                     [m[1, 2] * m[2, 0] - m[1, 0] * m[2, 2], m[0, 0] * m[2, 2] - m[0, 2] * m[2, 0], m[0, 2] * m[1, 0] - m[0, 0] * m[1, 2]],
+                     [m[1, 0] * m[2, 1] - m[1, 1] * m[2, 0], m[0, 1] * m[2, 0] - m[0, 0] * m[2, 1], m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]]])
+
+
+def _projective_basis(p: np.ndarray) -> np.ndarray:
+    """3x3 matrix that sends e1, e2, e3, (1,1,1) to the four points p (4,2), each up to scale: columns l_j (x_j, y_j, 1) with
+    l = adj([p1 p2 p3]) p4."""
+    m = np.array([[p[0, 0], p[1, 0], p[2, 0]], [p[0, 1], p[1, 1], p[2, 1]], [1.0, 1.0, 1.0]])
+    lam = _adjugate(m) @ np.array([p[3, 0], p[3, 1], 1.0])
+    return m * lam
+
+
+def _homography4(obj: np.ndarray, mn: np.ndarray) -> Tuple[int, Optional[np.ndarray], np.ndarray]:
+    """``_homography`` for exactly four points: the homography through them in closed form (H = B adj(A), A and B the
+    projective bases of the centred board points and of the image points) in place of the 9x9 eigenproblem, which four
+    points determine exactly anyway.  The sampler has already refused collinear board points."""
+    mc = (obj[0, :2] + obj[1, :2] + obj[2, :2] + obj[3, :2]) / 4.0
+    H = _projective_basis(mn) @ _adjugate(_projective_basis(obj[:, :2] - mc))
+    if not abs(H[2, 2]) > 1e-12 * np.abs(H).max():
+        return PNP_DEGENERATE, None, mc
+    return PNP_OK, H / H[2, 2], mc
+
+
+def _row_errors2(obj: np.ndarray, img: np.ndarray, p: np.ndarray, K: np.ndarray, k: np.ndarray) -> np.ndarray:
+    """Squared reprojection error (px^2) of every row at pose p; inf for a row that is not in front of the camera."""
+    X = obj @ _rodrigues(p[:3]).T + p[3:]
+    e2 = np.full(obj.shape[0], math.inf)
+    front = X[:, 2] > 0
+    if front.any():
+        res, _, _ = _project(obj[front], img[front], p, K, k, False)
+        e2[front] = (res * res).sum(1)
+    return e2
+
+
+def _ransac_args(iterations, reproj_error, min_inliers):
+    if not 1 <= int(iterations) <= RANSAC_MAX_ITERATIONS:
+        raise ValueError(f"iterations must be in [1, {RANSAC_MAX_ITERATIONS}]")
+    if not (math.isfinite(float(reproj_error)) and float(reproj_error) > 0):
+        raise ValueError("reproj_error must be finite and positive")
+    return int(iterations), float(reproj_error), int(min_inliers)
+
+
+def solve_pnp_ransac_host_full(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations=100,
+                               reproj_error=8.0, min_inliers=4, seed=0, with_margin=False, pool_order=False):
+    """The definition of the RANSAC solver (``cv2.solvePnPRansac``'s defaults: 100 iterations, 8 px) ->
+    (status, pose[8], inliers bool[N] in the caller's row order, winning hypothesis or -1).
+
+    Rows are taken in the order the corner pool holds them, which is what the sampler's slots count: a keypoint list is laid
+    into a pool id-sorted (stable; ``_pack``), so that is the default; ``pool_order=True`` says the rows already stand as in the
+    pool (``infer_batch_device`` leaves a frame's corners in raster order) and takes them as they are.  Hypothesis h = the planar pose through four sampled rows
+    (``_ransac_sample``, ``_homography4``, ``_pose_of_homography``; no LM); its score = the rows whose reprojection error
+    through the full distortion model is <= reproj_error px (a row not in front of the camera is an outlier).  All ``iterations``
+    hypotheses are scored; the winner is the highest score, the lowest h among equals.  No valid hypothesis: DEGENERATE; fewer
+    than max(min_inliers, 4) inliers: NO_CONSENSUS; else the pose is ``_solve`` (init + LM) on the winner's inlier rows alone,
+    pose[6] their rms, and the mask is the winner's (not recomputed after the refit).  Without a pose the mask is all False.
+
+    ``with_margin``: a fifth value, the smallest |error - reproj_error| / reproj_error of any row under any hypothesis that
+    scores within one of the winner: how far the frame is from a decision rounding could flip (inf if there is no winner)."""
+    K, k = _camera(camera_matrix), _dist(dist_coeffs)
+    iterations, thr, min_inliers = _ransac_args(iterations, reproj_error, min_inliers)
+    kp = np.asarray(keypoints)
+    n = kp.shape[0] if kp.ndim == 2 else 0
+
+    def done(status, pose=None, mask=None, winner=-1, margin=math.inf):
+        out = (status, np.zeros(POSE_WORDS) if pose is None else pose, np.zeros(n, bool) if mask is None else mask, winner)
+        return out + (margin,) if with_margin else out
+
+    if kp.ndim != 2 or kp.shape[0] < 4:
+        return done(PNP_TOO_FEW)
+    order = np.arange(kp.shape[0]) if pool_order else np.argsort(kp[:, 2], kind="stable")
+    kp = kp[order]
+    ids = kp[:, 2].astype(np.int64)
+    obj32, img32 = object_points(ids, col_count, row_count, square_len), kp[:, :2].astype(np.float32)
+    obj, img = obj32.astype(np.float64), img32.astype(np.float64)
+    mn = _undistort(img, K, k)
+    best, winner, best_e2, records = -1, -1, None, []
+    for h in range(iterations):
+        s = _ransac_sample(seed, n, h, ids, row_count - 1)
+        if s is None:
+            continue
+        st, H, mc = _homography4(obj[s], mn[s])
+        if st == PNP_OK:
+            st, p0 = _pose_of_homography(H, mc)
+        if st != PNP_OK:
+            continue
+        e2 = _row_errors2(obj, img, p0, K, k)
+        score = int((e2 <= thr * thr).sum())
+        records.append((score, e2))
+        if score > best:
+            best, winner, best_e2 = score, h, e2
+    if winner < 0:
+        return done(PNP_DEGENERATE)
+    margin = min(float(np.abs(np.sqrt(e2[np.isfinite(e2)]) - thr).min()) / thr for sc, e2 in records
+                 if sc >= best - 1 and np.isfinite(e2).any())
+    if best < max(min_inliers, 4):
+        return done(PNP_NO_CONSENSUS, winner=winner, margin=margin)
+    m = best_e2 <= thr * thr
+    st, pose = _solve(obj32[m], img32[m], K, k)
+    if st != PNP_OK:
+        return done(st, winner=winner, margin=margin)
+    mask = np.empty(n, bool)
+    mask[order] = m
+    return done(st, pose, mask, winner, margin)
+
+
+def _as_cv2_ransac(status: int, pose: np.ndarray, inliers: np.ndarray):
+    return _as_cv2(status, pose) + (inliers,)
+
+
+def solve_pnp_ransac_host(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations=100,
+                          reproj_error=8.0, min_inliers=4, seed=0):
+    """``solve_pnp_host`` with consensus -> (ret, rvec (3,1), tvec (3,1), inliers bool[N]); (False, None, None, all False)
+    when no pose comes out.  Same exceptions as ``solve_pnp_host``, and ValueError for a refused iterations / reproj_error."""
+    return _as_cv2_ransac(*solve_pnp_ransac_host_full(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs,
+                                                      iterations, reproj_error, min_inliers, seed)[:3])
 
 
 # ------------------------------------------------------------------------------------------------ the device solver
@@ -482,3 +665,113 @@ def solve_pnp_device(keypoints, col_count, row_count, square_len, camera_matrix,
         _camera_args(camera_matrix, dist_coeffs)
         return False, None, None
     return solve_pnp_batch_device([kp], col_count, row_count, square_len, camera_matrix, dist_coeffs, device)[0]
+
+
+# ------------------------------------------------------------------------------------------------ RANSAC on the device
+
+def ransac_workspace_bytes(batch: int, pool: int, iterations: int = 100) -> int:
+    """Bytes of device workspace ``solve_pnp_ransac_pool`` needs (every hypothesis' pose and score, the inlier index list)."""
+    from . import _lib
+    n = int(_lib.lib().dcx_solve_pnp_ransac_workspace_bytes(int(batch), int(pool), int(iterations)))
+    if n == 0:
+        raise ValueError(f"batch >= 1, pool >= 0 and iterations in [1, {RANSAC_MAX_ITERATIONS}] are required")
+    return n
+
+
+def solve_pnp_ransac_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len, camera_matrix,
+                          dist_coeffs, iterations=100, reproj_error=8.0, min_inliers=4, seed=0, out=None, workspace=None):
+    """``solve_pnp_pool`` behind a consensus search (``solve_pnp_ransac_host_full`` is the definition): two kernel launches on the
+    current stream, no host sync, nothing allocated when ``out`` and ``workspace`` are given (capture-safe).  Returns device
+    tensors ``(status int32 [B], pose float64 [B, 8], info int32 [B, 2] = inlier count and winning hypothesis (-1: none),
+    inliers uint8 [pool] in slot order)``; ``out`` = that tuple, ``workspace`` = a contiguous device tensor of at least
+    ``ransac_workspace_bytes(batch, pool, iterations)`` bytes.  Slots of the mask that belong to no frame are not written."""
+    import torch
+    from . import _lib
+    dev = packed.device
+    iterations, reproj_error, min_inliers = _ransac_args(iterations, reproj_error, min_inliers)
+    if packed.dtype != torch.int32 or not packed.is_contiguous() or packed.numel() < 2 * batch + (6 if refined else 4) * pool:
+        raise ValueError("packed must be a contiguous int32 corner pool of at least packed_len(batch, pool) words")
+    need = ransac_workspace_bytes(batch, pool, iterations)
+    if workspace is None:
+        workspace = torch.empty(((need + 7) // 8,), dtype=torch.float64, device=dev)
+    if workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {dev}")
+    if out is None:
+        out = (torch.empty((batch,), dtype=torch.int32, device=dev),
+               torch.empty((batch, POSE_WORDS), dtype=torch.float64, device=dev),
+               torch.empty((batch, 2), dtype=torch.int32, device=dev),
+               torch.zeros((max(pool, 1),), dtype=torch.uint8, device=dev))
+    want = ((torch.int32, batch), (torch.float64, batch * POSE_WORDS), (torch.int32, 2 * batch), (torch.uint8, pool))
+    if len(out) != 4 or any(t.device != dev or t.dtype != dt or t.numel() < n or not t.is_contiguous() for t, (dt, n) in zip(out, want)):
+        raise ValueError(f"out must be (int32 [{batch}], float64 [{batch}, 8], int32 [{batch}, 2], uint8 [{pool}]) contiguous "
+                         f"tensors on {dev}")
+    st, pose, info, inl = out
+    cam, dist, n_dist = _camera_args(camera_matrix, dist_coeffs)
+    base = packed.data_ptr()
+    rows_p = base + 8 * batch
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().dcx_solve_pnp_ransac_pool(
+            base, base + 4 * batch, rows_p, rows_p + 16 * pool if refined else None, int(batch), int(pool), int(col_count),
+            int(row_count), float(square_len), cam, dist, n_dist, iterations, reproj_error, min_inliers, int(seed) & _M32,
+            workspace.data_ptr(), workspace.numel() * workspace.element_size(), st.data_ptr(), pose.data_ptr(), info.data_ptr(),
+            inl.data_ptr(), _lib.current_stream()), "dcx_solve_pnp_ransac_pool")
+    return st, pose, info, inl
+
+
+def unpack_ransac(status, pose, inliers, counts, starts, ids=None) -> List[tuple]:
+    """Host copies of ``solve_pnp_ransac_pool``'s outputs and of the pool's counts / starts -> per-frame
+    ``(ret, rvec (3,1), tvec (3,1), inliers bool[counts[b]])``; the mask is all False without a pose.  The masks are in the
+    pool's slot order, or, with ``ids`` (the pool's id column, ``rows[:, 2]``), in ``unpack_results``' row order (stable by id)."""
+    status, inliers = np.asarray(status), np.asarray(inliers)
+    pose = np.asarray(pose, dtype=np.float64).reshape(-1, POSE_WORDS)
+    out = []
+    for b, s in enumerate(status.tolist()):
+        n, s0 = int(counts[b]), int(starts[b])
+        mask = inliers[s0:s0 + n].astype(bool) if s == PNP_OK else np.zeros(max(n, 0), bool)
+        if ids is not None and s == PNP_OK:
+            mask = mask[np.argsort(np.asarray(ids[s0:s0 + n]), kind="stable")]
+        out.append(_as_cv2_ransac(int(s), pose[b], mask))
+    return out
+
+
+def solve_pnp_ransac_batch_device(keypoints_list, col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations=100,
+                                  reproj_error=8.0, min_inliers=4, seed=0, device="cuda", full=False):
+    """``solve_pnp_ransac_host`` of every frame of a list of keypoint arrays on the GPU -> list of
+    ``(ret, rvec, tvec, inliers)``, ``inliers`` a bool array in the caller's row order.  ``full=True``: list of
+    ``(status, pose[8], inliers, winner)`` like ``solve_pnp_ransac_host_full``.  IndexError if any frame with >= 4 points carries
+    an id outside the board."""
+    import torch
+    from .models._handles import require_cuda
+    dev = require_cuda(device)
+    _camera_args(camera_matrix, dist_coeffs)                  # ValueError before anything is uploaded
+    _ransac_args(iterations, reproj_error, min_inliers)
+    if len(keypoints_list) == 0:
+        return []
+    packed, b, pool = _pack(keypoints_list, dev)
+    with torch.cuda.device(dev):
+        st, pose, info, inl = solve_pnp_ransac_pool(packed, b, pool, True, col_count, row_count, square_len, camera_matrix,
+                                                    dist_coeffs, iterations, reproj_error, min_inliers, seed)
+        st, pose, info, inl, head = (t.cpu().numpy() for t in (st, pose, info, inl, packed[:2 * b]))
+    if (st == PNP_BAD_ID).any():
+        n = (col_count - 1) * (row_count - 1)
+        raise IndexError(f"corner id outside [0, {n}) for a {col_count}x{row_count} board")
+    out = []
+    for i, (ret, rvec, tvec, mask) in enumerate(unpack_ransac(st, pose, inl, head[:b], head[b:])):
+        kp = np.asarray(keypoints_list[i])
+        if mask.size:                                         # undo _pack's stable id sort
+            mask = mask[np.argsort(np.argsort(kp.reshape(-1, 3)[:, 2], kind="stable"), kind="stable")]
+        out.append((int(st[i]), pose[i].copy(), mask, int(info[i, 1])) if full else (ret, rvec, tvec, mask))
+    return out
+
+
+def solve_pnp_ransac_device(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations=100,
+                            reproj_error=8.0, min_inliers=4, seed=0, device="cuda"):
+    """``cv2.solvePnPRansac``'s role on the GPU, without OpenCV -> ``(ret, rvec, tvec, inliers bool[N])``;
+    ``(False, None, None, all False)`` for fewer than 4 points, a refused input or no consensus."""
+    kp = np.asarray(keypoints)
+    if kp.ndim != 2 or kp.shape[0] < 4:
+        _camera_args(camera_matrix, dist_coeffs)
+        _ransac_args(iterations, reproj_error, min_inliers)
+        return False, None, None, np.zeros(kp.shape[0] if kp.ndim == 2 else 0, bool)
+    return solve_pnp_ransac_batch_device([kp], col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations,
+                                         reproj_error, min_inliers, seed, device)[0]

@@ -10,7 +10,9 @@ camera_matrix=, dist_coeffs=)`` the pipeline gets the reference callers' last st
 when a batch is retired its frames' ``solve_pnp`` calls are submitted to host threads and run while the GPU works on
 the next batches; ``run`` then yields ``(ticket, results, poses)``.  ``pnp_device=True`` solves the poses on the GPU instead
 (``pnp.solve_pnp_pool``, no OpenCV): the kernel reads the batch's corner pool on the compute stream right after the pipeline and
-the poses come back through pinned memory with the corners.
+the poses come back through pinned memory with the corners.  ``pnp_ransac=dict(iterations=, reproj_error=, min_inliers=, seed=)``
+puts the consensus search of ``pnp.solve_pnp_ransac_pool`` in that kernel's place; a frame's pose is then
+``(ret, rvec, tvec, inliers)``.
 """
 from __future__ import annotations
 
@@ -23,19 +25,23 @@ import torch
 
 from .inference import DEFAULT_KMAX, infer_batch, infer_batch_device, packed_len, solve_pnp_submit, unpack_results
 from .models._handles import unwrap
-from .pnp import POSE_WORDS, solve_pnp_batch_device, solve_pnp_pool, unpack_poses
+from .pnp import (POSE_WORDS, ransac_workspace_bytes, solve_pnp_batch_device, solve_pnp_pool, solve_pnp_ransac_batch_device,
+                  solve_pnp_ransac_pool, unpack_poses, unpack_ransac)
 
 
 class FrameStream:
     def __init__(self, dust_bin_ids: int, deepc, refinenet=None, batch: int = 32, height: int = 240,
                  width: int = 320, kmax: int = DEFAULT_KMAX, depth: int = 2, pnp: Optional[dict] = None,
-                 compute_streams: int = 1, bgr: bool = False, h2d_on_compute: Optional[bool] = None, pnp_device: bool = False):
+                 compute_streams: int = 1, bgr: bool = False, h2d_on_compute: Optional[bool] = None, pnp_device: bool = False,
+                 pnp_ransac: Optional[dict] = None):
         """``bgr=True``: the stream is fed (n,H,W,3) BGR frames, as the reference's callers hold them (pose_estimation.py:53-59);
         the colour conversion of inference.py:40 happens on the device inside the first layer's load.  ``kmax``: the AVERAGE
         number of corners per frame the buffers are sized for -- the corner pool of a batch holds ``batch * kmax`` corners and a
         single frame may use any share of it.  ``pnp_device=True`` (with ``pnp``): the poses are solved on the GPU
         (``solve_pnp_pool`` enqueued behind the pipeline on the same stream, into a per-slot buffer copied to pinned memory before
-        the batch's completion event) and handed out resolved, without OpenCV; the default keeps the host-thread stage."""
+        the batch's completion event) and handed out resolved, without OpenCV; the default keeps the host-thread stage.
+        ``pnp_ransac`` (a dict of ``solve_pnp_ransac_pool``'s keyword arguments, possibly empty; needs ``pnp_device=True``): the
+        device stage is the RANSAC solver, with a workspace and a mask buffer per slot allocated here."""
         det = unwrap(deepc)
         self.dev = det.device
         self.dust_bin_ids, self.deepc, self.refinenet = dust_bin_ids, deepc, refinenet
@@ -47,6 +53,9 @@ class FrameStream:
         self.h2d_on_compute = compute_streams > 1 if h2d_on_compute is None else bool(h2d_on_compute)
         self.pnp = pnp
         self.pnp_device = bool(pnp_device) and pnp is not None
+        if pnp_ransac is not None and not self.pnp_device:
+            raise ValueError("pnp_ransac needs pnp=... and pnp_device=True")
+        self.pnp_ransac = None if pnp_ransac is None else dict(pnp_ransac)
         if not (1 <= compute_streams <= depth):
             raise ValueError("compute_streams must be between 1 and depth")
         n_out = packed_len(batch, self.pool)
@@ -71,6 +80,13 @@ class FrameStream:
                                  torch.empty((batch, POSE_WORDS), dtype=torch.float64, device=self.dev)) for _ in range(depth)]
                 self.pin_pnp = [(torch.empty((batch,), dtype=torch.int32).pin_memory(),
                                  torch.empty((batch, POSE_WORDS), dtype=torch.float64).pin_memory()) for _ in range(depth)]
+            if self.pnp_ransac is not None:      # info and mask join the slot's outputs; one workspace per slot
+                ws = ransac_workspace_bytes(batch, self.pool, self.pnp_ransac.get("iterations", 100))
+                self.dev_pnp = [o + (torch.empty((batch, 2), dtype=torch.int32, device=self.dev),
+                                     torch.zeros((self.pool,), dtype=torch.uint8, device=self.dev)) for o in self.dev_pnp]
+                self.pin_pnp = [o + (torch.empty((batch, 2), dtype=torch.int32).pin_memory(),
+                                     torch.zeros((self.pool,), dtype=torch.uint8).pin_memory()) for o in self.pin_pnp]
+                self.ws_pnp = [torch.empty(((ws + 7) // 8,), dtype=torch.float64, device=self.dev) for _ in range(depth)]
         self._pending: List[Optional[Tuple[int, int, np.ndarray]]] = [None] * depth   # (ticket, n_frames, host frames)
         self._ticket = 0
 
@@ -84,8 +100,16 @@ class FrameStream:
         if need > self.pool:         # rare: the batch fired more cells than its pool holds -> exact re-run with the pool it asked for
             warnings.warn(f"a batch produced {need} corners > pool={self.pool} (batch x kmax); re-running it with pool={need}")
             res = infer_batch(frames, self.dust_bin_ids, self.deepc, self.refinenet, pool=need)
+            if self.pnp_ransac is not None:   # (its hypotheses sample the id-sorted rows, not the pool's raster order)
+                return ticket, res, solve_pnp_ransac_batch_device(res, device=self.dev, **self.pnp, **self.pnp_ransac)
             if self.pnp_device:      # the device poses of this slot were solved on the truncated pool
                 return ticket, res, solve_pnp_batch_device(res, device=self.dev, **self.pnp)
+        if self.pnp_ransac is not None:
+            st, pose, _, mask = self.pin_pnp[slot]
+            head = self.pin_out[slot].numpy()        # the masks follow res: unpack_results' id-sorted rows
+            ids = head[2 * self.batch:2 * self.batch + 4 * self.pool].reshape(self.pool, 4)[:, 2]
+            return ticket, res, unpack_ransac(st.numpy()[:n], pose.numpy()[:n], mask.numpy(), head[:self.batch],
+                                              head[self.batch:2 * self.batch], ids)
         if self.pnp_device:
             st, pose = self.pin_pnp[slot]
             return ticket, res, unpack_poses(st.numpy()[:n], pose.numpy()[:n])
@@ -122,7 +146,10 @@ class FrameStream:
                 infer_batch_device(self.dev_in[slot], self.dust_bin_ids, self.deepc, self.refinenet, out=self.dev_out[slot],
                                    pool=self.pool)
                 self.ev_free[slot].record(compute)
-                if self.pnp_device:
+                if self.pnp_ransac is not None:
+                    solve_pnp_ransac_pool(self.dev_out[slot], self.batch, self.pool, self.refinenet is not None,
+                                          out=self.dev_pnp[slot], workspace=self.ws_pnp[slot], **self.pnp, **self.pnp_ransac)
+                elif self.pnp_device:
                     solve_pnp_pool(self.dev_out[slot], self.batch, self.pool, self.refinenet is not None, out=self.dev_pnp[slot],
                                    **self.pnp)
                 self.pin_out[slot].copy_(self.dev_out[slot], non_blocking=True)

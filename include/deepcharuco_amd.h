@@ -210,6 +210,34 @@ int dcx_solve_pnp_pool(const int32_t* d_counts, const int32_t* d_starts, const i
                        int32_t* d_status, double* d_pose /* [B][8] = rvec3, tvec3, rms_px, iterations */,
                        void* stream);
 
+/* ---- the same solver behind a consensus search (cv2.solvePnPRansac's role): poses that survive mislabelled corners ---------
+ * Pool, object points, image points, camera arguments and the per-frame checks (TOO_FEW, TRUNCATED, BAD_ID) as for
+ * dcx_solve_pnp_pool; the frames' slot ranges must not overlap (each frame's inlier list lives at its own slots of the workspace).
+ * Per frame, `iterations` hypotheses (1..4096), all of them evaluated (no confidence-based early exit: the work is fixed):
+ * hypothesis h draws four rows (slots of the frame as the pool holds them, whatever their order) by a 32-bit counter hash of
+ * (seed, counts[b], h, draw) -- not of b, so a frame gives the same
+ * result wherever it stands in a batch -- with distinct ids and no three board points on a line (8 draws at most), takes the
+ * planar pose through them (closed-form homography, OpenCV's decomposition, no LM) and scores the rows whose reprojection error
+ * through the full distortion model is <= reproj_error px (finite, > 0); a row behind the camera is an outlier.  The winner is the
+ * highest score, the lowest h among equals.  No hypothesis: DCX_PNP_DEGENERATE.  Fewer than max(min_inliers, 4) inliers:
+ * DCX_PNP_NO_CONSENSUS.  Else d_pose[b] is dcx_solve_pnp_pool's solve over the winner's inlier rows alone (rms over them) and its
+ * status the frame's.  deepcharuco_amd/pnp.py restates the steps (solve_pnp_ransac_host_full).
+ * d_info int32 [B][2]: inlier count (the population of the frame's mask), winning hypothesis (-1: none).  d_inliers uint8 [pool]
+ * (may be NULL): 1 at the winner's inlier slots (not recomputed after the refit, as in cv2); 0 at every slot of a frame that ends
+ * without a pose; slots of no frame are not written.  d_workspace: dcx_solve_pnp_ransac_workspace_bytes(batch, pool, iterations)
+ * bytes, 8-byte aligned (DCX_E_ARG if smaller).  Two launches on `stream`; no allocation, no synchronisation, no atomics: two
+ * calls give the same bits and the call can be captured in a hipGraph.                                                       */
+#define DCX_PNP_NO_CONSENSUS 6
+size_t dcx_solve_pnp_ransac_workspace_bytes(int batch, int pool, int iterations);   /* 0 for refused arguments */
+int dcx_solve_pnp_ransac_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows,
+                              const float* d_xy /* NULL = use integer rows x,y */, int batch, int pool,
+                              int col_count, int row_count, double square_len,
+                              const double* h_camera9, const double* h_dist, int n_dist,
+                              int iterations, double reproj_error, int min_inliers, unsigned seed,
+                              void* d_workspace, size_t workspace_bytes,
+                              int32_t* d_status, double* d_pose /* [B][8] */, int32_t* d_info /* [B][2] */,
+                              uint8_t* d_inliers /* [pool], may be NULL */, void* stream);
+
 /* ---- camera calibration from the views of a ChArUco board in a pool (cv2.calibrateCamera with default flags, planar target) --
  * The camera model solve_pnp needs (calib_intrinsics.py:44, cv2.calibrateCamera) from the corners of
  * `batch` views, read in place from a corner pool laid out as for dcx_solve_pnp_pool (same object points, same image points, same
