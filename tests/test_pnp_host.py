@@ -172,6 +172,8 @@ def test_integer_keypoints():
 
 
 def test_matches_cv2_where_available():
+    """Where cv2 is absent, tests/test_pose_exact_host.py stands in: it holds the same solver to an exact restatement of the
+    camera model cv2 documents."""
     cv2 = pytest.importorskip("cv2")
     rng = np.random.default_rng(11)
     for sigma in (0.0, 0.3):
