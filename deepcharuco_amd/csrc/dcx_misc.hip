@@ -329,15 +329,25 @@ __device__ __forceinline__ float dcx_logit(const DcxLogitView& v, int b, int c, 
     return v.p[(size_t)b * v.sb + (size_t)(c >> 2) * v.sq + (size_t)cell * v.sp + (size_t)(c & 3) * v.sc];
 }
 
-// per-cell 65-/17-way arg-max (model_utils.py:53-66: first maximum wins) with the dust-bin substitution
+// torch.argmax / torch.max order (what pred_argmax and speedy_bargmax2d call): NaN is the maximum and the first NaN wins, else the
+// first largest value.  v replaces best when it is larger, or when it is NaN and best is not; nothing replaces a NaN best.
+__device__ __forceinline__ bool dcx_argmax_takes(float v, float best) { return v > best || (v != v && best == best); }
+// the same order with an index for merges of partial results: of two equals (or two NaNs) the lower index wins
+__device__ __forceinline__ bool dcx_argmax_takes(float v, int i, float best, int besti) {
+    const bool vn = v != v, bn = best != best;
+    if (vn || bn) return vn && (!bn || i < besti);
+    return v > best || (v == best && i < besti);
+}
+
+// per-cell 65-/17-way arg-max (model_utils.py:53-66: first maximum wins, NaN counts as the maximum) with the dust-bin substitution
 template <bool C4>
 __device__ __forceinline__ void dcx_cell_argmax(const DcxLogitView& loc, const DcxLogitView& ids, int n_loc, int n_ids1,
                                                 int cells, int dust_bin, int b, int cell, int& la, int& ia) {
     la = 0; ia = 0;
     if (C4) {
         // C4 logits [b][quad][cell][4]: one 16-B load per channel quad, lanes on consecutive cells.
-        // Channels are visited in increasing order with a strict '>' so the first maximum wins
-        // (torch.argmax); the zero-filled pad channels of the last quad are never looked at.
+        // Channels are visited in increasing order and an equal value never replaces the best, so the first
+        // maximum wins (torch.argmax); the zero-filled pad channels of the last quad are never looked at.
         const float4* lq = reinterpret_cast<const float4*>(loc.p) + (size_t)b * (loc.sb >> 2) + cell;
         const float4* iq = reinterpret_cast<const float4*>(ids.p) + (size_t)b * (ids.sb >> 2) + cell;
         float best = -INFINITY;
@@ -346,7 +356,7 @@ __device__ __forceinline__ void dcx_cell_argmax(const DcxLogitView& loc, const D
             const float e[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if (4 * q + k < n_loc && (e[k] > best || (q == 0 && k == 0))) { best = e[k]; la = 4 * q + k; }
+                if (4 * q + k < n_loc && (dcx_argmax_takes(e[k], best) || (q == 0 && k == 0))) { best = e[k]; la = 4 * q + k; }
         }
         best = -INFINITY;
         for (int q = 0; 4 * q < n_ids1; ++q) {
@@ -354,18 +364,18 @@ __device__ __forceinline__ void dcx_cell_argmax(const DcxLogitView& loc, const D
             const float e[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                if (4 * q + k < n_ids1 && (e[k] > best || (q == 0 && k == 0))) { best = e[k]; ia = 4 * q + k; }
+                if (4 * q + k < n_ids1 && (dcx_argmax_takes(e[k], best) || (q == 0 && k == 0))) { best = e[k]; ia = 4 * q + k; }
         }
     } else {
         float best = dcx_logit(loc, b, 0, cell);
         for (int c = 1; c < n_loc; ++c) {            // torch.argmax: first maximum wins
             const float v = dcx_logit(loc, b, c, cell);
-            if (v > best) { best = v; la = c; }
+            if (dcx_argmax_takes(v, best)) { best = v; la = c; }
         }
         best = dcx_logit(ids, b, 0, cell);
         for (int c = 1; c < n_ids1; ++c) {
             const float v = dcx_logit(ids, b, c, cell);
-            if (v > best) { best = v; ia = c; }
+            if (dcx_argmax_takes(v, best)) { best = v; ia = c; }
         }
     }
     if (la == n_loc - 1) ia = dust_bin;          // where(loc_argmax == 64, dust_bin, ids_argmax)
@@ -399,8 +409,8 @@ __device__ __forceinline__ void dcx_compact_chunk(bool fire, int la, int ia, int
     __syncthreads();
 }
 
-// single-kernel decode: one workgroup per frame (used when the caller has no scratch buffer)
-template <bool C4>
+// single-kernel decode: one workgroup per frame (used when the caller has no scratch buffer: dcx_pred_to_keypoints, whose
+// NCHW logits go through the strided view)
 __global__ __launch_bounds__(256) void dcx_decode_kernel(DcxLogitView loc, DcxLogitView ids, int n_loc, int n_ids1,
                                                            int hc, int wc, int dust_bin, int kmax,
                                                            int32_t* __restrict__ counts, int32_t* __restrict__ rows,
@@ -418,7 +428,7 @@ __global__ __launch_bounds__(256) void dcx_decode_kernel(DcxLogitView loc, DcxLo
         bool fire = false;
         int la = 0, ia = 0;
         if (cell < cells) {
-            dcx_cell_argmax<C4>(loc, ids, n_loc, n_ids1, cells, dust_bin, b, cell, la, ia);
+            dcx_cell_argmax<false>(loc, ids, n_loc, n_ids1, cells, dust_bin, b, cell, la, ia);
             fire = ia != dust_bin;
             if (loc_argmax) loc_argmax[(size_t)b * cells + cell] = la;
             if (ids_argmax) ids_argmax[(size_t)b * cells + cell] = ia;
@@ -493,12 +503,9 @@ int dcx_launch_decode(DcxLogitView loc, DcxLogitView ids, int batch, int n_loc, 
                            counts, rows);
         return (int)hipGetLastError();
     }
-    if (c4)
-        hipLaunchKernelGGL(dcx_decode_kernel<true>, dim3((unsigned)batch), dim3(256), 0, s, loc, ids, n_loc, n_ids1, hc, wc,
-                           dust_bin, kmax, counts, rows, loc_argmax, ids_argmax);
-    else
-        hipLaunchKernelGGL(dcx_decode_kernel<false>, dim3((unsigned)batch), dim3(256), 0, s, loc, ids, n_loc, n_ids1, hc, wc,
-                           dust_bin, kmax, counts, rows, loc_argmax, ids_argmax);
+    // no scratch: the strided view reads any layout
+    hipLaunchKernelGGL(dcx_decode_kernel, dim3((unsigned)batch), dim3(256), 0, s, loc, ids, n_loc, n_ids1, hc, wc,
+                       dust_bin, kmax, counts, rows, loc_argmax, ids_argmax);
     return (int)hipGetLastError();
 }
 
@@ -694,18 +701,18 @@ __global__ __launch_bounds__(256) void dcx_argmax2d_kernel(const float* __restri
     int besti = 0x7fffffff;
     for (int i = tid; i < hw; i += 256) {
         const float v = p[i];
-        if (v > best) { best = v; besti = i; }   // i increases per thread: first max kept
+        if (dcx_argmax_takes(v, i, best, besti)) { best = v; besti = i; }   // i increases per thread: first max (or first NaN) kept
     }
     for (int off = 32; off >= 1; off >>= 1) {
         const float ov = __shfl_xor(best, off);
         const int oi = __shfl_xor(besti, off);
-        if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+        if (dcx_argmax_takes(ov, oi, best, besti)) { best = ov; besti = oi; }
     }
     if (lane == 0) { sv[wave] = best; si[wave] = besti; }
     __syncthreads();
     if (tid == 0) {
         for (int wv = 1; wv < 4; ++wv)
-            if (sv[wv] > best || (sv[wv] == best && si[wv] < besti)) { best = sv[wv]; besti = si[wv]; }
+            if (dcx_argmax_takes(sv[wv], si[wv], best, besti)) { best = sv[wv]; besti = si[wv]; }
         if (besti == 0x7fffffff) besti = 0;
         out[2 * k] = besti % w;
         out[2 * k + 1] = besti / w;

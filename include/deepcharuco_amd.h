@@ -98,6 +98,12 @@ int dcx_detector_forward(const dcx_detector* det,
  * dust_bin is the reference's `dust_bin_ids` argument: any value in [0, 255] (else DCX_E_NIDS) with the reference's
  * semantics `ids != dust_bin_ids` -- it normally equals n_ids but is not required to.
  * Optional dense maps d_loc_argmax / d_ids_argmax: int32 [B][Hc][Wc] (ids map is post-mask).
+ * Truncation: d_counts[b] is never capped; d_rows[b][k] is written for k < min(d_counts[b], kmax) and left untouched beyond
+ * (a frame that fires nothing writes no row); kmax <= 0 is DCX_E_SHAPE.
+ * Non-finite logits: the arg-max follows torch.argmax -- NaN counts as the maximum and the first NaN wins, else the first
+ * largest value (+inf and -inf order like any number; all -inf gives class 0).  That holds for the three entries below, which
+ * take or re-read logits a caller can see.  The fused pipeline (dcx_infer_batch) never stores its logits and only non-finite
+ * WEIGHTS could make them non-finite: its arg-max on such logits is unspecified.
  * dcx_detector_decode reads the logits the preceding dcx_detector_forward left in d_ws and
  * uses 4 bytes per cell of scratch in it (arg-max of all cells in parallel, then one ordered
  * compaction per frame); dcx_pred_to_keypoints takes caller NCHW logits (the reference's own
@@ -121,14 +127,20 @@ int dcx_label_to_keypoints(const long long* d_loc, const long long* d_ids, int b
 /* ---- patch table: compacts the per-frame rows of a batch into one patch list ----------
  * d_table int32 [B*kmax][4] = {frame, x, y, slot = frame*kmax + k}; d_total int32 [1] =
  * sum_b min(counts[b], kmax).  Device-side replacement for the host syncs at
- * model_utils.py:114 / inference.py:51.                                                  */
+ * model_utils.py:114 / inference.py:51.  Frames in order, each frame's rows in order, no gaps: frame b's entries start at
+ * sum_{a<b} min(counts[a], kmax); counts above kmax are capped (the rows beyond were never stored), frames at 0 take no entry.
+ * Entries at and beyond *d_total are left untouched.  Any batch >= 1 (one workgroup walks the frames 256 at a time).        */
 int dcx_build_patch_table(const int32_t* d_counts, const int32_t* d_rows, int batch, int kmax,
                           int32_t* d_table, int32_t* d_total, void* stream);
 
 /* ---- extract_patches models/model_utils.py:19-36 ---------------------------------------
  * patch[p][i][j] = img[y-12+i][x-12+j], 0.0f outside the image (zero pad of the NORMALISED
- * image).  d_table rows {frame,x,y,slot}; patches beyond *d_total (if non-null) are skipped.
- * u8 variant normalises on the fly; f32 variant takes dense normalised images [B][H][W].   */
+ * image).  d_table rows {frame,x,y,slot}; patches beyond *d_total (if non-null) are skipped:
+ * d_patches[p] is left untouched for p >= *d_total.  With d_total == NULL all max_patches table rows are read.
+ * u8 variant normalises on the fly ((float(g) - 128) / 255, as dcx_pre_image); frames are windows of a caller buffer: frame f's
+ * pixel (y, x) is the byte d_frames[f*frame_stride + y*pitch + x], bytes outside a window are never read.
+ * f32 variant takes dense normalised images [B][H][W].  Any height, width >= 1 (a frame may be smaller than a patch).
+ * The table is trusted: frame indices must lie inside the frames passed, *d_total <= max_patches.                      */
 int dcx_extract_patches_u8(const uint8_t* d_frames, long frame_stride, int pitch, int height, int width,
                            const int32_t* d_table, const int32_t* d_total, int max_patches,
                            float* d_patches, void* stream);
@@ -140,14 +152,17 @@ int dcx_extract_patches_f32(const float* d_images, int height, int width,
  * d_patches f32 [P][24][24] -> per patch flat argmax (first max) of the 64x64 heat-map:
  * d_corners int32 [P][2] = {col,row}; if d_table/d_xy given, d_xy[slot] = {(col-32)/8 + x,
  * (row-32)/8 + y} (float32, refinenet.py:114).  d_heat (nullable) f32 [P][64][64] receives
- * the raw heat-map.  Patches >= *d_total (if non-null) are skipped.                       */
+ * the raw heat-map.  Patches >= *d_total (if non-null) are skipped: their d_corners / d_heat entries and every d_xy slot no
+ * live table row names are left untouched.  The slots are the table's (frame*kmax + k from dcx_build_patch_table), so d_xy
+ * must hold the largest slot + 1 pairs; *d_total <= max_patches is trusted.  Skipped patches are skipped in every layer: the
+ * call writes at most dcx_refiner_workspace_bytes(rf, *d_total) bytes of d_ws (none when *d_total is 0).                  */
 int dcx_refiner_forward(const dcx_refiner* rf, const float* d_patches, int max_patches,
                         const int32_t* d_total, const int32_t* d_table,
                         void* d_ws, size_t ws_bytes,
                         int32_t* d_corners, float* d_xy, float* d_heat, void* stream);
 
 /* ---- speedy_bargmax2d models/model_utils.py:39-43 --------------------------------------
- * d_x f32 [K][h][w] -> d_out int32 [K][2] = {col,row} of the first maximum.               */
+ * d_x f32 [K][h][w] -> d_out int32 [K][2] = {col,row} of the first maximum (torch.max: a NaN is the maximum, the first one wins). */
 int dcx_argmax2d(const float* d_x, int k, int h, int w, int32_t* d_out, void* stream);
 
 /* ---- whole path for a batch: infer_image inference.py:32-70 without host syncs ----------
