@@ -287,7 +287,7 @@ extern "C" const char* dcx_error_string(int code) {
         case DCX_E_ARG: return "DCX_E_ARG: null pointer or bad scalar argument";
         case DCX_E_SHAPE: return "DCX_E_SHAPE: unsupported shape (H/W below 8, patches not 24x24, batch x kmax too large, ...)";
         case DCX_E_WS: return "DCX_E_WS: workspace too small";
-        case DCX_E_NIDS: return "DCX_E_NIDS: n_ids outside [1, 62] or dust_bin outside [0, 255]";
+        case DCX_E_NIDS: return "DCX_E_NIDS: n_ids outside [1, 63] or dust_bin outside [0, 255]";
         default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown dcx error";
     }
 }
@@ -295,7 +295,7 @@ extern "C" const char* dcx_error_string(int code) {
 // ---- detector ---------------------------------------------------------------------------------
 extern "C" int dcx_detector_create(dcx_detector** out, const float* const* t, int n_tensors, int n_ids) {
     if (!out || !t) return DCX_E_ARG;
-    if (n_ids < 1 || n_ids > 62) return DCX_E_NIDS;
+    if (n_ids < 1 || n_ids > 63) return DCX_E_NIDS;   // n_ids + 1 rows: at most the two 32-row ids tiles of the fused tail
     if (n_tensors != 64) return DCX_E_ARG;   // 10 conv+BN (6 tensors) + 2 raw convs (2 tensors)
     for (int i = 0; i < n_tensors; ++i)
         if (!t[i]) return DCX_E_ARG;

@@ -32,7 +32,7 @@ extern "C" {
 #define DCX_E_ARG      (-1)   /* null pointer / bad scalar */
 #define DCX_E_SHAPE    (-2)   /* H or W below 8, patch not 24x24, capacity overflow ... */
 #define DCX_E_WS       (-3)   /* workspace too small */
-#define DCX_E_NIDS     (-4)   /* n_ids outside [1, 62] at create(); dust_bin outside [0, 255] at decode */
+#define DCX_E_NIDS     (-4)   /* n_ids outside [1, 63] at create(); dust_bin outside [0, 255] at decode */
 
 typedef struct dcx_detector dcx_detector;   /* dcModel  (models/net.py:9-99)        */
 typedef struct dcx_refiner  dcx_refiner;    /* RefineNet (models/refinenet.py:9-115) */
