@@ -25,6 +25,12 @@ calibrates from; this module restates the solve for a planar (z = 0) target and 
 Deviations from ``cv2.calibrateCamera``: the homographies of the init are not refined by LM; each LM step is solved by Cholesky
 of the reduced system instead of an SVD of the dense one; unusable views are reported instead of raising (``calibrate_camera_host``
 raises like cv2).
+
+``calibrate_camera_ransac_*`` / ``calibrate_charuco_ransac_*`` put a consensus search in front of that solve and a re-check behind
+it: a corner with a wrong id sits a board square away from its label, the joint least squares has no defence, and every pose
+computed later inherits the wrong model.  ``calibrate_camera_ransac_host_full`` is the definition and carries the steps;
+``calibrate_charuco_ransac_pool`` / ``_device`` run them in csrc/dcx_calib_ransac.hip.  The discrete results (winners, masks,
+number of solves) are equal on host and device wherever no row stands within rounding of a threshold.
 """
 from __future__ import annotations
 
@@ -35,7 +41,8 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import pnp
-from .pnp import (PNP_BAD_ID, PNP_NONFINITE, PNP_OK, PNP_TOO_FEW, _cholesky_solve, _homography, _project, _rodrigues, _solve)
+from .pnp import (PNP_BAD_ID, PNP_DEGENERATE, PNP_NO_CONSENSUS, PNP_NONFINITE, PNP_OK, PNP_TOO_FEW, _cholesky_solve, _homography,
+                  _project, _rodrigues, _solve)
 
 # overall status (include/deepcharuco_amd.h); per-view statuses are pnp's PNP_*
 CALIB_OK, CALIB_NO_VIEWS, CALIB_DEGENERATE, CALIB_NONFINITE = range(4)
@@ -44,8 +51,12 @@ CALIB_EPS = float(np.finfo(np.float64).eps)
 N_INTR = 9                     # fx, fy, cx, cy, k1, k2, p1, p2, k3
 RESULT_WORDS = 16              # h_result of dcx_calibrate_pool
 
+RANSAC_MAX_ROUNDS = 8          # re-mask rounds of the robust calibration
+
 __all__ = ["CalibResult", "calibrate_camera_host", "calibrate_camera_host_full", "calibrate_charuco_pool",
-           "calibrate_charuco_device", "CALIB_OK", "CALIB_NO_VIEWS", "CALIB_DEGENERATE", "CALIB_NONFINITE"]
+           "calibrate_charuco_device", "CALIB_OK", "CALIB_NO_VIEWS", "CALIB_DEGENERATE", "CALIB_NONFINITE",
+           "RobustCalibResult", "calibrate_camera_ransac_host", "calibrate_camera_ransac_host_full",
+           "calibrate_charuco_ransac_pool", "calibrate_charuco_ransac_device", "ransac_workspace_bytes"]
 
 
 class CalibResult(NamedTuple):
@@ -332,6 +343,201 @@ def calibrate_camera_host(object_points, image_points, image_size):
             tuple(v.reshape(3, 1).copy() for v in r.tvecs))
 
 
+# ------------------------------------------------------------------------------------------------ consensus: the definition
+
+class RobustCalibResult(NamedTuple):
+    status: int                  # CALIB_* of the last solve
+    rms: float                   # over the inlier rows of the views used
+    camera_matrix: np.ndarray
+    dist_coeffs: np.ndarray
+    view_status: np.ndarray      # int32 [B], pnp.PNP_* (incl. NO_CONSENSUS, and DEGENERATE for a view without a hypothesis)
+    rvecs: np.ndarray
+    tvecs: np.ndarray
+    view_rms: np.ndarray         # [B], over the view's inlier rows
+    view_points: np.ndarray      # int64 [B]: the rows OFFERED by the view
+    iterations: int
+    attempts: int
+    views_used: int
+    points_used: int             # inlier rows of the views used
+    inliers: list                # per view a bool array: the mask the last solve was given (all False for a view left out)
+    view_inliers: np.ndarray     # int64 [B]
+    winners: np.ndarray          # int32 [B]: the winning hypothesis, -1 where there is none
+    solves: int                  # joint solves run (1 .. 1 + rounds)
+    stable: bool                 # the last re-mask changed nothing (False when none ran after the last solve)
+
+
+def _calib_ransac_args(iterations, consensus_error, reproj_error, min_inliers, rounds):
+    iterations, reproj_error, min_inliers = pnp._ransac_args(iterations, reproj_error, min_inliers)
+    if not (math.isfinite(float(consensus_error)) and float(consensus_error) > 0):
+        raise ValueError("consensus_error must be finite and positive")
+    if not 0 <= int(rounds) <= RANSAC_MAX_ROUNDS:
+        raise ValueError(f"rounds must be in [0, {RANSAC_MAX_ROUNDS}]")
+    return iterations, float(consensus_error), reproj_error, min_inliers, int(rounds)
+
+
+def _transfer_errors2(H: np.ndarray, mc: np.ndarray, obj: np.ndarray, img: np.ndarray) -> np.ndarray:
+    """Squared distance (px^2) of every row's image point from H (board xy - mc); inf where q_z <= 0."""
+    X, Y = obj[:, 0] - mc[0], obj[:, 1] - mc[1]
+    qx = H[0, 0] * X + H[0, 1] * Y + H[0, 2]
+    qy = H[1, 0] * X + H[1, 1] * Y + H[1, 2]
+    qz = H[2, 0] * X + H[2, 1] * Y + H[2, 2]
+    e2 = np.full(obj.shape[0], math.inf)
+    f = qz > 0
+    du, dv = qx[f] / qz[f] - img[f, 0], qy[f] / qz[f] - img[f, 1]
+    e2[f] = du * du + dv * dv
+    return e2
+
+
+def _margin(e2: np.ndarray, thr: float) -> float:
+    e2 = e2[np.isfinite(e2)]
+    return float(np.abs(np.sqrt(e2) - thr).min()) / thr if e2.size else math.inf
+
+
+def _view_consensus(obj, img, ids, row_count, iterations, thr, min_inliers, seed):
+    """Step B for one view (rows in pool order, float64) -> (status, mask, winner, score, margin).  Only the view's own rows
+    and (seed, n, h) enter: the outcome does not depend on the view's place in a batch."""
+    n = obj.shape[0]
+    best, winner, best_e2, records = -1, -1, None, []
+    for h in range(iterations):
+        s = pnp._ransac_sample(seed, n, h, ids, row_count - 1)
+        if s is None:
+            continue
+        st, H, mc = pnp._homography4(obj[s], img[s])        # board xy - centroid -> RAW pixels: there is no model to undistort by
+        if st != PNP_OK:
+            continue
+        e2 = _transfer_errors2(H, mc, obj, img)
+        score = int((e2 <= thr * thr).sum())
+        records.append((score, e2))
+        if score > best:
+            best, winner, best_e2 = score, h, e2
+    if winner < 0:
+        return PNP_DEGENERATE, np.zeros(n, bool), -1, 0, math.inf
+    margin = min(_margin(e2, thr) for sc, e2 in records if sc >= best - 1)
+    if best < max(min_inliers, 4):
+        return PNP_NO_CONSENSUS, np.zeros(n, bool), winner, best, margin
+    return PNP_OK, best_e2 <= thr * thr, winner, best, margin
+
+
+def calibrate_camera_ransac_host_full(keypoints_list, col_count, row_count, square_len, image_size, iterations=100,
+                                      consensus_error=8.0, reproj_error=3.0, min_inliers=6, rounds=2, seed=0, with_margin=False,
+                                      pool_order=False):
+    """The definition of the robust calibration -> ``RobustCalibResult`` (with ``with_margin``: ``(result, margin)``).
+
+    ``keypoints_list``: per view an array of [x, y, id] rows.  Rows are taken in the order the corner pool holds them, as in
+    ``pnp.solve_pnp_ransac_host_full``: id-sorted stably, or as they stand with ``pool_order=True``.  Object points are
+    ``pnp.object_points`` (float32 -> float64), image points float32 -> float64.
+
+    A. per-view checks, with ``calibrate_charuco_pool``'s codes: fewer than 4 rows TOO_FEW, an id outside the board BAD_ID.
+    B. consensus per view, without a camera: hypothesis h draws four rows with ``pnp._ransac_sample`` and takes
+       ``pnp._homography4`` through them, board xy minus the sample's centroid -> RAW pixels (a pose hypothesis would need the
+       model this call is about to estimate; a homography has to absorb the lens, which is what ``consensus_error`` allows for).
+       Its score is the rows with |H(X) - x|^2 <= consensus_error^2 (q_z <= 0: an outlier).  All hypotheses are scored; the
+       winner is the highest score, the lowest h among equals.  No hypothesis: DEGENERATE; a score below max(min_inliers, 4):
+       NO_CONSENSUS; else the view's mask is the winner's.
+    C. ``calibrate_camera_host_full`` on the masked rows of the views that still stand (so a batch whose masks are all true gives
+       the plain result bit for bit).  A view that fails the solve's checks gets that status.  An overall status other than
+       CALIB_OK is returned as it is, with the masks that were used.
+    D. at most ``rounds`` times: ALL rows of every view the last solve used are projected through the solved (K, dist, rvec, tvec)
+       (``pnp._row_errors2``); the new mask is e^2 <= reproj_error^2; a view left with fewer than max(min_inliers, 4) rows
+       becomes NO_CONSENSUS with an all-false mask; views left out earlier never come back.  If no mask changed: ``stable``, stop.
+       Else solve again FROM SCRATCH on the new masks.  The result is always the last solve with the masks it was given, so
+       ``stable`` is False when the rounds ran out (or ``rounds=0``) before a re-mask could confirm the last solve.
+
+    The defaults are parameters, not measured claims: 8 px for the homography (solvePnPRansac's default), 3 px for the model;
+    min_inliers 6 because four rows always agree with the homography through themselves.
+
+    ``with_margin``: the smallest relative distance of any decision to its threshold: in B the rows of every hypothesis that
+    scores within one of its view's winner against ``consensus_error``, in D every row at every re-mask against ``reproj_error``."""
+    w, h = _image_size(image_size)
+    iterations, cthr, rthr, min_inliers, rounds = _calib_ransac_args(iterations, consensus_error, reproj_error, min_inliers, rounds)
+    need = max(min_inliers, 4)
+    B, n_ids = len(keypoints_list), (col_count - 1) * (row_count - 1)
+    vstat = np.full(B, PNP_OK, np.int32)                     # steps A, B, D: OK = the view still stands
+    winners = np.full(B, -1, np.int32)
+    offered = np.zeros(B, np.int64)
+    orders, obj32, img32, masks = [None] * B, [None] * B, [None] * B, [None] * B
+    margin = math.inf
+    for b, kp in enumerate(keypoints_list):
+        kp = np.asarray(kp)
+        kp = kp.reshape(-1, 3) if kp.size else np.zeros((0, 3))
+        n = offered[b] = kp.shape[0]
+        masks[b] = np.zeros(n, bool)
+        orders[b] = np.arange(n) if pool_order else np.argsort(kp[:, 2], kind="stable")
+        if n < 4:
+            vstat[b] = PNP_TOO_FEW
+            continue
+        kp = kp[orders[b]]
+        ids = kp[:, 2].astype(np.int64)
+        if ids.min() < 0 or ids.max() >= n_ids:
+            vstat[b] = PNP_BAD_ID
+            continue
+        obj32[b], img32[b] = pnp.object_points(ids, col_count, row_count, square_len), kp[:, :2].astype(np.float32)
+        vstat[b], masks[b], winners[b], _, mg = _view_consensus(obj32[b].astype(np.float64), img32[b].astype(np.float64), ids,
+                                                                row_count, iterations, cthr, min_inliers, seed)
+        margin = min(margin, mg)
+
+    solves, stable = 0, False
+    while True:
+        standing = np.flatnonzero(vstat == PNP_OK)
+        r = calibrate_camera_host_full([obj32[b][masks[b]] for b in standing], [img32[b][masks[b]] for b in standing], (w, h))
+        solves += 1
+        if r.status != CALIB_OK or solves > rounds:
+            break
+        k8 = np.zeros(8)
+        k8[:5] = r.dist_coeffs.ravel()
+        changed = False
+        for j, b in enumerate(standing):
+            if r.view_status[j] != PNP_OK:                   # not used by the solve: nothing to project it through
+                continue
+            e2 = pnp._row_errors2(obj32[b].astype(np.float64), img32[b].astype(np.float64), np.r_[r.rvecs[j], r.tvecs[j]],
+                                  r.camera_matrix, k8)
+            margin = min(margin, _margin(e2, rthr))
+            m = e2 <= rthr * rthr
+            if int(m.sum()) < need:
+                vstat[b], m = PNP_NO_CONSENSUS, np.zeros(m.size, bool)
+            changed |= not np.array_equal(m, masks[b])
+            masks[b] = m
+        if not changed:
+            stable = True
+            break
+
+    view_status = vstat.copy()
+    view_status[standing] = r.view_status
+    rv, tv, vr = np.zeros((B, 3)), np.zeros((B, 3)), np.zeros(B)
+    rv[standing], tv[standing], vr[standing] = r.rvecs, r.tvecs, r.view_rms
+    inliers = []
+    for b in range(B):
+        m = np.empty(masks[b].size, bool)
+        m[orders[b]] = masks[b]                               # back to the caller's row order
+        inliers.append(m)
+    out = RobustCalibResult(r.status, r.rms, r.camera_matrix, r.dist_coeffs, view_status, rv, tv, vr, offered, r.iterations,
+                            r.attempts, r.views_used, r.points_used, inliers, np.array([int(m.sum()) for m in inliers], np.int64),
+                            winners, solves, stable)
+    return (out, margin) if with_margin else out
+
+
+def _bad_id_error(col_count, row_count):
+    return IndexError(f"corner id outside [0, {(col_count - 1) * (row_count - 1)}) for a {col_count}x{row_count} board")
+
+
+def calibrate_camera_ransac_host(keypoints_list, col_count, row_count, square_len, image_size, iterations=100, consensus_error=8.0,
+                                 reproj_error=3.0, min_inliers=6, rounds=2, seed=0):
+    """cv2's 5-tuple plus the masks: ``(rms, K 3x3, dist 1x5, rvecs, tvecs, inliers)``.  Raises like ``calibrate_camera_host``:
+    ValueError for a view that cannot be used (too few rows, no consensus, degenerate) or a failed calibration; IndexError for an
+    id outside the board."""
+    r = calibrate_camera_ransac_host_full(keypoints_list, col_count, row_count, square_len, image_size, iterations,
+                                          consensus_error, reproj_error, min_inliers, rounds, seed)
+    if (r.view_status == PNP_BAD_ID).any():
+        raise _bad_id_error(col_count, row_count)
+    bad = np.flatnonzero(r.view_status != PNP_OK)
+    if bad.size:
+        raise ValueError(f"view {int(bad[0])} cannot be used (status {int(r.view_status[bad[0]])})")
+    if r.status != CALIB_OK:
+        raise ValueError(f"calibration failed (status {r.status})")
+    return (r.rms, r.camera_matrix, r.dist_coeffs, tuple(v.reshape(3, 1).copy() for v in r.rvecs),
+            tuple(v.reshape(3, 1).copy() for v in r.tvecs), r.inliers)
+
+
 # ------------------------------------------------------------------------------------------------ the device solver
 
 def workspace_bytes(batch: int) -> int:
@@ -389,3 +595,89 @@ def calibrate_charuco_device(keypoints_list: Sequence, col_count, row_count, squ
         n = (col_count - 1) * (row_count - 1)
         raise IndexError(f"corner id outside [0, {n}) for a {col_count}x{row_count} board")
     return r
+
+
+# ------------------------------------------------------------------------------------------------ consensus on the device
+
+def ransac_workspace_bytes(batch: int, pool: int, iterations: int = 100) -> int:
+    """Bytes of device workspace ``calibrate_charuco_ransac_pool`` needs (the scores, the filtered pool, the masks and the inner
+    solve's workspace)."""
+    from . import _lib
+    n = int(_lib.lib().dcx_calibrate_ransac_workspace_bytes(int(batch), int(pool), int(iterations)))
+    if n == 0:
+        raise ValueError(f"batch >= 1, pool >= 0 and iterations in [1, {pnp.RANSAC_MAX_ITERATIONS}] are required")
+    return n
+
+
+def calibrate_charuco_ransac_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len, image_size,
+                                  iterations=100, consensus_error=8.0, reproj_error=3.0, min_inliers=6, rounds=2, seed=0,
+                                  out_inliers=None) -> RobustCalibResult:
+    """``calibrate_charuco_pool`` behind the consensus search and re-check of ``calibrate_camera_ransac_host_full`` (the
+    definition), read in place from the corner pool.  The views' slot ranges must not overlap (DcxError).  ``inliers`` holds each
+    view's mask in SLOT order (``counts[b]`` values; all False for a view cut by the pool).  ``out_inliers``: a contiguous uint8
+    device tensor of at least ``pool`` values that receives the mask by slot; slots of no view are not written.  Like
+    ``calibrate_charuco_pool`` the call synchronises the current stream and cannot be captured in a graph."""
+    import torch
+    from . import _lib
+    w, h = _image_size(image_size)
+    iterations, cthr, rthr, min_inliers, rounds = _calib_ransac_args(iterations, consensus_error, reproj_error, min_inliers, rounds)
+    dev = packed.device
+    if packed.dtype != torch.int32 or not packed.is_contiguous() or packed.numel() < 2 * batch + (6 if refined else 4) * pool:
+        raise ValueError("packed must be a contiguous int32 corner pool of at least packed_len(batch, pool) words")
+    if out_inliers is None:
+        out_inliers = torch.zeros((max(pool, 1),), dtype=torch.uint8, device=dev)
+    if (out_inliers.device != dev or out_inliers.dtype != torch.uint8 or out_inliers.numel() < pool
+            or not out_inliers.is_contiguous()):
+        raise ValueError(f"out_inliers must be a contiguous uint8 tensor of at least {pool} values on {dev}")
+    st = torch.empty((batch,), dtype=torch.int32, device=dev)
+    pose = torch.empty((batch, pnp.POSE_WORDS), dtype=torch.float64, device=dev)
+    info = torch.empty((batch, 2), dtype=torch.int32, device=dev)
+    nbytes = ransac_workspace_bytes(batch, pool, iterations)
+    ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev)
+    res = (_ctypes.c_double * RESULT_WORDS)()
+    base = packed.data_ptr()
+    rows_p = base + 8 * batch
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().dcx_calibrate_ransac_pool(
+            base, base + 4 * batch, rows_p, rows_p + 16 * pool if refined else None, int(batch), int(pool), int(col_count),
+            int(row_count), float(square_len), w, h, iterations, cthr, rthr, min_inliers, rounds, int(seed) & 0xFFFFFFFF,
+            ws.data_ptr(), nbytes, st.data_ptr(), pose.data_ptr(), info.data_ptr(), out_inliers.data_ptr(), res,
+            _lib.current_stream()), "dcx_calibrate_ransac_pool")
+        st_h, pose_h, info_h, inl_h, head = (t.cpu().numpy() for t in (st, pose, info, out_inliers, packed[:2 * batch]))
+    r = np.array(res[:], np.float64)
+    status = int(r[14])
+    K = np.array([[r[0], 0.0, r[2]], [0.0, r[1], r[3]], [0.0, 0.0, 1.0]]) if status == CALIB_OK else np.zeros((3, 3))
+    inl_b = inl_h.astype(bool)
+    inliers = [inl_b[s0:s0 + n] if n > 0 and s0 >= 0 and s0 + n <= pool else np.zeros(max(n, 0), bool)
+               for n, s0 in zip(head[:batch].tolist(), head[batch:].tolist())]
+    return RobustCalibResult(status, float(r[9]), K, r[4:9].reshape(1, 5).copy(), st_h.astype(np.int32), pose_h[:, 0:3].copy(),
+                             pose_h[:, 3:6].copy(), pose_h[:, 6].copy(), pose_h[:, 7].astype(np.int64), int(r[10]), int(r[11]),
+                             int(r[12]), int(r[13]), inliers, info_h[:, 0].astype(np.int64), info_h[:, 1].astype(np.int32),
+                             int(r[15]) % 16, int(r[15]) >= 16)
+
+
+def calibrate_charuco_ransac_device(keypoints_list: Sequence, col_count, row_count, square_len, image_size, iterations=100,
+                                    consensus_error=8.0, reproj_error=3.0, min_inliers=6, rounds=2, seed=0,
+                                    device="cuda") -> RobustCalibResult:
+    """The robust calibration from ``infer_image``-format keypoint arrays on the GPU -> ``RobustCalibResult``, the masks in the
+    caller's row order.  IndexError if a view with >= 4 points carries an id outside the board."""
+    import torch
+    from .models._handles import require_cuda
+    dev = require_cuda(device)
+    _image_size(image_size)
+    _calib_ransac_args(iterations, consensus_error, reproj_error, min_inliers, rounds)
+    if len(keypoints_list) == 0:
+        raise ValueError("no views")
+    packed, b, pool = pnp._pack(keypoints_list, dev)
+    with torch.cuda.device(dev):
+        r = calibrate_charuco_ransac_pool(packed, b, pool, True, col_count, row_count, square_len, image_size, iterations,
+                                          consensus_error, reproj_error, min_inliers, rounds, seed)
+    if (r.view_status == PNP_BAD_ID).any():
+        raise _bad_id_error(col_count, row_count)
+    inliers = []
+    for kp, mask in zip(keypoints_list, r.inliers):
+        kp = np.asarray(kp)
+        if mask.size:                                         # undo _pack's stable id sort
+            mask = mask[np.argsort(np.argsort(kp.reshape(-1, 3)[:, 2], kind="stable"), kind="stable")]
+        inliers.append(mask)
+    return r._replace(inliers=inliers)

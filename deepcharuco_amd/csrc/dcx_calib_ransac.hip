@@ -1,0 +1,375 @@
+// dcx_calib_ransac.hip -- the camera calibration of dcx_calib.hip behind a consensus search, read in place from the corner pool: a
+// view's mislabelled corners are left out before the joint solve and re-checked after it.  deepcharuco_amd/calib.py restates every
+// step (calibrate_camera_ransac_host_full), which is the pin of these kernels.  All fp64.
+//
+//   consensus       grid (view, block of 64 hypotheses), one LANE per hypothesis: dcx_pnp_ransac.hip's sampler picks four rows, the
+//                   homography through them comes in closed form and maps board xy to RAW pixels (there is no camera model yet, so
+//                   nothing is undistorted and no pose can be scored), and a serial loop over the view's rows (every lane reads the
+//                   same row) counts those within consensus_error px of their transfer.  Scores (-1: no hypothesis) go to the
+//                   workspace.
+//   select_compact  one wave per view: first maximum of the scores in a fixed order, the winner's homography and mask recomputed,
+//                   the surviving rows compacted in order (ballot + prefix popcount, 64 rows at a time) into a FILTERED POOL in the
+//                   workspace: counts', starts', rows', xy'.  A view keeps its own slot range there; an excluded view gets
+//                   counts' = 0.
+//   (solve)         dcx_calibrate_pool, unchanged, on the filtered pool
+//   remask          one wave per view, at most `rounds` times: every row of the ORIGINAL pool projected through the solved model and
+//                   the view's pose; the new mask, the filtered pool re-compacted, a per-view "changed" word
+//   changed_sum     (one wave) those words summed in a fixed order: the one word the host reads per round.  Zero: done; else the
+//                   solve runs again from scratch on the new filtered pool
+//   merge           one wave per view, after the last solve: the consensus statuses laid over the inner solve's, d_pose[b][7] = the
+//                   rows offered, d_info, d_inliers
+// A view's slot range is written in the filtered pool, so ranges must not overlap: `overlap` (one wave per view against every other
+// view) looks first and the call is refused before anything else runs.  Nothing is allocated, no atomics, every reduction has a
+// fixed order: two calls give the same bits.  Like dcx_calibrate_pool the call synchronises its stream.
+#include "dcx_pnp_dev.h"
+
+namespace {
+
+constexpr int kMaxRounds = 8;            // calib.RANSAC_MAX_ROUNDS
+constexpr int kHeadWords = 16;           // int32 words at the head of the workspace
+enum : int { kOverlap = 0, kChanged = 1 };
+
+struct RPool {                           // the caller's pool
+    const int32_t* counts;
+    const int32_t* starts;
+    const int32_t* rows;
+    const float* xy;                     // or null: the integer rows are the image points
+    int pool, n_ids, rm1;
+    double square_len;
+};
+
+// workspace: head | dcx_calibrate_pool's workspace | scores [B][iterations] | counts' starts' vstat winner changed [B] each |
+// rows' [pool][4] | xy' [pool][2] | mask [pool], every part 8-byte aligned
+struct RWs {
+    int32_t* head;
+    void* inner;
+    int32_t *scores, *counts, *starts, *vstat, *winner, *changed, *rows;
+    float* xy;
+    uint8_t* mask;
+};
+
+__host__ __device__ inline size_t up8(size_t n) { return (n + 7) & ~(size_t)7; }
+
+size_t rws_layout(void* base, int batch, int pool, int iterations, RWs* w) {
+    const size_t inner = dcx_calibrate_workspace_bytes(batch);
+    size_t at = 0;
+    char* p = (char*)base;
+    auto take = [&](size_t bytes) {
+        char* q = p + at;
+        at += up8(bytes);
+        return q;
+    };
+    RWs r;
+    r.head = (int32_t*)take(kHeadWords * sizeof(int32_t));
+    r.inner = take(inner);
+    r.scores = (int32_t*)take((size_t)batch * (size_t)iterations * sizeof(int32_t));
+    r.counts = (int32_t*)take((size_t)batch * sizeof(int32_t));
+    r.starts = (int32_t*)take((size_t)batch * sizeof(int32_t));
+    r.vstat = (int32_t*)take((size_t)batch * sizeof(int32_t));
+    r.winner = (int32_t*)take((size_t)batch * sizeof(int32_t));
+    r.changed = (int32_t*)take((size_t)batch * sizeof(int32_t));
+    r.rows = (int32_t*)take((size_t)pool * 4 * sizeof(int32_t));
+    r.xy = (float*)take((size_t)pool * 2 * sizeof(float));
+    r.mask = (uint8_t*)take((size_t)pool);
+    if (w) *w = r;
+    return at;
+}
+
+// Four sampled rows of a view -> the homography board xy - centroid -> raw pixels; false if the sampler or the closed form refuses
+__device__ __forceinline__ bool view_hypothesis(const Frame& f, uint32_t seed, int h, double* H, double& mcx, double& mcy) {
+    int s[4];
+    if (!ransac_sample(f.rows, seed, f.n, h, f.rm1, s)) return false;
+    Sample q;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) f.load(s[k], q.mx[k], q.my[k], q.x[k], q.y[k]);
+    PnpCamera none;                      // (the overload's camera is unused: the image points are taken as they are)
+    none.fx = none.fy = 1.0;
+    none.cx = none.cy = 0.0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) none.k[i] = 0.0;
+    return homography(q, none, false, H, mcx, mcy) == DCX_PNP_OK;
+}
+
+// squared transfer error (px^2) of one row under H; +inf if the row maps to the far side of the line at infinity (q_z <= 0)
+__device__ __forceinline__ double transfer_error2(const double* H, double mcx, double mcy, double bx, double by, double u, double v) {
+    const double X = bx - mcx, Y = by - mcy;
+    const double qx = H[0] * X + H[1] * Y + H[2];
+    const double qy = H[3] * X + H[4] * Y + H[5];
+    const double qz = H[6] * X + H[7] * Y + H[8];
+    if (!(qz > 0)) return INFINITY;
+    const double du = qx / qz - u, dv = qy / qz - v;
+    return du * du + dv * dv;
+}
+
+__device__ __forceinline__ Frame frame_of(const RPool& pl, int n, int s0) {
+    return Frame{pl.rows + 4 * (long long)s0, pl.xy ? pl.xy + 2 * (long long)s0 : nullptr, n, pl.rm1, pl.square_len};
+}
+
+// One wave per view: does its slot range (the part inside the pool) meet another view's?  The lanes share the other views out.
+__global__ __launch_bounds__(kLanes) void calib_ransac_overlap_kernel(RPool pl, int batch, int32_t* __restrict__ head) {
+    const int b = blockIdx.x;
+    const long long n = pl.counts[b], s0 = pl.starts[b];
+    if (n <= 0) return;
+    const long long lo = s0 < 0 ? 0 : s0, hi = s0 + n < pl.pool ? s0 + n : pl.pool;
+    if (lo >= hi) return;
+    bool hit = false;
+    for (int o = threadIdx.x; o < batch; o += kLanes) {
+        const long long on = pl.counts[o], os = pl.starts[o];
+        if (o == b || on <= 0) continue;
+        const long long olo = os < 0 ? 0 : os, ohi = os + on < pl.pool ? os + on : pl.pool;
+        hit |= olo < ohi && olo < hi && lo < ohi;
+    }
+    if (__any(hit) && threadIdx.x == 0) head[kOverlap] = 1;
+}
+
+__global__ __launch_bounds__(kLanes) void calib_ransac_consensus_kernel(RPool pl, int iterations, double thr2, uint32_t seed,
+                                                                        int32_t* __restrict__ scores) {
+    const int b = blockIdx.x, h = blockIdx.y * kLanes + threadIdx.x;
+    int n, s0;
+    if (frame_status(pl.counts, pl.starts, pl.rows, b, pl.pool, pl.n_ids, n, s0) != DCX_PNP_OK) return;   // select reads no score
+    if (h >= iterations) return;
+    const Frame f = frame_of(pl, n, s0);
+    double H[9], mcx, mcy;
+    int score = -1;
+    if (view_hypothesis(f, seed, h, H, mcx, mcy)) {
+        score = 0;
+        for (int i = 0; i < n; ++i) {
+            double bx, by, u, v;
+            f.load(i, bx, by, u, v);
+            score += transfer_error2(H, mcx, mcy, bx, by, u, v) <= thr2 ? 1 : 0;
+        }
+    }
+    scores[(long long)b * iterations + h] = score;
+}
+
+// Rows base .. base + 63 of the view: the mask slot, and the rows that stay appended in order to the view's share of the filtered
+// pool.  -> the number that stayed.  Wave-wide.
+__device__ __forceinline__ int keep_rows(const RPool& pl, const RWs& ws, int s0, int i, int n, bool in, int count) {
+    const int lane = threadIdx.x;
+    const unsigned long long m = __ballot(in);
+    if (i < n) ws.mask[(long long)s0 + i] = in ? 1 : 0;
+    if (in) {
+        const long long from = (long long)s0 + i, to = (long long)s0 + count + __popcll(m & ((1ull << lane) - 1ull));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ws.rows[4 * to + k] = pl.rows[4 * from + k];
+        if (pl.xy) {
+            ws.xy[2 * to] = pl.xy[2 * from];
+            ws.xy[2 * to + 1] = pl.xy[2 * from + 1];
+        }
+    }
+    return __popcll(m);
+}
+
+// The view leaves the calibration: an empty view in the filtered pool, an all-false mask over its slots that lie in the pool.
+__device__ __forceinline__ void exclude_view(const RPool& pl, const RWs& ws, int b, int n, int s0, int status) {
+    const int lane = threadIdx.x;
+    if (n > 0)
+        for (long long i = lane; i < n; i += kLanes)
+            if (s0 + i >= 0 && s0 + i < pl.pool) ws.mask[s0 + i] = 0;
+    if (lane == 0) {
+        ws.vstat[b] = status;
+        ws.counts[b] = 0;
+    }
+}
+
+__global__ __launch_bounds__(kLanes) void calib_ransac_select_compact_kernel(RPool pl, int iterations, double thr2, int need,
+                                                                             uint32_t seed, RWs ws) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    int n, s0;
+    const int st = frame_status(pl.counts, pl.starts, pl.rows, b, pl.pool, pl.n_ids, n, s0);
+    if (lane == 0) {
+        ws.starts[b] = st == DCX_PNP_OK ? s0 : 0;
+        ws.winner[b] = -1;
+        ws.changed[b] = 0;
+    }
+    if (st != DCX_PNP_OK) {
+        exclude_view(pl, ws, b, n, s0, st);
+        return;
+    }
+    // the highest score, the lowest h among equals: ascending h in each lane, then a butterfly with the same rule
+    int best = -1, bh = 0x7fffffff;
+    for (int h = lane; h < iterations; h += kLanes) {
+        const int sc = ws.scores[(long long)b * iterations + h];
+        if (sc > best) {
+            best = sc;
+            bh = h;
+        }
+    }
+#pragma unroll
+    for (int m = kLanes / 2; m >= 1; m >>= 1) {
+        const int ob = __shfl_xor(best, m, kLanes), oh = __shfl_xor(bh, m, kLanes);
+        if (ob > best || (ob == best && oh < bh)) {
+            best = ob;
+            bh = oh;
+        }
+    }
+    if (best < 0) {
+        exclude_view(pl, ws, b, n, s0, DCX_PNP_DEGENERATE);
+        return;
+    }
+    const Frame f = frame_of(pl, n, s0);
+    double H[9], mcx, mcy;
+    view_hypothesis(f, seed, bh, H, mcx, mcy);          // (it scored, so it exists: every lane recomputes the same H)
+    int count = 0;
+    for (int base = 0; base < n; base += kLanes) {
+        const int i = base + lane;
+        bool in = false;
+        if (i < n) {
+            double bx, by, u, v;
+            f.load(i, bx, by, u, v);
+            in = transfer_error2(H, mcx, mcy, bx, by, u, v) <= thr2;
+        }
+        count += keep_rows(pl, ws, s0, i, n, in, count);
+    }
+    if (lane == 0) ws.winner[b] = bh;
+    if (count < need) {
+        exclude_view(pl, ws, b, n, s0, DCX_PNP_NO_CONSENSUS);
+        return;
+    }
+    if (lane == 0) {
+        ws.vstat[b] = DCX_PNP_OK;
+        ws.counts[b] = count;
+    }
+}
+
+__global__ __launch_bounds__(kLanes) void calib_ransac_remask_kernel(RPool pl, PnpCamera cam, double thr2, int need,
+                                                                     const int32_t* __restrict__ view_status,
+                                                                     const double* __restrict__ pose, RWs ws) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    // a view the last solve did not use keeps its mask; one excluded earlier does not come back
+    if (ws.vstat[b] != DCX_PNP_OK || view_status[b] != DCX_PNP_OK) {
+        if (lane == 0) ws.changed[b] = 0;
+        return;
+    }
+    const int n = pl.counts[b], s0 = pl.starts[b];
+    const Frame f = frame_of(pl, n, s0);
+    double p[6], R[9];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) p[i] = pose[8 * (long long)b + i];
+    rodrigues(p, R);
+    int count = 0;
+    bool diff = false;
+    for (int base = 0; base < n; base += kLanes) {
+        const int i = base + lane;
+        bool in = false;
+        if (i < n) {
+            double bx, by, u, v;
+            f.load(i, bx, by, u, v);
+            in = row_error2(R, p + 3, cam, bx, by, u, v) <= thr2;
+            diff |= in != (ws.mask[(long long)s0 + i] != 0);
+        }
+        count += keep_rows(pl, ws, s0, i, n, in, count);
+    }
+    const bool changed = __any(diff);
+    if (count < need) {
+        exclude_view(pl, ws, b, n, s0, DCX_PNP_NO_CONSENSUS);
+    } else if (lane == 0) {
+        ws.counts[b] = count;
+    }
+    if (lane == 0) ws.changed[b] = changed ? 1 : 0;
+}
+
+__global__ __launch_bounds__(kLanes) void calib_ransac_changed_sum_kernel(int batch, RWs ws) {
+    int s = 0;
+    for (int b = threadIdx.x; b < batch; b += kLanes) s += ws.changed[b];
+#pragma unroll
+    for (int m = kLanes / 2; m >= 1; m >>= 1) s += __shfl_xor(s, m, kLanes);
+    if (threadIdx.x == 0) ws.head[kChanged] = s;
+}
+
+__global__ __launch_bounds__(kLanes) void calib_ransac_merge_kernel(RPool pl, RWs ws, int32_t* __restrict__ view_status,
+                                                                    double* __restrict__ pose, int32_t* __restrict__ info,
+                                                                    uint8_t* __restrict__ inliers) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const long long n = pl.counts[b], s0 = pl.starts[b];
+    if (inliers && n > 0)
+        for (long long i = lane; i < n; i += kLanes)
+            if (s0 + i >= 0 && s0 + i < pl.pool) inliers[s0 + i] = ws.mask[s0 + i];
+    if (lane != 0) return;
+    const int vs = ws.vstat[b];
+    if (vs != DCX_PNP_OK) {              // (the inner solve saw an empty view: TOO_FEW, zeros)
+        view_status[b] = vs;
+#pragma unroll
+        for (int i = 0; i < 7; ++i) pose[8 * (long long)b + i] = 0.0;
+    }
+    pose[8 * (long long)b + 7] = (double)pl.counts[b];
+    info[2 * (long long)b] = ws.counts[b];
+    info[2 * (long long)b + 1] = ws.winner[b];
+}
+
+bool ransac_sizes_ok(int batch, int pool, int iterations) {
+    return batch > 0 && pool >= 0 && iterations >= 1 && iterations <= kMaxIterations;
+}
+
+}  // namespace
+
+extern "C" size_t dcx_calibrate_ransac_workspace_bytes(int batch, int pool, int iterations) {
+    if (!ransac_sizes_ok(batch, pool, iterations)) return 0;
+    return rws_layout(nullptr, batch, pool, iterations, nullptr);
+}
+
+extern "C" int dcx_calibrate_ransac_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows, const float* d_xy,
+                                         int batch, int pool, int col_count, int row_count, double square_len, int image_width,
+                                         int image_height, int iterations, double consensus_error, double reproj_error,
+                                         int min_inliers, int rounds, unsigned seed, void* d_workspace, size_t workspace_bytes,
+                                         int32_t* d_view_status, double* d_pose, int32_t* d_info, uint8_t* d_inliers,
+                                         double* h_result, void* stream) {
+    if (!d_counts || !d_starts || !d_rows || !d_workspace || !d_view_status || !d_pose || !d_info || !h_result) return DCX_E_ARG;
+    if (!ransac_sizes_ok(batch, pool, iterations) || col_count < 2 || row_count < 2 || image_width <= 0 || image_height <= 0)
+        return DCX_E_ARG;
+    if ((long long)(col_count - 1) * (row_count - 1) > 0x7fffffffLL) return DCX_E_ARG;
+    if (!isfinite(square_len) || !isfinite(consensus_error) || !(consensus_error > 0) || !isfinite(reproj_error) ||
+        !(reproj_error > 0) || rounds < 0 || rounds > kMaxRounds)
+        return DCX_E_ARG;
+    if ((uintptr_t)d_workspace & 7) return DCX_E_ARG;
+    if (workspace_bytes < rws_layout(nullptr, batch, pool, iterations, nullptr)) return DCX_E_WS;
+    RWs ws;
+    rws_layout(d_workspace, batch, pool, iterations, &ws);
+    const size_t inner_bytes = dcx_calibrate_workspace_bytes(batch);
+    hipStream_t s = (hipStream_t)stream;
+    const RPool pl{d_counts, d_starts, d_rows, d_xy, pool, (col_count - 1) * (row_count - 1), row_count - 1, square_len};
+    const dim3 views((unsigned)batch), wave(kLanes), one(1);
+    const int need = min_inliers > 4 ? min_inliers : 4;
+
+    int word = 0;
+    DCX_CHECK_HIP(hipMemsetAsync(ws.head, 0, kHeadWords * sizeof(int32_t), s));
+    hipLaunchKernelGGL(calib_ransac_overlap_kernel, views, wave, 0, s, pl, batch, ws.head);
+    DCX_CHECK_HIP(hipGetLastError());
+    DCX_CHECK_HIP(hipMemcpyAsync(&word, ws.head + kOverlap, sizeof(int), hipMemcpyDeviceToHost, s));
+    DCX_CHECK_HIP(hipStreamSynchronize(s));
+    if (word) return DCX_E_ARG;          // two views share slots: nothing has been written
+
+    hipLaunchKernelGGL(calib_ransac_consensus_kernel, dim3((unsigned)batch, (unsigned)((iterations + kLanes - 1) / kLanes)), wave, 0,
+                       s, pl, iterations, consensus_error * consensus_error, (uint32_t)seed, ws.scores);
+    hipLaunchKernelGGL(calib_ransac_select_compact_kernel, views, wave, 0, s, pl, iterations, consensus_error * consensus_error,
+                       need, (uint32_t)seed, ws);
+    DCX_CHECK_HIP(hipGetLastError());
+
+    int solves = 0, stable = 0;
+    while (true) {
+        const int rc = dcx_calibrate_pool(ws.counts, ws.starts, ws.rows, d_xy ? ws.xy : nullptr, batch, pool, col_count, row_count,
+                                          square_len, image_width, image_height, ws.inner, inner_bytes, d_view_status, d_pose,
+                                          h_result, stream);
+        if (rc != 0) return rc;
+        ++solves;
+        if ((int)h_result[14] != DCX_CALIB_OK || solves > rounds) break;
+        PnpCamera cam;
+        cam.fx = h_result[0]; cam.fy = h_result[1]; cam.cx = h_result[2]; cam.cy = h_result[3];
+        for (int i = 0; i < 8; ++i) cam.k[i] = i < 5 ? h_result[4 + i] : 0.0;
+        hipLaunchKernelGGL(calib_ransac_remask_kernel, views, wave, 0, s, pl, cam, reproj_error * reproj_error, need, d_view_status,
+                           d_pose, ws);
+        hipLaunchKernelGGL(calib_ransac_changed_sum_kernel, one, wave, 0, s, batch, ws);
+        DCX_CHECK_HIP(hipGetLastError());
+        DCX_CHECK_HIP(hipMemcpyAsync(&word, ws.head + kChanged, sizeof(int), hipMemcpyDeviceToHost, s));
+        DCX_CHECK_HIP(hipStreamSynchronize(s));
+        if (word == 0) {
+            stable = 1;
+            break;
+        }
+    }
+    hipLaunchKernelGGL(calib_ransac_merge_kernel, views, wave, 0, s, pl, ws, d_view_status, d_pose, d_info, d_inliers);
+    DCX_CHECK_HIP(hipGetLastError());
+    DCX_CHECK_HIP(hipStreamSynchronize(s));
+    h_result[15] = (double)(solves + 16 * stable);
+    return 0;
+}

@@ -1,7 +1,9 @@
 // dcx_pnp_dev.h -- the fp64 device steps of the PnP solver (dcx_pnp.hip) that the camera calibration (dcx_calib.hip) reuses:
 // packed symmetric storage, the wave butterfly, cyclic Jacobi, Rodrigues both ways, the SO(3) right Jacobian, the pool reader
 // (Frame), undistortPoints, the 6x6 Cholesky, the planar DLT homography, the planar pose init and the PnP Levenberg-Marquardt; dcx_pnp_ransac.hip runs the
-// last three over an index list of a frame's rows (the frame type is a template parameter).
+// last three over an index list of a frame's rows (the frame type is a template parameter).  Also here: what the two consensus
+// searches (dcx_pnp_ransac.hip, dcx_calib_ransac.hip) share: the per-frame checks, the sampler, the four-point homography and one
+// row's reprojection error.
 // deepcharuco_amd/pnp.py restates every step (its functions of the same names).  Everything is force-inlined and has internal
 // linkage, so each translation unit compiles its own copy.
 #pragma once
@@ -427,6 +429,158 @@ __device__ __forceinline__ int homography(const F& f, const PnpCamera& cam, bool
     double hmax = 0.0;
 #pragma unroll
     for (int i = 0; i < 9; ++i) hmax = fmax(hmax, fabs(H[i]));
+    if (!(fabs(H[8]) > 1e-12 * hmax)) return DCX_PNP_DEGENERATE;
+    const double h22 = H[8];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) H[i] /= h22;
+    mc_x = mcx;
+    mc_y = mcy;
+    return DCX_PNP_OK;
+}
+
+// ---- the consensus searches' shared steps (dcx_pnp_ransac.hip, dcx_calib_ransac.hip): the per-frame checks, the counter-hash
+// sampler, the closed-form homography through four rows and one row's reprojection error
+
+constexpr int kMaxIterations = 4096; // hypotheses per frame (pnp.RANSAC_MAX_ITERATIONS)
+constexpr int kSampleTries = 8;      // complete 4-samples per hypothesis (pnp.RANSAC_SAMPLE_TRIES)
+constexpr int kMaxDraws = 256;       // slot draws per hypothesis, redraws included (pnp.RANSAC_MAX_DRAWS)
+
+// The per-frame checks of dcx_solve_pnp_kernel, in its order -> DCX_PNP_OK if the frame's rows can be read and solved.  Wave-wide.
+__device__ __forceinline__ int frame_status(const int32_t* counts, const int32_t* starts, const int32_t* rows, int b, int pool,
+                                            int n_ids, int& n, int& s0) {
+    n = counts[b];
+    s0 = starts[b];
+    if (n <= 0) return DCX_PNP_TOO_FEW;
+    if (s0 < 0 || (long long)s0 + n > (long long)pool) return DCX_PNP_TRUNCATED;      // (its slots are not read)
+    if (n < 4) return DCX_PNP_TOO_FEW;
+    bool bad = false;
+    for (int i = threadIdx.x; i < n; i += kLanes) {
+        const int id = rows[4 * ((long long)s0 + i) + 2];
+        bad |= id < 0 || id >= n_ids;
+    }
+    return __any(bad) ? DCX_PNP_BAD_ID : DCX_PNP_OK;
+}
+
+__device__ __forceinline__ uint32_t mix32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7FEB352Du;
+    x ^= x >> 15;
+    x *= 0x846CA68Bu;
+    return x ^ (x >> 16);
+}
+
+// draw c of hypothesis h of a frame with n rows -> a slot in [0, n)  (pnp._ransac_draw)
+__device__ __forceinline__ int ransac_draw(uint32_t seed, uint32_t n, uint32_t h, uint32_t c) {
+    const uint32_t r = mix32(seed ^ mix32(n * 0x9E3779B9u + mix32(h * 0x85EBCA6Bu + c)));
+    return (int)(((uint64_t)r * n) >> 32);
+}
+
+__device__ __forceinline__ bool on_a_line(const int* gx, const int* gy, int a, int b, int c) {
+    return (long long)(gx[b] - gx[a]) * (gy[c] - gy[a]) - (long long)(gy[b] - gy[a]) * (gx[c] - gx[a]) == 0;
+}
+
+// pnp._ransac_sample: four distinct slots whose ids are distinct and hold no collinear triple on the id grid; false if none came
+__device__ __forceinline__ bool ransac_sample(const int32_t* rows, uint32_t seed, int n, int h, int rm1, int (&s)[4]) {
+    uint32_t c = 0;
+#pragma unroll 1
+    for (int attempt = 0; attempt < kSampleTries; ++attempt) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            while (true) {
+                if (c >= (uint32_t)kMaxDraws) return false;
+                const int i = ransac_draw(seed, (uint32_t)n, (uint32_t)h, c++);
+                bool held = false;
+#pragma unroll
+                for (int j = 0; j < k; ++j) held |= s[j] == i;
+                if (!held) {
+                    s[k] = i;
+                    break;
+                }
+            }
+        }
+        int id[4], gx[4], gy[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            id[k] = rows[4 * s[k] + 2];
+            gx[k] = id[k] % rm1;
+            gy[k] = id[k] / rm1;
+        }
+        const bool shared = id[0] == id[1] || id[0] == id[2] || id[0] == id[3] || id[1] == id[2] || id[1] == id[3] || id[2] == id[3];
+        if (!shared && !on_a_line(gx, gy, 1, 2, 3) && !on_a_line(gx, gy, 0, 2, 3) && !on_a_line(gx, gy, 0, 1, 3) &&
+            !on_a_line(gx, gy, 0, 1, 2))
+            return true;
+    }
+    return false;
+}
+
+// adjugate of a row-major 3x3
+__device__ __forceinline__ void adjugate(const double* m, double* a) {
+    a[0] = m[4] * m[8] - m[5] * m[7]; a[1] = m[2] * m[7] - m[1] * m[8]; a[2] = m[1] * m[5] - m[2] * m[4];
+    a[3] = m[5] * m[6] - m[3] * m[8]; a[4] = m[0] * m[8] - m[2] * m[6]; a[5] = m[2] * m[3] - m[0] * m[5];
+    a[6] = m[3] * m[7] - m[4] * m[6]; a[7] = m[1] * m[6] - m[0] * m[7]; a[8] = m[0] * m[4] - m[1] * m[3];
+}
+
+// pnp._projective_basis: the 3x3 that sends e1, e2, e3, (1,1,1) to the four points, each up to scale
+__device__ __forceinline__ void projective_basis(const double* x, const double* y, double* A) {
+    const double m[9] = {x[0], x[1], x[2], y[0], y[1], y[2], 1.0, 1.0, 1.0};
+    double a[9];
+    adjugate(m, a);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double lam = a[j * 3] * x[3] + a[j * 3 + 1] * y[3] + a[j * 3 + 2];
+        A[j] = m[j] * lam;
+        A[3 + j] = m[3 + j] * lam;
+        A[6 + j] = lam;
+    }
+}
+
+// squared reprojection error (px^2) of one row at the pose (R, t) through the full distortion model; +inf if the point is not in
+// front of the camera (evaluate()'s projection, per row)
+__device__ __forceinline__ double row_error2(const double* R, const double* t, const PnpCamera& cam, double mx, double my, double u,
+                                             double v) {
+    const double X = R[0] * mx + R[1] * my + t[0];
+    const double Y = R[3] * mx + R[4] * my + t[1];
+    const double Z = R[6] * mx + R[7] * my + t[2];
+    if (!(Z > 0)) return INFINITY;
+    const double* k = cam.k;
+    const double iz = 1.0 / Z, x = X * iz, y = Y * iz;
+    const double r2 = x * x + y * y;
+    const double num = 1 + r2 * (k[0] + r2 * (k[1] + r2 * k[4]));
+    const double den = 1 + r2 * (k[5] + r2 * (k[6] + r2 * k[7]));
+    const double g = num / den;
+    const double xd = x * g + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x);
+    const double yd = y * g + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y;
+    const double ru = cam.fx * xd + cam.cx - u, rv = cam.fy * yd + cam.cy - v;
+    return ru * ru + rv * rv;
+}
+
+// Four sampled rows of a frame, held by one lane: board points and undistorted image points.
+struct Sample {
+    double mx[4], my[4], x[4], y[4];
+};
+
+// pnp._homography4: the homography through exactly four points in closed form, H = B adj(A) with A, B the projective bases of the
+// centred board points and of the image points.  init_pose() picks this overload for a Sample; no cross-lane step.
+__device__ __forceinline__ int homography(const Sample& q, const PnpCamera&, bool, double* H, double& mc_x, double& mc_y) {
+    const double mcx = (q.mx[0] + q.mx[1] + q.mx[2] + q.mx[3]) / 4.0, mcy = (q.my[0] + q.my[1] + q.my[2] + q.my[3]) / 4.0;
+    double cx[4], cy[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        cx[k] = q.mx[k] - mcx;
+        cy[k] = q.my[k] - mcy;
+    }
+    double A[9], B[9], Aa[9];
+    projective_basis(cx, cy, A);
+    projective_basis(q.x, q.y, B);
+    adjugate(A, Aa);
+    double hmax = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            H[i * 3 + j] = B[i * 3] * Aa[j] + B[i * 3 + 1] * Aa[3 + j] + B[i * 3 + 2] * Aa[6 + j];
+            hmax = fmax(hmax, fabs(H[i * 3 + j]));
+        }
     if (!(fabs(H[8]) > 1e-12 * hmax)) return DCX_PNP_DEGENERATE;
     const double h22 = H[8];
 #pragma unroll

@@ -281,6 +281,38 @@ int dcx_calibrate_pool(const int32_t* d_counts, const int32_t* d_starts, const i
                        int32_t* d_view_status /* [B] DCX_PNP_* */, double* d_pose /* [B][8] */,
                        double* h_result /* [16] */, void* stream);
 
+/* ---- the same calibration behind a consensus search: a camera model that survives mislabelled corners -----------------------
+ * Pool, object points, image points and the per-view checks as for dcx_calibrate_pool; the views' slot ranges must not overlap
+ * (DCX_E_ARG, looked for on the device before anything is written: each view's surviving rows live at its own slots of the
+ * workspace).  Steps, restated in deepcharuco_amd/calib.py (calibrate_camera_ransac_host_full):
+ * B. per view, `iterations` hypotheses (1..4096) drawn by dcx_solve_pnp_ransac_pool's sampler, all evaluated: the closed-form
+ *    homography through the four rows maps board xy to RAW pixels (no camera model exists yet, so nothing is undistorted and no
+ *    pose can be scored), and the score is the rows whose transfer error is <= consensus_error px (finite, > 0; a row with
+ *    q_z <= 0 is an outlier).  The winner is the highest score, the lowest h among equals.  No hypothesis: DCX_PNP_DEGENERATE;
+ *    fewer than max(min_inliers, 4) inliers: DCX_PNP_NO_CONSENSUS; either way the view is left out.
+ * C. dcx_calibrate_pool, unchanged, over the surviving rows of the views that still stand.
+ * D. at most `rounds` (0..8) times: every row of every view the solve used is projected through the solved model and pose; the
+ *    new mask is error <= reproj_error px (finite, > 0); a view left with fewer than max(min_inliers, 4) rows becomes
+ *    DCX_PNP_NO_CONSENSUS; excluded views never come back.  If no mask changed the result is stable; else C runs again from
+ *    scratch on the new masks.  The outputs are always those of the last solve and the masks it was given.
+ * d_view_status, d_pose, h_result as dcx_calibrate_pool, except: the status of a view left out by B or D is that step's,
+ * d_pose[b][6] and h_result[9], [13] are over inlier rows, d_pose[b][7] is the rows OFFERED (counts[b]), and h_result[15] =
+ * solves + 16 * stable.  d_info int32 [B][2]: the view's inlier count, its winning hypothesis (-1: none).  d_inliers uint8 [pool]
+ * (may be NULL): the mask the last solve was given, 0 at every slot of a view that was left out; slots of no view are not
+ * written.  d_workspace: dcx_calibrate_ransac_workspace_bytes(batch, pool, iterations) bytes, 8-byte aligned (DCX_E_WS if
+ * smaller); nothing is allocated.  Like dcx_calibrate_pool this entry point SYNCHRONISES `stream` (once for the overlap word, in
+ * every solve, and once per round for the "changed" word) and cannot be captured in a graph.  No atomics: two calls give the
+ * same bits.                                                                                                                 */
+size_t dcx_calibrate_ransac_workspace_bytes(int batch, int pool, int iterations);   /* 0 for refused arguments */
+int dcx_calibrate_ransac_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows,
+                              const float* d_xy /* NULL = use integer rows x,y */, int batch, int pool,
+                              int col_count, int row_count, double square_len, int image_width, int image_height,
+                              int iterations, double consensus_error, double reproj_error, int min_inliers, int rounds,
+                              unsigned seed, void* d_workspace, size_t workspace_bytes,
+                              int32_t* d_view_status /* [B] DCX_PNP_* */, double* d_pose /* [B][8] */,
+                              int32_t* d_info /* [B][2]: inliers, winner */, uint8_t* d_inliers /* [pool], may be NULL */,
+                              double* h_result /* [16] */, void* stream);
+
 /* ---- stage-level entry point for kernel tests / roofline measurement -------------------
  * One 3x3 (or 1x1) convolution + bias [+ eval-BN + ReLU] [+ 2x2 max-pool] on C4 tensors
  * using the same MFMA kernel the networks use.  h_* are host arrays in PyTorch layout;
