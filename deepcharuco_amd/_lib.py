@@ -79,6 +79,10 @@ SIGNATURES = {
     "dcx_calibrate_ransac_workspace_bytes": (_sz, [_i, _i, _i]),
     "dcx_calibrate_ransac_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _i, _i, _i, C.c_double, C.c_double, _i, _i,
                                       C.c_uint, _vp, _sz, _vp, _vp, _vp, _vp, C.POINTER(C.c_double), _vp]),
+    "dcx_stereo_calibrate_workspace_bytes": (_sz, [_i, _i, _i]),
+    "dcx_stereo_calibrate_pool": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), _i,
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double), _i, _vp, _sz, _vp, _vp, _vp,
+                                      C.POINTER(C.c_double), _vp]),
     "dcx_conv_layer": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "dcx_nchw_to_c4": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "dcx_c4_to_nchw": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),

@@ -1,0 +1,906 @@
+// dcx_stereo.hip -- cv2.stereoCalibrate with CALIB_FIX_INTRINSIC for a planar ChArUco board, on the device, read straight from the
+// two corner pools dcx_infer_batch writes for two rigidly mounted cameras: the rig transform X = (R, T), q1 = R q0 + T, and the
+// board's pose P_t in camera 0's frame per timestamp.  The two views of a timestamp need no common id.  The steps (all fp64) are
+// restated readably in deepcharuco_amd/stereo.py (stereo_calibrate_host_full), which is the pin of these kernels:
+//   per-view checks (an optional per-slot mask drops rows first) -> every view's pose by the PnP solver (solve(), its camera's
+//   model) -> a timestamp whose two views are OK is a pair -> rig init: R_t = R1_t R0_t^T, T_t = t1_t - R_t t0_t per pair, the
+//   element-wise lower median over the pairs, the polar factor, rvec_of -> joint Levenberg-Marquardt over X (6) and every pair's
+//   P_t (6), CvLevMarq's rules, at most 30 accepted steps, stop at |dp| / |p| < DBL_EPSILON.
+//
+// The normal matrix is block-sparse: a pair's P_t couples only to X.  Per pair, [J_X | J_P | r] (13 columns; J_X = 0 on camera 0's
+// rows) gives a symmetric 13x13 [V_t W_t g_a,t; W_t^T U_t g_b,t; . . cost_t], 91 packed entries.  Each LM attempt eliminates the
+// 6x6 blocks U_t (Schur complement) and solves one damped 6x6 system:
+//   S = V* - sum W_t U_t*^-1 W_t^T,  dX = S^-1 (g_a - sum W_t U_t*^-1 g_b,t),  dP_t = U_t*^-1 g_b,t - U_t*^-1 W_t^T dX.
+//
+// Launches (one 64-lane wave per timestamp unless noted):
+//   overlap         only for a pool with a mask (one wave per view against every other view): a view's kept rows are listed at its
+//                   own slots of the workspace, so its views' slot ranges must not meet
+//   ident           the index list 0, 1, 2, ... that a pool without a mask reads its rows through
+//   init_views      grid (timestamp, camera): the checks; with a mask the kept rows compacted in order (ballot + prefix popcount,
+//                   64 rows at a time) into an index list; solve() over an IndexedFrame either way, so a NULL mask and a mask of
+//                   ones run the same instructions on the same values
+//   pairs           (one lane per timestamp) which timestamps pair, their R_t, T_t, P_t = camera 0's pose
+//   (host)          one copy of the T x 12 doubles and the pair flags; the lower medians by std::nth_element
+//   rig             (one wave) the median matrix's polar factor, rvec_of -> X0; the state
+//   evaluate        after the init and after each accepted step: the pair's 91 entries.  The lanes stride over camera 0's rows,
+//                   then camera 1's; the per-row rows of [J | r] are staged in LDS, 64 rows at a time, and lane l sums the
+//                   entries l and l + 64 over them in row order.  The row count is not capped
+//   schur           per attempt: damping, 6x6 Cholesky of U_t*, U_t*^-1 [W_t^T | g_b,t], the pair's part of S and of the rhs
+//   reduce          (one 64-lane block per kChunk = 16 timestamps) the block's 54 partial sums, each by one lane in order
+//   reduce_solve    (one workgroup, kSlices = 16 slices x 64 entry slots) the partials summed slice-wise, the slices by a fixed
+//                   tree, diag(sum V) damped, 6x6 Cholesky -> dX.  4,096 timestamps: 16 + 16 serial additions and 4 tree levels
+//   trial           the pair's dP, trial pose and trial cost per camera, its share of |dp|^2 and |p|^2
+//   decide          (one workgroup) accept or reject, lg, the stop test; a state word for the host, the outputs when done
+// The LM loop runs on the host: it reads the state word after every attempt (the number of attempts depends on the data), so the
+// call synchronises its stream and cannot be captured in a graph.  Every sum has a fixed order (no atomics): two calls on the same
+// input give the same bits.  No device memory is allocated: the caller passes the workspace.
+#include "dcx_pnp_dev.h"
+
+#include <algorithm>
+#include <vector>
+
+namespace {
+
+constexpr int kStereoMaxIter = 30;
+constexpr double kStereoEps = 2.220446049250313e-16;     // DBL_EPSILON
+constexpr int kRedThreads = 1024;                         // decide's one-workgroup reduction over timestamps
+constexpr int kChunk = 16;                                // reduce: timestamps per block (first fan-in)
+constexpr int kSlices = 16;                               // reduce_solve: slices of the blocks' partials (second fan-in)
+constexpr int kEntries = 91;                              // packed 13x13: [J_X (6) | J_P (6) | r]
+constexpr int kCost = 90;                                 // pk<13>(12, 12)
+constexpr int kTot = 54;                                  // sum V (21), sum g_a (6), sum S_t (21), sum W U*^-1 g_b (6)
+constexpr int kYZ = 42;                                   // U*^-1 W^T (6 x 6, row major) and U*^-1 g_b (6)
+constexpr int kSC = 27;                                   // the pair's part of S (21 packed) and of the rhs (6)
+constexpr int kLdsStride = 13;
+
+enum : int { kNextEvaluate = 0, kNextSchur = 1, kFinished = 2 };
+enum : int { kOverlap = 0, kHeadWords = 2 };
+
+struct StereoState {
+    double x[6], x_trial[6], dx[6];
+    double prev_cost;
+    double result[16];       // h_result
+    int lg, iters, attempts, code;
+};
+constexpr int kState = 512;              // bytes reserved for StereoState
+static_assert(sizeof(StereoState) <= kState, "state");
+
+struct SPool {
+    const int32_t* counts;
+    const int32_t* starts;
+    const int32_t* rows;
+    const float* xy;                     // or null: the integer rows are the image points
+    const uint8_t* mask;                 // or null: every row is kept
+    int pool;
+};
+
+struct Board {
+    int n_ids, rm1;
+    double square_len;
+};
+
+struct Med {
+    double v[12];                        // the lower medians of R_t (9, row major) and T_t (3)
+};
+
+struct Ws {
+    StereoState* st;
+    double *m, *yz, *sc, *part, *pose, *trial_pose, *trial, *vpose, *rig;   // trial = {cost 0, cost 1, |dp|^2, |p|^2}
+    int32_t *head, *pair, *fail, *pfail, *count, *idx0, *idx1, *ident;
+};
+
+__host__ __device__ inline size_t up8(size_t n) { return (n + 7) & ~(size_t)7; }
+inline int chunks_of(int batch) { return (batch + kChunk - 1) / kChunk; }
+
+size_t ws_layout(void* base, int batch, int pool0, int pool1, Ws* w) {
+    size_t at = 0;
+    char* p = (char*)base;
+    auto take = [&](size_t bytes) {
+        char* q = p + at;
+        at += up8(bytes);
+        return q;
+    };
+    const size_t B = (size_t)batch, G = (size_t)chunks_of(batch), d = sizeof(double), i = sizeof(int32_t);
+    Ws r;
+    r.st = (StereoState*)take(kState);
+    r.m = (double*)take(B * kEntries * d);
+    r.yz = (double*)take(B * kYZ * d);
+    r.sc = (double*)take(B * kSC * d);
+    r.part = (double*)take(G * kTot * d);
+    r.pose = (double*)take(B * 6 * d);
+    r.trial_pose = (double*)take(B * 6 * d);
+    r.trial = (double*)take(B * 4 * d);
+    r.vpose = (double*)take(B * 12 * d);
+    r.rig = (double*)take(B * 12 * d);
+    r.head = (int32_t*)take(kHeadWords * i);
+    r.pair = (int32_t*)take(B * i);
+    r.fail = (int32_t*)take(B * i);
+    r.pfail = (int32_t*)take(G * i);
+    r.count = (int32_t*)take(B * 2 * i);
+    r.idx0 = (int32_t*)take((size_t)pool0 * i);
+    r.idx1 = (int32_t*)take((size_t)pool1 * i);
+    r.ident = (int32_t*)take((size_t)(pool0 > pool1 ? pool0 : pool1) * i);
+    if (w) *w = r;
+    return at;
+}
+
+bool sizes_ok(int batch, int pool0, int pool1) { return batch > 0 && pool0 >= 0 && pool1 >= 0; }
+
+// View (t, c) as the later kernels read it: its kept rows through the index list init_views left.
+__device__ __forceinline__ IndexedFrame view_frame(const SPool& pl, const Board& bd, const Ws& ws, int t, int c) {
+    const long long s0 = pl.starts[t];
+    const Frame f{pl.rows + 4 * s0, pl.xy ? pl.xy + 2 * s0 : nullptr, pl.counts[t], bd.rm1, bd.square_len};
+    return IndexedFrame{f, pl.mask ? (c ? ws.idx1 : ws.idx0) + s0 : ws.ident, ws.count[2 * t + c]};
+}
+
+// ---------------------------------------------------------------------------------------------------------------- init
+
+// One wave per view of a pool with a mask: does its slot range (the part inside the pool) meet another view's?
+__global__ __launch_bounds__(kLanes) void stereo_overlap_kernel(SPool pl, int batch, int32_t* __restrict__ head) {
+    const int b = blockIdx.x;
+    const long long n = pl.counts[b], s0 = pl.starts[b];
+    if (n <= 0) return;
+    const long long lo = s0 < 0 ? 0 : s0, hi = s0 + n < pl.pool ? s0 + n : pl.pool;
+    if (lo >= hi) return;
+    bool hit = false;
+    for (int o = threadIdx.x; o < batch; o += kLanes) {
+        const long long on = pl.counts[o], os = pl.starts[o];
+        if (o == b || on <= 0) continue;
+        const long long olo = os < 0 ? 0 : os, ohi = os + on < pl.pool ? os + on : pl.pool;
+        hit |= olo < ohi && olo < hi && lo < ohi;
+    }
+    if (__any(hit) && threadIdx.x == 0) head[kOverlap] = 1;
+}
+
+__global__ __launch_bounds__(256) void stereo_ident_kernel(int n, int32_t* __restrict__ ident) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) ident[i] = i;
+}
+
+__global__ __launch_bounds__(kLanes) void stereo_init_views_kernel(SPool pl0, SPool pl1, PnpCamera cam0, PnpCamera cam1, Board bd,
+                                                                   int32_t* __restrict__ status, double* __restrict__ view_info,
+                                                                   Ws ws) {
+    const int t = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
+    const SPool pl = c ? pl1 : pl0;
+    const int n = pl.counts[t], s0 = pl.starts[t];
+    int st = DCX_PNP_OK, kept = 0;
+    const int32_t* idx = ws.ident;
+    if (n <= 0) {
+        st = DCX_PNP_TOO_FEW;
+    } else if (s0 < 0 || (long long)s0 + n > (long long)pl.pool) {
+        st = DCX_PNP_TRUNCATED;               // (its slots are not read)
+    } else {
+        bool bad = false;
+        if (pl.mask) {
+            int32_t* list = (c ? ws.idx1 : ws.idx0) + s0;
+            for (int base = 0; base < n; base += kLanes) {
+                const int i = base + lane;
+                const bool in = i < n && pl.mask[(long long)s0 + i] != 0;
+                const unsigned long long m = __ballot(in);
+                if (in) {
+                    list[kept + __popcll(m & ((1ull << lane) - 1ull))] = i;
+                    const int id = pl.rows[4 * ((long long)s0 + i) + 2];
+                    bad |= id < 0 || id >= bd.n_ids;
+                }
+                kept += __popcll(m);
+            }
+            idx = list;
+        } else {
+            for (int i = lane; i < n; i += kLanes) {
+                const int id = pl.rows[4 * ((long long)s0 + i) + 2];
+                bad |= id < 0 || id >= bd.n_ids;
+            }
+            kept = n;
+        }
+        __syncthreads();                      // one wave: the list is read below by other lanes than wrote it
+        if (kept < 4) st = DCX_PNP_TOO_FEW;
+        else if (__any(bad)) st = DCX_PNP_BAD_ID;
+    }
+    double out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (st == DCX_PNP_OK) {
+        const PnpCamera cam = c ? cam1 : cam0;
+        const Frame f{pl.rows + 4 * (long long)s0, pl.xy ? pl.xy + 2 * (long long)s0 : nullptr, n, bd.rm1, bd.square_len};
+        const IndexedFrame g{f, idx, kept};
+        st = solve(g, cam, out);
+    }
+    if (lane == 0) {
+        const long long v = 2 * (long long)t + c;
+        status[v] = st;
+        view_info[2 * v] = 0.0;
+        view_info[2 * v + 1] = (double)kept;
+        ws.count[v] = kept;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) ws.vpose[6 * v + i] = st == DCX_PNP_OK ? out[i] : 0.0;
+    }
+}
+
+__global__ __launch_bounds__(kLanes) void stereo_pairs_kernel(int batch, const int32_t* __restrict__ status,
+                                                              double* __restrict__ pose, Ws ws) {
+    const int t = blockIdx.x * kLanes + threadIdx.x;
+    if (t >= batch) return;
+    const bool pr = status[2 * (long long)t] == DCX_PNP_OK && status[2 * (long long)t + 1] == DCX_PNP_OK;
+    ws.pair[t] = pr ? 1 : 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) pose[8 * (long long)t + i] = 0.0;
+    double p0[6], p1[6], rig[12];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        p0[i] = ws.vpose[12 * (long long)t + i];
+        p1[i] = ws.vpose[12 * (long long)t + 6 + i];
+    }
+    double R0[9], R1[9];
+    rodrigues(p0, R0);
+    rodrigues(p1, R1);
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) rig[a * 3 + b] = R1[a * 3] * R0[b * 3] + R1[a * 3 + 1] * R0[b * 3 + 1] + R1[a * 3 + 2] * R0[b * 3 + 2];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) rig[9 + a] = p1[3 + a] - (rig[a * 3] * p0[3] + rig[a * 3 + 1] * p0[4] + rig[a * 3 + 2] * p0[5]);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) ws.rig[12 * (long long)t + i] = pr ? rig[i] : 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) ws.pose[6 * (long long)t + i] = pr ? p0[i] : 0.0;
+}
+
+__global__ __launch_bounds__(kLanes) void stereo_rig_kernel(Med med, int npairs, int batch, Ws ws) {
+    StereoState* st = ws.st;
+    const bool writer = threadIdx.x == 0;
+    double points[1] = {0.0};            // the rows of the pairs found: reported whatever the status
+    for (int t = threadIdx.x; t < batch; t += kLanes)
+        if (ws.pair[t]) points[0] += (double)(ws.count[2 * t] + ws.count[2 * t + 1]);
+    wave_sum(points);
+    if (writer) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) st->result[i] = 0.0;
+        st->lg = -3;
+        st->iters = 0;
+        st->attempts = 0;
+        st->result[9] = (double)npairs;
+        st->result[10] = points[0];
+        st->code = kFinished;
+    }
+    if (npairs == 0) {
+        if (writer) st->result[11] = DCX_STEREO_NO_PAIRS;
+        return;
+    }
+    // polar factor M (M^T M)^-1/2 of the median matrix, as init_pose orthonormalises its decomposition
+    const double* M = med.v;
+    double S[6], W[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = a; b < 3; ++b) S[pk<3>(a, b)] = M[a] * M[b] + M[3 + a] * M[3 + b] + M[6 + a] * M[6 + b];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) W[a][b] = a == b ? 1.0 : 0.0;
+    jacobi<3, 3>(S, W);
+    double iw[3];
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double w = S[pk<3>(c, c)];
+        ok &= w > 0;
+        iw[c] = 1.0 / sqrt(w);
+    }
+    if (!ok) {
+        if (writer) st->result[11] = DCX_STEREO_DEGENERATE;
+        return;
+    }
+    double P[9], Q[9], x[6];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) P[a * 3 + b] = W[a][0] * iw[0] * W[b][0] + W[a][1] * iw[1] * W[b][1] + W[a][2] * iw[2] * W[b][2];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) Q[a * 3 + b] = M[a * 3 + 0] * P[b] + M[a * 3 + 1] * P[3 + b] + M[a * 3 + 2] * P[6 + b];
+    rvec_of(Q, x);
+    bool finite = true;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) x[3 + i] = med.v[9 + i];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) finite &= isfinite(x[i]);
+    if (!writer) return;
+    if (!finite) {
+        st->result[11] = DCX_STEREO_NONFINITE;
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) st->x[i] = x[i];
+    st->code = kNextEvaluate;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- LM
+
+// What every row of a pair shares: R(P), t_P, G[c] = -R [e_c]x Jr(r_P) (d(R m)/dr for the board point m = e_c; the board has
+// z = 0), R(X), T_X and Jr(r_X).
+struct PairBasis {
+    double RP[9], tP[3], G[2][9], RX[9], TX[3], JX[9];
+};
+
+template <bool JAC>
+__device__ __forceinline__ void pair_basis(const double* x, const double* p, PairBasis& B) {
+    rodrigues(p, B.RP);
+    rodrigues(x, B.RX);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        B.tP[i] = p[3 + i];
+        B.TX[i] = x[3 + i];
+    }
+    if (!JAC) return;
+    double Jr[9];
+    right_jacobian(p, Jr);
+    right_jacobian(x, B.JX);
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        double E[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // [e_c]x
+        if (c == 0) { E[5] = -1.0; E[7] = 1.0; } else { E[2] = 1.0; E[6] = -1.0; }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                double s = 0.0;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    double ej = 0.0;
+#pragma unroll
+                    for (int l = 0; l < 3; ++l) ej += E[k * 3 + l] * Jr[l * 3 + j];
+                    s += B.RP[i * 3 + k] * ej;
+                }
+                B.G[c][i * 3 + j] = -s;
+            }
+    }
+}
+
+// One row of camera SECOND's view at (X, P) -> residual (ru, rv); with JAC its two rows of [J_X (6) | J_P (6)]: evaluate()'s
+// projection and derivatives of dcx_pnp_dev.h on the point q = R_P m + t_P (camera 0) or R_X q + T_X (camera 1).  false if the
+// point is not in front of the camera.
+template <bool JAC, bool SECOND>
+__device__ __forceinline__ bool stereo_row(const PnpCamera& cam, const PairBasis& B, double mx, double my, double u, double v,
+                                           double& ru, double& rv, double* ju, double* jv) {
+    double q0[3], q[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) q0[i] = B.RP[i * 3] * mx + B.RP[i * 3 + 1] * my + B.tP[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        q[i] = SECOND ? B.RX[i * 3] * q0[0] + B.RX[i * 3 + 1] * q0[1] + B.RX[i * 3 + 2] * q0[2] + B.TX[i] : q0[i];
+    if (!(q[2] > 0)) return false;
+    const double* k = cam.k;
+    const double iz = 1.0 / q[2], x = q[0] * iz, y = q[1] * iz;
+    const double r2 = x * x + y * y;
+    const double num = 1 + r2 * (k[0] + r2 * (k[1] + r2 * k[4]));
+    const double den = 1 + r2 * (k[5] + r2 * (k[6] + r2 * k[7]));
+    const double g = num / den;
+    const double xd = x * g + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x);
+    const double yd = y * g + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y;
+    ru = cam.fx * xd + cam.cx - u;
+    rv = cam.fy * yd + cam.cy - v;
+    if (!JAC) return true;
+    const double dg = ((k[0] + r2 * (2 * k[1] + 3 * k[4] * r2)) * den - num * (k[5] + r2 * (2 * k[6] + 3 * k[7] * r2))) / (den * den);
+    const double dxd_dx = g + 2 * x * x * dg + 2 * k[2] * y + 6 * k[3] * x;
+    const double dxd_dy = 2 * x * y * dg + 2 * k[2] * x + 2 * k[3] * y;
+    const double dyd_dx = dxd_dy;
+    const double dyd_dy = g + 2 * y * y * dg + 6 * k[2] * y + 2 * k[3] * x;
+    // d(u, v)/dq
+    const double a0 = cam.fx * dxd_dx, a1 = cam.fx * dxd_dy, b0 = cam.fy * dyd_dx, b1 = cam.fy * dyd_dy;
+    const double du[3] = {a0 * iz, a1 * iz, -(a0 * x + a1 * y) * iz};
+    const double dv[3] = {b0 * iz, b1 * iz, -(b0 * x + b1 * y) * iz};
+    // d(u, v)/dq0: camera 1 sees q0 through R_X
+    double eu[3], ev[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        eu[j] = SECOND ? du[0] * B.RX[j] + du[1] * B.RX[3 + j] + du[2] * B.RX[6 + j] : du[j];
+        ev[j] = SECOND ? dv[0] * B.RX[j] + dv[1] * B.RX[3 + j] + dv[2] * B.RX[6 + j] : dv[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        double su = 0.0, sv = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double dX = mx * B.G[0][c * 3 + j] + my * B.G[1][c * 3 + j];
+            su += eu[c] * dX;
+            sv += ev[c] * dX;
+        }
+        ju[6 + j] = su;
+        jv[6 + j] = sv;
+        ju[9 + j] = eu[j];
+        jv[9 + j] = ev[j];
+    }
+    if (SECOND) {
+        // dq/dr_X = -R_X [q0]x Jr(r_X), so d(u, v)/dr_X = -(e . A), A = [q0]x Jr(r_X)
+        const double S[9] = {0.0, -q0[2], q0[1], q0[2], 0.0, -q0[0], -q0[1], q0[0], 0.0};
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double su = 0.0, sv = 0.0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const double a = S[i * 3] * B.JX[j] + S[i * 3 + 1] * B.JX[3 + j] + S[i * 3 + 2] * B.JX[6 + j];
+                su += eu[i] * a;
+                sv += ev[i] * a;
+            }
+            ju[j] = -su;
+            jv[j] = -sv;
+            ju[3 + j] = du[j];
+            jv[3 + j] = dv[j];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) ju[j] = jv[j] = 0.0;
+    }
+    return true;
+}
+
+// One view's rows added to the pair's 91 entries: 64 rows at a time through LDS, every lane its two entries in row order.
+template <bool SECOND>
+__device__ __forceinline__ void accumulate_view(const IndexedFrame& f, const PnpCamera& cam, const PairBasis& B,
+                                                double (*sj)[kLdsStride], const int* ea, const int* eb, double* acc, bool& behind) {
+    const int lane = threadIdx.x;
+    for (int c0 = 0; c0 < f.n; c0 += kLanes) {
+        const int i = c0 + lane;
+        double ju[13], jv[13];
+#pragma unroll
+        for (int j = 0; j < 13; ++j) ju[j] = jv[j] = 0.0;
+        if (i < f.n) {
+            double mx, my, u, v, ru, rv;
+            f.load(i, mx, my, u, v);
+            if (stereo_row<true, SECOND>(cam, B, mx, my, u, v, ru, rv, ju, jv)) {
+                ju[12] = ru;
+                jv[12] = rv;
+            } else {
+                behind = true;
+#pragma unroll
+                for (int j = 0; j < 13; ++j) ju[j] = jv[j] = 0.0;
+            }
+        }
+        __syncthreads();                     // the previous chunk's rows have been read
+#pragma unroll
+        for (int j = 0; j < 13; ++j) {
+            sj[2 * lane][j] = ju[j];
+            sj[2 * lane + 1][j] = jv[j];
+        }
+        __syncthreads();
+        const int rows = 2 * min(kLanes, f.n - c0);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            if (ea[q] < 0) continue;
+            double s = acc[q];
+            for (int r = 0; r < rows; ++r) s += sj[r][ea[q]] * sj[r][eb[q]];
+            acc[q] = s;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kLanes) void stereo_evaluate_kernel(SPool pl0, SPool pl1, PnpCamera cam0, PnpCamera cam1, Board bd,
+                                                                 Ws ws) {
+    __shared__ double sj[2 * kLanes][kLdsStride];
+    const int t = blockIdx.x, lane = threadIdx.x;
+    if (ws.st->code != kNextEvaluate || !ws.pair[t]) return;
+    double x[6], p[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        x[i] = ws.st->x[i];
+        p[i] = ws.pose[(long long)t * 6 + i];
+    }
+    PairBasis B;
+    pair_basis<true>(x, p, B);
+    // the entries this lane owns: e = lane + 64 q, (ea, eb) its row and column in the packed 13 x 13
+    int ea[2], eb[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        ea[q] = eb[q] = -1;
+        const int e = lane + kLanes * q;
+        if (e >= kEntries) continue;
+        int a = 0, first = 0;
+        while (first + (13 - a) <= e) { first += 13 - a; ++a; }
+        ea[q] = a;
+        eb[q] = a + (e - first);
+    }
+    double acc[2] = {0, 0};
+    bool behind = false;
+    accumulate_view<false>(view_frame(pl0, bd, ws, t, 0), cam0, B, sj, ea, eb, acc, behind);
+    accumulate_view<true>(view_frame(pl1, bd, ws, t, 1), cam1, B, sj, ea, eb, acc, behind);
+    const bool inf = __any(behind);
+    double* m = ws.m + (long long)t * kEntries;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int e = lane + kLanes * q;
+        if (e < kEntries) m[e] = (e == kCost && inf) ? INFINITY : acc[q];
+    }
+}
+
+__global__ __launch_bounds__(kLanes) void stereo_schur_kernel(Ws ws) {
+    __shared__ double sy[7][6];              // U*^-1 W^T's 6 columns, then U*^-1 g_b
+    const int t = blockIdx.x, lane = threadIdx.x;
+    if (ws.st->code == kFinished || !ws.pair[t]) return;
+    const double scale = 1.0 + pow(10.0, (double)ws.st->lg);
+    const double* m = ws.m + (long long)t * kEntries;
+    double u[21], rhs[6], xs[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) u[pk<6>(i, j)] = m[pk<13>(6 + i, 6 + j)];
+    // lane j < 6: column j of U*^-1 W^T (rhs = row j of W); the other lanes: U*^-1 g_b.  Every lane factors U* itself.
+#pragma unroll
+    for (int k = 0; k < 6; ++k) rhs[k] = lane < 6 ? m[pk<13>(lane, 6 + k)] : m[pk<13>(6 + k, 12)];
+    const bool ok = cholesky_solve(u, rhs, scale, xs);
+    if (lane == 0) ws.fail[t] = ok ? 0 : 1;
+    double* sc = ws.sc + (long long)t * kSC;
+    if (!ok) {
+        if (lane < kSC) sc[lane] = 0.0;
+        return;
+    }
+    if (lane < 7) {
+        double* yz = ws.yz + (long long)t * kYZ;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            sy[lane][k] = xs[k];
+            if (lane < 6) yz[k * 6 + lane] = xs[k];
+            else yz[36 + k] = xs[k];
+        }
+    }
+    __syncthreads();
+    if (lane < kSC) {                        // entries 0..20: S_t = W U*^-1 W^T (packed 6x6); 21..26: W U*^-1 g_b
+        int a, c;
+        if (lane < 21) {
+            a = 0;
+            int first = 0;
+            while (first + (6 - a) <= lane) { first += 6 - a; ++a; }
+            c = a + (lane - first);
+        } else {
+            a = lane - 21;
+            c = 6;
+        }
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s += m[pk<13>(a, 6 + k)] * sy[c][k];
+        sc[lane] = s;
+    }
+}
+
+// the step could not be solved: the outputs stay zero but for the counts
+__device__ __forceinline__ void fail(StereoState* st, int status) {
+    st->result[7] = st->iters;
+    st->result[8] = st->attempts;
+    st->result[11] = status;
+    st->code = kFinished;
+}
+
+// First fan-in: block g sums the kTot values over its kChunk timestamps, lane e one value in timestamp order.
+__global__ __launch_bounds__(kLanes) void stereo_reduce_kernel(int batch, Ws ws) {
+    if (ws.st->code == kFinished) return;
+    const int g = blockIdx.x, e = threadIdx.x;
+    int src = 0;                             // where value e lives: in the pair's 91 (m) or in its Schur part (sc)
+    if (e < 21) {
+        int a = 0, first = 0;
+        while (first + (6 - a) <= e) { first += 6 - a; ++a; }
+        src = pk<13>(a, a + (e - first));
+    } else if (e < 27) {
+        src = pk<13>(e - 21, 12);
+    } else if (e < kTot) {
+        src = e - 27;
+    }
+    double s = 0.0;
+    int f = 0;
+    const int end = min(batch, (g + 1) * kChunk);
+    for (int t = g * kChunk; t < end; ++t) {
+        if (!ws.pair[t]) continue;
+        if (e < kTot) s += e < 27 ? ws.m[(long long)t * kEntries + src] : ws.sc[(long long)t * kSC + src];
+        if (e == 0) f |= ws.fail[t];
+    }
+    if (e < kTot) ws.part[(long long)g * kTot + e] = s;
+    if (e == 0) ws.pfail[g] = f;
+}
+
+// Second fan-in and the solve: slice sl sums the blocks sl, sl + kSlices, ... in order, the slices meet in a fixed tree.
+__global__ __launch_bounds__(kSlices * kLanes) void stereo_reduce_solve_kernel(int chunks, Ws ws) {
+    __shared__ double part[kSlices][kLanes];
+    __shared__ int bad[kSlices];
+    StereoState* st = ws.st;
+    if (st->code == kFinished) return;
+    const int t = threadIdx.x, e = t % kLanes, sl = t / kLanes;
+    double s = 0.0;
+    int f = 0;
+    for (int g = sl; g < chunks; g += kSlices) {
+        if (e < kTot) s += ws.part[(long long)g * kTot + e];
+        if (e == 0) f |= ws.pfail[g];
+    }
+    part[sl][e] = s;
+    if (e == 0) bad[sl] = f;
+    for (int h = kSlices / 2; h >= 1; h >>= 1) {
+        __syncthreads();
+        if (sl < h) {
+            part[sl][e] += part[sl + h][e];
+            if (e == 0) bad[sl] |= bad[sl + h];
+        }
+    }
+    __syncthreads();
+    if (t != 0) return;
+    if (bad[0]) {
+        fail(st, DCX_STEREO_DEGENERATE);
+        return;
+    }
+    const double scale = 1.0 + pow(10.0, (double)st->lg);
+    double S[21], rhs[6], x[6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+#pragma unroll
+        for (int c = a; c < 6; ++c) S[pk<6>(a, c)] = part[0][pk<6>(a, c)] * (a == c ? scale : 1.0) - part[0][27 + pk<6>(a, c)];
+        rhs[a] = part[0][21 + a] - part[0][48 + a];
+    }
+    if (!cholesky_solve(S, rhs, 1.0, x)) {
+        fail(st, DCX_STEREO_DEGENERATE);
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        st->dx[i] = x[i];
+        st->x_trial[i] = st->x[i] - x[i];
+    }
+}
+
+template <bool SECOND>
+__device__ __forceinline__ double view_cost(const IndexedFrame& f, const PnpCamera& cam, const PairBasis& B) {
+    double c[1] = {0.0};
+    for (int i = threadIdx.x; i < f.n; i += kLanes) {
+        double mx, my, u, v, ru, rv;
+        f.load(i, mx, my, u, v);
+        if (!stereo_row<false, SECOND>(cam, B, mx, my, u, v, ru, rv, nullptr, nullptr)) {
+            c[0] = INFINITY;
+            continue;
+        }
+        c[0] += ru * ru + rv * rv;
+    }
+    wave_sum(c);
+    return c[0];
+}
+
+__global__ __launch_bounds__(kLanes) void stereo_trial_kernel(SPool pl0, SPool pl1, PnpCamera cam0, PnpCamera cam1, Board bd, Ws ws) {
+    const int t = blockIdx.x, lane = threadIdx.x;
+    if (ws.st->code == kFinished || !ws.pair[t]) return;
+    const double* yz = ws.yz + (long long)t * kYZ;
+    double x[6], p[6];
+    double dn = 0.0, pn = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        double s = yz[36 + k];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) s -= yz[k * 6 + j] * ws.st->dx[j];
+        const double p0 = ws.pose[(long long)t * 6 + k];
+        p[k] = p0 - s;
+        dn += (p[k] - p0) * (p[k] - p0);
+        pn += p0 * p0;
+        x[k] = ws.st->x_trial[k];
+    }
+    PairBasis B;
+    pair_basis<false>(x, p, B);
+    const double c0 = view_cost<false>(view_frame(pl0, bd, ws, t, 0), cam0, B);
+    const double c1 = view_cost<true>(view_frame(pl1, bd, ws, t, 1), cam1, B);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) ws.trial_pose[(long long)t * 6 + k] = p[k];
+        ws.trial[(long long)t * 4 + 0] = c0;
+        ws.trial[(long long)t * 4 + 1] = c1;
+        ws.trial[(long long)t * 4 + 2] = dn;
+        ws.trial[(long long)t * 4 + 3] = pn;
+    }
+}
+
+// Fixed-order tree over the kRedThreads partials in s (LDS), NV values per thread; the totals end in s[0][0..NV).
+template <int NV>
+__device__ __forceinline__ void block_tree(double (*s)[NV]) {
+    const int t = threadIdx.x;
+    for (int h = kRedThreads / 2; h >= 1; h >>= 1) {
+        __syncthreads();
+        if (t < h) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) s[t][j] += s[t + h][j];
+        }
+    }
+    __syncthreads();
+}
+
+// init = 1: after the first evaluate (the initial cost); init = 0: after a trial
+__global__ __launch_bounds__(kRedThreads) void stereo_decide_kernel(int batch, int init, double* __restrict__ pose,
+                                                                    double* __restrict__ view_info, Ws ws) {
+    __shared__ double s[kRedThreads][6];     // cost, |dp|^2, |p|^2, pairs, points, non-finite poses
+    __shared__ int verdict;                  // 0: nothing to commit, 1: commit and continue, 2: commit and finish
+    StereoState* st = ws.st;
+    if (st->code == kFinished) return;
+    const int t = threadIdx.x;
+    double a[6] = {0, 0, 0, 0, 0, 0};
+    for (int b = t; b < batch; b += kRedThreads) {
+        if (!ws.pair[b]) continue;
+        if (init) {
+            a[0] += ws.m[(long long)b * kEntries + kCost];
+        } else {
+            const double* tr = ws.trial + (long long)b * 4;
+            a[0] += tr[0] + tr[1]; a[1] += tr[2]; a[2] += tr[3];
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+                if (!isfinite(ws.trial_pose[(long long)b * 6 + k])) a[5] = 1.0;
+        }
+        a[3] += 1.0;
+        a[4] += (double)(ws.count[2 * b] + ws.count[2 * b + 1]);
+    }
+#pragma unroll
+    for (int j = 0; j < 6; ++j) s[t][j] = a[j];
+    block_tree<6>(s);
+    const double cost = s[0][0], points = s[0][4];
+    if (t == 0) {
+        verdict = 0;
+        st->result[9] = s[0][3];
+        st->result[10] = points;
+        if (init) {
+            if (!isfinite(cost)) {
+                st->result[11] = DCX_STEREO_DEGENERATE;
+                st->code = kFinished;
+            } else {
+                st->prev_cost = cost;
+                st->code = kNextSchur;
+            }
+        } else {
+            st->attempts += 1;
+            bool forced = false;
+            if (!(cost <= st->prev_cost)) {  // (a point behind a camera: cost = inf, rejected like an increase)
+                if (++st->lg <= 16) {
+                    st->code = kNextSchur;   // retry from the same point with more damping
+                } else {
+                    forced = true;
+                }
+            } else {
+                forced = true;
+            }
+            if (forced) {
+                st->lg = max(st->lg - 1, -16);
+                st->iters += 1;
+                double dn = s[0][1], pn = s[0][2];
+                bool bad = s[0][5] != 0.0;
+                for (int i = 0; i < 6; ++i) {
+                    const double d = st->x_trial[i] - st->x[i];
+                    dn += d * d;
+                    pn += st->x[i] * st->x[i];
+                    st->x[i] = st->x_trial[i];
+                    bad |= !isfinite(st->x[i]);
+                }
+                if (st->iters >= kStereoMaxIter || sqrt(dn) < kStereoEps * sqrt(pn)) {
+                    int res = DCX_STEREO_OK;
+                    if (bad || isnan(cost)) res = DCX_STEREO_NONFINITE;
+                    else if (!isfinite(cost)) res = DCX_STEREO_DEGENERATE;
+                    if (res == DCX_STEREO_OK) {
+                        for (int i = 0; i < 6; ++i) st->result[i] = st->x[i];
+                        st->result[6] = sqrt(cost / points);
+                    }
+                    st->result[7] = st->iters;
+                    st->result[8] = st->attempts;
+                    st->result[11] = res;
+                    st->code = kFinished;
+                    verdict = res == DCX_STEREO_OK ? 2 : 1;
+                } else if (!isfinite(cost)) {
+                    // forced at lg > 16 with a point behind a camera: there are no normal equations to go on from
+                    st->result[7] = st->iters;
+                    st->result[8] = st->attempts;
+                    st->result[11] = bad || isnan(cost) ? DCX_STEREO_NONFINITE : DCX_STEREO_DEGENERATE;
+                    st->code = kFinished;
+                    verdict = 1;
+                } else {
+                    st->prev_cost = cost;
+                    st->code = kNextEvaluate;
+                    verdict = 1;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (verdict == 0) return;
+    for (int b = t; b < batch; b += kRedThreads) {
+        if (!ws.pair[b]) continue;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) ws.pose[(long long)b * 6 + k] = ws.trial_pose[(long long)b * 6 + k];
+        if (verdict == 2) {
+            double* o = pose + 8 * (long long)b;
+            const double* tr = ws.trial + (long long)b * 4;
+            const double n0 = (double)ws.count[2 * b], n1 = (double)ws.count[2 * b + 1];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) o[k] = ws.trial_pose[(long long)b * 6 + k];
+            o[6] = sqrt((tr[0] + tr[1]) / (n0 + n1));
+            o[7] = n0 + n1;
+            view_info[4 * (long long)b] = sqrt(tr[0] / n0);
+            view_info[4 * (long long)b + 2] = sqrt(tr[1] / n1);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" size_t dcx_stereo_calibrate_workspace_bytes(int batch, int pool0, int pool1) {
+    if (!sizes_ok(batch, pool0, pool1)) return 0;
+    return ws_layout(nullptr, batch, pool0, pool1, nullptr);
+}
+
+extern "C" int dcx_stereo_calibrate_pool(const int32_t* d_counts0, const int32_t* d_starts0, const int32_t* d_rows0,
+                                         const float* d_xy0, const uint8_t* d_mask0, const int32_t* d_counts1,
+                                         const int32_t* d_starts1, const int32_t* d_rows1, const float* d_xy1,
+                                         const uint8_t* d_mask1, int batch, int pool0, int pool1, int col_count, int row_count,
+                                         double square_len, const double* h_camera9_0, const double* h_dist0, int n_dist0,
+                                         const double* h_camera9_1, const double* h_dist1, int n_dist1, void* d_workspace,
+                                         size_t workspace_bytes, int32_t* d_view_status, double* d_pose, double* d_view_info,
+                                         double* h_result, void* stream) {
+    if (!d_counts0 || !d_starts0 || !d_rows0 || !d_counts1 || !d_starts1 || !d_rows1 || !d_workspace || !d_view_status || !d_pose ||
+        !d_view_info || !h_result)
+        return DCX_E_ARG;
+    if (!sizes_ok(batch, pool0, pool1) || col_count < 2 || row_count < 2) return DCX_E_ARG;
+    if ((long long)(col_count - 1) * (row_count - 1) > 0x7fffffffLL) return DCX_E_ARG;
+    if (!isfinite(square_len) || ((uintptr_t)d_workspace & 7)) return DCX_E_ARG;
+    PnpCamera cam0, cam1;
+    if (!pnp_camera(h_camera9_0, h_dist0, n_dist0, cam0) || !pnp_camera(h_camera9_1, h_dist1, n_dist1, cam1)) return DCX_E_ARG;
+    if (workspace_bytes < ws_layout(nullptr, batch, pool0, pool1, nullptr)) return DCX_E_WS;
+    Ws ws;
+    ws_layout(d_workspace, batch, pool0, pool1, &ws);
+    hipStream_t s = (hipStream_t)stream;
+    const SPool pl0{d_counts0, d_starts0, d_rows0, d_xy0, d_mask0, pool0}, pl1{d_counts1, d_starts1, d_rows1, d_xy1, d_mask1, pool1};
+    const Board bd{(col_count - 1) * (row_count - 1), row_count - 1, square_len};
+    const int chunks = chunks_of(batch);
+    const dim3 stamps((unsigned)batch), views((unsigned)batch, 2), wave(kLanes), one(1), red(kRedThreads);
+    const dim3 blocks((unsigned)chunks), per_lane((unsigned)((batch + kLanes - 1) / kLanes)), solve_threads(kSlices * kLanes);
+
+    DCX_CHECK_HIP(hipMemsetAsync(ws.head, 0, kHeadWords * sizeof(int32_t), s));
+    if (d_mask0) hipLaunchKernelGGL(stereo_overlap_kernel, stamps, wave, 0, s, pl0, batch, ws.head);
+    if (d_mask1) hipLaunchKernelGGL(stereo_overlap_kernel, stamps, wave, 0, s, pl1, batch, ws.head);
+    const int n_ident = !d_mask0 && !d_mask1 ? (pool0 > pool1 ? pool0 : pool1) : !d_mask0 ? pool0 : !d_mask1 ? pool1 : 0;
+    if (n_ident > 0) hipLaunchKernelGGL(stereo_ident_kernel, dim3((unsigned)((n_ident + 255) / 256)), dim3(256), 0, s, n_ident, ws.ident);
+    hipLaunchKernelGGL(stereo_init_views_kernel, views, wave, 0, s, pl0, pl1, cam0, cam1, bd, d_view_status, d_view_info, ws);
+    hipLaunchKernelGGL(stereo_pairs_kernel, per_lane, wave, 0, s, batch, d_view_status, d_pose, ws);
+    DCX_CHECK_HIP(hipGetLastError());
+
+    // the rig init's medians, on the host: one copy of the pairs' R_t, T_t and flags (and the overlap word)
+    std::vector<double> rig((size_t)batch * 12);
+    std::vector<int32_t> pair((size_t)batch);
+    int32_t head[kHeadWords] = {0, 0};
+    DCX_CHECK_HIP(hipMemcpyAsync(rig.data(), ws.rig, rig.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    DCX_CHECK_HIP(hipMemcpyAsync(pair.data(), ws.pair, pair.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    DCX_CHECK_HIP(hipMemcpyAsync(head, ws.head, sizeof(head), hipMemcpyDeviceToHost, s));
+    DCX_CHECK_HIP(hipStreamSynchronize(s));
+    if (head[kOverlap]) return DCX_E_ARG;    // two views of a masked pool share slots
+    Med med;
+    int npairs = 0;
+    {
+        std::vector<double> col;
+        col.reserve((size_t)batch);
+        for (int e = 0; e < 12; ++e) {
+            col.clear();
+            for (int t = 0; t < batch; ++t)
+                if (pair[(size_t)t]) col.push_back(rig[(size_t)t * 12 + e]);
+            npairs = (int)col.size();
+            med.v[e] = 0.0;
+            if (npairs) {
+                std::nth_element(col.begin(), col.begin() + (npairs - 1) / 2, col.end());
+                med.v[e] = col[(size_t)(npairs - 1) / 2];
+            }
+        }
+    }
+    hipLaunchKernelGGL(stereo_rig_kernel, one, wave, 0, s, med, npairs, batch, ws);
+    hipLaunchKernelGGL(stereo_evaluate_kernel, stamps, wave, 0, s, pl0, pl1, cam0, cam1, bd, ws);
+    hipLaunchKernelGGL(stereo_decide_kernel, one, red, 0, s, batch, 1, d_pose, d_view_info, ws);
+    DCX_CHECK_HIP(hipGetLastError());
+    // every attempt ends in decide, which increments `attempts` or finishes: at most 30 accepted steps, each after at most
+    // 20 rejections (lg from -3 climbs to 17), so the loop below always ends by the state word
+    for (int guard = 0; guard < kStereoMaxIter * 40; ++guard) {
+        int code = kFinished;
+        DCX_CHECK_HIP(hipMemcpyAsync(&code, &ws.st->code, sizeof(int), hipMemcpyDeviceToHost, s));
+        DCX_CHECK_HIP(hipStreamSynchronize(s));
+        if (code == kFinished) break;
+        if (code == kNextEvaluate) hipLaunchKernelGGL(stereo_evaluate_kernel, stamps, wave, 0, s, pl0, pl1, cam0, cam1, bd, ws);
+        hipLaunchKernelGGL(stereo_schur_kernel, stamps, wave, 0, s, ws);
+        hipLaunchKernelGGL(stereo_reduce_kernel, blocks, wave, 0, s, batch, ws);
+        hipLaunchKernelGGL(stereo_reduce_solve_kernel, one, solve_threads, 0, s, chunks, ws);
+        hipLaunchKernelGGL(stereo_trial_kernel, stamps, wave, 0, s, pl0, pl1, cam0, cam1, bd, ws);
+        hipLaunchKernelGGL(stereo_decide_kernel, one, red, 0, s, batch, 0, d_pose, d_view_info, ws);
+        DCX_CHECK_HIP(hipGetLastError());
+    }
+    DCX_CHECK_HIP(hipMemcpyAsync(h_result, ws.st->result, 16 * sizeof(double), hipMemcpyDeviceToHost, s));
+    DCX_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}

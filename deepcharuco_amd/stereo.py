@@ -1,0 +1,546 @@
+"""Stereo extrinsic calibration without OpenCV: ``cv2.stereoCalibrate`` with CALIB_FIX_INTRINSIC (its default) from the ChArUco
+corners of two rigidly mounted cameras, on the host and on the GPU.
+
+Two cameras 0 and 1 with known ``(camera_matrix, dist_coeffs)`` (none, 4, 5 or 8 coefficients each, as the PnP entry points take
+them; the two models may differ) see the same board at the same instants: view t of camera 0 and view t of camera 1 belong
+together.  Every corner carries its id, so the two views of a timestamp need NOT share a single id (``cv2.stereoCalibrate`` needs
+the same points in both images).  Unknowns: the rig transform X = (R, T) in cv2's convention, q1 = R q0 + T for a point q0 in
+camera 0's frame, and the board's pose P_t in camera 0's frame for every timestamp that is used.  Cost: the squared pixel distance
+of pi0(P_t o) to the rows of view (0, t) and of pi1(X P_t o) to the rows of view (1, t).  Steps, all in float64:
+
+1. per-view checks with the PnP status codes.  An optional mask per view drops rows first (the format of the inlier masks the
+   consensus calls emit; that is how they compose with this one); then fewer than 4 rows -> TOO_FEW, an id outside the board ->
+   BAD_ID (from a pool also TRUNCATED);
+2. per-view pose: ``pnp._solve`` with that camera's model, unchanged (a failure: DEGENERATE / NONFINITE).  A timestamp is a PAIR,
+   and is used, only if both of its views are PNP_OK; the others are left out and reported per camera;
+3. rig init: per pair R_t = R1_t R0_t^T, T_t = t1_t - R_t t0_t; X0 = the element-wise LOWER median over the pairs of the 9 entries
+   of R_t and the 3 of T_t (element (n - 1) // 2 of the sorted values: no two values are averaged), the median matrix
+   orthonormalised by the polar factor of ``pnp._pose_of_homography`` and passed through ``pnp._rvec_of``.  P_t starts at camera
+   0's own pose;
+4. joint Levenberg-Marquardt over X (6 parameters) and every used P_t (6 each), analytic Jacobians through SO(3)'s right Jacobian
+   as in ``pnp._project``, the CvLevMarq rules of ``calib.py`` exactly (damping diag * (1 + 10^lg), lg from -3, +1 on a rejected
+   step up to 16, then -1 down to -16; a point behind either camera is a rejection), at most 30 accepted steps, stop at
+   |dp| / |p| < DBL_EPSILON over all 6 + 6N parameters.  Each step by block elimination: P_t couples only to X, so the 6x6 blocks
+   U_t are eliminated (Schur complement) and one 6x6 system remains, solved by Cholesky;
+5. outputs: rvec(R), T, rms = sqrt(sum |r|^2 / points used) over both cameras (cv2's return value), per timestamp P_t, both
+   views' status, rms and row count; in Python from those E = [T]x R and F = K1^-T E K0^-1, scaled so that F[2, 2] = 1 where that
+   entry is not zero (as cv2 does).
+
+``stereo_calibrate_host_full`` is the readable definition and the test pin; ``stereo_calibrate_pool`` /
+``stereo_calibrate_device`` run the same steps on the GPU (csrc/dcx_stereo.hip).  The two agree to rounding (summation order), not
+bit for bit.
+
+Deviations from ``cv2.stereoCalibrate``:
+* the rig initialisation takes the median over MATRIX entries (then the polar factor) where cv2 takes it over rotation VECTORS: a
+  rig whose relative rotation is near pi does not wrap (the vectors r and r (1 - 2 pi / |r|) are one rotation and far apart);
+* the stop test uses DBL_EPSILON where cv2's default criteria for stereoCalibrate use 1e-6, for the reason ``calib.py`` gives: a
+  stop decided well above rounding makes host and device stop a whole step apart;
+* the two views of a timestamp need no common id, and their poses are initialised separately;
+* each step is solved by Cholesky of the reduced system; unusable views are reported instead of raising
+  (``stereo_calibrate_host`` raises like cv2).
+"""
+from __future__ import annotations
+
+import ctypes as _ctypes
+import math
+from typing import NamedTuple, Optional, Sequence
+
+import numpy as np
+
+from . import pnp
+from .pnp import (PNP_BAD_ID, PNP_OK, PNP_TOO_FEW, _camera, _cholesky_solve, _dist, _jacobi, _right_jacobian, _rodrigues, _rvec_of,
+                  _skew, _solve)
+
+# overall status (include/deepcharuco_amd.h); per-view statuses are pnp's PNP_*
+STEREO_OK, STEREO_NO_PAIRS, STEREO_DEGENERATE, STEREO_NONFINITE = range(4)
+STEREO_MAX_ITER = 30
+STEREO_EPS = float(np.finfo(np.float64).eps)
+RESULT_WORDS = 16              # h_result of dcx_stereo_calibrate_pool
+REDUCE_CHUNK, REDUCE_SLICES = 16, 16   # csrc/dcx_stereo.hip's kChunk, kSlices: the two fan-ins of the per-attempt reduction
+
+__all__ = ["StereoResult", "stereo_calibrate_host", "stereo_calibrate_host_full", "stereo_calibrate_pool",
+           "stereo_calibrate_device", "workspace_bytes", "essential_fundamental", "STEREO_OK", "STEREO_NO_PAIRS",
+           "STEREO_DEGENERATE", "STEREO_NONFINITE"]
+
+
+class StereoResult(NamedTuple):
+    status: int                  # STEREO_*
+    rms: float                   # sqrt(sum |r|^2 / points used) over both cameras: cv2.stereoCalibrate's return value
+    R: np.ndarray                # 3x3: q1 = R q0 + T
+    T: np.ndarray                # [3]
+    rvec: np.ndarray             # [3] Rodrigues vector of R
+    E: np.ndarray                # 3x3 [T]x R
+    F: np.ndarray                # 3x3 K1^-T E K0^-1, F[2, 2] = 1 where it is not zero
+    view_status: np.ndarray      # int32 [T, 2], pnp.PNP_* per camera
+    rvecs: np.ndarray            # [T, 3] the board's pose P_t in camera 0's frame; zeros unless the pair was used
+    tvecs: np.ndarray            # [T, 3]
+    pair_rms: np.ndarray         # [T] rms over both views of the pair at the solution (px)
+    pair_points: np.ndarray      # int64 [T] rows of both views of a used pair; zeros unless STEREO_OK
+    view_rms: np.ndarray         # [T, 2]
+    view_points: np.ndarray      # int64 [T, 2] rows the view brings (after its mask), used or not
+    iterations: int              # accepted LM steps
+    attempts: int                # LM trial steps (accepted + rejected)
+    pairs_used: int              # the pairs found and their rows, whatever the status
+    points_used: int
+
+
+# ------------------------------------------------------------------------------------------------ the fp64 steps
+
+def _project_q(Q: np.ndarray, img: np.ndarray, K: np.ndarray, k: np.ndarray, jac: bool):
+    """Points Q (n, 3) in a camera's frame -> residuals (projected - observed, px) and, with ``jac``, d(u, v)/dQ (n, 2, 3):
+    ``pnp._project``'s model and derivatives with the pose taken out.  Every Z must be positive (the caller checks)."""
+    iz = 1.0 / Q[:, 2]
+    x, y = Q[:, 0] * iz, Q[:, 1] * iz
+    r2 = x * x + y * y
+    num = 1 + r2 * (k[0] + r2 * (k[1] + r2 * k[4]))
+    den = 1 + r2 * (k[5] + r2 * (k[6] + r2 * k[7]))
+    g = num / den
+    xd = x * g + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x)
+    yd = y * g + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y
+    fx, fy = K[0, 0], K[1, 1]
+    res = np.stack([fx * xd + K[0, 2] - img[:, 0], fy * yd + K[1, 2] - img[:, 1]], 1)
+    if not jac:
+        return res, None
+    dg = ((k[0] + r2 * (2 * k[1] + 3 * k[4] * r2)) * den - num * (k[5] + r2 * (2 * k[6] + 3 * k[7] * r2))) / (den * den)
+    dxd_dx = g + 2 * x * x * dg + 2 * k[2] * y + 6 * k[3] * x
+    dxd_dy = 2 * x * y * dg + 2 * k[2] * x + 2 * k[3] * y
+    dyd_dy = g + 2 * y * y * dg + 6 * k[2] * y + 2 * k[3] * x
+    a0, a1, b0, b1 = fx * dxd_dx, fx * dxd_dy, fy * dxd_dy, fy * dyd_dy
+    D = np.empty((Q.shape[0], 2, 3))
+    D[:, 0, 0], D[:, 0, 1], D[:, 0, 2] = a0 * iz, a1 * iz, -(a0 * x + a1 * y) * iz
+    D[:, 1, 0], D[:, 1, 1], D[:, 1, 2] = b0 * iz, b1 * iz, -(b0 * x + b1 * y) * iz
+    return res, D
+
+
+class _Rows(NamedTuple):
+    """Every row of every used pair, pair by pair, camera 0's rows of a pair before camera 1's."""
+    obj: np.ndarray              # (M, 3) board points
+    img: np.ndarray              # (M, 2)
+    cam: np.ndarray              # (M,) 0 / 1
+    pair: np.ndarray             # (M,) index of the row's pair
+    starts: np.ndarray           # (N,) first row of every pair
+    vstarts: np.ndarray          # (2N,) first row of every view (pair-major)
+
+
+def _rows_of(views) -> _Rows:
+    """Per pair (obj0, img0, obj1, img1) -> the rows of all pairs, pair by pair, camera 0's rows first, in float64."""
+    cam, pair, obj, img, counts = [], [], [], [], []
+    for i, v in enumerate(views):
+        for c in range(2):
+            n = v[2 * c].shape[0]
+            obj.append(np.asarray(v[2 * c], np.float64))
+            img.append(np.asarray(v[2 * c + 1], np.float64))
+            cam.append(np.full(n, c))
+            pair.append(np.full(n, i))
+            counts.append(n)
+    vstarts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+    return _Rows(np.concatenate(obj), np.concatenate(img), np.concatenate(cam), np.concatenate(pair), vstarts[0::2], vstarts)
+
+
+def _skews(v: np.ndarray) -> np.ndarray:
+    S = np.zeros((v.shape[0], 3, 3))
+    S[:, 0, 1], S[:, 0, 2] = -v[:, 2], v[:, 1]
+    S[:, 1, 0], S[:, 1, 2] = v[:, 2], -v[:, 0]
+    S[:, 2, 0], S[:, 2, 1] = -v[:, 1], v[:, 0]
+    return S
+
+
+def _evaluate(rows: _Rows, cams, X: np.ndarray, P: np.ndarray, jac: bool):
+    """Residuals (M, 2) at rig X = (rvec, T) and board poses P (N, 6), and with ``jac`` the rows' Jacobians J_X (M, 2, 6) (zero for
+    camera 0's rows) and J_P (M, 2, 6) with respect to the row's own P_t.  None if a point is not in front of its camera."""
+    RX = _rodrigues(X[:3])
+    RP = np.stack([_rodrigues(p[:3]) for p in P])
+    Q0 = np.einsum("mij,mj->mi", RP[rows.pair], rows.obj) + P[rows.pair, 3:]
+    c1 = rows.cam == 1
+    Q = Q0.copy()
+    Q[c1] = Q0[c1] @ RX.T + X[3:]
+    if not (Q[:, 2] > 0).all():
+        return None
+    M = rows.obj.shape[0]
+    res, D = np.empty((M, 2)), (np.empty((M, 2, 3)) if jac else None)
+    for c, (K, k) in enumerate(cams):
+        sel = rows.cam == c
+        r, d = _project_q(Q[sel], rows.img[sel], K, k, jac)
+        res[sel] = r
+        if jac:
+            D[sel] = d
+    if not jac:
+        return res, None, None
+    JrP = np.stack([_right_jacobian(p[:3]) for p in P])
+    dQ0_dr = -np.einsum("mij,mjk,mkl->mil", RP[rows.pair], _skews(rows.obj), JrP[rows.pair])      # -R_P [o]x Jr(r_P)
+    Dp = D.copy()
+    Dp[c1] = D[c1] @ RX                                        # camera 1 sees Q0 through R_X: d(u, v)/dQ0 = d(u, v)/dQ R_X
+    JP = np.concatenate([Dp @ dQ0_dr, Dp], 2)
+    JX = np.zeros((M, 2, 6))
+    dQ_drx = -np.einsum("ij,mjk,kl->mil", RX, _skews(Q0[c1]), _right_jacobian(X[:3]))              # -R_X [Q0]x Jr(r_X)
+    JX[c1, :, :3] = D[c1] @ dQ_drx
+    JX[c1, :, 3:] = D[c1]
+    return res, JX, JP
+
+
+def _normal_blocks(rows: _Rows, cams, X, P):
+    """The blocks of JtJ and Jtr: U [N, 6, 6] (P_t - P_t), W [N, 6, 6] (X - P_t), V [6, 6] (X - X, summed over the pairs in order),
+    ga [6], gb [N, 6], the per-view costs [N, 2].  None if a point is behind a camera."""
+    ev = _evaluate(rows, cams, X, P, True)
+    if ev is None:
+        return None
+    res, JX, JP = ev
+    s = rows.starts
+    U = np.add.reduceat(np.einsum("mai,maj->mij", JP, JP), s, 0)
+    W = np.add.reduceat(np.einsum("mai,maj->mij", JX, JP), s, 0)
+    Vt = np.add.reduceat(np.einsum("mai,maj->mij", JX, JX), s, 0)
+    gb = np.add.reduceat(np.einsum("mai,ma->mi", JP, res), s, 0)
+    gat = np.add.reduceat(np.einsum("mai,ma->mi", JX, res), s, 0)
+    V, ga = np.zeros((6, 6)), np.zeros(6)
+    for i in range(len(s)):
+        V += Vt[i]
+        ga += gat[i]
+    return U, W, V, ga, gb, _view_costs(rows, res)
+
+
+def _view_costs(rows: _Rows, res: np.ndarray) -> np.ndarray:
+    return np.add.reduceat((res * res).sum(1), rows.vstarts).reshape(-1, 2)
+
+
+def _schur_step(U, W, V, ga, gb, lg: int):
+    """Solve [V* W; W^T U*] [dX; dP] = [ga; gb] with the diagonals of V and of every U_t scaled by 1 + 10^lg (Marquardt), by
+    eliminating the pose blocks: S = V* - sum W_t U_t*^-1 W_t^T, dX = S^-1 (ga - sum W_t U_t*^-1 gb_t),
+    dP_t = U_t*^-1 (gb_t - W_t^T dX).  -> (dX [6], dP [N, 6]), or None if a block is not positive definite."""
+    s = 1.0 + 10.0 ** lg
+    Us = U.copy()
+    d6 = np.arange(6)
+    Us[:, d6, d6] *= s
+    try:
+        np.linalg.cholesky(Us)
+    except np.linalg.LinAlgError:
+        return None
+    Y = np.linalg.solve(Us, W.transpose(0, 2, 1))                  # U_t*^-1 W_t^T  [N, 6, 6]
+    z = np.linalg.solve(Us, gb[:, :, None])[:, :, 0]              # U_t*^-1 gb_t   [N, 6]
+    S = V.copy()
+    S[d6, d6] *= s
+    S -= np.einsum("nij,njk->ik", W, Y)
+    rhs = ga - np.einsum("nij,nj->i", W, z)
+    dx = _cholesky_solve(S, rhs)
+    if dx is None:
+        return None
+    return dx, z - np.einsum("nij,j->ni", Y, dx)
+
+
+def _total(costs: np.ndarray) -> float:
+    c = 0.0
+    for v in costs.sum(1).tolist():
+        c += v
+    return c
+
+
+def _refine(rows: _Rows, cams, X: np.ndarray, P: np.ndarray):
+    """Joint LM (module docstring, step 4) -> (status, X, P, per-view costs [N, 2], accepted steps, attempts)."""
+    blocks = _normal_blocks(rows, cams, X, P)
+    if blocks is None or not math.isfinite(_total(blocks[5])):
+        return STEREO_DEGENERATE, X, P, None, 0, 0
+    vc = blocks[5]
+    prev_cost, lg, iters, attempts = _total(vc), -3, 0, 0
+    while True:
+        U, W, V, ga, gb, _ = blocks
+        prev_x, prev_p = X, P
+        while True:
+            step = _schur_step(U, W, V, ga, gb, lg)
+            if step is None:
+                return STEREO_DEGENERATE, X, P, None, iters, attempts
+            X, P = prev_x - step[0], prev_p - step[1]
+            ev = _evaluate(rows, cams, X, P, False)
+            vc = _view_costs(rows, ev[0]) if ev is not None else None
+            cost = _total(vc) if ev is not None else math.inf
+            attempts += 1
+            if not cost <= prev_cost:              # (a point behind a camera: cost = inf, rejected like an increase)
+                lg += 1
+                if lg <= 16:
+                    continue
+            break
+        lg = max(lg - 1, -16)
+        iters += 1
+        d = np.r_[X - prev_x, (P - prev_p).ravel()]
+        pv = np.r_[prev_x, prev_p.ravel()]
+        if iters >= STEREO_MAX_ITER or math.sqrt(float(d @ d)) < STEREO_EPS * math.sqrt(float(pv @ pv)):
+            break
+        prev_cost = cost
+        blocks = _normal_blocks(rows, cams, X, P)
+        if blocks is None:                         # forced at lg > 16 with a point behind a camera: nothing to go on from
+            bad = not (np.isfinite(X).all() and np.isfinite(P).all())
+            return (STEREO_NONFINITE if bad else STEREO_DEGENERATE), X, P, None, iters, attempts
+    if not (np.isfinite(X).all() and np.isfinite(P).all()) or math.isnan(cost):
+        return STEREO_NONFINITE, X, P, None, iters, attempts
+    if not math.isfinite(cost):
+        return STEREO_DEGENERATE, X, P, None, iters, attempts
+    return STEREO_OK, X, P, vc, iters, attempts
+
+
+def lower_median(values) -> float:
+    """Element (n - 1) // 2 of the sorted values."""
+    v = np.sort(np.asarray(values, np.float64))
+    return float(v[(v.size - 1) // 2])
+
+
+def _rig_init(poses0: np.ndarray, poses1: np.ndarray):
+    """Step 3 -> (status, X0 (6) or None, the sine term of ``_rvec_of`` at the orthonormalised median: its branch switches at
+    1e-5)."""
+    n = poses0.shape[0]
+    Rt, Tt = np.empty((n, 3, 3)), np.empty((n, 3))
+    for i in range(n):
+        Rt[i] = _rodrigues(poses1[i, :3]) @ _rodrigues(poses0[i, :3]).T
+        Tt[i] = poses1[i, 3:] - Rt[i] @ poses0[i, 3:]
+    M = np.array([[lower_median(Rt[:, a, b]) for b in range(3)] for a in range(3)])
+    T = np.array([lower_median(Tt[:, a]) for a in range(3)])
+    ws, W = _jacobi(M.T @ M)                     # polar factor M (M^T M)^-1/2, as pnp._pose_of_homography
+    if not ws.min() > 0:
+        return STEREO_DEGENERATE, None, math.inf
+    Q = M @ (W @ np.diag(1.0 / np.sqrt(ws)) @ W.T)
+    X0 = np.r_[_rvec_of(Q), T]
+    sine = 0.5 * math.sqrt((Q[2, 1] - Q[1, 2]) ** 2 + (Q[0, 2] - Q[2, 0]) ** 2 + (Q[1, 0] - Q[0, 1]) ** 2)
+    if not np.isfinite(X0).all():
+        return STEREO_NONFINITE, None, sine
+    return STEREO_OK, X0, sine
+
+
+def essential_fundamental(R, T, camera0, camera1):
+    """E = [T]x R and F = K1^-T E K0^-1, F scaled so that F[2, 2] = 1 where that entry is not zero (as cv2.stereoCalibrate)."""
+    E = _skew(np.asarray(T, np.float64)) @ np.asarray(R, np.float64)
+    F = np.linalg.inv(np.asarray(camera1, np.float64)).T @ E @ np.linalg.inv(np.asarray(camera0, np.float64))
+    if F[2, 2] != 0.0:
+        F = F / F[2, 2]
+    return E, F
+
+
+def _result(status, X, K0, K1, view_status, view_points, used, P, vc, iters, attempts) -> StereoResult:
+    B = view_status.shape[0]
+    rv, tv, pr, vr = np.zeros((B, 3)), np.zeros((B, 3)), np.zeros(B), np.zeros((B, 2))
+    pp = np.zeros(B, np.int64)
+    points = int(view_points[used].sum())          # the rows of the pairs found: reported whatever the status
+    R, T, rvec, E, F, rms = np.zeros((3, 3)), np.zeros(3), np.zeros(3), np.zeros((3, 3)), np.zeros((3, 3)), 0.0
+    if status == STEREO_OK:
+        pp[used] = view_points[used].sum(1)
+        rvec, T = X[:3].copy(), X[3:].copy()
+        R = _rodrigues(rvec)
+        E, F = essential_fundamental(R, T, K0, K1)
+        rv[used], tv[used] = P[:, :3], P[:, 3:]
+        vr[used] = np.sqrt(vc / view_points[used])
+        pr[used] = np.sqrt(vc.sum(1) / pp[used])
+        rms = math.sqrt(_total(vc) / points)
+    return StereoResult(int(status), float(rms), R, T, rvec, E, F, view_status.astype(np.int32), rv, tv, pr, pp, vr,
+                        view_points.astype(np.int64), int(iters), int(attempts), int(used.size), points)
+
+
+def _mask_pair(masks):
+    if masks is None:
+        return None, None
+    if len(masks) != 2:
+        raise ValueError("masks must be None or a pair (masks of camera 0, masks of camera 1), either of which may be None")
+    return masks[0], masks[1]
+
+
+def stereo_calibrate_host_full(keypoints_list0, keypoints_list1, col_count, row_count, square_len, camera0, dist0, camera1, dist1,
+                               masks=None, pool_order=False, with_margin=False):
+    """The definition (module docstring) -> ``StereoResult`` (with ``with_margin``: ``(result, margin)``).
+
+    ``keypoints_list0`` / ``keypoints_list1``: per timestamp an array of [x, y, id] rows of camera 0 / 1 (an empty array for a
+    timestamp the camera did not see).  Rows are taken in the order the corner pool holds them, as in
+    ``pnp.solve_pnp_ransac_host_full``: id-sorted stably, or as they stand with ``pool_order=True``.  Object points are
+    ``pnp.object_points`` (float32 -> float64), image points float32 -> float64.  ``masks``: None, or a pair (camera 0's,
+    camera 1's) of None or per-timestamp bool arrays in the caller's row order (None: keep every row) that drop rows before the
+    checks.  Nothing raises for unusable views; ValueError for a refused camera or lists of different lengths.
+
+    ``with_margin``: the smallest relative distance of a discrete decision of steps 3 - 5 from its threshold: the sine term of
+    the rig init's matrix -> vector conversion from its switch at 1e-5, and the depth of every used row at the solution from 0
+    (relative to its distance from the camera centre)."""
+    cams = [(_camera(camera0), _dist(dist0)), (_camera(camera1), _dist(dist1))]
+    lists = (keypoints_list0, keypoints_list1)
+    if len(lists[0]) != len(lists[1]):
+        raise ValueError(f"{len(lists[0])} views of camera 0 but {len(lists[1])} of camera 1")
+    B, n_ids = len(lists[0]), (col_count - 1) * (row_count - 1)
+    mk = _mask_pair(masks)
+    view_status = np.full((B, 2), PNP_OK, np.int32)
+    view_points = np.zeros((B, 2), np.int64)
+    poses = np.zeros((B, 2, 6))
+    obj_l, img_l = [[None, None] for _ in range(B)], [[None, None] for _ in range(B)]
+    for t in range(B):
+        for c in range(2):
+            kp = np.asarray(lists[c][t])
+            kp = kp.reshape(-1, 3) if kp.size else np.zeros((0, 3))
+            keep = np.ones(kp.shape[0], bool)
+            if mk[c] is not None and mk[c][t] is not None:
+                keep = np.asarray(mk[c][t]).astype(bool).ravel()
+                if keep.size != kp.shape[0]:
+                    raise ValueError(f"view ({c}, {t}) has {kp.shape[0]} rows but its mask {keep.size}")
+            order = np.arange(kp.shape[0]) if pool_order else np.argsort(kp[:, 2], kind="stable")
+            kp = kp[order][keep[order]]
+            view_points[t, c] = kp.shape[0]
+            if kp.shape[0] < 4:
+                view_status[t, c] = PNP_TOO_FEW
+                continue
+            ids = kp[:, 2].astype(np.int64)
+            if ids.min() < 0 or ids.max() >= n_ids:
+                view_status[t, c] = PNP_BAD_ID
+                continue
+            obj_l[t][c] = pnp.object_points(ids, col_count, row_count, square_len)
+            img_l[t][c] = kp[:, :2].astype(np.float32)
+            st, pose = _solve(obj_l[t][c], img_l[t][c], *cams[c])
+            view_status[t, c] = st
+            poses[t, c] = pose[:6]
+    used = np.flatnonzero((view_status == PNP_OK).all(1))
+
+    def done(status, X=None, P=None, vc=None, iters=0, attempts=0, margin=math.inf):
+        r = _result(status, X, cams[0][0], cams[1][0], view_status, view_points, used, P, vc, iters, attempts)
+        return (r, margin) if with_margin else r
+
+    if not used.size:
+        return done(STEREO_NO_PAIRS)
+    st, X0, sine = _rig_init(poses[used, 0], poses[used, 1])
+    margin = abs(sine - 1e-5) / 1e-5
+    if st != STEREO_OK:
+        return done(st, margin=margin)
+    rows = _rows_of([(obj_l[t][0], img_l[t][0], obj_l[t][1], img_l[t][1]) for t in used])
+    st, X, P, vc, iters, attempts = _refine(rows, cams, X0, poses[used, 0].copy())
+    if st == STEREO_OK and with_margin:
+        RX = _rodrigues(X[:3])
+        Q0 = np.einsum("mij,mj->mi", np.stack([_rodrigues(p[:3]) for p in P])[rows.pair], rows.obj) + P[rows.pair, 3:]
+        Q = np.where((rows.cam == 1)[:, None], Q0 @ RX.T + X[3:], Q0)
+        margin = min(margin, float((Q[:, 2] / np.linalg.norm(Q, axis=1)).min()))
+    return done(st, X, P, vc, iters, attempts, margin)
+
+
+def _bad_id_error(col_count, row_count):
+    return IndexError(f"corner id outside [0, {(col_count - 1) * (row_count - 1)}) for a {col_count}x{row_count} board")
+
+
+def _raise_like_cv2(r: StereoResult, col_count, row_count):
+    if (r.view_status == PNP_BAD_ID).any():
+        raise _bad_id_error(col_count, row_count)
+    bad = np.argwhere(r.view_status != PNP_OK)
+    if bad.size:
+        t, c = (int(v) for v in bad[0])
+        raise ValueError(f"view {t} of camera {c} cannot be used (status {int(r.view_status[t, c])})")
+    if r.status != STEREO_OK:
+        raise ValueError(f"stereo calibration failed (status {r.status})")
+
+
+def stereo_calibrate_host(keypoints_list0, keypoints_list1, col_count, row_count, square_len, camera0, dist0, camera1, dist1,
+                          masks=None):
+    """cv2.stereoCalibrate's 9-tuple ``(rms, K0, d0, K1, d1, R, T (3, 1), E, F)`` with the intrinsics as they were given
+    (CALIB_FIX_INTRINSIC).  Raises where cv2 would: ValueError for a view that cannot be used (too few rows, degenerate) or a failed
+    calibration, IndexError for an id outside the board."""
+    r = stereo_calibrate_host_full(keypoints_list0, keypoints_list1, col_count, row_count, square_len, camera0, dist0, camera1,
+                                   dist1, masks)
+    _raise_like_cv2(r, col_count, row_count)
+    d0 = np.zeros((1, 0)) if dist0 is None else np.asarray(dist0, np.float64).reshape(1, -1).copy()
+    d1 = np.zeros((1, 0)) if dist1 is None else np.asarray(dist1, np.float64).reshape(1, -1).copy()
+    return (r.rms, _camera(camera0).copy(), d0, _camera(camera1).copy(), d1, r.R, r.T.reshape(3, 1).copy(), r.E, r.F)
+
+
+# ------------------------------------------------------------------------------------------------ the device solver
+
+def workspace_bytes(batch: int, pool0: int, pool1: int) -> int:
+    """Bytes of device workspace ``stereo_calibrate_pool`` needs."""
+    from . import _lib
+    n = int(_lib.lib().dcx_stereo_calibrate_workspace_bytes(int(batch), int(pool0), int(pool1)))
+    if n == 0:
+        raise ValueError("batch >= 1 and pool0, pool1 >= 0 are required")
+    return n
+
+
+def _pool_ptrs(packed, batch, pool, refined):
+    import torch
+    if packed.dtype != torch.int32 or not packed.is_contiguous() or packed.numel() < 2 * batch + (6 if refined else 4) * pool:
+        raise ValueError("packed must be a contiguous int32 corner pool of at least packed_len(batch, pool) words")
+    base = packed.data_ptr()
+    rows_p = base + 8 * batch
+    return base, base + 4 * batch, rows_p, rows_p + 16 * pool if refined else None
+
+
+def stereo_calibrate_pool(packed0, packed1, batch: int, pool0: int, pool1: int, refined: bool, col_count, row_count, square_len,
+                          camera0, dist0, camera1, dist1, masks=None) -> StereoResult:
+    """The rig of two cameras from two ``infer_batch_device`` results of ``batch`` frames each, read in place from the two corner
+    pools (the conventions of ``pnp.solve_pnp_pool``; frame t of ``packed0`` and frame t of ``packed1`` were taken at the same
+    instant).  ``masks``: None, or a pair of None / contiguous uint8 device tensors of at least ``pool0`` / ``pool1`` values by
+    SLOT, the ``inliers`` that ``pnp.solve_pnp_ransac_pool`` and ``calib.calibrate_charuco_ransac_pool`` write: rows with 0 are
+    dropped before the checks.  With a mask the slot ranges of that pool's views must not overlap (DcxError).  The call
+    synchronises the current stream (the rig init's median and the LM loop's state word are read on the host) and cannot be
+    captured in a graph."""
+    import torch
+    from . import _lib
+    dev = packed0.device
+    if packed1.device != dev:
+        raise ValueError("the two pools must be on one device")
+    p0, p1 = _pool_ptrs(packed0, batch, pool0, refined), _pool_ptrs(packed1, batch, pool1, refined)
+    mk = list(_mask_pair(masks))
+    for c, pool in enumerate((pool0, pool1)):
+        m = mk[c]
+        if m is not None and (m.device != dev or m.dtype != torch.uint8 or m.numel() < pool or not m.is_contiguous()):
+            raise ValueError(f"mask {c} must be a contiguous uint8 tensor of at least {pool} values on {dev}")
+    cam0, d0, n0 = pnp._camera_args(camera0, dist0)
+    cam1, d1, n1 = pnp._camera_args(camera1, dist1)
+    st = torch.empty((batch, 2), dtype=torch.int32, device=dev)
+    pose = torch.empty((batch, pnp.POSE_WORDS), dtype=torch.float64, device=dev)
+    info = torch.empty((batch, 2, 2), dtype=torch.float64, device=dev)
+    nbytes = workspace_bytes(batch, pool0, pool1)
+    ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev)
+    res = (_ctypes.c_double * RESULT_WORDS)()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().dcx_stereo_calibrate_pool(
+            *p0, _lib.ptr(mk[0]), *p1, _lib.ptr(mk[1]), int(batch), int(pool0), int(pool1), int(col_count), int(row_count),
+            float(square_len), cam0, d0, n0, cam1, d1, n1, ws.data_ptr(), nbytes, st.data_ptr(), pose.data_ptr(), info.data_ptr(),
+            res, _lib.current_stream()), "dcx_stereo_calibrate_pool")
+        st_h, pose_h, info_h = st.cpu().numpy(), pose.cpu().numpy(), info.cpu().numpy()
+    r = np.array(res[:], np.float64)
+    status = int(r[11])
+    R, E, F = np.zeros((3, 3)), np.zeros((3, 3)), np.zeros((3, 3))
+    if status == STEREO_OK:
+        R = _rodrigues(r[0:3])
+        E, F = essential_fundamental(R, r[3:6], _camera(camera0), _camera(camera1))
+    return StereoResult(status, float(r[6]), R, r[3:6].copy(), r[0:3].copy(), E, F, st_h.astype(np.int32), pose_h[:, 0:3].copy(),
+                        pose_h[:, 3:6].copy(), pose_h[:, 6].copy(), pose_h[:, 7].astype(np.int64), info_h[:, :, 0].copy(),
+                        info_h[:, :, 1].astype(np.int64), int(r[7]), int(r[8]), int(r[9]), int(r[10]))
+
+
+def _slot_mask(keypoints_list, masks, pool, dev):
+    """Per-view masks in the caller's row order -> a uint8 device tensor by slot of the pool ``pnp._pack`` lays (stable id sort)."""
+    import torch
+    out = np.ones(pool, np.uint8)
+    s = 0
+    for t, kp in enumerate(keypoints_list):
+        kp = np.asarray(kp)
+        kp = kp.reshape(-1, 3) if kp.size else np.zeros((0, 3))
+        n = kp.shape[0]
+        if masks[t] is not None:
+            m = np.asarray(masks[t]).astype(bool).ravel()
+            if m.size != n:
+                raise ValueError(f"view {t} has {n} rows but its mask {m.size}")
+            out[s:s + n] = m[np.argsort(kp[:, 2], kind="stable")]
+        s += n
+    return torch.from_numpy(out).to(dev)
+
+
+def stereo_calibrate_device(keypoints_list0: Sequence, keypoints_list1: Sequence, col_count, row_count, square_len, camera0, dist0,
+                            camera1, dist1, masks=None, device="cuda") -> StereoResult:
+    """``stereo_calibrate_host_full`` on the GPU from ``infer_image``-format keypoint arrays ([x, y, id] rows; one list per
+    camera, equally long) -> ``StereoResult``.  ``masks`` as for the host definition.  IndexError if a view with >= 4 rows carries
+    an id outside the board."""
+    import torch
+    from .models._handles import require_cuda
+    dev = require_cuda(device)
+    pnp._camera_args(camera0, dist0)                          # ValueError before anything is uploaded
+    pnp._camera_args(camera1, dist1)
+    if len(keypoints_list0) != len(keypoints_list1):
+        raise ValueError(f"{len(keypoints_list0)} views of camera 0 but {len(keypoints_list1)} of camera 1")
+    if len(keypoints_list0) == 0:
+        raise ValueError("no views")
+    mk = _mask_pair(masks)
+    packed0, b, pool0 = pnp._pack(keypoints_list0, dev)
+    packed1, _, pool1 = pnp._pack(keypoints_list1, dev)
+    dm = [None if m is None else _slot_mask(kl, m, pool, dev)
+          for kl, m, pool in ((keypoints_list0, mk[0], pool0), (keypoints_list1, mk[1], pool1))]
+    with torch.cuda.device(dev):
+        r = stereo_calibrate_pool(packed0, packed1, b, pool0, pool1, True, col_count, row_count, square_len, camera0, dist0,
+                                  camera1, dist1, None if masks is None else tuple(dm))
+    if (r.view_status == PNP_BAD_ID).any():
+        raise _bad_id_error(col_count, row_count)
+    return r

@@ -313,6 +313,53 @@ int dcx_calibrate_ransac_pool(const int32_t* d_counts, const int32_t* d_starts, 
                               int32_t* d_info /* [B][2]: inliers, winner */, uint8_t* d_inliers /* [pool], may be NULL */,
                               double* h_result /* [16] */, void* stream);
 
+/* ---- stereo extrinsic calibration from two corner pools (cv2.stereoCalibrate with CALIB_FIX_INTRINSIC, planar target) ---------
+ * Two rigidly mounted cameras 0 and 1 with known models (h_camera9_c, h_dist_c, n_dist_c as for dcx_solve_pnp_pool; they may
+ * differ) and one corner pool each, laid out as for dcx_solve_pnp_pool, with the same `batch`: frame t of pool 0 and frame t of
+ * pool 1 show the same board at the same instant.  The two views of a timestamp need no common id.  Result: the rig transform
+ * (R, T) in cv2's convention, q1 = R q0 + T, and the board's pose P_t in camera 0's frame for every timestamp used.  All fp64;
+ * deepcharuco_amd/stereo.py restates the steps (stereo_calibrate_host_full):
+ * 1. per view, d_mask_c (uint8 by SLOT of pool c, the format of the d_inliers that dcx_solve_pnp_ransac_pool and
+ *    dcx_calibrate_ransac_pool write; NULL keeps every row) drops the rows with 0; then the checks of dcx_solve_pnp_pool, on
+ *    the rows kept: fewer than 4 DCX_PNP_TOO_FEW, a frame cut by the pool DCX_PNP_TRUNCATED, an id outside the board
+ *    DCX_PNP_BAD_ID.  With a mask the slot ranges of that pool's frames must not overlap (DCX_E_ARG, found on the device: a
+ *    frame's kept rows are listed at its own slots of the workspace; the outputs are then unspecified).
+ * 2. per view, dcx_solve_pnp_pool's solve with that camera's model (a failure: DCX_PNP_DEGENERATE / DCX_PNP_NONFINITE).  A
+ *    timestamp is a pair, and is used, only if both of its views are DCX_PNP_OK.
+ * 3. rig init: per pair R_t = R1_t R0_t^T, T_t = t1_t - R_t t0_t; the element-wise LOWER median over the pairs (element
+ *    (n - 1) / 2 of the sorted values) of the 9 + 3 entries, the median matrix orthonormalised by its polar factor, then
+ *    Rodrigues.  (cv2 takes the median of rotation vectors, which wrap near pi.)  P_t starts at camera 0's own pose.
+ * 4. joint Levenberg-Marquardt over (rvec(R), T) and every pair's P_t on the pixel reprojection error of both cameras, the rules
+ *    of dcx_calibrate_pool (<= 30 accepted steps, stop at |dp|/|p| < DBL_EPSILON where cv2's default criteria use 1e-6), each
+ *    step by block elimination of the pairs' 6x6 pose blocks and a 6x6 Cholesky.
+ * Like dcx_calibrate_pool this entry point SYNCHRONISES `stream`: once for the rig init (the pairs' R_t, T_t are copied to the
+ * host, where the medians are taken) and after every LM attempt (a state word; their number depends on the data), so the call
+ * cannot be captured in a graph.  d_workspace: dcx_stereo_calibrate_workspace_bytes(batch, pool0, pool1) bytes of device
+ * memory, 8-byte aligned (DCX_E_WS if smaller); no device memory is allocated.
+ * d_view_status int32 [B][2]: DCX_PNP_* of view (t, camera).  d_pose f64 [B][8] = P_t as rvec(3), tvec(3), the pair's rms
+ * reprojection error over both views (px), the rows of both views; all zero unless the pair was used and the status is
+ * DCX_STEREO_OK.  d_view_info f64 [B][2][2] = per view its rms at the solution (zero unless its pair was used and the status is
+ * DCX_STEREO_OK) and the rows it brings after its mask (every view; 0 for a frame that is empty or cut by the pool).
+ * h_result f64 [16] = rvec(R) (3), T (3), rms (sqrt(sum |r|^2 / points used) over both cameras, cv2's return value), accepted
+ * LM steps, attempts, pairs used, points used (the pairs found and their rows, whatever the status), DCX_STEREO_* status, 0...;
+ * the first seven are zero unless DCX_STEREO_OK.
+ * No atomics: two calls on the same input give the same bits.                                                               */
+#define DCX_STEREO_OK          0
+#define DCX_STEREO_NO_PAIRS    1   /* no timestamp has two usable views */
+#define DCX_STEREO_DEGENERATE  2   /* the median matrix or a damped step is singular, or the cost is not finite */
+#define DCX_STEREO_NONFINITE   3
+size_t dcx_stereo_calibrate_workspace_bytes(int batch, int pool0, int pool1);   /* 0 for refused arguments */
+int dcx_stereo_calibrate_pool(const int32_t* d_counts0, const int32_t* d_starts0, const int32_t* d_rows0,
+                              const float* d_xy0 /* NULL = use integer rows x,y */, const uint8_t* d_mask0 /* [pool0] or NULL */,
+                              const int32_t* d_counts1, const int32_t* d_starts1, const int32_t* d_rows1,
+                              const float* d_xy1, const uint8_t* d_mask1 /* [pool1] or NULL */,
+                              int batch, int pool0, int pool1, int col_count, int row_count, double square_len,
+                              const double* h_camera9_0, const double* h_dist0, int n_dist0,
+                              const double* h_camera9_1, const double* h_dist1, int n_dist1,
+                              void* d_workspace, size_t workspace_bytes,
+                              int32_t* d_view_status /* [B][2] DCX_PNP_* */, double* d_pose /* [B][8] */,
+                              double* d_view_info /* [B][2][2] */, double* h_result /* [16] */, void* stream);
+
 /* ---- stage-level entry point for kernel tests / roofline measurement -------------------
  * One 3x3 (or 1x1) convolution + bias [+ eval-BN + ReLU] [+ 2x2 max-pool] on C4 tensors
  * using the same MFMA kernel the networks use.  h_* are host arrays in PyTorch layout;
