@@ -83,6 +83,11 @@ SIGNATURES = {
     "dcx_stereo_calibrate_pool": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), _i,
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), _i, _vp, _sz, _vp, _vp, _vp,
                                       C.POINTER(C.c_double), _vp]),
+    "dcx_undistort_rectify_map": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double), _i, C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double), _i, _i, _vp, _vp]),
+    "dcx_rectify_points_pool": (_i, [_vp, _vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), _i, C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), _vp, _vp]),
+    "dcx_remap_u8": (_i, [_vp, _l, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "dcx_conv_layer": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "dcx_nchw_to_c4": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "dcx_c4_to_nchw": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),

@@ -360,6 +360,47 @@ int dcx_stereo_calibrate_pool(const int32_t* d_counts0, const int32_t* d_starts0
                               int32_t* d_view_status /* [B][2] DCX_PNP_* */, double* d_pose /* [B][8] */,
                               double* d_view_info /* [B][2][2] */, double* h_result /* [16] */, void* stream);
 
+/* ---- stereo rectification: the undistort + rectify map, the remap of u8 frames, the corner pool in rectified coordinates ------
+ * What follows dcx_stereo_calibrate_pool: with the rig's rectifying transforms (R1, R2, P1, P2 of
+ * deepcharuco_amd/rectify.py:stereo_rectify_host, Bouguet's construction as cv2.stereoRectify with CALIB_ZERO_DISPARITY; host
+ * code, once per rig) the three calls put both cameras' frames and corners on common epipolar rows.  Cameras as for
+ * dcx_solve_pnp_pool (h_camera9 without skew, n_dist = 0, 4, 5 or 8; DCX_E_ARG otherwise).  h_R9: a 3x3 rotation, row major, NULL =
+ * identity.  h_P12: a 3x4 projection, row major, of which the left 3x3 is used (P[0][1] must be 0, P[0][0] and P[1][1] not),
+ * NULL = K; with both NULL the calls undistort a single camera.  All host arguments are copied into the kernel arguments at the
+ * call.  Each call is one launch on `stream`: no allocation, no synchronisation, no atomics, so two calls give the same bits and
+ * every call can be captured in a hipGraph.  deepcharuco_amd/rectify.py restates the steps.
+ *
+ * dcx_undistort_rectify_map (cv2.initUndistortRectifyMap; fp64, once per camera and rig): d_map int32 [height][width][2],
+ * 8-byte aligned here and in dcx_remap_u8 (DCX_E_ARG otherwise).  For
+ * output pixel (u, v): x = (u - P02) / P00, y = (v - P12) / P11, q = R^T (x, y, 1); the entry is rint(32 m) (5 fractional bits,
+ * ties to even) with m the camera's projection of (q_x / q_z, q_y / q_z) through its distortion model, or INT32_MIN in both
+ * components ("outside") if q_z <= 0 or m is not finite or beyond +-32768 px.  The output size need not be the source's.
+ *
+ * dcx_rectify_points_pool (cv2.undistortPoints with R and P; fp64): every SLOT i < pool of a corner pool, one lane each, whatever
+ * frame it belongs to: the pixel d_xy[i] (or, with d_xy == NULL, the integer x, y of d_rows[i]) -> d_out f64 [pool][2] =
+ * P R undistort(pixel).  Undistortion is Newton on the distortion model's analytic 2x2 Jacobian from the normalised pixel, until
+ * both components of a step are below 1e-15, at most 20 steps (NOT the 5 fixed-point rounds of dcx_solve_pnp_pool: those are
+ * up to 4.8e-3 px off over a 320x240 frame with k1 = -0.25); NaN if it has not converged or the rotated z <= 0.  pool = 0 is
+ * allowed (nothing is launched).
+ *
+ * dcx_remap_u8 (cv2.remap INTER_LINEAR, BORDER_CONSTANT; the per-frame hot path): batch frames d_src (u8, `channels` = 1 or 3
+ * interleaved, rows `pitch` bytes apart, frames `frame_stride` bytes apart, both in bytes as for dcx_bgr2gray) through ONE map ->
+ * d_out u8 [batch][out_h][out_w][channels], dense.  Integer arithmetic, bit-exact against rectify.py:remap_host: with (mx, my) the
+ * entry, x0 = mx >> 5, y0 = my >> 5 (arithmetic), fx = mx & 31, fy = my & 31, taps p00 = (x0, y0), p10 = (x0+1, y0),
+ * p01 = (x0, y0+1), p11 = (x0+1, y0+1), each tap outside the source reading `border` (0..255; so does an "outside" entry),
+ * out = ((32-fx)(32-fy) p00 + fx (32-fy) p10 + (32-fx) fy p01 + fx fy p11 + 512) >> 10 per channel.  This is cv2's 5-bit scheme
+ * with the weights as exact products; cv2 rounds its weight table and patches it to sum to 2^15, so its bits are not claimed.
+ * pitch * src_h must fit an int32 (DCX_E_SHAPE).                                                                              */
+int dcx_undistort_rectify_map(const double* h_camera9, const double* h_dist, int n_dist,
+                              const double* h_R9 /* NULL = identity */, const double* h_P12 /* NULL = K */,
+                              int width, int height, int32_t* d_map /* [height][width][2] */, void* stream);
+int dcx_rectify_points_pool(const int32_t* d_rows, const float* d_xy /* NULL = use integer rows x,y */, int pool,
+                            const double* h_camera9, const double* h_dist, int n_dist,
+                            const double* h_R9 /* NULL = identity */, const double* h_P12 /* NULL = K */,
+                            double* d_out /* [pool][2] */, void* stream);
+int dcx_remap_u8(const uint8_t* d_src, long frame_stride, int pitch, int src_h, int src_w, int channels /* 1 or 3 */,
+                 const int32_t* d_map, int out_h, int out_w, int batch, int border, uint8_t* d_out, void* stream);
+
 /* ---- stage-level entry point for kernel tests / roofline measurement -------------------
  * One 3x3 (or 1x1) convolution + bias [+ eval-BN + ReLU] [+ 2x2 max-pool] on C4 tensors
  * using the same MFMA kernel the networks use.  h_* are host arrays in PyTorch layout;
