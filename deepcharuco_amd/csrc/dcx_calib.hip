@@ -25,6 +25,10 @@
 // The LM loop runs on the host: it reads the state word after every attempt (the number of attempts depends on the data), so
 // the call synchronises its stream and cannot be captured in a graph.  Every sum has a fixed order (no atomics): two calls on
 // the same input give the same bits.  Nothing is allocated: the caller passes the workspace.
+// Shared with dcx_stereo.hip through dcx_mat_dev.h: schur's body (schur_view), the lane's entries (lane_entries), the one-workgroup
+// tree (block_tree), the workspace carver; evaluate's LDS-staged loop mirrors accumulate_rows there (see the kernel).  The camera
+// model, its derivative and the pose columns are dcx_camera_dev.h's (project, pose_basis, pose_columns); project_point() below
+// adds the nine intrinsic columns.
 #include "dcx_pnp_dev.h"
 
 namespace {
@@ -56,26 +60,24 @@ struct Ws {
     CalibState* st;
     double *rows, *m, *yz, *sc, *pose, *trial_pose, *trial;   // trial = {cost, |dp|^2, |p|^2}
     int* fail;
-
-    __host__ __device__ Ws(void* base, int batch) {
-        char* p = (char*)base;
-        st = (CalibState*)p;
-        double* d = (double*)(p + kState);
-        rows = d;            d += (size_t)batch * kRows;
-        m = d;               d += (size_t)batch * kEntries;
-        yz = d;              d += (size_t)batch * kYZ;
-        sc = d;              d += (size_t)batch * kSC;
-        pose = d;            d += (size_t)batch * 6;
-        trial_pose = d;      d += (size_t)batch * 6;
-        trial = d;           d += (size_t)batch * 3;
-        fail = (int*)d;
-    }
 };
 
-size_t ws_bytes(int batch) {
-    if (batch <= 0) return 0;
-    return (size_t)kState + (size_t)batch * (kRows + kEntries + kYZ + kSC + 6 + 6 + 3) * sizeof(double) +
-           (((size_t)batch * sizeof(int) + 7) & ~(size_t)7);
+// -> the bytes needed; *w (if given) = the parts of the workspace at base
+size_t ws_layout(void* base, int batch, Ws* w) {
+    const size_t B = (size_t)batch;
+    Carver c{(char*)base, 0};
+    Ws r;
+    r.st = (CalibState*)c.take<char>(kState);
+    r.rows = c.take<double>(B * kRows);
+    r.m = c.take<double>(B * kEntries);
+    r.yz = c.take<double>(B * kYZ);
+    r.sc = c.take<double>(B * kSC);
+    r.pose = c.take<double>(B * 6);
+    r.trial_pose = c.take<double>(B * 6);
+    r.trial = c.take<double>(B * 3);
+    r.fail = c.take<int>(B);
+    if (w) *w = r;
+    return c.at;
 }
 
 struct Pool {
@@ -92,78 +94,51 @@ struct Pool {
     }
 };
 
-__device__ __forceinline__ PnpCamera camera_of(const double* th) {
-    PnpCamera c;
-    c.fx = th[0]; c.fy = th[1]; c.cx = th[2]; c.cy = th[3];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) c.k[i] = i < 5 ? th[4 + i] : 0.0;
-    return c;
-}
-
 // ---------------------------------------------------------------------------------------------------------------- init
 
 __global__ __launch_bounds__(kLanes) void calib_init_views_kernel(Pool pl, int pool, int n_ids, double cx, double cy,
                                                                   int32_t* __restrict__ status, double* __restrict__ pose, Ws ws) {
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int n = pl.counts[b], s0 = pl.starts[b];
+    int n, s0;
+    int st = frame_status(pl.counts, pl.starts, pl.rows, b, pool, n_ids, n, s0);
     double r[6] = {0, 0, 0, 0, 0, 0};
-    int st;
-    if (n <= 0) {
-        st = DCX_PNP_TOO_FEW;
-    } else if (s0 < 0 || (long long)s0 + n > (long long)pool) {
-        st = DCX_PNP_TRUNCATED;               // (its slots are not read)
-    } else if (n < 4) {
-        st = DCX_PNP_TOO_FEW;
-    } else {
-        bool bad = false;
-        for (int i = lane; i < n; i += kLanes) {
-            const int id = pl.rows[4 * ((long long)s0 + i) + 2];
-            bad |= id < 0 || id >= n_ids;
-        }
-        if (__any(bad)) {
-            st = DCX_PNP_BAD_ID;
-        } else {
-            // the DLT on the pixels themselves: undistort() with fx = fy = 1, cx = cy = 0 and no distortion is the identity
-            PnpCamera ident;
-            ident.fx = ident.fy = 1.0;
-            ident.cx = ident.cy = 0.0;
+    if (st == DCX_PNP_OK) {
+        // the DLT on the pixels themselves: undistort() through the identity camera leaves them as they are
+        const PnpCamera ident = identity_camera();
+        double H[9], mcx, mcy;
+        st = homography(pl.frame(b), ident, false, H, mcx, mcy);
+        if (st == DCX_PNP_OK) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) ident.k[i] = 0.0;
-            double H[9], mcx, mcy;
-            st = homography(pl.frame(b), ident, false, H, mcx, mcy);
-            if (st == DCX_PNP_OK) {
+            for (int j = 0; j < 3; ++j) {        // the principal point subtracted
+                H[j] -= H[6 + j] * cx;
+                H[3 + j] -= H[6 + j] * cy;
+            }
+            double h[3], v[3], d1[3], d2[3], nn[4] = {0, 0, 0, 0};
 #pragma unroll
-                for (int j = 0; j < 3; ++j) {        // the principal point subtracted
-                    H[j] -= H[6 + j] * cx;
-                    H[3 + j] -= H[6 + j] * cy;
-                }
-                double h[3], v[3], d1[3], d2[3], nn[4] = {0, 0, 0, 0};
+            for (int j = 0; j < 3; ++j) {
+                h[j] = H[3 * j];
+                v[j] = H[3 * j + 1];
+                d1[j] = (h[j] + v[j]) * 0.5;
+                d2[j] = (h[j] - v[j]) * 0.5;
+            }
 #pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    h[j] = H[3 * j];
-                    v[j] = H[3 * j + 1];
-                    d1[j] = (h[j] + v[j]) * 0.5;
-                    d2[j] = (h[j] - v[j]) * 0.5;
-                }
+            for (int j = 0; j < 3; ++j) {
+                nn[0] += h[j] * h[j]; nn[1] += v[j] * v[j]; nn[2] += d1[j] * d1[j]; nn[3] += d2[j] * d2[j];
+            }
 #pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    nn[0] += h[j] * h[j]; nn[1] += v[j] * v[j]; nn[2] += d1[j] * d1[j]; nn[3] += d2[j] * d2[j];
-                }
+            for (int j = 0; j < 4; ++j) nn[j] = 1.0 / sqrt(nn[j]);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) nn[j] = 1.0 / sqrt(nn[j]);
+            for (int j = 0; j < 3; ++j) {
+                h[j] *= nn[0]; v[j] *= nn[1]; d1[j] *= nn[2]; d2[j] *= nn[3];
+            }
+            r[0] = h[0] * v[0]; r[1] = h[1] * v[1]; r[2] = -h[2] * v[2];
+            r[3] = d1[0] * d2[0]; r[4] = d1[1] * d2[1]; r[5] = -d1[2] * d2[2];
 #pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    h[j] *= nn[0]; v[j] *= nn[1]; d1[j] *= nn[2]; d2[j] *= nn[3];
-                }
-                r[0] = h[0] * v[0]; r[1] = h[1] * v[1]; r[2] = -h[2] * v[2];
-                r[3] = d1[0] * d2[0]; r[4] = d1[1] * d2[1]; r[5] = -d1[2] * d2[2];
+            for (int j = 0; j < 6; ++j)
+                if (!isfinite(r[j])) st = DCX_PNP_NONFINITE;
+            if (st != DCX_PNP_OK) {
 #pragma unroll
-                for (int j = 0; j < 6; ++j)
-                    if (!isfinite(r[j])) st = DCX_PNP_NONFINITE;
-                if (st != DCX_PNP_OK) {
-#pragma unroll
-                    for (int j = 0; j < 6; ++j) r[j] = 0.0;
-                }
+                for (int j = 0; j < 6; ++j) r[j] = 0.0;
             }
         }
     }
@@ -175,20 +150,6 @@ __global__ __launch_bounds__(kLanes) void calib_init_views_kernel(Pool pl, int p
 #pragma unroll
         for (int i = 0; i < 6; ++i) ws.rows[(long long)b * kRows + i] = r[i];
     }
-}
-
-// Fixed-order tree over the kRedThreads partials in s (LDS), NV values per thread; the totals end in s[0..NV).
-template <int NV>
-__device__ __forceinline__ void block_tree(double (*s)[NV]) {
-    const int t = threadIdx.x;
-    for (int h = kRedThreads / 2; h >= 1; h >>= 1) {
-        __syncthreads();
-        if (t < h) {
-#pragma unroll
-            for (int j = 0; j < NV; ++j) s[t][j] += s[t + h][j];
-        }
-    }
-    __syncthreads();
 }
 
 __global__ __launch_bounds__(kRedThreads) void calib_init_reduce_kernel(int batch, double cx, double cy,
@@ -210,7 +171,7 @@ __global__ __launch_bounds__(kRedThreads) void calib_init_reduce_kernel(int batc
     }
 #pragma unroll
     for (int j = 0; j < 7; ++j) s[t][j] = a[j];
-    block_tree<7>(s);
+    block_tree<kRedThreads, 7>(s);
     if (t != 0) return;
     CalibState* st = ws.st;
     const double a00 = s[0][0], a01 = s[0][1], a11 = s[0][2], b0 = s[0][3], b1 = s[0][4];
@@ -255,26 +216,17 @@ __global__ __launch_bounds__(kLanes) void calib_init_poses_kernel(Pool pl, int32
 
 // ---------------------------------------------------------------------------------------------------------------- LM
 
-// One point's projection at (theta, pose) -> residual (ru, rv); with JAC its two rows of [J_theta | J_pose] (pnp._project's pose
-// columns, calib._project_full's intrinsic columns).  false if the point is not in front of the camera.
+// One point's projection at (theta, pose) -> residual (ru, rv); with JAC its two rows of [J_theta | J_pose]: calib._project_full's
+// intrinsic columns here, the model, its derivative and the pose columns by the header.  false if the point is not in front of
+// the camera.
 template <bool JAC>
 __device__ __forceinline__ bool project_point(const PnpCamera& cam, const double* p, const double* R, const double (*G)[9], double mx,
                                               double my, double u, double v, double& ru, double& rv, double* ju, double* jv) {
-    const double X = R[0] * mx + R[1] * my + p[3];
-    const double Y = R[3] * mx + R[4] * my + p[4];
-    const double Z = R[6] * mx + R[7] * my + p[5];
-    if (!(Z > 0)) return false;
-    const double* k = cam.k;
-    const double iz = 1.0 / Z, x = X * iz, y = Y * iz;
-    const double r2 = x * x + y * y;
-    const double num = 1 + r2 * (k[0] + r2 * (k[1] + r2 * k[4]));
-    const double den = 1 + r2 * (k[5] + r2 * (k[6] + r2 * k[7]));
-    const double g = num / den;
-    const double xd = x * g + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x);
-    const double yd = y * g + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y;
-    ru = cam.fx * xd + cam.cx - u;
-    rv = cam.fy * yd + cam.cy - v;
+    double q[3], du[3], dv[3], x, y, xd, yd;
+    board_point(R, p + 3, mx, my, q);
+    if (!project<JAC>(cam, q, u, v, ru, rv, du, dv, x, y, xd, yd)) return false;
     if (!JAC) return true;
+    const double r2 = x * x + y * y;
     const double r4 = r2 * r2, r6 = r2 * r2 * r2;
     ju[0] = xd;  ju[1] = 0.0; ju[2] = 1.0; ju[3] = 0.0;
     jv[0] = 0.0; jv[1] = yd;  jv[2] = 0.0; jv[3] = 1.0;
@@ -283,55 +235,8 @@ __device__ __forceinline__ bool project_point(const PnpCamera& cam, const double
     ju[6] = cam.fx * (2 * x * y);         jv[6] = cam.fy * (r2 + 2 * y * y);
     ju[7] = cam.fx * (r2 + 2 * x * x);    jv[7] = cam.fy * (2 * x * y);
     ju[8] = cam.fx * (x * r6);            jv[8] = cam.fy * (y * r6);
-    const double dg = ((k[0] + r2 * (2 * k[1] + 3 * k[4] * r2)) * den - num * (k[5] + r2 * (2 * k[6] + 3 * k[7] * r2))) / (den * den);
-    const double dxd_dx = g + 2 * x * x * dg + 2 * k[2] * y + 6 * k[3] * x;
-    const double dxd_dy = 2 * x * y * dg + 2 * k[2] * x + 2 * k[3] * y;
-    const double dyd_dx = dxd_dy;
-    const double dyd_dy = g + 2 * y * y * dg + 6 * k[2] * y + 2 * k[3] * x;
-    const double a0 = cam.fx * dxd_dx, a1 = cam.fx * dxd_dy, b0 = cam.fy * dyd_dx, b1 = cam.fy * dyd_dy;
-    const double du[3] = {a0 * iz, a1 * iz, -(a0 * x + a1 * y) * iz};
-    const double dv[3] = {b0 * iz, b1 * iz, -(b0 * x + b1 * y) * iz};
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        double su = 0.0, sv = 0.0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double dX = mx * G[0][c * 3 + j] + my * G[1][c * 3 + j];
-            su += du[c] * dX;
-            sv += dv[c] * dX;
-        }
-        ju[9 + j] = su;
-        jv[9 + j] = sv;
-        ju[12 + j] = du[j];
-        jv[12 + j] = dv[j];
-    }
+    pose_columns(du, dv, mx, my, G, ju + 9, jv + 9);
     return true;
-}
-
-// R(p) and G[c] = -R [e_c]x Jr(p): d(R m)/dr for the board point m = e_c (the board has z = 0)
-__device__ __forceinline__ void pose_basis(const double* p, double* R, double (*G)[9]) {
-    double Jr[9];
-    rodrigues(p, R);
-    right_jacobian(p, Jr);
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        double E[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // [e_c]x
-        if (c == 0) { E[5] = -1.0; E[7] = 1.0; } else { E[2] = 1.0; E[6] = -1.0; }
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                double s = 0.0;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    double ej = 0.0;
-#pragma unroll
-                    for (int l = 0; l < 3; ++l) ej += E[k * 3 + l] * Jr[l * 3 + j];
-                    s += R[i * 3 + k] * ej;
-                }
-                G[c][i * 3 + j] = -s;
-            }
-    }
 }
 
 constexpr int kLdsStride = 17;     // 16 values per row, padded
@@ -347,20 +252,13 @@ __global__ __launch_bounds__(kLanes) void calib_evaluate_kernel(Pool pl, const i
     for (int i = 0; i < 6; ++i) p[i] = ws.pose[(long long)b * 6 + i];
     double R[9], G[2][9];
     pose_basis(p, R, G);
-    // the entries this lane owns: e = lane + 64 q, (ea, eb) its row and column in the packed 16 x 16
     int ea[3], eb[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        ea[q] = eb[q] = -1;
-        const int e = lane + kLanes * q;
-        if (e >= kEntries) continue;
-        int a = 0, first = 0;
-        while (first + (16 - a) <= e) { first += 16 - a; ++a; }
-        ea[q] = a;
-        eb[q] = a + (e - first);
-    }
+    lane_entries<16, 3>(lane, ea, eb);
     double acc[3] = {0, 0, 0};
     bool behind = false;
+    // dcx_mat_dev.h's accumulate_rows<16, 3, 17>, spelt out: called through it, this kernel's code generation moves (the compiler
+    // then shares the sine and cosine range reductions of pose_basis: 46 instructions fewer, other opcode counts than before).  The
+    // stereo solve runs the shared loop; a change there is a change here.
     for (int c0 = 0; c0 < f.n; c0 += kLanes) {
         const int i = c0 + lane;
         double ju[16], jv[16];
@@ -403,87 +301,14 @@ __global__ __launch_bounds__(kLanes) void calib_evaluate_kernel(Pool pl, const i
     }
 }
 
-// 6x6 Cholesky of u (packed) with its diagonal scaled by `scale` -> L (packed); false if not positive definite
-__device__ __forceinline__ bool cholesky6(const double* u, double scale, double* L) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-            double s = u[pk<6>(i, j)] * (i == j ? scale : 1.0);
-#pragma unroll
-            for (int k = 0; k < j; ++k) s -= L[pk<6>(i, k)] * L[pk<6>(j, k)];
-            if (i == j) {
-                if (!(s > 0)) return false;
-                L[pk<6>(i, i)] = sqrt(s);
-            } else {
-                L[pk<6>(i, j)] = s / L[pk<6>(j, j)];
-            }
-        }
-    }
-    return true;
-}
-
 __global__ __launch_bounds__(kLanes) void calib_schur_kernel(const int32_t* __restrict__ status, Ws ws) {
     __shared__ double sy[10][6];             // U*^-1 W^T's 9 columns, then U*^-1 g_b
     const int b = blockIdx.x, lane = threadIdx.x;
     if (ws.st->code == kFinished || status[b] != DCX_PNP_OK) return;
     const double scale = 1.0 + pow(10.0, (double)ws.st->lg);
-    const double* m = ws.m + (long long)b * kEntries;
-    double u[21], L[21];
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = i; j < 6; ++j) u[pk<6>(i, j)] = m[pk<16>(9 + i, 9 + j)];
-    const bool ok = cholesky6(u, scale, L);
+    const bool ok = schur_view<9>(ws.m + (long long)b * kEntries, scale, lane, sy, ws.yz + (long long)b * kYZ,
+                                  ws.sc + (long long)b * kSC);
     if (lane == 0) ws.fail[b] = ok ? 0 : 1;
-    double* sc = ws.sc + (long long)b * kSC;
-    if (!ok) {
-        if (lane < kSC) sc[lane] = 0.0;
-        return;
-    }
-    if (lane < 10) {                         // lane j < 9: column j of U*^-1 W^T (rhs = row j of W); lane 9: U*^-1 g_b
-        double rhs[6], y[6], x[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) rhs[k] = lane < 9 ? m[pk<16>(lane, 9 + k)] : m[pk<16>(9 + k, 15)];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            double s = rhs[i];
-#pragma unroll
-            for (int k = 0; k < i; ++k) s -= L[pk<6>(i, k)] * y[k];
-            y[i] = s / L[pk<6>(i, i)];
-        }
-#pragma unroll
-        for (int i = 5; i >= 0; --i) {
-            double s = y[i];
-#pragma unroll
-            for (int k = i + 1; k < 6; ++k) s -= L[pk<6>(k, i)] * x[k];
-            x[i] = s / L[pk<6>(i, i)];
-        }
-        double* yz = ws.yz + (long long)b * kYZ;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            sy[lane][k] = x[k];
-            if (lane < 9) yz[k * 9 + lane] = x[k];
-            else yz[54 + k] = x[k];
-        }
-    }
-    __syncthreads();
-    if (lane < kSC) {                        // entries 0..44: S_i = W U*^-1 W^T (packed 9x9); 45..53: W U*^-1 g_b
-        int a, c;
-        if (lane < 45) {
-            a = 0;
-            int first = 0;
-            while (first + (9 - a) <= lane) { first += 9 - a; ++a; }
-            c = a + (lane - first);
-        } else {
-            a = lane - 45;
-            c = 9;
-        }
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) s += m[pk<16>(a, 9 + k)] * sy[c][k];
-        sc[lane] = s;
-    }
 }
 
 // the step could not be solved: the outputs stay zero but for the counts
@@ -498,7 +323,8 @@ __global__ __launch_bounds__(kRedThreads) void calib_reduce_solve_kernel(int bat
     constexpr int kTot = 108;                // sum V (45), sum g_a (9), sum S_i (45), sum W U*^-1 g_b (9)
     __shared__ double part[kSlices][kTot];
     __shared__ int bad[kSlices];
-    // thread 0's small dense solve, indexed in loops: kept in LDS rather than in (scratch-backed) private arrays
+    // thread 0's small dense solve, indexed in loops: kept in LDS rather than in (scratch-backed) private arrays, and rolled, so it
+    // is spelt out here and is not the header's unrolled cholesky_factor / cholesky_substitute on registers
     __shared__ double tot[kTot], S[45], L[45], rhs[9], y[9], x[9];
     CalibState* st = ws.st;
     if (st->code == kFinished) return;
@@ -506,9 +332,9 @@ __global__ __launch_bounds__(kRedThreads) void calib_reduce_solve_kernel(int bat
     if (e < kTot) {
         int src;                             // where entry e lives: in the view's 136 (m) or in its Schur part (sc)
         if (e < 45) {
-            int a = 0, first = 0;
-            while (first + (9 - a) <= e) { first += 9 - a; ++a; }
-            src = pk<16>(a, a + (e - first));
+            int a, c;
+            unpk<9>(e, a, c);
+            src = pk<16>(a, c);
         } else if (e < 54) {
             src = pk<16>(e - 45, 15);
         } else {
@@ -638,7 +464,7 @@ __global__ __launch_bounds__(kRedThreads) void calib_decide_kernel(int batch, in
     }
 #pragma unroll
     for (int j = 0; j < 6; ++j) s[t][j] = a[j];
-    block_tree<6>(s);
+    block_tree<kRedThreads, 6>(s);
     const double cost = s[0][0], views = s[0][3], points = s[0][4];
     if (t == 0) {
         verdict = 0;
@@ -717,7 +543,7 @@ __global__ __launch_bounds__(kRedThreads) void calib_decide_kernel(int batch, in
 
 }  // namespace
 
-extern "C" size_t dcx_calibrate_workspace_bytes(int batch) { return ws_bytes(batch); }
+extern "C" size_t dcx_calibrate_workspace_bytes(int batch) { return batch > 0 ? ws_layout(nullptr, batch, nullptr) : 0; }
 
 extern "C" int dcx_calibrate_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows, const float* d_xy,
                                   int batch, int pool, int col_count, int row_count, double square_len, int image_width,
@@ -727,9 +553,10 @@ extern "C" int dcx_calibrate_pool(const int32_t* d_counts, const int32_t* d_star
     if (batch <= 0 || pool < 0 || col_count < 2 || row_count < 2 || image_width <= 0 || image_height <= 0) return DCX_E_ARG;
     if ((long long)(col_count - 1) * (row_count - 1) > 0x7fffffffLL) return DCX_E_ARG;
     if (!isfinite(square_len)) return DCX_E_ARG;
-    if (workspace_bytes < ws_bytes(batch)) return DCX_E_WS;
+    if (workspace_bytes < ws_layout(nullptr, batch, nullptr)) return DCX_E_WS;
     hipStream_t s = (hipStream_t)stream;
-    const Ws ws(d_workspace, batch);
+    Ws ws;
+    ws_layout(d_workspace, batch, &ws);
     const Pool pl{d_counts, d_starts, d_rows, d_xy, row_count - 1, square_len};
     const double cx = (image_width - 1) * 0.5, cy = (image_height - 1) * 0.5;
     const dim3 views((unsigned)batch), wave(kLanes), one(1), red(kRedThreads);

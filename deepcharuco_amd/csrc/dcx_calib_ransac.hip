@@ -21,6 +21,8 @@
 // A view's slot range is written in the filtered pool, so ranges must not overlap: `overlap` (one wave per view against every other
 // view) looks first and the call is refused before anything else runs.  Nothing is allocated, no atomics, every reduction has a
 // fixed order: two calls give the same bits.  Like dcx_calibrate_pool the call synchronises its stream.
+// From the headers: frame_status, ranges_overlap, the sampler, the four-point homography, row_error2 and best_hypothesis
+// (dcx_pnp_dev.h), append_kept and the workspace carver (dcx_mat_dev.h), identity_camera and camera_of (dcx_camera_dev.h).
 #include "dcx_pnp_dev.h"
 
 namespace {
@@ -48,31 +50,24 @@ struct RWs {
     uint8_t* mask;
 };
 
-__host__ __device__ inline size_t up8(size_t n) { return (n + 7) & ~(size_t)7; }
-
 size_t rws_layout(void* base, int batch, int pool, int iterations, RWs* w) {
     const size_t inner = dcx_calibrate_workspace_bytes(batch);
-    size_t at = 0;
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) {
-        char* q = p + at;
-        at += up8(bytes);
-        return q;
-    };
+    const size_t B = (size_t)batch;
+    Carver c{(char*)base, 0};
     RWs r;
-    r.head = (int32_t*)take(kHeadWords * sizeof(int32_t));
-    r.inner = take(inner);
-    r.scores = (int32_t*)take((size_t)batch * (size_t)iterations * sizeof(int32_t));
-    r.counts = (int32_t*)take((size_t)batch * sizeof(int32_t));
-    r.starts = (int32_t*)take((size_t)batch * sizeof(int32_t));
-    r.vstat = (int32_t*)take((size_t)batch * sizeof(int32_t));
-    r.winner = (int32_t*)take((size_t)batch * sizeof(int32_t));
-    r.changed = (int32_t*)take((size_t)batch * sizeof(int32_t));
-    r.rows = (int32_t*)take((size_t)pool * 4 * sizeof(int32_t));
-    r.xy = (float*)take((size_t)pool * 2 * sizeof(float));
-    r.mask = (uint8_t*)take((size_t)pool);
+    r.head = c.take<int32_t>(kHeadWords);
+    r.inner = c.take<char>(inner);
+    r.scores = c.take<int32_t>(B * (size_t)iterations);
+    r.counts = c.take<int32_t>(B);
+    r.starts = c.take<int32_t>(B);
+    r.vstat = c.take<int32_t>(B);
+    r.winner = c.take<int32_t>(B);
+    r.changed = c.take<int32_t>(B);
+    r.rows = c.take<int32_t>((size_t)pool * 4);
+    r.xy = c.take<float>((size_t)pool * 2);
+    r.mask = c.take<uint8_t>((size_t)pool);
     if (w) *w = r;
-    return at;
+    return c.at;
 }
 
 // Four sampled rows of a view -> the homography board xy - centroid -> raw pixels; false if the sampler or the closed form refuses
@@ -82,11 +77,7 @@ __device__ __forceinline__ bool view_hypothesis(const Frame& f, uint32_t seed, i
     Sample q;
 #pragma unroll
     for (int k = 0; k < 4; ++k) f.load(s[k], q.mx[k], q.my[k], q.x[k], q.y[k]);
-    PnpCamera none;                      // (the overload's camera is unused: the image points are taken as they are)
-    none.fx = none.fy = 1.0;
-    none.cx = none.cy = 0.0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) none.k[i] = 0.0;
+    const PnpCamera none = identity_camera();   // (the overload's camera is unused: the image points are taken as they are)
     return homography(q, none, false, H, mcx, mcy) == DCX_PNP_OK;
 }
 
@@ -105,21 +96,9 @@ __device__ __forceinline__ Frame frame_of(const RPool& pl, int n, int s0) {
     return Frame{pl.rows + 4 * (long long)s0, pl.xy ? pl.xy + 2 * (long long)s0 : nullptr, n, pl.rm1, pl.square_len};
 }
 
-// One wave per view: does its slot range (the part inside the pool) meet another view's?  The lanes share the other views out.
+// One wave per view: does its slot range meet another view's?
 __global__ __launch_bounds__(kLanes) void calib_ransac_overlap_kernel(RPool pl, int batch, int32_t* __restrict__ head) {
-    const int b = blockIdx.x;
-    const long long n = pl.counts[b], s0 = pl.starts[b];
-    if (n <= 0) return;
-    const long long lo = s0 < 0 ? 0 : s0, hi = s0 + n < pl.pool ? s0 + n : pl.pool;
-    if (lo >= hi) return;
-    bool hit = false;
-    for (int o = threadIdx.x; o < batch; o += kLanes) {
-        const long long on = pl.counts[o], os = pl.starts[o];
-        if (o == b || on <= 0) continue;
-        const long long olo = os < 0 ? 0 : os, ohi = os + on < pl.pool ? os + on : pl.pool;
-        hit |= olo < ohi && olo < hi && lo < ohi;
-    }
-    if (__any(hit) && threadIdx.x == 0) head[kOverlap] = 1;
+    if (ranges_overlap(pl.counts, pl.starts, pl.pool, batch, blockIdx.x) && threadIdx.x == 0) head[kOverlap] = 1;
 }
 
 __global__ __launch_bounds__(kLanes) void calib_ransac_consensus_kernel(RPool pl, int iterations, double thr2, uint32_t seed,
@@ -143,13 +122,11 @@ __global__ __launch_bounds__(kLanes) void calib_ransac_consensus_kernel(RPool pl
 }
 
 // Rows base .. base + 63 of the view: the mask slot, and the rows that stay appended in order to the view's share of the filtered
-// pool.  -> the number that stayed.  Wave-wide.
-__device__ __forceinline__ int keep_rows(const RPool& pl, const RWs& ws, int s0, int i, int n, bool in, int count) {
-    const int lane = threadIdx.x;
-    const unsigned long long m = __ballot(in);
-    if (i < n) ws.mask[(long long)s0 + i] = in ? 1 : 0;
+// pool; count moves past them.  Wave-wide.
+__device__ __forceinline__ void keep_rows(const RPool& pl, const RWs& ws, int s0, int i, int n, bool in, int& count) {
+    const long long from = (long long)s0 + i, to = (long long)s0 + append_kept(in, threadIdx.x, count);
+    if (i < n) ws.mask[from] = in ? 1 : 0;
     if (in) {
-        const long long from = (long long)s0 + i, to = (long long)s0 + count + __popcll(m & ((1ull << lane) - 1ull));
 #pragma unroll
         for (int k = 0; k < 4; ++k) ws.rows[4 * to + k] = pl.rows[4 * from + k];
         if (pl.xy) {
@@ -157,7 +134,6 @@ __device__ __forceinline__ int keep_rows(const RPool& pl, const RWs& ws, int s0,
             ws.xy[2 * to + 1] = pl.xy[2 * from + 1];
         }
     }
-    return __popcll(m);
 }
 
 // The view leaves the calibration: an empty view in the filtered pool, an all-false mask over its slots that lie in the pool.
@@ -186,23 +162,8 @@ __global__ __launch_bounds__(kLanes) void calib_ransac_select_compact_kernel(RPo
         exclude_view(pl, ws, b, n, s0, st);
         return;
     }
-    // the highest score, the lowest h among equals: ascending h in each lane, then a butterfly with the same rule
-    int best = -1, bh = 0x7fffffff;
-    for (int h = lane; h < iterations; h += kLanes) {
-        const int sc = ws.scores[(long long)b * iterations + h];
-        if (sc > best) {
-            best = sc;
-            bh = h;
-        }
-    }
-#pragma unroll
-    for (int m = kLanes / 2; m >= 1; m >>= 1) {
-        const int ob = __shfl_xor(best, m, kLanes), oh = __shfl_xor(bh, m, kLanes);
-        if (ob > best || (ob == best && oh < bh)) {
-            best = ob;
-            bh = oh;
-        }
-    }
+    int best, bh;
+    best_hypothesis(ws.scores + (long long)b * iterations, iterations, best, bh);
     if (best < 0) {
         exclude_view(pl, ws, b, n, s0, DCX_PNP_DEGENERATE);
         return;
@@ -219,7 +180,7 @@ __global__ __launch_bounds__(kLanes) void calib_ransac_select_compact_kernel(RPo
             f.load(i, bx, by, u, v);
             in = transfer_error2(H, mcx, mcy, bx, by, u, v) <= thr2;
         }
-        count += keep_rows(pl, ws, s0, i, n, in, count);
+        keep_rows(pl, ws, s0, i, n, in, count);
     }
     if (lane == 0) ws.winner[b] = bh;
     if (count < need) {
@@ -258,7 +219,7 @@ __global__ __launch_bounds__(kLanes) void calib_ransac_remask_kernel(RPool pl, P
             in = row_error2(R, p + 3, cam, bx, by, u, v) <= thr2;
             diff |= in != (ws.mask[(long long)s0 + i] != 0);
         }
-        count += keep_rows(pl, ws, s0, i, n, in, count);
+        keep_rows(pl, ws, s0, i, n, in, count);
     }
     const bool changed = __any(diff);
     if (count < need) {
@@ -353,9 +314,7 @@ extern "C" int dcx_calibrate_ransac_pool(const int32_t* d_counts, const int32_t*
         if (rc != 0) return rc;
         ++solves;
         if ((int)h_result[14] != DCX_CALIB_OK || solves > rounds) break;
-        PnpCamera cam;
-        cam.fx = h_result[0]; cam.fy = h_result[1]; cam.cx = h_result[2]; cam.cy = h_result[3];
-        for (int i = 0; i < 8; ++i) cam.k[i] = i < 5 ? h_result[4 + i] : 0.0;
+        const PnpCamera cam = camera_of(h_result);
         hipLaunchKernelGGL(calib_ransac_remask_kernel, views, wave, 0, s, pl, cam, reproj_error * reproj_error, need, d_view_status,
                            d_pose, ws);
         hipLaunchKernelGGL(calib_ransac_changed_sum_kernel, one, wave, 0, s, batch, ws);

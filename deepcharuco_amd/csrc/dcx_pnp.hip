@@ -12,6 +12,8 @@
 // redundantly and takes the same branches: no LDS, no barrier.  The exception is the 9x9 Jacobi's eigenvector matrix: lane j keeps
 // row j of V (a rotation mixes two entries of every row, so no lane needs another's data), which keeps it out of 81 registers.
 // K and the distortion coefficients are kernel arguments (captured by value in a hipGraph); no allocation, no synchronisation.
+// The solver itself is dcx_pnp_dev.h (solve and what it calls) on dcx_camera_dev.h (camera model, rotations) and dcx_mat_dev.h
+// (Jacobi, Cholesky, the butterfly).
 #include "dcx_pnp_dev.h"
 
 namespace {
@@ -23,6 +25,8 @@ __global__ __launch_bounds__(kLanes) void dcx_solve_pnp_kernel(const int32_t* __
     const int b = blockIdx.x, lane = threadIdx.x;
     const int n = counts[b], s0 = starts[b];
     double out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // The header's frame_status(), spelt out: through the call this kernel's code generation moves (the compiler shares one large-
+    // argument sine reduction less, four registers and eight SGPR spills more).  A change there is a change here.
     int st;
     if (n <= 0) {
         st = DCX_PNP_TOO_FEW;

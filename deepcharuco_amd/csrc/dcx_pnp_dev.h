@@ -1,169 +1,19 @@
-// dcx_pnp_dev.h -- the fp64 device steps of the PnP solver (dcx_pnp.hip) that the camera calibration (dcx_calib.hip) reuses:
-// packed symmetric storage, the wave butterfly, cyclic Jacobi, Rodrigues both ways, the SO(3) right Jacobian, the pool reader
-// (Frame), undistortPoints, the 6x6 Cholesky, the planar DLT homography, the planar pose init and the PnP Levenberg-Marquardt; dcx_pnp_ransac.hip runs the
-// last three over an index list of a frame's rows (the frame type is a template parameter).  Also here: what the two consensus
-// searches (dcx_pnp_ransac.hip, dcx_calib_ransac.hip) share: the per-frame checks, the sampler, the four-point homography and one
-// row's reprojection error.
+// dcx_pnp_dev.h -- the pool reader, the consensus steps and the PnP solver, on top of dcx_camera_dev.h (camera model, rotations) and
+// dcx_mat_dev.h (small matrices, reductions): the frame types (Frame, IndexedFrame), the per-frame checks, the normal equations of
+// a frame at a pose (evaluate), the planar DLT homography, the planar pose init and the PnP Levenberg-Marquardt (solve), which
+// dcx_pnp.hip runs per frame, dcx_calib.hip and dcx_stereo.hip per view, and dcx_pnp_ransac.hip over an index list of a frame's rows
+// (the frame type is a template parameter).  Also here: what the consensus searches (dcx_pnp_ransac.hip, dcx_calib_ransac.hip) and
+// the masked stereo solve share: the slot-range overlap test, the sampler, the four-point homography, one row's reprojection error
+// and the first-maximum score search.
 // deepcharuco_amd/pnp.py restates every step (its functions of the same names).  Everything is force-inlined and has internal
 // linkage, so each translation unit compiles its own copy.
 #pragma once
-#include "dcx_common.h"
-
-#include <math.h>
+#include "dcx_camera_dev.h"
 
 namespace {
 
-constexpr int kLanes = 64;
 constexpr int kLmMaxIter = 20;
 constexpr double kLmEps = 1.1920928955078125e-07;   // FLT_EPSILON
-constexpr int kUndistortIters = 5;
-constexpr int kJacobiMaxSweeps = 16;
-
-struct PnpCamera {
-    double fx, fy, cx, cy;
-    double k[8];            // k1 k2 p1 p2 k3 k4 k5 k6, zero padded
-};
-
-// K (row major, no skew) and 0 / 4 / 5 / 8 distortion coefficients from the host -> the kernel argument; false if refused
-inline bool pnp_camera(const double* h_camera9, const double* h_dist, int n_dist, PnpCamera& cam) {
-    if (!h_camera9 || !(n_dist == 0 || n_dist == 4 || n_dist == 5 || n_dist == 8) || (n_dist > 0 && !h_dist)) return false;
-    if (h_camera9[1] != 0.0) return false;                         // skew is not supported
-    cam.fx = h_camera9[0];
-    cam.fy = h_camera9[4];
-    cam.cx = h_camera9[2];
-    cam.cy = h_camera9[5];
-    if (!(isfinite(cam.fx) && isfinite(cam.fy) && isfinite(cam.cx) && isfinite(cam.cy)) || cam.fx == 0.0 || cam.fy == 0.0)
-        return false;
-    for (int i = 0; i < 8; ++i) {
-        cam.k[i] = i < n_dist ? h_dist[i] : 0.0;
-        if (!isfinite(cam.k[i])) return false;
-    }
-    return true;
-}
-
-// packed upper triangle of a symmetric N x N matrix, row major
-template <int N>
-__device__ constexpr int pk(int i, int j) {
-    return i <= j ? i * N - i * (i - 1) / 2 + (j - i) : j * N - j * (j - 1) / 2 + (i - j);
-}
-
-template <int N>
-__device__ __forceinline__ void wave_sum(double (&a)[N]) {
-#pragma unroll
-    for (int m = kLanes / 2; m >= 1; m >>= 1) {
-#pragma unroll
-        for (int i = 0; i < N; ++i) a[i] += __shfl_xor(a[i], m, kLanes);
-    }
-}
-
-// Cyclic Jacobi on the packed symmetric a (eigenvalues end on its diagonal).  v holds NR rows of V (a = V diag V^T); the caller
-// initialises them.  Same rotation formulas and order as pnp._jacobi.
-template <int N, int NR>
-__device__ __forceinline__ void jacobi(double (&a)[N * (N + 1) / 2], double (&v)[NR][N]) {
-#pragma unroll 1
-    for (int sweep = 0; sweep < kJacobiMaxSweeps; ++sweep) {
-        double off = 0.0, dia = 0.0;
-#pragma unroll
-        for (int p = 0; p < N; ++p) {
-            dia += a[pk<N>(p, p)] * a[pk<N>(p, p)];
-#pragma unroll
-            for (int q = p + 1; q < N; ++q) off += a[pk<N>(p, q)] * a[pk<N>(p, q)];
-        }
-        if (!(off > 1e-30 * dia)) break;
-#pragma unroll
-        for (int p = 0; p < N; ++p) {
-#pragma unroll
-            for (int q = p + 1; q < N; ++q) {
-                const double apq = a[pk<N>(p, q)], app = a[pk<N>(p, p)], aqq = a[pk<N>(q, q)];
-                double t = 0.0;
-                if (apq != 0.0) {
-                    const double theta = (aqq - app) / (2.0 * apq);
-                    t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
-                    if (theta < 0) t = -t;
-                }
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                // columns p, q, then rows p, q (the 2x2 block in two steps, as the host does on the full matrix)
-                const double bpp = c * app - s * apq, bpq = s * app + c * apq;
-                const double bqp = c * apq - s * aqq, bqq = s * apq + c * aqq;
-#pragma unroll
-                for (int r = 0; r < N; ++r) {
-                    if (r == p || r == q) continue;
-                    const double arp = a[pk<N>(r, p)], arq = a[pk<N>(r, q)];
-                    a[pk<N>(r, p)] = c * arp - s * arq;
-                    a[pk<N>(r, q)] = s * arp + c * arq;
-                }
-                a[pk<N>(p, p)] = c * bpp - s * bqp;
-                a[pk<N>(q, q)] = s * bpq + c * bqq;
-                a[pk<N>(p, q)] = 0.0;
-#pragma unroll
-                for (int r = 0; r < NR; ++r) {
-                    const double vp = v[r][p], vq = v[r][q];
-                    v[r][p] = c * vp - s * vq;
-                    v[r][q] = s * vp + c * vq;
-                }
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ void rodrigues(const double* r, double* R) {
-    const double th = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-    if (!(th >= 1e-300)) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
-        return;
-    }
-    const double kx = r[0] / th, ky = r[1] / th, kz = r[2] / th;
-    const double sn = sin(th), cs = 1.0 - cos(th);
-    // I + sin K + (1 - cos) K^2,  K^2 = k k^T - I
-    R[0] = 1.0 + cs * (kx * kx - 1.0); R[1] = -sn * kz + cs * kx * ky; R[2] = sn * ky + cs * kx * kz;
-    R[3] = sn * kz + cs * kx * ky;     R[4] = 1.0 + cs * (ky * ky - 1.0); R[5] = -sn * kx + cs * ky * kz;
-    R[6] = -sn * ky + cs * kx * kz;    R[7] = sn * kx + cs * ky * kz;     R[8] = 1.0 + cs * (kz * kz - 1.0);
-}
-
-// rotation vector of an orthonormal matrix: cvRodrigues2's matrix -> vector branch after its SVD
-__device__ __forceinline__ void rvec_of(const double* R, double* r) {
-    const double rx = R[7] - R[5], ry = R[2] - R[6], rz = R[3] - R[1];
-    const double s = sqrt((rx * rx + ry * ry + rz * rz) * 0.25);
-    const double c = fmin(fmax((R[0] + R[4] + R[8] - 1.0) * 0.5, -1.0), 1.0);
-    const double theta = acos(c);
-    if (s < 1e-5) {
-        if (c > 0) { r[0] = r[1] = r[2] = 0.0; return; }
-        double x = sqrt(fmax((R[0] + 1.0) * 0.5, 0.0));
-        double y = sqrt(fmax((R[4] + 1.0) * 0.5, 0.0)) * (R[1] < 0 ? -1.0 : 1.0);
-        double z = sqrt(fmax((R[8] + 1.0) * 0.5, 0.0)) * (R[2] < 0 ? -1.0 : 1.0);
-        if (fabs(x) < fabs(y) && fabs(x) < fabs(z) && ((R[5] > 0) != (y * z > 0))) z = -z;
-        const double f = M_PI / sqrt(x * x + y * y + z * z);
-        r[0] = x * f; r[1] = y * f; r[2] = z * f;
-        return;
-    }
-    const double f = theta / (2.0 * s);
-    r[0] = rx * f; r[1] = ry * f; r[2] = rz * f;
-}
-
-// right Jacobian of SO(3): d(R(r) u)/dr = -R [u]x Jr(r)
-__device__ __forceinline__ void right_jacobian(const double* r, double* J) {
-    const double th2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-    double a, b;
-    if (th2 < 1e-8) {
-        a = 0.5 - th2 / 24.0;
-        b = 1.0 / 6.0 - th2 / 120.0;
-    } else {
-        const double th = sqrt(th2);
-        a = (1.0 - cos(th)) / th2;
-        b = (th - sin(th)) / (th2 * th);
-    }
-    const double S[9] = {0.0, -r[2], r[1], r[2], 0.0, -r[0], -r[1], r[0], 0.0};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double s2 = 0.0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) s2 += S[i * 3 + k] * S[k * 3 + j];
-            J[i * 3 + j] = (i == j ? 1.0 : 0.0) - a * S[i * 3 + j] + b * s2;
-        }
-}
 
 struct Frame {
     const int32_t* rows;     // this frame's rows (x, y, id, cell), n of them
@@ -196,103 +46,27 @@ struct IndexedFrame {
     __device__ __forceinline__ void load(int i, double& X, double& Y, double& u, double& v) const { base.load(idx[i], X, Y, u, v); }
 };
 
-__device__ __forceinline__ void undistort(const PnpCamera& cam, bool dist, double u, double v, double& x, double& y) {
-    const double x0 = (u - cam.cx) / cam.fx, y0 = (v - cam.cy) / cam.fy;
-    x = x0;
-    y = y0;
-    if (!dist) return;
-    const double* k = cam.k;
-    for (int it = 0; it < kUndistortIters; ++it) {
-        const double r2 = x * x + y * y;
-        const double icdist = (1 + ((k[7] * r2 + k[6]) * r2 + k[5]) * r2) / (1 + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2);
-        if (icdist < 0) {
-            x = x0;
-            y = y0;
-            break;
-        }
-        const double dx = 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x);
-        const double dy = k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y;
-        x = (x0 - dx) * icdist;
-        y = (y0 - dy) * icdist;
-    }
-}
-
 // Sum over the frame's points of the squared reprojection error at pose p (+inf if a point is not in front of the camera) and,
 // with JAC, of JtJ (21, packed) and Jtr (6).  acc = {cost, JtJ[21], Jtr[6]} on return, identical in every lane.
 template <bool JAC, class F>
 __device__ __forceinline__ void evaluate(const F& f, const PnpCamera& cam, const double* p, double (&acc)[28]) {
-    double R[9], G[2][9];           // G[c] = -R [e_c]x Jr: d(R m)/dr for the board point m = e_c (the board has z = 0)
-    rodrigues(p, R);
-    if (JAC) {
-        double Jr[9];
-        right_jacobian(p, Jr);
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            double E[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // [e_c]x
-            if (c == 0) { E[5] = -1.0; E[7] = 1.0; } else { E[2] = 1.0; E[6] = -1.0; }
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    double s = 0.0;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        double ej = 0.0;
-#pragma unroll
-                        for (int l = 0; l < 3; ++l) ej += E[k * 3 + l] * Jr[l * 3 + j];
-                        s += R[i * 3 + k] * ej;
-                    }
-                    G[c][i * 3 + j] = -s;
-                }
-        }
-    }
+    double R[9], G[2][9];
+    if (JAC) pose_basis(p, R, G);
+    else rodrigues(p, R);
 #pragma unroll
     for (int i = 0; i < 28; ++i) acc[i] = 0.0;
-    const double* k = cam.k;
     for (int i = threadIdx.x; i < f.n; i += kLanes) {
-        double mx, my, u, v;
+        double mx, my, u, v, q[3], ru, rv, du[3], dv[3];
         f.load(i, mx, my, u, v);
-        const double X = R[0] * mx + R[1] * my + p[3];
-        const double Y = R[3] * mx + R[4] * my + p[4];
-        const double Z = R[6] * mx + R[7] * my + p[5];
-        if (!(Z > 0)) {
+        board_point(R, p + 3, mx, my, q);
+        if (!project<JAC>(cam, q, u, v, ru, rv, du, dv)) {
             acc[0] = INFINITY;
             continue;
         }
-        const double iz = 1.0 / Z, x = X * iz, y = Y * iz;
-        const double r2 = x * x + y * y;
-        const double num = 1 + r2 * (k[0] + r2 * (k[1] + r2 * k[4]));
-        const double den = 1 + r2 * (k[5] + r2 * (k[6] + r2 * k[7]));
-        const double g = num / den;
-        const double xd = x * g + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x);
-        const double yd = y * g + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y;
-        const double ru = cam.fx * xd + cam.cx - u, rv = cam.fy * yd + cam.cy - v;
         acc[0] += ru * ru + rv * rv;
         if (!JAC) continue;
-        const double dg = ((k[0] + r2 * (2 * k[1] + 3 * k[4] * r2)) * den - num * (k[5] + r2 * (2 * k[6] + 3 * k[7] * r2))) / (den * den);
-        const double dxd_dx = g + 2 * x * x * dg + 2 * k[2] * y + 6 * k[3] * x;
-        const double dxd_dy = 2 * x * y * dg + 2 * k[2] * x + 2 * k[3] * y;
-        const double dyd_dx = dxd_dy;
-        const double dyd_dy = g + 2 * y * y * dg + 6 * k[2] * y + 2 * k[3] * x;
-        // d(u, v)/d(X, Y, Z)
-        const double a0 = cam.fx * dxd_dx, a1 = cam.fx * dxd_dy, b0 = cam.fy * dyd_dx, b1 = cam.fy * dyd_dy;
-        const double du[3] = {a0 * iz, a1 * iz, -(a0 * x + a1 * y) * iz};
-        const double dv[3] = {b0 * iz, b1 * iz, -(b0 * x + b1 * y) * iz};
         double ju[6], jv[6];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double su = 0.0, sv = 0.0;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const double dX = mx * G[0][c * 3 + j] + my * G[1][c * 3 + j];
-                su += du[c] * dX;
-                sv += dv[c] * dX;
-            }
-            ju[j] = su;
-            jv[j] = sv;
-            ju[3 + j] = du[j];
-            jv[3 + j] = dv[j];
-        }
+        pose_columns(du, dv, mx, my, G, ju, jv);
 #pragma unroll
         for (int a = 0; a < 6; ++a) {
 #pragma unroll
@@ -301,42 +75,6 @@ __device__ __forceinline__ void evaluate(const F& f, const PnpCamera& cam, const
         }
     }
     wave_sum(acc);
-}
-
-// (JtJ with its diagonal scaled by 1 + lambda) x = Jtr by Cholesky; false if not positive definite
-__device__ __forceinline__ bool cholesky_solve(const double* jtj, const double* jtr, double scale, double* x) {
-    double L[21];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-            double s = jtj[pk<6>(i, j)] * (i == j ? scale : 1.0);
-#pragma unroll
-            for (int k = 0; k < j; ++k) s -= L[pk<6>(i, k)] * L[pk<6>(j, k)];
-            if (i == j) {
-                if (!(s > 0)) return false;
-                L[pk<6>(i, i)] = sqrt(s);
-            } else {
-                L[pk<6>(i, j)] = s / L[pk<6>(j, j)];
-            }
-        }
-    }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double s = jtr[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) s -= L[pk<6>(i, k)] * y[k];
-        y[i] = s / L[pk<6>(i, i)];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) s -= L[pk<6>(k, i)] * x[k];
-        x[i] = s / L[pk<6>(i, i)];
-    }
-    return true;
 }
 
 // Planar DLT (pnp._homography) of the board points to the (undistorted) image points -> status; H (row major, h33 = 1) maps
@@ -438,14 +176,16 @@ __device__ __forceinline__ int homography(const F& f, const PnpCamera& cam, bool
     return DCX_PNP_OK;
 }
 
-// ---- the consensus searches' shared steps (dcx_pnp_ransac.hip, dcx_calib_ransac.hip): the per-frame checks, the counter-hash
-// sampler, the closed-form homography through four rows and one row's reprojection error
+// ---- the consensus searches' shared steps (dcx_pnp_ransac.hip, dcx_calib_ransac.hip): the per-frame checks, the slot-range overlap
+// test, the counter-hash sampler, the closed-form homography through four rows, one row's reprojection error and the first maximum
+// of the scores
 
 constexpr int kMaxIterations = 4096; // hypotheses per frame (pnp.RANSAC_MAX_ITERATIONS)
 constexpr int kSampleTries = 8;      // complete 4-samples per hypothesis (pnp.RANSAC_SAMPLE_TRIES)
 constexpr int kMaxDraws = 256;       // slot draws per hypothesis, redraws included (pnp.RANSAC_MAX_DRAWS)
 
-// The per-frame checks of dcx_solve_pnp_kernel, in its order -> DCX_PNP_OK if the frame's rows can be read and solved.  Wave-wide.
+// The per-frame checks, in the order of dcx_solve_pnp_kernel (which spells them out itself, see there) -> DCX_PNP_OK if the frame's
+// rows can be read and solved.  Wave-wide.
 __device__ __forceinline__ int frame_status(const int32_t* counts, const int32_t* starts, const int32_t* rows, int b, int pool,
                                             int n_ids, int& n, int& s0) {
     n = counts[b];
@@ -459,6 +199,23 @@ __device__ __forceinline__ int frame_status(const int32_t* counts, const int32_t
         bad |= id < 0 || id >= n_ids;
     }
     return __any(bad) ? DCX_PNP_BAD_ID : DCX_PNP_OK;
+}
+
+// One wave per view b of a pool whose views own their slot ranges: does b's range (the part inside the pool) meet another view's?
+// The lanes share the other views out.  Wave-wide.
+__device__ __forceinline__ bool ranges_overlap(const int32_t* counts, const int32_t* starts, int pool, int batch, int b) {
+    const long long n = counts[b], s0 = starts[b];
+    if (n <= 0) return false;
+    const long long lo = s0 < 0 ? 0 : s0, hi = s0 + n < pool ? s0 + n : pool;
+    if (lo >= hi) return false;
+    bool hit = false;
+    for (int o = threadIdx.x; o < batch; o += kLanes) {
+        const long long on = counts[o], os = starts[o];
+        if (o == b || on <= 0) continue;
+        const long long olo = os < 0 ? 0 : os, ohi = os + on < pool ? os + on : pool;
+        hit |= olo < ohi && olo < hi && lo < ohi;
+    }
+    return __any(hit);
 }
 
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
@@ -513,13 +270,6 @@ __device__ __forceinline__ bool ransac_sample(const int32_t* rows, uint32_t seed
     return false;
 }
 
-// adjugate of a row-major 3x3
-__device__ __forceinline__ void adjugate(const double* m, double* a) {
-    a[0] = m[4] * m[8] - m[5] * m[7]; a[1] = m[2] * m[7] - m[1] * m[8]; a[2] = m[1] * m[5] - m[2] * m[4];
-    a[3] = m[5] * m[6] - m[3] * m[8]; a[4] = m[0] * m[8] - m[2] * m[6]; a[5] = m[2] * m[3] - m[0] * m[5];
-    a[6] = m[3] * m[7] - m[4] * m[6]; a[7] = m[1] * m[6] - m[0] * m[7]; a[8] = m[0] * m[4] - m[1] * m[3];
-}
-
 // pnp._projective_basis: the 3x3 that sends e1, e2, e3, (1,1,1) to the four points, each up to scale
 __device__ __forceinline__ void projective_basis(const double* x, const double* y, double* A) {
     const double m[9] = {x[0], x[1], x[2], y[0], y[1], y[2], 1.0, 1.0, 1.0};
@@ -538,20 +288,32 @@ __device__ __forceinline__ void projective_basis(const double* x, const double* 
 // front of the camera (evaluate()'s projection, per row)
 __device__ __forceinline__ double row_error2(const double* R, const double* t, const PnpCamera& cam, double mx, double my, double u,
                                              double v) {
-    const double X = R[0] * mx + R[1] * my + t[0];
-    const double Y = R[3] * mx + R[4] * my + t[1];
-    const double Z = R[6] * mx + R[7] * my + t[2];
-    if (!(Z > 0)) return INFINITY;
-    const double* k = cam.k;
-    const double iz = 1.0 / Z, x = X * iz, y = Y * iz;
-    const double r2 = x * x + y * y;
-    const double num = 1 + r2 * (k[0] + r2 * (k[1] + r2 * k[4]));
-    const double den = 1 + r2 * (k[5] + r2 * (k[6] + r2 * k[7]));
-    const double g = num / den;
-    const double xd = x * g + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x);
-    const double yd = y * g + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y;
-    const double ru = cam.fx * xd + cam.cx - u, rv = cam.fy * yd + cam.cy - v;
+    double q[3], ru, rv;
+    board_point(R, t, mx, my, q);
+    if (!project<false>(cam, q, u, v, ru, rv, nullptr, nullptr)) return INFINITY;
     return ru * ru + rv * rv;
+}
+
+// The first maximum of a frame's `iterations` scores: the highest score, the lowest h among equals (ascending h in each lane, then
+// a butterfly with the same rule).  best < 0: no hypothesis scored.  Wave-wide; every lane gets the same answer.
+__device__ __forceinline__ void best_hypothesis(const int32_t* scores, int iterations, int& best, int& bh) {
+    best = -1;
+    bh = 0x7fffffff;
+    for (int h = threadIdx.x; h < iterations; h += kLanes) {
+        const int sc = scores[h];
+        if (sc > best) {
+            best = sc;
+            bh = h;
+        }
+    }
+#pragma unroll
+    for (int m = kLanes / 2; m >= 1; m >>= 1) {
+        const int ob = __shfl_xor(best, m, kLanes), oh = __shfl_xor(bh, m, kLanes);
+        if (ob > best || (ob == best && oh < bh)) {
+            best = ob;
+            bh = oh;
+        }
+    }
 }
 
 // Four sampled rows of a frame, held by one lane: board points and undistorted image points.
@@ -607,33 +369,8 @@ __device__ __forceinline__ int init_pose(const F& f, const PnpCamera& cam, bool 
     Rr[5] = Rr[6] * Rr[1] - Rr[0] * Rr[7];
     Rr[8] = Rr[0] * Rr[4] - Rr[3] * Rr[1];
     double t[3] = {H[2] * it, H[5] * it, H[8] * it};
-    // polar factor Rr (Rr^T Rr)^-1/2
-    double S[6], W[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = a; b < 3; ++b) S[pk<3>(a, b)] = Rr[a] * Rr[b] + Rr[3 + a] * Rr[3 + b] + Rr[6 + a] * Rr[6 + b];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) W[a][b] = a == b ? 1.0 : 0.0;
-    jacobi<3, 3>(S, W);
-    double iw[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double w = S[pk<3>(c, c)];
-        if (!(w > 0)) return DCX_PNP_DEGENERATE;
-        iw[c] = 1.0 / sqrt(w);
-    }
-    double P[9], Q[9];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) P[a * 3 + b] = W[a][0] * iw[0] * W[b][0] + W[a][1] * iw[1] * W[b][1] + W[a][2] * iw[2] * W[b][2];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) Q[a * 3 + b] = Rr[a * 3 + 0] * P[b] + Rr[a * 3 + 1] * P[3 + b] + Rr[a * 3 + 2] * P[6 + b];
+    double Q[9];
+    if (!polar_factor(Rr, Q)) return DCX_PNP_DEGENERATE;
     rvec_of(Q, p0);
     double R[9];
     rodrigues(p0, R);
@@ -648,9 +385,7 @@ __device__ __forceinline__ int init_pose(const F& f, const PnpCamera& cam, bool 
 
 template <class F>
 __device__ __forceinline__ int solve(const F& f, const PnpCamera& cam, double* pose) {
-    bool dist = false;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) dist |= cam.k[i] != 0.0;
+    const bool dist = has_distortion(cam);
     double p[6];
     int st = init_pose(f, cam, dist, p);
     if (st != DCX_PNP_OK) return st;

@@ -12,6 +12,7 @@
 //               slots compacted in order into an index list, then the unchanged solve() (init + LM) over that list.
 // The sampler never looks at the frame's position in the batch, nothing is allocated, no atomics, no early exit: the work is fixed,
 // two runs give the same bits and the call can be captured in a hipGraph.
+// The sampler, the four-point homography, row_error2, best_hypothesis and solve() are dcx_pnp_dev.h's; append_kept is dcx_mat_dev.h's.
 #include "dcx_pnp_dev.h"
 
 namespace {
@@ -37,13 +38,6 @@ __device__ __forceinline__ int hypothesis(const Frame& f, const PnpCamera& cam, 
         score += row_error2(R, p0 + 3, cam, bx, by, u, v) <= thr2 ? 1 : 0;
     }
     return score;
-}
-
-__device__ __forceinline__ bool has_distortion(const PnpCamera& cam) {
-    bool dist = false;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) dist |= cam.k[i] != 0.0;
-    return dist;
 }
 
 __global__ __launch_bounds__(kLanes) void dcx_pnp_ransac_hypotheses_kernel(
@@ -74,23 +68,8 @@ __global__ __launch_bounds__(kLanes) void dcx_pnp_ransac_select_kernel(
     double out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int winner = -1, count = 0;
     if (st == DCX_PNP_OK) {
-        // the highest score, the lowest h among equals: ascending h in each lane, then a butterfly with the same rule
-        int best = -1, bh = 0x7fffffff;
-        for (int h = lane; h < iterations; h += kLanes) {
-            const int sc = scores[(long long)b * iterations + h];
-            if (sc > best) {
-                best = sc;
-                bh = h;
-            }
-        }
-#pragma unroll
-        for (int m = kLanes / 2; m >= 1; m >>= 1) {
-            const int ob = __shfl_xor(best, m, kLanes), oh = __shfl_xor(bh, m, kLanes);
-            if (ob > best || (ob == best && oh < bh)) {
-                best = ob;
-                bh = oh;
-            }
-        }
+        int best, bh;
+        best_hypothesis(scores + (long long)b * iterations, iterations, best, bh);
         if (best < 0) {
             st = DCX_PNP_DEGENERATE;
         } else {
@@ -110,9 +89,8 @@ __global__ __launch_bounds__(kLanes) void dcx_pnp_ransac_select_kernel(
                     in = row_error2(R, p + 3, cam, bx, by, u, v) <= thr2;
                     if (inliers) inliers[(long long)s0 + i] = in ? 1 : 0;
                 }
-                const unsigned long long m = __ballot(in);
-                if (in) list[count + __popcll(m & ((1ull << lane) - 1ull))] = i;
-                count += __popcll(m);
+                const int at = append_kept(in, lane, count);
+                if (in) list[at] = i;
             }
             __syncthreads();                               // one wave: the list is read below by other lanes than wrote it
             if (count < max(min_inliers, 4)) {

@@ -6,8 +6,9 @@
 //
 // Map and points are fp64 and agree with the host to rounding; the remap is integer and agrees bit for bit.  K, the distortion
 // coefficients, R and P are kernel arguments (a captured hipGraph keeps them).  No allocation, no synchronisation, no atomics, no
-// LDS in any of the three.
-#include "dcx_pnp_dev.h"
+// LDS in any of the three.  The distortion model and its derivative (distort<>) are dcx_camera_dev.h's, the one copy the pose and
+// calibration kernels project through.
+#include "dcx_camera_dev.h"
 
 namespace {
 
@@ -36,22 +37,6 @@ inline bool rect_xform(const double* h_R9, const double* h_P12, const PnpCamera&
         x.fx = cam.fx; x.fy = cam.fy; x.cx = cam.cx; x.cy = cam.cy;
     }
     return isfinite(x.fx) && isfinite(x.fy) && isfinite(x.cx) && isfinite(x.cy) && x.fx != 0.0 && x.fy != 0.0;
-}
-
-// normalised (x, y) -> distorted normalised (xd, yd) and, with JAC, dxd/dx, dxd/dy (= dyd/dx), dyd/dy: evaluate()'s model
-template <bool JAC>
-__device__ __forceinline__ void distort(const double* k, double x, double y, double& xd, double& yd, double& a, double& b, double& d) {
-    const double r2 = x * x + y * y;
-    const double num = 1 + r2 * (k[0] + r2 * (k[1] + r2 * k[4]));
-    const double den = 1 + r2 * (k[5] + r2 * (k[6] + r2 * k[7]));
-    const double g = num / den;
-    xd = x * g + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x);
-    yd = y * g + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y;
-    if (!JAC) return;
-    const double dg = ((k[0] + r2 * (2 * k[1] + 3 * k[4] * r2)) * den - num * (k[5] + r2 * (2 * k[6] + 3 * k[7] * r2))) / (den * den);
-    a = g + 2 * x * x * dg + 2 * k[2] * y + 6 * k[3] * x;
-    b = 2 * x * y * dg + 2 * k[2] * x + 2 * k[3] * y;
-    d = g + 2 * y * y * dg + 6 * k[2] * y + 2 * k[3] * x;
 }
 
 // ---- the map: one thread per output pixel

@@ -34,6 +34,10 @@
 // The LM loop runs on the host: it reads the state word after every attempt (the number of attempts depends on the data), so the
 // call synchronises its stream and cannot be captured in a graph.  Every sum has a fixed order (no atomics): two calls on the same
 // input give the same bits.  No device memory is allocated: the caller passes the workspace.
+// Shared with dcx_calib.hip through dcx_mat_dev.h: evaluate's LDS-staged loop (accumulate_rows), schur's body (schur_view), the
+// rig's polar_factor, block_tree, the workspace carver; overlap is dcx_pnp_dev.h's ranges_overlap.  The camera model, its
+// derivative and the pose columns are dcx_camera_dev.h's (project, pose_basis, pose_columns); stereo_row() below adds the chain
+// through R_X and the rig columns.
 #include "dcx_pnp_dev.h"
 
 #include <algorithm>
@@ -89,39 +93,32 @@ struct Ws {
     int32_t *head, *pair, *fail, *pfail, *count, *idx0, *idx1, *ident;
 };
 
-__host__ __device__ inline size_t up8(size_t n) { return (n + 7) & ~(size_t)7; }
 inline int chunks_of(int batch) { return (batch + kChunk - 1) / kChunk; }
 
 size_t ws_layout(void* base, int batch, int pool0, int pool1, Ws* w) {
-    size_t at = 0;
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) {
-        char* q = p + at;
-        at += up8(bytes);
-        return q;
-    };
-    const size_t B = (size_t)batch, G = (size_t)chunks_of(batch), d = sizeof(double), i = sizeof(int32_t);
+    const size_t B = (size_t)batch, G = (size_t)chunks_of(batch);
+    Carver c{(char*)base, 0};
     Ws r;
-    r.st = (StereoState*)take(kState);
-    r.m = (double*)take(B * kEntries * d);
-    r.yz = (double*)take(B * kYZ * d);
-    r.sc = (double*)take(B * kSC * d);
-    r.part = (double*)take(G * kTot * d);
-    r.pose = (double*)take(B * 6 * d);
-    r.trial_pose = (double*)take(B * 6 * d);
-    r.trial = (double*)take(B * 4 * d);
-    r.vpose = (double*)take(B * 12 * d);
-    r.rig = (double*)take(B * 12 * d);
-    r.head = (int32_t*)take(kHeadWords * i);
-    r.pair = (int32_t*)take(B * i);
-    r.fail = (int32_t*)take(B * i);
-    r.pfail = (int32_t*)take(G * i);
-    r.count = (int32_t*)take(B * 2 * i);
-    r.idx0 = (int32_t*)take((size_t)pool0 * i);
-    r.idx1 = (int32_t*)take((size_t)pool1 * i);
-    r.ident = (int32_t*)take((size_t)(pool0 > pool1 ? pool0 : pool1) * i);
+    r.st = (StereoState*)c.take<char>(kState);
+    r.m = c.take<double>(B * kEntries);
+    r.yz = c.take<double>(B * kYZ);
+    r.sc = c.take<double>(B * kSC);
+    r.part = c.take<double>(G * kTot);
+    r.pose = c.take<double>(B * 6);
+    r.trial_pose = c.take<double>(B * 6);
+    r.trial = c.take<double>(B * 4);
+    r.vpose = c.take<double>(B * 12);
+    r.rig = c.take<double>(B * 12);
+    r.head = c.take<int32_t>(kHeadWords);
+    r.pair = c.take<int32_t>(B);
+    r.fail = c.take<int32_t>(B);
+    r.pfail = c.take<int32_t>(G);
+    r.count = c.take<int32_t>(B * 2);
+    r.idx0 = c.take<int32_t>((size_t)pool0);
+    r.idx1 = c.take<int32_t>((size_t)pool1);
+    r.ident = c.take<int32_t>((size_t)(pool0 > pool1 ? pool0 : pool1));
     if (w) *w = r;
-    return at;
+    return c.at;
 }
 
 bool sizes_ok(int batch, int pool0, int pool1) { return batch > 0 && pool0 >= 0 && pool1 >= 0; }
@@ -135,21 +132,9 @@ __device__ __forceinline__ IndexedFrame view_frame(const SPool& pl, const Board&
 
 // ---------------------------------------------------------------------------------------------------------------- init
 
-// One wave per view of a pool with a mask: does its slot range (the part inside the pool) meet another view's?
+// One wave per view of a pool with a mask: does its slot range meet another view's?
 __global__ __launch_bounds__(kLanes) void stereo_overlap_kernel(SPool pl, int batch, int32_t* __restrict__ head) {
-    const int b = blockIdx.x;
-    const long long n = pl.counts[b], s0 = pl.starts[b];
-    if (n <= 0) return;
-    const long long lo = s0 < 0 ? 0 : s0, hi = s0 + n < pl.pool ? s0 + n : pl.pool;
-    if (lo >= hi) return;
-    bool hit = false;
-    for (int o = threadIdx.x; o < batch; o += kLanes) {
-        const long long on = pl.counts[o], os = pl.starts[o];
-        if (o == b || on <= 0) continue;
-        const long long olo = os < 0 ? 0 : os, ohi = os + on < pl.pool ? os + on : pl.pool;
-        hit |= olo < ohi && olo < hi && lo < ohi;
-    }
-    if (__any(hit) && threadIdx.x == 0) head[kOverlap] = 1;
+    if (ranges_overlap(pl.counts, pl.starts, pl.pool, batch, blockIdx.x) && threadIdx.x == 0) head[kOverlap] = 1;
 }
 
 __global__ __launch_bounds__(256) void stereo_ident_kernel(int n, int32_t* __restrict__ ident) {
@@ -176,13 +161,12 @@ __global__ __launch_bounds__(kLanes) void stereo_init_views_kernel(SPool pl0, SP
             for (int base = 0; base < n; base += kLanes) {
                 const int i = base + lane;
                 const bool in = i < n && pl.mask[(long long)s0 + i] != 0;
-                const unsigned long long m = __ballot(in);
+                const int at = append_kept(in, lane, kept);
                 if (in) {
-                    list[kept + __popcll(m & ((1ull << lane) - 1ull))] = i;
+                    list[at] = i;
                     const int id = pl.rows[4 * ((long long)s0 + i) + 2];
                     bad |= id < 0 || id >= bd.n_ids;
                 }
-                kept += __popcll(m);
             }
             idx = list;
         } else {
@@ -264,39 +248,12 @@ __global__ __launch_bounds__(kLanes) void stereo_rig_kernel(Med med, int npairs,
         if (writer) st->result[11] = DCX_STEREO_NO_PAIRS;
         return;
     }
-    // polar factor M (M^T M)^-1/2 of the median matrix, as init_pose orthonormalises its decomposition
-    const double* M = med.v;
-    double S[6], W[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = a; b < 3; ++b) S[pk<3>(a, b)] = M[a] * M[b] + M[3 + a] * M[3 + b] + M[6 + a] * M[6 + b];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) W[a][b] = a == b ? 1.0 : 0.0;
-    jacobi<3, 3>(S, W);
-    double iw[3];
-    bool ok = true;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const double w = S[pk<3>(c, c)];
-        ok &= w > 0;
-        iw[c] = 1.0 / sqrt(w);
-    }
-    if (!ok) {
+    // the median matrix's polar factor, as init_pose orthonormalises its decomposition
+    double Q[9], x[6];
+    if (!polar_factor(med.v, Q)) {
         if (writer) st->result[11] = DCX_STEREO_DEGENERATE;
         return;
     }
-    double P[9], Q[9], x[6];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) P[a * 3 + b] = W[a][0] * iw[0] * W[b][0] + W[a][1] * iw[1] * W[b][1] + W[a][2] * iw[2] * W[b][2];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) Q[a * 3 + b] = M[a * 3 + 0] * P[b] + M[a * 3 + 1] * P[3 + b] + M[a * 3 + 2] * P[6 + b];
     rvec_of(Q, x);
     bool finite = true;
 #pragma unroll
@@ -315,79 +272,37 @@ __global__ __launch_bounds__(kLanes) void stereo_rig_kernel(Med med, int npairs,
 
 // ---------------------------------------------------------------------------------------------------------------- LM
 
-// What every row of a pair shares: R(P), t_P, G[c] = -R [e_c]x Jr(r_P) (d(R m)/dr for the board point m = e_c; the board has
-// z = 0), R(X), T_X and Jr(r_X).
+// What every row of a pair shares: R(P), t_P, pose_basis()'s G at P, R(X), T_X and Jr(r_X).
 struct PairBasis {
     double RP[9], tP[3], G[2][9], RX[9], TX[3], JX[9];
 };
 
 template <bool JAC>
 __device__ __forceinline__ void pair_basis(const double* x, const double* p, PairBasis& B) {
-    rodrigues(p, B.RP);
+    if (JAC) pose_basis(p, B.RP, B.G);
+    else rodrigues(p, B.RP);
     rodrigues(x, B.RX);
+    if (JAC) right_jacobian(x, B.JX);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         B.tP[i] = p[3 + i];
         B.TX[i] = x[3 + i];
     }
-    if (!JAC) return;
-    double Jr[9];
-    right_jacobian(p, Jr);
-    right_jacobian(x, B.JX);
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        double E[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // [e_c]x
-        if (c == 0) { E[5] = -1.0; E[7] = 1.0; } else { E[2] = 1.0; E[6] = -1.0; }
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                double s = 0.0;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    double ej = 0.0;
-#pragma unroll
-                    for (int l = 0; l < 3; ++l) ej += E[k * 3 + l] * Jr[l * 3 + j];
-                    s += B.RP[i * 3 + k] * ej;
-                }
-                B.G[c][i * 3 + j] = -s;
-            }
-    }
 }
 
-// One row of camera SECOND's view at (X, P) -> residual (ru, rv); with JAC its two rows of [J_X (6) | J_P (6)]: evaluate()'s
-// projection and derivatives of dcx_pnp_dev.h on the point q = R_P m + t_P (camera 0) or R_X q + T_X (camera 1).  false if the
+// One row of camera SECOND's view at (X, P) -> residual (ru, rv); with JAC its two rows of [J_X (6) | J_P (6)]: the header's
+// project() and pose_columns() on the point q = R_P m + t_P (camera 0) or R_X q + T_X (camera 1).  false if the
 // point is not in front of the camera.
 template <bool JAC, bool SECOND>
 __device__ __forceinline__ bool stereo_row(const PnpCamera& cam, const PairBasis& B, double mx, double my, double u, double v,
                                            double& ru, double& rv, double* ju, double* jv) {
-    double q0[3], q[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) q0[i] = B.RP[i * 3] * mx + B.RP[i * 3 + 1] * my + B.tP[i];
+    double q0[3], q[3], du[3], dv[3];
+    board_point(B.RP, B.tP, mx, my, q0);
 #pragma unroll
     for (int i = 0; i < 3; ++i)
         q[i] = SECOND ? B.RX[i * 3] * q0[0] + B.RX[i * 3 + 1] * q0[1] + B.RX[i * 3 + 2] * q0[2] + B.TX[i] : q0[i];
-    if (!(q[2] > 0)) return false;
-    const double* k = cam.k;
-    const double iz = 1.0 / q[2], x = q[0] * iz, y = q[1] * iz;
-    const double r2 = x * x + y * y;
-    const double num = 1 + r2 * (k[0] + r2 * (k[1] + r2 * k[4]));
-    const double den = 1 + r2 * (k[5] + r2 * (k[6] + r2 * k[7]));
-    const double g = num / den;
-    const double xd = x * g + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x);
-    const double yd = y * g + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y;
-    ru = cam.fx * xd + cam.cx - u;
-    rv = cam.fy * yd + cam.cy - v;
+    if (!project<JAC>(cam, q, u, v, ru, rv, du, dv)) return false;
     if (!JAC) return true;
-    const double dg = ((k[0] + r2 * (2 * k[1] + 3 * k[4] * r2)) * den - num * (k[5] + r2 * (2 * k[6] + 3 * k[7] * r2))) / (den * den);
-    const double dxd_dx = g + 2 * x * x * dg + 2 * k[2] * y + 6 * k[3] * x;
-    const double dxd_dy = 2 * x * y * dg + 2 * k[2] * x + 2 * k[3] * y;
-    const double dyd_dx = dxd_dy;
-    const double dyd_dy = g + 2 * y * y * dg + 6 * k[2] * y + 2 * k[3] * x;
-    // d(u, v)/dq
-    const double a0 = cam.fx * dxd_dx, a1 = cam.fx * dxd_dy, b0 = cam.fy * dyd_dx, b1 = cam.fy * dyd_dy;
-    const double du[3] = {a0 * iz, a1 * iz, -(a0 * x + a1 * y) * iz};
-    const double dv[3] = {b0 * iz, b1 * iz, -(b0 * x + b1 * y) * iz};
     // d(u, v)/dq0: camera 1 sees q0 through R_X
     double eu[3], ev[3];
 #pragma unroll
@@ -395,20 +310,7 @@ __device__ __forceinline__ bool stereo_row(const PnpCamera& cam, const PairBasis
         eu[j] = SECOND ? du[0] * B.RX[j] + du[1] * B.RX[3 + j] + du[2] * B.RX[6 + j] : du[j];
         ev[j] = SECOND ? dv[0] * B.RX[j] + dv[1] * B.RX[3 + j] + dv[2] * B.RX[6 + j] : dv[j];
     }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        double su = 0.0, sv = 0.0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double dX = mx * B.G[0][c * 3 + j] + my * B.G[1][c * 3 + j];
-            su += eu[c] * dX;
-            sv += ev[c] * dX;
-        }
-        ju[6 + j] = su;
-        jv[6 + j] = sv;
-        ju[9 + j] = eu[j];
-        jv[9 + j] = ev[j];
-    }
+    pose_columns(eu, ev, mx, my, B.G, ju + 6, jv + 6);
     if (SECOND) {
         // dq/dr_X = -R_X [q0]x Jr(r_X), so d(u, v)/dr_X = -(e . A), A = [q0]x Jr(r_X)
         const double S[9] = {0.0, -q0[2], q0[1], q0[2], 0.0, -q0[0], -q0[1], q0[0], 0.0};
@@ -437,40 +339,11 @@ __device__ __forceinline__ bool stereo_row(const PnpCamera& cam, const PairBasis
 template <bool SECOND>
 __device__ __forceinline__ void accumulate_view(const IndexedFrame& f, const PnpCamera& cam, const PairBasis& B,
                                                 double (*sj)[kLdsStride], const int* ea, const int* eb, double* acc, bool& behind) {
-    const int lane = threadIdx.x;
-    for (int c0 = 0; c0 < f.n; c0 += kLanes) {
-        const int i = c0 + lane;
-        double ju[13], jv[13];
-#pragma unroll
-        for (int j = 0; j < 13; ++j) ju[j] = jv[j] = 0.0;
-        if (i < f.n) {
-            double mx, my, u, v, ru, rv;
-            f.load(i, mx, my, u, v);
-            if (stereo_row<true, SECOND>(cam, B, mx, my, u, v, ru, rv, ju, jv)) {
-                ju[12] = ru;
-                jv[12] = rv;
-            } else {
-                behind = true;
-#pragma unroll
-                for (int j = 0; j < 13; ++j) ju[j] = jv[j] = 0.0;
-            }
-        }
-        __syncthreads();                     // the previous chunk's rows have been read
-#pragma unroll
-        for (int j = 0; j < 13; ++j) {
-            sj[2 * lane][j] = ju[j];
-            sj[2 * lane + 1][j] = jv[j];
-        }
-        __syncthreads();
-        const int rows = 2 * min(kLanes, f.n - c0);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            if (ea[q] < 0) continue;
-            double s = acc[q];
-            for (int r = 0; r < rows; ++r) s += sj[r][ea[q]] * sj[r][eb[q]];
-            acc[q] = s;
-        }
-    }
+    accumulate_rows<13, 2, kLdsStride>(f.n, [&](int i, double* ju, double* jv) {
+        double mx, my, u, v;
+        f.load(i, mx, my, u, v);
+        return stereo_row<true, SECOND>(cam, B, mx, my, u, v, ju[12], jv[12], ju, jv);
+    }, sj, ea, eb, acc, behind);
 }
 
 __global__ __launch_bounds__(kLanes) void stereo_evaluate_kernel(SPool pl0, SPool pl1, PnpCamera cam0, PnpCamera cam1, Board bd,
@@ -486,18 +359,8 @@ __global__ __launch_bounds__(kLanes) void stereo_evaluate_kernel(SPool pl0, SPoo
     }
     PairBasis B;
     pair_basis<true>(x, p, B);
-    // the entries this lane owns: e = lane + 64 q, (ea, eb) its row and column in the packed 13 x 13
     int ea[2], eb[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        ea[q] = eb[q] = -1;
-        const int e = lane + kLanes * q;
-        if (e >= kEntries) continue;
-        int a = 0, first = 0;
-        while (first + (13 - a) <= e) { first += 13 - a; ++a; }
-        ea[q] = a;
-        eb[q] = a + (e - first);
-    }
+    lane_entries<13, 2>(lane, ea, eb);
     double acc[2] = {0, 0};
     bool behind = false;
     accumulate_view<false>(view_frame(pl0, bd, ws, t, 0), cam0, B, sj, ea, eb, acc, behind);
@@ -516,48 +379,9 @@ __global__ __launch_bounds__(kLanes) void stereo_schur_kernel(Ws ws) {
     const int t = blockIdx.x, lane = threadIdx.x;
     if (ws.st->code == kFinished || !ws.pair[t]) return;
     const double scale = 1.0 + pow(10.0, (double)ws.st->lg);
-    const double* m = ws.m + (long long)t * kEntries;
-    double u[21], rhs[6], xs[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = i; j < 6; ++j) u[pk<6>(i, j)] = m[pk<13>(6 + i, 6 + j)];
-    // lane j < 6: column j of U*^-1 W^T (rhs = row j of W); the other lanes: U*^-1 g_b.  Every lane factors U* itself.
-#pragma unroll
-    for (int k = 0; k < 6; ++k) rhs[k] = lane < 6 ? m[pk<13>(lane, 6 + k)] : m[pk<13>(6 + k, 12)];
-    const bool ok = cholesky_solve(u, rhs, scale, xs);
+    const bool ok = schur_view<6>(ws.m + (long long)t * kEntries, scale, lane, sy, ws.yz + (long long)t * kYZ,
+                                  ws.sc + (long long)t * kSC);
     if (lane == 0) ws.fail[t] = ok ? 0 : 1;
-    double* sc = ws.sc + (long long)t * kSC;
-    if (!ok) {
-        if (lane < kSC) sc[lane] = 0.0;
-        return;
-    }
-    if (lane < 7) {
-        double* yz = ws.yz + (long long)t * kYZ;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            sy[lane][k] = xs[k];
-            if (lane < 6) yz[k * 6 + lane] = xs[k];
-            else yz[36 + k] = xs[k];
-        }
-    }
-    __syncthreads();
-    if (lane < kSC) {                        // entries 0..20: S_t = W U*^-1 W^T (packed 6x6); 21..26: W U*^-1 g_b
-        int a, c;
-        if (lane < 21) {
-            a = 0;
-            int first = 0;
-            while (first + (6 - a) <= lane) { first += 6 - a; ++a; }
-            c = a + (lane - first);
-        } else {
-            a = lane - 21;
-            c = 6;
-        }
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) s += m[pk<13>(a, 6 + k)] * sy[c][k];
-        sc[lane] = s;
-    }
 }
 
 // the step could not be solved: the outputs stay zero but for the counts
@@ -574,9 +398,9 @@ __global__ __launch_bounds__(kLanes) void stereo_reduce_kernel(int batch, Ws ws)
     const int g = blockIdx.x, e = threadIdx.x;
     int src = 0;                             // where value e lives: in the pair's 91 (m) or in its Schur part (sc)
     if (e < 21) {
-        int a = 0, first = 0;
-        while (first + (6 - a) <= e) { first += 6 - a; ++a; }
-        src = pk<13>(a, a + (e - first));
+        int a, c;
+        unpk<6>(e, a, c);
+        src = pk<13>(a, c);
     } else if (e < 27) {
         src = pk<13>(e - 21, 12);
     } else if (e < kTot) {
@@ -688,20 +512,6 @@ __global__ __launch_bounds__(kLanes) void stereo_trial_kernel(SPool pl0, SPool p
     }
 }
 
-// Fixed-order tree over the kRedThreads partials in s (LDS), NV values per thread; the totals end in s[0][0..NV).
-template <int NV>
-__device__ __forceinline__ void block_tree(double (*s)[NV]) {
-    const int t = threadIdx.x;
-    for (int h = kRedThreads / 2; h >= 1; h >>= 1) {
-        __syncthreads();
-        if (t < h) {
-#pragma unroll
-            for (int j = 0; j < NV; ++j) s[t][j] += s[t + h][j];
-        }
-    }
-    __syncthreads();
-}
-
 // init = 1: after the first evaluate (the initial cost); init = 0: after a trial
 __global__ __launch_bounds__(kRedThreads) void stereo_decide_kernel(int batch, int init, double* __restrict__ pose,
                                                                     double* __restrict__ view_info, Ws ws) {
@@ -727,7 +537,7 @@ __global__ __launch_bounds__(kRedThreads) void stereo_decide_kernel(int batch, i
     }
 #pragma unroll
     for (int j = 0; j < 6; ++j) s[t][j] = a[j];
-    block_tree<6>(s);
+    block_tree<kRedThreads, 6>(s);
     const double cost = s[0][0], points = s[0][4];
     if (t == 0) {
         verdict = 0;

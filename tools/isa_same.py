@@ -1,6 +1,9 @@
 """Refactoring aid: is the gfx950 device code of this tree the same as REV's?  Compiles the named translation units of
 deepcharuco_amd/csrc (default dcx_conv_mfma.hip) to assembly with the Makefile's flags, once from this tree and once from
 `git archive REV`, and compares kernel by kernel after dropping the __hip_cuid_ lines (a hash of the source text).  No GPU.
+For a kernel that DIFFERS it also says whether every floating-point arithmetic opcode (the v_*_f64 and v_*_f32 instructions but
+compares and moves) is used as often on both sides: the same counts mean rescheduled, other counts mean recomputed.  The encoding
+suffixes (_e32, _e64, _dpp, _sdwa) are dropped, and v_fmac counts as v_fma: the same operation with the addend's register tied.
 usage: python tools/isa_same.py REV [file.hip ...]      exit status 0 only if every kernel is identical"""
 import collections, os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
@@ -24,8 +27,21 @@ def compile_s(tree, unit, out):
     return "".join(l for l in open(out) if "__hip_cuid_" not in l)
 
 
+def fp_ops(body):
+    """floating-point arithmetic opcode -> how often the body uses it"""
+    n = collections.Counter()
+    for l in body.split("\n"):
+        m = re.match(r"\t(v_\w+)", l)
+        if not m:
+            continue
+        op = re.sub(r"_(e32|e64|dpp|sdwa)$", "", m.group(1)).replace("v_fmac_", "v_fma_")
+        if re.search(r"_f(64|32)$", op) and not re.match(r"v_(cmpx?|mov)_", op):
+            n[op] += 1
+    return n
+
+
 def kernels(s):
-    """name -> (function body + kernel descriptor, resource figures, instruction count)"""
+    """name -> (function body + kernel descriptor, resource figures, instruction count, fp arithmetic opcode counts)"""
     meta = {}
     for item in re.split(r"\n  - (?=\.)", s[s.index("amdhsa.kernels:"):] if "amdhsa.kernels:" in s else ""):
         name = re.search(r"\.name:\s+(\S+)", item)
@@ -37,7 +53,7 @@ def kernels(s):
         start = re.search(r"^%s:[^\n]*\n" % re.escape(sym), s, re.M).end()
         body = s[start:s.index(".Lfunc_end", start)]
         n_ins = sum(1 for l in body.split("\n") if l.startswith("\t") and not l.strip().startswith((".", ";")))
-        res[sym] = (body + m.group(0), meta.get(sym, {}), n_ins)
+        res[sym] = (body + m.group(0), meta.get(sym, {}), n_ins, fp_ops(body))
     return res
 
 
@@ -71,8 +87,10 @@ def main():
                 else:
                     figs = "same" if ka[sym][1] == kb[sym][1] else " ".join(
                         "%s %d->%d" % (f, ka[sym][1].get(f, -1), kb[sym][1].get(f, -1)) for f in FIGS if ka[sym][1].get(f) != kb[sym][1].get(f))
-                    print("  DIFFERS    %s   resource figures: %s   instructions: %d -> %d (%+d)"
-                          % (sym, figs, ka[sym][2], kb[sym][2], kb[sym][2] - ka[sym][2]))
+                    fa, fb = ka[sym][3], kb[sym][3]
+                    fp = "same" if fa == fb else " ".join("%s %d->%d" % (o, fa[o], fb[o]) for o in sorted(set(fa) | set(fb)) if fa[o] != fb[o])
+                    print("  DIFFERS    %s   resource figures: %s   instructions: %d -> %d (%+d, %+.2f %%)   fp arithmetic opcode counts: %s"
+                          % (sym, figs, ka[sym][2], kb[sym][2], kb[sym][2] - ka[sym][2], 100.0 * (kb[sym][2] - ka[sym][2]) / max(ka[sym][2], 1), fp))
     print("%d of %d kernels identical" % (n_same, n_all))
     sys.exit(0 if n_same == n_all and n_all > 0 else 1)
 
