@@ -401,6 +401,40 @@ int dcx_rectify_points_pool(const int32_t* d_rows, const float* d_xy /* NULL = u
 int dcx_remap_u8(const uint8_t* d_src, long frame_stride, int pitch, int src_h, int src_w, int channels /* 1 or 3 */,
                  const int32_t* d_map, int out_h, int out_w, int batch, int border, uint8_t* d_out, void* stream);
 
+/* ---- dense stereo matching on a rectified pair, and the disparity map as 3-D points ------------------------------------------
+ * What follows dcx_remap_u8: semi-global matching (what cv2.StereoSGBM is called for) over 9 x 7 census costs, integer throughout
+ * and bit-exact against deepcharuco_amd/disparity.py:sgm_host, which states every step.  d_left is rectified camera 0 and d_right
+ * rectified camera 1 of a horizontal rig (a vertical rig passes transposed frames); the disparity d = x_left - x_right is the d of
+ * Q.  Both are u8 gray frames, rows pitch_* bytes apart and frames frame_stride_* bytes apart, each image its own (pitch >= width,
+ * else DCX_E_SHAPE).  num_disparities D is 64, 128 or 256, 1 <= width <= 4096, 1 <= height <= 32768 (DCX_E_SHAPE);
+ * 0 <= p1 <= p2 <= 255, 0 <= uniqueness < 100, -2047 <= min_disparity and min_disparity + D <= 2047 (DCX_E_ARG);
+ * lr_max_diff < 0 switches the left-right check off.  d_disp16 int16 [batch][height][width], dense: the disparity times 16,
+ * 16 (min_disparity - 1) where invalid (cv2's convention).
+ *
+ * Steps: census words (62 bits: neighbour < centre, rows top to bottom, columns left to right, the first neighbour most
+ * significant, edge-replicated); C(y, x, d) = popcount(cenL[y][x] ^ cenR[y][clamp(x - m - d, 0, W - 1)]); four paths (both
+ * directions along rows and columns) L(p, d) = C + min(L(q, d), L(q, d - 1) + p1, L(q, d + 1) + p1, M + p2) - M with
+ * M = min_k L(q, k), summed into S (u16); the winner d* = the lowest d of the smallest S; invalid if x - m - d* leaves the row, if
+ * some d with |d - d*| > 1 has S[d] (100 - uniqueness) < S[d*] 100, or if the right view's winner at x - m - d* (the lowest d of
+ * the smallest S(y, xr + m + d, d)) is more than lr_max_diff from d*; sub-pixel off = floor((16 num + den) / (2 den)) with
+ * num = S[d*-1] - S[d*+1], den = S[d*-1] + S[d*+1] - 2 S[d*], where 0 < d* < D - 1 and den > 0; the value is 16 (m + d*) + off.
+ *
+ * d_workspace (8-byte aligned, DCX_E_ARG otherwise): dcx_sgm_workspace_bytes(batch, ...) = batch * height * width * (16 + 2 D)
+ * bytes take the batch in one pass of four launches; with fewer bytes the batch is taken in chunks of as many frames as fit, and
+ * with less than one frame's the call is refused (DCX_E_WS).  Launches on `stream` only: no allocation, no synchronisation, no
+ * global atomics, so two calls give the same bits and a call can be captured in a hipGraph.
+ *
+ * dcx_disparity_to_points (cv2.reprojectImageTo3D): one thread per pixel; with d = disp16 / 16 and h = Q (x, y, d, 1)^T, each row
+ * summed left to right in fp64 without contraction, d_xyz f32 [batch][height][width][3] = h[0..2] / h[3], rounded to float once;
+ * NaN where disp16 < 16 min_disparity (invalid) or disp16 == 0.  h_Q16: 4x4 row major, finite (DCX_E_ARG otherwise), copied into
+ * the kernel arguments at the call.                                                                                           */
+size_t dcx_sgm_workspace_bytes(int batch, int height, int width, int num_disparities);   /* 0 for refused arguments */
+int dcx_sgm_u8(const uint8_t* d_left, long frame_stride_l, int pitch_l, const uint8_t* d_right, long frame_stride_r, int pitch_r,
+               int batch, int height, int width, int min_disparity, int num_disparities, int p1, int p2, int uniqueness,
+               int lr_max_diff, int16_t* d_disp16, void* d_workspace, size_t workspace_bytes, void* stream);
+int dcx_disparity_to_points(const int16_t* d_disp16, int batch, int height, int width, int min_disparity,
+                            const double* h_Q16 /* 4x4 row major */, float* d_xyz /* [batch][height][width][3] */, void* stream);
+
 /* ---- stage-level entry point for kernel tests / roofline measurement -------------------
  * One 3x3 (or 1x1) convolution + bias [+ eval-BN + ReLU] [+ 2x2 max-pool] on C4 tensors
  * using the same MFMA kernel the networks use.  h_* are host arrays in PyTorch layout;
