@@ -1,0 +1,90 @@
+"""The joint Levenberg-Marquardt driver of the two calibration definitions (``calib.py`` over 9 intrinsics, ``stereo.py`` over the 6
+rig parameters), one copy: g holds the global parameters, P [N, 6] one pose per unit (a view, a pair) that couples only to g.
+csrc/dcx_lm_dev.h is the same driver for the kernels; tests/test_lm_host.py walks both through the same scripts.
+
+The CvLevMarq rules: damping diag * (1 + 10^lg), lg from -3; a step whose cost is not <= the cost before is rejected: lg + 1 and
+the same point is tried again, up to lg = 16; at 17 the step is taken whatever it costs (forced); an accepted or forced step takes
+lg - 1, down to -16; at most ``max_iter`` accepted steps; stop at |dp| < eps |p| over all parameters.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from .pnp import _cholesky_solve
+
+# the overall status: calib's CALIB_* and stereo's STEREO_* are these numbers (include/deepcharuco_amd.h)
+LM_OK, LM_NO_UNITS, LM_DEGENERATE, LM_NONFINITE = range(4)
+
+
+def schur_step(U, W, V, ga, gb, lg: int):
+    """Solve [V* W; W^T U*] [dg; dP] = [ga; gb] with the diagonals of V and of every U_i scaled by 1 + 10^lg (Marquardt), by
+    eliminating the pose blocks: S = V* - sum W_i U_i*^-1 W_i^T, dg = S^-1 (ga - sum W_i U_i*^-1 gb_i),
+    dP_i = U_i*^-1 (gb_i - W_i^T dg).  U [N, 6, 6], W [N, n, 6], V [n, n] for any n.  -> (dg [n], dP [N, 6]), or None if a block is
+    not positive definite."""
+    s = 1.0 + 10.0 ** lg
+    Us = U.copy()
+    d6 = np.arange(6)
+    Us[:, d6, d6] *= s
+    try:
+        np.linalg.cholesky(Us)
+    except np.linalg.LinAlgError:
+        return None
+    Y = np.linalg.solve(Us, W.transpose(0, 2, 1))                  # U_i*^-1 W_i^T  [N, 6, n]
+    z = np.linalg.solve(Us, gb[:, :, None])[:, :, 0]              # U_i*^-1 gb_i   [N, 6]
+    S = V.copy()
+    S[np.diag_indices(V.shape[0])] *= s
+    S -= np.einsum("nij,njk->ik", W, Y)
+    rhs = ga - np.einsum("nij,nj->i", W, z)
+    dg = _cholesky_solve(S, rhs)
+    if dg is None:
+        return None
+    return dg, z - np.einsum("nij,j->ni", Y, dg)
+
+
+def refine(g, P, normal_blocks, trial_costs, total, stop_forced: bool, max_iter: int, eps: float):
+    """-> (status LM_*, g, P, the units' costs at the solution or None, accepted steps, attempts).
+
+    ``normal_blocks(g, P)`` -> (U, W, V, ga, gb, costs) as ``schur_step`` takes them, or None if a point is behind a camera;
+    ``trial_costs(g, P)`` -> the units' costs, or None for the same reason (the cost is then inf); ``total(costs)`` adds them up
+    in the caller's order.  ``stop_forced``: a step forced at lg > 16 that leaves a point behind a camera ends the solve
+    (DEGENERATE, NONFINITE if a parameter is not finite): there are no normal equations to go on from.  Without it that case is
+    not handled here (``normal_blocks`` must not answer None after an accepted step)."""
+    blocks = normal_blocks(g, P)
+    if blocks is None or not math.isfinite(total(blocks[5])):
+        return LM_DEGENERATE, g, P, None, 0, 0
+    vc = blocks[5]
+    prev_cost, lg, iters, attempts = total(vc), -3, 0, 0
+    while True:
+        U, W, V, ga, gb, _ = blocks
+        prev_g, prev_p = g, P
+        while True:
+            step = schur_step(U, W, V, ga, gb, lg)
+            if step is None:
+                return LM_DEGENERATE, g, P, None, iters, attempts
+            g, P = prev_g - step[0], prev_p - step[1]
+            vc = trial_costs(g, P)
+            cost = total(vc) if vc is not None else math.inf
+            attempts += 1
+            if not cost <= prev_cost:              # (a point behind a camera: cost = inf, rejected like an increase)
+                lg += 1
+                if lg <= 16:
+                    continue
+            break
+        lg = max(lg - 1, -16)
+        iters += 1
+        d = np.r_[g - prev_g, (P - prev_p).ravel()]
+        pv = np.r_[prev_g, prev_p.ravel()]
+        if iters >= max_iter or math.sqrt(float(d @ d)) < eps * math.sqrt(float(pv @ pv)):
+            break
+        prev_cost = cost
+        blocks = normal_blocks(g, P)
+        if blocks is None and stop_forced:         # forced at lg > 16 with a point behind a camera: nothing to go on from
+            bad = not (np.isfinite(g).all() and np.isfinite(P).all())
+            return (LM_NONFINITE if bad else LM_DEGENERATE), g, P, None, iters, attempts
+    if not (np.isfinite(g).all() and np.isfinite(P).all()) or math.isnan(cost):
+        return LM_NONFINITE, g, P, None, iters, attempts
+    if not math.isfinite(cost):
+        return LM_DEGENERATE, g, P, None, iters, attempts
+    return LM_OK, g, P, vc, iters, attempts

@@ -40,12 +40,12 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import pnp
-from .pnp import (PNP_BAD_ID, PNP_DEGENERATE, PNP_NO_CONSENSUS, PNP_NONFINITE, PNP_OK, PNP_TOO_FEW, _cholesky_solve, _homography,
+from . import _lm, pnp
+from .pnp import (PNP_BAD_ID, PNP_DEGENERATE, PNP_NO_CONSENSUS, PNP_NONFINITE, PNP_OK, PNP_TOO_FEW, _bad_id_error, _homography,
                   _project, _rodrigues, _solve)
 
 # overall status (include/deepcharuco_amd.h); per-view statuses are pnp's PNP_*
-CALIB_OK, CALIB_NO_VIEWS, CALIB_DEGENERATE, CALIB_NONFINITE = range(4)
+CALIB_OK, CALIB_NO_VIEWS, CALIB_DEGENERATE, CALIB_NONFINITE = _lm.LM_OK, _lm.LM_NO_UNITS, _lm.LM_DEGENERATE, _lm.LM_NONFINITE
 CALIB_MAX_ITER = 30
 CALIB_EPS = float(np.finfo(np.float64).eps)
 N_INTR = 9                     # fx, fy, cx, cy, k1, k2, p1, p2, k3
@@ -201,28 +201,7 @@ def _normal_blocks(views, theta: np.ndarray, poses: np.ndarray):
     return U, W, V, ga, gb, costs
 
 
-def _schur_step(U, W, V, ga, gb, lg: int):
-    """Solve [V* W; W^T U*] [dtheta; dpose] = [ga; gb] with the diagonals of V and of every U_i scaled by 1 + 10^lg (Marquardt),
-    by eliminating the pose blocks: S = V* - sum W_i U_i*^-1 W_i^T, dtheta = S^-1 (ga - sum W_i U_i*^-1 gb_i),
-    dpose_i = U_i*^-1 (gb_i - W_i^T dtheta).  -> (dtheta [9], dpose [N, 6]), or None if a block is not positive definite."""
-    s = 1.0 + 10.0 ** lg
-    Us = U.copy()
-    d6 = np.arange(6)
-    Us[:, d6, d6] *= s
-    try:
-        np.linalg.cholesky(Us)
-    except np.linalg.LinAlgError:
-        return None
-    Y = np.linalg.solve(Us, W.transpose(0, 2, 1))                  # U_i*^-1 W_i^T  [N, 6, 9]
-    z = np.linalg.solve(Us, gb[:, :, None])[:, :, 0]              # U_i*^-1 gb_i   [N, 6]
-    S = V.copy()
-    S[np.diag_indices(N_INTR)] *= s
-    S -= np.einsum("nij,njk->ik", W, Y)
-    rhs = ga - np.einsum("nij,nj->i", W, z)
-    dt = _cholesky_solve(S, rhs)
-    if dt is None:
-        return None
-    return dt, z - np.einsum("nij,j->ni", Y, dt)
+_schur_step = _lm.schur_step     # one copy, generic in the global block's size
 
 
 def _view_costs(views, theta, poses) -> np.ndarray:
@@ -238,40 +217,8 @@ def _total(costs: np.ndarray) -> float:
 
 def _refine(views, theta: np.ndarray, poses: np.ndarray):
     """Joint LM (module docstring, step 4) -> (status, theta, poses, per-view costs, accepted steps, attempts)."""
-    blocks = _normal_blocks(views, theta, poses)
-    if blocks is None or not math.isfinite(_total(blocks[5])):
-        return CALIB_DEGENERATE, theta, poses, None, 0, 0
-    vc = blocks[5]
-    prev_cost, lg, iters, attempts = _total(vc), -3, 0, 0
-    while True:
-        U, W, V, ga, gb, _ = blocks
-        prev_t, prev_p = theta, poses
-        while True:
-            step = _schur_step(U, W, V, ga, gb, lg)
-            if step is None:
-                return CALIB_DEGENERATE, theta, poses, None, iters, attempts
-            theta, poses = prev_t - step[0], prev_p - step[1]
-            vc = _view_costs(views, theta, poses)
-            cost = _total(vc)
-            attempts += 1
-            if not cost <= prev_cost:              # (a point behind the camera: cost = inf, rejected like an increase)
-                lg += 1
-                if lg <= 16:
-                    continue
-            break
-        lg = max(lg - 1, -16)
-        iters += 1
-        d = np.r_[theta - prev_t, (poses - prev_p).ravel()]
-        pv = np.r_[prev_t, prev_p.ravel()]
-        if iters >= CALIB_MAX_ITER or math.sqrt(float(d @ d)) < CALIB_EPS * math.sqrt(float(pv @ pv)):
-            break
-        prev_cost = cost
-        blocks = _normal_blocks(views, theta, poses)
-    if not (np.isfinite(theta).all() and np.isfinite(poses).all()) or math.isnan(cost):
-        return CALIB_NONFINITE, theta, poses, None, iters, attempts
-    if not math.isfinite(cost):
-        return CALIB_DEGENERATE, theta, poses, None, iters, attempts
-    return CALIB_OK, theta, poses, vc, iters, attempts
+    return _lm.refine(theta, poses, lambda t, p: _normal_blocks(views, t, p), lambda t, p: _view_costs(views, t, p), _total,
+                      False, CALIB_MAX_ITER, CALIB_EPS)
 
 
 def _views(object_points, image_points):
@@ -458,11 +405,9 @@ def calibrate_camera_ransac_host_full(keypoints_list, col_count, row_count, squa
     orders, obj32, img32, masks = [None] * B, [None] * B, [None] * B, [None] * B
     margin = math.inf
     for b, kp in enumerate(keypoints_list):
-        kp = np.asarray(kp)
-        kp = kp.reshape(-1, 3) if kp.size else np.zeros((0, 3))
+        kp, orders[b] = pnp._pool_rows(kp, pool_order)
         n = offered[b] = kp.shape[0]
         masks[b] = np.zeros(n, bool)
-        orders[b] = np.arange(n) if pool_order else np.argsort(kp[:, 2], kind="stable")
         if n < 4:
             vstat[b] = PNP_TOO_FEW
             continue
@@ -516,10 +461,6 @@ def calibrate_camera_ransac_host_full(keypoints_list, col_count, row_count, squa
     return (out, margin) if with_margin else out
 
 
-def _bad_id_error(col_count, row_count):
-    return IndexError(f"corner id outside [0, {(col_count - 1) * (row_count - 1)}) for a {col_count}x{row_count} board")
-
-
 def calibrate_camera_ransac_host(keypoints_list, col_count, row_count, square_len, image_size, iterations=100, consensus_error=8.0,
                                  reproj_error=3.0, min_inliers=6, rounds=2, seed=0):
     """cv2's 5-tuple plus the masks: ``(rms, K 3x3, dist 1x5, rvecs, tvecs, inliers)``.  Raises like ``calibrate_camera_host``:
@@ -555,19 +496,15 @@ def calibrate_charuco_pool(packed, batch: int, pool: int, refined: bool, col_cou
     from . import _lib
     w, h = _image_size(image_size)
     dev = packed.device
-    if packed.dtype != torch.int32 or not packed.is_contiguous() or packed.numel() < 2 * batch + (6 if refined else 4) * pool:
-        raise ValueError("packed must be a contiguous int32 corner pool of at least packed_len(batch, pool) words")
+    ptrs = pnp._pool_ptrs(packed, batch, pool, refined)
     st = torch.empty((batch,), dtype=torch.int32, device=dev)
     pose = torch.empty((batch, pnp.POSE_WORDS), dtype=torch.float64, device=dev)
     nbytes = workspace_bytes(batch)
     ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
     res = (_ctypes.c_double * RESULT_WORDS)()
-    base = packed.data_ptr()
-    rows_p = base + 8 * batch
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().dcx_calibrate_pool(base, base + 4 * batch, rows_p, rows_p + 16 * pool if refined else None,
-                                                 int(batch), int(pool), int(col_count), int(row_count), float(square_len), w, h,
-                                                 ws.data_ptr(), nbytes, st.data_ptr(), pose.data_ptr(), res,
+        _lib.check(_lib.lib().dcx_calibrate_pool(*ptrs, int(batch), int(pool), int(col_count), int(row_count), float(square_len),
+                                                 w, h, ws.data_ptr(), nbytes, st.data_ptr(), pose.data_ptr(), res,
                                                  _lib.current_stream()), "dcx_calibrate_pool")
         st_h, pose_h = st.cpu().numpy(), pose.cpu().numpy()
     r = np.array(res[:], np.float64)
@@ -592,8 +529,7 @@ def calibrate_charuco_device(keypoints_list: Sequence, col_count, row_count, squ
     with torch.cuda.device(dev):
         r = calibrate_charuco_pool(packed, b, pool, True, col_count, row_count, square_len, image_size)
     if (r.view_status == PNP_BAD_ID).any():
-        n = (col_count - 1) * (row_count - 1)
-        raise IndexError(f"corner id outside [0, {n}) for a {col_count}x{row_count} board")
+        raise _bad_id_error(col_count, row_count)
     return r
 
 
@@ -622,8 +558,7 @@ def calibrate_charuco_ransac_pool(packed, batch: int, pool: int, refined: bool, 
     w, h = _image_size(image_size)
     iterations, cthr, rthr, min_inliers, rounds = _calib_ransac_args(iterations, consensus_error, reproj_error, min_inliers, rounds)
     dev = packed.device
-    if packed.dtype != torch.int32 or not packed.is_contiguous() or packed.numel() < 2 * batch + (6 if refined else 4) * pool:
-        raise ValueError("packed must be a contiguous int32 corner pool of at least packed_len(batch, pool) words")
+    ptrs = pnp._pool_ptrs(packed, batch, pool, refined)
     if out_inliers is None:
         out_inliers = torch.zeros((max(pool, 1),), dtype=torch.uint8, device=dev)
     if (out_inliers.device != dev or out_inliers.dtype != torch.uint8 or out_inliers.numel() < pool
@@ -635,12 +570,10 @@ def calibrate_charuco_ransac_pool(packed, batch: int, pool: int, refined: bool, 
     nbytes = ransac_workspace_bytes(batch, pool, iterations)
     ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev)
     res = (_ctypes.c_double * RESULT_WORDS)()
-    base = packed.data_ptr()
-    rows_p = base + 8 * batch
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().dcx_calibrate_ransac_pool(
-            base, base + 4 * batch, rows_p, rows_p + 16 * pool if refined else None, int(batch), int(pool), int(col_count),
-            int(row_count), float(square_len), w, h, iterations, cthr, rthr, min_inliers, rounds, int(seed) & 0xFFFFFFFF,
+            *ptrs, int(batch), int(pool), int(col_count), int(row_count), float(square_len), w, h, iterations, cthr, rthr,
+            min_inliers, rounds, int(seed) & 0xFFFFFFFF,
             ws.data_ptr(), nbytes, st.data_ptr(), pose.data_ptr(), info.data_ptr(), out_inliers.data_ptr(), res,
             _lib.current_stream()), "dcx_calibrate_ransac_pool")
         st_h, pose_h, info_h, inl_h, head = (t.cpu().numpy() for t in (st, pose, info, out_inliers, packed[:2 * batch]))
@@ -674,10 +607,5 @@ def calibrate_charuco_ransac_device(keypoints_list: Sequence, col_count, row_cou
                                           consensus_error, reproj_error, min_inliers, rounds, seed)
     if (r.view_status == PNP_BAD_ID).any():
         raise _bad_id_error(col_count, row_count)
-    inliers = []
-    for kp, mask in zip(keypoints_list, r.inliers):
-        kp = np.asarray(kp)
-        if mask.size:                                         # undo _pack's stable id sort
-            mask = mask[np.argsort(np.argsort(kp.reshape(-1, 3)[:, 2], kind="stable"), kind="stable")]
-        inliers.append(mask)
-    return r._replace(inliers=inliers)
+    # undo _pack's stable id sort
+    return r._replace(inliers=[mask[pnp._caller_order(kp)] for kp, mask in zip(keypoints_list, r.inliers)])

@@ -28,26 +28,21 @@
 // Shared with dcx_stereo.hip through dcx_mat_dev.h: schur's body (schur_view), the lane's entries (lane_entries), the one-workgroup
 // tree (block_tree), the workspace carver; evaluate's LDS-staged loop mirrors accumulate_rows there (see the kernel).  The camera
 // model, its derivative and the pose columns are dcx_camera_dev.h's (project, pose_basis, pose_columns); project_point() below
-// adds the nine intrinsic columns.
+// adds the nine intrinsic columns.  The LM machinery is dcx_lm_dev.h's, shared with dcx_stereo.hip: the state and the accept /
+// reject / forced / stop automaton (LmState<9>, lm_decide with STOP_FORCED = false), decide's body (lm_decide_block), trial's
+// prologue (lm_trial_pose), reduce_solve's entry -> source mapping (lm_source), the damping and the host loop (lm_run).  The
+// reduction in front of the 9x9 solve (8 slices x 128, added serially) is this unit's own: its order is part of the output bits.
 #include "dcx_pnp_dev.h"
+#include "dcx_lm_dev.h"
 
 namespace {
 
-constexpr int kCalibMaxIter = 30;
-constexpr double kCalibEps = 2.220446049250313e-16;      // DBL_EPSILON
-constexpr int kRedThreads = 1024;                         // one-workgroup reductions over views
+constexpr int kRedThreads = kLmThreads;                   // one-workgroup reductions over views
 constexpr int kSlices = kRedThreads / 128;                // reduce_solve: 8 view slices x 128 entry slots
 constexpr int kEntries = 136;                             // packed 16x16: [J_theta (9) | J_pose (6) | r]
 constexpr int kCost = 135;                                // pk<16>(15, 15)
 
-enum : int { kNextEvaluate = 0, kNextSchur = 1, kFinished = 2 };
-
-struct CalibState {
-    double theta[9], theta_trial[9], dtheta[9];
-    double prev_cost;
-    double result[16];       // h_result
-    int lg, iters, attempts, code;
-};
+using CalibState = LmState<9>;             // g = theta; result = h_result
 
 // per-view workspace, in doubles
 constexpr int kRows = 6;                 // the two init rows (a0, a1, b) x 2
@@ -175,11 +170,7 @@ __global__ __launch_bounds__(kRedThreads) void calib_init_reduce_kernel(int batc
     if (t != 0) return;
     CalibState* st = ws.st;
     const double a00 = s[0][0], a01 = s[0][1], a11 = s[0][2], b0 = s[0][3], b1 = s[0][4];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) st->result[i] = 0.0;
-    st->lg = -3;
-    st->iters = 0;
-    st->attempts = 0;
+    lm_reset(st);
     st->result[12] = s[0][5];
     st->result[13] = s[0][6];
     if (s[0][5] == 0.0) {
@@ -197,14 +188,14 @@ __global__ __launch_bounds__(kRedThreads) void calib_init_reduce_kernel(int batc
     }
     const double th[9] = {fx, fy, cx, cy, 0, 0, 0, 0, 0};
 #pragma unroll
-    for (int i = 0; i < 9; ++i) st->theta[i] = th[i];
+    for (int i = 0; i < 9; ++i) st->g[i] = th[i];
     st->code = kNextEvaluate;
 }
 
 __global__ __launch_bounds__(kLanes) void calib_init_poses_kernel(Pool pl, int32_t* __restrict__ status, Ws ws) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (ws.st->code == kFinished || status[b] != DCX_PNP_OK) return;
-    const PnpCamera cam = camera_of(ws.st->theta);       // K0, zero distortion
+    const PnpCamera cam = camera_of(ws.st->g);       // K0, zero distortion
     double out[8];
     const int st = solve(pl.frame(b), cam, out);
     if (lane == 0) {
@@ -246,7 +237,7 @@ __global__ __launch_bounds__(kLanes) void calib_evaluate_kernel(Pool pl, const i
     const int b = blockIdx.x, lane = threadIdx.x;
     if (ws.st->code != kNextEvaluate || status[b] != DCX_PNP_OK) return;
     const Frame f = pl.frame(b);
-    const PnpCamera cam = camera_of(ws.st->theta);
+    const PnpCamera cam = camera_of(ws.st->g);
     double p[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) p[i] = ws.pose[(long long)b * 6 + i];
@@ -305,18 +296,10 @@ __global__ __launch_bounds__(kLanes) void calib_schur_kernel(const int32_t* __re
     __shared__ double sy[10][6];             // U*^-1 W^T's 9 columns, then U*^-1 g_b
     const int b = blockIdx.x, lane = threadIdx.x;
     if (ws.st->code == kFinished || status[b] != DCX_PNP_OK) return;
-    const double scale = 1.0 + pow(10.0, (double)ws.st->lg);
+    const double scale = lm_damping(ws.st->lg);
     const bool ok = schur_view<9>(ws.m + (long long)b * kEntries, scale, lane, sy, ws.yz + (long long)b * kYZ,
                                   ws.sc + (long long)b * kSC);
     if (lane == 0) ws.fail[b] = ok ? 0 : 1;
-}
-
-// the step could not be solved: the outputs stay zero but for the counts
-__device__ __forceinline__ void fail(CalibState* st, int status) {
-    st->result[10] = st->iters;
-    st->result[11] = st->attempts;
-    st->result[14] = status;
-    st->code = kFinished;
 }
 
 __global__ __launch_bounds__(kRedThreads) void calib_reduce_solve_kernel(int batch, const int32_t* __restrict__ status, Ws ws) {
@@ -330,16 +313,7 @@ __global__ __launch_bounds__(kRedThreads) void calib_reduce_solve_kernel(int bat
     if (st->code == kFinished) return;
     const int t = threadIdx.x, e = t % 128, sl = t / 128;
     if (e < kTot) {
-        int src;                             // where entry e lives: in the view's 136 (m) or in its Schur part (sc)
-        if (e < 45) {
-            int a, c;
-            unpk<9>(e, a, c);
-            src = pk<16>(a, c);
-        } else if (e < 54) {
-            src = pk<16>(e - 45, 15);
-        } else {
-            src = e - 54;
-        }
+        const int src = lm_source<9>(e);     // where entry e lives: in the view's 136 (m) or in its Schur part (sc)
         double s = 0.0;
         int f = 0;
         for (int b = sl; b < batch; b += kSlices) {
@@ -360,10 +334,10 @@ __global__ __launch_bounds__(kRedThreads) void calib_reduce_solve_kernel(int bat
     }
     for (int k = 0; k < kSlices; ++k) anybad |= bad[k];
     if (anybad) {
-        fail(st, DCX_CALIB_DEGENERATE);
+        lm_fail(st, DCX_CALIB_DEGENERATE);
         return;
     }
-    const double scale = 1.0 + pow(10.0, (double)st->lg);
+    const double scale = lm_damping(st->lg);
     for (int a = 0; a < 9; ++a) {
         for (int c = a; c < 9; ++c) S[pk<9>(a, c)] = tot[pk<9>(a, c)] * (a == c ? scale : 1.0) - tot[54 + pk<9>(a, c)];
         rhs[a] = tot[45 + a] - tot[99 + a];
@@ -374,7 +348,7 @@ __global__ __launch_bounds__(kRedThreads) void calib_reduce_solve_kernel(int bat
             for (int k = 0; k < j; ++k) s -= L[pk<9>(i, k)] * L[pk<9>(j, k)];
             if (i == j) {
                 if (!(s > 0)) {
-                    fail(st, DCX_CALIB_DEGENERATE);
+                    lm_fail(st, DCX_CALIB_DEGENERATE);
                     return;
                 }
                 L[pk<9>(i, i)] = sqrt(s);
@@ -394,14 +368,17 @@ __global__ __launch_bounds__(kRedThreads) void calib_reduce_solve_kernel(int bat
         x[i] = s / L[pk<9>(i, i)];
     }
     for (int i = 0; i < 9; ++i) {
-        st->dtheta[i] = x[i];
-        st->theta_trial[i] = st->theta[i] - x[i];
+        st->dg[i] = x[i];
+        st->g_trial[i] = st->g[i] - x[i];
     }
 }
 
 __global__ __launch_bounds__(kLanes) void calib_trial_kernel(Pool pl, const int32_t* __restrict__ status, Ws ws) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (ws.st->code == kFinished || status[b] != DCX_PNP_OK) return;
+    // dcx_lm_dev.h's lm_trial_pose<9>, spelt out: called through it, this kernel's SGPR spills rise from 38 to 62 (the 75 uniform
+    // doubles of yz, dtheta and the pose do not fit the scalar registers and the compiler then orders their loads otherwise).  The
+    // stereo solve runs the shared prologue; a change there is a change here.
     const double* yz = ws.yz + (long long)b * kYZ;
     double p0[6], p[6];
     double dn = 0.0, pn = 0.0;
@@ -409,13 +386,13 @@ __global__ __launch_bounds__(kLanes) void calib_trial_kernel(Pool pl, const int3
     for (int k = 0; k < 6; ++k) {
         double s = yz[54 + k];
 #pragma unroll
-        for (int j = 0; j < 9; ++j) s -= yz[k * 9 + j] * ws.st->dtheta[j];
+        for (int j = 0; j < 9; ++j) s -= yz[k * 9 + j] * ws.st->dg[j];
         p0[k] = ws.pose[(long long)b * 6 + k];
         p[k] = p0[k] - s;
         dn += (p[k] - p0[k]) * (p[k] - p0[k]);
         pn += p0[k] * p0[k];
     }
-    const PnpCamera cam = camera_of(ws.st->theta_trial);
+    const PnpCamera cam = camera_of(ws.st->g_trial);
     const Frame f = pl.frame(b);
     double R[9];
     rodrigues(p, R);
@@ -442,103 +419,20 @@ __global__ __launch_bounds__(kLanes) void calib_trial_kernel(Pool pl, const int3
 // init = 1: after the first evaluate (the initial cost); init = 0: after a trial
 __global__ __launch_bounds__(kRedThreads) void calib_decide_kernel(int batch, int init, const int32_t* __restrict__ status,
                                                                    double* __restrict__ pose, Ws ws) {
-    __shared__ double s[kRedThreads][6];     // cost, |dp|^2, |p|^2, views, points, non-finite poses
-    __shared__ int verdict;                  // 0: nothing to commit, 1: commit and continue, 2: commit and finish
-    CalibState* st = ws.st;
-    if (st->code == kFinished) return;
-    const int t = threadIdx.x;
-    double a[6] = {0, 0, 0, 0, 0, 0};
-    for (int b = t; b < batch; b += kRedThreads) {
-        if (status[b] != DCX_PNP_OK) continue;
-        if (init) {
-            a[0] += ws.m[(long long)b * kEntries + kCost];
-        } else {
+    lm_decide_block<9, false>(
+        ws.st, batch, init, ws.pose, ws.trial_pose, [&](int b) { return status[b] == DCX_PNP_OK; },
+        [&](int b) { return ws.m[(long long)b * kEntries + kCost]; },
+        [&](int b, double* a) {
             const double* tr = ws.trial + (long long)b * 3;
             a[0] += tr[0]; a[1] += tr[1]; a[2] += tr[2];
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-                if (!isfinite(ws.trial_pose[(long long)b * 6 + k])) a[5] = 1.0;
-        }
-        a[3] += 1.0;
-        a[4] += pose[8 * (long long)b + 7];
-    }
-#pragma unroll
-    for (int j = 0; j < 6; ++j) s[t][j] = a[j];
-    block_tree<kRedThreads, 6>(s);
-    const double cost = s[0][0], views = s[0][3], points = s[0][4];
-    if (t == 0) {
-        verdict = 0;
-        st->result[12] = views;
-        st->result[13] = points;
-        if (init) {
-            if (views == 0.0) {
-                st->result[14] = DCX_CALIB_NO_VIEWS;
-                st->code = kFinished;
-            } else if (!isfinite(cost)) {
-                st->result[14] = DCX_CALIB_DEGENERATE;
-                st->code = kFinished;
-            } else {
-                st->prev_cost = cost;
-                st->code = kNextSchur;
-            }
-        } else {
-            st->attempts += 1;
-            bool forced = false;
-            if (!(cost <= st->prev_cost)) {  // (a point behind the camera: cost = inf, rejected like an increase)
-                if (++st->lg <= 16) {
-                    st->code = kNextSchur;   // retry from the same point with more damping
-                } else {
-                    forced = true;
-                }
-            } else {
-                forced = true;
-            }
-            if (forced) {
-                st->lg = max(st->lg - 1, -16);
-                st->iters += 1;
-                double dn = s[0][1], pn = s[0][2];
-                bool bad = s[0][5] != 0.0;
-                for (int i = 0; i < 9; ++i) {
-                    const double d = st->theta_trial[i] - st->theta[i];
-                    dn += d * d;
-                    pn += st->theta[i] * st->theta[i];
-                    st->theta[i] = st->theta_trial[i];
-                    bad |= !isfinite(st->theta[i]);
-                }
-                if (st->iters >= kCalibMaxIter || sqrt(dn) < kCalibEps * sqrt(pn)) {
-                    int res = DCX_CALIB_OK;
-                    if (bad || isnan(cost)) res = DCX_CALIB_NONFINITE;
-                    else if (!isfinite(cost)) res = DCX_CALIB_DEGENERATE;
-                    if (res == DCX_CALIB_OK) {
-                        for (int i = 0; i < 9; ++i) st->result[i] = st->theta[i];
-                        st->result[9] = sqrt(cost / points);
-                    }
-                    st->result[10] = st->iters;
-                    st->result[11] = st->attempts;
-                    st->result[14] = res;
-                    st->code = kFinished;
-                    verdict = res == DCX_CALIB_OK ? 2 : 1;
-                } else {
-                    st->prev_cost = cost;
-                    st->code = kNextEvaluate;
-                    verdict = 1;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    if (verdict == 0) return;
-    for (int b = t; b < batch; b += kRedThreads) {
-        if (status[b] != DCX_PNP_OK) continue;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) ws.pose[(long long)b * 6 + k] = ws.trial_pose[(long long)b * 6 + k];
-        if (verdict == 2) {
+        },
+        [&](int b) { return pose[8 * (long long)b + 7]; },
+        [&](int b) {
             double* o = pose + 8 * (long long)b;
 #pragma unroll
             for (int k = 0; k < 6; ++k) o[k] = ws.trial_pose[(long long)b * 6 + k];
             o[6] = sqrt(ws.trial[(long long)b * 3] / o[7]);
-        }
-    }
+        });
 }
 
 }  // namespace
@@ -567,20 +461,13 @@ extern "C" int dcx_calibrate_pool(const int32_t* d_counts, const int32_t* d_star
     hipLaunchKernelGGL(calib_evaluate_kernel, views, wave, 0, s, pl, d_view_status, ws);
     hipLaunchKernelGGL(calib_decide_kernel, one, red, 0, s, batch, 1, d_view_status, d_pose, ws);
     DCX_CHECK_HIP(hipGetLastError());
-    // every attempt ends in decide, which increments `attempts` or finishes: at most 30 accepted steps, each after at most
-    // 20 rejections (lg from -3 climbs to 17), so the loop below always ends by the state word
-    for (int guard = 0; guard < kCalibMaxIter * 40; ++guard) {
-        int code = kFinished;
-        DCX_CHECK_HIP(hipMemcpyAsync(&code, &ws.st->code, sizeof(int), hipMemcpyDeviceToHost, s));
-        DCX_CHECK_HIP(hipStreamSynchronize(s));
-        if (code == kFinished) break;
-        if (code == kNextEvaluate) hipLaunchKernelGGL(calib_evaluate_kernel, views, wave, 0, s, pl, d_view_status, ws);
+    DCX_CHECK_HIP(lm_run(s, &ws.st->code, kJointMaxIter, [&](bool evaluate) {
+        if (evaluate) hipLaunchKernelGGL(calib_evaluate_kernel, views, wave, 0, s, pl, d_view_status, ws);
         hipLaunchKernelGGL(calib_schur_kernel, views, wave, 0, s, d_view_status, ws);
         hipLaunchKernelGGL(calib_reduce_solve_kernel, one, red, 0, s, batch, d_view_status, ws);
         hipLaunchKernelGGL(calib_trial_kernel, views, wave, 0, s, pl, d_view_status, ws);
         hipLaunchKernelGGL(calib_decide_kernel, one, red, 0, s, batch, 0, d_view_status, d_pose, ws);
-        DCX_CHECK_HIP(hipGetLastError());
-    }
+    }));
     DCX_CHECK_HIP(hipMemcpyAsync(h_result, ws.st->result, 16 * sizeof(double), hipMemcpyDeviceToHost, s));
     DCX_CHECK_HIP(hipStreamSynchronize(s));
     return 0;

@@ -37,17 +37,20 @@
 // Shared with dcx_calib.hip through dcx_mat_dev.h: evaluate's LDS-staged loop (accumulate_rows), schur's body (schur_view), the
 // rig's polar_factor, block_tree, the workspace carver; overlap is dcx_pnp_dev.h's ranges_overlap.  The camera model, its
 // derivative and the pose columns are dcx_camera_dev.h's (project, pose_basis, pose_columns); stereo_row() below adds the chain
-// through R_X and the rig columns.
+// through R_X and the rig columns.  The LM machinery is dcx_lm_dev.h's, shared with dcx_calib.hip: the state and the accept /
+// reject / forced / stop automaton (LmState<6>, lm_decide with STOP_FORCED = true: a step forced with a point behind a camera ends
+// the solve), decide's body (lm_decide_block), trial's prologue (lm_trial_pose), reduce's entry -> source mapping (lm_source), the
+// damping and the host loop (lm_run).  The two fan-ins kChunk / kSlices in front of the 6x6 solve are this unit's own: their order
+// is part of the output bits.
 #include "dcx_pnp_dev.h"
+#include "dcx_lm_dev.h"
 
 #include <algorithm>
 #include <vector>
 
 namespace {
 
-constexpr int kStereoMaxIter = 30;
-constexpr double kStereoEps = 2.220446049250313e-16;     // DBL_EPSILON
-constexpr int kRedThreads = 1024;                         // decide's one-workgroup reduction over timestamps
+constexpr int kRedThreads = kLmThreads;                       // decide's one-workgroup reduction over timestamps
 constexpr int kChunk = 16;                                // reduce: timestamps per block (first fan-in)
 constexpr int kSlices = 16;                               // reduce_solve: slices of the blocks' partials (second fan-in)
 constexpr int kEntries = 91;                              // packed 13x13: [J_X (6) | J_P (6) | r]
@@ -57,15 +60,9 @@ constexpr int kYZ = 42;                                   // U*^-1 W^T (6 x 6, r
 constexpr int kSC = 27;                                   // the pair's part of S (21 packed) and of the rhs (6)
 constexpr int kLdsStride = 13;
 
-enum : int { kNextEvaluate = 0, kNextSchur = 1, kFinished = 2 };
 enum : int { kOverlap = 0, kHeadWords = 2 };
 
-struct StereoState {
-    double x[6], x_trial[6], dx[6];
-    double prev_cost;
-    double result[16];       // h_result
-    int lg, iters, attempts, code;
-};
+using StereoState = LmState<6>;          // g = X; result = h_result
 constexpr int kState = 512;              // bytes reserved for StereoState
 static_assert(sizeof(StereoState) <= kState, "state");
 
@@ -235,11 +232,7 @@ __global__ __launch_bounds__(kLanes) void stereo_rig_kernel(Med med, int npairs,
         if (ws.pair[t]) points[0] += (double)(ws.count[2 * t] + ws.count[2 * t + 1]);
     wave_sum(points);
     if (writer) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) st->result[i] = 0.0;
-        st->lg = -3;
-        st->iters = 0;
-        st->attempts = 0;
+        lm_reset(st);
         st->result[9] = (double)npairs;
         st->result[10] = points[0];
         st->code = kFinished;
@@ -266,7 +259,7 @@ __global__ __launch_bounds__(kLanes) void stereo_rig_kernel(Med med, int npairs,
         return;
     }
 #pragma unroll
-    for (int i = 0; i < 6; ++i) st->x[i] = x[i];
+    for (int i = 0; i < 6; ++i) st->g[i] = x[i];
     st->code = kNextEvaluate;
 }
 
@@ -354,7 +347,7 @@ __global__ __launch_bounds__(kLanes) void stereo_evaluate_kernel(SPool pl0, SPoo
     double x[6], p[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
-        x[i] = ws.st->x[i];
+        x[i] = ws.st->g[i];
         p[i] = ws.pose[(long long)t * 6 + i];
     }
     PairBasis B;
@@ -378,34 +371,17 @@ __global__ __launch_bounds__(kLanes) void stereo_schur_kernel(Ws ws) {
     __shared__ double sy[7][6];              // U*^-1 W^T's 6 columns, then U*^-1 g_b
     const int t = blockIdx.x, lane = threadIdx.x;
     if (ws.st->code == kFinished || !ws.pair[t]) return;
-    const double scale = 1.0 + pow(10.0, (double)ws.st->lg);
+    const double scale = lm_damping(ws.st->lg);
     const bool ok = schur_view<6>(ws.m + (long long)t * kEntries, scale, lane, sy, ws.yz + (long long)t * kYZ,
                                   ws.sc + (long long)t * kSC);
     if (lane == 0) ws.fail[t] = ok ? 0 : 1;
-}
-
-// the step could not be solved: the outputs stay zero but for the counts
-__device__ __forceinline__ void fail(StereoState* st, int status) {
-    st->result[7] = st->iters;
-    st->result[8] = st->attempts;
-    st->result[11] = status;
-    st->code = kFinished;
 }
 
 // First fan-in: block g sums the kTot values over its kChunk timestamps, lane e one value in timestamp order.
 __global__ __launch_bounds__(kLanes) void stereo_reduce_kernel(int batch, Ws ws) {
     if (ws.st->code == kFinished) return;
     const int g = blockIdx.x, e = threadIdx.x;
-    int src = 0;                             // where value e lives: in the pair's 91 (m) or in its Schur part (sc)
-    if (e < 21) {
-        int a, c;
-        unpk<6>(e, a, c);
-        src = pk<13>(a, c);
-    } else if (e < 27) {
-        src = pk<13>(e - 21, 12);
-    } else if (e < kTot) {
-        src = e - 27;
-    }
+    const int src = lm_source<6>(e);         // where value e lives: in the pair's 91 (m) or in its Schur part (sc)
     double s = 0.0;
     int f = 0;
     const int end = min(batch, (g + 1) * kChunk);
@@ -443,10 +419,10 @@ __global__ __launch_bounds__(kSlices * kLanes) void stereo_reduce_solve_kernel(i
     __syncthreads();
     if (t != 0) return;
     if (bad[0]) {
-        fail(st, DCX_STEREO_DEGENERATE);
+        lm_fail(st, DCX_STEREO_DEGENERATE);
         return;
     }
-    const double scale = 1.0 + pow(10.0, (double)st->lg);
+    const double scale = lm_damping(st->lg);
     double S[21], rhs[6], x[6];
 #pragma unroll
     for (int a = 0; a < 6; ++a) {
@@ -455,13 +431,13 @@ __global__ __launch_bounds__(kSlices * kLanes) void stereo_reduce_solve_kernel(i
         rhs[a] = part[0][21 + a] - part[0][48 + a];
     }
     if (!cholesky_solve(S, rhs, 1.0, x)) {
-        fail(st, DCX_STEREO_DEGENERATE);
+        lm_fail(st, DCX_STEREO_DEGENERATE);
         return;
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
-        st->dx[i] = x[i];
-        st->x_trial[i] = st->x[i] - x[i];
+        st->dg[i] = x[i];
+        st->g_trial[i] = st->g[i] - x[i];
     }
 }
 
@@ -484,20 +460,10 @@ __device__ __forceinline__ double view_cost(const IndexedFrame& f, const PnpCame
 __global__ __launch_bounds__(kLanes) void stereo_trial_kernel(SPool pl0, SPool pl1, PnpCamera cam0, PnpCamera cam1, Board bd, Ws ws) {
     const int t = blockIdx.x, lane = threadIdx.x;
     if (ws.st->code == kFinished || !ws.pair[t]) return;
-    const double* yz = ws.yz + (long long)t * kYZ;
-    double x[6], p[6];
-    double dn = 0.0, pn = 0.0;
+    double x[6], p[6], dn, pn;
+    lm_trial_pose<6>(ws.yz + (long long)t * kYZ, ws.st->dg, ws.pose + (long long)t * 6, p, dn, pn);
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        double s = yz[36 + k];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) s -= yz[k * 6 + j] * ws.st->dx[j];
-        const double p0 = ws.pose[(long long)t * 6 + k];
-        p[k] = p0 - s;
-        dn += (p[k] - p0) * (p[k] - p0);
-        pn += p0 * p0;
-        x[k] = ws.st->x_trial[k];
-    }
+    for (int k = 0; k < 6; ++k) x[k] = ws.st->g_trial[k];
     PairBasis B;
     pair_basis<false>(x, p, B);
     const double c0 = view_cost<false>(view_frame(pl0, bd, ws, t, 0), cam0, B);
@@ -515,101 +481,15 @@ __global__ __launch_bounds__(kLanes) void stereo_trial_kernel(SPool pl0, SPool p
 // init = 1: after the first evaluate (the initial cost); init = 0: after a trial
 __global__ __launch_bounds__(kRedThreads) void stereo_decide_kernel(int batch, int init, double* __restrict__ pose,
                                                                     double* __restrict__ view_info, Ws ws) {
-    __shared__ double s[kRedThreads][6];     // cost, |dp|^2, |p|^2, pairs, points, non-finite poses
-    __shared__ int verdict;                  // 0: nothing to commit, 1: commit and continue, 2: commit and finish
-    StereoState* st = ws.st;
-    if (st->code == kFinished) return;
-    const int t = threadIdx.x;
-    double a[6] = {0, 0, 0, 0, 0, 0};
-    for (int b = t; b < batch; b += kRedThreads) {
-        if (!ws.pair[b]) continue;
-        if (init) {
-            a[0] += ws.m[(long long)b * kEntries + kCost];
-        } else {
+    lm_decide_block<6, true>(
+        ws.st, batch, init, ws.pose, ws.trial_pose, [&](int b) { return ws.pair[b] != 0; },
+        [&](int b) { return ws.m[(long long)b * kEntries + kCost]; },
+        [&](int b, double* a) {
             const double* tr = ws.trial + (long long)b * 4;
             a[0] += tr[0] + tr[1]; a[1] += tr[2]; a[2] += tr[3];
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-                if (!isfinite(ws.trial_pose[(long long)b * 6 + k])) a[5] = 1.0;
-        }
-        a[3] += 1.0;
-        a[4] += (double)(ws.count[2 * b] + ws.count[2 * b + 1]);
-    }
-#pragma unroll
-    for (int j = 0; j < 6; ++j) s[t][j] = a[j];
-    block_tree<kRedThreads, 6>(s);
-    const double cost = s[0][0], points = s[0][4];
-    if (t == 0) {
-        verdict = 0;
-        st->result[9] = s[0][3];
-        st->result[10] = points;
-        if (init) {
-            if (!isfinite(cost)) {
-                st->result[11] = DCX_STEREO_DEGENERATE;
-                st->code = kFinished;
-            } else {
-                st->prev_cost = cost;
-                st->code = kNextSchur;
-            }
-        } else {
-            st->attempts += 1;
-            bool forced = false;
-            if (!(cost <= st->prev_cost)) {  // (a point behind a camera: cost = inf, rejected like an increase)
-                if (++st->lg <= 16) {
-                    st->code = kNextSchur;   // retry from the same point with more damping
-                } else {
-                    forced = true;
-                }
-            } else {
-                forced = true;
-            }
-            if (forced) {
-                st->lg = max(st->lg - 1, -16);
-                st->iters += 1;
-                double dn = s[0][1], pn = s[0][2];
-                bool bad = s[0][5] != 0.0;
-                for (int i = 0; i < 6; ++i) {
-                    const double d = st->x_trial[i] - st->x[i];
-                    dn += d * d;
-                    pn += st->x[i] * st->x[i];
-                    st->x[i] = st->x_trial[i];
-                    bad |= !isfinite(st->x[i]);
-                }
-                if (st->iters >= kStereoMaxIter || sqrt(dn) < kStereoEps * sqrt(pn)) {
-                    int res = DCX_STEREO_OK;
-                    if (bad || isnan(cost)) res = DCX_STEREO_NONFINITE;
-                    else if (!isfinite(cost)) res = DCX_STEREO_DEGENERATE;
-                    if (res == DCX_STEREO_OK) {
-                        for (int i = 0; i < 6; ++i) st->result[i] = st->x[i];
-                        st->result[6] = sqrt(cost / points);
-                    }
-                    st->result[7] = st->iters;
-                    st->result[8] = st->attempts;
-                    st->result[11] = res;
-                    st->code = kFinished;
-                    verdict = res == DCX_STEREO_OK ? 2 : 1;
-                } else if (!isfinite(cost)) {
-                    // forced at lg > 16 with a point behind a camera: there are no normal equations to go on from
-                    st->result[7] = st->iters;
-                    st->result[8] = st->attempts;
-                    st->result[11] = bad || isnan(cost) ? DCX_STEREO_NONFINITE : DCX_STEREO_DEGENERATE;
-                    st->code = kFinished;
-                    verdict = 1;
-                } else {
-                    st->prev_cost = cost;
-                    st->code = kNextEvaluate;
-                    verdict = 1;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    if (verdict == 0) return;
-    for (int b = t; b < batch; b += kRedThreads) {
-        if (!ws.pair[b]) continue;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) ws.pose[(long long)b * 6 + k] = ws.trial_pose[(long long)b * 6 + k];
-        if (verdict == 2) {
+        },
+        [&](int b) { return (double)(ws.count[2 * b] + ws.count[2 * b + 1]); },
+        [&](int b) {
             double* o = pose + 8 * (long long)b;
             const double* tr = ws.trial + (long long)b * 4;
             const double n0 = (double)ws.count[2 * b], n1 = (double)ws.count[2 * b + 1];
@@ -619,8 +499,7 @@ __global__ __launch_bounds__(kRedThreads) void stereo_decide_kernel(int batch, i
             o[7] = n0 + n1;
             view_info[4 * (long long)b] = sqrt(tr[0] / n0);
             view_info[4 * (long long)b + 2] = sqrt(tr[1] / n1);
-        }
-    }
+        });
 }
 
 }  // namespace
@@ -695,21 +574,14 @@ extern "C" int dcx_stereo_calibrate_pool(const int32_t* d_counts0, const int32_t
     hipLaunchKernelGGL(stereo_evaluate_kernel, stamps, wave, 0, s, pl0, pl1, cam0, cam1, bd, ws);
     hipLaunchKernelGGL(stereo_decide_kernel, one, red, 0, s, batch, 1, d_pose, d_view_info, ws);
     DCX_CHECK_HIP(hipGetLastError());
-    // every attempt ends in decide, which increments `attempts` or finishes: at most 30 accepted steps, each after at most
-    // 20 rejections (lg from -3 climbs to 17), so the loop below always ends by the state word
-    for (int guard = 0; guard < kStereoMaxIter * 40; ++guard) {
-        int code = kFinished;
-        DCX_CHECK_HIP(hipMemcpyAsync(&code, &ws.st->code, sizeof(int), hipMemcpyDeviceToHost, s));
-        DCX_CHECK_HIP(hipStreamSynchronize(s));
-        if (code == kFinished) break;
-        if (code == kNextEvaluate) hipLaunchKernelGGL(stereo_evaluate_kernel, stamps, wave, 0, s, pl0, pl1, cam0, cam1, bd, ws);
+    DCX_CHECK_HIP(lm_run(s, &ws.st->code, kJointMaxIter, [&](bool evaluate) {
+        if (evaluate) hipLaunchKernelGGL(stereo_evaluate_kernel, stamps, wave, 0, s, pl0, pl1, cam0, cam1, bd, ws);
         hipLaunchKernelGGL(stereo_schur_kernel, stamps, wave, 0, s, ws);
         hipLaunchKernelGGL(stereo_reduce_kernel, blocks, wave, 0, s, batch, ws);
         hipLaunchKernelGGL(stereo_reduce_solve_kernel, one, solve_threads, 0, s, chunks, ws);
         hipLaunchKernelGGL(stereo_trial_kernel, stamps, wave, 0, s, pl0, pl1, cam0, cam1, bd, ws);
         hipLaunchKernelGGL(stereo_decide_kernel, one, red, 0, s, batch, 0, d_pose, d_view_info, ws);
-        DCX_CHECK_HIP(hipGetLastError());
-    }
+    }));
     DCX_CHECK_HIP(hipMemcpyAsync(h_result, ws.st->result, 16 * sizeof(double), hipMemcpyDeviceToHost, s));
     DCX_CHECK_HIP(hipStreamSynchronize(s));
     return 0;

@@ -81,6 +81,23 @@ def _dist(dist_coeffs) -> np.ndarray:
     return out
 
 
+def _bad_id_error(col_count, row_count):
+    return IndexError(f"corner id outside [0, {(col_count - 1) * (row_count - 1)}) for a {col_count}x{row_count} board")
+
+
+def _pool_rows(keypoints, pool_order=False):
+    """A view's [x, y, id] rows -> (rows (n, 3), an empty array gives (0, 3); the indices that put them in the order the corner pool
+    holds them: id-sorted stably as ``_pack`` lays them, or as they stand with ``pool_order``)."""
+    kp = np.asarray(keypoints)
+    kp = kp.reshape(-1, 3) if kp.size else np.zeros((0, 3))
+    return kp, np.arange(kp.shape[0]) if pool_order else np.argsort(kp[:, 2], kind="stable")
+
+
+def _caller_order(keypoints):
+    """The inverse of ``_pool_rows``' id sort: ``mask[_caller_order(kp)]`` takes a mask by pool slot back to the caller's rows."""
+    return np.argsort(_pool_rows(keypoints)[1], kind="stable")
+
+
 def object_points(ids, col_count: int, row_count: int, square_len: float) -> np.ndarray:
     """Board-frame corners of ``ids`` exactly as inference.py:20-26 builds them (float32, z = 0), without the full table:
     id i -> ((1 + i % (row_count-1)) * square_len, (1 + i // (row_count-1)) * square_len, 0), each product taken in float64 and
@@ -88,7 +105,7 @@ def object_points(ids, col_count: int, row_count: int, square_len: float) -> np.
     ids = np.asarray(ids).astype(np.int64)
     n = (col_count - 1) * (row_count - 1)
     if ids.size and (ids.min() < 0 or ids.max() >= n):
-        raise IndexError(f"corner id outside [0, {n}) for a {col_count}x{row_count} board")
+        raise _bad_id_error(col_count, row_count)
     out = np.zeros((ids.size, 3), np.float32)
     out[:, 0] = (1 + ids % (row_count - 1)) * float(square_len)
     out[:, 1] = (1 + ids // (row_count - 1)) * float(square_len)
@@ -569,6 +586,16 @@ def _camera_args(camera_matrix, dist_coeffs):
     return (_ctypes.c_double * 9)(*K.ravel().tolist()), (_ctypes.c_double * 8)(*k.tolist()), n
 
 
+def _pool_ptrs(packed, batch, pool, refined):
+    """The corner pool's layout check -> the addresses of (counts, starts, rows, xy or None)."""
+    import torch
+    if packed.dtype != torch.int32 or not packed.is_contiguous() or packed.numel() < 2 * batch + (6 if refined else 4) * pool:
+        raise ValueError("packed must be a contiguous int32 corner pool of at least packed_len(batch, pool) words")
+    base = packed.data_ptr()
+    rows_p = base + 8 * batch
+    return base, base + 4 * batch, rows_p, rows_p + 16 * pool if refined else None
+
+
 def _launch(counts_p, starts_p, rows_p, xy_p, batch, pool, col_count, row_count, square_len, camera_matrix, dist_coeffs,
             status_p, pose_p):
     from . import _lib
@@ -586,8 +613,7 @@ def solve_pnp_pool(packed, batch: int, pool: int, refined: bool, col_count, row_
     (``out`` = that pair, preallocated); ``unpack_poses`` turns them into per-frame ``(ret, rvec, tvec)``."""
     import torch
     dev = packed.device
-    if packed.dtype != torch.int32 or not packed.is_contiguous() or packed.numel() < 2 * batch + (6 if refined else 4) * pool:
-        raise ValueError("packed must be a contiguous int32 corner pool of at least packed_len(batch, pool) words")
+    ptrs = _pool_ptrs(packed, batch, pool, refined)
     if out is None:
         out = (torch.empty((batch,), dtype=torch.int32, device=dev),
                torch.empty((batch, POSE_WORDS), dtype=torch.float64, device=dev))
@@ -595,11 +621,8 @@ def solve_pnp_pool(packed, batch: int, pool: int, refined: bool, col_count, row_
     if (st.device != dev or st.dtype != torch.int32 or st.numel() != batch or not st.is_contiguous() or pose.device != dev
             or pose.dtype != torch.float64 or pose.numel() != batch * POSE_WORDS or not pose.is_contiguous()):
         raise ValueError(f"out must be (int32 [{batch}], float64 [{batch}, 8]) contiguous tensors on {dev}")
-    base = packed.data_ptr()
-    rows_p = base + 8 * batch
     with torch.cuda.device(dev):
-        _launch(base, base + 4 * batch, rows_p, rows_p + 16 * pool if refined else None, batch, pool, col_count, row_count,
-                square_len, camera_matrix, dist_coeffs, st.data_ptr(), pose.data_ptr())
+        _launch(*ptrs, batch, pool, col_count, row_count, square_len, camera_matrix, dist_coeffs, st.data_ptr(), pose.data_ptr())
     return st, pose
 
 
@@ -617,21 +640,18 @@ def _pack(keypoints_list: Sequence, dev):
     """Host keypoint lists -> a device corner pool (counts | starts | rows | xy), frames id-sorted like the reference."""
     import torch
     b = len(keypoints_list)
-    kps = []
-    for kp in keypoints_list:
-        kp = np.asarray(kp)
-        kps.append(kp.reshape(-1, 3) if kp.size else np.zeros((0, 3)))
-    counts = np.array([k.shape[0] for k in kps], np.int64)
+    kps = [_pool_rows(kp) for kp in keypoints_list]
+    counts = np.array([k.shape[0] for k, _ in kps], np.int64)
     pool = max(int(counts.sum()), 1)
     packed = np.zeros(2 * b + 6 * pool, np.int32)
     starts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
     packed[:b], packed[b:2 * b] = counts, starts
     rows = packed[2 * b:2 * b + 4 * pool].reshape(pool, 4)
     xy = packed[2 * b + 4 * pool:].view(np.float32).reshape(pool, 2)
-    for kp, s in zip(kps, starts.tolist()):
+    for (kp, order), s in zip(kps, starts.tolist()):
         if not kp.shape[0]:
             continue
-        kp = kp[np.argsort(kp[:, 2], kind="stable")]           # inference.py:68-69
+        kp = kp[order]                                         # inference.py:68-69
         ids = kp[:, 2].astype(np.int64)
         rows[s:s + kp.shape[0], 2] = np.clip(ids, -1, np.iinfo(np.int32).max)
         xy[s:s + kp.shape[0]] = kp[:, :2].astype(np.float32)
@@ -652,8 +672,7 @@ def solve_pnp_batch_device(keypoints_list, col_count, row_count, square_len, cam
         st, pose = solve_pnp_pool(packed, b, pool, True, col_count, row_count, square_len, camera_matrix, dist_coeffs)
         st_h, pose_h = st.cpu().numpy(), pose.cpu().numpy()
     if (st_h == PNP_BAD_ID).any():
-        n = (col_count - 1) * (row_count - 1)
-        raise IndexError(f"corner id outside [0, {n}) for a {col_count}x{row_count} board")
+        raise _bad_id_error(col_count, row_count)
     return unpack_poses(st_h, pose_h)
 
 
@@ -689,8 +708,7 @@ def solve_pnp_ransac_pool(packed, batch: int, pool: int, refined: bool, col_coun
     from . import _lib
     dev = packed.device
     iterations, reproj_error, min_inliers = _ransac_args(iterations, reproj_error, min_inliers)
-    if packed.dtype != torch.int32 or not packed.is_contiguous() or packed.numel() < 2 * batch + (6 if refined else 4) * pool:
-        raise ValueError("packed must be a contiguous int32 corner pool of at least packed_len(batch, pool) words")
+    ptrs = _pool_ptrs(packed, batch, pool, refined)
     need = ransac_workspace_bytes(batch, pool, iterations)
     if workspace is None:
         workspace = torch.empty(((need + 7) // 8,), dtype=torch.float64, device=dev)
@@ -707,14 +725,11 @@ def solve_pnp_ransac_pool(packed, batch: int, pool: int, refined: bool, col_coun
                          f"tensors on {dev}")
     st, pose, info, inl = out
     cam, dist, n_dist = _camera_args(camera_matrix, dist_coeffs)
-    base = packed.data_ptr()
-    rows_p = base + 8 * batch
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().dcx_solve_pnp_ransac_pool(
-            base, base + 4 * batch, rows_p, rows_p + 16 * pool if refined else None, int(batch), int(pool), int(col_count),
-            int(row_count), float(square_len), cam, dist, n_dist, iterations, reproj_error, min_inliers, int(seed) & _M32,
-            workspace.data_ptr(), workspace.numel() * workspace.element_size(), st.data_ptr(), pose.data_ptr(), info.data_ptr(),
-            inl.data_ptr(), _lib.current_stream()), "dcx_solve_pnp_ransac_pool")
+            *ptrs, int(batch), int(pool), int(col_count), int(row_count), float(square_len), cam, dist, n_dist, iterations,
+            reproj_error, min_inliers, int(seed) & _M32, workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+            st.data_ptr(), pose.data_ptr(), info.data_ptr(), inl.data_ptr(), _lib.current_stream()), "dcx_solve_pnp_ransac_pool")
     return st, pose, info, inl
 
 
@@ -753,13 +768,10 @@ def solve_pnp_ransac_batch_device(keypoints_list, col_count, row_count, square_l
                                                     dist_coeffs, iterations, reproj_error, min_inliers, seed)
         st, pose, info, inl, head = (t.cpu().numpy() for t in (st, pose, info, inl, packed[:2 * b]))
     if (st == PNP_BAD_ID).any():
-        n = (col_count - 1) * (row_count - 1)
-        raise IndexError(f"corner id outside [0, {n}) for a {col_count}x{row_count} board")
+        raise _bad_id_error(col_count, row_count)
     out = []
     for i, (ret, rvec, tvec, mask) in enumerate(unpack_ransac(st, pose, inl, head[:b], head[b:])):
-        kp = np.asarray(keypoints_list[i])
-        if mask.size:                                         # undo _pack's stable id sort
-            mask = mask[np.argsort(np.argsort(kp.reshape(-1, 3)[:, 2], kind="stable"), kind="stable")]
+        mask = mask[_caller_order(keypoints_list[i])]         # undo _pack's stable id sort
         out.append((int(st[i]), pose[i].copy(), mask, int(info[i, 1])) if full else (ret, rvec, tvec, mask))
     return out
 

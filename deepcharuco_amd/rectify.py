@@ -379,17 +379,15 @@ def rectify_points_pool(packed, batch: int, pool: int, refined: bool, camera_mat
     from . import _lib
     dev = packed.device
     batch, pool = int(batch), int(pool)
-    if packed.dtype != torch.int32 or not packed.is_contiguous() or packed.numel() < 2 * batch + (6 if refined else 4) * pool:
-        raise ValueError("packed must be a contiguous int32 corner pool of at least packed_len(batch, pool) words")
+    rows_p, xy_p = pnp._pool_ptrs(packed, batch, pool, refined)[2:]
     cam, d, n = pnp._camera_args(camera_matrix, dist_coeffs)
     r, p = _rp_args(R, P, _camera(camera_matrix))
     if out is None:
         out = torch.empty((pool, 2), dtype=torch.float64, device=dev)
     if out.device != dev or out.dtype != torch.float64 or out.numel() != 2 * pool or not out.is_contiguous():
         raise ValueError(f"out must be a contiguous float64 [{pool}, 2] tensor on {dev}")
-    rows_p = packed.data_ptr() + 8 * batch
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().dcx_rectify_points_pool(rows_p, rows_p + 16 * pool if refined else None, pool, cam, d, n, r, p,
+        _lib.check(_lib.lib().dcx_rectify_points_pool(rows_p, xy_p, pool, cam, d, n, r, p,
                                                       out.data_ptr() if pool else None, _lib.current_stream()),
                    "dcx_rectify_points_pool")
     return out

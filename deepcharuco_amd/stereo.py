@@ -47,12 +47,12 @@ from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from . import pnp
-from .pnp import (PNP_BAD_ID, PNP_OK, PNP_TOO_FEW, _camera, _cholesky_solve, _dist, _jacobi, _right_jacobian, _rodrigues, _rvec_of,
-                  _skew, _solve)
+from . import _lm, pnp
+from .pnp import (PNP_BAD_ID, PNP_OK, PNP_TOO_FEW, _bad_id_error, _camera, _dist, _jacobi, _pool_ptrs, _right_jacobian, _rodrigues,
+                  _rvec_of, _skew, _solve)
 
 # overall status (include/deepcharuco_amd.h); per-view statuses are pnp's PNP_*
-STEREO_OK, STEREO_NO_PAIRS, STEREO_DEGENERATE, STEREO_NONFINITE = range(4)
+STEREO_OK, STEREO_NO_PAIRS, STEREO_DEGENERATE, STEREO_NONFINITE = _lm.LM_OK, _lm.LM_NO_UNITS, _lm.LM_DEGENERATE, _lm.LM_NONFINITE
 STEREO_MAX_ITER = 30
 STEREO_EPS = float(np.finfo(np.float64).eps)
 RESULT_WORDS = 16              # h_result of dcx_stereo_calibrate_pool
@@ -202,30 +202,6 @@ def _view_costs(rows: _Rows, res: np.ndarray) -> np.ndarray:
     return np.add.reduceat((res * res).sum(1), rows.vstarts).reshape(-1, 2)
 
 
-def _schur_step(U, W, V, ga, gb, lg: int):
-    """Solve [V* W; W^T U*] [dX; dP] = [ga; gb] with the diagonals of V and of every U_t scaled by 1 + 10^lg (Marquardt), by
-    eliminating the pose blocks: S = V* - sum W_t U_t*^-1 W_t^T, dX = S^-1 (ga - sum W_t U_t*^-1 gb_t),
-    dP_t = U_t*^-1 (gb_t - W_t^T dX).  -> (dX [6], dP [N, 6]), or None if a block is not positive definite."""
-    s = 1.0 + 10.0 ** lg
-    Us = U.copy()
-    d6 = np.arange(6)
-    Us[:, d6, d6] *= s
-    try:
-        np.linalg.cholesky(Us)
-    except np.linalg.LinAlgError:
-        return None
-    Y = np.linalg.solve(Us, W.transpose(0, 2, 1))                  # U_t*^-1 W_t^T  [N, 6, 6]
-    z = np.linalg.solve(Us, gb[:, :, None])[:, :, 0]              # U_t*^-1 gb_t   [N, 6]
-    S = V.copy()
-    S[d6, d6] *= s
-    S -= np.einsum("nij,njk->ik", W, Y)
-    rhs = ga - np.einsum("nij,nj->i", W, z)
-    dx = _cholesky_solve(S, rhs)
-    if dx is None:
-        return None
-    return dx, z - np.einsum("nij,j->ni", Y, dx)
-
-
 def _total(costs: np.ndarray) -> float:
     c = 0.0
     for v in costs.sum(1).tolist():
@@ -235,44 +211,11 @@ def _total(costs: np.ndarray) -> float:
 
 def _refine(rows: _Rows, cams, X: np.ndarray, P: np.ndarray):
     """Joint LM (module docstring, step 4) -> (status, X, P, per-view costs [N, 2], accepted steps, attempts)."""
-    blocks = _normal_blocks(rows, cams, X, P)
-    if blocks is None or not math.isfinite(_total(blocks[5])):
-        return STEREO_DEGENERATE, X, P, None, 0, 0
-    vc = blocks[5]
-    prev_cost, lg, iters, attempts = _total(vc), -3, 0, 0
-    while True:
-        U, W, V, ga, gb, _ = blocks
-        prev_x, prev_p = X, P
-        while True:
-            step = _schur_step(U, W, V, ga, gb, lg)
-            if step is None:
-                return STEREO_DEGENERATE, X, P, None, iters, attempts
-            X, P = prev_x - step[0], prev_p - step[1]
-            ev = _evaluate(rows, cams, X, P, False)
-            vc = _view_costs(rows, ev[0]) if ev is not None else None
-            cost = _total(vc) if ev is not None else math.inf
-            attempts += 1
-            if not cost <= prev_cost:              # (a point behind a camera: cost = inf, rejected like an increase)
-                lg += 1
-                if lg <= 16:
-                    continue
-            break
-        lg = max(lg - 1, -16)
-        iters += 1
-        d = np.r_[X - prev_x, (P - prev_p).ravel()]
-        pv = np.r_[prev_x, prev_p.ravel()]
-        if iters >= STEREO_MAX_ITER or math.sqrt(float(d @ d)) < STEREO_EPS * math.sqrt(float(pv @ pv)):
-            break
-        prev_cost = cost
-        blocks = _normal_blocks(rows, cams, X, P)
-        if blocks is None:                         # forced at lg > 16 with a point behind a camera: nothing to go on from
-            bad = not (np.isfinite(X).all() and np.isfinite(P).all())
-            return (STEREO_NONFINITE if bad else STEREO_DEGENERATE), X, P, None, iters, attempts
-    if not (np.isfinite(X).all() and np.isfinite(P).all()) or math.isnan(cost):
-        return STEREO_NONFINITE, X, P, None, iters, attempts
-    if not math.isfinite(cost):
-        return STEREO_DEGENERATE, X, P, None, iters, attempts
-    return STEREO_OK, X, P, vc, iters, attempts
+    def trial_costs(x, p):
+        ev = _evaluate(rows, cams, x, p, False)
+        return _view_costs(rows, ev[0]) if ev is not None else None
+
+    return _lm.refine(X, P, lambda x, p: _normal_blocks(rows, cams, x, p), trial_costs, _total, True, STEREO_MAX_ITER, STEREO_EPS)
 
 
 def lower_median(values) -> float:
@@ -364,14 +307,12 @@ def stereo_calibrate_host_full(keypoints_list0, keypoints_list1, col_count, row_
     obj_l, img_l = [[None, None] for _ in range(B)], [[None, None] for _ in range(B)]
     for t in range(B):
         for c in range(2):
-            kp = np.asarray(lists[c][t])
-            kp = kp.reshape(-1, 3) if kp.size else np.zeros((0, 3))
+            kp, order = pnp._pool_rows(lists[c][t], pool_order)
             keep = np.ones(kp.shape[0], bool)
             if mk[c] is not None and mk[c][t] is not None:
                 keep = np.asarray(mk[c][t]).astype(bool).ravel()
                 if keep.size != kp.shape[0]:
                     raise ValueError(f"view ({c}, {t}) has {kp.shape[0]} rows but its mask {keep.size}")
-            order = np.arange(kp.shape[0]) if pool_order else np.argsort(kp[:, 2], kind="stable")
             kp = kp[order][keep[order]]
             view_points[t, c] = kp.shape[0]
             if kp.shape[0] < 4:
@@ -408,10 +349,6 @@ def stereo_calibrate_host_full(keypoints_list0, keypoints_list1, col_count, row_
     return done(st, X, P, vc, iters, attempts, margin)
 
 
-def _bad_id_error(col_count, row_count):
-    return IndexError(f"corner id outside [0, {(col_count - 1) * (row_count - 1)}) for a {col_count}x{row_count} board")
-
-
 def _raise_like_cv2(r: StereoResult, col_count, row_count):
     if (r.view_status == PNP_BAD_ID).any():
         raise _bad_id_error(col_count, row_count)
@@ -445,15 +382,6 @@ def workspace_bytes(batch: int, pool0: int, pool1: int) -> int:
     if n == 0:
         raise ValueError("batch >= 1 and pool0, pool1 >= 0 are required")
     return n
-
-
-def _pool_ptrs(packed, batch, pool, refined):
-    import torch
-    if packed.dtype != torch.int32 or not packed.is_contiguous() or packed.numel() < 2 * batch + (6 if refined else 4) * pool:
-        raise ValueError("packed must be a contiguous int32 corner pool of at least packed_len(batch, pool) words")
-    base = packed.data_ptr()
-    rows_p = base + 8 * batch
-    return base, base + 4 * batch, rows_p, rows_p + 16 * pool if refined else None
 
 
 def stereo_calibrate_pool(packed0, packed1, batch: int, pool0: int, pool1: int, refined: bool, col_count, row_count, square_len,
@@ -507,14 +435,13 @@ def _slot_mask(keypoints_list, masks, pool, dev):
     out = np.ones(pool, np.uint8)
     s = 0
     for t, kp in enumerate(keypoints_list):
-        kp = np.asarray(kp)
-        kp = kp.reshape(-1, 3) if kp.size else np.zeros((0, 3))
+        kp, order = pnp._pool_rows(kp)
         n = kp.shape[0]
         if masks[t] is not None:
             m = np.asarray(masks[t]).astype(bool).ravel()
             if m.size != n:
                 raise ValueError(f"view {t} has {n} rows but its mask {m.size}")
-            out[s:s + n] = m[np.argsort(kp[:, 2], kind="stable")]
+            out[s:s + n] = m[order]
         s += n
     return torch.from_numpy(out).to(dev)
 

@@ -73,6 +73,36 @@ def test_device_matches_host(dev, seed, n_views, sigma):
     print(f"{n_views} views sigma {sigma}: rms gate", "absolute 1e-12 px (float32 floor)" if floor else "relative 1e-12")
 
 
+def _small_views(seed):
+    """Four noise-free views of eight rows each: make_views' views cut to eight of their ids (not on one line)."""
+    objs, imgs, ids_l, _ = make_views(seed, 4)
+    rng = np.random.default_rng([seed, 8])
+    for i in range(4):
+        while True:
+            sel = np.sort(rng.choice(len(ids_l[i]), 8, replace=False))
+            g = objs[i][sel, :2].astype(np.float64)
+            if np.linalg.matrix_rank(g - g.mean(0), tol=1e-6) == 2:
+                break
+        objs[i], imgs[i], ids_l[i] = objs[i][sel], imgs[i][sel], ids_l[i][sel]
+    return objs, imgs, ids_l
+
+
+def test_a_rejected_step_is_retried(dev):
+    """The smallest scene the kernels take, 4 views of 8 rows, with a seed at which the host definition alone rejects steps (its
+    first trial step raises the cost by more than 1 %; 10 accepted steps in 21 attempts): the device must report rejected steps
+    too, so the retry launch (Schur, reduce, trial and decide without an evaluate, more damping) has run, and still meet this
+    file's gates."""
+    objs, imgs, ids_l = _small_views(334)
+    assert [len(i) for i in ids_l] == [8] * 4
+    h = calib.calibrate_camera_host_full(objs, imgs, SIZE)
+    assert h.status == calib.CALIB_OK and h.attempts > h.iterations        # a condition on the input
+    d = calib.calibrate_charuco_device(_kps(imgs, ids_l), *BOARD, SIZE)
+    assert d.attempts > d.iterations, (d.iterations, d.attempts)
+    # noise-free: the absolute 1e-12 px gate where the rms is the float32 rounding of the image points (test_device_matches_host)
+    _, floor = _check(d, h, "4 views of 8 rows", rms_floor=1e-12)
+    print("4 views of 8 rows: rms gate", "absolute 1e-12 px (float32 floor)" if floor else "relative 1e-12")
+
+
 STRIDE_BOARD = (11, 14, 0.012)                  # 10 x 13 = 130 ids
 STRIDE_ROWS = (63, 64, 65, 127, 128, 129, 130)  # one short of / exactly / one past one and two 64-row strides; the whole board
 

@@ -101,6 +101,19 @@ def test_row_counts_at_the_evaluate_stride(dev, sigma):
     assert h.pairs_used == len(rows) and h.view_points.tolist() == [list(r) for r in rows]
 
 
+def test_a_rejected_step_is_retried(dev):
+    """The smallest scene the kernels take, 3 pairs of 8 rows per view, with a seed at which the host definition alone rejects
+    steps (9 accepted steps in 24 attempts): the device must report rejected steps too, so the retry launch (Schur, the two
+    reductions, trial and decide without an evaluate, more damping) has run, and still meet this file's gates."""
+    s = sx.scene(300, 3, "small", sx.BOARD_S, "A", "B", sigma=0.3, rows=8)
+    h, margin = _host(s)
+    assert margin >= MARGIN and h.status == stereo.STEREO_OK and h.pairs_used == 3 and h.view_points.tolist() == [[8, 8]] * 3
+    assert h.attempts > h.iterations                                        # a condition on the input
+    d = _device(s)
+    assert d.attempts > d.iterations, (d.iterations, d.attempts)
+    print("3 pairs of 8 rows: stopping-rule fallback taken:", _agree(d, h, "3 pairs of 8 rows"))
+
+
 def _fan_ins():
     src = open(os.path.join(os.path.dirname(stereo.__file__), "csrc", "dcx_stereo.hip")).read()
     chunk = int(re.search(r"constexpr int kChunk = (\d+);", src).group(1))
