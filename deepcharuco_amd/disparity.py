@@ -1,6 +1,7 @@
 """Dense stereo matching without OpenCV: semi-global matching over census costs on a rectified pair (what a cv2 user does with
-``StereoSGBM`` after ``rectify.remap_device``), and the disparity map as 3-D points (``cv2.reprojectImageTo3D``), on the host and
-on the GPU (csrc/dcx_sgm.hip).  Every step of the matcher is integer, so the device equals ``sgm_host`` bit for bit.
+``StereoSGBM`` after ``rectify.remap_device``), a speckle filter for disparity maps (``cv2.filterSpeckles``) and the disparity map
+as 3-D points (``cv2.reprojectImageTo3D``), on the host and on the GPU (csrc/dcx_sgm.hip, csrc/dcx_speckle.hip).  Every step of
+the matcher and of the filter is integer, so the device equals ``sgm_host`` and ``filter_speckles_host`` bit for bit.
 
 Conventions: ``left`` is rectified camera 0 and ``right`` rectified camera 1 of a horizontal rig (``Rectification.axis == 0``), the
 disparity d = x_left - x_right is ``rectify.reproject_to_3d``'s d.  A vertical rig (``axis == 1``) passes both frames transposed
@@ -26,10 +27,18 @@ With m = min_disparity, D = num_disparities and d in [0, D) the candidate (the d
 6. sub-pixel: with 0 < d* < D - 1, num = S[d*-1] - S[d*+1], den = S[d*-1] + S[d*+1] - 2 S[d*]; den > 0 gives
    off = floor((16 num + den) / (2 den)) (a FLOOR division: the parabola's offset in sixteenths, rounded half up, in [-8, 8]), else
    off = 0.  The output is 16 (m + d*) + off.
+7. with speckle_window_size > 0, the speckle filter on that map: ``filter_speckles_host`` with new_val = 16 (m - 1),
+   max_speckle_size = speckle_window_size and max_diff = 16 speckle_range, as cv2's ``StereoSGBM`` calls ``filterSpeckles``.
+
+The speckle filter (``filter_speckles_host``, cv2.filterSpeckles): pixels equal to new_val are never touched and belong to no
+component.  Among the others, two 4-neighbours p, q of one frame are joined when |disp16[p] - disp16[q]| <= max_diff (in at least
+32 bits); the components are the connected components of that graph (connectivity is transitive: a ramp whose neighbours differ
+by max_diff is one component however far its ends are apart); every pixel of a component of at most max_speckle_size pixels
+becomes new_val.  The result depends on the component sizes only, so on no order of visiting.
 
 Deviations from cv2.StereoSGBM, on purpose: census costs instead of Birchfield-Tomasi on Sobel-filtered images (integer, no
 pre-filter cap to tune, and two popcounts per candidate); P2 fixed rather than scaled by the local gradient; four paths
-(MODE_SGBM has five, MODE_HH eight); no speckle filter and no pre-filter cap.
+(MODE_SGBM has five, MODE_HH eight); no pre-filter cap.
 
 ``min_disparity`` must keep every output inside an int16: -2047 <= m and m + D <= 2047.
 """
@@ -42,8 +51,12 @@ DISPARITY_SHIFT = 4                          # fractional bits of an output valu
 NUM_DISPARITIES = (64, 128, 256)
 MAX_DEVICE_WIDTH = 4096                      # csrc/dcx_sgm.hip keeps a row's right-view winners in LDS
 
-__all__ = ["census_host", "cost_volume_host", "aggregate_host", "select_host", "sgm_host", "disparity_to_points_host",
-           "sgm_workspace_bytes", "sgm_device", "disparity_to_points_device", "NUM_DISPARITIES", "MAX_DEVICE_WIDTH"]
+MAX_SPECKLE_PIXELS = 1 << 30                 # csrc/dcx_speckle.hip labels a frame's pixels with 32-bit indices
+MAX_SPECKLE_SIDE = 1 << 20                   # and walks a frame's tiles in one grid
+
+__all__ = ["census_host", "cost_volume_host", "aggregate_host", "select_host", "sgm_host", "filter_speckles_host",
+           "disparity_to_points_host", "sgm_workspace_bytes", "sgm_device", "filter_speckles_workspace_bytes",
+           "filter_speckles_device", "disparity_to_points_device", "NUM_DISPARITIES", "MAX_DEVICE_WIDTH"]
 
 
 def _params(min_disparity, num_disparities, p1, p2, uniqueness, lr_max_diff):
@@ -60,6 +73,31 @@ def _params(min_disparity, num_disparities, p1, p2, uniqueness, lr_max_diff):
     if m < -2047 or m + D > 2047:
         raise ValueError("min_disparity must keep 16 (m - 1) and 16 (m + D) inside an int16: -2047 <= m, m + D <= 2047")
     return m, D, p1, p2, u, max(lr, -1)
+
+
+def _speckle_params(new_val, max_speckle_size, max_diff):
+    vals = (new_val, max_speckle_size, max_diff)
+    if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in vals):
+        raise ValueError("the speckle filter's parameters must be integers")
+    nv, size, diff = (int(v) for v in vals)
+    if not -32768 <= nv <= 32767:
+        raise ValueError("new_val must be an int16 value")
+    if size < 0:
+        raise ValueError("max_speckle_size must not be negative")
+    if not 0 <= diff <= 65535:
+        raise ValueError("0 <= max_diff <= 65535 is required")
+    return nv, size, diff
+
+
+def _sgm_speckle_params(speckle_window_size, speckle_range):
+    """-> (max_speckle_size, max_diff) of step 7."""
+    vals = (speckle_window_size, speckle_range)
+    if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in vals):
+        raise ValueError("speckle_window_size and speckle_range must be integers")
+    size, rng = (int(v) for v in vals)
+    if size < 0 or not 0 <= 16 * rng <= 65535:
+        raise ValueError("speckle_window_size >= 0 and 0 <= 16 speckle_range <= 65535 are required")
+    return size, 16 * rng
 
 
 # ------------------------------------------------------------------------------------------------ the definition, step by step
@@ -150,20 +188,69 @@ def select_host(S, min_disparity: int, uniqueness: int, lr_max_diff: int) -> np.
     return out.astype(np.int16)
 
 
+def _components(disp, new_val: int, max_diff: int):
+    """One frame int16 (H, W) -> (alive bool (H W), root int64 (H W)): the component of pixel p is named by its smallest pixel
+    index, root[p] (p itself where p is not alive).  Union-find over all edges at once: every round hooks, for each edge whose
+    ends have different roots, the larger root under the smaller (the smallest wins where several ask), then follows every pixel's
+    entry until each points at a root.  A pixel's entry never grows and some root is hooked in every round but the last."""
+    H, W = disp.shape
+    v = disp.astype(np.int64).ravel()
+    alive = v != new_val
+    idx = np.arange(H * W).reshape(H, W)
+    ends = []
+    for a, b in ((idx[:, :-1], idx[:, 1:]), (idx[:-1, :], idx[1:, :])):
+        a, b = a.ravel(), b.ravel()
+        join = alive[a] & alive[b] & (np.abs(v[a] - v[b]) <= max_diff)
+        ends.append((a[join], b[join]))
+    a, b = np.concatenate([e[0] for e in ends]), np.concatenate([e[1] for e in ends])
+    root = np.arange(H * W)
+    while True:
+        while True:
+            up = root[root]
+            if np.array_equal(up, root):
+                break
+            root = up
+        ra, rb = root[a], root[b]
+        apart = ra != rb
+        if not apart.any():
+            return alive, root
+        np.minimum.at(root, np.maximum(ra, rb)[apart], np.minimum(ra, rb)[apart])
+
+
+def filter_speckles_host(disp16, new_val: int, max_speckle_size: int, max_diff: int) -> np.ndarray:
+    """The speckle filter's definition (module docstring; ``cv2.filterSpeckles``): ``disp16`` int16 (H, W) or (B, H, W), each
+    frame on its own -> a copy of the same shape in which every pixel of a component of at most ``max_speckle_size`` pixels holds
+    ``new_val``.  ``new_val`` an int16 value, ``max_speckle_size`` >= 0 (0 changes nothing), 0 <= ``max_diff`` <= 65535, all
+    integers; ValueError otherwise."""
+    nv, size, diff = _speckle_params(new_val, max_speckle_size, max_diff)
+    disp16 = np.asarray(disp16)
+    if disp16.dtype != np.int16 or disp16.ndim not in (2, 3) or disp16.size == 0:
+        raise ValueError("disp16 must be a non-empty int16 array (H, W) or (B, H, W)")
+    if disp16.ndim == 3:
+        return np.stack([filter_speckles_host(f, nv, size, diff) for f in disp16])
+    alive, root = _components(disp16, nv, diff)
+    count = np.bincount(root[alive], minlength=root.size)
+    out = disp16.copy()
+    out.reshape(-1)[alive & (count[root] <= size)] = nv
+    return out
+
+
 def sgm_host(left, right, min_disparity: int = 0, num_disparities: int = 64, p1: int = 7, p2: int = 86, uniqueness: int = 10,
-             lr_max_diff: int = 1) -> np.ndarray:
+             lr_max_diff: int = 1, speckle_window_size: int = 0, speckle_range: int = 0) -> np.ndarray:
     """The definition (module docstring): ``left``, ``right`` uint8 (H, W) or (B, H, W), rectified on a horizontal rig, ``left``
     camera 0 -> int16 of the same shape, the disparity times 16, 16 (min_disparity - 1) where invalid.  A vertical rig passes
-    transposed frames.  ``lr_max_diff`` < 0 switches the left-right check off.  ValueError for anything else that the module
-    docstring does not allow."""
+    transposed frames.  ``lr_max_diff`` < 0 switches the left-right check off; ``speckle_window_size`` > 0 switches the speckle
+    filter (step 7) on.  ValueError for anything else that the module docstring does not allow."""
     m, D, p1, p2, u, lr = _params(min_disparity, num_disparities, p1, p2, uniqueness, lr_max_diff)
+    size, diff = _sgm_speckle_params(speckle_window_size, speckle_range)
     left, right = np.asarray(left), np.asarray(right)
     if left.dtype != np.uint8 or right.dtype != np.uint8 or left.shape != right.shape or left.ndim not in (2, 3) or left.size == 0:
         raise ValueError("left and right must be non-empty uint8 arrays of one shape, (H, W) or (B, H, W)")
     if left.ndim == 3:
-        return np.stack([sgm_host(a, b, m, D, p1, p2, u, lr) for a, b in zip(left, right)])
+        return np.stack([sgm_host(a, b, m, D, p1, p2, u, lr, size, diff // 16) for a, b in zip(left, right)])
     C = cost_volume_host(census_host(left), census_host(right), m, D)
-    return select_host(aggregate_host(C, p1, p2), m, u, lr)
+    out = select_host(aggregate_host(C, p1, p2), m, u, lr)
+    return filter_speckles_host(out, 16 * (m - 1), size, diff) if size > 0 else out
 
 
 def _q44(Q) -> np.ndarray:
@@ -205,15 +292,18 @@ def sgm_workspace_bytes(batch: int, height: int, width: int, num_disparities: in
 
 
 def sgm_device(left, right, min_disparity: int = 0, num_disparities: int = 64, p1: int = 7, p2: int = 86, uniqueness: int = 10,
-               lr_max_diff: int = 1, out=None, workspace=None):
+               lr_max_diff: int = 1, out=None, workspace=None, speckle_window_size: int = 0, speckle_range: int = 0):
     """``sgm_host`` on the GPU: ``left``, ``right`` uint8 GPU tensors (H, W) or (B, H, W) of one shape whose rows are contiguous
     (any row pitch and frame stride, each tensor its own) -> int16 tensor of the same shape, contiguous (``out``: that tensor,
     preallocated).  ``workspace``: a uint8 GPU tensor of ``sgm_workspace_bytes`` bytes, or fewer but at least one frame's (the batch
     is then taken in chunks); allocated when None.  Enqueued on the current stream, no host sync, deterministic; nothing is
-    allocated when ``out`` and ``workspace`` are given (capture-safe).  Equal to ``sgm_host`` bit for bit.  width <= 4096."""
+    allocated when ``out`` and ``workspace`` are given (capture-safe).  Equal to ``sgm_host`` bit for bit.  width <= 4096.
+    With ``speckle_window_size`` > 0 the speckle filter (step 7) follows on the same stream, in place on ``out`` and in the same
+    workspace, which the matcher is done with by then and which holds at least 18 frames of the filter's per frame of its own."""
     import torch
     from . import _lib
     m, D, p1, p2, u, lr = _params(min_disparity, num_disparities, p1, p2, uniqueness, lr_max_diff)
+    size, diff = _sgm_speckle_params(speckle_window_size, speckle_range)
     for t in (left, right):
         if t.device.type != "cuda" or t.dtype != torch.uint8 or t.ndim not in (2, 3):
             raise ValueError("left and right must be uint8 GPU tensors (H, W) or (B, H, W)")
@@ -247,6 +337,55 @@ def sgm_device(left, right, min_disparity: int = 0, num_disparities: int = 64, p
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().dcx_sgm_u8(pl, fl, tl, pr, fr, tr, B, H, W, m, D, p1, p2, u, lr, out.data_ptr(),
                                          workspace.data_ptr(), workspace.numel(), _lib.current_stream()), "dcx_sgm_u8")
+        if size > 0:
+            _lib.check(_lib.lib().dcx_filter_speckles_s16(out.data_ptr(), out.data_ptr(), B, H, W, 16 * (m - 1), size, diff,
+                                                          workspace.data_ptr(), workspace.numel(), _lib.current_stream()),
+                       "dcx_filter_speckles_s16")
+    return out
+
+
+def filter_speckles_workspace_bytes(batch: int, height: int, width: int) -> int:
+    """Bytes of device workspace with which ``filter_speckles_device`` takes the whole batch in one chunk: a 32-bit label and a
+    32-bit size per pixel, 8 H W per frame.  A smaller workspace that holds at least one frame is accepted and the batch is chunked."""
+    from . import _lib
+    n = int(_lib.lib().dcx_filter_speckles_workspace_bytes(int(batch), int(height), int(width)))
+    if n == 0:
+        raise ValueError(f"refused shape: batch >= 1, 1 <= height, width <= {MAX_SPECKLE_SIDE} and height * width <= "
+                         f"{MAX_SPECKLE_PIXELS} are required")
+    return n
+
+
+def filter_speckles_device(disp16, new_val: int, max_speckle_size: int, max_diff: int, out=None, workspace=None):
+    """``filter_speckles_host`` on the GPU: ``disp16`` a contiguous int16 GPU tensor (H, W) or (B, H, W) -> int16 tensor of the
+    same shape (``out``: that tensor, preallocated and contiguous; it may be ``disp16`` itself, any other overlap is the caller's
+    error).  ``workspace``: a uint8 GPU tensor of ``filter_speckles_workspace_bytes`` bytes, or fewer but at least one frame's (the
+    batch is then taken in chunks); allocated when None.  Four launches per chunk on the current stream, no host sync; nothing is
+    allocated when ``out`` and ``workspace`` are given (capture-safe).  Equal to ``filter_speckles_host`` bit for bit."""
+    import torch
+    from . import _lib
+    nv, size, diff = _speckle_params(new_val, max_speckle_size, max_diff)
+    if disp16.device.type != "cuda" or disp16.dtype != torch.int16 or disp16.ndim not in (2, 3) or not disp16.is_contiguous() \
+            or disp16.numel() == 0:
+        raise ValueError("disp16 must be a non-empty contiguous int16 GPU tensor (H, W) or (B, H, W)")
+    dev = disp16.device
+    shape = tuple(disp16.shape)
+    B = int(shape[0]) if disp16.ndim == 3 else 1
+    H, W = int(shape[-2]), int(shape[-1])
+    one = filter_speckles_workspace_bytes(1, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.int16, device=dev)
+    if out.device != dev or out.dtype != torch.int16 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous int16 {shape} tensor on {dev}")
+    if workspace is None:
+        workspace = torch.empty(B * one, dtype=torch.uint8, device=dev)
+    if workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.data_ptr() % 8:
+        raise ValueError(f"workspace must be a contiguous, 8-byte aligned uint8 tensor on {dev}")
+    if workspace.numel() < one:
+        raise ValueError("the workspace does not hold one frame: see filter_speckles_workspace_bytes(1, height, width)")
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().dcx_filter_speckles_s16(disp16.data_ptr(), out.data_ptr(), B, H, W, nv, size, diff,
+                                                      workspace.data_ptr(), workspace.numel(), _lib.current_stream()),
+                   "dcx_filter_speckles_s16")
     return out
 
 

@@ -435,6 +435,26 @@ int dcx_sgm_u8(const uint8_t* d_left, long frame_stride_l, int pitch_l, const ui
 int dcx_disparity_to_points(const int16_t* d_disp16, int batch, int height, int width, int min_disparity,
                             const double* h_Q16 /* 4x4 row major */, float* d_xyz /* [batch][height][width][3] */, void* stream);
 
+/* ---- the speckle filter for disparity maps (cv2.filterSpeckles) -----------------------------------------------------------------
+ * What follows dcx_sgm_u8 (cv2's StereoSGBM calls it with new_val = 16 (min_disparity - 1), max_speckle_size = speckleWindowSize,
+ * max_diff = 16 speckleRange).  d_in int16 [batch][height][width], dense, each frame on its own.  Pixels equal to new_val are never
+ * touched and belong to no component; among the others two 4-neighbours are joined when their values differ by at most max_diff;
+ * every pixel of a connected component of at most max_speckle_size pixels becomes new_val in d_out (max_speckle_size = 0 copies).
+ * All integer and bit-exact against deepcharuco_amd/disparity.py:filter_speckles_host: the result depends on the components'
+ * sizes only, so on no order of execution, and two calls give the same bits.  d_out may equal d_in; any other overlap is the
+ * caller's error.  new_val an int16 value, max_speckle_size >= 0, 0 <= max_diff <= 65535 (DCX_E_ARG); batch >= 1,
+ * 1 <= height, width <= 2^20 and height * width <= 2^30 (DCX_E_SHAPE); d_in, d_out 2-byte and d_workspace 8-byte aligned (DCX_E_ARG).
+ *
+ * d_workspace: dcx_filter_speckles_workspace_bytes(batch, ...) = batch * height * width * 8 bytes (a 32-bit label and a 32-bit
+ * size per pixel) take the batch in one pass; with fewer bytes the batch is taken in chunks of as many frames as fit, and with
+ * less than one frame's the call is refused (DCX_E_WS).  One frame of dcx_sgm_u8's workspace holds at least 18 frames of this one,
+ * so the matcher's workspace serves the filter that follows it.  Four launches per chunk on `stream` (labels of 32 x 32 tiles in
+ * LDS; unions across tile edges by global atomics; roots and sizes; the rewrite): no allocation, no synchronisation, no kernel
+ * waits for another workgroup, and a call can be captured in a hipGraph.                                                       */
+size_t dcx_filter_speckles_workspace_bytes(int batch, int height, int width);   /* batch * H * W * 8; 0 for refused shapes */
+int dcx_filter_speckles_s16(const int16_t* d_in, int16_t* d_out, int batch, int height, int width, int new_val,
+                            int max_speckle_size, int max_diff, void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- stage-level entry point for kernel tests / roofline measurement -------------------
  * One 3x3 (or 1x1) convolution + bias [+ eval-BN + ReLU] [+ 2x2 max-pool] on C4 tensors
  * using the same MFMA kernel the networks use.  h_* are host arrays in PyTorch layout;
