@@ -90,6 +90,7 @@ SIGNATURES = {
     "dcx_remap_u8": (_i, [_vp, _l, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "dcx_sgm_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "dcx_sgm_u8": (_i, [_vp, _l, _i, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "dcx_sgm_u8_paths": (_i, [_vp, _l, _i, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "dcx_disparity_to_points": (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_double), _vp, _vp]),
     "dcx_filter_speckles_workspace_bytes": (_sz, [_i, _i, _i]),
     "dcx_filter_speckles_s16": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),

@@ -1,7 +1,7 @@
-// dcx_sgm.hip -- dense stereo matching on rectified u8 pairs: semi-global matching over 9 x 7 census costs (four paths, cv2's
-// uniqueness rule, a left-right check made from the same summed costs, a parabola's sub-pixel step in sixteenths), and the
-// disparity map as 3-D points.  deepcharuco_amd/disparity.py restates every step (sgm_host, disparity_to_points_host) and is the
-// pin of these kernels: the matcher is integer throughout and agrees with it bit for bit.
+// dcx_sgm.hip -- dense stereo matching on rectified u8 pairs: semi-global matching over 9 x 7 census costs (four paths, or
+// eight with the diagonals; cv2's uniqueness rule, a left-right check made from the same summed costs, a parabola's sub-pixel
+// step in sixteenths), and the disparity map as 3-D points.  deepcharuco_amd/disparity.py restates every step (sgm_host,
+// disparity_to_points_host) and is the pin of these kernels: the matcher is integer throughout and agrees with it bit for bit.
 //
 // Shape.  A candidate disparity is a lane: a wave owns one path line (a row of a frame for the two horizontal paths, a column for
 // the two vertical ones) and walks it pixel by pixel with the line's L_r(., d) in its lanes, D / 64 consecutive disparities to a
@@ -15,6 +15,8 @@
 //   path kernel, rows  left -> right writes S = L; right -> left by the same wave adds its L   (S: one write, one update that the
 //                                                                                               wave's own lanes wrote and L2 holds)
 //   path kernel, cols  top -> bottom adds, bottom -> top adds                                  (S: two updates)
+//   diagonal kernel    paths == 8 only, one launch per family: "\" (+1, +1) adds, (-1, -1) adds;   (S: two updates per launch)
+//                      "/" (+1, -1) adds, (-1, +1) adds
 //   select kernel      one workgroup per row reads S once: a wave per pixel finds the winner (one wave minimum of S << 16 | d,
 //                      so ties take the lowest d), the uniqueness verdict (a ballot) and the sub-pixel step, and every lane
 //                      folds its S into the right view's winner of ITS right pixel, x - m - d, by an LDS minimum of the same
@@ -24,6 +26,21 @@
 // A step's loads (census words, and S where it is updated) do not depend on the recursion, so each pass loads pixel p + 1's
 // before it computes pixel p.  What is left on the chain is the shifts, the wave minimum and a handful of integer operations;
 // throughput comes from the lines in flight (B H or B W waves).
+//
+// The diagonal paths.  A wave per START COLUMN c, not per diagonal: at row y the wave stands on column (c + slope y) mod W, slope
+// +1 for the "\" family and -1 for "/", so it walks all H rows like a column wave and every launch is B W waves of H steps,
+// whatever the lengths (1 ... min(H, W)) of the frame's H + W - 1 diagonals are.  Where the column wraps across the frame edge
+// the previous pixel of the path lies outside the frame, and the recursion starts again (L = C) as it does on a line's first
+// pixel: the wave carries one diagonal after another, end to end.  The reverse pass walks the same pixels from the last row up
+// and starts again where it wraps the other way.  W = 1 wraps at every step (every diagonal has one pixel), H = 1 is one step,
+// and a tall frame wraps several times: none needs a launch of its own.  The waves of a workgroup stand on adjacent pixels of
+// S at every step, as in the column pass.
+//
+// Updating S in place is safe because, WITHIN ONE LAUNCH, EVERY ELEMENT OF S IS READ AND WRITTEN BY EXACTLY ONE WAVE, and by
+// the same lane of it in both passes: rows and columns partition a frame, and c -> (c + slope y) mod W is a bijection of the
+// columns at every row y, so the start-column lines do too.  A wave's reverse pass touches only what its own lanes stored in its
+// forward pass (program order; nothing else in the launch reads or writes those addresses).  The two diagonal families visit the
+// same pixels from different lines, as rows and columns do, which is why each is a launch of its own and the stream orders them.
 //
 // No allocation, no synchronisation, no global atomics; every call is a fixed sequence of launches on the stream.
 #include <cmath>
@@ -113,7 +130,8 @@ __global__ __launch_bounds__(256) void dcx_sgm_census_kernel(const uint8_t* __re
 // ---- the paths
 
 // One line's geometry: pixel p of the line is pixel `base + p * step` of the chunk; its image column is x0 + p * dx and its row
-// starts at pixel row0 + p * drow of the chunk.
+// starts at pixel row0 + p * drow of the chunk.  A wrapped line (sgm_pass<..., WRAP>) has the column (x0 + p * dx) mod width and
+// its pixel at row start + column; base and step are not read.
 struct Line {
     size_t base, step, row0, drow;
     int x0, dx, n;
@@ -139,22 +157,53 @@ __device__ __forceinline__ Fetch<NPL> fetch(const Line& ln, int p, int lane, con
     return f;
 }
 
-// One path along the line: REVERSE walks it from its last pixel; ACC adds L to S (else S = L).
-template <int NPL, bool REVERSE, bool ACC>
+// Pixel p of a wrapped line, whose column x the caller keeps: the same reads as fetch's.
+template <int NPL, bool ACC>
+__device__ __forceinline__ Fetch<NPL> fetch_wrapped(const Line& ln, int p, int x, int lane, const uint64_t* __restrict__ cen_l,
+                                                    const uint64_t* __restrict__ cen_r, const uint16_t* S, int width, int m) {
+    Fetch<NPL> f = {};
+    const size_t row = ln.row0 + (size_t)p * ln.drow;
+    f.cl = cen_l[row + x];
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) f.cr[k] = cen_r[row + min(max(x - m - lane * NPL - k, 0), width - 1)];
+    if (ACC) load_s<NPL>(S + (row + x) * (64 * NPL) + lane * NPL, f.s);
+    return f;
+}
+
+// One path along the line: REVERSE walks it from its last pixel; ACC adds L to S (else S = L).  WRAP: the line is wrapped (Line),
+// and the path starts again, L = C, at every pixel that the walk reaches by wrapping across the frame edge (a select after the
+// step, not a branch around it: in one block the next step's loads stay ahead of the step, past a branch they sink below it).
+// The line's geometry should be wave-uniform in scalar registers: the columns, the wraps and the row addresses are then scalar.
+template <int NPL, bool REVERSE, bool ACC, bool WRAP = false>
 __device__ __forceinline__ void sgm_pass(const Line& ln, int lane, const uint64_t* __restrict__ cen_l,
                                          const uint64_t* __restrict__ cen_r, uint16_t* S, int width, int m, int p1, int p2) {
     int L[NPL];
     int p = REVERSE ? ln.n - 1 : 0;
-    Fetch<NPL> next = fetch<NPL, ACC>(ln, p, lane, cen_l, cen_r, S, width, m);
+    int x = 0, xn = 0;                                                          // WRAP: the columns of pixel p and of the next one,
+    bool restart = true, restart_next = false;                                  // and whether the walk wrapped to reach them
+    if constexpr (WRAP) {
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) L[k] = 0;                                 // (a restart is a select, so the first step reads L)
+        x = (ln.x0 + p * ln.dx) % width;                                        // (once per pass; the steps add and compare)
+        x += x < 0 ? width : 0;
+    }
+    Fetch<NPL> next = WRAP ? fetch_wrapped<NPL, ACC>(ln, p, x, lane, cen_l, cen_r, S, width, m)
+                           : fetch<NPL, ACC>(ln, p, lane, cen_l, cen_r, S, width, m);
 #pragma unroll 1
     for (int t = 0; t < ln.n; ++t) {
         const Fetch<NPL> cur = next;
         const int pn = REVERSE ? max(p - 1, 0) : min(p + 1, ln.n - 1);          // (the last step fetches its own pixel again, unused)
-        next = fetch<NPL, ACC>(ln, pn, lane, cen_l, cen_r, S, width, m);
+        if constexpr (WRAP) {
+            xn = x + (REVERSE ? -ln.dx : ln.dx);
+            restart_next = xn < 0 || xn >= width;
+            xn = pn == p ? x : xn < 0 ? width - 1 : xn >= width ? 0 : xn;       // (the last step stays on its own pixel here too)
+        }
+        next = WRAP ? fetch_wrapped<NPL, ACC>(ln, pn, xn, lane, cen_l, cen_r, S, width, m)
+                    : fetch<NPL, ACC>(ln, pn, lane, cen_l, cen_r, S, width, m);
         int C[NPL];
 #pragma unroll
         for (int k = 0; k < NPL; ++k) C[k] = __popcll(cur.cl ^ cur.cr[k]);
-        if (t == 0) {
+        if (!WRAP && t == 0) {
 #pragma unroll
             for (int k = 0; k < NPL; ++k) L[k] = C[k];
         } else {
@@ -172,13 +221,17 @@ __device__ __forceinline__ void sgm_pass(const Line& ln, int lane, const uint64_
                 nl[k] = C[k] + min(min(L[k], min(lo, hi) + p1), M + p2) - M;
             }
 #pragma unroll
-            for (int k = 0; k < NPL; ++k) L[k] = nl[k];
+            for (int k = 0; k < NPL; ++k) L[k] = WRAP && restart ? C[k] : nl[k];    // (one block with no branch: the loads stay ahead of it)
         }
         int o[NPL];
 #pragma unroll
         for (int k = 0; k < NPL; ++k) o[k] = ACC ? cur.s[k] + L[k] : L[k];
-        store_s<NPL>(S + (ln.base + (size_t)p * ln.step) * (64 * NPL) + lane * NPL, o);
+        store_s<NPL>(S + (WRAP ? ln.row0 + (size_t)p * ln.drow + x : ln.base + (size_t)p * ln.step) * (64 * NPL) + lane * NPL, o);
         p = pn;
+        if constexpr (WRAP) {
+            x = xn;
+            restart = restart_next;
+        }
     }
 }
 
@@ -201,6 +254,22 @@ __global__ __launch_bounds__(256) void dcx_sgm_path_kernel(const uint64_t* __res
     }
     sgm_pass<NPL, false, VERT>(ln, lane, cen_l, cen_r, S, width, m, p1, p2);
     sgm_pass<NPL, true, true>(ln, lane, cen_l, cen_r, S, width, m, p1, p2);
+}
+
+// The two diagonal paths of one family, SLOPE = +1: (+1, +1) then (-1, -1); SLOPE = -1: (+1, -1) then (-1, +1).  A wave per start
+// column c walks every row y at column (c + SLOPE y) mod width (the file's head has the reasons and the in-place invariant).  The
+// wave's index is made a scalar, so the columns, the wraps and the addresses of a step are scalar arithmetic.
+template <int NPL, int SLOPE>
+__global__ __launch_bounds__(256) void dcx_sgm_diag_kernel(const uint64_t* __restrict__ cen_l, const uint64_t* __restrict__ cen_r,
+                                                             uint16_t* S, int frames, int height, int width, int m, int p1, int p2) {
+    const int lane = threadIdx.x & 63;
+    const long long line = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (line >= (long long)frames * width) return;                              // (wave-uniform)
+    const int f = (int)(line / width), c = (int)(line - (long long)f * width);
+    Line ln;
+    ln.base = 0; ln.step = 0; ln.row0 = (size_t)f * height * width; ln.drow = (size_t)width; ln.x0 = c; ln.dx = SLOPE; ln.n = height;
+    sgm_pass<NPL, false, true, true>(ln, lane, cen_l, cen_r, S, width, m, p1, p2);
+    sgm_pass<NPL, true, true, true>(ln, lane, cen_l, cen_r, S, width, m, p1, p2);
 }
 
 // ---- winner, invalidation, sub-pixel: one workgroup per row
@@ -293,8 +362,8 @@ __global__ __launch_bounds__(256) void dcx_disparity_points_kernel(const int16_t
 
 template <int NPL>
 int sgm_launch(const uint8_t* d_left, long frame_stride_l, int pitch_l, const uint8_t* d_right, long frame_stride_r, int pitch_r,
-               int batch, int height, int width, int m, int p1, int p2, int uniqueness, int lr_max_diff, int16_t* d_disp16,
-               void* d_workspace, int chunk, hipStream_t stream) {
+               int batch, int height, int width, int m, int p1, int p2, int uniqueness, int lr_max_diff, int paths,
+               int16_t* d_disp16, void* d_workspace, int chunk, hipStream_t stream) {
     const size_t px = (size_t)height * width;
     uint64_t* cen_l = static_cast<uint64_t*>(d_workspace);
     uint64_t* cen_r = cen_l + (size_t)chunk * px;
@@ -308,6 +377,11 @@ int sgm_launch(const uint8_t* d_left, long frame_stride_l, int pitch_l, const ui
                            cen_l, cen_r, S, frames, height, width, m, p1, p2);
         hipLaunchKernelGGL((dcx_sgm_path_kernel<NPL, true>), dim3((unsigned)(((long long)frames * width + 3) / 4)), dim3(256), 0, stream,
                            cen_l, cen_r, S, frames, height, width, m, p1, p2);
+        if (paths == 8) {
+            const dim3 grid((unsigned)(((long long)frames * width + 3) / 4));
+            hipLaunchKernelGGL((dcx_sgm_diag_kernel<NPL, 1>), grid, dim3(256), 0, stream, cen_l, cen_r, S, frames, height, width, m, p1, p2);
+            hipLaunchKernelGGL((dcx_sgm_diag_kernel<NPL, -1>), grid, dim3(256), 0, stream, cen_l, cen_r, S, frames, height, width, m, p1, p2);
+        }
         hipLaunchKernelGGL((dcx_sgm_select_kernel<NPL>), dim3((unsigned)((long long)frames * height)), dim3(256),
                            2 * (size_t)width * sizeof(unsigned), stream, S, width, m, uniqueness, lr_max_diff, d_disp16 + (size_t)f0 * px);
         const hipError_t e = hipGetLastError();
@@ -332,10 +406,11 @@ extern "C" size_t dcx_sgm_workspace_bytes(int batch, int height, int width, int 
     return (size_t)batch * sgm_frame_bytes(height, width, num_disparities);
 }
 
-extern "C" int dcx_sgm_u8(const uint8_t* d_left, long frame_stride_l, int pitch_l, const uint8_t* d_right, long frame_stride_r,
-                          int pitch_r, int batch, int height, int width, int min_disparity, int num_disparities, int p1, int p2,
-                          int uniqueness, int lr_max_diff, int16_t* d_disp16, void* d_workspace, size_t workspace_bytes,
-                          void* stream) {
+extern "C" int dcx_sgm_u8_paths(const uint8_t* d_left, long frame_stride_l, int pitch_l, const uint8_t* d_right, long frame_stride_r,
+                                int pitch_r, int batch, int height, int width, int min_disparity, int num_disparities, int p1, int p2,
+                                int uniqueness, int lr_max_diff, int paths, int16_t* d_disp16, void* d_workspace,
+                                size_t workspace_bytes, void* stream) {
+    if (paths != 4 && paths != 8) return DCX_E_ARG;
     if (!d_left || !d_right || !d_disp16 || ((uintptr_t)d_disp16 & 1) || !d_workspace || ((uintptr_t)d_workspace & 7)) return DCX_E_ARG;
     if (frame_stride_l < 0 || frame_stride_r < 0 || p1 < 0 || p1 > p2 || p2 > 255 || uniqueness < 0 || uniqueness >= 100) return DCX_E_ARG;
     if (!sgm_shape_ok(batch, height, width, num_disparities) || pitch_l < width || pitch_r < width) return DCX_E_SHAPE;
@@ -347,9 +422,17 @@ extern "C" int dcx_sgm_u8(const uint8_t* d_left, long frame_stride_l, int pitch_
     const int lr = lr_max_diff < 0 ? -1 : lr_max_diff;
 #define DCX_SGM(NPL)                                                                                                             \
     sgm_launch<NPL>(d_left, frame_stride_l, pitch_l, d_right, frame_stride_r, pitch_r, batch, height, width, min_disparity, p1, p2, \
-                    uniqueness, lr, d_disp16, d_workspace, (int)chunk, (hipStream_t)stream)
+                    uniqueness, lr, paths, d_disp16, d_workspace, (int)chunk, (hipStream_t)stream)
     return num_disparities == 64 ? DCX_SGM(1) : num_disparities == 128 ? DCX_SGM(2) : DCX_SGM(4);
 #undef DCX_SGM
+}
+
+extern "C" int dcx_sgm_u8(const uint8_t* d_left, long frame_stride_l, int pitch_l, const uint8_t* d_right, long frame_stride_r,
+                          int pitch_r, int batch, int height, int width, int min_disparity, int num_disparities, int p1, int p2,
+                          int uniqueness, int lr_max_diff, int16_t* d_disp16, void* d_workspace, size_t workspace_bytes,
+                          void* stream) {
+    return dcx_sgm_u8_paths(d_left, frame_stride_l, pitch_l, d_right, frame_stride_r, pitch_r, batch, height, width, min_disparity,
+                            num_disparities, p1, p2, uniqueness, lr_max_diff, 4, d_disp16, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int dcx_disparity_to_points(const int16_t* d_disp16, int batch, int height, int width, int min_disparity,

@@ -19,6 +19,10 @@ With m = min_disparity, D = num_disparities and d in [0, D) the candidate (the d
    L_r(p, d) = C(p, d) + min(L_r(q, d), L_r(q, d - 1) + P1, L_r(q, d + 1) + P1, M + P2) - M, q the previous pixel of the path,
    M = min_k L_r(q, k); a term with d +- 1 outside [0, D) is left out; at a path's first pixel L_r = C.  S = sum_r L_r
    <= 4 (62 + 255) = 1268.
+   With ``paths=8`` S also receives the four diagonal paths, whose directions (dy, dx) are (+1, +1), (-1, -1), (+1, -1) and
+   (-1, +1): the same recursion with q = p - (dy, dx); a pixel whose q lies outside the frame is a path's first pixel (L_r = C),
+   so in a 1 x W or H x 1 frame every diagonal has one pixel.  S <= 8 (62 + 255) = 2536: still a u16, and S << 16 | d a word.
+   Steps 4 - 7 read that larger S unchanged (the uniqueness rule is a ratio).  ``paths=4`` is the default.
 4. the winner d* = argmin_d S, the lowest d on ties.
 5. a pixel is invalid if x - m - d* lies outside [0, W); or (cv2's uniqueness rule) some d with |d - d*| > 1 has
    S[d] (100 - uniqueness) < S[d*] 100; or, with lr_max_diff >= 0, |dR(x - m - d*) - d*| > lr_max_diff, where for a right pixel xr
@@ -37,8 +41,10 @@ by max_diff is one component however far its ends are apart); every pixel of a c
 becomes new_val.  The result depends on the component sizes only, so on no order of visiting.
 
 Deviations from cv2.StereoSGBM, on purpose: census costs instead of Birchfield-Tomasi on Sobel-filtered images (integer, no
-pre-filter cap to tune, and two popcounts per candidate); P2 fixed rather than scaled by the local gradient; four paths
-(MODE_SGBM has five, MODE_HH eight); no pre-filter cap.
+pre-filter cap to tune, and two popcounts per candidate); P2 fixed rather than scaled by the local gradient; four paths by
+default and eight with ``paths=8`` (MODE_HH's directions; MODE_SGBM's five and the 16 of the literature are not built); no
+pre-filter cap.  Eight paths are an option and no general gain: on a depth edge that runs diagonally they leave fewer wrong
+pixels, on an axis-aligned rectangle slightly more, since the diagonals cross its corners (DESIGN 3.13b has both figures).
 
 ``min_disparity`` must keep every output inside an int16: -2047 <= m and m + D <= 2047.
 """
@@ -49,6 +55,7 @@ import numpy as np
 CENSUS_W, CENSUS_H = 9, 7
 DISPARITY_SHIFT = 4                          # fractional bits of an output value
 NUM_DISPARITIES = (64, 128, 256)
+PATHS = (4, 8)                               # aggregation paths: the axis-aligned four, or those and the four diagonals
 MAX_DEVICE_WIDTH = 4096                      # csrc/dcx_sgm.hip keeps a row's right-view winners in LDS
 
 MAX_SPECKLE_PIXELS = 1 << 30                 # csrc/dcx_speckle.hip labels a frame's pixels with 32-bit indices
@@ -56,7 +63,7 @@ MAX_SPECKLE_SIDE = 1 << 20                   # and walks a frame's tiles in one 
 
 __all__ = ["census_host", "cost_volume_host", "aggregate_host", "select_host", "sgm_host", "filter_speckles_host",
            "disparity_to_points_host", "sgm_workspace_bytes", "sgm_device", "filter_speckles_workspace_bytes",
-           "filter_speckles_device", "disparity_to_points_device", "NUM_DISPARITIES", "MAX_DEVICE_WIDTH"]
+           "filter_speckles_device", "disparity_to_points_device", "NUM_DISPARITIES", "PATHS", "MAX_DEVICE_WIDTH"]
 
 
 def _params(min_disparity, num_disparities, p1, p2, uniqueness, lr_max_diff):
@@ -73,6 +80,12 @@ def _params(min_disparity, num_disparities, p1, p2, uniqueness, lr_max_diff):
     if m < -2047 or m + D > 2047:
         raise ValueError("min_disparity must keep 16 (m - 1) and 16 (m + D) inside an int16: -2047 <= m, m + D <= 2047")
     return m, D, p1, p2, u, max(lr, -1)
+
+
+def _paths(paths) -> int:
+    if isinstance(paths, bool) or not isinstance(paths, (int, np.integer)) or int(paths) not in PATHS:
+        raise ValueError(f"paths must be one of {PATHS}")
+    return int(paths)
 
 
 def _speckle_params(new_val, max_speckle_size, max_diff):
@@ -131,8 +144,9 @@ def cost_volume_host(cen_left, cen_right, min_disparity: int, num_disparities: i
     return _popcount64(cen_left[:, :, None] ^ cen_right[:, np.clip(x, 0, W - 1)])
 
 
-def _path(C, p1: int, p2: int, reverse: bool) -> np.ndarray:
-    """One path along axis 1 of C (N, n, D) -> L of the same shape."""
+def _path(C, p1: int, p2: int, reverse: bool, first=None) -> np.ndarray:
+    """One path along axis 1 of C (N, n, D) -> L of the same shape.  ``first`` bool (N, n): the pixels, beside each line's first,
+    at which a path begins (L = C)."""
     n, D = C.shape[1], C.shape[2]
     big = np.int32(1 << 20)
     L = np.empty_like(C)
@@ -146,17 +160,40 @@ def _path(C, p1: int, p2: int, reverse: bool) -> np.ndarray:
             lo = np.concatenate([np.full((prev.shape[0], 1), big, np.int32), prev[:, :-1]], 1) + p1      # L(q, d - 1) + P1
             hi = np.concatenate([prev[:, 1:], np.full((prev.shape[0], 1), big, np.int32)], 1) + p1       # L(q, d + 1) + P1
             cur = C[:, i] + np.minimum(np.minimum(prev, lo), np.minimum(hi, M + p2)) - M
+            if first is not None:
+                cur = np.where(first[:, i, None], C[:, i], cur)
         L[:, i] = cur
         prev = cur
     return L
 
 
-def aggregate_host(C, p1: int, p2: int) -> np.ndarray:
-    """Step 3: the cost volume int32 (H, W, D) -> S int32 (H, W, D), the sum of the four paths."""
+def _diagonals(C, p1: int, p2: int, slope: int) -> np.ndarray:
+    """The two paths of one diagonal family, (dy, dx) = (+1, slope) and (-1, -slope), summed: C (H, W, D) -> (H, W, D).  The
+    frame's diagonals are laid end to end on W lines of H pixels: line c holds, at row y, the pixel of column (c + slope y) mod W,
+    and wherever the previous pixel of a path, p - (dy, dx), lies outside the frame a new path begins.  Every pixel is on exactly
+    one line."""
+    H, W, _ = C.shape
+    y = np.broadcast_to(np.arange(H)[None, :], (W, H))
+    x = (np.arange(W)[:, None] + slope * y) % W
+    lines = C[y, x]                                                          # (W, H, D)
+    out = np.zeros_like(C)
+    for reverse in (False, True):
+        dy, dx = (-1, -slope) if reverse else (1, slope)
+        first = (y - dy < 0) | (y - dy >= H) | (x - dx < 0) | (x - dx >= W)
+        out[y, x] += _path(lines, p1, p2, reverse, first)
+    return out
+
+
+def aggregate_host(C, p1: int, p2: int, paths: int = 4) -> np.ndarray:
+    """Step 3: the cost volume int32 (H, W, D) -> S int32 (H, W, D), the sum of the four paths, or with ``paths=8`` of those and
+    the four diagonal ones."""
+    paths = _paths(paths)
     C = np.ascontiguousarray(C, np.int32)
     Ct = np.ascontiguousarray(C.transpose(1, 0, 2))
     S = _path(C, p1, p2, False) + _path(C, p1, p2, True)
     S += (_path(Ct, p1, p2, False) + _path(Ct, p1, p2, True)).transpose(1, 0, 2)
+    if paths == 8:
+        S += _diagonals(C, p1, p2, 1) + _diagonals(C, p1, p2, -1)
     return S
 
 
@@ -236,20 +273,21 @@ def filter_speckles_host(disp16, new_val: int, max_speckle_size: int, max_diff: 
 
 
 def sgm_host(left, right, min_disparity: int = 0, num_disparities: int = 64, p1: int = 7, p2: int = 86, uniqueness: int = 10,
-             lr_max_diff: int = 1, speckle_window_size: int = 0, speckle_range: int = 0) -> np.ndarray:
+             lr_max_diff: int = 1, speckle_window_size: int = 0, speckle_range: int = 0, paths: int = 4) -> np.ndarray:
     """The definition (module docstring): ``left``, ``right`` uint8 (H, W) or (B, H, W), rectified on a horizontal rig, ``left``
     camera 0 -> int16 of the same shape, the disparity times 16, 16 (min_disparity - 1) where invalid.  A vertical rig passes
     transposed frames.  ``lr_max_diff`` < 0 switches the left-right check off; ``speckle_window_size`` > 0 switches the speckle
-    filter (step 7) on.  ValueError for anything else that the module docstring does not allow."""
+    filter (step 7) on; ``paths`` is 4 or 8 (step 3).  ValueError for anything else that the module docstring does not allow."""
     m, D, p1, p2, u, lr = _params(min_disparity, num_disparities, p1, p2, uniqueness, lr_max_diff)
     size, diff = _sgm_speckle_params(speckle_window_size, speckle_range)
+    paths = _paths(paths)
     left, right = np.asarray(left), np.asarray(right)
     if left.dtype != np.uint8 or right.dtype != np.uint8 or left.shape != right.shape or left.ndim not in (2, 3) or left.size == 0:
         raise ValueError("left and right must be non-empty uint8 arrays of one shape, (H, W) or (B, H, W)")
     if left.ndim == 3:
-        return np.stack([sgm_host(a, b, m, D, p1, p2, u, lr, size, diff // 16) for a, b in zip(left, right)])
+        return np.stack([sgm_host(a, b, m, D, p1, p2, u, lr, size, diff // 16, paths) for a, b in zip(left, right)])
     C = cost_volume_host(census_host(left), census_host(right), m, D)
-    out = select_host(aggregate_host(C, p1, p2), m, u, lr)
+    out = select_host(aggregate_host(C, p1, p2, paths), m, u, lr)
     return filter_speckles_host(out, 16 * (m - 1), size, diff) if size > 0 else out
 
 
@@ -292,18 +330,21 @@ def sgm_workspace_bytes(batch: int, height: int, width: int, num_disparities: in
 
 
 def sgm_device(left, right, min_disparity: int = 0, num_disparities: int = 64, p1: int = 7, p2: int = 86, uniqueness: int = 10,
-               lr_max_diff: int = 1, out=None, workspace=None, speckle_window_size: int = 0, speckle_range: int = 0):
+               lr_max_diff: int = 1, out=None, workspace=None, speckle_window_size: int = 0, speckle_range: int = 0,
+               paths: int = 4):
     """``sgm_host`` on the GPU: ``left``, ``right`` uint8 GPU tensors (H, W) or (B, H, W) of one shape whose rows are contiguous
     (any row pitch and frame stride, each tensor its own) -> int16 tensor of the same shape, contiguous (``out``: that tensor,
     preallocated).  ``workspace``: a uint8 GPU tensor of ``sgm_workspace_bytes`` bytes, or fewer but at least one frame's (the batch
     is then taken in chunks); allocated when None.  Enqueued on the current stream, no host sync, deterministic; nothing is
     allocated when ``out`` and ``workspace`` are given (capture-safe).  Equal to ``sgm_host`` bit for bit.  width <= 4096.
     With ``speckle_window_size`` > 0 the speckle filter (step 7) follows on the same stream, in place on ``out`` and in the same
-    workspace, which the matcher is done with by then and which holds at least 18 frames of the filter's per frame of its own."""
+    workspace, which the matcher is done with by then and which holds at least 18 frames of the filter's per frame of its own.
+    ``paths=8`` adds the diagonal paths' two launches per chunk; the workspace is the same."""
     import torch
     from . import _lib
     m, D, p1, p2, u, lr = _params(min_disparity, num_disparities, p1, p2, uniqueness, lr_max_diff)
     size, diff = _sgm_speckle_params(speckle_window_size, speckle_range)
+    paths = _paths(paths)
     for t in (left, right):
         if t.device.type != "cuda" or t.dtype != torch.uint8 or t.ndim not in (2, 3):
             raise ValueError("left and right must be uint8 GPU tensors (H, W) or (B, H, W)")
@@ -335,8 +376,8 @@ def sgm_device(left, right, min_disparity: int = 0, num_disparities: int = 64, p
         raise ValueError("the workspace does not hold one frame: see sgm_workspace_bytes(1, height, width, num_disparities)")
     (pl, fl, tl), (pr, fr, tr) = views
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().dcx_sgm_u8(pl, fl, tl, pr, fr, tr, B, H, W, m, D, p1, p2, u, lr, out.data_ptr(),
-                                         workspace.data_ptr(), workspace.numel(), _lib.current_stream()), "dcx_sgm_u8")
+        _lib.check(_lib.lib().dcx_sgm_u8_paths(pl, fl, tl, pr, fr, tr, B, H, W, m, D, p1, p2, u, lr, paths, out.data_ptr(),
+                                               workspace.data_ptr(), workspace.numel(), _lib.current_stream()), "dcx_sgm_u8_paths")
         if size > 0:
             _lib.check(_lib.lib().dcx_filter_speckles_s16(out.data_ptr(), out.data_ptr(), B, H, W, 16 * (m - 1), size, diff,
                                                           workspace.data_ptr(), workspace.numel(), _lib.current_stream()),

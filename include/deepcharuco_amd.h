@@ -424,6 +424,12 @@ int dcx_remap_u8(const uint8_t* d_src, long frame_stride, int pitch, int src_h, 
  * with less than one frame's the call is refused (DCX_E_WS).  Launches on `stream` only: no allocation, no synchronisation, no
  * global atomics, so two calls give the same bits and a call can be captured in a hipGraph.
  *
+ * dcx_sgm_u8_paths is dcx_sgm_u8 with the number of aggregation paths, 4 or 8 (anything else DCX_E_ARG, before anything is
+ * launched).  With 4 it is dcx_sgm_u8: the same launches, the same bits.  With 8 S also receives the four diagonal paths,
+ * (dy, dx) = (+1, +1), (-1, -1), (+1, -1), (-1, +1): the same recursion with q = p - (dy, dx), a path beginning (L = C) at every
+ * pixel whose q lies outside the frame; S <= 8 (62 + 255) still fits its u16.  Two more launches per chunk, one per diagonal
+ * family, in the same workspace.
+ *
  * dcx_disparity_to_points (cv2.reprojectImageTo3D): one thread per pixel; with d = disp16 / 16 and h = Q (x, y, d, 1)^T, each row
  * summed left to right in fp64 without contraction, d_xyz f32 [batch][height][width][3] = h[0..2] / h[3], rounded to float once;
  * NaN where disp16 < 16 min_disparity (invalid) or disp16 == 0.  h_Q16: 4x4 row major, finite (DCX_E_ARG otherwise), copied into
@@ -432,6 +438,10 @@ size_t dcx_sgm_workspace_bytes(int batch, int height, int width, int num_dispari
 int dcx_sgm_u8(const uint8_t* d_left, long frame_stride_l, int pitch_l, const uint8_t* d_right, long frame_stride_r, int pitch_r,
                int batch, int height, int width, int min_disparity, int num_disparities, int p1, int p2, int uniqueness,
                int lr_max_diff, int16_t* d_disp16, void* d_workspace, size_t workspace_bytes, void* stream);
+int dcx_sgm_u8_paths(const uint8_t* d_left, long frame_stride_l, int pitch_l, const uint8_t* d_right, long frame_stride_r, int pitch_r,
+                     int batch, int height, int width, int min_disparity, int num_disparities, int p1, int p2, int uniqueness,
+                     int lr_max_diff, int paths /* 4 or 8 */, int16_t* d_disp16, void* d_workspace, size_t workspace_bytes,
+                     void* stream);
 int dcx_disparity_to_points(const int16_t* d_disp16, int batch, int height, int width, int min_disparity,
                             const double* h_Q16 /* 4x4 row major */, float* d_xyz /* [batch][height][width][3] */, void* stream);
 

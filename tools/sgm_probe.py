@@ -3,7 +3,8 @@
 copies that move as many bytes as the matcher moves of S, the one array of it that does not fit a cache.  Per call S (u16,
 B H W D 2 bytes) is written once and read and rewritten three times by the path kernels (rows: S = L, then += L; columns: += L
 twice) and read once by the select kernel: 8 |S| bytes, which four copy_ calls of an |S|-byte buffer move (4 reads, 4 writes).
-The census images (16 B per pixel against 2 D of S) and the frames are left out of the floor.
+The census images (16 B per pixel against 2 D of S) and the frames are left out of the floor.  With --paths 8 the two diagonal
+kernels read and rewrite S twice each: 12 |S| bytes, six copy_ calls.
 
 Timing: device events around `inner` back-to-back calls after three warm-up calls of each, rounds repeated until the matcher
 alone has run for --seconds (default 1 s) and at least 20 rounds; the figure is the median round's time per call.  Frames: a
@@ -26,6 +27,7 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
 S_PASSES = 8                 # reads + writes of S per call (module docstring)
+S_PASSES_BY_PATHS = {4: S_PASSES, 8: 12}
 
 
 def alternate(fns, seconds, min_rounds=20):
@@ -64,19 +66,21 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--paths", type=int, default=4, choices=sorted(S_PASSES_BY_PATHS), help="aggregation paths of the matcher")
     a = ap.parse_args()
     import torch
     import disparity_cases as dc
     from deepcharuco_amd import disparity as dp
     assert torch.cuda.is_available(), "sgm_probe measures the GPU kernels: no GPU visible"
     dev = torch.device("cuda", 0)
+    paths, s_passes = a.paths, S_PASSES_BY_PATHS[a.paths]
 
     left, right = dc.two_plane_scene()[:2]
     pair = [np.stack([x, x[::-1]]) for x in (left, right)]
-    got = dp.sgm_device(torch.from_numpy(pair[0]).to(dev), torch.from_numpy(pair[1]).to(dev)).cpu().numpy()
-    assert np.array_equal(got, dp.sgm_host(pair[0], pair[1])), "the device does not match the numpy definition"
+    got = dp.sgm_device(torch.from_numpy(pair[0]).to(dev), torch.from_numpy(pair[1]).to(dev), paths=paths).cpu().numpy()
+    assert np.array_equal(got, dp.sgm_host(pair[0], pair[1], paths=paths)), "the device does not match the numpy definition"
 
-    result = {"device": torch.cuda.get_device_name(dev), "seconds": a.seconds, "s_passes": S_PASSES, "sgm": {}}
+    result = {"device": torch.cuda.get_device_name(dev), "seconds": a.seconds, "paths": paths, "s_passes": s_passes, "sgm": {}}
     batch = 32
     Q = np.array([[1, 0, 0, -160.0], [0, 1, 0, -120.0], [0, 0, 0, 300.0], [0, 0, 1.0 / 0.06, 0]])
     for h, w, D in ((240, 320, 64), (480, 640, 128)):
@@ -92,10 +96,10 @@ def main():
         xyz = torch.empty((batch, h, w, 3), dtype=torch.float32, device=dev)
 
         def sgm():
-            return dp.sgm_device(fl, fr, 0, D, out=out, workspace=ws)
+            return dp.sgm_device(fl, fr, 0, D, out=out, workspace=ws, paths=paths)
 
         def copy():
-            for _ in range(S_PASSES // 2):
+            for _ in range(s_passes // 2):
                 cd.copy_(cs)
 
         def points():
@@ -105,8 +109,8 @@ def main():
         valid = float((out >= 0).float().mean())
         result["sgm"][key] = {
             "sgm_ms": ms["sgm"], "copy_floor_ms": ms["copy_floor"], "points_ms": ms["points"], "sgm_over_floor": ms["sgm"] / ms["copy_floor"],
-            "s_bytes": s_bytes, "s_bytes_moved": S_PASSES * s_bytes, "sgm_GBps_of_S": S_PASSES * s_bytes / ms["sgm"] / 1e6,
-            "copy_GBps": S_PASSES * s_bytes / ms["copy_floor"] / 1e6, "frames_per_s": batch / ms["sgm"] * 1e3,
+            "s_bytes": s_bytes, "s_bytes_moved": s_passes * s_bytes, "sgm_GBps_of_S": s_passes * s_bytes / ms["sgm"] / 1e6,
+            "copy_GBps": s_passes * s_bytes / ms["copy_floor"] / 1e6, "frames_per_s": batch / ms["sgm"] * 1e3,
             "min_max_ms": spread, "inner": inner, "rounds": rounds, "valid_fraction": valid}
         print(key, json.dumps(result["sgm"][key]), flush=True)
         del fl, fr, out, ws, cs, cd, xyz
