@@ -67,6 +67,10 @@ SIGNATURES = {
     "dcx_argmax2d": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "dcx_pipeline_workspace_bytes": (_sz, [_vp, _vp, _i, _i, _i, _i]),
     "dcx_infer_batch": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dcx_front_bytes": (_sz, [_vp, _i, _i, _i]),
+    "dcx_detector_front": (_i, [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "dcx_infer_batch_prefetched": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp]),
     "dcx_stream_synchronize": (_i, [_vp]),
     "dcx_solve_pnp_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), _i,
                                _vp, _vp, _vp]),

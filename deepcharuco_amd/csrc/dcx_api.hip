@@ -350,22 +350,41 @@ extern "C" size_t dcx_detector_workspace_bytes(const dcx_detector* det, int batc
 namespace {
 // conv1a .. convPa|convDa; with_heads: also the two raw 1x1 heads into the workspace's C4 logit buffers (dcModel.forward).
 // Without them the 512-channel activation is left in buf0 for the fused tail kernel (dcx_tail.hip).
+// act0 (nullable): conv1a's output is already there (detector_front ran for this batch, which also cleared the control words);
+// conv1a is not launched, conv1b reads act0 and never writes it -- the later layers alternate between the workspace's two buffers
 int detector_run(const dcx_detector* det, const uint8_t* d_frames_u8, long frame_stride, int pitch, int pix,
                  const float* d_images_f32, int batch, int height, int width, void* d_ws, size_t ws_bytes,
-                 bool with_heads, float* d_loc_nchw, float* d_ids_nchw, int32_t* zero_words, int n_zero, void* stream);
+                 bool with_heads, float* d_loc_nchw, float* d_ids_nchw, int32_t* zero_words, int n_zero, const float* act0,
+                 void* stream);
 }  // namespace
 
 extern "C" int dcx_detector_forward(const dcx_detector* det, const uint8_t* d_frames_u8, long frame_stride, int pitch,
                                     const float* d_images_f32, int batch, int height, int width, void* d_ws,
                                     size_t ws_bytes, float* d_loc_nchw, float* d_ids_nchw, void* stream) {
     return detector_run(det, d_frames_u8, frame_stride, pitch, DCX_PIX_GRAY8, d_images_f32, batch, height, width, d_ws, ws_bytes, true,
-                        d_loc_nchw, d_ids_nchw, nullptr, 0, stream);
+                        d_loc_nchw, d_ids_nchw, nullptr, 0, nullptr, stream);
 }
 
 namespace {
+// conv1a + bn1a + relu (net.py:60) of a batch into out; workgroup (0, 0) also clears zero_words
+int detector_front(const dcx_detector* det, const uint8_t* d_frames_u8, long frame_stride, int pitch, int pix,
+                   const float* d_images_f32, int batch, int h, int w, float* out, int32_t* zero_words, int n_zero, hipStream_t s) {
+    int rc;
+    const int pt0 = dcx_prof_begin(DCX_PROF_CONV1A, batch, s);
+    if (d_frames_u8)
+        rc = dcx_launch_conv1_u8(d_frames_u8, frame_stride, pitch, pix, batch, h, w, 1, det->first.w, det->first.bias,
+                                 det->first.alpha, det->first.beta, out, nullptr, zero_words, n_zero, s);
+    else
+        rc = dcx_launch_conv1_f32(d_images_f32, (long)h * w, w, batch, h, w, 1, det->first.w, det->first.bias,
+                                  det->first.alpha, det->first.beta, out, nullptr, s);
+    if (rc) return rc;
+    return dcx_prof_end(pt0, s);
+}
+
 int detector_run(const dcx_detector* det, const uint8_t* d_frames_u8, long frame_stride, int pitch, int pix,
                  const float* d_images_f32, int batch, int height, int width, void* d_ws, size_t ws_bytes,
-                 bool with_heads, float* d_loc_nchw, float* d_ids_nchw, int32_t* zero_words, int n_zero, void* stream) {
+                 bool with_heads, float* d_loc_nchw, float* d_ids_nchw, int32_t* zero_words, int n_zero, const float* act0,
+                 void* stream) {
     if (!det || !d_ws) return DCX_E_ARG;
     if ((d_frames_u8 == nullptr) == (d_images_f32 == nullptr)) return DCX_E_ARG;
     if (batch <= 0 || height < 8 || width < 8) return DCX_E_SHAPE;      // any size >= 8: the three poolings floor (net.py:16)
@@ -379,27 +398,20 @@ int detector_run(const dcx_detector* det, const uint8_t* d_frames_u8, long frame
     float* ids = (float*)(ws + L.ids);
     const int h = height, w = width;
     int rc;
-    // conv1a + bn1a + relu (net.py:60)
-    const int pt0 = dcx_prof_begin(DCX_PROF_CONV1A, batch, s);
-    if (d_frames_u8)
-        rc = dcx_launch_conv1_u8(d_frames_u8, frame_stride, pitch, pix, batch, h, w, 1, det->first.w, det->first.bias,
-                                 det->first.alpha, det->first.beta, buf0, nullptr, zero_words, n_zero, s);
-    else
-        rc = dcx_launch_conv1_f32(d_images_f32, (long)h * w, w, batch, h, w, 1, det->first.w, det->first.bias,
-                                  det->first.alpha, det->first.beta, buf0, nullptr, s);
-    if (rc) return rc;
-    if ((rc = dcx_prof_end(pt0, s))) return rc;
+    if (act0 == nullptr && (rc = detector_front(det, d_frames_u8, frame_stride, pitch, pix, d_images_f32, batch, h, w, buf0,
+                                                zero_words, n_zero, s)))
+        return rc;
     // encoder (net.py:61-70): {layer, input divisor, pool}
     struct Step { int layer, div, pool; };
     static const Step steps[7] = {{0, 1, 1}, {1, 2, 0}, {2, 2, 1}, {3, 4, 0}, {4, 4, 1}, {5, 8, 0}, {6, 8, 0}};
-    float* src = buf0;
+    const float* src = act0 ? act0 : buf0;
     float* dst = buf1;
     for (const Step& st : steps) {
         const DevLayer& l = det->enc[st.layer];
         DcxConvArgs a = conv_args(l, src, batch, l.cin / 4, 0, h / st.div, w / st.div, 0, 1, dst, l.cout / 4, nullptr);
         rc = dcx_launch_conv_mfma(a, 3, st.pool, DCX_EPI_BNRELU, s);
         if (rc) return rc;
-        float* t = src; src = dst; dst = t;
+        src = dst; dst = dst == buf1 ? buf0 : buf1;
     }
     // after 7 steps: src = buf1 holds conv4b output (128 ch @ H/8 x W/8), dst = buf0
     const int hc = h / 8, wc = w / 8;
@@ -573,12 +585,24 @@ namespace {
 // ctrl: int32 words cleared by the detector's first kernel: [0] = pool cursor (ends as the batch's firing-cell count = RefineNet's
 // n_limit), [64 .. 64 + B) = the frames' tail tickets
 struct PipeWs { size_t det, table, ctrl, ref, total; int ctrl_words; };
+inline int ctrl_word_count(int b) { return 64 + b; }
+// one prefetch set: conv1a's output for a batch (what buf0 holds in front of conv1b) and control words of its own
+struct FrontWs { size_t act, ctrl, total; int ctrl_words; };
+FrontWs front_layout(int b, int h, int w) {
+    FrontWs F;
+    size_t off = 0;
+    F.act = off; off = align_up(off + (size_t)b * 64 * h * w * 4, 256);
+    F.ctrl_words = ctrl_word_count(b);
+    F.ctrl = off; off = align_up(off + (size_t)F.ctrl_words * 4, 256);
+    F.total = off;
+    return F;
+}
 PipeWs pipe_layout(const dcx_detector* det, const dcx_refiner* rf, int b, int h, int w, int pool) {
     PipeWs L;
     size_t off = 0;
     L.det = off; off = align_up(off + det_layout(det->n_ids, b, h, w).total, 256);
     L.table = off; off = align_up(off + (size_t)pool * 16, 256);
-    L.ctrl_words = 64 + b;
+    L.ctrl_words = ctrl_word_count(b);
     L.ctrl = off; off = align_up(off + (size_t)L.ctrl_words * 4, 256);
     L.ref = off; off = align_up(off + (rf ? ref_layout(pool).total : 0), 256);
     L.total = off;
@@ -592,23 +616,58 @@ extern "C" size_t dcx_pipeline_workspace_bytes(const dcx_detector* det, const dc
     return pipe_layout(det, rf, batch, height, width, pool).total;
 }
 
+extern "C" size_t dcx_front_bytes(const dcx_detector* det, int batch, int height, int width) {
+    if (!det || batch <= 0 || height <= 0 || width <= 0) return 0;
+    return front_layout(batch, height, width).total;
+}
+
 namespace {
-// the whole path for frames [0, batch) on ONE stream
+// dcx_infer_batch's checks of the frames and the shape, for the two prefetch entries
+int check_batch_args(const dcx_detector* det, const uint8_t* d_frames_u8, int pitch, int pixel_format, int batch, int height,
+                     int width) {
+    if (!det || !d_frames_u8) return DCX_E_ARG;
+    if (pixel_format != DCX_PIX_GRAY8 && pixel_format != DCX_PIX_BGR8 && pixel_format != DCX_PIX_BGR8_LEGACY14) return DCX_E_ARG;
+    if (batch <= 0 || batch > (1 << 20) || height < 8 || width < 8) return DCX_E_SHAPE;      // any size >= 8: the three poolings floor (net.py:16)
+    if (pitch < width * (pixel_format == DCX_PIX_GRAY8 ? 1 : 3)) return DCX_E_SHAPE;
+    return 0;
+}
+}  // namespace
+
+extern "C" int dcx_detector_front(const dcx_detector* det, const uint8_t* d_frames_u8, long frame_stride, int pitch,
+                                  int pixel_format, int batch, int height, int width, void* d_front, size_t front_bytes,
+                                  void* stream) {
+    if (!d_front) return DCX_E_ARG;
+    if (const int rc = check_batch_args(det, d_frames_u8, pitch, pixel_format, batch, height, width)) return rc;
+    const FrontWs F = front_layout(batch, height, width);
+    if (front_bytes < F.total) return DCX_E_WS;
+    char* front = (char*)d_front;
+    return detector_front(det, d_frames_u8, frame_stride, pitch, pixel_format, nullptr, batch, height, width, (float*)(front + F.act),
+                          (int32_t*)(front + F.ctrl), F.ctrl_words, (hipStream_t)stream);
+}
+
+namespace {
+// the whole path for frames [0, batch) on ONE stream.  front (nullable): a prefetch set dcx_detector_front has filled for these
+// frames -- conv1a is not launched, its output and the control words are the set's
 int infer_range(const dcx_detector* det, const dcx_refiner* rf, const uint8_t* d_frames_u8, long frame_stride, int pitch, int pix,
-                int batch, int height, int width, int dust_bin, int pool, char* ws, size_t ws_bytes, int32_t* d_counts,
-                int32_t* d_starts, int32_t* d_rows, float* d_xy, float* d_conf, hipStream_t s, bool timing) {
+                int batch, int height, int width, int dust_bin, int pool, char* ws, size_t ws_bytes, char* front,
+                hipEvent_t detector_done, int32_t* d_counts, int32_t* d_starts, int32_t* d_rows, float* d_xy, float* d_conf,
+                hipStream_t s, bool timing) {
     void* stream = (void*)s;
     const PipeWs L = pipe_layout(det, rf, batch, height, width, pool);
     if (ws_bytes < L.total) return DCX_E_WS;
     int rc = timing ? timing_mark(0, s) : 0;
     if (rc) return rc;
-    int32_t* ctrl = (int32_t*)(ws + L.ctrl);
+    const FrontWs F = front_layout(batch, height, width);
+    int32_t* ctrl = (int32_t*)(front ? front + F.ctrl : ws + L.ctrl);
     // detector up to convPa|convDa (its first kernel also clears the pool cursor and the frame tickets), then ONE kernel for the
     // 1x1 heads + per-cell arg-max + dust-bin rule + ordered compaction into the batch's corner pool (the logits never reach HBM;
     // dcModel.forward keeps the separate heads because it has to return them)
     rc = detector_run(det, d_frames_u8, frame_stride, pitch, pix, nullptr, batch, height, width, ws + L.det, L.table - L.det,
-                      false, nullptr, nullptr, ctrl, L.ctrl_words, stream);
+                      false, nullptr, nullptr, ctrl, L.ctrl_words, front ? (const float*)(front + F.act) : nullptr, stream);
     if (rc) return rc;
+    // behind the detector's last full-chip convolution: from here to RefineNet's conv1b the launches are small (tail, patch
+    // gather) and a caller's next front can run beside them
+    if (detector_done) DCX_CHECK_HIP(hipEventRecord(detector_done, s));
     if (timing && (rc = timing_mark(1, s))) return rc;
     int32_t* table = (int32_t*)(ws + L.table);
     {
@@ -655,7 +714,23 @@ extern "C" int dcx_infer_batch(const dcx_detector* det, const dcx_refiner* rf, c
     //  bs=32.  What does gain ~7 % is overlapping CONSECUTIVE batches on two streams, which is the caller's business:
     //  tools/two_stream_probe.py.)
     return infer_range(det, rf, d_frames_u8, frame_stride, pitch, pixel_format, batch, height, width, dust_bin, pool, ws, ws_bytes,
-                       d_counts, d_starts, d_rows, d_xy, d_conf, s, true);
+                       nullptr, nullptr, d_counts, d_starts, d_rows, d_xy, d_conf, s, true);
+}
+
+extern "C" int dcx_infer_batch_prefetched(const dcx_detector* det, const dcx_refiner* rf, const uint8_t* d_frames_u8,
+                                          long frame_stride, int pitch, int pixel_format, int batch, int height, int width,
+                                          int dust_bin, int pool, void* d_ws, size_t ws_bytes, void* d_front, size_t front_bytes,
+                                          int32_t* d_counts, int32_t* d_starts, int32_t* d_rows, float* d_xy, float* d_conf,
+                                          void* detector_done_event, void* stream) {
+    if (!d_ws || !d_front || !d_counts || !d_starts || !d_rows) return DCX_E_ARG;
+    if (rf != nullptr && d_xy == nullptr) return DCX_E_ARG;
+    if (const int rc = check_batch_args(det, d_frames_u8, pitch, pixel_format, batch, height, width)) return rc;
+    if (pool <= 0 || pool > (1 << 22)) return DCX_E_SHAPE;
+    if (dust_bin < 0 || dust_bin > 255) return DCX_E_NIDS;
+    if (front_bytes < front_layout(batch, height, width).total) return DCX_E_WS;
+    return infer_range(det, rf, d_frames_u8, frame_stride, pitch, pixel_format, batch, height, width, dust_bin, pool, (char*)d_ws,
+                       ws_bytes, (char*)d_front, (hipEvent_t)detector_done_event, d_counts, d_starts, d_rows, d_xy, d_conf,
+                       (hipStream_t)stream, true);
 }
 
 extern "C" int dcx_stream_synchronize(void* stream) { return (int)hipStreamSynchronize((hipStream_t)stream); }

@@ -170,16 +170,45 @@ def packed_len(batch: int, pool: int, conf: bool = False) -> int:
 
 
 def launch_pipeline(det, ref, frames_ptr: int, b: int, h: int, w: int, bpp: int, pix: int, dust_bin_ids: int, pool: int,
-                    ws: torch.Tensor, out_ptr: int, conf: bool = False) -> None:
+                    ws: torch.Tensor, out_ptr: int, conf: bool = False, front: Optional[torch.Tensor] = None,
+                    detector_done: Optional[int] = None) -> None:
     """``dcx_infer_batch`` on raw pointers (current device / stream): dense frames at ``frames_ptr``, the packed result
     (``packed_len(b, pool, conf)`` int32 words) at ``out_ptr``.  The pointers only have to be DEVICE-ACCESSIBLE: pinned host
-    memory qualifies, which is how the bs=1 hipGraph reads the frame and writes the corner list without copy nodes."""
+    memory qualifies, which is how the bs=1 hipGraph reads the frame and writes the corner list without copy nodes.
+    ``front``: a prefetch set that ``launch_front`` has filled for the same frames -- the path then starts at conv1b
+    (``dcx_infer_batch_prefetched``); ``detector_done``: a hipEvent_t it records behind the detector's last convolution."""
     counts_p, starts_p, rows_p = out_ptr, out_ptr + 4 * b, out_ptr + 8 * b
     xy_p = rows_p + 16 * pool
     conf_p = xy_p + 8 * pool
-    _lib.check(_lib.lib().dcx_infer_batch(det.handle, ref.handle if ref else None, frames_ptr, h * w * bpp, w * bpp, pix, b, h, w,
-                                          dust_bin_ids, pool, ws.data_ptr(), ws.numel(), counts_p, starts_p, rows_p,
-                                          xy_p if ref else None, conf_p if conf else None, _lib.current_stream()), "dcx_infer_batch")
+    head = (det.handle, ref.handle if ref else None, frames_ptr, h * w * bpp, w * bpp, pix, b, h, w, dust_bin_ids, pool,
+            ws.data_ptr(), ws.numel())
+    tail = (counts_p, starts_p, rows_p, xy_p if ref else None, conf_p if conf else None, _lib.current_stream())
+    if front is None:
+        _lib.check(_lib.lib().dcx_infer_batch(*head, *tail), "dcx_infer_batch")
+    else:
+        _lib.check(_lib.lib().dcx_infer_batch_prefetched(*head, front.data_ptr(), front.numel(), *tail[:-1], detector_done, tail[-1]),
+                   "dcx_infer_batch_prefetched")
+
+
+def launch_front(det, frames_ptr: int, b: int, h: int, w: int, bpp: int, pix: int, front: torch.Tensor) -> None:
+    """``dcx_detector_front`` on raw pointers (current device / stream): the detector's conv1a of the frames into the prefetch set
+    ``front`` (uint8 GPU tensor of at least ``dcx_front_bytes`` bytes), whose control words it clears."""
+    _lib.check(_lib.lib().dcx_detector_front(det.handle, frames_ptr, h * w * bpp, w * bpp, pix, b, h, w, front.data_ptr(),
+                                             front.numel(), _lib.current_stream()), "dcx_detector_front")
+
+
+def pipeline_workspace(det, ref, b: int, h: int, w: int, pool: int, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The scratch buffer of one pipeline launch (current device / stream): the caller's ``ws`` checked against
+    ``dcx_pipeline_workspace_bytes``, or the buffer the detector object keeps per HIP stream."""
+    dev = det.device
+    nbytes = _lib.lib().dcx_pipeline_workspace_bytes(det.handle, ref.handle if ref else None, b, h, w, pool)
+    if nbytes == 0:
+        raise ValueError("bad batch/shape for dcx_pipeline_workspace_bytes")
+    if ws is None:
+        return det._ws.get("pipe", dev, nbytes)
+    if ws.device != dev or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes:
+        raise ValueError(f"ws must be a contiguous uint8 tensor of >= {nbytes} bytes on {dev}")
+    return ws
 
 
 def infer_batch_device(frames: torch.Tensor, dust_bin_ids: int, deepc, refinenet=None, kmax: int = DEFAULT_KMAX,
@@ -221,15 +250,8 @@ def infer_batch_device(frames: torch.Tensor, dust_bin_ids: int, deepc, refinenet
         pool = b * kmax
     if pool <= 0:
         raise ValueError("pool must be positive")
-    L = _lib.lib()
     with torch.cuda.device(dev):
-        nbytes = L.dcx_pipeline_workspace_bytes(det.handle, ref.handle if ref else None, b, h, w, pool)
-        if nbytes == 0:
-            raise ValueError("bad batch/shape for dcx_pipeline_workspace_bytes")
-        if ws is None:
-            ws = det._ws.get("pipe", dev, nbytes)
-        elif ws.device != dev or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < nbytes:
-            raise ValueError(f"ws must be a contiguous uint8 tensor of >= {nbytes} bytes on {dev}")
+        ws = pipeline_workspace(det, ref, b, h, w, pool, ws)
         n_i32 = packed_len(b, pool, conf)
         if out is None:
             out = torch.empty((n_i32,), dtype=torch.int32, device=dev)

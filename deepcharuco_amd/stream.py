@@ -16,6 +16,7 @@ puts the consensus search of ``pnp.solve_pnp_ransac_pool`` in that kernel's plac
 """
 from __future__ import annotations
 
+import os
 import time
 import warnings
 from typing import Iterable, Iterator, List, Optional, Tuple
@@ -23,7 +24,9 @@ from typing import Iterable, Iterator, List, Optional, Tuple
 import numpy as np
 import torch
 
-from .inference import DEFAULT_KMAX, infer_batch, infer_batch_device, packed_len, solve_pnp_submit, unpack_results
+from . import _lib
+from .inference import (DEFAULT_KMAX, PIXEL_FORMATS, infer_batch, infer_batch_device, launch_front, launch_pipeline, packed_len, pipeline_workspace, solve_pnp_submit,
+                        unpack_results)
 from .models._handles import unwrap
 from .pnp import (POSE_WORDS, ransac_workspace_bytes, solve_pnp_batch_device, solve_pnp_pool, solve_pnp_ransac_batch_device,
                   solve_pnp_ransac_pool, unpack_poses, unpack_ransac)
@@ -215,12 +218,33 @@ class ResidentStream:
     per-frame key-point arrays -- no host work besides the event wait (a batch that had to be re-run comes back laid out for
     ``pool = sum(counts)``, which the buffer's own first ``n`` words give).  Overflow of a batch's corner pool (``batch * kmax``
     corners for the whole batch, no per-frame cap) is handled as everywhere else: that batch is run once more with the pool the
-    first pass reported."""
+    first pass reported.
+
+    The packed result of a batch is written by the kernels themselves into the slot's pinned buffer (no device copy, no D2H
+    copy node).
+
+    With one compute stream the detector's conv1a of a batch is PREFETCHED: ``submit`` enqueues it on a side stream of the stream
+    object's own (``dcx_detector_front``), released by the event the previous batch records behind its detector's last convolution,
+    so it runs beside that batch's tail / patch-gather launches and the first RefineNet launch instead of in front of its own
+    conv1b; the compute stream waits for it and runs the rest (``dcx_infer_batch_prefetched``).  Two prefetch sets (conv1a's
+    output + the batch's control words) alternate by ticket; a set's reuse is ordered behind the batch that last used it.  They
+    are allocated once per stream object and cost 2 x 630 MB at 32 frames of 320x240, 2 x 2.5 GB at 128 of 640x480, 2 x 10 GB at
+    32 of 1280x960; by default they are only taken up to ``PREFETCH_MAX_BYTES`` (1 GiB) per set -- above it conv1a is many times
+    longer than the small launches it can hide behind -- and ``prefetch=True`` / ``False`` overrides that.  If the allocation
+    fails the stream warns once and runs the plain path.  WHERE the front runs decides
+    everything: released at the start of the previous batch (beside its conv1b) it costs 11.6 %, released behind the detector it
+    gains 1.1 % (profiles/experiments/front_prefetch.txt).  The plain, unprefetched path stays for ``compute_streams`` > 1, for
+    the pool-overflow re-run inside ``_collect``, for ``infer_batch_device`` itself and for the N>1 path under
+    ``sharding.OverlappedGather``."""
+
+    PREFETCH_MAX_BYTES = 1 << 30       # a prefetch set above this size is not allocated unless asked for (class docstring)
 
     def __init__(self, dust_bin_ids: int, deepc, refinenet=None, batch: int = 32, height: int = 240, width: int = 320,
                  kmax: int = DEFAULT_KMAX, compute_streams: int = 1, depth: Optional[int] = None, bgr: bool = False,
-                 raw: bool = False, timing: bool = False):
-        """``timing=True``: every batch is bracketed by a timing-enabled event pair on its compute stream; ``gpu_ms`` then
+                 raw: bool = False, timing: bool = False, prefetch: Optional[bool] = None):
+        """``prefetch``: the conv1a prefetch of the class docstring.  None (default): on with one compute stream when a prefetch
+        set is at most ``PREFETCH_MAX_BYTES``; True: on whatever the size (one compute stream only); False: off.
+        ``timing=True``: every batch is bracketed by a timing-enabled event pair on its compute stream; ``gpu_ms`` then
         holds, per retired batch, the time from the moment the stream reached the batch to its last byte in pinned memory
         (bench.py's step_breakdown).  The host-side counters ``host_enqueue_s`` (time spent inside ``submit`` launching work) and
         ``host_wait_s`` (time blocked on the oldest batch's completion event) are always kept."""
@@ -238,11 +262,32 @@ class ResidentStream:
         n_out = packed_len(batch, self.pool)
         with torch.cuda.device(self.dev):
             self.compute = [torch.cuda.Stream() for _ in range(compute_streams)]
-            self.dev_out = [torch.empty((n_out,), dtype=torch.int32, device=self.dev) for _ in range(depth)]
             self.pin_out = [torch.empty((n_out,), dtype=torch.int32).pin_memory() for _ in range(depth)]
             self.ev_in = [torch.cuda.Event() for _ in range(depth)]
             self.ev_start = [torch.cuda.Event(enable_timing=True) for _ in range(depth)] if self.timing else None
             self.ev_done = [torch.cuda.Event(enable_timing=self.timing) for _ in range(depth)]
+            self._front = None
+            if prefetch and compute_streams != 1:
+                raise ValueError("prefetch needs compute_streams == 1 (several streams already overlap everything)")
+            nb = _lib.lib().dcx_front_bytes(det.handle, batch, height, width)
+            if prefetch is None and os.environ.get("DCX_RS_PREFETCH"):          # A/B switches of the measurement
+                prefetch = os.environ["DCX_RS_PREFETCH"] != "0"
+            if os.environ.get("DCX_RS_PRIO", "0") != "0":
+                self.compute = [torch.cuda.Stream(priority=-1)]
+            if prefetch is None:
+                prefetch = compute_streams == 1 and nb <= self.PREFETCH_MAX_BYTES
+            if prefetch and compute_streams == 1:
+                try:
+                    self._front = [torch.empty((nb,), dtype=torch.uint8, device=self.dev) for _ in range(2)]
+                except torch.cuda.OutOfMemoryError:
+                    warnings.warn(f"ResidentStream: no memory for two prefetch sets of {nb} bytes; running without the conv1a prefetch")
+                else:
+                    self.side = torch.cuda.Stream()
+                    self.ev_front = [torch.cuda.Event() for _ in range(depth)]
+                    self.ev_det = [torch.cuda.Event() for _ in range(depth)]     # behind the detector's last conv of the slot's batch
+                    for e in self.ev_det:
+                        e.record(self.side)          # (creates the hipEvent_t the native call records)
+                    self._last_det: Optional[torch.cuda.Event] = None
         self._pending: List[Optional[Tuple[int, torch.Tensor, torch.cuda.Stream]]] = [None] * depth     # (ticket, device frames, its stream)
         self._ticket = 0
         self.gpu_ms: List[float] = []
@@ -297,17 +342,37 @@ class ResidentStream:
         slot = self._ticket % self.depth
         retired = self._collect(slot) if self._pending[slot] is not None else None
         t0 = time.perf_counter()
-        n_out = packed_len(n, self.pool)
         with torch.cuda.device(self.dev):
             compute = self.compute[self._ticket % len(self.compute)]
             self.ev_in[slot].record(torch.cuda.current_stream())     # whatever produced `frames` was enqueued on the caller's stream
+            det, ref = unwrap(self.deepc), unwrap(self.refinenet)
+            bpp, pix = (3, PIXEL_FORMATS["opencv4"]) if self.bgr else (1, PIXEL_FORMATS["gray"])
+            front = None
+            if self._front is not None:
+                # conv1a of THIS batch on the side stream, released by the previous batch's detector-done event: it runs beside
+                # that batch's tail / patch-gather launches.  The event is on the compute stream behind everything of the batch two
+                # tickets back, the last user of this set
+                front = self._front[self._ticket % 2]
+                with torch.cuda.stream(self.side):
+                    self.side.wait_event(self.ev_in[slot])
+                    if self._last_det is not None:
+                        self.side.wait_event(self._last_det)
+                    launch_front(det, frames.data_ptr(), n, self.h, self.w, bpp, pix, front)
+                    self.ev_front[slot].record(self.side)
+                self._last_det = self.ev_det[slot]
             with torch.cuda.stream(compute):
                 compute.wait_event(self.ev_in[slot])
                 if self.timing:
                     self.ev_start[slot].record(compute)
-                infer_batch_device(frames, self.dust_bin_ids, self.deepc, self.refinenet, out=self.dev_out[slot][:n_out],
-                                   pool=self.pool)
-                self.pin_out[slot][:n_out].copy_(self.dev_out[slot][:n_out], non_blocking=True)
+                if front is not None:
+                    compute.wait_event(self.ev_front[slot])
+                # the kernels get the slot's PINNED buffer as their result: the tail and finalize kernels write the packed list
+                # (49 KB at bs=32) to host memory with their ordinary stores, as graph.py's one-frame path has done since round 5.
+                # No device copy of the result and no D2H copy in the stream, behind which the next batch's first kernel waited
+                # (profiles/experiments/front_prefetch.txt).  Same call as infer_batch_device otherwise: scratch per (model, stream)
+                launch_pipeline(det, ref, frames.data_ptr(), n, self.h, self.w, bpp, pix, self.dust_bin_ids, self.pool,
+                                pipeline_workspace(det, ref, n, self.h, self.w, self.pool), self.pin_out[slot].data_ptr(), front=front,
+                                detector_done=self.ev_det[slot].cuda_event if front is not None else None)
                 self.ev_done[slot].record(compute)
         self._pending[slot] = (self._ticket, frames, compute)
         self._ticket += 1

@@ -194,6 +194,25 @@ int dcx_infer_batch(const dcx_detector* det, const dcx_refiner* rf,
                     int batch, int height, int width, int dust_bin, int pool,
                     void* d_ws, size_t ws_bytes,
                     int32_t* d_counts, int32_t* d_starts, int32_t* d_rows, float* d_xy, float* d_conf, void* stream);
+/* The same path in two calls, for a caller that runs the NEXT batch's first layer beside the current batch's convolutions:
+ * dcx_detector_front runs the detector's conv1a (u8 load, BN, ReLU) of a batch into a PREFETCH SET -- conv1a's output,
+ * batch x 64 x H x W f32, and the control words of the batch (pool cursor, frame tickets), which it clears -- on the stream it is
+ * given; it depends on nothing but the frames.  dcx_infer_batch_prefetched then does what dcx_infer_batch does from conv1b on:
+ * it reads the set instead of launching conv1a and leaves the same results, bit for bit.  The set is in use from the front
+ * call until the prefetched call's last kernel has finished (RefineNet reads the cursor as its patch count): two sets let
+ * consecutive batches alternate.  Order the two calls with an event if they are on different streams; frames, shape and pixel
+ * format must be the same in both.  detector_done_event (a hipEvent_t, nullable) is recorded on the stream behind the detector's last
+ * convolution launch: the point from which the launches are small until RefineNet's conv1b -- where a front for the next batch
+ * does least harm.  d_front must hold dcx_front_bytes() (0: bad arguments); DCX_E_WS if it does not.          */
+size_t dcx_front_bytes(const dcx_detector* det, int batch, int height, int width);
+int dcx_detector_front(const dcx_detector* det, const uint8_t* d_frames_u8, long frame_stride, int pitch, int pixel_format,
+                       int batch, int height, int width, void* d_front, size_t front_bytes, void* stream);
+int dcx_infer_batch_prefetched(const dcx_detector* det, const dcx_refiner* rf,
+                               const uint8_t* d_frames_u8, long frame_stride, int pitch, int pixel_format,
+                               int batch, int height, int width, int dust_bin, int pool,
+                               void* d_ws, size_t ws_bytes, void* d_front, size_t front_bytes,
+                               int32_t* d_counts, int32_t* d_starts, int32_t* d_rows, float* d_xy, float* d_conf,
+                               void* detector_done_event, void* stream);
 /* hipStreamSynchronize(stream) -> the hipError_t.  Waits in the HIP runtime this library was linked against, which is the one
  * whose streams the caller passes here (torch's, in the Python package): a second copy of the runtime loaded beside it would not
  * know those streams, and its synchronisation of the default stream would return without waiting.                           */
