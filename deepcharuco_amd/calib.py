@@ -40,7 +40,7 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _lm, pnp
+from . import _dev, _lm, pnp
 from .pnp import (PNP_BAD_ID, PNP_DEGENERATE, PNP_NO_CONSENSUS, PNP_NONFINITE, PNP_OK, PNP_TOO_FEW, _bad_id_error, _homography,
                   _project, _rodrigues, _solve)
 
@@ -486,6 +486,16 @@ def workspace_bytes(batch: int) -> int:
     return int(_lib.lib().dcx_calibrate_workspace_bytes(int(batch)))
 
 
+def _common_fields(res, view_status, pose) -> tuple:
+    """The 16-double result of either device calibration and the host copies of its per-view outputs -> the fields that
+    ``CalibResult`` and ``RobustCalibResult`` share, in their order."""
+    r = np.array(res[:], np.float64)
+    status = int(r[14])
+    K = np.array([[r[0], 0.0, r[2]], [0.0, r[1], r[3]], [0.0, 0.0, 1.0]]) if status == CALIB_OK else np.zeros((3, 3))
+    return (status, float(r[9]), K, r[4:9].reshape(1, 5).copy(), view_status.astype(np.int32), pose[:, 0:3].copy(),
+            pose[:, 3:6].copy(), pose[:, 6].copy(), pose[:, 7].astype(np.int64), int(r[10]), int(r[11]), int(r[12]), int(r[13]))
+
+
 def calibrate_charuco_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len,
                            image_size) -> CalibResult:
     """Calibrate from every frame of an ``infer_batch_device`` result, read in place from the corner pool (the conventions of
@@ -507,12 +517,7 @@ def calibrate_charuco_pool(packed, batch: int, pool: int, refined: bool, col_cou
                                                  w, h, ws.data_ptr(), nbytes, st.data_ptr(), pose.data_ptr(), res,
                                                  _lib.current_stream()), "dcx_calibrate_pool")
         st_h, pose_h = st.cpu().numpy(), pose.cpu().numpy()
-    r = np.array(res[:], np.float64)
-    status = int(r[14])
-    K = np.array([[r[0], 0.0, r[2]], [0.0, r[1], r[3]], [0.0, 0.0, 1.0]]) if status == CALIB_OK else np.zeros((3, 3))
-    return CalibResult(status, float(r[9]), K, r[4:9].reshape(1, 5).copy(), st_h.astype(np.int32), pose_h[:, 0:3].copy(),
-                       pose_h[:, 3:6].copy(), pose_h[:, 6].copy(), pose_h[:, 7].astype(np.int64), int(r[10]), int(r[11]),
-                       int(r[12]), int(r[13]))
+    return CalibResult(*_common_fields(res, st_h, pose_h))
 
 
 def calibrate_charuco_device(keypoints_list: Sequence, col_count, row_count, square_len, image_size,
@@ -559,16 +564,13 @@ def calibrate_charuco_ransac_pool(packed, batch: int, pool: int, refined: bool, 
     iterations, cthr, rthr, min_inliers, rounds = _calib_ransac_args(iterations, consensus_error, reproj_error, min_inliers, rounds)
     dev = packed.device
     ptrs = pnp._pool_ptrs(packed, batch, pool, refined)
-    if out_inliers is None:
-        out_inliers = torch.zeros((max(pool, 1),), dtype=torch.uint8, device=dev)
-    if (out_inliers.device != dev or out_inliers.dtype != torch.uint8 or out_inliers.numel() < pool
-            or not out_inliers.is_contiguous()):
-        raise ValueError(f"out_inliers must be a contiguous uint8 tensor of at least {pool} values on {dev}")
+    out_inliers = _dev.tensor(out_inliers, dev, torch.uint8, (pool,),
+                              f"out_inliers must be a contiguous uint8 tensor of at least {pool} values on {dev}", "min", zeros=True)
     st = torch.empty((batch,), dtype=torch.int32, device=dev)
     pose = torch.empty((batch, pnp.POSE_WORDS), dtype=torch.float64, device=dev)
     info = torch.empty((batch, 2), dtype=torch.int32, device=dev)
     nbytes = ransac_workspace_bytes(batch, pool, iterations)
-    ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev)
+    ws = _dev.workspace(None, dev, nbytes)
     res = (_ctypes.c_double * RESULT_WORDS)()
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().dcx_calibrate_ransac_pool(
@@ -577,16 +579,11 @@ def calibrate_charuco_ransac_pool(packed, batch: int, pool: int, refined: bool, 
             ws.data_ptr(), nbytes, st.data_ptr(), pose.data_ptr(), info.data_ptr(), out_inliers.data_ptr(), res,
             _lib.current_stream()), "dcx_calibrate_ransac_pool")
         st_h, pose_h, info_h, inl_h, head = (t.cpu().numpy() for t in (st, pose, info, out_inliers, packed[:2 * batch]))
-    r = np.array(res[:], np.float64)
-    status = int(r[14])
-    K = np.array([[r[0], 0.0, r[2]], [0.0, r[1], r[3]], [0.0, 0.0, 1.0]]) if status == CALIB_OK else np.zeros((3, 3))
-    inl_b = inl_h.astype(bool)
+    inl_b, solves = inl_h.astype(bool), int(res[15])
     inliers = [inl_b[s0:s0 + n] if n > 0 and s0 >= 0 and s0 + n <= pool else np.zeros(max(n, 0), bool)
                for n, s0 in zip(head[:batch].tolist(), head[batch:].tolist())]
-    return RobustCalibResult(status, float(r[9]), K, r[4:9].reshape(1, 5).copy(), st_h.astype(np.int32), pose_h[:, 0:3].copy(),
-                             pose_h[:, 3:6].copy(), pose_h[:, 6].copy(), pose_h[:, 7].astype(np.int64), int(r[10]), int(r[11]),
-                             int(r[12]), int(r[13]), inliers, info_h[:, 0].astype(np.int64), info_h[:, 1].astype(np.int32),
-                             int(r[15]) % 16, int(r[15]) >= 16)
+    return RobustCalibResult(*_common_fields(res, st_h, pose_h), inliers, info_h[:, 0].astype(np.int64),
+                             info_h[:, 1].astype(np.int32), solves % 16, solves >= 16)
 
 
 def calibrate_charuco_ransac_device(keypoints_list: Sequence, col_count, row_count, square_len, image_size, iterations=100,

@@ -32,6 +32,7 @@
 // reject / forced / stop automaton (LmState<9>, lm_decide with STOP_FORCED = false), decide's body (lm_decide_block), trial's
 // prologue (lm_trial_pose), reduce_solve's entry -> source mapping (lm_source), the damping and the host loop (lm_run).  The
 // reduction in front of the 9x9 solve (8 slices x 128, added serially) is this unit's own: its order is part of the output bits.
+// The pool is dcx_pnp_dev.h's CornerPool (frame(b), frame_status), which its host check corner_pool() fills or refuses.
 #include "dcx_pnp_dev.h"
 #include "dcx_lm_dev.h"
 
@@ -75,27 +76,13 @@ size_t ws_layout(void* base, int batch, Ws* w) {
     return c.at;
 }
 
-struct Pool {
-    const int32_t* counts;
-    const int32_t* starts;
-    const int32_t* rows;
-    const float* xy;
-    int rm1;
-    double square_len;
-
-    __device__ Frame frame(int b) const {
-        const long long s0 = starts[b];
-        return Frame{rows + 4 * s0, xy ? xy + 2 * s0 : nullptr, counts[b], rm1, square_len};
-    }
-};
-
 // ---------------------------------------------------------------------------------------------------------------- init
 
-__global__ __launch_bounds__(kLanes) void calib_init_views_kernel(Pool pl, int pool, int n_ids, double cx, double cy,
-                                                                  int32_t* __restrict__ status, double* __restrict__ pose, Ws ws) {
+__global__ __launch_bounds__(kLanes) void calib_init_views_kernel(CornerPool pl, double cx, double cy, int32_t* __restrict__ status,
+                                                                  double* __restrict__ pose, Ws ws) {
     const int b = blockIdx.x, lane = threadIdx.x;
     int n, s0;
-    int st = frame_status(pl.counts, pl.starts, pl.rows, b, pool, n_ids, n, s0);
+    int st = frame_status(pl, b, n, s0);
     double r[6] = {0, 0, 0, 0, 0, 0};
     if (st == DCX_PNP_OK) {
         // the DLT on the pixels themselves: undistort() through the identity camera leaves them as they are
@@ -192,7 +179,7 @@ __global__ __launch_bounds__(kRedThreads) void calib_init_reduce_kernel(int batc
     st->code = kNextEvaluate;
 }
 
-__global__ __launch_bounds__(kLanes) void calib_init_poses_kernel(Pool pl, int32_t* __restrict__ status, Ws ws) {
+__global__ __launch_bounds__(kLanes) void calib_init_poses_kernel(CornerPool pl, int32_t* __restrict__ status, Ws ws) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (ws.st->code == kFinished || status[b] != DCX_PNP_OK) return;
     const PnpCamera cam = camera_of(ws.st->g);       // K0, zero distortion
@@ -232,7 +219,7 @@ __device__ __forceinline__ bool project_point(const PnpCamera& cam, const double
 
 constexpr int kLdsStride = 17;     // 16 values per row, padded
 
-__global__ __launch_bounds__(kLanes) void calib_evaluate_kernel(Pool pl, const int32_t* __restrict__ status, Ws ws) {
+__global__ __launch_bounds__(kLanes) void calib_evaluate_kernel(CornerPool pl, const int32_t* __restrict__ status, Ws ws) {
     __shared__ double sj[2 * kLanes][kLdsStride];
     const int b = blockIdx.x, lane = threadIdx.x;
     if (ws.st->code != kNextEvaluate || status[b] != DCX_PNP_OK) return;
@@ -373,7 +360,7 @@ __global__ __launch_bounds__(kRedThreads) void calib_reduce_solve_kernel(int bat
     }
 }
 
-__global__ __launch_bounds__(kLanes) void calib_trial_kernel(Pool pl, const int32_t* __restrict__ status, Ws ws) {
+__global__ __launch_bounds__(kLanes) void calib_trial_kernel(CornerPool pl, const int32_t* __restrict__ status, Ws ws) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (ws.st->code == kFinished || status[b] != DCX_PNP_OK) return;
     // dcx_lm_dev.h's lm_trial_pose<9>, spelt out: called through it, this kernel's SGPR spills rise from 38 to 62 (the 75 uniform
@@ -443,19 +430,16 @@ extern "C" int dcx_calibrate_pool(const int32_t* d_counts, const int32_t* d_star
                                   int batch, int pool, int col_count, int row_count, double square_len, int image_width,
                                   int image_height, void* d_workspace, size_t workspace_bytes, int32_t* d_view_status,
                                   double* d_pose, double* h_result, void* stream) {
-    if (!d_counts || !d_starts || !d_rows || !d_workspace || !d_view_status || !d_pose || !h_result) return DCX_E_ARG;
-    if (batch <= 0 || pool < 0 || col_count < 2 || row_count < 2 || image_width <= 0 || image_height <= 0) return DCX_E_ARG;
-    if ((long long)(col_count - 1) * (row_count - 1) > 0x7fffffffLL) return DCX_E_ARG;
-    if (!isfinite(square_len)) return DCX_E_ARG;
+    CornerPool pl;
+    if (!corner_pool(d_counts, d_starts, d_rows, d_xy, batch, pool, col_count, row_count, square_len, pl)) return DCX_E_ARG;
+    if (!d_workspace || !d_view_status || !d_pose || !h_result || image_width <= 0 || image_height <= 0) return DCX_E_ARG;
     if (workspace_bytes < ws_layout(nullptr, batch, nullptr)) return DCX_E_WS;
     hipStream_t s = (hipStream_t)stream;
     Ws ws;
     ws_layout(d_workspace, batch, &ws);
-    const Pool pl{d_counts, d_starts, d_rows, d_xy, row_count - 1, square_len};
     const double cx = (image_width - 1) * 0.5, cy = (image_height - 1) * 0.5;
     const dim3 views((unsigned)batch), wave(kLanes), one(1), red(kRedThreads);
-    hipLaunchKernelGGL(calib_init_views_kernel, views, wave, 0, s, pl, pool, (col_count - 1) * (row_count - 1), cx, cy, d_view_status,
-                       d_pose, ws);
+    hipLaunchKernelGGL(calib_init_views_kernel, views, wave, 0, s, pl, cx, cy, d_view_status, d_pose, ws);
     hipLaunchKernelGGL(calib_init_reduce_kernel, one, red, 0, s, batch, cx, cy, d_view_status, d_pose, ws);
     hipLaunchKernelGGL(calib_init_poses_kernel, views, wave, 0, s, pl, d_view_status, ws);
     hipLaunchKernelGGL(calib_evaluate_kernel, views, wave, 0, s, pl, d_view_status, ws);

@@ -21,6 +21,8 @@
 // A view's slot range is written in the filtered pool, so ranges must not overlap: `overlap` (one wave per view against every other
 // view) looks first and the call is refused before anything else runs.  Nothing is allocated, no atomics, every reduction has a
 // fixed order: two calls give the same bits.  Like dcx_calibrate_pool the call synchronises its stream.
+// The caller's pool is dcx_pnp_dev.h's CornerPool, filled by its host check corner_pool(); the filtered pool in the workspace goes to
+// dcx_calibrate_pool through the C entry, which checks and fills its own.
 // From the headers: frame_status, ranges_overlap, the sampler, the four-point homography, row_error2 and best_hypothesis
 // (dcx_pnp_dev.h), append_kept and the workspace carver (dcx_mat_dev.h), identity_camera and camera_of (dcx_camera_dev.h).
 #include "dcx_pnp_dev.h"
@@ -30,15 +32,6 @@ namespace {
 constexpr int kMaxRounds = 8;            // calib.RANSAC_MAX_ROUNDS
 constexpr int kHeadWords = 16;           // int32 words at the head of the workspace
 enum : int { kOverlap = 0, kChanged = 1 };
-
-struct RPool {                           // the caller's pool
-    const int32_t* counts;
-    const int32_t* starts;
-    const int32_t* rows;
-    const float* xy;                     // or null: the integer rows are the image points
-    int pool, n_ids, rm1;
-    double square_len;
-};
 
 // workspace: head | dcx_calibrate_pool's workspace | scores [B][iterations] | counts' starts' vstat winner changed [B] each |
 // rows' [pool][4] | xy' [pool][2] | mask [pool], every part 8-byte aligned
@@ -92,22 +85,18 @@ __device__ __forceinline__ double transfer_error2(const double* H, double mcx, d
     return du * du + dv * dv;
 }
 
-__device__ __forceinline__ Frame frame_of(const RPool& pl, int n, int s0) {
-    return Frame{pl.rows + 4 * (long long)s0, pl.xy ? pl.xy + 2 * (long long)s0 : nullptr, n, pl.rm1, pl.square_len};
-}
-
 // One wave per view: does its slot range meet another view's?
-__global__ __launch_bounds__(kLanes) void calib_ransac_overlap_kernel(RPool pl, int batch, int32_t* __restrict__ head) {
-    if (ranges_overlap(pl.counts, pl.starts, pl.pool, batch, blockIdx.x) && threadIdx.x == 0) head[kOverlap] = 1;
+__global__ __launch_bounds__(kLanes) void calib_ransac_overlap_kernel(CornerPool pl, int batch, int32_t* __restrict__ head) {
+    if (ranges_overlap(pl, batch, blockIdx.x) && threadIdx.x == 0) head[kOverlap] = 1;
 }
 
-__global__ __launch_bounds__(kLanes) void calib_ransac_consensus_kernel(RPool pl, int iterations, double thr2, uint32_t seed,
+__global__ __launch_bounds__(kLanes) void calib_ransac_consensus_kernel(CornerPool pl, int iterations, double thr2, uint32_t seed,
                                                                         int32_t* __restrict__ scores) {
     const int b = blockIdx.x, h = blockIdx.y * kLanes + threadIdx.x;
     int n, s0;
-    if (frame_status(pl.counts, pl.starts, pl.rows, b, pl.pool, pl.n_ids, n, s0) != DCX_PNP_OK) return;   // select reads no score
+    if (frame_status(pl, b, n, s0) != DCX_PNP_OK) return;   // select reads no score
     if (h >= iterations) return;
-    const Frame f = frame_of(pl, n, s0);
+    const Frame f = pl.frame(n, s0);
     double H[9], mcx, mcy;
     int score = -1;
     if (view_hypothesis(f, seed, h, H, mcx, mcy)) {
@@ -123,7 +112,7 @@ __global__ __launch_bounds__(kLanes) void calib_ransac_consensus_kernel(RPool pl
 
 // Rows base .. base + 63 of the view: the mask slot, and the rows that stay appended in order to the view's share of the filtered
 // pool; count moves past them.  Wave-wide.
-__device__ __forceinline__ void keep_rows(const RPool& pl, const RWs& ws, int s0, int i, int n, bool in, int& count) {
+__device__ __forceinline__ void keep_rows(const CornerPool& pl, const RWs& ws, int s0, int i, int n, bool in, int& count) {
     const long long from = (long long)s0 + i, to = (long long)s0 + append_kept(in, threadIdx.x, count);
     if (i < n) ws.mask[from] = in ? 1 : 0;
     if (in) {
@@ -137,7 +126,7 @@ __device__ __forceinline__ void keep_rows(const RPool& pl, const RWs& ws, int s0
 }
 
 // The view leaves the calibration: an empty view in the filtered pool, an all-false mask over its slots that lie in the pool.
-__device__ __forceinline__ void exclude_view(const RPool& pl, const RWs& ws, int b, int n, int s0, int status) {
+__device__ __forceinline__ void exclude_view(const CornerPool& pl, const RWs& ws, int b, int n, int s0, int status) {
     const int lane = threadIdx.x;
     if (n > 0)
         for (long long i = lane; i < n; i += kLanes)
@@ -148,11 +137,11 @@ __device__ __forceinline__ void exclude_view(const RPool& pl, const RWs& ws, int
     }
 }
 
-__global__ __launch_bounds__(kLanes) void calib_ransac_select_compact_kernel(RPool pl, int iterations, double thr2, int need,
+__global__ __launch_bounds__(kLanes) void calib_ransac_select_compact_kernel(CornerPool pl, int iterations, double thr2, int need,
                                                                              uint32_t seed, RWs ws) {
     const int b = blockIdx.x, lane = threadIdx.x;
     int n, s0;
-    const int st = frame_status(pl.counts, pl.starts, pl.rows, b, pl.pool, pl.n_ids, n, s0);
+    const int st = frame_status(pl, b, n, s0);
     if (lane == 0) {
         ws.starts[b] = st == DCX_PNP_OK ? s0 : 0;
         ws.winner[b] = -1;
@@ -168,7 +157,7 @@ __global__ __launch_bounds__(kLanes) void calib_ransac_select_compact_kernel(RPo
         exclude_view(pl, ws, b, n, s0, DCX_PNP_DEGENERATE);
         return;
     }
-    const Frame f = frame_of(pl, n, s0);
+    const Frame f = pl.frame(n, s0);
     double H[9], mcx, mcy;
     view_hypothesis(f, seed, bh, H, mcx, mcy);          // (it scored, so it exists: every lane recomputes the same H)
     int count = 0;
@@ -193,7 +182,7 @@ __global__ __launch_bounds__(kLanes) void calib_ransac_select_compact_kernel(RPo
     }
 }
 
-__global__ __launch_bounds__(kLanes) void calib_ransac_remask_kernel(RPool pl, PnpCamera cam, double thr2, int need,
+__global__ __launch_bounds__(kLanes) void calib_ransac_remask_kernel(CornerPool pl, PnpCamera cam, double thr2, int need,
                                                                      const int32_t* __restrict__ view_status,
                                                                      const double* __restrict__ pose, RWs ws) {
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -203,7 +192,7 @@ __global__ __launch_bounds__(kLanes) void calib_ransac_remask_kernel(RPool pl, P
         return;
     }
     const int n = pl.counts[b], s0 = pl.starts[b];
-    const Frame f = frame_of(pl, n, s0);
+    const Frame f = pl.frame(n, s0);
     double p[6], R[9];
 #pragma unroll
     for (int i = 0; i < 6; ++i) p[i] = pose[8 * (long long)b + i];
@@ -238,7 +227,7 @@ __global__ __launch_bounds__(kLanes) void calib_ransac_changed_sum_kernel(int ba
     if (threadIdx.x == 0) ws.head[kChanged] = s;
 }
 
-__global__ __launch_bounds__(kLanes) void calib_ransac_merge_kernel(RPool pl, RWs ws, int32_t* __restrict__ view_status,
+__global__ __launch_bounds__(kLanes) void calib_ransac_merge_kernel(CornerPool pl, RWs ws, int32_t* __restrict__ view_status,
                                                                     double* __restrict__ pose, int32_t* __restrict__ info,
                                                                     uint8_t* __restrict__ inliers) {
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -275,11 +264,11 @@ extern "C" int dcx_calibrate_ransac_pool(const int32_t* d_counts, const int32_t*
                                          int min_inliers, int rounds, unsigned seed, void* d_workspace, size_t workspace_bytes,
                                          int32_t* d_view_status, double* d_pose, int32_t* d_info, uint8_t* d_inliers,
                                          double* h_result, void* stream) {
-    if (!d_counts || !d_starts || !d_rows || !d_workspace || !d_view_status || !d_pose || !d_info || !h_result) return DCX_E_ARG;
-    if (!ransac_sizes_ok(batch, pool, iterations) || col_count < 2 || row_count < 2 || image_width <= 0 || image_height <= 0)
-        return DCX_E_ARG;
-    if ((long long)(col_count - 1) * (row_count - 1) > 0x7fffffffLL) return DCX_E_ARG;
-    if (!isfinite(square_len) || !isfinite(consensus_error) || !(consensus_error > 0) || !isfinite(reproj_error) ||
+    CornerPool pl;                       // the caller's pool
+    if (!corner_pool(d_counts, d_starts, d_rows, d_xy, batch, pool, col_count, row_count, square_len, pl)) return DCX_E_ARG;
+    if (!d_workspace || !d_view_status || !d_pose || !d_info || !h_result) return DCX_E_ARG;
+    if (!ransac_sizes_ok(batch, pool, iterations) || image_width <= 0 || image_height <= 0) return DCX_E_ARG;
+    if (!isfinite(consensus_error) || !(consensus_error > 0) || !isfinite(reproj_error) ||
         !(reproj_error > 0) || rounds < 0 || rounds > kMaxRounds)
         return DCX_E_ARG;
     if ((uintptr_t)d_workspace & 7) return DCX_E_ARG;
@@ -288,7 +277,6 @@ extern "C" int dcx_calibrate_ransac_pool(const int32_t* d_counts, const int32_t*
     rws_layout(d_workspace, batch, pool, iterations, &ws);
     const size_t inner_bytes = dcx_calibrate_workspace_bytes(batch);
     hipStream_t s = (hipStream_t)stream;
-    const RPool pl{d_counts, d_starts, d_rows, d_xy, pool, (col_count - 1) * (row_count - 1), row_count - 1, square_len};
     const dim3 views((unsigned)batch), wave(kLanes), one(1);
     const int need = min_inliers > 4 ? min_inliers : 4;
 

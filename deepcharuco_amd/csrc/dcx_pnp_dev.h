@@ -1,10 +1,11 @@
 // dcx_pnp_dev.h -- the pool reader, the consensus steps and the PnP solver, on top of dcx_camera_dev.h (camera model, rotations) and
-// dcx_mat_dev.h (small matrices, reductions): the frame types (Frame, IndexedFrame), the per-frame checks, the normal equations of
-// a frame at a pose (evaluate), the planar DLT homography, the planar pose init and the PnP Levenberg-Marquardt (solve), which
-// dcx_pnp.hip runs per frame, dcx_calib.hip and dcx_stereo.hip per view, and dcx_pnp_ransac.hip over an index list of a frame's rows
-// (the frame type is a template parameter).  Also here: what the consensus searches (dcx_pnp_ransac.hip, dcx_calib_ransac.hip) and
-// the masked stereo solve share: the slot-range overlap test, the sampler, the four-point homography, one row's reprojection error
-// and the first-maximum score search.
+// dcx_mat_dev.h (small matrices, reductions): the corner pool as every kernel receives it (CornerPool) and the one host-side check
+// that fills it from the C ABI's pool arguments (corner_pool), the frame types (Frame, IndexedFrame), the per-frame checks
+// (frame_status, ranges_overlap), the normal equations of a frame at a pose (evaluate), the planar DLT homography, the planar pose
+// init and the PnP Levenberg-Marquardt (solve), which dcx_pnp.hip runs per frame, dcx_calib.hip and dcx_stereo.hip per view, and
+// dcx_pnp_ransac.hip over an index list of a frame's rows (the frame type is a template parameter).  Also here: what the consensus
+// searches (dcx_pnp_ransac.hip, dcx_calib_ransac.hip) and the masked stereo solve share: the slot-range overlap test, the sampler,
+// the four-point homography, one row's reprojection error and the first-maximum score search.
 // deepcharuco_amd/pnp.py restates every step (its functions of the same names).  Everything is force-inlined and has internal
 // linkage, so each translation unit compiles its own copy.
 #pragma once
@@ -36,6 +37,33 @@ struct Frame {
         }
     }
 };
+
+// The corner pool dcx_infer_batch writes, with the board its ids refer to: what the five pool entries (dcx_solve_pnp_pool,
+// dcx_solve_pnp_ransac_pool, dcx_calibrate_pool, dcx_calibrate_ransac_pool, dcx_stereo_calibrate_pool) pass to their kernels.
+struct CornerPool {
+    const int32_t* counts;   // rows per frame
+    const int32_t* starts;   // a frame's first slot
+    const int32_t* rows;     // (x, y, id, cell) per slot
+    const float* xy;         // refined xy per slot, or null: the integer rows are the image points
+    int pool, n_ids, rm1;    // slots; (col_count - 1) * (row_count - 1); row_count - 1
+    double square_len;
+
+    __device__ __forceinline__ Frame frame(int n, long long s0) const {
+        return Frame{rows + 4 * s0, xy ? xy + 2 * s0 : nullptr, n, rm1, square_len};
+    }
+    __device__ __forceinline__ Frame frame(int b) const { return frame(counts[b], starts[b]); }
+};
+
+// The C ABI's pool arguments -> the pool, or false: what every pool entry refuses with DCX_E_ARG before it looks at anything else
+// of its own (a null pool pointer, no frames, a negative pool, a board without inner corners or with more than 2^31 - 1 of them,
+// a non-finite square).  d_xy may be null.
+inline bool corner_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows, const float* d_xy, int batch, int pool,
+                        int col_count, int row_count, double square_len, CornerPool& pl) {
+    if (!d_counts || !d_starts || !d_rows || batch <= 0 || pool < 0 || col_count < 2 || row_count < 2) return false;
+    if ((long long)(col_count - 1) * (row_count - 1) > 0x7fffffffLL || !isfinite(square_len)) return false;
+    pl = CornerPool{d_counts, d_starts, d_rows, d_xy, pool, (col_count - 1) * (row_count - 1), row_count - 1, square_len};
+    return true;
+}
 
 // The rows of a frame picked by an index list (the RANSAC refit over the inlier slots): row i of this frame is row idx[i] of base.
 struct IndexedFrame {
@@ -186,25 +214,25 @@ constexpr int kMaxDraws = 256;       // slot draws per hypothesis, redraws inclu
 
 // The per-frame checks, in the order of dcx_solve_pnp_kernel (which spells them out itself, see there) -> DCX_PNP_OK if the frame's
 // rows can be read and solved.  Wave-wide.
-__device__ __forceinline__ int frame_status(const int32_t* counts, const int32_t* starts, const int32_t* rows, int b, int pool,
-                                            int n_ids, int& n, int& s0) {
-    n = counts[b];
-    s0 = starts[b];
+__device__ __forceinline__ int frame_status(const CornerPool& pl, int b, int& n, int& s0) {
+    n = pl.counts[b];
+    s0 = pl.starts[b];
     if (n <= 0) return DCX_PNP_TOO_FEW;
-    if (s0 < 0 || (long long)s0 + n > (long long)pool) return DCX_PNP_TRUNCATED;      // (its slots are not read)
+    if (s0 < 0 || (long long)s0 + n > (long long)pl.pool) return DCX_PNP_TRUNCATED;   // (its slots are not read)
     if (n < 4) return DCX_PNP_TOO_FEW;
     bool bad = false;
     for (int i = threadIdx.x; i < n; i += kLanes) {
-        const int id = rows[4 * ((long long)s0 + i) + 2];
-        bad |= id < 0 || id >= n_ids;
+        const int id = pl.rows[4 * ((long long)s0 + i) + 2];
+        bad |= id < 0 || id >= pl.n_ids;
     }
     return __any(bad) ? DCX_PNP_BAD_ID : DCX_PNP_OK;
 }
 
 // One wave per view b of a pool whose views own their slot ranges: does b's range (the part inside the pool) meet another view's?
 // The lanes share the other views out.  Wave-wide.
-__device__ __forceinline__ bool ranges_overlap(const int32_t* counts, const int32_t* starts, int pool, int batch, int b) {
-    const long long n = counts[b], s0 = starts[b];
+__device__ __forceinline__ bool ranges_overlap(const CornerPool& pl, int batch, int b) {
+    const int32_t *counts = pl.counts, *starts = pl.starts;
+    const long long n = counts[b], s0 = starts[b], pool = pl.pool;
     if (n <= 0) return false;
     const long long lo = s0 < 0 ? 0 : s0, hi = s0 + n < pool ? s0 + n : pool;
     if (lo >= hi) return false;

@@ -12,7 +12,8 @@
 //               slots compacted in order into an index list, then the unchanged solve() (init + LM) over that list.
 // The sampler never looks at the frame's position in the batch, nothing is allocated, no atomics, no early exit: the work is fixed,
 // two runs give the same bits and the call can be captured in a hipGraph.
-// The sampler, the four-point homography, row_error2, best_hypothesis and solve() are dcx_pnp_dev.h's; append_kept is dcx_mat_dev.h's.
+// The pool type and its host check (CornerPool, corner_pool), frame_status, the sampler, the four-point homography, row_error2,
+// best_hypothesis and solve() are dcx_pnp_dev.h's; append_kept is dcx_mat_dev.h's.
 #include "dcx_pnp_dev.h"
 
 namespace {
@@ -40,15 +41,18 @@ __device__ __forceinline__ int hypothesis(const Frame& f, const PnpCamera& cam, 
     return score;
 }
 
+// Both kernels take the pool as loose __restrict__ parameters and make the CornerPool in their first line, as dcx_solve_pnp_kernel
+// does and for its reason (see there).
 __global__ __launch_bounds__(kLanes) void dcx_pnp_ransac_hypotheses_kernel(
     const int32_t* __restrict__ counts, const int32_t* __restrict__ starts, const int32_t* __restrict__ rows,
     const float* __restrict__ xy, int pool, int n_ids, int rm1, double square_len, PnpCamera cam, int iterations, double thr2,
     uint32_t seed, int32_t* __restrict__ scores, double* __restrict__ poses) {
     const int b = blockIdx.x, h = blockIdx.y * kLanes + threadIdx.x;
+    const CornerPool pl{counts, starts, rows, xy, pool, n_ids, rm1, square_len};
     int n, s0;
-    if (frame_status(counts, starts, rows, b, pool, n_ids, n, s0) != DCX_PNP_OK) return;   // select reports it and reads no score
+    if (frame_status(pl, b, n, s0) != DCX_PNP_OK) return;   // select reports it and reads no score
     if (h >= iterations) return;
-    const Frame f{rows + 4 * (long long)s0, xy ? xy + 2 * (long long)s0 : nullptr, n, rm1, square_len};
+    const Frame f = pl.frame(n, s0);
     double p0[6] = {0, 0, 0, 0, 0, 0};
     const int score = hypothesis(f, cam, has_distortion(cam), seed, h, thr2, p0);
     const long long at = (long long)b * iterations + h;
@@ -63,8 +67,9 @@ __global__ __launch_bounds__(kLanes) void dcx_pnp_ransac_select_kernel(
     int min_inliers, const int32_t* __restrict__ scores, const double* __restrict__ poses, int32_t* idx,
     int32_t* __restrict__ status, double* __restrict__ pose, int32_t* __restrict__ info, uint8_t* __restrict__ inliers) {
     const int b = blockIdx.x, lane = threadIdx.x;
+    const CornerPool pl{counts, starts, rows, xy, pool, n_ids, rm1, square_len};
     int n, s0;
-    int st = frame_status(counts, starts, rows, b, pool, n_ids, n, s0);
+    int st = frame_status(pl, b, n, s0);
     double out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int winner = -1, count = 0;
     if (st == DCX_PNP_OK) {
@@ -74,7 +79,7 @@ __global__ __launch_bounds__(kLanes) void dcx_pnp_ransac_select_kernel(
             st = DCX_PNP_DEGENERATE;
         } else {
             winner = bh;
-            const Frame f{rows + 4 * (long long)s0, xy ? xy + 2 * (long long)s0 : nullptr, n, rm1, square_len};
+            const Frame f = pl.frame(n, s0);
             double p[6], R[9];
 #pragma unroll
             for (int i = 0; i < 6; ++i) p[i] = poses[6 * ((long long)b * iterations + winner) + i];
@@ -107,7 +112,7 @@ __global__ __launch_bounds__(kLanes) void dcx_pnp_ransac_select_kernel(
         count = 0;
         // no pose, no inliers: every slot of the frame that lies in the pool (the lane that wrote a slot above rewrites it)
         if (inliers && n > 0 && s0 >= 0)
-            for (long long i = lane; i < n && s0 + i < pool; i += kLanes) inliers[s0 + i] = 0;
+            for (long long i = lane; i < n && s0 + i < pl.pool; i += kLanes) inliers[s0 + i] = 0;
     }
     if (lane == 0) {
         status[b] = st;
@@ -133,25 +138,22 @@ extern "C" int dcx_solve_pnp_ransac_pool(const int32_t* d_counts, const int32_t*
                                          double reproj_error, int min_inliers, unsigned seed, void* d_workspace,
                                          size_t workspace_bytes, int32_t* d_status, double* d_pose, int32_t* d_info,
                                          uint8_t* d_inliers, void* stream) {
-    if (!d_counts || !d_starts || !d_rows || !h_camera9 || !d_status || !d_pose || !d_info || !d_workspace) return DCX_E_ARG;
-    if (batch <= 0 || pool < 0 || col_count < 2 || row_count < 2) return DCX_E_ARG;
-    if ((long long)(col_count - 1) * (row_count - 1) > 0x7fffffffLL) return DCX_E_ARG;
+    CornerPool pl;
     PnpCamera cam;
-    if (!pnp_camera(h_camera9, h_dist, n_dist, cam)) return DCX_E_ARG;
-    if (!isfinite(square_len)) return DCX_E_ARG;
+    if (!corner_pool(d_counts, d_starts, d_rows, d_xy, batch, pool, col_count, row_count, square_len, pl)) return DCX_E_ARG;
+    if (!h_camera9 || !d_status || !d_pose || !d_info || !d_workspace || !pnp_camera(h_camera9, h_dist, n_dist, cam)) return DCX_E_ARG;
     if (iterations < 1 || iterations > kMaxIterations || !isfinite(reproj_error) || !(reproj_error > 0)) return DCX_E_ARG;
     if (workspace_bytes < dcx_solve_pnp_ransac_workspace_bytes(batch, pool, iterations) || ((uintptr_t)d_workspace & 7)) return DCX_E_ARG;
     const size_t hyp = (size_t)batch * (size_t)iterations;
     double* poses = (double*)d_workspace;
     int32_t* scores = (int32_t*)(poses + 6 * hyp);
     int32_t* idx = scores + hyp;
-    const int n_ids = (col_count - 1) * (row_count - 1), rm1 = row_count - 1;
     const double thr2 = reproj_error * reproj_error;
     hipLaunchKernelGGL(dcx_pnp_ransac_hypotheses_kernel, dim3((unsigned)batch, (unsigned)((iterations + kLanes - 1) / kLanes)),
-                       dim3(kLanes), 0, (hipStream_t)stream, d_counts, d_starts, d_rows, d_xy, pool, n_ids, rm1, square_len, cam,
-                       iterations, thr2, (uint32_t)seed, scores, poses);
-    hipLaunchKernelGGL(dcx_pnp_ransac_select_kernel, dim3((unsigned)batch), dim3(kLanes), 0, (hipStream_t)stream, d_counts, d_starts,
-                       d_rows, d_xy, pool, n_ids, rm1, square_len, cam, iterations, thr2, min_inliers, scores, poses, idx, d_status,
-                       d_pose, d_info, d_inliers);
+                       dim3(kLanes), 0, (hipStream_t)stream, pl.counts, pl.starts, pl.rows, pl.xy, pl.pool, pl.n_ids, pl.rm1, pl.square_len,
+                       cam, iterations, thr2, (uint32_t)seed, scores, poses);
+    hipLaunchKernelGGL(dcx_pnp_ransac_select_kernel, dim3((unsigned)batch), dim3(kLanes), 0, (hipStream_t)stream, pl.counts, pl.starts,
+                       pl.rows, pl.xy, pl.pool, pl.n_ids, pl.rm1, pl.square_len, cam, iterations, thr2, min_inliers, scores, poses,
+                       idx, d_status, d_pose, d_info, d_inliers);
     return (int)hipGetLastError();
 }

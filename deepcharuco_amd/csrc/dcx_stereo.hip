@@ -35,7 +35,9 @@
 // call synchronises its stream and cannot be captured in a graph.  Every sum has a fixed order (no atomics): two calls on the same
 // input give the same bits.  No device memory is allocated: the caller passes the workspace.
 // Shared with dcx_calib.hip through dcx_mat_dev.h: evaluate's LDS-staged loop (accumulate_rows), schur's body (schur_view), the
-// rig's polar_factor, block_tree, the workspace carver; overlap is dcx_pnp_dev.h's ranges_overlap.  The camera model, its
+// rig's polar_factor, block_tree, the workspace carver; overlap is dcx_pnp_dev.h's ranges_overlap, and each camera's pool is that
+// header's CornerPool (both carry the board), filled by its host check corner_pool(), with the optional mask beside it
+// (MaskedPool).  The camera model, its
 // derivative and the pose columns are dcx_camera_dev.h's (project, pose_basis, pose_columns); stereo_row() below adds the chain
 // through R_X and the rig columns.  The LM machinery is dcx_lm_dev.h's, shared with dcx_calib.hip: the state and the accept /
 // reject / forced / stop automaton (LmState<6>, lm_decide with STOP_FORCED = true: a step forced with a point behind a camera ends
@@ -66,18 +68,9 @@ using StereoState = LmState<6>;          // g = X; result = h_result
 constexpr int kState = 512;              // bytes reserved for StereoState
 static_assert(sizeof(StereoState) <= kState, "state");
 
-struct SPool {
-    const int32_t* counts;
-    const int32_t* starts;
-    const int32_t* rows;
-    const float* xy;                     // or null: the integer rows are the image points
-    const uint8_t* mask;                 // or null: every row is kept
-    int pool;
-};
-
-struct Board {
-    int n_ids, rm1;
-    double square_len;
+struct MaskedPool {                      // one camera's pool and the optional mask that rides beside it
+    CornerPool p;
+    const uint8_t* mask;                 // per slot, or null: every row is kept
 };
 
 struct Med {
@@ -121,17 +114,16 @@ size_t ws_layout(void* base, int batch, int pool0, int pool1, Ws* w) {
 bool sizes_ok(int batch, int pool0, int pool1) { return batch > 0 && pool0 >= 0 && pool1 >= 0; }
 
 // View (t, c) as the later kernels read it: its kept rows through the index list init_views left.
-__device__ __forceinline__ IndexedFrame view_frame(const SPool& pl, const Board& bd, const Ws& ws, int t, int c) {
-    const long long s0 = pl.starts[t];
-    const Frame f{pl.rows + 4 * s0, pl.xy ? pl.xy + 2 * s0 : nullptr, pl.counts[t], bd.rm1, bd.square_len};
-    return IndexedFrame{f, pl.mask ? (c ? ws.idx1 : ws.idx0) + s0 : ws.ident, ws.count[2 * t + c]};
+__device__ __forceinline__ IndexedFrame view_frame(const MaskedPool& pl, const Ws& ws, int t, int c) {
+    const long long s0 = pl.p.starts[t];
+    return IndexedFrame{pl.p.frame(pl.p.counts[t], s0), pl.mask ? (c ? ws.idx1 : ws.idx0) + s0 : ws.ident, ws.count[2 * t + c]};
 }
 
 // ---------------------------------------------------------------------------------------------------------------- init
 
 // One wave per view of a pool with a mask: does its slot range meet another view's?
-__global__ __launch_bounds__(kLanes) void stereo_overlap_kernel(SPool pl, int batch, int32_t* __restrict__ head) {
-    if (ranges_overlap(pl.counts, pl.starts, pl.pool, batch, blockIdx.x) && threadIdx.x == 0) head[kOverlap] = 1;
+__global__ __launch_bounds__(kLanes) void stereo_overlap_kernel(CornerPool pl, int batch, int32_t* __restrict__ head) {
+    if (ranges_overlap(pl, batch, blockIdx.x) && threadIdx.x == 0) head[kOverlap] = 1;
 }
 
 __global__ __launch_bounds__(256) void stereo_ident_kernel(int n, int32_t* __restrict__ ident) {
@@ -139,17 +131,19 @@ __global__ __launch_bounds__(256) void stereo_ident_kernel(int n, int32_t* __res
     if (i < n) ident[i] = i;
 }
 
-__global__ __launch_bounds__(kLanes) void stereo_init_views_kernel(SPool pl0, SPool pl1, PnpCamera cam0, PnpCamera cam1, Board bd,
+__global__ __launch_bounds__(kLanes) void stereo_init_views_kernel(MaskedPool pl0, MaskedPool pl1, PnpCamera cam0, PnpCamera cam1,
                                                                    int32_t* __restrict__ status, double* __restrict__ view_info,
                                                                    Ws ws) {
     const int t = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
-    const SPool pl = c ? pl1 : pl0;
-    const int n = pl.counts[t], s0 = pl.starts[t];
+    const MaskedPool pl = c ? pl1 : pl0;
+    const int n = pl.p.counts[t], s0 = pl.p.starts[t];
     int st = DCX_PNP_OK, kept = 0;
     const int32_t* idx = ws.ident;
+    // Not the header's frame_status(): with a mask this is another function (only the kept rows' ids are checked, and TOO_FEW is
+    // judged on the kept rows, after the pool cut).  Its first two rules mirror frame_status(); a change there is a change here.
     if (n <= 0) {
         st = DCX_PNP_TOO_FEW;
-    } else if (s0 < 0 || (long long)s0 + n > (long long)pl.pool) {
+    } else if (s0 < 0 || (long long)s0 + n > (long long)pl.p.pool) {
         st = DCX_PNP_TRUNCATED;               // (its slots are not read)
     } else {
         bool bad = false;
@@ -161,15 +155,15 @@ __global__ __launch_bounds__(kLanes) void stereo_init_views_kernel(SPool pl0, SP
                 const int at = append_kept(in, lane, kept);
                 if (in) {
                     list[at] = i;
-                    const int id = pl.rows[4 * ((long long)s0 + i) + 2];
-                    bad |= id < 0 || id >= bd.n_ids;
+                    const int id = pl.p.rows[4 * ((long long)s0 + i) + 2];
+                    bad |= id < 0 || id >= pl.p.n_ids;
                 }
             }
             idx = list;
         } else {
             for (int i = lane; i < n; i += kLanes) {
-                const int id = pl.rows[4 * ((long long)s0 + i) + 2];
-                bad |= id < 0 || id >= bd.n_ids;
+                const int id = pl.p.rows[4 * ((long long)s0 + i) + 2];
+                bad |= id < 0 || id >= pl.p.n_ids;
             }
             kept = n;
         }
@@ -180,8 +174,7 @@ __global__ __launch_bounds__(kLanes) void stereo_init_views_kernel(SPool pl0, SP
     double out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (st == DCX_PNP_OK) {
         const PnpCamera cam = c ? cam1 : cam0;
-        const Frame f{pl.rows + 4 * (long long)s0, pl.xy ? pl.xy + 2 * (long long)s0 : nullptr, n, bd.rm1, bd.square_len};
-        const IndexedFrame g{f, idx, kept};
+        const IndexedFrame g{pl.p.frame(n, s0), idx, kept};
         st = solve(g, cam, out);
     }
     if (lane == 0) {
@@ -339,7 +332,7 @@ __device__ __forceinline__ void accumulate_view(const IndexedFrame& f, const Pnp
     }, sj, ea, eb, acc, behind);
 }
 
-__global__ __launch_bounds__(kLanes) void stereo_evaluate_kernel(SPool pl0, SPool pl1, PnpCamera cam0, PnpCamera cam1, Board bd,
+__global__ __launch_bounds__(kLanes) void stereo_evaluate_kernel(MaskedPool pl0, MaskedPool pl1, PnpCamera cam0, PnpCamera cam1,
                                                                  Ws ws) {
     __shared__ double sj[2 * kLanes][kLdsStride];
     const int t = blockIdx.x, lane = threadIdx.x;
@@ -356,8 +349,8 @@ __global__ __launch_bounds__(kLanes) void stereo_evaluate_kernel(SPool pl0, SPoo
     lane_entries<13, 2>(lane, ea, eb);
     double acc[2] = {0, 0};
     bool behind = false;
-    accumulate_view<false>(view_frame(pl0, bd, ws, t, 0), cam0, B, sj, ea, eb, acc, behind);
-    accumulate_view<true>(view_frame(pl1, bd, ws, t, 1), cam1, B, sj, ea, eb, acc, behind);
+    accumulate_view<false>(view_frame(pl0, ws, t, 0), cam0, B, sj, ea, eb, acc, behind);
+    accumulate_view<true>(view_frame(pl1, ws, t, 1), cam1, B, sj, ea, eb, acc, behind);
     const bool inf = __any(behind);
     double* m = ws.m + (long long)t * kEntries;
 #pragma unroll
@@ -457,7 +450,7 @@ __device__ __forceinline__ double view_cost(const IndexedFrame& f, const PnpCame
     return c[0];
 }
 
-__global__ __launch_bounds__(kLanes) void stereo_trial_kernel(SPool pl0, SPool pl1, PnpCamera cam0, PnpCamera cam1, Board bd, Ws ws) {
+__global__ __launch_bounds__(kLanes) void stereo_trial_kernel(MaskedPool pl0, MaskedPool pl1, PnpCamera cam0, PnpCamera cam1, Ws ws) {
     const int t = blockIdx.x, lane = threadIdx.x;
     if (ws.st->code == kFinished || !ws.pair[t]) return;
     double x[6], p[6], dn, pn;
@@ -466,8 +459,8 @@ __global__ __launch_bounds__(kLanes) void stereo_trial_kernel(SPool pl0, SPool p
     for (int k = 0; k < 6; ++k) x[k] = ws.st->g_trial[k];
     PairBasis B;
     pair_basis<false>(x, p, B);
-    const double c0 = view_cost<false>(view_frame(pl0, bd, ws, t, 0), cam0, B);
-    const double c1 = view_cost<true>(view_frame(pl1, bd, ws, t, 1), cam1, B);
+    const double c0 = view_cost<false>(view_frame(pl0, ws, t, 0), cam0, B);
+    const double c1 = view_cost<true>(view_frame(pl1, ws, t, 1), cam1, B);
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) ws.trial_pose[(long long)t * 6 + k] = p[k];
@@ -517,30 +510,27 @@ extern "C" int dcx_stereo_calibrate_pool(const int32_t* d_counts0, const int32_t
                                          const double* h_camera9_1, const double* h_dist1, int n_dist1, void* d_workspace,
                                          size_t workspace_bytes, int32_t* d_view_status, double* d_pose, double* d_view_info,
                                          double* h_result, void* stream) {
-    if (!d_counts0 || !d_starts0 || !d_rows0 || !d_counts1 || !d_starts1 || !d_rows1 || !d_workspace || !d_view_status || !d_pose ||
-        !d_view_info || !h_result)
+    MaskedPool pl0{{}, d_mask0}, pl1{{}, d_mask1};
+    if (!corner_pool(d_counts0, d_starts0, d_rows0, d_xy0, batch, pool0, col_count, row_count, square_len, pl0.p) ||
+        !corner_pool(d_counts1, d_starts1, d_rows1, d_xy1, batch, pool1, col_count, row_count, square_len, pl1.p))
         return DCX_E_ARG;
-    if (!sizes_ok(batch, pool0, pool1) || col_count < 2 || row_count < 2) return DCX_E_ARG;
-    if ((long long)(col_count - 1) * (row_count - 1) > 0x7fffffffLL) return DCX_E_ARG;
-    if (!isfinite(square_len) || ((uintptr_t)d_workspace & 7)) return DCX_E_ARG;
+    if (!d_workspace || !d_view_status || !d_pose || !d_view_info || !h_result || ((uintptr_t)d_workspace & 7)) return DCX_E_ARG;
     PnpCamera cam0, cam1;
     if (!pnp_camera(h_camera9_0, h_dist0, n_dist0, cam0) || !pnp_camera(h_camera9_1, h_dist1, n_dist1, cam1)) return DCX_E_ARG;
     if (workspace_bytes < ws_layout(nullptr, batch, pool0, pool1, nullptr)) return DCX_E_WS;
     Ws ws;
     ws_layout(d_workspace, batch, pool0, pool1, &ws);
     hipStream_t s = (hipStream_t)stream;
-    const SPool pl0{d_counts0, d_starts0, d_rows0, d_xy0, d_mask0, pool0}, pl1{d_counts1, d_starts1, d_rows1, d_xy1, d_mask1, pool1};
-    const Board bd{(col_count - 1) * (row_count - 1), row_count - 1, square_len};
     const int chunks = chunks_of(batch);
     const dim3 stamps((unsigned)batch), views((unsigned)batch, 2), wave(kLanes), one(1), red(kRedThreads);
     const dim3 blocks((unsigned)chunks), per_lane((unsigned)((batch + kLanes - 1) / kLanes)), solve_threads(kSlices * kLanes);
 
     DCX_CHECK_HIP(hipMemsetAsync(ws.head, 0, kHeadWords * sizeof(int32_t), s));
-    if (d_mask0) hipLaunchKernelGGL(stereo_overlap_kernel, stamps, wave, 0, s, pl0, batch, ws.head);
-    if (d_mask1) hipLaunchKernelGGL(stereo_overlap_kernel, stamps, wave, 0, s, pl1, batch, ws.head);
+    if (d_mask0) hipLaunchKernelGGL(stereo_overlap_kernel, stamps, wave, 0, s, pl0.p, batch, ws.head);
+    if (d_mask1) hipLaunchKernelGGL(stereo_overlap_kernel, stamps, wave, 0, s, pl1.p, batch, ws.head);
     const int n_ident = !d_mask0 && !d_mask1 ? (pool0 > pool1 ? pool0 : pool1) : !d_mask0 ? pool0 : !d_mask1 ? pool1 : 0;
     if (n_ident > 0) hipLaunchKernelGGL(stereo_ident_kernel, dim3((unsigned)((n_ident + 255) / 256)), dim3(256), 0, s, n_ident, ws.ident);
-    hipLaunchKernelGGL(stereo_init_views_kernel, views, wave, 0, s, pl0, pl1, cam0, cam1, bd, d_view_status, d_view_info, ws);
+    hipLaunchKernelGGL(stereo_init_views_kernel, views, wave, 0, s, pl0, pl1, cam0, cam1, d_view_status, d_view_info, ws);
     hipLaunchKernelGGL(stereo_pairs_kernel, per_lane, wave, 0, s, batch, d_view_status, d_pose, ws);
     DCX_CHECK_HIP(hipGetLastError());
 
@@ -571,15 +561,15 @@ extern "C" int dcx_stereo_calibrate_pool(const int32_t* d_counts0, const int32_t
         }
     }
     hipLaunchKernelGGL(stereo_rig_kernel, one, wave, 0, s, med, npairs, batch, ws);
-    hipLaunchKernelGGL(stereo_evaluate_kernel, stamps, wave, 0, s, pl0, pl1, cam0, cam1, bd, ws);
+    hipLaunchKernelGGL(stereo_evaluate_kernel, stamps, wave, 0, s, pl0, pl1, cam0, cam1, ws);
     hipLaunchKernelGGL(stereo_decide_kernel, one, red, 0, s, batch, 1, d_pose, d_view_info, ws);
     DCX_CHECK_HIP(hipGetLastError());
     DCX_CHECK_HIP(lm_run(s, &ws.st->code, kJointMaxIter, [&](bool evaluate) {
-        if (evaluate) hipLaunchKernelGGL(stereo_evaluate_kernel, stamps, wave, 0, s, pl0, pl1, cam0, cam1, bd, ws);
+        if (evaluate) hipLaunchKernelGGL(stereo_evaluate_kernel, stamps, wave, 0, s, pl0, pl1, cam0, cam1, ws);
         hipLaunchKernelGGL(stereo_schur_kernel, stamps, wave, 0, s, ws);
         hipLaunchKernelGGL(stereo_reduce_kernel, blocks, wave, 0, s, batch, ws);
         hipLaunchKernelGGL(stereo_reduce_solve_kernel, one, solve_threads, 0, s, chunks, ws);
-        hipLaunchKernelGGL(stereo_trial_kernel, stamps, wave, 0, s, pl0, pl1, cam0, cam1, bd, ws);
+        hipLaunchKernelGGL(stereo_trial_kernel, stamps, wave, 0, s, pl0, pl1, cam0, cam1, ws);
         hipLaunchKernelGGL(stereo_decide_kernel, one, red, 0, s, batch, 0, d_pose, d_view_info, ws);
     }));
     DCX_CHECK_HIP(hipMemcpyAsync(h_result, ws.st->result, 16 * sizeof(double), hipMemcpyDeviceToHost, s));

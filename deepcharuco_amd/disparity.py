@@ -52,6 +52,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _dev
+
 CENSUS_W, CENSUS_H = 9, 7
 DISPARITY_SHIFT = 4                          # fractional bits of an output value
 NUM_DISPARITIES = (64, 128, 256)
@@ -352,29 +354,16 @@ def sgm_device(left, right, min_disparity: int = 0, num_disparities: int = 64, p
         raise ValueError("left and right must be non-empty, of one shape and on one device")
     dev = left.device
     single = left.ndim == 2
-    views = []
-    for t in (left, right):
-        x = t[None] if single else t
-        st = x.stride()
-        B, H, W = (int(s) for s in x.shape)
-        pitch, frame_stride = (int(st[1]) if H > 1 else W), (int(st[0]) if B > 1 else 0)
-        if (W > 1 and st[2] != 1) or pitch < W or frame_stride < 0:
-            raise ValueError("the pixels of a row must be contiguous, the pitch at least a row and the frame stride not negative")
-        views.append((x.data_ptr(), frame_stride, pitch))
+    (pl, fl, tl, B, H, W), (pr, fr, tr, _, _, _) = (_dev.u8_frames(t[None] if single else t, unit_axes_free=True) for t in (left, right))
     if W > MAX_DEVICE_WIDTH:
         raise ValueError(f"sgm_device takes frames up to {MAX_DEVICE_WIDTH} wide")
     shape = tuple(left.shape)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.int16, device=dev)
-    if out.device != dev or out.dtype != torch.int16 or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous int16 {shape} tensor on {dev}")
+    out = _dev.tensor(out, dev, torch.int16, shape, f"out must be a contiguous int16 {shape} tensor on {dev}")
     if workspace is None:
         workspace = torch.empty(sgm_workspace_bytes(B, H, W, D), dtype=torch.uint8, device=dev)
-    if workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.data_ptr() % 8:
-        raise ValueError(f"workspace must be a contiguous, 8-byte aligned uint8 tensor on {dev}")
+    _dev.workspace(workspace, dev, 0, f"workspace must be a contiguous, 8-byte aligned uint8 tensor on {dev}", aligned_u8=True)
     if workspace.numel() < sgm_workspace_bytes(1, H, W, D):
         raise ValueError("the workspace does not hold one frame: see sgm_workspace_bytes(1, height, width, num_disparities)")
-    (pl, fl, tl), (pr, fr, tr) = views
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().dcx_sgm_u8_paths(pl, fl, tl, pr, fr, tr, B, H, W, m, D, p1, p2, u, lr, paths, out.data_ptr(),
                                                workspace.data_ptr(), workspace.numel(), _lib.current_stream()), "dcx_sgm_u8_paths")
@@ -413,14 +402,10 @@ def filter_speckles_device(disp16, new_val: int, max_speckle_size: int, max_diff
     B = int(shape[0]) if disp16.ndim == 3 else 1
     H, W = int(shape[-2]), int(shape[-1])
     one = filter_speckles_workspace_bytes(1, H, W)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.int16, device=dev)
-    if out.device != dev or out.dtype != torch.int16 or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous int16 {shape} tensor on {dev}")
+    out = _dev.tensor(out, dev, torch.int16, shape, f"out must be a contiguous int16 {shape} tensor on {dev}")
     if workspace is None:
         workspace = torch.empty(B * one, dtype=torch.uint8, device=dev)
-    if workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.data_ptr() % 8:
-        raise ValueError(f"workspace must be a contiguous, 8-byte aligned uint8 tensor on {dev}")
+    _dev.workspace(workspace, dev, 0, f"workspace must be a contiguous, 8-byte aligned uint8 tensor on {dev}", aligned_u8=True)
     if workspace.numel() < one:
         raise ValueError("the workspace does not hold one frame: see filter_speckles_workspace_bytes(1, height, width)")
     with torch.cuda.device(dev):
@@ -446,10 +431,7 @@ def disparity_to_points_device(disp16, Q, min_disparity: int = 0, out=None):
         raise ValueError("min_disparity must be in [-2047, 2047]")
     dev = disp16.device
     shape = tuple(disp16.shape) + (3,)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
-    if out.device != dev or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous float32 {shape} tensor on {dev}")
+    out = _dev.tensor(out, dev, torch.float32, shape, f"out must be a contiguous float32 {shape} tensor on {dev}")
     B = int(disp16.shape[0]) if disp16.ndim == 3 else 1
     H, W = int(disp16.shape[-2]), int(disp16.shape[-1])
     q = (C.c_double * 16)(*Q.ravel().tolist())

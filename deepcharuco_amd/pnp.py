@@ -36,6 +36,9 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import _dev
+from ._dev import pool_ptrs as _pool_ptrs
+
 # per-frame status (include/deepcharuco_amd.h)
 PNP_OK, PNP_TOO_FEW, PNP_TRUNCATED, PNP_BAD_ID, PNP_DEGENERATE, PNP_NONFINITE = range(6)
 PNP_NO_CONSENSUS = 6            # RANSAC: the best hypothesis has fewer than max(min_inliers, 4) inliers
@@ -586,16 +589,6 @@ def _camera_args(camera_matrix, dist_coeffs):
     return (_ctypes.c_double * 9)(*K.ravel().tolist()), (_ctypes.c_double * 8)(*k.tolist()), n
 
 
-def _pool_ptrs(packed, batch, pool, refined):
-    """The corner pool's layout check -> the addresses of (counts, starts, rows, xy or None)."""
-    import torch
-    if packed.dtype != torch.int32 or not packed.is_contiguous() or packed.numel() < 2 * batch + (6 if refined else 4) * pool:
-        raise ValueError("packed must be a contiguous int32 corner pool of at least packed_len(batch, pool) words")
-    base = packed.data_ptr()
-    rows_p = base + 8 * batch
-    return base, base + 4 * batch, rows_p, rows_p + 16 * pool if refined else None
-
-
 def _launch(counts_p, starts_p, rows_p, xy_p, batch, pool, col_count, row_count, square_len, camera_matrix, dist_coeffs,
             status_p, pose_p):
     from . import _lib
@@ -614,13 +607,10 @@ def solve_pnp_pool(packed, batch: int, pool: int, refined: bool, col_count, row_
     import torch
     dev = packed.device
     ptrs = _pool_ptrs(packed, batch, pool, refined)
-    if out is None:
-        out = (torch.empty((batch,), dtype=torch.int32, device=dev),
-               torch.empty((batch, POSE_WORDS), dtype=torch.float64, device=dev))
-    st, pose = out
-    if (st.device != dev or st.dtype != torch.int32 or st.numel() != batch or not st.is_contiguous() or pose.device != dev
-            or pose.dtype != torch.float64 or pose.numel() != batch * POSE_WORDS or not pose.is_contiguous()):
-        raise ValueError(f"out must be (int32 [{batch}], float64 [{batch}, 8]) contiguous tensors on {dev}")
+    st, pose = (None, None) if out is None else out
+    msg = f"out must be (int32 [{batch}], float64 [{batch}, 8]) contiguous tensors on {dev}"
+    st = _dev.tensor(st, dev, torch.int32, (batch,), msg, "numel")
+    pose = _dev.tensor(pose, dev, torch.float64, (batch, POSE_WORDS), msg, "numel")
     with torch.cuda.device(dev):
         _launch(*ptrs, batch, pool, col_count, row_count, square_len, camera_matrix, dist_coeffs, st.data_ptr(), pose.data_ptr())
     return st, pose
@@ -710,20 +700,13 @@ def solve_pnp_ransac_pool(packed, batch: int, pool: int, refined: bool, col_coun
     iterations, reproj_error, min_inliers = _ransac_args(iterations, reproj_error, min_inliers)
     ptrs = _pool_ptrs(packed, batch, pool, refined)
     need = ransac_workspace_bytes(batch, pool, iterations)
-    if workspace is None:
-        workspace = torch.empty(((need + 7) // 8,), dtype=torch.float64, device=dev)
-    if workspace.device != dev or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need:
-        raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {dev}")
-    if out is None:
-        out = (torch.empty((batch,), dtype=torch.int32, device=dev),
-               torch.empty((batch, POSE_WORDS), dtype=torch.float64, device=dev),
-               torch.empty((batch, 2), dtype=torch.int32, device=dev),
-               torch.zeros((max(pool, 1),), dtype=torch.uint8, device=dev))
-    want = ((torch.int32, batch), (torch.float64, batch * POSE_WORDS), (torch.int32, 2 * batch), (torch.uint8, pool))
-    if len(out) != 4 or any(t.device != dev or t.dtype != dt or t.numel() < n or not t.is_contiguous() for t, (dt, n) in zip(out, want)):
-        raise ValueError(f"out must be (int32 [{batch}], float64 [{batch}, 8], int32 [{batch}, 2], uint8 [{pool}]) contiguous "
-                         f"tensors on {dev}")
-    st, pose, info, inl = out
+    workspace = _dev.workspace(workspace, dev, need, f"workspace must be a contiguous tensor of at least {need} bytes on {dev}")
+    msg = f"out must be (int32 [{batch}], float64 [{batch}, 8], int32 [{batch}, 2], uint8 [{pool}]) contiguous tensors on {dev}"
+    want = ((torch.int32, (batch,)), (torch.float64, (batch, POSE_WORDS)), (torch.int32, (batch, 2)), (torch.uint8, (pool,)))
+    if out is not None and len(out) != 4:
+        raise ValueError(msg)
+    st, pose, info, inl = (_dev.tensor(t, dev, dt, shape, msg, "min", zeros=dt is torch.uint8)
+                           for t, (dt, shape) in zip(out or (None,) * 4, want))
     cam, dist, n_dist = _camera_args(camera_matrix, dist_coeffs)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().dcx_solve_pnp_ransac_pool(

@@ -48,7 +48,7 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 
-from . import pnp
+from . import _dev, pnp
 from .pnp import _camera, _dist, _rodrigues, _rvec_of
 
 MAP_SENTINEL = int(np.iinfo(np.int32).min)     # both components of a map entry that is outside
@@ -382,10 +382,7 @@ def rectify_points_pool(packed, batch: int, pool: int, refined: bool, camera_mat
     rows_p, xy_p = pnp._pool_ptrs(packed, batch, pool, refined)[2:]
     cam, d, n = pnp._camera_args(camera_matrix, dist_coeffs)
     r, p = _rp_args(R, P, _camera(camera_matrix))
-    if out is None:
-        out = torch.empty((pool, 2), dtype=torch.float64, device=dev)
-    if out.device != dev or out.dtype != torch.float64 or out.numel() != 2 * pool or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous float64 [{pool}, 2] tensor on {dev}")
+    out = _dev.tensor(out, dev, torch.float64, (pool, 2), f"out must be a contiguous float64 [{pool}, 2] tensor on {dev}", "numel")
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().dcx_rectify_points_pool(rows_p, xy_p, pool, cam, d, n, r, p,
                                                       out.data_ptr() if pool else None, _lib.current_stream()),
@@ -413,10 +410,7 @@ def remap_device(frames, map_, border: int = 0, out=None):
     B, H, W = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
     if B < 1 or H < 1 or W < 1:
         raise ValueError("frames must not be empty")
-    st = x.stride()
-    pitch, frame_stride = int(st[1]), (int(st[0]) if B > 1 else 0)
-    if (colour and (st[3] != 1 or st[2] != 3)) or (not colour and st[2] != 1) or pitch < W * ch or frame_stride < 0:
-        raise ValueError("the pixels of a row must be contiguous, the pitch at least a row and the frame stride not negative")
+    frames_p, frame_stride, pitch = _dev.u8_frames(x, ch)[:3]
     if (map_.device != dev or map_.dtype != torch.int32 or map_.ndim != 3 or map_.shape[2] != 2 or not map_.is_contiguous()
             or map_.numel() == 0):
         raise ValueError(f"the map must be a contiguous int32 (out_h, out_w, 2) tensor on {dev}")
@@ -424,11 +418,8 @@ def remap_device(frames, map_, border: int = 0, out=None):
         raise ValueError("border must be in [0, 255]")
     oh, ow = int(map_.shape[0]), int(map_.shape[1])
     shape = ((B,) if not single else ()) + (oh, ow) + ((3,) if colour else ())
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=dev)
-    if out.device != dev or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous uint8 {shape} tensor on {dev}")
+    out = _dev.tensor(out, dev, torch.uint8, shape, f"out must be a contiguous uint8 {shape} tensor on {dev}")
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().dcx_remap_u8(x.data_ptr(), frame_stride, pitch, H, W, ch, map_.data_ptr(), oh, ow, B, int(border),
+        _lib.check(_lib.lib().dcx_remap_u8(frames_p, frame_stride, pitch, H, W, ch, map_.data_ptr(), oh, ow, B, int(border),
                                            out.data_ptr(), _lib.current_stream()), "dcx_remap_u8")
     return out

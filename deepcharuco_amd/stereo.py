@@ -47,7 +47,7 @@ from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from . import _lm, pnp
+from . import _dev, _lm, pnp
 from .pnp import (PNP_BAD_ID, PNP_OK, PNP_TOO_FEW, _bad_id_error, _camera, _dist, _jacobi, _pool_ptrs, _right_jacobian, _rodrigues,
                   _rvec_of, _skew, _solve)
 
@@ -401,16 +401,16 @@ def stereo_calibrate_pool(packed0, packed1, batch: int, pool0: int, pool1: int, 
     p0, p1 = _pool_ptrs(packed0, batch, pool0, refined), _pool_ptrs(packed1, batch, pool1, refined)
     mk = list(_mask_pair(masks))
     for c, pool in enumerate((pool0, pool1)):
-        m = mk[c]
-        if m is not None and (m.device != dev or m.dtype != torch.uint8 or m.numel() < pool or not m.is_contiguous()):
-            raise ValueError(f"mask {c} must be a contiguous uint8 tensor of at least {pool} values on {dev}")
+        if mk[c] is not None:
+            _dev.tensor(mk[c], dev, torch.uint8, (pool,), f"mask {c} must be a contiguous uint8 tensor of at least {pool} values on {dev}",
+                        "min")
     cam0, d0, n0 = pnp._camera_args(camera0, dist0)
     cam1, d1, n1 = pnp._camera_args(camera1, dist1)
     st = torch.empty((batch, 2), dtype=torch.int32, device=dev)
     pose = torch.empty((batch, pnp.POSE_WORDS), dtype=torch.float64, device=dev)
     info = torch.empty((batch, 2, 2), dtype=torch.float64, device=dev)
     nbytes = workspace_bytes(batch, pool0, pool1)
-    ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev)
+    ws = _dev.workspace(None, dev, nbytes)
     res = (_ctypes.c_double * RESULT_WORDS)()
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().dcx_stereo_calibrate_pool(

@@ -258,6 +258,24 @@ def test_pool_form_reads_two_hand_built_pools_in_place(dev, refined):
     _agree(d, h, f"hand-built pools refined={refined}")
 
 
+def test_pool_form_reports_views_outside_the_pool(dev):
+    """A view that starts before the pool and one cut by the pool's end are TRUNCATED and their slots are not read: everything
+    else is stereo_calibrate_host_full's answer with those two views empty (which the host calls TOO_FEW)."""
+    s = sx.scene(62, 2, "small", sx.BOARD_S, "A", "B", sigma=0.3, rows=12)
+    pool = 2 + 2 * (12 + 3)
+    p0, p1 = _hand_built_pool(s.kps0, pool, 1), _hand_built_pool(s.kps1, pool, 2)
+    p0[2 + 1] = -1                       # starts[1] of camera 0: a negative start
+    p1[2 + 1] = pool - 11                # starts[1] of camera 1: its 12 rows end one slot past the pool
+    d = stereo.stereo_calibrate_pool(torch.from_numpy(p0).to(dev), torch.from_numpy(p1).to(dev), 2, pool, pool, True, *s.board,
+                                     *sx.cam_args(s))
+    none = np.zeros((0, 3))
+    h = stereo.stereo_calibrate_host_full([s.kps0[0], none], [s.kps1[0], none], *s.board, *sx.cam_args(s))
+    assert h.view_status.tolist() == [[pnp.PNP_OK] * 2, [pnp.PNP_TOO_FEW] * 2]
+    assert d.view_status.tolist() == [[pnp.PNP_OK] * 2, [pnp.PNP_TRUNCATED] * 2]
+    assert d.pairs_used == 1
+    _agree(d._replace(view_status=h.view_status), h, "views outside the pool")
+
+
 def test_calibrate_then_stereo_on_the_device(dev):
     """calibrate_charuco_pool on each camera's pool, then stereo_calibrate_pool with the two solved models, from the same two
     device pools.  The rig is recovered to the accuracy the host chain (calibrate_camera_host_full twice, then

@@ -4,6 +4,8 @@ deepcharuco_amd/csrc (default dcx_conv_mfma.hip) to assembly with the Makefile's
 For a kernel that DIFFERS it also says whether every floating-point arithmetic opcode (the v_*_f64 and v_*_f32 instructions but
 compares and moves) is used as often on both sides: the same counts mean rescheduled, other counts mean recomputed.  The encoding
 suffixes (_e32, _e64, _dpp, _sdwa) are dropped, and v_fmac counts as v_fma: the same operation with the addend's register tied.
+A kernel whose parameter list changed has another mangled name: such kernels are paired by their unmangled function name
+(where that is unique on both sides) and compared like the rest.
 usage: python tools/isa_same.py REV [file.hip ...]      exit status 0 only if every kernel is identical"""
 import collections, os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
@@ -57,6 +59,15 @@ def kernels(s):
     return res
 
 
+def bare_name(sym):
+    """the function name inside an Itanium-mangled symbol (the last component of its nested name), or the symbol itself"""
+    parts, at = [], 3 if sym.startswith("_ZN") else 2 if sym.startswith("_Z") else len(sym)
+    while (m := re.compile(r"\d+").match(sym, at)):
+        at = m.end() + int(m.group())
+        parts.append(sym[m.end():at])
+    return parts[-1] if parts else sym
+
+
 def main():
     if len(sys.argv) < 2:
         sys.exit(__doc__)
@@ -77,6 +88,14 @@ def main():
                 fb = ex.submit(compile_s, ROOT, unit, os.path.join(tmp, "b.s"))
                 ka, kb = kernels(fa.result()), kernels(fb.result())
             print("%s: %d kernels at the base, %d here" % (unit, len(ka), len(kb)))
+            # a kernel with a new parameter list: this tree's symbol is compared under the base's, if the function name is unique
+            only_a, only_b = [k for k in ka if k not in kb], [k for k in kb if k not in ka]
+            for k in only_a:
+                here = [o for o in only_b if bare_name(o) == bare_name(k)]
+                if len(here) == 1 and sum(bare_name(o) == bare_name(k) for o in only_a) == 1:
+                    body, *rest = kb.pop(here[0])
+                    kb[k] = (body.replace(here[0], k), *rest)
+                    print("  paired     %s  <-  %s" % (k, here[0]))
             for sym in list(ka) + [k for k in kb if k not in ka]:
                 n_all += 1
                 if sym not in ka or sym not in kb:
