@@ -2,15 +2,17 @@
 with the tensors given nothing here allocates or synchronises (capture-safe entries rely on it).  The error texts are the callers'."""
 import math
 
+from .corner_pool import layout, ptrs
+
 
 def pool_ptrs(packed, batch, pool, refined):
     """The corner pool's layout check -> the addresses of (counts, starts, rows, xy or None)."""
     import torch
-    if packed.dtype != torch.int32 or not packed.is_contiguous() or packed.numel() < 2 * batch + (6 if refined else 4) * pool:
+    at = layout(batch, pool)
+    if packed.dtype != torch.int32 or not packed.is_contiguous() or packed.numel() < (at.conf if refined else at.xy):
         raise ValueError("packed must be a contiguous int32 corner pool of at least packed_len(batch, pool) words")
-    base = packed.data_ptr()
-    rows_p = base + 8 * batch
-    return base, base + 4 * batch, rows_p, rows_p + 16 * pool if refined else None
+    counts_p, starts_p, rows_p, xy_p, _ = ptrs(packed.data_ptr(), batch, pool)
+    return counts_p, starts_p, rows_p, xy_p if refined else None
 
 
 def tensor(t, dev, dtype, shape, message, rule="shape", zeros=False):

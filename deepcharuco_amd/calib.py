@@ -41,6 +41,7 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _dev, _lm, pnp
+from .corner_pool import _caller_order, _pool_rows, layout, pack_keypoints, views
 from .pnp import (PNP_BAD_ID, PNP_DEGENERATE, PNP_NO_CONSENSUS, PNP_NONFINITE, PNP_OK, PNP_TOO_FEW, _bad_id_error, _homography,
                   _project, _rodrigues, _solve)
 
@@ -405,7 +406,7 @@ def calibrate_camera_ransac_host_full(keypoints_list, col_count, row_count, squa
     orders, obj32, img32, masks = [None] * B, [None] * B, [None] * B, [None] * B
     margin = math.inf
     for b, kp in enumerate(keypoints_list):
-        kp, orders[b] = pnp._pool_rows(kp, pool_order)
+        kp, orders[b] = _pool_rows(kp, pool_order)
         n = offered[b] = kp.shape[0]
         masks[b] = np.zeros(n, bool)
         if n < 4:
@@ -530,7 +531,7 @@ def calibrate_charuco_device(keypoints_list: Sequence, col_count, row_count, squ
     _image_size(image_size)
     if len(keypoints_list) == 0:
         raise ValueError("no views")
-    packed, b, pool = pnp._pack(keypoints_list, dev)
+    packed, b, pool = pack_keypoints(keypoints_list, dev)
     with torch.cuda.device(dev):
         r = calibrate_charuco_pool(packed, b, pool, True, col_count, row_count, square_len, image_size)
     if (r.view_status == PNP_BAD_ID).any():
@@ -578,10 +579,11 @@ def calibrate_charuco_ransac_pool(packed, batch: int, pool: int, refined: bool, 
             min_inliers, rounds, int(seed) & 0xFFFFFFFF,
             ws.data_ptr(), nbytes, st.data_ptr(), pose.data_ptr(), info.data_ptr(), out_inliers.data_ptr(), res,
             _lib.current_stream()), "dcx_calibrate_ransac_pool")
-        st_h, pose_h, info_h, inl_h, head = (t.cpu().numpy() for t in (st, pose, info, out_inliers, packed[:2 * batch]))
+        st_h, pose_h, info_h, inl_h, head = (t.cpu().numpy() for t in (st, pose, info, out_inliers, packed[:layout(batch, pool).rows]))
     inl_b, solves = inl_h.astype(bool), int(res[15])
+    counts, starts = views(head, batch, pool)[:2]
     inliers = [inl_b[s0:s0 + n] if n > 0 and s0 >= 0 and s0 + n <= pool else np.zeros(max(n, 0), bool)
-               for n, s0 in zip(head[:batch].tolist(), head[batch:].tolist())]
+               for n, s0 in zip(counts.tolist(), starts.tolist())]
     return RobustCalibResult(*_common_fields(res, st_h, pose_h), inliers, info_h[:, 0].astype(np.int64),
                              info_h[:, 1].astype(np.int32), solves % 16, solves >= 16)
 
@@ -598,11 +600,11 @@ def calibrate_charuco_ransac_device(keypoints_list: Sequence, col_count, row_cou
     _calib_ransac_args(iterations, consensus_error, reproj_error, min_inliers, rounds)
     if len(keypoints_list) == 0:
         raise ValueError("no views")
-    packed, b, pool = pnp._pack(keypoints_list, dev)
+    packed, b, pool = pack_keypoints(keypoints_list, dev)
     with torch.cuda.device(dev):
         r = calibrate_charuco_ransac_pool(packed, b, pool, True, col_count, row_count, square_len, image_size, iterations,
                                           consensus_error, reproj_error, min_inliers, rounds, seed)
     if (r.view_status == PNP_BAD_ID).any():
         raise _bad_id_error(col_count, row_count)
-    # undo _pack's stable id sort
-    return r._replace(inliers=[mask[pnp._caller_order(kp)] for kp, mask in zip(keypoints_list, r.inliers)])
+    # undo pack_keypoints' stable id sort
+    return r._replace(inliers=[mask[_caller_order(kp)] for kp, mask in zip(keypoints_list, r.inliers)])

@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .corner_pool import frame_keypoints, views
 from .inference import DEFAULT_KMAX, PIXEL_FORMATS, infer_batch, launch_pipeline, packed_len, unpack_results
 from .models._handles import unwrap
 
@@ -156,10 +157,8 @@ class GraphedPipeline:
         self._in_np = self.pin_in.numpy()
         self._out_np = self.pin_out.numpy()
         self._dev_index = self.dev.index
-        # views of the packed result for the one-frame unpack (inference.unpack_results' layout: counts, starts, rows, xy)
-        o, b, pool = self._out_np, batch, self.pool
-        self._rows_np = o[2 * b:2 * b + 4 * pool].reshape(pool, 4)
-        self._xy_np = o[2 * b + 4 * pool:2 * b + 6 * pool].view(np.float32).reshape(pool, 2)
+        # views of the packed result for the one-frame unpack, built once
+        self._counts_np, self._starts_np, self._rows_np, self._xy_np, _ = views(self._out_np, batch, self.pool)
         with _cache_lock:
             _live.add(self)           # every pipeline that exists, cached or evicted-but-still-held (drop_graphs_of closes them all)
 
@@ -226,17 +225,12 @@ class GraphedPipeline:
                     graph.replay()
                     _sync_current_stream(self._dev_index)
             if self.batch == 1:
-                # unpack_results for ONE frame on pre-built views (same values, same dtypes, same stable sort by id: inference.py:68-69)
-                need, s0 = out_np[:2].tolist()
+                # unpack_results for ONE frame on the pre-built views
+                need, s0 = int(self._counts_np[0]), int(self._starts_np[0])
                 if need == 0:
                     res = [np.array([])]
                 elif s0 + need <= self.pool:
-                    rb = self._rows_np[s0:s0 + need]
-                    refined = self._ref is not None
-                    a = np.empty((need, 3), np.float64 if refined else np.int64)
-                    a[:, 0:2] = self._xy_np[s0:s0 + need] if refined else rb[:, 0:2]
-                    a[:, 2] = rb[:, 2]
-                    res = [a[rb[:, 2].argsort(kind="stable")]]
+                    res = [frame_keypoints(self._rows_np, self._xy_np, s0, need, self._ref is not None)[0]]
                 else:
                     res = [None]
             else:

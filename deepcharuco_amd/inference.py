@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .corner_pool import frame_keypoints, packed_len, ptrs, views
 from .imgproc import _opencv, bgr2gray
 from .models._handles import require_cuda, unwrap
 from .models.model_utils import extract_patches, pre_bgr_image, pred_to_keypoints
@@ -164,11 +165,6 @@ def get_xcd_weights(device="cuda") -> List[float]:
 PIXEL_FORMATS = {"gray": 0, "opencv4": 1, "legacy14": 2}       # DCX_PIX_GRAY8 / DCX_PIX_BGR8 / DCX_PIX_BGR8_LEGACY14
 
 
-def packed_len(batch: int, pool: int, conf: bool = False) -> int:
-    """int32 words of the packed result of a batch: counts[B] | starts[B] | rows[pool][4] | xy[pool][2] (| conf[pool][2])."""
-    return 2 * batch + (8 if conf else 6) * pool
-
-
 def launch_pipeline(det, ref, frames_ptr: int, b: int, h: int, w: int, bpp: int, pix: int, dust_bin_ids: int, pool: int,
                     ws: torch.Tensor, out_ptr: int, conf: bool = False, front: Optional[torch.Tensor] = None,
                     detector_done: Optional[int] = None) -> None:
@@ -177,9 +173,7 @@ def launch_pipeline(det, ref, frames_ptr: int, b: int, h: int, w: int, bpp: int,
     memory qualifies, which is how the bs=1 hipGraph reads the frame and writes the corner list without copy nodes.
     ``front``: a prefetch set that ``launch_front`` has filled for the same frames -- the path then starts at conv1b
     (``dcx_infer_batch_prefetched``); ``detector_done``: a hipEvent_t it records behind the detector's last convolution."""
-    counts_p, starts_p, rows_p = out_ptr, out_ptr + 4 * b, out_ptr + 8 * b
-    xy_p = rows_p + 16 * pool
-    conf_p = xy_p + 8 * pool
+    counts_p, starts_p, rows_p, xy_p, conf_p = ptrs(out_ptr, b, pool)
     head = (det.handle, ref.handle if ref else None, frames_ptr, h * w * bpp, w * bpp, pix, b, h, w, dust_bin_ids, pool,
             ws.data_ptr(), ws.numel())
     tail = (counts_p, starts_p, rows_p, xy_p if ref else None, conf_p if conf else None, _lib.current_stream())
@@ -230,6 +224,7 @@ def infer_batch_device(frames: torch.Tensor, dust_bin_ids: int, deepc, refinenet
         [.., + 2 pool)        xy[p]       refined (x, y) as float32 bit patterns (if refinenet)
         [.., + 2 pool)        conf[p]     (``conf=True``) soft-max probability of the winning loc / ids class, float32 bits
     Slots >= pool are dropped; ``sum(counts) > pool`` tells the caller to re-run with a larger pool.  Use ``unpack_results``.
+    ``corner_pool.py`` is the definition of these offsets (``layout`` / ``ptrs`` / ``views``); nothing else restates them.
 
     Scratch memory: by default a buffer owned by the detector object and keyed by the current HIP stream (so several
     streams / threads may drive one model pair concurrently, each on its own stream); pass ``ws`` (uint8 GPU tensor of
@@ -270,15 +265,10 @@ def unpack_results(packed: np.ndarray, batch: int, pool: int, refined: bool, con
     pool.  Also returns the raw counts; with ``conf=True`` a third value, the per-frame (K,2) float32 arrays
     [p_loc, p_ids] in the same (id-sorted) order."""
     packed = np.asarray(packed, dtype=np.int32)
-    counts = packed[:batch]
-    head = packed[:2 * batch].tolist()          # counts, starts as Python ints (the per-frame loop below is host-latency code: bs=1 calls)
-    rows = packed[2 * batch:2 * batch + 4 * pool].reshape(pool, 4)
-    xy = packed[2 * batch + 4 * pool:2 * batch + 6 * pool].view(np.float32).reshape(pool, 2)
-    cf = packed[2 * batch + 6 * pool:2 * batch + 8 * pool].view(np.float32).reshape(pool, 2) if conf else None
+    counts, starts, rows, xy, cf = views(packed, batch, pool)
     res: List[Optional[np.ndarray]] = []
     confs: List[Optional[np.ndarray]] = []
-    for b in range(batch):
-        k, s0 = head[b], head[batch + b]
+    for k, s0 in zip(counts.tolist(), starts.tolist()):          # Python ints (the per-frame loop is host-latency code: bs=1 calls)
         if k == 0:
             res.append(np.array([]))
             confs.append(np.zeros((0, 2), np.float32))
@@ -287,12 +277,8 @@ def unpack_results(packed: np.ndarray, batch: int, pool: int, refined: bool, con
             res.append(None)
             confs.append(None)
             continue
-        rb = rows[s0:s0 + k]
-        order = rb[:, 2].argsort(kind="stable")
-        a = np.empty((k, 3), np.float64 if refined else np.int64)
-        a[:, 0:2] = xy[s0:s0 + k] if refined else rb[:, 0:2]          # (the assignment widens: float32 -> float64 / int32 -> int64)
-        a[:, 2] = rb[:, 2]
-        res.append(a[order])
+        a, order = frame_keypoints(rows, xy, s0, k, refined)
+        res.append(a)
         if conf:
             confs.append(cf[s0:s0 + k][order].copy())
     if conf:

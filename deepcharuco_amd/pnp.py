@@ -32,12 +32,13 @@ from __future__ import annotations
 
 import ctypes as _ctypes
 import math
-from typing import List, Optional, Sequence, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 
 from . import _dev
 from ._dev import pool_ptrs as _pool_ptrs
+from .corner_pool import _caller_order, layout, pack_keypoints, views
 
 # per-frame status (include/deepcharuco_amd.h)
 PNP_OK, PNP_TOO_FEW, PNP_TRUNCATED, PNP_BAD_ID, PNP_DEGENERATE, PNP_NONFINITE = range(6)
@@ -86,19 +87,6 @@ def _dist(dist_coeffs) -> np.ndarray:
 
 def _bad_id_error(col_count, row_count):
     return IndexError(f"corner id outside [0, {(col_count - 1) * (row_count - 1)}) for a {col_count}x{row_count} board")
-
-
-def _pool_rows(keypoints, pool_order=False):
-    """A view's [x, y, id] rows -> (rows (n, 3), an empty array gives (0, 3); the indices that put them in the order the corner pool
-    holds them: id-sorted stably as ``_pack`` lays them, or as they stand with ``pool_order``)."""
-    kp = np.asarray(keypoints)
-    kp = kp.reshape(-1, 3) if kp.size else np.zeros((0, 3))
-    return kp, np.arange(kp.shape[0]) if pool_order else np.argsort(kp[:, 2], kind="stable")
-
-
-def _caller_order(keypoints):
-    """The inverse of ``_pool_rows``' id sort: ``mask[_caller_order(kp)]`` takes a mask by pool slot back to the caller's rows."""
-    return np.argsort(_pool_rows(keypoints)[1], kind="stable")
 
 
 def object_points(ids, col_count: int, row_count: int, square_len: float) -> np.ndarray:
@@ -512,7 +500,7 @@ def solve_pnp_ransac_host_full(keypoints, col_count, row_count, square_len, came
     (status, pose[8], inliers bool[N] in the caller's row order, winning hypothesis or -1).
 
     Rows are taken in the order the corner pool holds them, which is what the sampler's slots count: a keypoint list is laid
-    into a pool id-sorted (stable; ``_pack``), so that is the default; ``pool_order=True`` says the rows already stand as in the
+    into a pool id-sorted (stable; ``pack_keypoints``), so that is the default; ``pool_order=True`` says the rows already stand as in the
     pool (``infer_batch_device`` leaves a frame's corners in raster order) and takes them as they are.  Hypothesis h = the planar pose through four sampled rows
     (``_ransac_sample``, ``_homography4``, ``_pose_of_homography``; no LM); its score = the rows whose reprojection error
     through the full distortion model is <= reproj_error px (a row not in front of the camera is an outlier).  All ``iterations``
@@ -626,28 +614,6 @@ def unpack_poses(status, pose) -> List[tuple]:
     return [_as_cv2(int(s), p) for s, p in zip(status.tolist(), pose)]
 
 
-def _pack(keypoints_list: Sequence, dev):
-    """Host keypoint lists -> a device corner pool (counts | starts | rows | xy), frames id-sorted like the reference."""
-    import torch
-    b = len(keypoints_list)
-    kps = [_pool_rows(kp) for kp in keypoints_list]
-    counts = np.array([k.shape[0] for k, _ in kps], np.int64)
-    pool = max(int(counts.sum()), 1)
-    packed = np.zeros(2 * b + 6 * pool, np.int32)
-    starts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
-    packed[:b], packed[b:2 * b] = counts, starts
-    rows = packed[2 * b:2 * b + 4 * pool].reshape(pool, 4)
-    xy = packed[2 * b + 4 * pool:].view(np.float32).reshape(pool, 2)
-    for (kp, order), s in zip(kps, starts.tolist()):
-        if not kp.shape[0]:
-            continue
-        kp = kp[order]                                         # inference.py:68-69
-        ids = kp[:, 2].astype(np.int64)
-        rows[s:s + kp.shape[0], 2] = np.clip(ids, -1, np.iinfo(np.int32).max)
-        xy[s:s + kp.shape[0]] = kp[:, :2].astype(np.float32)
-    return torch.from_numpy(packed).to(dev), b, pool
-
-
 def solve_pnp_batch_device(keypoints_list, col_count, row_count, square_len, camera_matrix, dist_coeffs, device="cuda"):
     """``solve_pnp`` of every frame of a list of keypoint arrays in one kernel launch -> list of ``(ret, rvec, tvec)`` like
     ``solve_pnp_batch``'s (without OpenCV).  IndexError if any frame with >= 4 points carries an id outside the board."""
@@ -657,7 +623,7 @@ def solve_pnp_batch_device(keypoints_list, col_count, row_count, square_len, cam
     _camera_args(camera_matrix, dist_coeffs)                  # ValueError before anything is uploaded
     if len(keypoints_list) == 0:
         return []
-    packed, b, pool = _pack(keypoints_list, dev)
+    packed, b, pool = pack_keypoints(keypoints_list, dev)
     with torch.cuda.device(dev):
         st, pose = solve_pnp_pool(packed, b, pool, True, col_count, row_count, square_len, camera_matrix, dist_coeffs)
         st_h, pose_h = st.cpu().numpy(), pose.cpu().numpy()
@@ -745,16 +711,16 @@ def solve_pnp_ransac_batch_device(keypoints_list, col_count, row_count, square_l
     _ransac_args(iterations, reproj_error, min_inliers)
     if len(keypoints_list) == 0:
         return []
-    packed, b, pool = _pack(keypoints_list, dev)
+    packed, b, pool = pack_keypoints(keypoints_list, dev)
     with torch.cuda.device(dev):
         st, pose, info, inl = solve_pnp_ransac_pool(packed, b, pool, True, col_count, row_count, square_len, camera_matrix,
                                                     dist_coeffs, iterations, reproj_error, min_inliers, seed)
-        st, pose, info, inl, head = (t.cpu().numpy() for t in (st, pose, info, inl, packed[:2 * b]))
+        st, pose, info, inl, head = (t.cpu().numpy() for t in (st, pose, info, inl, packed[:layout(b, pool).rows]))
     if (st == PNP_BAD_ID).any():
         raise _bad_id_error(col_count, row_count)
     out = []
-    for i, (ret, rvec, tvec, mask) in enumerate(unpack_ransac(st, pose, inl, head[:b], head[b:])):
-        mask = mask[_caller_order(keypoints_list[i])]         # undo _pack's stable id sort
+    for i, (ret, rvec, tvec, mask) in enumerate(unpack_ransac(st, pose, inl, *views(head, b, pool)[:2])):
+        mask = mask[_caller_order(keypoints_list[i])]         # undo pack_keypoints' stable id sort
         out.append((int(st[i]), pose[i].copy(), mask, int(info[i, 1])) if full else (ret, rvec, tvec, mask))
     return out
 

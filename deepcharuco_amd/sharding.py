@@ -19,7 +19,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .inference import packed_len, unpack_results  # noqa: F401  (packed_len is re-exported: callers size buffers with it)
+from .corner_pool import layout, packed_len  # noqa: F401  (packed_len is re-exported: callers size buffers with it)
+from .inference import unpack_results
 from .models._handles import unwrap
 
 
@@ -38,9 +39,10 @@ def pad_packed(packed: torch.Tensor, batch: int, pool: int, batch_max: int) -> t
     if batch == batch_max:
         return packed
     out = torch.zeros(packed_len(batch_max, pool), dtype=packed.dtype, device=packed.device)
-    out[:batch] = packed[:batch]
-    out[batch_max:batch_max + batch] = packed[batch:2 * batch]
-    out[2 * batch_max:] = packed[2 * batch:]
+    src, dst = layout(batch, pool), layout(batch_max, pool)
+    out[dst.counts:dst.counts + batch] = packed[src.counts:src.starts]
+    out[dst.starts:dst.starts + batch] = packed[src.starts:src.rows]
+    out[dst.rows:] = packed[src.rows:]
     return out
 
 

@@ -48,6 +48,7 @@ from typing import NamedTuple, Optional, Sequence
 import numpy as np
 
 from . import _dev, _lm, pnp
+from .corner_pool import _pool_rows, pack_keypoints
 from .pnp import (PNP_BAD_ID, PNP_OK, PNP_TOO_FEW, _bad_id_error, _camera, _dist, _jacobi, _pool_ptrs, _right_jacobian, _rodrigues,
                   _rvec_of, _skew, _solve)
 
@@ -307,7 +308,7 @@ def stereo_calibrate_host_full(keypoints_list0, keypoints_list1, col_count, row_
     obj_l, img_l = [[None, None] for _ in range(B)], [[None, None] for _ in range(B)]
     for t in range(B):
         for c in range(2):
-            kp, order = pnp._pool_rows(lists[c][t], pool_order)
+            kp, order = _pool_rows(lists[c][t], pool_order)
             keep = np.ones(kp.shape[0], bool)
             if mk[c] is not None and mk[c][t] is not None:
                 keep = np.asarray(mk[c][t]).astype(bool).ravel()
@@ -430,12 +431,12 @@ def stereo_calibrate_pool(packed0, packed1, batch: int, pool0: int, pool1: int, 
 
 
 def _slot_mask(keypoints_list, masks, pool, dev):
-    """Per-view masks in the caller's row order -> a uint8 device tensor by slot of the pool ``pnp._pack`` lays (stable id sort)."""
+    """Per-view masks in the caller's row order -> a uint8 device tensor by slot of the pool ``pack_keypoints`` lays (stable id sort)."""
     import torch
     out = np.ones(pool, np.uint8)
     s = 0
     for t, kp in enumerate(keypoints_list):
-        kp, order = pnp._pool_rows(kp)
+        kp, order = _pool_rows(kp)
         n = kp.shape[0]
         if masks[t] is not None:
             m = np.asarray(masks[t]).astype(bool).ravel()
@@ -461,8 +462,8 @@ def stereo_calibrate_device(keypoints_list0: Sequence, keypoints_list1: Sequence
     if len(keypoints_list0) == 0:
         raise ValueError("no views")
     mk = _mask_pair(masks)
-    packed0, b, pool0 = pnp._pack(keypoints_list0, dev)
-    packed1, _, pool1 = pnp._pack(keypoints_list1, dev)
+    packed0, b, pool0 = pack_keypoints(keypoints_list0, dev)
+    packed1, _, pool1 = pack_keypoints(keypoints_list1, dev)
     dm = [None if m is None else _slot_mask(kl, m, pool, dev)
           for kl, m, pool in ((keypoints_list0, mk[0], pool0), (keypoints_list1, mk[1], pool1))]
     with torch.cuda.device(dev):

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .corner_pool import views
 from .inference import (DEFAULT_KMAX, PIXEL_FORMATS, infer_batch, infer_batch_device, launch_front, launch_pipeline, packed_len, pipeline_workspace, solve_pnp_submit,
                         unpack_results)
 from .models._handles import unwrap
@@ -109,10 +110,9 @@ class FrameStream:
                 return ticket, res, solve_pnp_batch_device(res, device=self.dev, **self.pnp)
         if self.pnp_ransac is not None:
             st, pose, _, mask = self.pin_pnp[slot]
-            head = self.pin_out[slot].numpy()        # the masks follow res: unpack_results' id-sorted rows
-            ids = head[2 * self.batch:2 * self.batch + 4 * self.pool].reshape(self.pool, 4)[:, 2]
-            return ticket, res, unpack_ransac(st.numpy()[:n], pose.numpy()[:n], mask.numpy(), head[:self.batch],
-                                              head[self.batch:2 * self.batch], ids)
+            counts, starts, rows, _, _ = views(self.pin_out[slot].numpy(), self.batch, self.pool)
+            # the masks follow res: unpack_results' id-sorted rows
+            return ticket, res, unpack_ransac(st.numpy()[:n], pose.numpy()[:n], mask.numpy(), counts, starts, rows[:, 2])
         if self.pnp_device:
             st, pose = self.pin_pnp[slot]
             return ticket, res, unpack_poses(st.numpy()[:n], pose.numpy()[:n])

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import camera_exact as cx
+import pool_cases
 from conftest import GoldenCase
 from deepcharuco_amd import calib, pnp
 from test_calib_host import BOARD, DIST_TRUE, K_TRUE, SIZE, make_views
@@ -171,20 +172,7 @@ def _hand_built_pool(seed):
     order = list(np.random.default_rng(seed).permutation(B - 1)) + [B - 1]
     gap = 5
     pool = sum(len(k) + gap for k in kps) - gap - 4
-    packed = np.zeros(2 * B + 6 * pool, np.int32)
-    rows = packed[2 * B:2 * B + 4 * pool].reshape(pool, 4)
-    xy = packed[2 * B + 4 * pool:].view(np.float32).reshape(pool, 2)
-    rows[:] = -9
-    s = 0
-    for b in order:
-        kp = kps[b]
-        packed[b], packed[B + b] = len(kp), s
-        k = min(len(kp), pool - s)
-        if k > 0:
-            rows[s:s + k, 0:2] = np.rint(kp[:k, :2])
-            rows[s:s + k, 2] = kp[:k, 2]
-            xy[s:s + k] = kp[:k, :2]
-        s += len(kp) + gap
+    packed, _ = pool_cases.lay_frames(kps, pool, order, gap=gap, filler=-9)
     expect = [pnp.PNP_OK] * B
     expect[2] = expect[4] = pnp.PNP_TOO_FEW
     expect[6], expect[8], expect[B - 1] = pnp.PNP_BAD_ID, pnp.PNP_DEGENERATE, pnp.PNP_TRUNCATED

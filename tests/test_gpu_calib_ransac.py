@@ -14,8 +14,9 @@ import numpy as np
 import pytest
 import torch
 
+import pool_cases
 from conftest import GoldenCase
-from deepcharuco_amd import _lib, calib, pnp
+from deepcharuco_amd import _lib, calib, corner_pool, pnp
 from test_calib_host import BOARD, DIST_TRUE, K_TRUE, SIZE, make_views
 from test_calib_ransac_host import SMALL_SEED, every_status_batch, keypoints, planted_views, small_view_batch
 from test_gpu_calib import _check, _gaps
@@ -90,24 +91,9 @@ def hand_built_pool(refined):
     order = list(np.random.default_rng(5).permutation(B - 1)) + [B - 1]
     gap = 3
     pool = sum(len(v) + gap for v in views) - gap - 4
-    packed = np.zeros(2 * B + 6 * pool, np.int32)
-    rows = packed[2 * B:2 * B + 4 * pool].reshape(pool, 4)
-    xy = packed[2 * B + 4 * pool:].view(np.float32).reshape(pool, 2)
-    rows[:] = -9
-    owned = np.zeros(pool, bool)
-    s = 0
-    for b in order:
-        v = views[b]
-        packed[b], packed[B + b] = len(v), s
-        k = min(len(v), pool - s)
-        if k > 0:
-            rows[s:s + k, 0:2] = np.rint(v[:k, :2])
-            rows[s:s + k, 2] = v[:k, 2]
-            xy[s:s + k] = v[:k, :2]
-            owned[s:s + k] = True
-        s += len(v) + gap
+    packed, owned = pool_cases.lay_frames(views, pool, order, gap=gap, filler=-9)
     if not refined:
-        xy[:] = np.nan                                                   # not read
+        corner_pool.views(packed, B, pool)[3][:] = np.nan                # xy: not read
     return views, packed, B, pool, owned
 
 
@@ -129,7 +115,7 @@ def test_pool_hand_built_every_status(dev, refined):
     # the continuous outputs: the plain device solve over the rows the host kept, every view in its place (an empty view where
     # one was left out), gives the same bits: the consensus steps add nothing to the solve but the choice of rows
     kept = [v[m] if st == pnp.PNP_OK else v[:0] for v, m, st in zip(views[:-1], h.inliers, h.view_status)] + [views[-1][:0]]
-    p = calib.calibrate_charuco_pool(*pnp._pack(kept, dev), True, *BOARD, SIZE)
+    p = calib.calibrate_charuco_pool(*corner_pool.pack_keypoints(kept, dev), True, *BOARD, SIZE)
     assert p.status == calib.CALIB_OK and p.view_points.tolist() == d.view_inliers.tolist()
     _bits_equal([d.rms, d.camera_matrix, d.dist_coeffs, d.rvecs, d.tvecs, d.view_rms, d.iterations, d.attempts, d.views_used,
                  d.points_used], [p.rms, p.camera_matrix, p.dist_coeffs, p.rvecs, p.tvecs, p.view_rms, p.iterations, p.attempts,
@@ -205,7 +191,7 @@ def test_all_true_masks_give_the_plain_device_solve(dev):
     """Clean views: every mask is all true, one solve, and the filtered pool is the pool: calibrate_charuco_pool's bits."""
     _, imgs, ids_l, _ = make_views(204, 48)
     kps = keypoints(imgs, ids_l)
-    packed, b, pool = pnp._pack(kps, dev)
+    packed, b, pool = corner_pool.pack_keypoints(kps, dev)
     r = calib.calibrate_charuco_ransac_pool(packed, b, pool, True, *BOARD, SIZE)
     p = calib.calibrate_charuco_pool(packed, b, pool, True, *BOARD, SIZE)
     assert p.status == calib.CALIB_OK and r.solves == 1 and r.stable and all(m.all() for m in r.inliers)
@@ -250,7 +236,7 @@ def test_device_errors(dev):
     r = calib.calibrate_charuco_ransac_device([k[:3] for k in kps], *BOARD, SIZE)
     assert r.status == calib.CALIB_NO_VIEWS and (r.view_status == pnp.PNP_TOO_FEW).all() and r.rms == 0.0 and r.solves == 1
     # two views that share slots are refused before anything is written
-    packed, b, pool = pnp._pack(kps, dev)
+    packed, b, pool = corner_pool.pack_keypoints(kps, dev)
     packed[b + 1] -= 2                                                   # view 1 starts inside view 0
     inl = torch.full((pool,), 7, dtype=torch.uint8, device=dev)
     with pytest.raises(_lib.DcxError) as e:

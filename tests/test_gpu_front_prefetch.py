@@ -12,6 +12,7 @@ import torch
 
 from deepcharuco_amd import weights as W
 from deepcharuco_amd import workload as WL
+from deepcharuco_amd.corner_pool import views
 
 pytestmark = pytest.mark.gpu
 
@@ -29,20 +30,19 @@ def _canon(packed, b, pool, refined, conf=False):
     """counts and, per frame, the words of its slots of rows / xy / conf, as written (raster order).  Also checks that the
     frames' slot ranges tile [0, sum(counts)) -- the part of starts[] that is specified."""
     packed = np.asarray(packed)
-    counts, starts = packed[:b].copy(), packed[b:2 * b]
+    counts, starts, rows, xy, cf = views(packed, b, pool)
+    counts = counts.copy()
     assert int(counts.sum()) <= pool
     spans = sorted((int(s), int(c)) for s, c in zip(starts, counts) if c)
     at = 0
     for s, c in spans:
         assert s == at
         at += c
-    rows = packed[2 * b:2 * b + 4 * pool].reshape(pool, 4)
     parts = [rows]
     if refined:
-        parts.append(packed[2 * b + 4 * pool:2 * b + 6 * pool].reshape(pool, 2))
+        parts.append(xy.view(np.int32))
     if conf:
-        lo = 2 * b + (6 if refined else 4) * pool
-        parts.append(packed[lo:lo + 2 * pool].reshape(pool, 2))
+        parts.append(cf.view(np.int32))
     return counts, [[p[s:s + c].copy() for p in parts] for s, c in zip(starts, counts)]
 
 

@@ -12,8 +12,9 @@ import numpy as np
 import pytest
 import torch
 
+import pool_cases
 from conftest import GoldenCase
-from deepcharuco_amd import pnp
+from deepcharuco_amd import corner_pool, pnp
 from test_pnp_host import BOARD, DIST5, K, make_frame
 
 pytestmark = pytest.mark.gpu
@@ -75,7 +76,7 @@ def test_batch_device_matches_host_64_frames(dev):
         frames.append(make_frame(rng, ids=ids, sigma=0.3 if i % 2 else 0.0)[0])
     got = pnp.solve_pnp_batch_device(frames, *BOARD, K, DIST5)
     assert len(got) == 64
-    packed, b, pool = pnp._pack(frames, dev)
+    packed, b, pool = corner_pool.pack_keypoints(frames, dev)
     st, pose = pnp.solve_pnp_pool(packed, b, pool, True, *BOARD, K, DIST5)
     st, pose = st.cpu().numpy(), pose.cpu().numpy()
     for b, (ret, rvec, tvec) in enumerate(got):         # the list form is the pool form, unpacked
@@ -133,19 +134,7 @@ def test_pool_hand_built_every_status(dev):
     order.append(4)
     B = len(frames)
     pool = sum(len(f) for f in frames) - 3    # frame 4 (last in the pool) does not fit
-    packed = np.zeros(2 * B + 6 * pool, np.int32)
-    rows = packed[2 * B:2 * B + 4 * pool].reshape(pool, 4)
-    xy = packed[2 * B + 4 * pool:].view(np.float32).reshape(pool, 2)
-    s = 0
-    for b in order:
-        kp = frames[b]
-        packed[b], packed[B + b] = len(kp), s
-        k = min(len(kp), pool - s)
-        rows[s:s + k, 0:2] = np.rint(kp[:k, :2])
-        rows[s:s + k, 2] = kp[:k, 2]
-        rows[s:s + k, 3] = -7
-        xy[s:s + k] = kp[:k, :2]
-        s += len(kp)
+    packed, _ = pool_cases.lay_frames(frames, pool, order, cell=-7)
     d = torch.from_numpy(packed).to(dev)
     expect = [pnp.PNP_OK, pnp.PNP_OK, pnp.PNP_TOO_FEW, pnp.PNP_TOO_FEW, pnp.PNP_TRUNCATED, pnp.PNP_BAD_ID,
               pnp.PNP_DEGENERATE, pnp.PNP_OK]

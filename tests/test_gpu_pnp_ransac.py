@@ -13,8 +13,9 @@ import numpy as np
 import pytest
 import torch
 
+import pool_cases
 from conftest import GoldenCase
-from deepcharuco_amd import pnp
+from deepcharuco_amd import corner_pool, pnp
 from test_gpu_pnp import _agree, _board_frame, _models
 from test_pnp_host import BOARD, DIST5, K, make_frame
 from test_pnp_ransac_host import REPROJ, SAMPLER_SEED, planted_frames
@@ -134,19 +135,7 @@ def hand_built_pool():
     order = [7, 8, 1, 0, 6, 3, 5, 2, 4]       # pool order; frame 4 goes last and is cut by the pool size
     B = len(frames)
     pool = sum(len(f) for f in frames) - 3
-    packed = np.zeros(2 * B + 6 * pool, np.int32)
-    rows = packed[2 * B:2 * B + 4 * pool].reshape(pool, 4)
-    xy = packed[2 * B + 4 * pool:].view(np.float32).reshape(pool, 2)
-    s = 0
-    for b in order:
-        kp = frames[b]
-        packed[b], packed[B + b] = len(kp), s
-        k = min(len(kp), pool - s)
-        rows[s:s + k, 0:2] = np.rint(kp[:k, :2])
-        rows[s:s + k, 2] = kp[:k, 2]
-        rows[s:s + k, 3] = -7
-        xy[s:s + k] = kp[:k, :2]
-        s += len(kp)
+    packed, _ = pool_cases.lay_frames(frames, pool, order, cell=-7)
     return board, frames, expect, packed, B, pool
 
 
@@ -200,9 +189,8 @@ def _pipeline(case, dev, frames):
 def _pool_frames(head, batch, pool):
     """The frames of a refined host pool as [x, y, id] rows in SLOT order (infer_batch_device: raster order), which is the
     order the hypotheses' slots count; unpack_results returns the same rows id-sorted."""
-    rows = head[2 * batch:2 * batch + 4 * pool].reshape(pool, 4)
-    xy = head[2 * batch + 4 * pool:2 * batch + 6 * pool].view(np.float32).reshape(pool, 2)
-    return [np.c_[xy[s:s + n].astype(np.float64), rows[s:s + n, 2]] for n, s in zip(head[:batch], head[batch:2 * batch])]
+    counts, starts, rows, xy, _ = corner_pool.views(head, batch, pool)
+    return [np.c_[xy[s:s + n].astype(np.float64), rows[s:s + n, 2]] for n, s in zip(counts, starts)]
 
 
 @pytest.mark.parametrize("name", ["board_240x320", "diverse_ids_240x320"])
@@ -220,7 +208,7 @@ def test_end_to_end_from_the_corner_pool(dev, name):
     head = packed.cpu().numpy()
     res, counts = unpack_results(head, len(frames), pool, True)
     slots = _pool_frames(head, len(frames), pool)
-    starts = head[len(frames):2 * len(frames)]
+    starts = corner_pool.views(head, len(frames), pool)[1]
     tally = [0, 0, 0]
     for thr, out in zip((8.0, 3.0), outs):
         st, pose, info, inl = (t.cpu().numpy() for t in out)
@@ -241,7 +229,7 @@ def test_two_runs_and_graph_replay_bit_identical(dev):
     packed, pool, cam = _pipeline(case, dev, frames)
     B = len(frames)
     # two pools in one: the golden frames' own, and the planted frames (poses come out, so the refit is replayed too)
-    planted, pb, ppool = pnp._pack([p[0] for p in planted_frames(8)], dev)
+    planted, pb, ppool = corner_pool.pack_keypoints([p[0] for p in planted_frames(8)], dev)
     for pk, b, pl, board, cm in ((packed, B, pool, (5, 5, 0.01), cam), (planted, pb, ppool, BOARD, K)):
         args = (pk, b, pl, True, *board, cm, DIST5)
         eager = pnp.solve_pnp_ransac_pool(*args, **RANSAC)
@@ -296,9 +284,9 @@ def test_frame_stream_ransac_stage(dev):
         packed = infer_batch_device(d, case.n_ids, dc, rn, pool=4 * 64)
         st, pose, info, inl = (t.cpu().numpy() for t in pnp.solve_pnp_ransac_pool(packed, 4, 4 * 64, True, **cfg, **ransac))
         head = packed.cpu().numpy()
-        ids = head[8:8 + 4 * 256].reshape(256, 4)[:, 2]
-        want += pnp.unpack_ransac(st, pose, inl, head[:4], head[4:8], ids)[:len(fr)]       # masks in unpack_results' row order
-        slot_order = pnp.unpack_ransac(st, pose, inl, head[:4], head[4:8])
+        counts, starts, rows, _, _ = corner_pool.views(head, 4, 256)
+        want += pnp.unpack_ransac(st, pose, inl, counts, starts, rows[:, 2])[:len(fr)]     # masks in unpack_results' row order
+        slot_order = pnp.unpack_ransac(st, pose, inl, counts, starts)
         for b, kp in enumerate(_pool_frames(head, 4, 256)[:len(fr)]):
             assert np.array_equal(slot_order[b][3][np.argsort(kp[:, 2], kind="stable")], want[b - len(fr)][3])
     n_ok = 0
@@ -323,7 +311,7 @@ def test_c_abi_refuses_bad_arguments(dev):
     E_ARG = -1
     assert L.dcx_error_string(E_ARG)                                     # the code the header calls DCX_E_ARG
     B, pool = 2, 32
-    packed = torch.zeros((2 * B + 6 * pool,), dtype=torch.int32, device=dev)
+    packed = torch.zeros((corner_pool.packed_len(B, pool),), dtype=torch.int32, device=dev)
     st = torch.full((B,), -5, dtype=torch.int32, device=dev)
     pose = torch.full((B, 8), -5.0, dtype=torch.float64, device=dev)
     info = torch.full((B, 2), -5, dtype=torch.int32, device=dev)
@@ -335,8 +323,8 @@ def test_c_abi_refuses_bad_arguments(dev):
     ws = torch.zeros((need // 8,), dtype=torch.float64, device=dev)
     cam = (ctypes.c_double * 9)(*K.ravel().tolist())
     dist = (ctypes.c_double * 8)(*DIST5.tolist(), 0, 0, 0)
-    base = packed.data_ptr()
-    good = dict(counts=base, starts=base + 4 * B, rows=base + 8 * B, xy=base + 8 * B + 16 * pool, batch=B, pool=pool, col=5, row=5,
+    counts_p, starts_p, rows_p, xy_p, _ = corner_pool.ptrs(packed.data_ptr(), B, pool)
+    good = dict(counts=counts_p, starts=starts_p, rows=rows_p, xy=xy_p, batch=B, pool=pool, col=5, row=5,
                 sq=0.01, cam=cam, dist=dist, n_dist=5, iterations=100, thr=8.0, min_inliers=4, seed=0, ws=ws.data_ptr(), ws_bytes=need,
                 st=st.data_ptr(), pose=pose.data_ptr(), info=info.data_ptr(), inl=inl.data_ptr())
 

@@ -13,7 +13,8 @@ import pytest
 import torch
 
 import camera_exact as A
-from deepcharuco_amd import calib, pnp
+import pool_cases
+from deepcharuco_amd import calib, corner_pool, pnp
 from test_gpu_calib import ABS_DIST, REL_K, REL_POSE, REL_RMS, _gaps
 from test_gpu_pnp import REL, _agree
 from test_gpu_pnp_ransac import MARGIN, _check_frame
@@ -106,7 +107,7 @@ def test_plain_solver_on_the_grid(dev):
         for model, dist in A.MODELS.items():
             idx = [i for i, f in enumerate(G) if f.board == board and f.model == model]
             frames = [G[i].kp for i in idx]
-            packed, b, pool = pnp._pack(frames, dev)
+            packed, b, pool = corner_pool.pack_keypoints(frames, dev)
             st, pose = pnp.solve_pnp_pool(packed, b, pool, True, *board, A.K_EDGE, dist)
             st, pose = st.cpu().numpy(), pose.cpu().numpy()
             got = pnp.solve_pnp_batch_device(frames, *board, A.K_EDGE, dist)        # the list form is the pool form, unpacked
@@ -225,18 +226,7 @@ def hand_built_pool(board=POOL_BOARD):
     order = list(np.random.default_rng(5).permutation(B))
     gap = 3
     pool = sum(len(k) + gap for k in kps)
-    packed = np.zeros(2 * B + 6 * pool, np.int32)
-    rows = packed[2 * B:2 * B + 4 * pool].reshape(pool, 4)
-    xy = packed[2 * B + 4 * pool:].view(np.float32).reshape(pool, 2)
-    rows[:] = -9
-    s = 0
-    for b in order:
-        kp = kps[b]
-        packed[b], packed[B + b] = len(kp), s
-        rows[s:s + len(kp), 0:2] = np.rint(kp[:, :2])
-        rows[s:s + len(kp), 2] = kp[:, 2]
-        xy[s:s + len(kp)] = kp[:, :2]
-        s += len(kp) + gap
+    packed, _ = pool_cases.lay_frames(kps, pool, order, gap=gap, filler=-9)
     expect = [pnp.PNP_OK] * 16 + [pnp.PNP_BAD_ID, pnp.PNP_TOO_FEW]
     return kps, poses, packed, B, pool, expect
 

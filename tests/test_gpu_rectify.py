@@ -10,7 +10,7 @@ import camera_exact as cx
 import rectify_exact as rx
 import stereo_exact as sx
 from camera_exact import f64
-from deepcharuco_amd import pnp, rectify as rc, stereo, weights
+from deepcharuco_amd import corner_pool, rectify as rc, stereo, weights
 
 pytestmark = pytest.mark.gpu
 
@@ -183,13 +183,13 @@ def test_remap_refuses(dev):
 def _pool(dev, xy, rows_xy=None):
     """A one-frame corner pool (counts | starts | rows | xy) of len(xy) slots."""
     n = len(xy)
-    packed = np.zeros(2 + 6 * n, np.int32)
-    packed[0] = n
-    rows = packed[2:2 + 4 * n].reshape(n, 4)
+    packed = np.zeros(corner_pool.packed_len(1, n), np.int32)
+    counts, _, rows, xy_v, _ = corner_pool.views(packed, 1, n)
+    counts[0] = n
     rows[:, 2] = np.arange(n) % 60
     if rows_xy is not None:
         rows[:, :2] = rows_xy
-    packed[2 + 4 * n:].view(np.float32)[:] = np.asarray(xy, np.float32).ravel()
+    xy_v[:] = np.asarray(xy, np.float32).reshape(n, 2)
     return torch.from_numpy(packed).to(dev)
 
 
@@ -265,7 +265,7 @@ def test_chain_from_pools_to_epipolar_rows(dev, kind, c0, c1):
     rectify_points_host) gives on the same scene."""
     s = rx.scene(kind, c0, c1)
     cams = sx.cam_args(s)
-    (p0, b, pool0), (p1, _, pool1) = pnp._pack(s.kps0, dev), pnp._pack(s.kps1, dev)
+    (p0, b, pool0), (p1, _, pool1) = corner_pool.pack_keypoints(s.kps0, dev), corner_pool.pack_keypoints(s.kps1, dev)
     est = stereo.stereo_calibrate_pool(p0, p1, b, pool0, pool1, True, *s.board, *cams)
     assert est.status == stereo.STEREO_OK and est.pairs_used == b
     r = rc.stereo_rectify_host(*cams, rx.SIZE, est.R, est.T)

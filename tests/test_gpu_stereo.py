@@ -16,8 +16,9 @@ import pytest
 import torch
 
 import camera_exact as cx
+import pool_cases
 import stereo_exact as sx
-from deepcharuco_amd import calib, pnp, stereo
+from deepcharuco_amd import calib, corner_pool, pnp, stereo
 
 pytestmark = pytest.mark.gpu
 
@@ -167,7 +168,7 @@ def test_masks_made_on_the_device_compose(dev):
     cams = (sx.CAMS[s.cam0], sx.CAMS[s.cam1])
     packs, dmasks, hmasks = [], [], ([], [])
     for c, kps in enumerate((s.kps0, s.kps1)):
-        packed, b, pool = pnp._pack(kps, dev)
+        packed, b, pool = corner_pool.pack_keypoints(kps, dev)
         st, _, info, inl = pnp.solve_pnp_ransac_pool(packed, b, pool, True, *s.board, *cams[c], **RANSAC)
         assert (st.cpu().numpy() == pnp.PNP_OK).all()
         packs.append((packed, pool))
@@ -221,20 +222,9 @@ def test_two_calls_give_the_same_bits(dev):
 
 def _hand_built_pool(kps, pool, seed, gap=3):
     """Views id-sorted, in scrambled pool order with gaps between them -> packed int32 (counts | starts | rows | xy)."""
-    B = len(kps)
-    packed = np.zeros(2 * B + 6 * pool, np.int32)
-    rows = packed[2 * B:2 * B + 4 * pool].reshape(pool, 4)
-    xy = packed[2 * B + 4 * pool:].view(np.float32).reshape(pool, 2)
-    rows[:] = -9
-    s0 = 2
-    for b in np.random.default_rng(seed).permutation(B):
-        kp = kps[b][np.argsort(kps[b][:, 2], kind="stable")] if len(kps[b]) else kps[b]
-        packed[b], packed[B + b] = len(kp), s0
-        assert s0 + len(kp) <= pool
-        rows[s0:s0 + len(kp), 0:2] = np.rint(kp[:, :2])
-        rows[s0:s0 + len(kp), 2] = kp[:, 2]
-        xy[s0:s0 + len(kp)] = kp[:, :2]
-        s0 += len(kp) + gap
+    packed, owned = pool_cases.lay_frames(kps, pool, np.random.default_rng(seed).permutation(len(kps)), gap=gap, first=2, filler=-9,
+                                          id_sorted=True)
+    assert owned.sum() == sum(len(k) for k in kps)                      # every view fits
     return packed
 
 
@@ -284,7 +274,7 @@ def test_calibrate_then_stereo_on_the_device(dev):
     sizes = ((320, 240), cx.CALIB_SIZE)
     packs, models, hmodels = [], [], []
     for c, kps in enumerate((s.kps0, s.kps1)):
-        packed, b, pool = pnp._pack(kps, dev)
+        packed, b, pool = corner_pool.pack_keypoints(kps, dev)
         r = calib.calibrate_charuco_pool(packed, b, pool, True, *s.board, sizes[c])
         assert r.status == calib.CALIB_OK
         packs.append((packed, pool))

@@ -360,6 +360,7 @@ def test_compaction_with_confidences_beyond_one_super_chunk(dev):
     the count the first `pool` slots hold the same rows and confidences, the count is still reported, and nothing is written
     past the pool (the buffer is prefilled); of two frames in a pool that holds only one of them, the complete one keeps its
     rows and confidences."""
+    from deepcharuco_amd.corner_pool import views
     from deepcharuco_amd.inference import infer_batch, infer_batch_device, packed_len, unpack_results
     from deepcharuco_amd.models.net import dcModel, lModel
     d = T.detector_regime()
@@ -389,11 +390,10 @@ def test_compaction_with_confidences_beyond_one_super_chunk(dev):
     d_frame = torch.from_numpy(frame).to(dev)
     big = infer_batch_device(d_frame, 16, dc, None, pool=1024, conf=True).cpu().numpy()
     assert big[0] == total and big[1] == 0
-    big_rows = big[2:2 + 4 * 1024].reshape(1024, 4)[:total]
-    big_conf = big[2 + 6 * 1024:].reshape(1024, 2)[:total]
+    _, _, big_rows, _, big_conf = (v[:total] for v in views(big, 1, 1024))
     assert np.array_equal(big_rows[:, 3], np.flatnonzero(fire))                       # cell indices in raster order
     assert np.array_equal(big_rows[:, :2], kp.numpy()) and np.array_equal(big_rows[:, 2], idf.numpy())
-    assert np.abs(big_conf.view(np.float32) - exp_c).max() <= CONF_392_ATOL
+    assert np.abs(big_conf - exp_c).max() <= CONF_392_ATOL
     sentinel, guard = -559038737, 256
     first = int(fire[:2048].sum())
     for pool in (first - 230, first + 70):      # the cut inside the first super-chunk, and inside the second
@@ -404,8 +404,9 @@ def test_compaction_with_confidences_beyond_one_super_chunk(dev):
         torch.cuda.synchronize()
         a = buf.cpu().numpy()
         assert a[0] == total and a[1] == 0, (pool, a[:2])
-        assert np.array_equal(a[2:2 + 4 * pool].reshape(pool, 4), big_rows[:pool]), pool
-        assert np.array_equal(a[2 + 6 * pool:n].reshape(pool, 2), big_conf[:pool]), pool
+        _, _, a_rows, _, a_conf = views(a[:n], 1, pool)
+        assert np.array_equal(a_rows, big_rows[:pool]), pool
+        assert np.array_equal(a_conf.view(np.int32), big_conf[:pool].view(np.int32)), pool
         assert np.all(a[2 + 4 * pool:2 + 6 * pool] == sentinel), f"pool={pool}: a row was written past the pool"
         assert np.all(a[n:] == sentinel), f"pool={pool}: a confidence was written past the pool"
     with pytest.warns(UserWarning, match=f"pool={total}"):

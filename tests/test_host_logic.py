@@ -108,18 +108,17 @@ def test_synthetic_frames_are_per_frame_deterministic():
 def test_unpack_results_sorting_and_dtypes():
     """The packed corner pool: counts[B] | starts[B] | rows[pool][4] | xy[pool][2] (| conf[pool][2]); frames sit in the pool in any
     order (starts[]), a frame may own any share of it, a frame that does not fit completely comes back as None."""
+    from deepcharuco_amd.corner_pool import views
     from deepcharuco_amd.inference import packed_len, unpack_results
     b, pool = 4, 8
-    assert packed_len(b, pool) == 2 * b + 6 * pool and packed_len(b, pool, True) == 2 * b + 8 * pool
+    assert packed_len(b, pool) == 56 and packed_len(b, pool, True) == 72
     packed = np.zeros(packed_len(b, pool, True), np.int32)
-    packed[:b] = [3, 0, 4, 5]                 # 12 corners > pool: the frame that was placed last does not fit
-    packed[b:2 * b] = [4, 7, 0, 7]            # frame 2 came first, then frame 0, then frame 3 (slots 7..11: only one exists)
-    rows = packed[2 * b:2 * b + 4 * pool].reshape(pool, 4)
+    counts_v, starts_v, rows, xy, cf = views(packed, b, pool)
+    counts_v[:] = [3, 0, 4, 5]                # 12 corners > pool: the frame that was placed last does not fit
+    starts_v[:] = [4, 7, 0, 7]                # frame 2 came first, then frame 0, then frame 3 (slots 7..11: only one exists)
     rows[4:7] = [[8, 9, 5, 1], [16, 17, 2, 2], [24, 25, 5, 3]]
     rows[0:4] = [[1, 1, 0, 0], [2, 2, 0, 1], [3, 3, 0, 2], [4, 4, 0, 3]]
-    xy = packed[2 * b + 4 * pool:2 * b + 6 * pool].view(np.float32).reshape(pool, 2)
     xy[4:7] = [[8.5, 9.25], [16.125, 17], [24, 25.5]]
-    cf = packed[2 * b + 6 * pool:].view(np.float32).reshape(pool, 2)
     cf[4:7] = [[0.5, 0.25], [0.75, 0.125], [1.0, 0.0625]]
     res, counts, confs = unpack_results(packed, b, pool, True, conf=True)
     assert res[0].dtype == np.float64

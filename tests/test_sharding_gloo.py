@@ -9,6 +9,8 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from deepcharuco_amd.corner_pool import packed_len, views
+
 
 def _fake_local(kcap):
     """(frames (b,H,W) u8, pool) -> packed int32 tensor exactly in infer_batch_device's layout (counts | starts | rows | xy).
@@ -17,15 +19,14 @@ def _fake_local(kcap):
     beyond the pool are dropped, as the kernels do."""
     def run(frames, pool):
         b = frames.shape[0]
-        packed = np.zeros(2 * b + 6 * pool, np.int32)
-        rows = packed[2 * b:2 * b + 4 * pool].reshape(pool, 4)
-        xy = packed[2 * b + 4 * pool:].view(np.float32).reshape(pool, 2)
+        packed = np.zeros(packed_len(b, pool), np.int32)
+        counts, starts, rows, xy, _ = views(packed, b, pool)
         cursor = 0
         for i in reversed(range(b)):
             tag = int(frames[i, 0, 0])
             k = tag % (kcap + 1)
-            packed[i] = k
-            packed[b + i] = cursor
+            counts[i] = k
+            starts[i] = cursor
             for j in range(k):
                 if cursor + j < pool:
                     rows[cursor + j] = [tag + j, 2 * tag + j, (tag * 7 + j * 3) % 16, j]

@@ -51,7 +51,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
-    from deepcharuco_amd import calib, pnp
+    from deepcharuco_amd import calib, corner_pool, pnp
     from test_calib_host import BOARD, SIZE
     assert torch.cuda.is_available(), "calib_probe measures the GPU kernels: no GPU visible"
     dev = torch.device("cuda", 0)
@@ -61,7 +61,7 @@ def main():
         for n_views in (64, 512, 4096):
             key = f"B{n_views}_n{n_corners}"
             objs, imgs, kps = views(1000 + n_views + n_corners, n_views, n_corners, 0.5)
-            packed, b, pool = pnp._pack(kps, dev)
+            packed, b, pool = corner_pool.pack_keypoints(kps, dev)
             d = calib.calibrate_charuco_pool(packed, b, pool, True, *BOARD, SIZE)      # warm-up
             ts = []
             for _ in range(a.reps):

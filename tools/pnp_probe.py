@@ -47,7 +47,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
-    from deepcharuco_amd import pnp
+    from deepcharuco_amd import corner_pool, pnp
     assert torch.cuda.is_available(), "pnp_probe measures the GPU kernel: no GPU visible"
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(0)
@@ -56,7 +56,7 @@ def main():
     for n_points in (16, 256):
         for b in (32, 128):
             fr = frames(rng, b, n_points)
-            packed, bb, pool = pnp._pack(fr, dev)
+            packed, bb, pool = corner_pool.pack_keypoints(fr, dev)
             out = pnp.solve_pnp_pool(packed, bb, pool, True, *BOARD, K, DIST5)
             for _ in range(a.warmup):
                 pnp.solve_pnp_pool(packed, bb, pool, True, *BOARD, K, DIST5, out=out)

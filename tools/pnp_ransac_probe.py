@@ -44,7 +44,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
-    from deepcharuco_amd import pnp
+    from deepcharuco_amd import corner_pool, pnp
     assert torch.cuda.is_available(), "pnp_ransac_probe measures the GPU kernels: no GPU visible"
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(0)
@@ -55,7 +55,7 @@ def main():
     for n_points in (16, 256):
         for b in (32, 128):
             fr = frames(rng, b, n_points)
-            packed, bb, pool = pnp._pack(fr, dev)
+            packed, bb, pool = corner_pool.pack_keypoints(fr, dev)
             args = (packed, bb, pool, True, *BOARD, K, DIST5)
             kw = dict(iterations=a.iterations, reproj_error=a.reproj_error, seed=0)
             plain = pnp.solve_pnp_pool(*args)

@@ -66,7 +66,7 @@ def main():
         return kernel_stats(a.kernel_stats)
     import torch
     import stereo_exact as sx
-    from deepcharuco_amd import calib, pnp, stereo
+    from deepcharuco_amd import calib, corner_pool, stereo
     assert torch.cuda.is_available(), "stereo_probe measures the GPU kernels: no GPU visible"
     dev = torch.device("cuda", 0)
     size0 = (320, 240)
@@ -78,7 +78,7 @@ def main():
             key = f"T{n_pairs}_n{n_rows}"
             s = sx.scene(3000 + n_pairs + n_rows, n_pairs, "toe90", sx.BOARD_S, "A", "B", sigma=0.5, rows=n_rows)
             cams = sx.cam_args(s)
-            (p0, b, pool0), (p1, _, pool1) = pnp._pack(s.kps0, dev), pnp._pack(s.kps1, dev)
+            (p0, b, pool0), (p1, _, pool1) = corner_pool.pack_keypoints(s.kps0, dev), corner_pool.pack_keypoints(s.kps1, dev)
             ms, d = timed(lambda: stereo.stereo_calibrate_pool(p0, p1, b, pool0, pool1, True, *s.board, *cams), a.reps)
             assert d.status == stereo.STEREO_OK, (key, d.status)
             cms, c = timed(lambda: calib.calibrate_charuco_pool(p0, b, pool0, True, *s.board, size0), a.reps)
