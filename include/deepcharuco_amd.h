@@ -183,7 +183,12 @@ int dcx_argmax2d(const float* d_x, int k, int h, int w, int32_t* d_out, void* st
  *                             the cell -- the "confidences" the docstring of pred_to_keypoints (model_utils.py:81-84) mentions;
  *                             the reference never thresholds on them and neither does this library
  * Slots >= pool are dropped: when sum(counts) > pool the caller re-runs with a larger pool (complete frames are still valid).
- * d_ws must hold dcx_pipeline_workspace_bytes().  rf may be null (detector + decode only).                                */
+ * d_ws must hold dcx_pipeline_workspace_bytes().  rf may be null (detector + decode only).
+ *
+ * WORKSPACES, here and for every entry that takes a d_ws, d_workspace or d_front: the contents of a workspace at entry do not
+ * matter; the call writes nothing outside [d_ws, d_ws + *_workspace_bytes()) and its output buffers.  A workspace may hold
+ * zeros, NaN bit patterns or what any earlier call left in it, of another batch size or shape; nothing has to be cleared between
+ * calls (tests/test_gpu_workspace_contract.py holds every entry to this on poisoned, exact-size buffers between guards).   */
 #define DCX_PIX_GRAY8          0
 #define DCX_PIX_BGR8           1   /* OpenCV 4.x 15-bit constants, = dcx_bgr2gray          */
 #define DCX_PIX_BGR8_LEGACY14  2   /* 14-bit constants,            = dcx_bgr2gray_legacy14 */

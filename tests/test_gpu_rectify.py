@@ -34,11 +34,12 @@ def _rectify(kind, c0, c1, alpha=None):
 
 # ------------------------------------------------------------------------------------------------ the map
 
-def _map_agrees(dev, K, d, R, P, w, h, name):
+def _map_agrees(dev, K, d, R, P, w, h, name, out=None):
     """Device map against host map: equal, but for entries whose unquantised 32 m lies within 1e-6 of a half-integer on the host
-    (the two sum in different orders), which may differ by 1.  -> (entries differing, entries near a tie)."""
+    (the two sum in different orders), which may differ by 1.  -> (entries differing, entries near a tie).  ``out``: the device
+    tensor that receives the map."""
     host = rc.undistort_rectify_map_host(K, d, R, P, w, h)
-    got = rc.undistort_rectify_map_device(K, d, R, P, w, h, device=dev)
+    got = rc.undistort_rectify_map_device(K, d, R, P, w, h, device=dev, out=out)
     assert got.dtype == torch.int32 and tuple(got.shape) == (h, w, 2)
     got = got.cpu().numpy()
     s_h, s_d = host == rc.MAP_SENTINEL, got == rc.MAP_SENTINEL

@@ -8,8 +8,9 @@ would call it.  Everything compares by exact equality, on int
   * the library's already pinned entries where an equality of two paths is the claim (dcx_infer_batch; dcx_refiner_forward
     without a limit, test_gpu_exact_chain.py).
 
-Every output buffer is prefilled with a sentinel and has a guard region behind it that is checked after the call.  Every table a
-test passes stays inside the buffers it allocates: no frame index, slot or total is out of range anywhere in this file.
+Every output buffer is prefilled with a sentinel and lies between two guard regions (tests/guarded.py) that are checked after the
+call.  Every table a test passes stays inside the buffers it allocates: no frame index, slot or total is out of range anywhere in
+this file.
 Counts per case go to staged_abi_report.json in the suite's report directory (beside test_gpu_parity.py's parity_report.json)."""
 import json
 import os
@@ -21,11 +22,11 @@ import torch
 from conftest import REPO, GoldenCase
 from deepcharuco_amd import weights as W
 from oracle import deepcharuco_oracle as O
+from guarded import Guarded
 from staged_exact import SENTINEL, decode_rows, gather_u8, patch_table
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 256                      # elements behind every output buffer
 FSENT = -12345.5                 # float sentinel (no kernel here can produce it: |normalised pixel| <= 0.5, xy >= -4)
 E_ARG, E_SHAPE, E_NIDS = -1, -2, -4
 
@@ -62,29 +63,6 @@ def L():
 def _stream():
     from deepcharuco_amd import _lib
     return _lib.current_stream()
-
-
-class Guarded:
-    """A device buffer of ``shape`` filled with ``fill``, with GUARD more elements of ``fill`` behind it."""
-
-    def __init__(self, dev, shape, dtype, fill):
-        self.n = int(np.prod(shape)) if len(shape) else 1
-        self.fill = fill
-        self.full = torch.full((self.n + GUARD,), fill, dtype=dtype, device=dev)
-        self.t = self.full[:self.n].view(*shape)
-
-    @property
-    def ptr(self):
-        return self.full.data_ptr()
-
-    def refill(self):
-        self.full.fill_(self.fill)
-
-    def guard_ok(self):
-        return bool((self.full[self.n:] == self.fill).all().item())
-
-    def cpu(self):
-        return self.t.cpu().numpy()
 
 
 def _ibuf(dev, *shape):
