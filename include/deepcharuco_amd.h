@@ -425,6 +425,32 @@ int dcx_rectify_points_pool(const int32_t* d_rows, const float* d_xy /* NULL = u
 int dcx_remap_u8(const uint8_t* d_src, long frame_stride, int pitch, int src_h, int src_w, int channels /* 1 or 3 */,
                  const int32_t* d_map, int out_h, int out_w, int batch, int border, uint8_t* d_out, void* stream);
 
+/* ---- image resizing (cv2.resize): what stands in front of the detector ---------------------------------------------------------
+ * dcx_resize_u8: batch frames d_src (u8, `channels` = 1 or 3 interleaved, rows `pitch` bytes apart, frames `frame_stride` bytes
+ * apart, any base address: a cropped view costs nothing) -> d_out u8 [batch][out_h][out_w][channels], dense.  Channels are
+ * independent.  Bit-exact against deepcharuco_amd/resize.py:resize_host, which states every step; the formulas are cv2's as
+ * published and are NOT pinned against cv2.  With sw, sh the source and dw, dh the output size, per axis
+ * scale = 1.0 / (dn / sn) in double (computed by this entry on the host, a kernel argument):
+ *
+ * interpolation 0, "nearest": sx = min(floor(dx * scale), sw - 1), the same in y, fp64.
+ * interpolation 2, "area": only sw = fx dw and sh = fy dh with integers 1 <= fx, fy <= 64 (DCX_E_SHAPE otherwise); sum = the
+ *   integer sum of the fx fy source pixels; fx = fy = 2: out = (sum + 2) >> 2; else out = rint(float(sum) * float(1.0 / (fx fy))),
+ *   one float32 product, ties to even.
+ * interpolation 1, "linear": sw = 2 dw and sh = 2 dh gives "area" (cv2's rule).  Otherwise per axis f = float((d + 0.5) * scale
+ *   - 0.5) (product and difference each rounded to double, no fused multiply-add), s = floor(f), f = f - float(s) in float32.
+ *   In x: s < 0 gives f = 0, s = 0; s >= sw - 1 gives f = 0, s = sw - 1; the taps are s and min(s + 1, sw - 1).  In y the rows are
+ *   clip(s, 0, sh - 1) and clip(s + 1, 0, sh - 1) and f stays.  Coefficients c0 = rint(float(1 - f) * 2048), c1 = rint(f * 2048)
+ *   in float32, ties to even, each on its own (a0, a1 in x; b0, b1 in y).  r = S[x0] a0 + S[x1] a1 on both rows (int32), then
+ *   out = (((b0 (r0 >> 4)) >> 16) + ((b1 (r1 >> 4)) >> 16) + 2) >> 2.  A reduction reads the two tap rows only.
+ *
+ * DCX_E_ARG: a null pointer, channels not 1 or 3, an interpolation not 0, 1 or 2, a negative frame_stride.  DCX_E_SHAPE: src_h,
+ * src_w, out_h, out_w or batch outside 1 .. 32768, pitch < src_w * channels, pitch * src_h beyond an int32, a refused area
+ * factor.  Every refusal comes before anything is launched.  One launch on `stream`: no workspace, no allocation, no
+ * synchronisation, no atomics, so two calls give the same bits and a call can be captured in a hipGraph.                      */
+int dcx_resize_u8(const uint8_t* d_src, long frame_stride, int pitch, int src_h, int src_w, int channels /* 1 or 3 */,
+                  int out_h, int out_w, int batch, int interpolation /* 0 nearest, 1 linear, 2 area */, uint8_t* d_out,
+                  void* stream);
+
 /* ---- dense stereo matching on a rectified pair, and the disparity map as 3-D points ------------------------------------------
  * What follows dcx_remap_u8: semi-global matching (what cv2.StereoSGBM is called for) over 9 x 7 census costs, integer throughout
  * and bit-exact against deepcharuco_amd/disparity.py:sgm_host, which states every step.  d_left is rectified camera 0 and d_right
