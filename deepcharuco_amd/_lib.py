@@ -87,6 +87,9 @@ SIGNATURES = {
     "dcx_stereo_calibrate_pool": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), _i,
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), _i, _vp, _sz, _vp, _vp, _vp,
                                       C.POINTER(C.c_double), _vp]),
+    "dcx_rig_calibrate_workspace_bytes": (_sz, [_i, _i, C.POINTER(C.c_int)]),
+    "dcx_rig_calibrate_pool": (_i, [_i, _vp, _i, _i, _i, C.c_double, _vp, _sz, _vp, _vp, _vp, C.POINTER(C.c_int32),
+                                   C.POINTER(C.c_double), _vp]),
     "dcx_undistort_rectify_map": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double), _i, C.POINTER(C.c_double),
                                       C.POINTER(C.c_double), _i, _i, _vp, _vp]),
     "dcx_rectify_points_pool": (_i, [_vp, _vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), _i, C.POINTER(C.c_double),

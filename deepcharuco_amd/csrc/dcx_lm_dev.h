@@ -1,6 +1,6 @@
-// dcx_lm_dev.h -- the joint Levenberg-Marquardt driver of the two calibrations (dcx_calib.hip over NG = 9 intrinsics,
-// dcx_stereo.hip over NG = 6 rig parameters; every unit -- a view, a pair -- adds 6 pose parameters that couple only to the NG
-// global ones), one copy.  deepcharuco_amd/_lm.py restates it for the host definitions.  Three parts:
+// dcx_lm_dev.h -- the joint Levenberg-Marquardt driver of the calibrations (dcx_calib.hip over NG = 9 intrinsics,
+// dcx_stereo.hip over NG = 6 rig parameters, dcx_rig.hip over NG = 42 of which a rig of C cameras uses 6 (C - 1); every unit -- a
+// view, a pair, a timestamp -- adds 6 pose parameters that couple only to the NG global ones), one copy.  deepcharuco_amd/_lm.py restates it for the host definitions.  Three parts:
 //   1. the automaton (CvLevMarq's rules), plain C++17 that a host compiler takes without any HIP header, so a stand-alone program
 //      can walk its branches (tests/lm_host_main.cpp): LmState, lm_reset, lm_fail, lm_decide;
 //   2. device helpers in the idiom of dcx_mat_dev.h's accumulate_rows (the caller passes callables): lm_decide_block (the decide
@@ -41,27 +41,29 @@ static_assert(DCX_CALIB_NONFINITE == kLmNonfinite && DCX_STEREO_NONFINITE == kLm
 constexpr int kJointMaxIter = 30;
 constexpr double kJointEps = 2.220446049250313e-16;         // DBL_EPSILON
 
-// result = h_result: g (NG), rms, accepted steps, attempts, units used, points used, status; the rest is the caller's
-template <int NG>
+// result = h_result: g (NG), rms, accepted steps, attempts, units used, points used, status; the rest is the caller's.  NR: its
+// words, 16 for the two solvers whose h_result that is; dcx_rig.hip's NG = 42 needs 48
+template <int NG, int NR = 16>
 struct LmState {
+    static_assert(NG + 6 <= NR, "result");
     double g[NG], g_trial[NG], dg[NG];
     double prev_cost;
-    double result[16];
+    double result[NR];
     int lg, iters, attempts, code;
 };
 
-template <int NG>
-DCX_LM_HD void lm_reset(LmState<NG>* st) {
+template <int NG, int NR>
+DCX_LM_HD void lm_reset(LmState<NG, NR>* st) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) st->result[i] = 0.0;
+    for (int i = 0; i < NR; ++i) st->result[i] = 0.0;
     st->lg = -3;
     st->iters = 0;
     st->attempts = 0;
 }
 
 // the step could not be solved: the outputs stay zero but for the counts
-template <int NG>
-DCX_LM_HD void lm_fail(LmState<NG>* st, int status) {
+template <int NG, int NR>
+DCX_LM_HD void lm_fail(LmState<NG, NR>* st, int status) {
     st->result[NG + 1] = st->iters;
     st->result[NG + 2] = st->attempts;
     st->result[NG + 5] = status;
@@ -71,8 +73,8 @@ DCX_LM_HD void lm_fail(LmState<NG>* st, int status) {
 // One decision.  init: after the first evaluate (cost = the initial cost); else after a trial with its cost, the units' shares
 // of |dp|^2 and |p|^2 (the global parameters' are added here) and whether a trial pose is not finite.
 // -> 0: nothing to commit, 1: commit the trial and continue (or fail), 2: commit and finish OK
-template <int NG, bool STOP_FORCED>
-DCX_LM_HD int lm_decide(LmState<NG>* st, bool init, double cost, double dn, double pn, double units, double points, bool bad) {
+template <int NG, bool STOP_FORCED, int NR>
+DCX_LM_HD int lm_decide(LmState<NG, NR>* st, bool init, double cost, double dn, double pn, double units, double points, bool bad) {
     st->result[NG + 3] = units;
     st->result[NG + 4] = points;
     if (init) {
@@ -170,8 +172,8 @@ __device__ __forceinline__ void lm_trial_pose(const double* yz, const double* dg
 // poses committed where the verdict says so.  used(b): unit b takes part; init_cost(b): its cost after evaluate; trial_sums(b, a):
 // its trial cost, |dp|^2 and |p|^2 added to a[0..2]; points(b): its rows; finish(b): the caller's own outputs of unit b when the
 // solve ends OK (verdict 2).
-template <int NG, bool STOP_FORCED, class Used, class InitCost, class TrialSums, class Points, class Finish>
-__device__ __forceinline__ void lm_decide_block(LmState<NG>* st, int batch, int init, double* pose, const double* trial_pose,
+template <int NG, bool STOP_FORCED, int NR, class Used, class InitCost, class TrialSums, class Points, class Finish>
+__device__ __forceinline__ void lm_decide_block(LmState<NG, NR>* st, int batch, int init, double* pose, const double* trial_pose,
                                                 const Used& used, const InitCost& init_cost, const TrialSums& trial_sums,
                                                 const Points& points, const Finish& finish) {
     __shared__ double s[kLmThreads][6];      // cost, |dp|^2, |p|^2, units, points, non-finite poses

@@ -1,0 +1,188 @@
+// dcx_stereo_dev.h -- what the joint extrinsic solves share (dcx_stereo.hip over two cameras, dcx_rig.hip over up to eight), one
+// copy of each fp64 step, on top of dcx_pnp_dev.h (pool, frames, solve) and dcx_lm_dev.h (the LM driver):
+//   MaskedPool, the overlap and ident kernels    a camera's pool with its optional per-slot mask, and what reading it needs
+//   view_solve                                   the init_views kernels' body: checks, mask compaction, solve()
+//   relative_pose                                R_t = R1 R0^T, T_t = t1 - R_t t0 of two poses of one board
+//   PairBasis, pair_basis, stereo_row            one row of a camera behind a rig transform: residual and its two lines of
+//                                                [J_X (6) | J_P (6)]; the reference camera's rows (SECOND = false) have J_X = 0
+//   accumulate_view, view_cost                   a view's rows added to its packed 13 x 13 / its trial cost
+// Everything is force-inlined and has internal linkage, so each translation unit compiles its own copy.
+#pragma once
+#include "dcx_pnp_dev.h"
+#include "dcx_lm_dev.h"
+
+namespace {
+
+constexpr int kLdsStride = 13;           // [J_X (6) | J_P (6) | r]
+
+struct MaskedPool {                      // one camera's pool and the optional mask that rides beside it
+    CornerPool p;
+    const uint8_t* mask;                 // per slot, or null: every row is kept
+};
+
+// One wave per view of a pool with a mask: does its slot range meet another view's?
+__global__ __launch_bounds__(kLanes) void stereo_overlap_kernel(CornerPool pl, int batch, int32_t* __restrict__ flag) {
+    if (ranges_overlap(pl, batch, blockIdx.x) && threadIdx.x == 0) *flag = 1;
+}
+
+__global__ __launch_bounds__(256) void stereo_ident_kernel(int n, int32_t* __restrict__ ident) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) ident[i] = i;
+}
+
+// View t of a pool: the checks; with a mask the kept rows compacted in order (ballot + prefix popcount, 64 rows at a time) into
+// the index list at the view's own slots of `lists`; solve() over an IndexedFrame either way, so a NULL mask and a mask of ones run
+// the same instructions on the same values.  -> DCX_PNP_*; out = solve()'s pose words (zero unless it ran), kept = the rows after
+// the mask (0 for a view that is empty or cut by the pool).  One wave, the whole block.
+__device__ __forceinline__ int view_solve(const MaskedPool& pl, const PnpCamera& cam, int t, int32_t* lists, const int32_t* ident,
+                                          double (&out)[8], int& kept) {
+    const int lane = threadIdx.x;
+    const int n = pl.p.counts[t], s0 = pl.p.starts[t];
+    int st = DCX_PNP_OK;
+    kept = 0;
+    const int32_t* idx = ident;
+    // Not the header's frame_status(): with a mask this is another function (only the kept rows' ids are checked, and TOO_FEW is
+    // judged on the kept rows, after the pool cut).  Its first two rules mirror frame_status(); a change there is a change here.
+    if (n <= 0) {
+        st = DCX_PNP_TOO_FEW;
+    } else if (s0 < 0 || (long long)s0 + n > (long long)pl.p.pool) {
+        st = DCX_PNP_TRUNCATED;               // (its slots are not read)
+    } else {
+        bool bad = false;
+        if (pl.mask) {
+            int32_t* list = lists + s0;
+            for (int base = 0; base < n; base += kLanes) {
+                const int i = base + lane;
+                const bool in = i < n && pl.mask[(long long)s0 + i] != 0;
+                const int at = append_kept(in, lane, kept);
+                if (in) {
+                    list[at] = i;
+                    const int id = pl.p.rows[4 * ((long long)s0 + i) + 2];
+                    bad |= id < 0 || id >= pl.p.n_ids;
+                }
+            }
+            idx = list;
+        } else {
+            for (int i = lane; i < n; i += kLanes) {
+                const int id = pl.p.rows[4 * ((long long)s0 + i) + 2];
+                bad |= id < 0 || id >= pl.p.n_ids;
+            }
+            kept = n;
+        }
+        __syncthreads();                      // one wave: the list is read below by other lanes than wrote it
+        if (kept < 4) st = DCX_PNP_TOO_FEW;
+        else if (__any(bad)) st = DCX_PNP_BAD_ID;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) out[i] = 0.0;
+    if (st == DCX_PNP_OK) {
+        const IndexedFrame g{pl.p.frame(n, s0), idx, kept};
+        st = solve(g, cam, out);
+    }
+    return st;
+}
+
+// Two poses (rvec, tvec) of one board, in cameras 0 and 1 -> rig = R_t (9, row major) = R1 R0^T, T_t (3) = t1 - R_t t0
+__device__ __forceinline__ void relative_pose(const double* p0, const double* p1, double* rig) {
+    double R0[9], R1[9];
+    rodrigues(p0, R0);
+    rodrigues(p1, R1);
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) rig[a * 3 + b] = R1[a * 3] * R0[b * 3] + R1[a * 3 + 1] * R0[b * 3 + 1] + R1[a * 3 + 2] * R0[b * 3 + 2];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) rig[9 + a] = p1[3 + a] - (rig[a * 3] * p0[3] + rig[a * 3 + 1] * p0[4] + rig[a * 3 + 2] * p0[5]);
+}
+
+// What every row of a pair shares: R(P), t_P, pose_basis()'s G at P, R(X), T_X and Jr(r_X).
+struct PairBasis {
+    double RP[9], tP[3], G[2][9], RX[9], TX[3], JX[9];
+};
+
+template <bool JAC>
+__device__ __forceinline__ void pair_basis(const double* x, const double* p, PairBasis& B) {
+    if (JAC) pose_basis(p, B.RP, B.G);
+    else rodrigues(p, B.RP);
+    rodrigues(x, B.RX);
+    if (JAC) right_jacobian(x, B.JX);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        B.tP[i] = p[3 + i];
+        B.TX[i] = x[3 + i];
+    }
+}
+
+// One row of camera SECOND's view at (X, P) -> residual (ru, rv); with JAC its two rows of [J_X (6) | J_P (6)]: the header's
+// project() and pose_columns() on the point q = R_P m + t_P (camera 0) or R_X q + T_X (camera 1).  false if the
+// point is not in front of the camera.
+template <bool JAC, bool SECOND>
+__device__ __forceinline__ bool stereo_row(const PnpCamera& cam, const PairBasis& B, double mx, double my, double u, double v,
+                                           double& ru, double& rv, double* ju, double* jv) {
+    double q0[3], q[3], du[3], dv[3];
+    board_point(B.RP, B.tP, mx, my, q0);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        q[i] = SECOND ? B.RX[i * 3] * q0[0] + B.RX[i * 3 + 1] * q0[1] + B.RX[i * 3 + 2] * q0[2] + B.TX[i] : q0[i];
+    if (!project<JAC>(cam, q, u, v, ru, rv, du, dv)) return false;
+    if (!JAC) return true;
+    // d(u, v)/dq0: camera 1 sees q0 through R_X
+    double eu[3], ev[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        eu[j] = SECOND ? du[0] * B.RX[j] + du[1] * B.RX[3 + j] + du[2] * B.RX[6 + j] : du[j];
+        ev[j] = SECOND ? dv[0] * B.RX[j] + dv[1] * B.RX[3 + j] + dv[2] * B.RX[6 + j] : dv[j];
+    }
+    pose_columns(eu, ev, mx, my, B.G, ju + 6, jv + 6);
+    if (SECOND) {
+        // dq/dr_X = -R_X [q0]x Jr(r_X), so d(u, v)/dr_X = -(e . A), A = [q0]x Jr(r_X)
+        const double S[9] = {0.0, -q0[2], q0[1], q0[2], 0.0, -q0[0], -q0[1], q0[0], 0.0};
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double su = 0.0, sv = 0.0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const double a = S[i * 3] * B.JX[j] + S[i * 3 + 1] * B.JX[3 + j] + S[i * 3 + 2] * B.JX[6 + j];
+                su += eu[i] * a;
+                sv += ev[i] * a;
+            }
+            ju[j] = -su;
+            jv[j] = -sv;
+            ju[3 + j] = du[j];
+            jv[3 + j] = dv[j];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) ju[j] = jv[j] = 0.0;
+    }
+    return true;
+}
+
+// One view's rows added to the pair's 91 entries: 64 rows at a time through LDS, every lane its two entries in row order.
+template <bool SECOND>
+__device__ __forceinline__ void accumulate_view(const IndexedFrame& f, const PnpCamera& cam, const PairBasis& B,
+                                                double (*sj)[kLdsStride], const int* ea, const int* eb, double* acc, bool& behind) {
+    accumulate_rows<13, 2, kLdsStride>(f.n, [&](int i, double* ju, double* jv) {
+        double mx, my, u, v;
+        f.load(i, mx, my, u, v);
+        return stereo_row<true, SECOND>(cam, B, mx, my, u, v, ju[12], jv[12], ju, jv);
+    }, sj, ea, eb, acc, behind);
+}
+
+template <bool SECOND>
+__device__ __forceinline__ double view_cost(const IndexedFrame& f, const PnpCamera& cam, const PairBasis& B) {
+    double c[1] = {0.0};
+    for (int i = threadIdx.x; i < f.n; i += kLanes) {
+        double mx, my, u, v, ru, rv;
+        f.load(i, mx, my, u, v);
+        if (!stereo_row<false, SECOND>(cam, B, mx, my, u, v, ru, rv, nullptr, nullptr)) {
+            c[0] = INFINITY;
+            continue;
+        }
+        c[0] += ru * ru + rv * rv;
+    }
+    wave_sum(c);
+    return c[0];
+}
+
+}  // namespace

@@ -384,6 +384,60 @@ int dcx_stereo_calibrate_pool(const int32_t* d_counts0, const int32_t* d_starts0
                               int32_t* d_view_status /* [B][2] DCX_PNP_* */, double* d_pose /* [B][8] */,
                               double* d_view_info /* [B][2][2] */, double* h_result /* [16] */, void* stream);
 
+/* ---- joint extrinsic calibration of a rig of 2 .. 8 cameras from their corner pools -------------------------------------------
+ * dcx_stereo_calibrate_pool over n_cams rigidly mounted cameras with known models and one corner pool each (DcxRigCamera), all
+ * with the same `batch`: frame t of every pool shows the same board at the same instant, and a camera that did not see it then
+ * has an empty frame.  Camera 0 is the reference.  Result: X_c = (rvec, T), q_c = R_c q_0 + T_c, for c = 1 .. n_cams - 1, and the
+ * board's pose P_t in camera 0's frame for every timestamp used.  All fp64; deepcharuco_amd/rig.py restates the steps
+ * (rig_calibrate_host_full):
+ * 1. per view the mask, the checks and the solve of dcx_stereo_calibrate_pool's steps 1 - 2.  A view is usable if it is
+ *    DCX_PNP_OK; a timestamp is used if at least two of its views are, whichever cameras they are.  A usable view that is alone
+ *    at its timestamp is reported and takes no part.
+ * 2. the camera graph, on the host from one copy of the statuses: cameras share a timestamp where both are usable; camera 0 is
+ *    placed, then each placed camera, in placement order, takes in ascending order every camera not placed yet that shares a
+ *    timestamp with it, as its child.  Per tree edge (a -> c) dcx_stereo_calibrate_pool's rig init over the timestamps a and c
+ *    share (lower medians of R_c,t R_a,t^T and t_c,t - R_t t_a,t, polar factor, Rodrigues), composed along the tree:
+ *    X_c = Z o X_a (a child of camera 0 takes Z unchanged).  No used timestamp: DCX_RIG_NO_STAMPS; else a camera that is never
+ *    placed: DCX_RIG_DISCONNECTED.
+ * 3. P_t starts at X_c^-1 o pose_{c,t} of the timestamp's lowest-numbered usable camera c (camera 0: its own pose, unchanged).
+ * 4. joint Levenberg-Marquardt over all X_c and every used P_t with dcx_stereo_calibrate_pool's rules, each step by block
+ *    elimination of the timestamps' 6x6 pose blocks and one Cholesky of 6 (n_cams - 1) rows.
+ * The entry point SYNCHRONISES `stream` (the statuses, the edges' R_t, T_t, a state word after every LM attempt) and cannot be
+ * captured in a graph.  d_workspace: dcx_rig_calibrate_workspace_bytes(n_cams, batch, h_pools) bytes of device memory, 8-byte
+ * aligned (DCX_E_WS if smaller); no device memory is allocated, and nothing but the workspace and the three output buffers is
+ * written.  DCX_E_ARG: n_cams outside [2, 8], a refused camera or pool, a masked pool whose frames'
+ * slot ranges overlap (found on the device; the outputs are then unspecified).
+ * d_view_status int32 [B][n_cams]: DCX_PNP_* of view (t, camera).  d_pose f64 [B][8] = P_t as rvec(3), tvec(3), the timestamp's
+ * rms over its usable views (px), their rows; all zero unless the timestamp was used and the status is DCX_RIG_OK.
+ * d_view_info f64 [B][n_cams][2] = per view its rms at the solution (zero unless it took part and the status is DCX_RIG_OK) and
+ * the rows it brings after its mask.  h_parents int32 [n_cams]: the tree, -1 for camera 0 and a camera that was not placed.
+ * h_result f64 [8 + 6 (n_cams - 1)] = rms, accepted LM steps, attempts, timestamps used, points used (whatever the status),
+ * DCX_RIG_* status, 0, 0, then X_1 .. X_{n_cams - 1} (rvec, T each); the rms and the X are zero unless DCX_RIG_OK.
+ * No atomics, every sum in a fixed order: two calls on the same input give the same bits, and so do a NULL mask and a mask of
+ * ones.                                                                                                                       */
+#define DCX_RIG_OK            0
+#define DCX_RIG_NO_STAMPS     1   /* no timestamp has two usable views */
+#define DCX_RIG_DEGENERATE    2   /* a median matrix or a damped step is singular, or the cost is not finite */
+#define DCX_RIG_NONFINITE     3
+#define DCX_RIG_DISCONNECTED  4   /* a camera shares no timestamp with the cameras reached from camera 0 */
+#define DCX_RIG_MAX_CAMERAS   8
+typedef struct DcxRigCamera {
+    const int32_t* d_counts;      /* the camera's corner pool, as for dcx_solve_pnp_pool */
+    const int32_t* d_starts;
+    const int32_t* d_rows;
+    const float* d_xy;            /* NULL = use integer rows x,y */
+    int pool;
+    const uint8_t* d_mask;        /* [pool] by slot, or NULL */
+    double camera9[9];            /* K row major, no skew */
+    double dist[8];               /* the first n_dist are read */
+    int n_dist;                   /* 0, 4, 5 or 8 */
+} DcxRigCamera;
+size_t dcx_rig_calibrate_workspace_bytes(int n_cams, int batch, const int* h_pools);   /* 0 for refused arguments */
+int dcx_rig_calibrate_pool(int n_cams, const DcxRigCamera* h_cams, int batch, int col_count, int row_count, double square_len,
+                           void* d_workspace, size_t workspace_bytes, int32_t* d_view_status /* [B][n_cams] DCX_PNP_* */,
+                           double* d_pose /* [B][8] */, double* d_view_info /* [B][n_cams][2] */, int32_t* h_parents /* [n_cams] */,
+                           double* h_result /* [8 + 6 (n_cams - 1)] */, void* stream);
+
 /* ---- stereo rectification: the undistort + rectify map, the remap of u8 frames, the corner pool in rectified coordinates ------
  * What follows dcx_stereo_calibrate_pool: with the rig's rectifying transforms (R1, R2, P1, P2 of
  * deepcharuco_amd/rectify.py:stereo_rectify_host, Bouguet's construction as cv2.stereoRectify with CALIB_ZERO_DISPARITY; host
