@@ -95,6 +95,15 @@ SIGNATURES = {
     "dcx_rectify_points_pool": (_i, [_vp, _vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), _i, C.POINTER(C.c_double),
                                     C.POINTER(C.c_double), _vp, _vp]),
     "dcx_remap_u8": (_i, [_vp, _l, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "dcx_fisheye_solve_pnp_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       _vp, _vp, _vp]),
+    "dcx_fisheye_calibrate_workspace_bytes": (_sz, [_i]),
+    "dcx_fisheye_calibrate_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _i, _i, C.c_double, _vp, _sz, _vp, _vp,
+                                       C.POINTER(C.c_double), _vp]),
+    "dcx_fisheye_undistort_rectify_map": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                              C.POINTER(C.c_double), _i, _i, _vp, _vp]),
+    "dcx_fisheye_rectify_points_pool": (_i, [_vp, _vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                            C.POINTER(C.c_double), _vp, _vp]),
     "dcx_resize_u8": (_i, [_vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "dcx_sgm_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "dcx_sgm_u8": (_i, [_vp, _l, _i, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),

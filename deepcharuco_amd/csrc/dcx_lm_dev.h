@@ -9,7 +9,7 @@
 //   3. lm_run, the host loop.
 // The rules: damping 1 + 10^lg, lg from -3; a step whose cost is not <= the cost before is rejected: lg + 1 and the same point is
 // tried again, up to lg = 16; at 17 the step is taken whatever it costs (forced); an accepted or forced step takes lg - 1, down to
-// -16; at most kJointMaxIter accepted steps; stop at |dp| < DBL_EPSILON |p| over all parameters.
+// -16; at most MAX_ITER accepted steps (kJointMaxIter unless the solver says otherwise: the fisheye calibration's 100); stop at |dp| < DBL_EPSILON |p| over all parameters.
 // STOP_FORCED is the one policy the two solvers do not share: a step forced with a cost that is not finite (a point behind a
 // camera) ends the stereo solve with DEGENERATE / NONFINITE, while calibration goes on from prev_cost = inf as it always has.
 // Deliberately NOT in here: the reductions in front of the global solve (calibration 8 slices x 128 added serially, stereo the
@@ -73,7 +73,7 @@ DCX_LM_HD void lm_fail(LmState<NG, NR>* st, int status) {
 // One decision.  init: after the first evaluate (cost = the initial cost); else after a trial with its cost, the units' shares
 // of |dp|^2 and |p|^2 (the global parameters' are added here) and whether a trial pose is not finite.
 // -> 0: nothing to commit, 1: commit the trial and continue (or fail), 2: commit and finish OK
-template <int NG, bool STOP_FORCED, int NR>
+template <int NG, bool STOP_FORCED, int NR, int MAX_ITER = kJointMaxIter>
 DCX_LM_HD int lm_decide(LmState<NG, NR>* st, bool init, double cost, double dn, double pn, double units, double points, bool bad) {
     st->result[NG + 3] = units;
     st->result[NG + 4] = points;
@@ -108,7 +108,7 @@ DCX_LM_HD int lm_decide(LmState<NG, NR>* st, bool init, double cost, double dn, 
         st->g[i] = st->g_trial[i];
         bad |= !isfinite(st->g[i]);
     }
-    if (st->iters >= kJointMaxIter || sqrt(dn) < kJointEps * sqrt(pn)) {
+    if (st->iters >= MAX_ITER || sqrt(dn) < kJointEps * sqrt(pn)) {
         int res = kLmOk;
         if (bad || isnan(cost)) res = kLmNonfinite;
         else if (!isfinite(cost)) res = kLmDegenerate;
@@ -172,7 +172,7 @@ __device__ __forceinline__ void lm_trial_pose(const double* yz, const double* dg
 // poses committed where the verdict says so.  used(b): unit b takes part; init_cost(b): its cost after evaluate; trial_sums(b, a):
 // its trial cost, |dp|^2 and |p|^2 added to a[0..2]; points(b): its rows; finish(b): the caller's own outputs of unit b when the
 // solve ends OK (verdict 2).
-template <int NG, bool STOP_FORCED, int NR, class Used, class InitCost, class TrialSums, class Points, class Finish>
+template <int NG, bool STOP_FORCED, int NR, int MAX_ITER = kJointMaxIter, class Used, class InitCost, class TrialSums, class Points, class Finish>
 __device__ __forceinline__ void lm_decide_block(LmState<NG, NR>* st, int batch, int init, double* pose, const double* trial_pose,
                                                 const Used& used, const InitCost& init_cost, const TrialSums& trial_sums,
                                                 const Points& points, const Finish& finish) {
@@ -197,7 +197,7 @@ __device__ __forceinline__ void lm_decide_block(LmState<NG, NR>* st, int batch, 
 #pragma unroll
     for (int j = 0; j < 6; ++j) s[t][j] = a[j];
     block_tree<kLmThreads, 6>(s);
-    if (t == 0) verdict = lm_decide<NG, STOP_FORCED>(st, init != 0, s[0][0], s[0][1], s[0][2], s[0][3], s[0][4], s[0][5] != 0.0);
+    if (t == 0) verdict = lm_decide<NG, STOP_FORCED, NR, MAX_ITER>(st, init != 0, s[0][0], s[0][1], s[0][2], s[0][3], s[0][4], s[0][5] != 0.0);
     __syncthreads();
     if (verdict == 0) return;
     for (int b = t; b < batch; b += kLmThreads) {

@@ -74,10 +74,17 @@ struct IndexedFrame {
     __device__ __forceinline__ void load(int i, double& X, double& Y, double& u, double& v) const { base.load(idx[i], X, Y, u, v); }
 };
 
+// The solver (evaluate, homography, init_pose, solve, row_error2) is a template on the camera class C and touches it through four
+// functions only: has_distortion(cam), undistort(cam, dist, u, v, x, y), project<JAC>(cam, q, u, v, ru, rv, du, dv) and
+// points_inside(f, cam): does every image point of the frame lie inside the camera's model?  The pinhole (PnpCamera,
+// dcx_camera_dev.h) takes every pixel; the fisheye (FisheyeCamera, dcx_fisheye_dev.h) refuses theta >= pi/2.
+template <class F>
+__device__ __forceinline__ bool points_inside(const F&, const PnpCamera&) { return true; }
+
 // Sum over the frame's points of the squared reprojection error at pose p (+inf if a point is not in front of the camera) and,
 // with JAC, of JtJ (21, packed) and Jtr (6).  acc = {cost, JtJ[21], Jtr[6]} on return, identical in every lane.
-template <bool JAC, class F>
-__device__ __forceinline__ void evaluate(const F& f, const PnpCamera& cam, const double* p, double (&acc)[28]) {
+template <bool JAC, class F, class C>
+__device__ __forceinline__ void evaluate(const F& f, const C& cam, const double* p, double (&acc)[28]) {
     double R[9], G[2][9];
     if (JAC) pose_basis(p, R, G);
     else rodrigues(p, R);
@@ -107,8 +114,8 @@ __device__ __forceinline__ void evaluate(const F& f, const PnpCamera& cam, const
 
 // Planar DLT (pnp._homography) of the board points to the (undistorted) image points -> status; H (row major, h33 = 1) maps
 // the centred board points (X - mcx, Y - mcy) to the image points.
-template <class F>
-__device__ __forceinline__ int homography(const F& f, const PnpCamera& cam, bool dist, double* H, double& mc_x, double& mc_y) {
+template <class F, class C>
+__device__ __forceinline__ int homography(const F& f, const C& cam, bool dist, double* H, double& mc_x, double& mc_y) {
     const int lane = threadIdx.x;
     const double n = (double)f.n;
     // centroids of the board points and of the normalised image points
@@ -314,7 +321,8 @@ __device__ __forceinline__ void projective_basis(const double* x, const double* 
 
 // squared reprojection error (px^2) of one row at the pose (R, t) through the full distortion model; +inf if the point is not in
 // front of the camera (evaluate()'s projection, per row)
-__device__ __forceinline__ double row_error2(const double* R, const double* t, const PnpCamera& cam, double mx, double my, double u,
+template <class C>
+__device__ __forceinline__ double row_error2(const double* R, const double* t, const C& cam, double mx, double my, double u,
                                              double v) {
     double q[3], ru, rv;
     board_point(R, t, mx, my, q);
@@ -351,7 +359,8 @@ struct Sample {
 
 // pnp._homography4: the homography through exactly four points in closed form, H = B adj(A) with A, B the projective bases of the
 // centred board points and of the image points.  init_pose() picks this overload for a Sample; no cross-lane step.
-__device__ __forceinline__ int homography(const Sample& q, const PnpCamera&, bool, double* H, double& mc_x, double& mc_y) {
+template <class C>
+__device__ __forceinline__ int homography(const Sample& q, const C&, bool, double* H, double& mc_x, double& mc_y) {
     const double mcx = (q.mx[0] + q.mx[1] + q.mx[2] + q.mx[3]) / 4.0, mcy = (q.my[0] + q.my[1] + q.my[2] + q.my[3]) / 4.0;
     double cx[4], cy[4];
 #pragma unroll
@@ -382,8 +391,8 @@ __device__ __forceinline__ int homography(const Sample& q, const PnpCamera&, boo
 
 // Planar initialisation (pnp._init_pose) -> status; p0 = rvec, tvec.  homography() is found by the frame's type: a frame of exactly
 // four rows may bring its own (dcx_pnp_ransac.hip); everything after it is per lane.
-template <class F>
-__device__ __forceinline__ int init_pose(const F& f, const PnpCamera& cam, bool dist, double* p0) {
+template <class F, class C>
+__device__ __forceinline__ int init_pose(const F& f, const C& cam, bool dist, double* p0) {
     double H[9], mcx, mcy;
     const int st = homography(f, cam, dist, H, mcx, mcy);
     if (st != DCX_PNP_OK) return st;
@@ -411,8 +420,9 @@ __device__ __forceinline__ int init_pose(const F& f, const PnpCamera& cam, bool 
     return DCX_PNP_OK;
 }
 
-template <class F>
-__device__ __forceinline__ int solve(const F& f, const PnpCamera& cam, double* pose) {
+template <class F, class C>
+__device__ __forceinline__ int solve(const F& f, const C& cam, double* pose) {
+    if (!points_inside(f, cam)) return DCX_PNP_DEGENERATE;
     const bool dist = has_distortion(cam);
     double p[6];
     int st = init_pose(f, cam, dist, p);

@@ -1,0 +1,549 @@
+"""The fisheye camera model without OpenCV: what a cv2 user calls ``cv2.fisheye.projectPoints`` / ``undistortPoints`` / ``calibrate``
+/ ``initUndistortRectifyMap`` and ``solvePnP`` on a fisheye camera, on the host and on the GPU (csrc/dcx_fisheye.hip on
+csrc/dcx_fisheye_dev.h).  The pinhole with rational and tangential distortion (``pnp``, ``calib``, ``rectify``) is a polynomial in
+tan(theta) and cannot fit a lens past about 100 degrees of field; this model is a polynomial in theta.
+
+The model (OpenCV's documented ``cv2.fisheye``, skew 0).  For a camera-frame point (X, Y, Z):
+
+    a = X / Z, b = Y / Z, r = sqrt(a^2 + b^2), theta = atan r,
+    theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8),
+    x' = (theta_d / r) a, y' = (theta_d / r) b, u = fx x' + cx, v = fy y' + cy.
+
+Eight intrinsics: fx, fy, cx, cy, k1..k4.  As everywhere in this package a point must have Z > 0, so the field of view is under 180
+degrees (theta in [0, pi/2)).  s = theta_d / r and w = (ds/dr) / r are taken by their series in r^2 below r = ``SMALL_R`` (no
+division by r): a point exactly on the optical axis is a valid input.
+
+The inverse (pixel -> theta) is Newton on theta (1 + k1 theta^2 + ...) - theta_d from theta = theta_d, run to convergence as
+``rectify.undistort_points_newton`` does (``NEWTON_MAX_ITER``, ``NEWTON_EPS``).  A pixel is OUTSIDE (NaN for points,
+``MAP_SENTINEL`` in a map) if Newton does not converge or theta is not in [0, pi/2).
+
+* pose: ``pnp``'s solver (planar DLT on the undistorted points, OpenCV's decomposition, Levenberg-Marquardt with CvLevMarq's
+  rules: 20 accepted steps, |dp| / |p| < FLT_EPSILON) through this model; a frame with a pixel outside the model is DEGENERATE;
+* calibration: joint Levenberg-Marquardt over the 8 intrinsics and every used view's pose with ``calib``'s rules and Schur
+  elimination (``_lm.refine``).  This model has no closed-form start: the principal point starts at ((w-1)/2, (h-1)/2),
+  fx = fy = ``focal0`` or, if that is not > 0, max(w, h) / 2 (at which every in-frame pixel undistorts: sqrt(2) < pi / 2), k = 0,
+  and every view's pose is the fisheye pose solve at that camera.  The start being cruder than Zhang's, the cap is 100 accepted
+  steps, not 30.  On noise-free 640 x 480 scenes of 12 views and 28 corners that start reached the truth for true focal lengths of
+  150, 230 and 400 px in 8 - 35 accepted steps (with max(w, h) / pi the 400 px lens is refused at the init); it rests on those
+  few scenes and nothing more;
+* the undistort + rectify map and the rectified points: ``rectify``'s steps 2 and 3 with the ray through this model; the map has
+  ``rectify``'s fixed-point format, so ``rectify.remap_device`` warps through it unchanged.
+
+The ``*_host`` functions are the readable fp64 definitions and the pins of the kernels; host and device agree to rounding
+(summation order, libm), not bit for bit.  Not here: consensus (RANSAC) variants, fisheye cameras inside the stereo and rig
+solvers, skew, cv2's CALIB_* flags, fields of 180 degrees and more; bit parity with cv2 is not claimed.
+"""
+from __future__ import annotations
+
+import ctypes as _ctypes
+import math
+from typing import Sequence, Tuple
+
+import numpy as np
+
+from . import _dev, _lm, pnp
+from .calib import (CALIB_DEGENERATE, CALIB_EPS, CALIB_NO_VIEWS, CALIB_OK, RESULT_WORDS, CalibResult, _image_size, _total, _views)
+from .corner_pool import pack_keypoints
+from .pnp import (LM_EPS, LM_MAX_ITER, PNP_BAD_ID, PNP_DEGENERATE, PNP_NONFINITE, PNP_OK, PNP_TOO_FEW, POSE_WORDS, _as_cv2,
+                  _bad_id_error, _camera, _cholesky_solve, _init_pose, _pool_ptrs, _right_jacobian, _rodrigues, _skew, object_points,
+                  unpack_poses)
+from .rectify import MAP_BITS, MAP_LIMIT, MAP_SENTINEL, NEWTON_EPS, NEWTON_MAX_ITER, _newcam, _rot, _rp_args
+
+SMALL_R = 1e-4                 # below it theta_d / r and its derivative come from their series
+SMALL_THETA_D = 1e-8           # below it tan(theta) / theta_d = 1 to the last bit
+N_INTR = 8                     # fx, fy, cx, cy, k1, k2, k3, k4
+CALIB_MAX_ITER = 100           # accepted steps of the joint LM
+
+__all__ = ["project_points_host", "undistort_points_host", "solve_pnp_fisheye_host", "solve_pnp_fisheye_host_full",
+           "calibrate_fisheye_host", "calibrate_fisheye_host_full", "undistort_rectify_map_fisheye_host",
+           "rectify_points_fisheye_host", "solve_pnp_fisheye_pool", "solve_pnp_fisheye_batch_device", "solve_pnp_fisheye_device",
+           "calibrate_fisheye_pool", "calibrate_fisheye_device", "workspace_bytes", "undistort_rectify_map_fisheye_device",
+           "rectify_points_fisheye_pool", "SMALL_R", "CALIB_MAX_ITER"]
+
+
+# ------------------------------------------------------------------------------------------------ arguments
+
+def _dist4(dist_coeffs) -> np.ndarray:
+    """-> (k1, k2, k3, k4); None is four zeros."""
+    d = np.zeros(4) if dist_coeffs is None else np.asarray(dist_coeffs, dtype=np.float64).ravel()
+    if d.size != 4:
+        raise ValueError(f"{d.size} distortion coefficients: the fisheye model has 4 (k1, k2, k3, k4)")
+    if not np.isfinite(d).all():
+        raise ValueError("distortion coefficients must be finite")
+    return d.copy()
+
+
+def _camera_args(camera_matrix, dist_coeffs):
+    K, k = _camera(camera_matrix), _dist4(dist_coeffs)
+    return (_ctypes.c_double * 9)(*K.ravel().tolist()), (_ctypes.c_double * 4)(*k.tolist())
+
+
+# ------------------------------------------------------------------------------------------------ the model
+
+def _distort(a, b, k, jac: bool):
+    """Normalised (a, b) (arrays) -> (x', y', tt = theta / r, t2 = theta^2) and with ``jac`` also (dx'/da, dx'/db = dy'/da,
+    dy'/db).  dx'/dk_j = a tt theta^(2j)."""
+    r2 = a * a + b * b
+    r = np.sqrt(r2)
+    th = np.arctan(r)
+    small = r < SMALL_R
+    with np.errstate(all="ignore"):
+        tt = np.where(small, 1.0 + r2 * (-1.0 / 3.0 + r2 * (1.0 / 5.0)), th / r)
+    t2 = th * th
+    s = tt * (1 + t2 * (k[0] + t2 * (k[1] + t2 * (k[2] + t2 * k[3]))))
+    xd, yd = s * a, s * b
+    if not jac:
+        return xd, yd, tt, t2
+    dthd = 1 + t2 * (3 * k[0] + t2 * (5 * k[1] + t2 * (7 * k[2] + t2 * 9 * k[3])))
+    # w = (ds/dr) / r; s = 1 + (k1 - 1/3) r^2 + (1/5 - k1 + k2) r^4 + ...
+    with np.errstate(all="ignore"):
+        w = np.where(small, 2.0 * (k[0] - 1.0 / 3.0) + 4.0 * (1.0 / 5.0 - k[0] + k[1]) * r2, (dthd / (1.0 + r2) - s) / r2)
+    return xd, yd, tt, t2, s + a * a * w, a * b * w, s + b * b * w
+
+
+def _undistort(img: np.ndarray, K: np.ndarray, k: np.ndarray) -> np.ndarray:
+    """Pixels (N, 2) -> the pinhole-normalised points (tan(theta) along the pixel's direction); NaN rows for pixels outside."""
+    xp = (img[:, 0] - K[0, 2]) / K[0, 0]
+    yp = (img[:, 1] - K[1, 2]) / K[1, 1]
+    thd = np.sqrt(xp * xp + yp * yp)
+    th = thd.copy()
+    done = np.zeros(th.shape[0], bool)
+    with np.errstate(all="ignore"):
+        for _ in range(NEWTON_MAX_ITER):
+            t2 = th * th
+            f = th * (1 + t2 * (k[0] + t2 * (k[1] + t2 * (k[2] + t2 * k[3])))) - thd
+            df = 1 + t2 * (3 * k[0] + t2 * (5 * k[1] + t2 * (7 * k[2] + t2 * 9 * k[3])))
+            s = f / df
+            live = ~done
+            th = np.where(live, th - s, th)
+            done |= live & (np.abs(s) < NEWTON_EPS)
+            if done.all():
+                break
+        inside = done & (th >= 0.0) & (th < math.pi / 2)
+        sc = np.where(thd < SMALL_THETA_D, 1.0, np.tan(th) / thd)
+    out = np.stack([xp * sc, yp * sc], 1)
+    out[~inside] = np.nan
+    return out
+
+
+def undistort_points_host(pix, camera_matrix, dist_coeffs) -> np.ndarray:
+    """Pixels (N, 2) -> normalised undistorted coordinates (N, 2) (``cv2.fisheye.undistortPoints`` without R and P): the
+    point tan(theta) from the axis along the pixel's direction.  NaN rows for pixels outside the model."""
+    return _undistort(np.asarray(pix, np.float64).reshape(-1, 2), _camera(camera_matrix), _dist4(dist_coeffs))
+
+
+def _project(obj: np.ndarray, img: np.ndarray, p: np.ndarray, K: np.ndarray, k: np.ndarray, jac: bool, intr: bool = False):
+    """``pnp._project`` through this model: residuals (projected - observed, px) at pose p, their cost, and with ``jac`` the
+    2N x 6 Jacobian (with ``intr`` 2N x 14: the 8 intrinsic columns first).  cost = inf when a point is not in front of the camera."""
+    R = _rodrigues(p[:3])
+    X = obj @ R.T + p[3:]
+    if not (X[:, 2] > 0).all():
+        return None, math.inf, None
+    iz = 1.0 / X[:, 2]
+    a, b = X[:, 0] * iz, X[:, 1] * iz
+    fx, fy = K[0, 0], K[1, 1]
+    d = _distort(a, b, k, jac)
+    xd, yd, tt, t2 = d[:4]
+    res = np.stack([fx * xd + K[0, 2] - img[:, 0], fy * yd + K[1, 2] - img[:, 1]], 1)
+    cost = float((res * res).sum())
+    if not jac:
+        return res, cost, None
+    dxa, dxb, dyb = d[4:]
+    n = obj.shape[0]
+    dab_dX = np.zeros((n, 2, 3))
+    dab_dX[:, 0, 0] = iz
+    dab_dX[:, 0, 2] = -a * iz
+    dab_dX[:, 1, 1] = iz
+    dab_dX[:, 1, 2] = -b * iz
+    duv_dab = np.empty((n, 2, 2))
+    duv_dab[:, 0, 0], duv_dab[:, 0, 1] = fx * dxa, fx * dxb
+    duv_dab[:, 1, 0], duv_dab[:, 1, 1] = fy * dxb, fy * dyb
+    duv_dX = duv_dab @ dab_dX
+    Jr = _right_jacobian(p[:3])
+    dX_dr = -np.einsum("ij,njk->nik", R, np.einsum("nij,jk->nik", np.stack([_skew(o) for o in obj]), Jr))
+    J = np.empty((n, 2, 6))
+    J[:, :, :3] = duv_dX @ dX_dr
+    J[:, :, 3:] = duv_dX
+    if not intr:
+        return res, cost, J.reshape(2 * n, 6)
+    Ji = np.zeros((n, 2, N_INTR))
+    Ji[:, 0, 0] = xd
+    Ji[:, 1, 1] = yd
+    Ji[:, 0, 2] = 1.0
+    Ji[:, 1, 3] = 1.0
+    pw = tt
+    for j in range(4):
+        pw = pw * t2
+        Ji[:, 0, 4 + j], Ji[:, 1, 4 + j] = fx * (a * pw), fy * (b * pw)
+    return res, cost, np.concatenate([Ji.reshape(2 * n, N_INTR), J.reshape(2 * n, 6)], 1)
+
+
+def project_points_host(object_points_, rvec, tvec, camera_matrix, dist_coeffs, jacobian: bool = False):
+    """``cv2.fisheye.projectPoints``: object points (N, 3) at the pose (rvec, tvec) -> pixels (N, 2); NaN rows for points that
+    are not in front of the camera.  With ``jacobian`` (every point must be in front): ``(pixels, J)`` with J (2N, 14) =
+    d(u, v)/d(fx, fy, cx, cy, k1, k2, k3, k4, rvec, tvec)."""
+    K, k = _camera(camera_matrix), _dist4(dist_coeffs)
+    obj = np.asarray(object_points_, np.float64).reshape(-1, 3)
+    p = np.r_[np.asarray(rvec, np.float64).ravel(), np.asarray(tvec, np.float64).ravel()]
+    X = obj @ _rodrigues(p[:3]).T + p[3:]
+    front = X[:, 2] > 0
+    out = np.full((obj.shape[0], 2), np.nan)
+    if jacobian:
+        if not front.all():
+            raise ValueError("a point is not in front of the camera")
+        res, _, J = _project(obj, np.zeros((obj.shape[0], 2)), p, K, k, True, True)
+        return res, J
+    if front.any():
+        out[front] = _project(obj[front], np.zeros((int(front.sum()), 2)), p, K, k, False)[0]
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ pose
+
+def _solve(obj: np.ndarray, img: np.ndarray, K: np.ndarray, k: np.ndarray) -> Tuple[int, np.ndarray]:
+    """``pnp._solve`` through this model: obj (N, 3) board points, img (N, 2) pixels -> (status, pose[8])."""
+    pose = np.zeros(POSE_WORDS)
+    obj = obj.astype(np.float64)
+    img = img.astype(np.float64)
+    mn = _undistort(img, K, k)
+    if not np.isfinite(mn).all():                # a pixel outside the model
+        return PNP_DEGENERATE, pose
+    st, p = _init_pose(obj, mn)
+    if st != PNP_OK:
+        return st, pose
+    res, cost, J = _project(obj, img, p, K, k, True)
+    if not math.isfinite(cost):
+        return PNP_DEGENERATE, pose
+    prev_cost, lg, iters = cost, -3, 0
+    while True:
+        JtJ, Jtr = J.T @ J, J.T @ res.ravel()
+        prev = p
+        while True:
+            A = JtJ.copy()
+            A[np.diag_indices(6)] *= 1.0 + 10.0 ** lg
+            x = _cholesky_solve(A, Jtr)
+            if x is None:
+                return PNP_DEGENERATE, pose
+            p = prev - x
+            _, cost, _ = _project(obj, img, p, K, k, False)
+            if not cost <= prev_cost:
+                lg += 1
+                if lg <= 16:
+                    continue
+            break
+        lg = max(lg - 1, -16)
+        iters += 1
+        if iters >= LM_MAX_ITER or math.sqrt(float((p - prev) @ (p - prev))) < LM_EPS * math.sqrt(float(prev @ prev)):
+            break
+        prev_cost = cost
+        res, cost, J = _project(obj, img, p, K, k, True)
+    if not np.isfinite(p).all() or math.isnan(cost):
+        return PNP_NONFINITE, pose
+    if not math.isfinite(cost):
+        return PNP_DEGENERATE, pose
+    pose[:6] = p
+    pose[6] = math.sqrt(cost / obj.shape[0])
+    pose[7] = iters
+    return PNP_OK, pose
+
+
+def solve_pnp_fisheye_host_full(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs):
+    """``pnp.solve_pnp_host_full`` on a fisheye camera: (status, pose[8] = rvec, tvec, rms px, accepted LM steps)."""
+    K, k = _camera(camera_matrix), _dist4(dist_coeffs)
+    kp = np.asarray(keypoints)
+    if kp.ndim != 2 or kp.shape[0] < 4:
+        return PNP_TOO_FEW, np.zeros(POSE_WORDS)
+    obj = object_points(kp[:, 2], col_count, row_count, square_len)
+    return _solve(obj, kp[:, :2].astype(np.float32), K, k)
+
+
+def solve_pnp_fisheye_host(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs):
+    """``pnp.solve_pnp_host`` on a fisheye camera -> (ret, rvec (3,1), tvec (3,1)); (False, None, None) for fewer than 4 points,
+    a pixel outside the model or input the solver refuses."""
+    return _as_cv2(*solve_pnp_fisheye_host_full(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs))
+
+
+# ------------------------------------------------------------------------------------------------ calibration
+
+def _camera_of(theta: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    return np.array([[theta[0], 0.0, theta[2]], [0.0, theta[1], theta[3]], [0.0, 0.0, 1.0]]), np.array(theta[4:8], np.float64)
+
+
+def _project_full(obj, img, theta, p, jac: bool):
+    K, k = _camera_of(theta)
+    return _project(obj, img, p, K, k, jac, True)
+
+
+def _normal_blocks(views, theta: np.ndarray, poses: np.ndarray):
+    """``calib._normal_blocks`` at 8 intrinsics."""
+    n = len(views)
+    U, W, gb, costs = np.zeros((n, 6, 6)), np.zeros((n, N_INTR, 6)), np.zeros((n, 6)), np.zeros(n)
+    V, ga = np.zeros((N_INTR, N_INTR)), np.zeros(N_INTR)
+    for i, (obj, img) in enumerate(views):
+        res, cost, J = _project_full(obj, img, theta, poses[i], True)
+        if res is None:
+            return None
+        r = res.ravel()
+        A, Bm = J[:, :N_INTR], J[:, N_INTR:]
+        U[i], W[i], gb[i], costs[i] = Bm.T @ Bm, A.T @ Bm, Bm.T @ r, cost
+        V += A.T @ A
+        ga += A.T @ r
+    return U, W, V, ga, gb, costs
+
+
+def _view_costs(views, theta, poses) -> np.ndarray:
+    return np.array([_project_full(obj, img, theta, poses[i], False)[1] for i, (obj, img) in enumerate(views)])
+
+
+def _theta0(w: int, h: int, focal0) -> np.ndarray:
+    f = float(focal0) if focal0 is not None and float(focal0) > 0 else max(w, h) / 2.0
+    if not math.isfinite(f):
+        raise ValueError("focal0 must be finite")
+    return np.array([f, f, (w - 1) * 0.5, (h - 1) * 0.5, 0, 0, 0, 0], np.float64)
+
+
+def _result(status, theta, view_status, poses, vc, counts, iters, attempts) -> CalibResult:
+    B = len(view_status)
+    used = np.flatnonzero(view_status == PNP_OK)
+    K, dist = np.zeros((3, 3)), np.zeros((1, 4))
+    rv, tv, vr = np.zeros((B, 3)), np.zeros((B, 3)), np.zeros(B)
+    rms = 0.0
+    if status == CALIB_OK:
+        K, k = _camera_of(theta)
+        dist = k.reshape(1, 4).copy()
+        rv[used], tv[used] = poses[:, :3], poses[:, 3:]
+        vr[used] = np.sqrt(vc / counts[used])
+        rms = math.sqrt(_total(vc) / int(counts[used].sum()))
+    return CalibResult(int(status), float(rms), K, dist, view_status.astype(np.int32), rv, tv, vr, counts.astype(np.int64),
+                       int(iters), int(attempts), int(used.size), int(counts[used].sum()))
+
+
+def calibrate_fisheye_host_full(object_points_, image_points, image_size, focal0=None) -> CalibResult:
+    """``cv2.fisheye.calibrate``'s role for a planar (z = 0) target, in float64 on the host (module docstring), with every output
+    of ``dcx_fisheye_calibrate_pool``: ``calib.CalibResult`` with ``dist_coeffs`` 1x4 = k1 k2 k3 k4.  A view with fewer than 4
+    points (TOO_FEW) or whose pose solve at the start camera fails (DEGENERATE: also a pixel beyond theta = pi/2 there) is left
+    out and reported in ``view_status``."""
+    w, h = _image_size(image_size)
+    views = _views(object_points_, image_points)
+    counts = np.array([obj.shape[0] for obj, _ in views], np.int64)
+    theta = _theta0(w, h, focal0)
+    K0, k0 = _camera_of(theta)
+    view_status = np.full(len(views), PNP_OK, np.int32)
+    poses0 = np.zeros((len(views), 6))
+    for i, (obj, img) in enumerate(views):
+        if obj.shape[0] < 4:
+            view_status[i] = PNP_TOO_FEW
+            continue
+        view_status[i], pose = _solve(obj, img, K0, k0)
+        poses0[i] = pose[:6]
+    used = np.flatnonzero(view_status == PNP_OK)
+    if not used.size:
+        return _result(CALIB_NO_VIEWS, theta, view_status, None, None, counts, 0, 0)
+    vs = [views[i] for i in used]
+    st, theta, poses, vc, iters, attempts = _lm.refine(theta, poses0[used], lambda t, p: _normal_blocks(vs, t, p),
+                                                       lambda t, p: _view_costs(vs, t, p), _total, False, CALIB_MAX_ITER, CALIB_EPS)
+    return _result(st, theta, view_status, poses, vc, counts, iters, attempts)
+
+
+def calibrate_fisheye_host(object_points_, image_points, image_size, focal0=None):
+    """cv2's 5-tuple ``(rms, K 3x3, D 1x4, rvecs, tvecs)``.  ValueError, as cv2 errors out, on a view that cannot be used or a
+    failed calibration."""
+    r = calibrate_fisheye_host_full(object_points_, image_points, image_size, focal0)
+    bad = np.flatnonzero(r.view_status != PNP_OK)
+    if bad.size:
+        raise ValueError(f"view {int(bad[0])} cannot be used (status {int(r.view_status[bad[0]])})")
+    if r.status != CALIB_OK:
+        raise ValueError(f"calibration failed (status {r.status})")
+    return (r.rms, r.camera_matrix, r.dist_coeffs, tuple(v.reshape(3, 1).copy() for v in r.rvecs),
+            tuple(v.reshape(3, 1).copy() for v in r.tvecs))
+
+
+# ------------------------------------------------------------------------------------------------ map and points
+
+def undistort_rectify_map_fisheye_host(camera_matrix, dist_coeffs, R, P, width: int, height: int, quantised: bool = True) -> np.ndarray:
+    """``rectify.undistort_rectify_map_host`` with the ray through this model (``cv2.fisheye.initUndistortRectifyMap``) -> int32
+    [height, width, 2] (x, y in 1/32 px, MAP_SENTINEL outside: q_z <= 0, a non-finite position or one beyond +-2^15 px); with
+    ``quantised=False`` float64 source pixels, NaN outside."""
+    K, k = _camera(camera_matrix), _dist4(dist_coeffs)
+    Rm, f = _rot(R), _newcam(P, K)
+    width, height = int(width), int(height)
+    if width < 1 or height < 1:
+        raise ValueError("width and height must be >= 1")
+    x = ((np.arange(width, dtype=np.float64) - f[2]) / f[0])[None, :]
+    y = ((np.arange(height, dtype=np.float64) - f[3]) / f[1])[:, None]
+    qx = Rm[0, 0] * x + Rm[1, 0] * y + Rm[2, 0]
+    qy = Rm[0, 1] * x + Rm[1, 1] * y + Rm[2, 1]
+    qz = Rm[0, 2] * x + Rm[1, 2] * y + Rm[2, 2]
+    with np.errstate(all="ignore"):
+        xd, yd, _, _ = _distort(qx / qz, qy / qz, k, False)
+        mx, my = K[0, 0] * xd + K[0, 2], K[1, 1] * yd + K[1, 2]
+        ok = (qz > 0) & (np.abs(mx) <= MAP_LIMIT) & (np.abs(my) <= MAP_LIMIT)          # (NaN and inf compare false)
+    if not quantised:
+        return np.stack([np.where(ok, mx, np.nan), np.where(ok, my, np.nan)], 2)
+    scale = float(1 << MAP_BITS)
+    out = np.full((height, width, 2), MAP_SENTINEL, np.int32)
+    out[..., 0][ok] = np.rint(scale * mx[ok]).astype(np.int32)
+    out[..., 1][ok] = np.rint(scale * my[ok]).astype(np.int32)
+    return out
+
+
+def rectify_points_fisheye_host(pix, camera_matrix, dist_coeffs, R=None, P=None) -> np.ndarray:
+    """``rectify.rectify_points_host`` through this model (``cv2.fisheye.undistortPoints`` with R and P): pixels (N, 2) ->
+    rectified pixels (N, 2), NaN rows for pixels outside the model or with a rotated z <= 0."""
+    K = _camera(camera_matrix)
+    f, Rm = _newcam(P, K), _rot(R)
+    n = undistort_points_host(pix, camera_matrix, dist_coeffs)
+    X = Rm[0, 0] * n[:, 0] + Rm[0, 1] * n[:, 1] + Rm[0, 2]
+    Y = Rm[1, 0] * n[:, 0] + Rm[1, 1] * n[:, 1] + Rm[1, 2]
+    Z = Rm[2, 0] * n[:, 0] + Rm[2, 1] * n[:, 1] + Rm[2, 2]
+    with np.errstate(all="ignore"):
+        out = np.stack([f[0] * (X / Z) + f[2], f[1] * (Y / Z) + f[3]], 1)
+    out[~(Z > 0)] = np.nan
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the device entry points
+
+def solve_pnp_fisheye_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len, camera_matrix,
+                           dist_coeffs, out=None):
+    """``pnp.solve_pnp_pool`` on a fisheye camera (``dcx_fisheye_solve_pnp_pool``): one launch on the current stream, no host sync,
+    nothing allocated when ``out`` is given (capture-safe).  Returns device tensors ``(status int32 [B], pose float64 [B, 8])``."""
+    import torch
+    from . import _lib
+    dev = packed.device
+    ptrs = _pool_ptrs(packed, batch, pool, refined)
+    st, pose = (None, None) if out is None else out
+    msg = f"out must be (int32 [{batch}], float64 [{batch}, 8]) contiguous tensors on {dev}"
+    st = _dev.tensor(st, dev, torch.int32, (batch,), msg, "numel")
+    pose = _dev.tensor(pose, dev, torch.float64, (batch, POSE_WORDS), msg, "numel")
+    cam, dist = _camera_args(camera_matrix, dist_coeffs)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().dcx_fisheye_solve_pnp_pool(*ptrs, int(batch), int(pool), int(col_count), int(row_count),
+                                                         float(square_len), cam, dist, st.data_ptr(), pose.data_ptr(),
+                                                         _lib.current_stream()), "dcx_fisheye_solve_pnp_pool")
+    return st, pose
+
+
+def solve_pnp_fisheye_batch_device(keypoints_list, col_count, row_count, square_len, camera_matrix, dist_coeffs, device="cuda"):
+    """``solve_pnp_fisheye_host`` of every frame of a list of keypoint arrays in one launch -> list of ``(ret, rvec, tvec)``.
+    IndexError if any frame with >= 4 points carries an id outside the board."""
+    import torch
+    from .models._handles import require_cuda
+    dev = require_cuda(device)
+    _camera_args(camera_matrix, dist_coeffs)                  # ValueError before anything is uploaded
+    if len(keypoints_list) == 0:
+        return []
+    packed, b, pool = pack_keypoints(keypoints_list, dev)
+    with torch.cuda.device(dev):
+        st, pose = solve_pnp_fisheye_pool(packed, b, pool, True, col_count, row_count, square_len, camera_matrix, dist_coeffs)
+        st_h, pose_h = st.cpu().numpy(), pose.cpu().numpy()
+    if (st_h == PNP_BAD_ID).any():
+        raise _bad_id_error(col_count, row_count)
+    return unpack_poses(st_h, pose_h)
+
+
+def solve_pnp_fisheye_device(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs, device="cuda"):
+    """``solve_pnp_fisheye_host`` on the GPU -> ``(ret, rvec, tvec)``."""
+    kp = np.asarray(keypoints)
+    if kp.ndim != 2 or kp.shape[0] < 4:
+        _camera_args(camera_matrix, dist_coeffs)
+        return False, None, None
+    return solve_pnp_fisheye_batch_device([kp], col_count, row_count, square_len, camera_matrix, dist_coeffs, device)[0]
+
+
+def workspace_bytes(batch: int) -> int:
+    """Bytes of device workspace ``calibrate_fisheye_pool`` needs."""
+    from . import _lib
+    return int(_lib.lib().dcx_fisheye_calibrate_workspace_bytes(int(batch)))
+
+
+def _calib_fields(res, view_status, pose) -> tuple:
+    """``dcx_fisheye_calibrate_pool``'s 16 doubles and the host copies of its per-view outputs -> ``CalibResult``'s fields."""
+    r = np.array(res[:], np.float64)
+    status = int(r[14])
+    K = np.array([[r[0], 0.0, r[2]], [0.0, r[1], r[3]], [0.0, 0.0, 1.0]]) if status == CALIB_OK else np.zeros((3, 3))
+    return (status, float(r[9]), K, r[4:8].reshape(1, 4).copy(), view_status.astype(np.int32), pose[:, 0:3].copy(),
+            pose[:, 3:6].copy(), pose[:, 6].copy(), pose[:, 7].astype(np.int64), int(r[10]), int(r[11]), int(r[12]), int(r[13]))
+
+
+def calibrate_fisheye_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len, image_size,
+                           focal0=None, workspace=None) -> CalibResult:
+    """``calibrate_fisheye_host_full`` from every frame of a corner pool, read in place (``calib.calibrate_charuco_pool``'s
+    conventions).  ``workspace``: a contiguous device tensor of at least ``workspace_bytes(batch)`` bytes (else one is made).
+    Like ``calibrate_charuco_pool`` the call synchronises the current stream and cannot be captured in a graph."""
+    import torch
+    from . import _lib
+    w, h = _image_size(image_size)
+    f0 = 0.0 if focal0 is None else float(focal0)             # not > 0: the entry takes max(w, h) / 2
+    _theta0(w, h, focal0)                                     # ValueError for an infinite one
+    dev = packed.device
+    ptrs = _pool_ptrs(packed, batch, pool, refined)
+    st = torch.empty((batch,), dtype=torch.int32, device=dev)
+    pose = torch.empty((batch, POSE_WORDS), dtype=torch.float64, device=dev)
+    nbytes = workspace_bytes(batch)
+    ws = _dev.workspace(workspace, dev, nbytes, f"workspace must be a contiguous tensor of at least {nbytes} bytes on {dev}")
+    res = (_ctypes.c_double * RESULT_WORDS)()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().dcx_fisheye_calibrate_pool(*ptrs, int(batch), int(pool), int(col_count), int(row_count),
+                                                         float(square_len), w, h, f0, ws.data_ptr(),
+                                                         ws.numel() * ws.element_size(), st.data_ptr(), pose.data_ptr(), res,
+                                                         _lib.current_stream()), "dcx_fisheye_calibrate_pool")
+        st_h, pose_h = st.cpu().numpy(), pose.cpu().numpy()
+    return CalibResult(*_calib_fields(res, st_h, pose_h))
+
+
+def calibrate_fisheye_device(keypoints_list: Sequence, col_count, row_count, square_len, image_size, focal0=None,
+                             device="cuda") -> CalibResult:
+    """Calibrate a fisheye camera from ``infer_image``-format keypoint arrays ([x, y, id] rows) on the GPU -> ``CalibResult``.
+    IndexError if a frame with >= 4 points carries an id outside the board."""
+    import torch
+    from .models._handles import require_cuda
+    dev = require_cuda(device)
+    _image_size(image_size)
+    if len(keypoints_list) == 0:
+        raise ValueError("no views")
+    packed, b, pool = pack_keypoints(keypoints_list, dev)
+    with torch.cuda.device(dev):
+        r = calibrate_fisheye_pool(packed, b, pool, True, col_count, row_count, square_len, image_size, focal0)
+    if (r.view_status == PNP_BAD_ID).any():
+        raise _bad_id_error(col_count, row_count)
+    return r
+
+
+def undistort_rectify_map_fisheye_device(camera_matrix, dist_coeffs, R, P, width: int, height: int, device="cuda", out=None):
+    """``undistort_rectify_map_fisheye_host`` on the GPU -> int32 device tensor [height, width, 2] (``out``: that tensor,
+    preallocated and contiguous); ``rectify.remap_device`` warps through it.  Enqueued on the current stream; nothing is allocated
+    when ``out`` is given.  Equal to the host map except where 32 m is within rounding of a half-integer, and there by 1."""
+    import torch
+    from . import _lib
+    from .models._handles import require_cuda
+    cam, d = _camera_args(camera_matrix, dist_coeffs)
+    r, p = _rp_args(R, P, _camera(camera_matrix))
+    width, height = int(width), int(height)
+    if width < 1 or height < 1:
+        raise ValueError("width and height must be >= 1")
+    if out is None:
+        out = torch.empty((height, width, 2), dtype=torch.int32, device=require_cuda(device))
+    if out.dtype != torch.int32 or tuple(out.shape) != (height, width, 2) or not out.is_contiguous() or out.device.type != "cuda":
+        raise ValueError(f"out must be a contiguous int32 [{height}, {width}, 2] GPU tensor")
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.lib().dcx_fisheye_undistort_rectify_map(cam, d, r, p, width, height, out.data_ptr(), _lib.current_stream()),
+                   "dcx_fisheye_undistort_rectify_map")
+    return out
+
+
+def rectify_points_fisheye_pool(packed, batch: int, pool: int, refined: bool, camera_matrix, dist_coeffs, R=None, P=None, out=None):
+    """``rectify.rectify_points_pool`` through this model: every slot of a corner pool in rectified coordinates -> float64 device
+    tensor [pool, 2] by slot; NaN where ``rectify_points_fisheye_host`` gives NaN.  Capture-safe when ``out`` is given."""
+    import torch
+    from . import _lib
+    dev = packed.device
+    batch, pool = int(batch), int(pool)
+    rows_p, xy_p = _pool_ptrs(packed, batch, pool, refined)[2:]
+    cam, d = _camera_args(camera_matrix, dist_coeffs)
+    r, p = _rp_args(R, P, _camera(camera_matrix))
+    out = _dev.tensor(out, dev, torch.float64, (pool, 2), f"out must be a contiguous float64 [{pool}, 2] tensor on {dev}", "numel")
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().dcx_fisheye_rectify_points_pool(rows_p, xy_p, pool, cam, d, r, p, out.data_ptr() if pool else None,
+                                                              _lib.current_stream()), "dcx_fisheye_rectify_points_pool")
+    return out

@@ -479,6 +479,55 @@ int dcx_rectify_points_pool(const int32_t* d_rows, const float* d_xy /* NULL = u
 int dcx_remap_u8(const uint8_t* d_src, long frame_stride, int pitch, int src_h, int src_w, int channels /* 1 or 3 */,
                  const int32_t* d_map, int out_h, int out_w, int batch, int border, uint8_t* d_out, void* stream);
 
+/* ---- the fisheye camera model (cv2.fisheye's documented model, skew 0): pose, calibration, undistortion ----------------------
+ * For a camera-frame point (X, Y, Z): a = X/Z, b = Y/Z, r = sqrt(a^2 + b^2), theta = atan r,
+ * theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8), x' = (theta_d / r) a, y' = (theta_d / r) b,
+ * u = fx x' + cx, v = fy y' + cy.  As everywhere here a point must have Z > 0: the field of view is under 180 degrees.  theta_d / r
+ * and its derivative come from their series below r = 1e-4, so a point on the optical axis is a valid input.  The inverse is
+ * Newton on theta (1 + k1 theta^2 + ...) - theta_d from theta = theta_d until a step is below 1e-15, at most 20 steps; a pixel is
+ * OUTSIDE if Newton does not converge or theta is not in [0, pi/2).  h_camera9 as for dcx_solve_pnp_pool (no skew, finite, non-zero
+ * focal lengths; DCX_E_ARG otherwise); h_dist4 = k1, k2, k3, k4 (finite), NULL = zeros.  All fp64; deepcharuco_amd/fisheye.py
+ * restates every step and csrc/dcx_fisheye_dev.h holds the model.
+ *
+ * dcx_fisheye_solve_pnp_pool: dcx_solve_pnp_pool with this camera: one wavefront per frame, the same pool, checks, DCX_PNP_* codes
+ * and [B][8] pose words; a frame with a pixel outside the model is DCX_PNP_DEGENERATE.  One launch on `stream`: no allocation, no
+ * synchronisation, capturable in a hipGraph.
+ *
+ * dcx_fisheye_calibrate_pool (cv2.fisheye.calibrate's role, planar target): pool, per-view checks, d_view_status, d_pose and the
+ * DCX_CALIB_* codes as for dcx_calibrate_pool.  Start: principal point ((w-1)/2, (h-1)/2); fx = fy = focal0, or max(w, h) / 2 if
+ * focal0 is not > 0 (+inf: DCX_E_ARG); k = 0; every view's pose by dcx_fisheye_solve_pnp_pool's solve at that camera (a view it
+ * refuses is left out and reported).  Then joint Levenberg-Marquardt over fx, fy, cx, cy, k1..k4 and every used view's pose with
+ * dcx_calibrate_pool's rules and block elimination, at most 100 accepted steps, stop at |dp|/|p| < DBL_EPSILON.
+ * h_result f64 [16] = fx, fy, cx, cy, k1, k2, k3, k4, 0, rms, accepted LM steps, attempts, views used, points used, DCX_CALIB_*
+ * status, 0; the first ten are zero unless DCX_CALIB_OK.  d_workspace: dcx_fisheye_calibrate_workspace_bytes(batch) bytes of
+ * device memory (DCX_E_WS if smaller); nothing is allocated.  Like dcx_calibrate_pool this entry point SYNCHRONISES `stream` (the
+ * LM loop runs on the host and reads a state word after every attempt) and cannot be captured in a graph.  No atomics: two calls
+ * on the same input give the same bits.
+ *
+ * dcx_fisheye_undistort_rectify_map / dcx_fisheye_rectify_points_pool: dcx_undistort_rectify_map / dcx_rectify_points_pool with
+ * the ray through this model (cv2.fisheye.initUndistortRectifyMap / undistortPoints): the same R and P, the same int32 map in
+ * 1/32 px with INT32_MIN for outside (q_z <= 0, a source position that is not finite or beyond +-32768 px), which dcx_remap_u8
+ * reads unchanged; the same f64 [pool][2] output, NaN for a pixel outside the model or a rotated z <= 0.                      */
+int dcx_fisheye_solve_pnp_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows,
+                               const float* d_xy /* NULL = use integer rows x,y */, int batch, int pool,
+                               int col_count, int row_count, double square_len,
+                               const double* h_camera9, const double* h_dist4 /* NULL = zeros */,
+                               int32_t* d_status, double* d_pose /* [B][8] */, void* stream);
+size_t dcx_fisheye_calibrate_workspace_bytes(int batch);
+int dcx_fisheye_calibrate_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows,
+                               const float* d_xy /* NULL = use integer rows x,y */, int batch, int pool,
+                               int col_count, int row_count, double square_len, int image_width, int image_height,
+                               double focal0 /* not > 0: max(w, h) / 2 */, void* d_workspace, size_t workspace_bytes,
+                               int32_t* d_view_status /* [B] DCX_PNP_* */, double* d_pose /* [B][8] */,
+                               double* h_result /* [16] */, void* stream);
+int dcx_fisheye_undistort_rectify_map(const double* h_camera9, const double* h_dist4,
+                                      const double* h_R9 /* NULL = identity */, const double* h_P12 /* NULL = K */,
+                                      int width, int height, int32_t* d_map /* [height][width][2] */, void* stream);
+int dcx_fisheye_rectify_points_pool(const int32_t* d_rows, const float* d_xy /* NULL = use integer rows x,y */, int pool,
+                                    const double* h_camera9, const double* h_dist4,
+                                    const double* h_R9 /* NULL = identity */, const double* h_P12 /* NULL = K */,
+                                    double* d_out /* [pool][2] */, void* stream);
+
 /* ---- image resizing (cv2.resize): what stands in front of the detector ---------------------------------------------------------
  * dcx_resize_u8: batch frames d_src (u8, `channels` = 1 or 3 interleaved, rows `pitch` bytes apart, frames `frame_stride` bytes
  * apart, any base address: a cropped view costs nothing) -> d_out u8 [batch][out_h][out_w][channels], dense.  Channels are
