@@ -87,9 +87,14 @@ SIGNATURES = {
     "dcx_stereo_calibrate_pool": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), _i,
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), _i, _vp, _sz, _vp, _vp, _vp,
                                       C.POINTER(C.c_double), _vp]),
+    "dcx_stereo_calibrate_models_pool": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, C.c_double, C.POINTER(C.c_double),
+                                             C.POINTER(C.c_double), _i, C.POINTER(C.c_double), C.POINTER(C.c_double), _i, _i, _i,
+                                             _vp, _sz, _vp, _vp, _vp, C.POINTER(C.c_double), _vp]),
     "dcx_rig_calibrate_workspace_bytes": (_sz, [_i, _i, C.POINTER(C.c_int)]),
     "dcx_rig_calibrate_pool": (_i, [_i, _vp, _i, _i, _i, C.c_double, _vp, _sz, _vp, _vp, _vp, C.POINTER(C.c_int32),
                                    C.POINTER(C.c_double), _vp]),
+    "dcx_rig_calibrate_models_pool": (_i, [_i, _vp, C.POINTER(C.c_int), _i, _i, _i, C.c_double, _vp, _sz, _vp, _vp, _vp,
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_double), _vp]),
     "dcx_undistort_rectify_map": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double), _i, C.POINTER(C.c_double),
                                       C.POINTER(C.c_double), _i, _i, _vp, _vp]),
     "dcx_rectify_points_pool": (_i, [_vp, _vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), _i, C.POINTER(C.c_double),
@@ -97,6 +102,8 @@ SIGNATURES = {
     "dcx_remap_u8": (_i, [_vp, _l, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "dcx_fisheye_solve_pnp_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        _vp, _vp, _vp]),
+    "dcx_fisheye_solve_pnp_ransac_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, C.POINTER(C.c_double),
+                                              C.POINTER(C.c_double), _i, C.c_double, _i, C.c_uint, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "dcx_fisheye_calibrate_workspace_bytes": (_sz, [_i]),
     "dcx_fisheye_calibrate_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _i, _i, C.c_double, _vp, _sz, _vp, _vp,
                                        C.POINTER(C.c_double), _vp]),

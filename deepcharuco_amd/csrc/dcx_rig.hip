@@ -36,6 +36,8 @@
 //   trial           grid (timestamp, camera): dP_t = z - sum_c Y_c dX_c (cameras ascending), the view's trial cost; camera 0's block
 //                   also writes the trial pose and the timestamp's share of |dp|^2 and |p|^2
 //   decide          (one workgroup) lm_decide_block with STOP_FORCED
+// A rig with a fisheye camera in it (dcx_rig_calibrate_models_pool) runs init_views, evaluate and trial as their *_mixed_kernel
+// forms on a table of AnyCamera (dcx_stereo_dev.h); the other launches never see a camera and are the same.
 // The LM loop runs on the host (lm_run): the call synchronises its stream and cannot be captured in a graph.  Every sum has a fixed
 // order (no atomics): two calls on the same input give the same bits.  No device memory is allocated.
 // The state is LmState<42, 48> whatever C is: the parameters past n stay zero, which adds exact zeros to lm_decide's two norms.
@@ -63,10 +65,16 @@ using RigState = LmState<kMaxG, kResWords>;
 constexpr int kState = 1536;             // bytes reserved for RigState
 static_assert(sizeof(RigState) <= kState, "state");
 
-struct RigCams {
+struct RigCams {                         // every camera a pinhole: what dcx_rig_calibrate_pool has always passed
     MaskedPool pl[kMaxCams];
     PnpCamera cam[kMaxCams];
 };
+
+struct MixedCams {                       // a model tag per camera (dcx_rig_calibrate_models_pool with a fisheye camera in the rig)
+    MaskedPool pl[kMaxCams];
+    AnyCamera cam[kMaxCams];
+};
+static_assert(sizeof(MixedCams) <= 2048, "kernel arguments");
 
 struct Tree {
     int parent[kMaxCams];                // -1 for camera 0
@@ -153,6 +161,7 @@ __device__ __forceinline__ void unpkn(int n, int e, int& a, int& b) {
 
 // ---------------------------------------------------------------------------------------------------------------- init
 
+// (restated on MixedCams as rig_init_views_mixed_kernel below: a change here is a change there)
 __global__ __launch_bounds__(kLanes) void rig_init_views_kernel(RigCams cams, int32_t* __restrict__ status,
                                                                 double* __restrict__ view_info, Ws ws) {
     const int t = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
@@ -317,6 +326,7 @@ __device__ __forceinline__ void camera_x(const double* g, int c, double* x) {
     for (int i = 0; i < 6; ++i) x[i] = c ? g[6 * (c - 1) + i] : 0.0;
 }
 
+// (restated on MixedCams as rig_evaluate_mixed_kernel below: a change here is a change there)
 __global__ __launch_bounds__(kLanes) void rig_evaluate_kernel(RigCams cams, const int32_t* __restrict__ status, Ws ws) {
     __shared__ double sj[2 * kLanes][kLdsStride];
     const int t = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
@@ -533,6 +543,7 @@ __global__ __launch_bounds__(kSlices * kLanes) void rig_reduce_solve_kernel(int 
     }
 }
 
+// (restated on MixedCams as rig_trial_mixed_kernel below: a change here is a change there)
 __global__ __launch_bounds__(kLanes) void rig_trial_kernel(RigCams cams, const int32_t* __restrict__ status, Ws ws) {
     const int t = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
     if (ws.st->code == kFinished || !ws.used[t]) return;
@@ -610,28 +621,117 @@ __global__ __launch_bounds__(kRedThreads) void rig_decide_kernel(int batch, int 
         });
 }
 
-}  // namespace
+// ---------------------------------------------------------------------------------------------------------------- mixed rigs
 
-extern "C" size_t dcx_rig_calibrate_workspace_bytes(int n_cams, int batch, const int* h_pools) {
-    if (!sizes_ok(n_cams, batch, h_pools)) return 0;
-    return ws_layout(nullptr, n_cams, batch, h_pools, nullptr);
+// init_views, evaluate and trial, the three kernels that meet a camera, on a table with model tags.  They restate the all-pinhole
+// kernels above line for line around with_camera(); a block works on camera blockIdx.y alone, so its branch on the model is uniform.
+// They are kernels of their own, after every other kernel of this file, and not one body shared with the kernels above: compiled
+// through a shared body the all-pinhole kernels come out scheduled differently, and they are to stay the code they were.
+__global__ __launch_bounds__(kLanes) void rig_init_views_mixed_kernel(MixedCams cams, int32_t* __restrict__ status,
+                                                                      double* __restrict__ view_info, Ws ws) {
+    const int t = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
+    double out[8];
+    int kept;
+    const int st = with_camera(cams.cam[c], [&](const auto& cam) { return view_solve(cams.pl[c], cam, t, ws.idx[c], ws.ident, out, kept); });
+    if (lane == 0) {
+        const long long v = (long long)t * ws.C + c;
+        status[v] = st;
+        view_info[2 * v] = 0.0;
+        view_info[2 * v + 1] = (double)kept;
+        ws.count[v] = kept;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) ws.vpose[6 * v + i] = st == DCX_PNP_OK ? out[i] : 0.0;
+    }
 }
 
-extern "C" int dcx_rig_calibrate_pool(int n_cams, const DcxRigCamera* h_cams, int batch, int col_count, int row_count,
-                                      double square_len, void* d_workspace, size_t workspace_bytes, int32_t* d_view_status,
-                                      double* d_pose, double* d_view_info, int32_t* h_parents, double* h_result, void* stream) {
-    if (n_cams < 2 || n_cams > kMaxCams || !h_cams) return DCX_E_ARG;
-    const int C = n_cams, n = 6 * (C - 1);
-    RigCams cams{};
-    int pools[kMaxCams];
-    for (int c = 0; c < C; ++c) {
-        const DcxRigCamera& h = h_cams[c];
-        cams.pl[c].mask = h.d_mask;
-        if (!corner_pool(h.d_counts, h.d_starts, h.d_rows, h.d_xy, batch, h.pool, col_count, row_count, square_len, cams.pl[c].p))
-            return DCX_E_ARG;
-        if (!pnp_camera(h.camera9, h.dist, h.n_dist, cams.cam[c])) return DCX_E_ARG;
-        pools[c] = h.pool;
+__global__ __launch_bounds__(kLanes) void rig_evaluate_mixed_kernel(MixedCams cams, const int32_t* __restrict__ status, Ws ws) {
+    __shared__ double sj[2 * kLanes][kLdsStride];
+    const int t = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
+    if (ws.st->code != kNextEvaluate || !ws.used[t] || !usable(status, ws, t, c)) return;
+    double x[6], p[6];
+    camera_x(ws.st->g, c, x);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) p[i] = ws.pose[(long long)t * 6 + i];
+    PairBasis B;
+    pair_basis<true>(x, p, B);
+    int ea[2], eb[2];
+    lane_entries<13, 2>(lane, ea, eb);
+    double acc[2] = {0, 0};
+    bool behind = false;
+    const IndexedFrame f = view_frame(cams.pl[c], ws, t, c);
+    with_camera(cams.cam[c], [&](const auto& cam) {
+        if (c) accumulate_view<true>(f, cam, B, sj, ea, eb, acc, behind);
+        else accumulate_view<false>(f, cam, B, sj, ea, eb, acc, behind);
+        return 0;
+    });
+    const bool inf = __any(behind);
+    double* m = ws.m + ((long long)t * ws.C + c) * kEntries;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int e = lane + kLanes * q;
+        if (e < kEntries) m[e] = (e == kCost && inf) ? INFINITY : acc[q];
     }
+}
+
+__global__ __launch_bounds__(kLanes) void rig_trial_mixed_kernel(MixedCams cams, const int32_t* __restrict__ status, Ws ws) {
+    const int t = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
+    if (ws.st->code == kFinished || !ws.used[t]) return;
+    const int C = ws.C;
+    // the timestamp's trial pose p = pose - (z - sum_c Y_c dX_c), the same in every block of the timestamp
+    double p[6], dn = 0.0, pn = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        double s = ws.z[(long long)t * 6 + k];
+        for (int cc = 1; cc < C; ++cc) {         // (a camera that is not there: schur left Y_c = 0, which takes off exact zeros)
+            const double* y = ws.y + ((long long)t * (C - 1) + cc - 1) * 36 + k * 6;
+#pragma unroll
+            for (int j = 0; j < 6; ++j) s -= y[j] * ws.st->dg[6 * (cc - 1) + j];
+        }
+        const double p0 = ws.pose[(long long)t * 6 + k];
+        p[k] = p0 - s;
+        dn += (p[k] - p0) * (p[k] - p0);
+        pn += p0 * p0;
+    }
+    double cost = 0.0;
+    if (usable(status, ws, t, c)) {
+        double x[6];
+        camera_x(ws.st->g_trial, c, x);
+        PairBasis B;
+        pair_basis<false>(x, p, B);
+        const IndexedFrame f = view_frame(cams.pl[c], ws, t, c);
+        cost = with_camera(cams.cam[c], [&](const auto& cam) { return c ? view_cost<true>(f, cam, B) : view_cost<false>(f, cam, B); });
+    }
+    if (lane == 0) {
+        double* tr = ws.trial + (long long)t * (C + 2);
+        tr[c] = cost;
+        if (c == 0) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) ws.trial_pose[(long long)t * 6 + k] = p[k];
+            tr[C] = dn;
+            tr[C + 1] = pn;
+        }
+    }
+}
+
+// The kernels of a camera table
+template <class CAMS> struct Kernels;
+template <> struct Kernels<RigCams> {
+    static constexpr auto init_views = rig_init_views_kernel;
+    static constexpr auto evaluate = rig_evaluate_kernel;
+    static constexpr auto trial = rig_trial_kernel;
+};
+template <> struct Kernels<MixedCams> {
+    static constexpr auto init_views = rig_init_views_mixed_kernel;
+    static constexpr auto evaluate = rig_evaluate_mixed_kernel;
+    static constexpr auto trial = rig_trial_mixed_kernel;
+};
+
+// Everything after the camera table is made: the entry points' common body.
+template <class CAMS>
+int rig_calibrate(const CAMS& cams, const int* pools, int C, int batch, void* d_workspace, size_t workspace_bytes,
+                  int32_t* d_view_status, double* d_pose, double* d_view_info, int32_t* h_parents, double* h_result, void* stream) {
+    using K = Kernels<CAMS>;
+    const int n = 6 * (C - 1);
     if (!d_workspace || !d_view_status || !d_pose || !d_view_info || !h_parents || !h_result || ((uintptr_t)d_workspace & 7))
         return DCX_E_ARG;
     if (workspace_bytes < ws_layout(nullptr, C, batch, pools, nullptr)) return DCX_E_WS;
@@ -650,7 +750,7 @@ extern "C" int dcx_rig_calibrate_pool(int n_cams, const DcxRigCamera* h_cams, in
         else if (pools[c] > n_ident) n_ident = pools[c];
     }
     if (n_ident > 0) hipLaunchKernelGGL(stereo_ident_kernel, dim3((unsigned)((n_ident + 255) / 256)), dim3(256), 0, s, n_ident, ws.ident);
-    hipLaunchKernelGGL(rig_init_views_kernel, views, wave, 0, s, cams, d_view_status, d_view_info, ws);
+    hipLaunchKernelGGL(K::init_views, views, wave, 0, s, cams, d_view_status, d_view_info, ws);
     hipLaunchKernelGGL(rig_stamps_kernel, per_lane, wave, 0, s, batch, d_view_status, d_pose, ws);
     DCX_CHECK_HIP(hipGetLastError());
 
@@ -725,15 +825,15 @@ extern "C" int dcx_rig_calibrate_pool(int n_cams, const DcxRigCamera* h_cams, in
         }
     }
     hipLaunchKernelGGL(rig_start_kernel, one, wave, 0, s, med, tree, n_stamps, (double)points, batch, d_view_status, ws);
-    hipLaunchKernelGGL(rig_evaluate_kernel, views, wave, 0, s, cams, d_view_status, ws);
+    hipLaunchKernelGGL(K::evaluate, views, wave, 0, s, cams, d_view_status, ws);
     hipLaunchKernelGGL(rig_decide_kernel, one, red, 0, s, batch, 1, d_view_status, d_pose, d_view_info, ws);
     DCX_CHECK_HIP(hipGetLastError());
     DCX_CHECK_HIP(lm_run(s, &ws.st->code, kJointMaxIter, [&](bool evaluate) {
-        if (evaluate) hipLaunchKernelGGL(rig_evaluate_kernel, views, wave, 0, s, cams, d_view_status, ws);
+        if (evaluate) hipLaunchKernelGGL(K::evaluate, views, wave, 0, s, cams, d_view_status, ws);
         hipLaunchKernelGGL(rig_schur_kernel, stamps, wave, 0, s, d_view_status, ws);
         hipLaunchKernelGGL(rig_reduce_kernel, blocks, dim3(kReduceThreads), 0, s, batch, d_view_status, ws);
         hipLaunchKernelGGL(rig_reduce_solve_kernel, one, solve_threads, 0, s, chunks, ws);
-        hipLaunchKernelGGL(rig_trial_kernel, views, wave, 0, s, cams, d_view_status, ws);
+        hipLaunchKernelGGL(K::trial, views, wave, 0, s, cams, d_view_status, ws);
         hipLaunchKernelGGL(rig_decide_kernel, one, red, 0, s, batch, 0, d_view_status, d_pose, d_view_info, ws);
     }));
     double res[kResWords];
@@ -747,4 +847,63 @@ extern "C" int dcx_rig_calibrate_pool(int n_cams, const DcxRigCamera* h_cams, in
     h_result[5] = res[kMaxG + 5];
     for (int i = 0; i < n; ++i) h_result[8 + i] = res[i];
     return 0;
+}
+
+// The pools and, per camera, what `camera` makes of its model fields -> false if anything is refused
+template <class CAMS, class F>
+bool camera_table(int n_cams, const DcxRigCamera* h_cams, int batch, int col_count, int row_count, double square_len, CAMS& cams,
+                  int* pools, F&& camera) {
+    if (n_cams < 2 || n_cams > kMaxCams || !h_cams) return false;
+    for (int c = 0; c < n_cams; ++c) {
+        const DcxRigCamera& h = h_cams[c];
+        cams.pl[c].mask = h.d_mask;
+        if (!corner_pool(h.d_counts, h.d_starts, h.d_rows, h.d_xy, batch, h.pool, col_count, row_count, square_len, cams.pl[c].p))
+            return false;
+        if (!camera(c, h, cams.cam[c])) return false;
+        pools[c] = h.pool;
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" size_t dcx_rig_calibrate_workspace_bytes(int n_cams, int batch, const int* h_pools) {
+    if (!sizes_ok(n_cams, batch, h_pools)) return 0;
+    return ws_layout(nullptr, n_cams, batch, h_pools, nullptr);
+}
+
+extern "C" int dcx_rig_calibrate_pool(int n_cams, const DcxRigCamera* h_cams, int batch, int col_count, int row_count,
+                                      double square_len, void* d_workspace, size_t workspace_bytes, int32_t* d_view_status,
+                                      double* d_pose, double* d_view_info, int32_t* h_parents, double* h_result, void* stream) {
+    RigCams cams{};
+    int pools[kMaxCams];
+    if (!camera_table(n_cams, h_cams, batch, col_count, row_count, square_len, cams, pools,
+                      [](int, const DcxRigCamera& h, PnpCamera& cam) { return pnp_camera(h.camera9, h.dist, h.n_dist, cam); }))
+        return DCX_E_ARG;
+    return rig_calibrate(cams, pools, n_cams, batch, d_workspace, workspace_bytes, d_view_status, d_pose, d_view_info, h_parents,
+                         h_result, stream);
+}
+
+// h_models NULL or all DCX_CAMERA_PINHOLE: dcx_rig_calibrate_pool, the same kernels on the same table.
+extern "C" int dcx_rig_calibrate_models_pool(int n_cams, const DcxRigCamera* h_cams, const int* h_models, int batch, int col_count,
+                                             int row_count, double square_len, void* d_workspace, size_t workspace_bytes,
+                                             int32_t* d_view_status, double* d_pose, double* d_view_info, int32_t* h_parents,
+                                             double* h_result, void* stream) {
+    bool mixed = false;
+    if (h_models && n_cams >= 2 && n_cams <= kMaxCams)
+        for (int c = 0; c < n_cams; ++c) {
+            if (h_models[c] != DCX_CAMERA_PINHOLE && h_models[c] != DCX_CAMERA_FISHEYE) return DCX_E_ARG;
+            mixed |= h_models[c] == DCX_CAMERA_FISHEYE;
+        }
+    if (!mixed)
+        return dcx_rig_calibrate_pool(n_cams, h_cams, batch, col_count, row_count, square_len, d_workspace, workspace_bytes,
+                                      d_view_status, d_pose, d_view_info, h_parents, h_result, stream);
+    MixedCams cams{};
+    int pools[kMaxCams];
+    if (!camera_table(n_cams, h_cams, batch, col_count, row_count, square_len, cams, pools, [&](int c, const DcxRigCamera& h, AnyCamera& cam) {
+            return any_camera(h_models[c], h.camera9, h.dist, h.n_dist, cam);
+        }))
+        return DCX_E_ARG;
+    return rig_calibrate(cams, pools, n_cams, batch, d_workspace, workspace_bytes, d_view_status, d_pose, d_view_info, h_parents,
+                         h_result, stream);
 }

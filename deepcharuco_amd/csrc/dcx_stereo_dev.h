@@ -6,14 +6,43 @@
 //   PairBasis, pair_basis, stereo_row            one row of a camera behind a rig transform: residual and its two lines of
 //                                                [J_X (6) | J_P (6)]; the reference camera's rows (SECOND = false) have J_X = 0
 //   accumulate_view, view_cost                   a view's rows added to its packed 13 x 13 / its trial cost
+//   AnyCamera, any_camera, with_camera           a camera of either model behind a tag, for rigs whose cameras differ
+// view_solve, stereo_row, accumulate_view and view_cost are templates on the camera class, as dcx_pnp_dev.h's solver is: PnpCamera
+// (dcx_camera_dev.h) or FisheyeCamera (dcx_fisheye_dev.h).
 // Everything is force-inlined and has internal linkage, so each translation unit compiles its own copy.
 #pragma once
+#include "dcx_fisheye_dev.h"
 #include "dcx_pnp_dev.h"
 #include "dcx_lm_dev.h"
 
 namespace {
 
 constexpr int kLdsStride = 13;           // [J_X (6) | J_P (6) | r]
+
+// A camera of either model (DCX_CAMERA_*).  The tag is the same for every lane of a workgroup that works on one camera, so the
+// branch in with_camera() is uniform.
+struct AnyCamera {
+    int model;
+    union {
+        PnpCamera pin;
+        FisheyeCamera fish;
+    };
+};
+
+// DcxRigCamera's camera fields under a model tag -> the kernel argument; false if refused: an unknown tag, what pnp_camera() /
+// fisheye_camera() refuse, and for a fisheye camera any n_dist but 4 or 0 (k1..k4 in h_dist[0..3], or zeros)
+inline bool any_camera(int model, const double* h_camera9, const double* h_dist, int n_dist, AnyCamera& cam) {
+    cam.model = model;
+    if (model == DCX_CAMERA_PINHOLE) return pnp_camera(h_camera9, h_dist, n_dist, cam.pin);
+    if (model != DCX_CAMERA_FISHEYE || !(n_dist == 0 || n_dist == 4) || (n_dist > 0 && !h_dist)) return false;
+    return fisheye_camera(h_camera9, n_dist ? h_dist : nullptr, cam.fish);
+}
+
+// f(the camera as its own class) -> what f returns
+template <class F>
+__device__ __forceinline__ auto with_camera(const AnyCamera& cam, F&& f) {
+    return cam.model == DCX_CAMERA_FISHEYE ? f(cam.fish) : f(cam.pin);
+}
 
 struct MaskedPool {                      // one camera's pool and the optional mask that rides beside it
     CornerPool p;
@@ -34,7 +63,8 @@ __global__ __launch_bounds__(256) void stereo_ident_kernel(int n, int32_t* __res
 // the index list at the view's own slots of `lists`; solve() over an IndexedFrame either way, so a NULL mask and a mask of ones run
 // the same instructions on the same values.  -> DCX_PNP_*; out = solve()'s pose words (zero unless it ran), kept = the rows after
 // the mask (0 for a view that is empty or cut by the pool).  One wave, the whole block.
-__device__ __forceinline__ int view_solve(const MaskedPool& pl, const PnpCamera& cam, int t, int32_t* lists, const int32_t* ident,
+template <class CAM>
+__device__ __forceinline__ int view_solve(const MaskedPool& pl, const CAM& cam, int t, int32_t* lists, const int32_t* ident,
                                           double (&out)[8], int& kept) {
     const int lane = threadIdx.x;
     const int n = pl.p.counts[t], s0 = pl.p.starts[t];
@@ -116,8 +146,8 @@ __device__ __forceinline__ void pair_basis(const double* x, const double* p, Pai
 // One row of camera SECOND's view at (X, P) -> residual (ru, rv); with JAC its two rows of [J_X (6) | J_P (6)]: the header's
 // project() and pose_columns() on the point q = R_P m + t_P (camera 0) or R_X q + T_X (camera 1).  false if the
 // point is not in front of the camera.
-template <bool JAC, bool SECOND>
-__device__ __forceinline__ bool stereo_row(const PnpCamera& cam, const PairBasis& B, double mx, double my, double u, double v,
+template <bool JAC, bool SECOND, class CAM>
+__device__ __forceinline__ bool stereo_row(const CAM& cam, const PairBasis& B, double mx, double my, double u, double v,
                                            double& ru, double& rv, double* ju, double* jv) {
     double q0[3], q[3], du[3], dv[3];
     board_point(B.RP, B.tP, mx, my, q0);
@@ -159,8 +189,8 @@ __device__ __forceinline__ bool stereo_row(const PnpCamera& cam, const PairBasis
 }
 
 // One view's rows added to the pair's 91 entries: 64 rows at a time through LDS, every lane its two entries in row order.
-template <bool SECOND>
-__device__ __forceinline__ void accumulate_view(const IndexedFrame& f, const PnpCamera& cam, const PairBasis& B,
+template <bool SECOND, class CAM>
+__device__ __forceinline__ void accumulate_view(const IndexedFrame& f, const CAM& cam, const PairBasis& B,
                                                 double (*sj)[kLdsStride], const int* ea, const int* eb, double* acc, bool& behind) {
     accumulate_rows<13, 2, kLdsStride>(f.n, [&](int i, double* ju, double* jv) {
         double mx, my, u, v;
@@ -169,8 +199,8 @@ __device__ __forceinline__ void accumulate_view(const IndexedFrame& f, const Pnp
     }, sj, ea, eb, acc, behind);
 }
 
-template <bool SECOND>
-__device__ __forceinline__ double view_cost(const IndexedFrame& f, const PnpCamera& cam, const PairBasis& B) {
+template <bool SECOND, class CAM>
+__device__ __forceinline__ double view_cost(const IndexedFrame& f, const CAM& cam, const PairBasis& B) {
     double c[1] = {0.0};
     for (int i = threadIdx.x; i < f.n; i += kLanes) {
         double mx, my, u, v, ru, rv;

@@ -30,8 +30,11 @@ The inverse (pixel -> theta) is Newton on theta (1 + k1 theta^2 + ...) - theta_d
   ``rectify``'s fixed-point format, so ``rectify.remap_device`` warps through it unchanged.
 
 The ``*_host`` functions are the readable fp64 definitions and the pins of the kernels; host and device agree to rounding
-(summation order, libm), not bit for bit.  Not here: consensus (RANSAC) variants, fisheye cameras inside the stereo and rig
-solvers, skew, cv2's CALIB_* flags, fields of 180 degrees and more; bit parity with cv2 is not claimed.
+(summation order, libm), not bit for bit.  A fisheye camera inside a rig is ``rig``'s ``models`` keyword, which takes this
+module's ``_solve`` and ``_project_q``, and so does ``stereo``'s for a pair; the consensus pose (``solve_pnp_fisheye_ransac_*``)
+is ``pnp``'s search run through this model.  Not here: fisheye inside ``calib.calibrate_charuco_ransac_*`` (its raw-pixel
+homography consensus does not hold through a fisheye lens), skew, cv2's CALIB_* flags, fields of 180 degrees and more; bit parity
+with cv2 is not claimed.
 """
 from __future__ import annotations
 
@@ -47,7 +50,8 @@ from .corner_pool import pack_keypoints
 from .pnp import (LM_EPS, LM_MAX_ITER, PNP_BAD_ID, PNP_DEGENERATE, PNP_NONFINITE, PNP_OK, PNP_TOO_FEW, POSE_WORDS, _as_cv2,
                   _bad_id_error, _camera, _cholesky_solve, _init_pose, _pool_ptrs, _right_jacobian, _rodrigues, _skew, object_points,
                   unpack_poses)
-from .rectify import MAP_BITS, MAP_LIMIT, MAP_SENTINEL, NEWTON_EPS, NEWTON_MAX_ITER, _newcam, _rot, _rp_args
+from .rectify import (MAP_BITS, MAP_LIMIT, MAP_SENTINEL, NEWTON_EPS, NEWTON_MAX_ITER, Rectification, _newcam, _projections,
+                      _rectifying_rotations, _rot, _rp_args)
 
 SMALL_R = 1e-4                 # below it theta_d / r and its derivative come from their series
 SMALL_THETA_D = 1e-8           # below it tan(theta) / theta_d = 1 to the last bit
@@ -56,7 +60,10 @@ CALIB_MAX_ITER = 100           # accepted steps of the joint LM
 
 __all__ = ["project_points_host", "undistort_points_host", "solve_pnp_fisheye_host", "solve_pnp_fisheye_host_full",
            "calibrate_fisheye_host", "calibrate_fisheye_host_full", "undistort_rectify_map_fisheye_host",
-           "rectify_points_fisheye_host", "solve_pnp_fisheye_pool", "solve_pnp_fisheye_batch_device", "solve_pnp_fisheye_device",
+           "rectify_points_fisheye_host", "stereo_rectify_fisheye_host", "solve_pnp_fisheye_pool",
+           "solve_pnp_fisheye_batch_device", "solve_pnp_fisheye_device", "solve_pnp_fisheye_ransac_host_full",
+           "solve_pnp_fisheye_ransac_host", "solve_pnp_fisheye_ransac_pool", "solve_pnp_fisheye_ransac_batch_device",
+           "solve_pnp_fisheye_ransac_device",
            "calibrate_fisheye_pool", "calibrate_fisheye_device", "workspace_bytes", "undistort_rectify_map_fisheye_device",
            "rectify_points_fisheye_pool", "SMALL_R", "CALIB_MAX_ITER"]
 
@@ -178,6 +185,25 @@ def _project(obj: np.ndarray, img: np.ndarray, p: np.ndarray, K: np.ndarray, k: 
     return res, cost, np.concatenate([Ji.reshape(2 * n, N_INTR), J.reshape(2 * n, 6)], 1)
 
 
+def _project_q(Q: np.ndarray, img: np.ndarray, K: np.ndarray, k: np.ndarray, jac: bool):
+    """``stereo._project_q`` through this model: points Q (n, 3) in the camera's frame -> residuals (projected - observed, px)
+    and, with ``jac``, d(u, v)/dQ (n, 2, 3): ``_project``'s model and derivatives with the pose taken out, which is what a camera
+    behind a rig transform needs.  Every Z must be positive (the caller checks)."""
+    iz = 1.0 / Q[:, 2]
+    a, b = Q[:, 0] * iz, Q[:, 1] * iz
+    fx, fy = K[0, 0], K[1, 1]
+    d = _distort(a, b, k, jac)
+    res = np.stack([fx * d[0] + K[0, 2] - img[:, 0], fy * d[1] + K[1, 2] - img[:, 1]], 1)
+    if not jac:
+        return res, None
+    dxa, dxb, dyb = d[4:]
+    a0, a1, b0, b1 = fx * dxa, fx * dxb, fy * dxb, fy * dyb
+    D = np.empty((Q.shape[0], 2, 3))
+    D[:, 0, 0], D[:, 0, 1], D[:, 0, 2] = a0 * iz, a1 * iz, -(a0 * a + a1 * b) * iz
+    D[:, 1, 0], D[:, 1, 1], D[:, 1, 2] = b0 * iz, b1 * iz, -(b0 * a + b1 * b) * iz
+    return res, D
+
+
 def project_points_host(object_points_, rvec, tvec, camera_matrix, dist_coeffs, jacobian: bool = False):
     """``cv2.fisheye.projectPoints``: object points (N, 3) at the pose (rvec, tvec) -> pixels (N, 2); NaN rows for points that
     are not in front of the camera.  With ``jacobian`` (every point must be in front): ``(pixels, J)`` with J (2N, 14) =
@@ -261,6 +287,24 @@ def solve_pnp_fisheye_host(keypoints, col_count, row_count, square_len, camera_m
     """``pnp.solve_pnp_host`` on a fisheye camera -> (ret, rvec (3,1), tvec (3,1)); (False, None, None) for fewer than 4 points,
     a pixel outside the model or input the solver refuses."""
     return _as_cv2(*solve_pnp_fisheye_host_full(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs))
+
+
+def solve_pnp_fisheye_ransac_host_full(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations=100,
+                                       reproj_error=8.0, min_inliers=4, seed=0, with_margin=False, pool_order=False):
+    """``pnp.solve_pnp_ransac_host_full`` on a fisheye camera, and the definition of ``dcx_fisheye_solve_pnp_ransac_pool`` ->
+    (status, pose[8], inliers bool[N] in the caller's row order, winning hypothesis or -1[, margin]).  The sampler, the four-point
+    pose, the scoring and the selection are ``pnp._ransac_host_full``'s, run through this model: the sample's pixels through
+    ``_undistort`` (a sample with a pixel outside the model has no hypothesis), the rows scored by ``_project``, the winner's
+    inliers solved by ``_solve`` (DEGENERATE if one of them lies outside the model)."""
+    return pnp._ransac_host_full(keypoints, col_count, row_count, square_len, _camera(camera_matrix), _dist4(dist_coeffs),
+                                 (_undistort, _project, _solve), iterations, reproj_error, min_inliers, seed, with_margin, pool_order)
+
+
+def solve_pnp_fisheye_ransac_host(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations=100,
+                                  reproj_error=8.0, min_inliers=4, seed=0):
+    """``pnp.solve_pnp_ransac_host`` on a fisheye camera -> (ret, rvec (3,1), tvec (3,1), inliers bool[N])."""
+    return pnp._as_cv2_ransac(*solve_pnp_fisheye_ransac_host_full(keypoints, col_count, row_count, square_len, camera_matrix,
+                                                                  dist_coeffs, iterations, reproj_error, min_inliers, seed)[:3])
 
 
 # ------------------------------------------------------------------------------------------------ calibration
@@ -402,6 +446,28 @@ def rectify_points_fisheye_host(pix, camera_matrix, dist_coeffs, R=None, P=None)
     return out
 
 
+def stereo_rectify_fisheye_host(camera0, dist0, camera1, dist1, image_size, R, T, focal=None) -> Rectification:
+    """``rectify.stereo_rectify_host`` for a pair of fisheye cameras (``cv2.fisheye.stereoRectify``'s role): the rig (R, T) with
+    q1 = R q0 + T -> ``rectify.Rectification``.  R1, R2, axis and Tn are ``stereo_rectify_host``'s (no camera enters them).  The
+    rectified cameras are pinholes with f = ``focal`` or, by default, min(fy0, fy1), and the principal point ((W - 1) / 2,
+    (H - 1) / 2): a wide lens's image corners need not undistort, so the corner-balancing principal point of the pinhole call is
+    not available, and neither is ``alpha``.  P1, P2 and Q take ``stereo_rectify_host``'s forms, so
+    ``undistort_rectify_map_fisheye_device``, ``rectify.remap_device``, ``rectify_points_fisheye_pool``,
+    ``rectify.reproject_to_3d`` and the matcher follow unchanged.  With a small f more of the field fits the rectified frame.
+    ValueError for refused cameras, a zero T or a focal length that is not positive and finite."""
+    K0, K1 = _camera(camera0), _camera(camera1)
+    _dist4(dist0), _dist4(dist1)
+    W, H = int(image_size[0]), int(image_size[1])
+    if W < 2 or H < 2:
+        raise ValueError("image_size must be (W, H) with both >= 2")
+    R1, R2, axis, Tn = _rectifying_rotations(R, T)
+    f = min(K0[1, 1], K1[1, 1]) if focal is None else float(focal)
+    if not (math.isfinite(f) and f > 0):
+        raise ValueError("the rectified focal length must be positive and finite")
+    P1, P2, Q = _projections(f, (W - 1) / 2, (H - 1) / 2, axis, Tn)
+    return Rectification(R1, R2, P1, P2, Q, axis, Tn)
+
+
 # ------------------------------------------------------------------------------------------------ the device entry points
 
 def solve_pnp_fisheye_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len, camera_matrix,
@@ -449,6 +515,53 @@ def solve_pnp_fisheye_device(keypoints, col_count, row_count, square_len, camera
         _camera_args(camera_matrix, dist_coeffs)
         return False, None, None
     return solve_pnp_fisheye_batch_device([kp], col_count, row_count, square_len, camera_matrix, dist_coeffs, device)[0]
+
+
+def solve_pnp_fisheye_ransac_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len, camera_matrix,
+                                  dist_coeffs, iterations=100, reproj_error=8.0, min_inliers=4, seed=0, out=None, workspace=None):
+    """``pnp.solve_pnp_ransac_pool`` on a fisheye camera (``dcx_fisheye_solve_pnp_ransac_pool``): the same two launches, outputs
+    ``(status, pose, info, inliers)``, ``out`` / ``workspace`` conventions (``pnp.ransac_workspace_bytes``) and capture safety."""
+    import torch
+    from . import _lib
+    dev = packed.device
+    iterations, reproj_error, min_inliers = pnp._ransac_args(iterations, reproj_error, min_inliers)
+    ptrs = _pool_ptrs(packed, batch, pool, refined)
+    need = pnp.ransac_workspace_bytes(batch, pool, iterations)
+    workspace = _dev.workspace(workspace, dev, need, f"workspace must be a contiguous tensor of at least {need} bytes on {dev}")
+    msg = f"out must be (int32 [{batch}], float64 [{batch}, 8], int32 [{batch}, 2], uint8 [{pool}]) contiguous tensors on {dev}"
+    want = ((torch.int32, (batch,)), (torch.float64, (batch, POSE_WORDS)), (torch.int32, (batch, 2)), (torch.uint8, (pool,)))
+    if out is not None and len(out) != 4:
+        raise ValueError(msg)
+    st, pose, info, inl = (_dev.tensor(t, dev, dt, shape, msg, "min", zeros=dt is torch.uint8)
+                           for t, (dt, shape) in zip(out or (None,) * 4, want))
+    cam, dist = _camera_args(camera_matrix, dist_coeffs)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().dcx_fisheye_solve_pnp_ransac_pool(
+            *ptrs, int(batch), int(pool), int(col_count), int(row_count), float(square_len), cam, dist, iterations, reproj_error,
+            min_inliers, int(seed) & 0xFFFFFFFF, workspace.data_ptr(), workspace.numel() * workspace.element_size(), st.data_ptr(),
+            pose.data_ptr(), info.data_ptr(), inl.data_ptr(), _lib.current_stream()), "dcx_fisheye_solve_pnp_ransac_pool")
+    return st, pose, info, inl
+
+
+def solve_pnp_fisheye_ransac_batch_device(keypoints_list, col_count, row_count, square_len, camera_matrix, dist_coeffs,
+                                          iterations=100, reproj_error=8.0, min_inliers=4, seed=0, device="cuda", full=False):
+    """``pnp.solve_pnp_ransac_batch_device`` on a fisheye camera -> list of ``(ret, rvec, tvec, inliers)`` (``full=True``: of
+    ``(status, pose[8], inliers, winner)``), the masks in the caller's row order."""
+    return pnp.solve_pnp_ransac_batch_device(keypoints_list, col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations,
+                                             reproj_error, min_inliers, seed, device, full,
+                                             _model=(_camera_args, solve_pnp_fisheye_ransac_pool))
+
+
+def solve_pnp_fisheye_ransac_device(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations=100,
+                                    reproj_error=8.0, min_inliers=4, seed=0, device="cuda"):
+    """``pnp.solve_pnp_ransac_device`` on a fisheye camera -> ``(ret, rvec, tvec, inliers bool[N])``."""
+    kp = np.asarray(keypoints)
+    if kp.ndim != 2 or kp.shape[0] < 4:
+        _camera_args(camera_matrix, dist_coeffs)
+        pnp._ransac_args(iterations, reproj_error, min_inliers)
+        return False, None, None, np.zeros(kp.shape[0] if kp.ndim == 2 else 0, bool)
+    return solve_pnp_fisheye_ransac_batch_device([kp], col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations,
+                                                 reproj_error, min_inliers, seed, device)[0]
 
 
 def workspace_bytes(batch: int) -> int:

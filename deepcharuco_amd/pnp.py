@@ -475,13 +475,15 @@ def _homography4(obj: np.ndarray, mn: np.ndarray) -> Tuple[int, Optional[np.ndar
     return PNP_OK, H / H[2, 2], mc
 
 
-def _row_errors2(obj: np.ndarray, img: np.ndarray, p: np.ndarray, K: np.ndarray, k: np.ndarray) -> np.ndarray:
-    """Squared reprojection error (px^2) of every row at pose p; inf for a row that is not in front of the camera."""
+def _row_errors2(obj: np.ndarray, img: np.ndarray, p: np.ndarray, K: np.ndarray, k: np.ndarray, project=None) -> np.ndarray:
+    """Squared reprojection error (px^2) of every row at pose p; inf for a row that is not in front of the camera.  ``project``:
+    the camera model's ``_project`` (default: this module's)."""
+    project = project or _project
     X = obj @ _rodrigues(p[:3]).T + p[3:]
     e2 = np.full(obj.shape[0], math.inf)
     front = X[:, 2] > 0
     if front.any():
-        res, _, _ = _project(obj[front], img[front], p, K, k, False)
+        res, _, _ = project(obj[front], img[front], p, K, k, False)
         e2[front] = (res * res).sum(1)
     return e2
 
@@ -510,7 +512,16 @@ def solve_pnp_ransac_host_full(keypoints, col_count, row_count, square_len, came
 
     ``with_margin``: a fifth value, the smallest |error - reproj_error| / reproj_error of any row under any hypothesis that
     scores within one of the winner: how far the frame is from a decision rounding could flip (inf if there is no winner)."""
-    K, k = _camera(camera_matrix), _dist(dist_coeffs)
+    return _ransac_host_full(keypoints, col_count, row_count, square_len, _camera(camera_matrix), _dist(dist_coeffs),
+                             (_undistort, _project, _solve), iterations, reproj_error, min_inliers, seed, with_margin, pool_order)
+
+
+def _ransac_host_full(keypoints, col_count, row_count, square_len, K, k, model, iterations, reproj_error, min_inliers, seed,
+                      with_margin, pool_order):
+    """``solve_pnp_ransac_host_full`` through a camera model = (undistort, project, solve): this module's, or ``fisheye``'s.  The
+    sampler, the four-point pose, the scoring, the selection and the margin are here once.  A sample with a pixel the model
+    cannot undistort (NaN; a pinhole has none) has no hypothesis."""
+    undistort, project, solve = model
     iterations, thr, min_inliers = _ransac_args(iterations, reproj_error, min_inliers)
     kp = np.asarray(keypoints)
     n = kp.shape[0] if kp.ndim == 2 else 0
@@ -526,18 +537,18 @@ def solve_pnp_ransac_host_full(keypoints, col_count, row_count, square_len, came
     ids = kp[:, 2].astype(np.int64)
     obj32, img32 = object_points(ids, col_count, row_count, square_len), kp[:, :2].astype(np.float32)
     obj, img = obj32.astype(np.float64), img32.astype(np.float64)
-    mn = _undistort(img, K, k)
+    mn = undistort(img, K, k)
     best, winner, best_e2, records = -1, -1, None, []
     for h in range(iterations):
         s = _ransac_sample(seed, n, h, ids, row_count - 1)
-        if s is None:
+        if s is None or not np.isfinite(mn[s]).all():
             continue
         st, H, mc = _homography4(obj[s], mn[s])
         if st == PNP_OK:
             st, p0 = _pose_of_homography(H, mc)
         if st != PNP_OK:
             continue
-        e2 = _row_errors2(obj, img, p0, K, k)
+        e2 = _row_errors2(obj, img, p0, K, k, project)
         score = int((e2 <= thr * thr).sum())
         records.append((score, e2))
         if score > best:
@@ -549,7 +560,7 @@ def solve_pnp_ransac_host_full(keypoints, col_count, row_count, square_len, came
     if best < max(min_inliers, 4):
         return done(PNP_NO_CONSENSUS, winner=winner, margin=margin)
     m = best_e2 <= thr * thr
-    st, pose = _solve(obj32[m], img32[m], K, k)
+    st, pose = solve(obj32[m], img32[m], K, k)
     if st != PNP_OK:
         return done(st, winner=winner, margin=margin)
     mask = np.empty(n, bool)
@@ -699,21 +710,22 @@ def unpack_ransac(status, pose, inliers, counts, starts, ids=None) -> List[tuple
 
 
 def solve_pnp_ransac_batch_device(keypoints_list, col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations=100,
-                                  reproj_error=8.0, min_inliers=4, seed=0, device="cuda", full=False):
+                                  reproj_error=8.0, min_inliers=4, seed=0, device="cuda", full=False, _model=None):
     """``solve_pnp_ransac_host`` of every frame of a list of keypoint arrays on the GPU -> list of
     ``(ret, rvec, tvec, inliers)``, ``inliers`` a bool array in the caller's row order.  ``full=True``: list of
     ``(status, pose[8], inliers, winner)`` like ``solve_pnp_ransac_host_full``.  IndexError if any frame with >= 4 points carries
-    an id outside the board."""
+    an id outside the board.  (``_model``: another camera model's (camera_args, pool call), ``fisheye``'s.)"""
     import torch
     from .models._handles import require_cuda
     dev = require_cuda(device)
-    _camera_args(camera_matrix, dist_coeffs)                  # ValueError before anything is uploaded
+    camera_args, pool_call = _model or (_camera_args, solve_pnp_ransac_pool)
+    camera_args(camera_matrix, dist_coeffs)                   # ValueError before anything is uploaded
     _ransac_args(iterations, reproj_error, min_inliers)
     if len(keypoints_list) == 0:
         return []
     packed, b, pool = pack_keypoints(keypoints_list, dev)
     with torch.cuda.device(dev):
-        st, pose, info, inl = solve_pnp_ransac_pool(packed, b, pool, True, col_count, row_count, square_len, camera_matrix,
+        st, pose, info, inl = pool_call(packed, b, pool, True, col_count, row_count, square_len, camera_matrix,
                                                     dist_coeffs, iterations, reproj_error, min_inliers, seed)
         st, pose, info, inl, head = (t.cpu().numpy() for t in (st, pose, info, inl, packed[:layout(b, pool).rows]))
     if (st == PNP_BAD_ID).any():

@@ -202,19 +202,10 @@ def _edge_extreme(K, d, Rc, W: int, H: int, edge: int, samples: np.ndarray) -> f
     return sign * best
 
 
-def stereo_rectify_host(camera0, dist0, camera1, dist1, image_size, R, T, alpha: Optional[float] = None) -> Rectification:
-    """The rectifying transforms of a rig (module docstring, step 1).  ``image_size`` = (W, H), shared by both cameras;
-    ``alpha``: None (no scaling) or a value in [0, 1].  ValueError for refused cameras, a zero T or a border that cannot be
-    undistorted."""
-    cams = [(_camera(camera0), dist0), (_camera(camera1), dist1)]
-    for _, d in cams:
-        _dist(d)
-    W, H = int(image_size[0]), int(image_size[1])
-    if W < 2 or H < 2:
-        raise ValueError("image_size must be (W, H) with both >= 2")
+def _rectifying_rotations(R, T):
+    """Step 1's rotations, which no camera model enters: the rig (R, T) -> (R1, R2, axis, Tn).  Each camera turns half of R towards
+    the other, then both turn the baseline onto the image axis it is closer to.  ValueError for a zero or non-finite T."""
     R, T = _rot(R), np.asarray(T, np.float64).reshape(3)
-    if alpha is not None and not 0.0 <= float(alpha) <= 1.0:
-        raise ValueError("alpha must be None or in [0, 1]")
     om = _rvec_of(R)
     r_r = _rodrigues(-0.5 * om)
     t = r_r @ T
@@ -230,7 +221,31 @@ def stereo_rectify_host(camera0, dist0, camera1, dist1, image_size, R, T, alpha:
         w = w * (math.atan2(nw, abs(t[axis])) / nw)
     wR = _rodrigues(w)
     R1, R2 = wR @ r_r.T, wR @ r_r
-    Tn = float((R2 @ T)[axis])
+    return R1, R2, axis, float((R2 @ T)[axis])
+
+
+def _projections(f: float, cx: float, cy: float, axis: int, Tn: float):
+    """-> (P1, P2, Q) of two rectified cameras with the focal length f and the principal point (cx, cy)."""
+    P1 = np.array([[f, 0, cx, 0], [0, f, cy, 0], [0, 0, 1, 0]], np.float64)
+    P2 = P1.copy()
+    P2[axis, 3] = Tn * f
+    Q = np.array([[1, 0, 0, -cx], [0, 1, 0, -cy], [0, 0, 0, f], [0, 0, -1.0 / Tn, 0]], np.float64)
+    return P1, P2, Q
+
+
+def stereo_rectify_host(camera0, dist0, camera1, dist1, image_size, R, T, alpha: Optional[float] = None) -> Rectification:
+    """The rectifying transforms of a rig (module docstring, step 1).  ``image_size`` = (W, H), shared by both cameras;
+    ``alpha``: None (no scaling) or a value in [0, 1].  ValueError for refused cameras, a zero T or a border that cannot be
+    undistorted."""
+    cams = [(_camera(camera0), dist0), (_camera(camera1), dist1)]
+    for _, d in cams:
+        _dist(d)
+    W, H = int(image_size[0]), int(image_size[1])
+    if W < 2 or H < 2:
+        raise ValueError("image_size must be (W, H) with both >= 2")
+    if alpha is not None and not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError("alpha must be None or in [0, 1]")
+    R1, R2, axis, Tn = _rectifying_rotations(R, T)
 
     f = min(cams[0][0][1, 1], cams[1][0][1, 1])
     Rs = (R1, R2)
@@ -259,10 +274,7 @@ def stereo_rectify_host(camera0, dist0, camera1, dist1, image_size, R, T, alpha:
         a = float(alpha)
         f = f * (s0 * (1.0 - a) + s1 * a)
 
-    P1 = np.array([[f, 0, cx, 0], [0, f, cy, 0], [0, 0, 1, 0]], np.float64)
-    P2 = P1.copy()
-    P2[axis, 3] = Tn * f
-    Q = np.array([[1, 0, 0, -cx], [0, 1, 0, -cy], [0, 0, 0, f], [0, 0, -1.0 / Tn, 0]], np.float64)
+    P1, P2, Q = _projections(f, cx, cy, axis, Tn)
     return Rectification(R1, R2, P1, P2, Q, axis, Tn)
 
 

@@ -40,6 +40,12 @@ same steps on the GPU (csrc/dcx_rig.hip).  The two agree to rounding (summation 
 are ``stereo.py``'s, and the result its result to rounding: V and g_a are summed in the same order, the cost per timestamp is
 added up camera by camera.
 
+``models`` (the last keyword of the four entry points): None, or per camera ``"pinhole"`` or ``"fisheye"``.  A fisheye camera is
+``fisheye.py``'s model with its four coefficients k1..k4 (or None) in ``dists``: its views are solved by ``fisheye._solve`` (a view
+with a pixel outside the model is PNP_DEGENERATE, and then not usable) and its rows enter step 4 through ``fisheye._project_q``.
+Nothing else changes: the steps above never look inside a camera.  With None, and with every camera a pinhole, the result is
+what it has always been, bit for bit.
+
 What it gives over C - 1 stereo solves: one consistent rig from one call, and cameras that never see the board together with
 camera 0.  Where every camera shares views with camera 0 it is not measurably more accurate than the pairwise solves.
 """
@@ -55,7 +61,8 @@ from . import _dev, _lm, pnp
 from .corner_pool import _pool_rows, pack_keypoints
 from .pnp import (PNP_BAD_ID, PNP_OK, PNP_TOO_FEW, _bad_id_error, _camera, _dist, _pool_ptrs, _right_jacobian, _rodrigues, _rvec_of,
                   _solve)
-from .stereo import _project_q, _rig_init, _skews, _slot_mask, essential_fundamental
+from .stereo import (MODELS, _model_args, _model_cameras, _model_of, _models, _project_q, _rig_init, _skews, _slot_mask,
+                     essential_fundamental)
 
 # overall status (include/deepcharuco_amd.h); per-view statuses are pnp's PNP_*
 RIG_OK, RIG_NO_STAMPS, RIG_DEGENERATE, RIG_NONFINITE = _lm.LM_OK, _lm.LM_NO_UNITS, _lm.LM_DEGENERATE, _lm.LM_NONFINITE
@@ -146,11 +153,11 @@ def _evaluate(rows: _Rows, cams, X: np.ndarray, P: np.ndarray, jac: bool):
         return None
     M = rows.obj.shape[0]
     res, D = np.empty((M, 2)), (np.empty((M, 2, 3)) if jac else None)
-    for c, (K, k) in enumerate(cams):
+    for c, cam in enumerate(cams):
         sel = rows.cam == c
         if not sel.any():
             continue
-        r, d = _project_q(Q[sel], rows.img[sel], K, k, jac)
+        r, d = _model_of(cam)[1](Q[sel], rows.img[sel], cam[0], cam[1], jac)
         res[sel] = r
         if jac:
             D[sel] = d
@@ -306,12 +313,12 @@ def _result(status, X, parents, view_status, view_points, usable, used, P, vc, i
                      view_points.astype(np.int64), vr, rv, tv, sr, sp, int(iters), int(attempts), int(used.size), points)
 
 
-def _cameras(cameras, dists):
+def _cameras(cameras, dists, models=None):
     if dists is None:
         dists = [None] * len(cameras)
     if not 2 <= len(cameras) <= RIG_MAX_CAMERAS or len(dists) != len(cameras):
         raise ValueError(f"2 to {RIG_MAX_CAMERAS} cameras and as many distortion models are required")
-    return [(_camera(K), _dist(d)) for K, d in zip(cameras, dists)], list(dists)
+    return _model_cameras(cameras, dists, _models(models, len(cameras))), list(dists)
 
 
 def _mask_lists(masks, n_cams):
@@ -323,20 +330,21 @@ def _mask_lists(masks, n_cams):
 
 
 def rig_calibrate_host_full(keypoints_lists, col_count, row_count, square_len, cameras, dists, masks=None, pool_order=False,
-                            with_margin=False):
+                            with_margin=False, models=None):
     """The definition (module docstring) -> ``RigResult`` (with ``with_margin``: ``(result, margin)``).
 
     ``keypoints_lists[c][t]``: the [x, y, id] rows of camera c at timestamp t (an empty array where the camera did not see the
     board); every camera's list is equally long.  Rows are taken in the order the corner pool holds them: id-sorted stably, or as
     they stand with ``pool_order=True``.  ``cameras`` / ``dists``: per camera its matrix and coefficients (``dists`` or an entry
     of it may be None).  ``masks``: None, or per camera None or per-timestamp bool arrays in the caller's row order (None: keep
-    every row) that drop rows before the checks.  Nothing raises for unusable views; ValueError for a refused camera, fewer than
+    every row) that drop rows before the checks.  ``models``: None or per camera "pinhole" / "fisheye" (module docstring).
+    Nothing raises for unusable views; ValueError for a refused camera, fewer than
     2 or more than 8 cameras, or lists of different lengths.
 
     ``with_margin``: the smallest relative distance of a discrete decision of steps 2 - 5 from its threshold: the sine term of
     every ``_rvec_of`` of the initialisation (every tree edge, every composition) from its switch at 1e-5, and the depth of every
     used row at the solution from 0 (relative to its distance from the camera centre)."""
-    cams, _ = _cameras(cameras, dists)
+    cams, _ = _cameras(cameras, dists, models)
     C = len(cams)
     if len(keypoints_lists) != C:
         raise ValueError(f"{len(keypoints_lists)} keypoint lists for {C} cameras")
@@ -369,7 +377,7 @@ def rig_calibrate_host_full(keypoints_lists, col_count, row_count, square_len, c
                 continue
             obj_l[t][c] = pnp.object_points(ids, col_count, row_count, square_len)
             img_l[t][c] = kp[:, :2].astype(np.float32)
-            st, pose = _solve(obj_l[t][c], img_l[t][c], *cams[c])
+            st, pose = _model_of(cams[c])[0](obj_l[t][c], img_l[t][c], cams[c][0], cams[c][1])
             view_status[t, c] = st
             poses[t, c] = pose[:6]
     usable = view_status == PNP_OK
@@ -407,18 +415,20 @@ def _raise_like_cv2(r: RigResult, col_count, row_count):
         raise ValueError(f"rig calibration failed (status {r.status})")
 
 
-def rig_calibrate_host(keypoints_lists, col_count, row_count, square_len, cameras, dists, masks=None):
+def rig_calibrate_host(keypoints_lists, col_count, row_count, square_len, cameras, dists, masks=None, models=None):
     """``(rms, R [C, 3, 3], T [C, 3, 1])`` with q_c = R[c] q_0 + T[c].  Raises where cv2's calibrations would: ValueError for a view
     that has rows and cannot be used (too few, degenerate) or a failed calibration (no timestamp with two views, a camera that
     shares no view with the others), IndexError for an id outside the board.  An empty view is not an error."""
-    r = rig_calibrate_host_full(keypoints_lists, col_count, row_count, square_len, cameras, dists, masks)
+    r = rig_calibrate_host_full(keypoints_lists, col_count, row_count, square_len, cameras, dists, masks, models=models)
     _raise_like_cv2(r, col_count, row_count)
     return r.rms, r.R, r.T.reshape(-1, 3, 1).copy()
 
 
 def rig_pair(result: RigResult, a: int, b: int, camera_a, camera_b):
     """The stereo pair (a, b) of a solved rig -> ``(R, T, E, F)`` with q_b = R q_a + T, from X_b o X_a^-1, and
-    ``stereo.essential_fundamental`` with the two camera matrices: what ``rectify.stereo_rectify_host`` takes."""
+    ``stereo.essential_fundamental`` with the two camera matrices: what ``rectify.stereo_rectify_host`` takes.  F relates pixels
+    of two PINHOLE cameras (undistorted ones): between cameras of which one is a fisheye it means nothing; R, T and E hold for any
+    pair."""
     if result.status != RIG_OK:
         raise ValueError(f"the rig was not solved (status {result.status})")
     C = result.R.shape[0]
@@ -452,17 +462,19 @@ def workspace_bytes(n_cams: int, batch: int, pools) -> int:
 
 
 def rig_calibrate_pools(packed_list, batch: int, pools, refined: bool, col_count, row_count, square_len, cameras, dists,
-                        masks=None) -> RigResult:
+                        masks=None, models=None) -> RigResult:
     """The rig of C cameras from C ``infer_batch_device`` results of ``batch`` frames each, read in place from the C corner pools
     (the conventions of ``pnp.solve_pnp_pool``; frame t of every pool was taken at the same instant).  ``pools``: the pool size per
     camera.  ``masks``: None, or per camera None or a contiguous uint8 device tensor of at least that pool's size by SLOT, the
     ``inliers`` that ``pnp.solve_pnp_ransac_pool`` and ``calib.calibrate_charuco_ransac_pool`` write: rows with 0 are dropped
-    before the checks.  With a mask the slot ranges of that pool's views must not overlap (DcxError).  The call synchronises the
+    before the checks.  With a mask the slot ranges of that pool's views must not overlap (DcxError).  ``models``: None
+    (``dcx_rig_calibrate_pool``) or per camera "pinhole" / "fisheye" (``dcx_rig_calibrate_models_pool``).  The call synchronises the
     current stream (the tree, the medians and the LM loop's state word are read on the host) and cannot be captured in a graph."""
     import torch
     from . import _lib
-    cams, dists = _cameras(cameras, dists)
+    cams, dists = _cameras(cameras, dists, models)
     C = len(cams)
+    models = _models(models, C)
     pools = [int(p) for p in pools]
     if len(packed_list) != C or len(pools) != C:
         raise ValueError(f"{C} cameras need {C} pools and {C} pool sizes")
@@ -476,7 +488,7 @@ def rig_calibrate_pools(packed_list, batch: int, pools, refined: bool, col_count
             _dev.tensor(mk[c], dev, torch.uint8, (pools[c],),
                         f"mask {c} must be a contiguous uint8 tensor of at least {pools[c]} values on {dev}", "min")
         counts_p, starts_p, rows_p, xy_p = _pool_ptrs(packed_list[c], batch, pools[c], refined)
-        cam9, d8, nd = pnp._camera_args(cameras[c], dists[c])
+        cam9, d8, nd = _model_args(cameras[c], dists[c], models and models[c])
         table[c] = _RigCamera(counts_p, starts_p, rows_p, xy_p, pools[c], _lib.ptr(mk[c]), cam9, d8, nd)
     st = torch.empty((batch, C), dtype=torch.int32, device=dev)
     pose = torch.empty((batch, pnp.POSE_WORDS), dtype=torch.float64, device=dev)
@@ -485,10 +497,15 @@ def rig_calibrate_pools(packed_list, batch: int, pools, refined: bool, col_count
     ws = _dev.workspace(None, dev, nbytes)
     res = (_ctypes.c_double * (RESULT_HEAD + 6 * (C - 1)))()
     par = (_ctypes.c_int32 * C)()
+    tail = (int(batch), int(col_count), int(row_count), float(square_len), ws.data_ptr(), nbytes, st.data_ptr(), pose.data_ptr(),
+            info.data_ptr(), par, res)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().dcx_rig_calibrate_pool(C, table, int(batch), int(col_count), int(row_count), float(square_len),
-                                                     ws.data_ptr(), nbytes, st.data_ptr(), pose.data_ptr(), info.data_ptr(), par,
-                                                     res, _lib.current_stream()), "dcx_rig_calibrate_pool")
+        if models is None:
+            _lib.check(_lib.lib().dcx_rig_calibrate_pool(C, table, *tail, _lib.current_stream()), "dcx_rig_calibrate_pool")
+        else:
+            tags = (_ctypes.c_int * C)(*(MODELS.index(m) for m in models))
+            _lib.check(_lib.lib().dcx_rig_calibrate_models_pool(C, table, tags, *tail, _lib.current_stream()),
+                       "dcx_rig_calibrate_models_pool")
         st_h, pose_h, info_h = st.cpu().numpy(), pose.cpu().numpy(), info.cpu().numpy()
     r = np.array(res[:], np.float64)
     status = int(r[5])
@@ -503,14 +520,14 @@ def rig_calibrate_pools(packed_list, batch: int, pools, refined: bool, col_count
 
 
 def rig_calibrate_device(keypoints_lists: Sequence, col_count, row_count, square_len, cameras, dists, masks=None,
-                         device="cuda") -> RigResult:
+                         device="cuda", models=None) -> RigResult:
     """``rig_calibrate_host_full`` on the GPU from ``infer_image``-format keypoint arrays ([x, y, id] rows; one list per camera,
-    equally long) -> ``RigResult``.  ``masks`` as for the host definition.  IndexError if a view with >= 4 rows carries an id
+    equally long) -> ``RigResult``.  ``masks`` and ``models`` as for the host definition.  IndexError if a view with >= 4 rows carries an id
     outside the board."""
     import torch
     from .models._handles import require_cuda
     dev = require_cuda(device)
-    cams, dists = _cameras(cameras, dists)                    # ValueError before anything is uploaded
+    cams, dists = _cameras(cameras, dists, models)            # ValueError before anything is uploaded
     C = len(cams)
     if len(keypoints_lists) != C:
         raise ValueError(f"{len(keypoints_lists)} keypoint lists for {C} cameras")
@@ -524,7 +541,7 @@ def rig_calibrate_device(keypoints_lists: Sequence, col_count, row_count, square
     dm = [None if mk[c] is None else _slot_mask(keypoints_lists[c], mk[c], packs[c][2], dev) for c in range(C)]
     with torch.cuda.device(dev):
         r = rig_calibrate_pools([p[0] for p in packs], B, [p[2] for p in packs], True, col_count, row_count, square_len, cameras,
-                                dists, None if masks is None else dm)
+                                dists, None if masks is None else dm, models)
     if (r.view_status == PNP_BAD_ID).any():
         raise _bad_id_error(col_count, row_count)
     return r

@@ -47,7 +47,7 @@ from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from . import _dev, _lm, pnp
+from . import _dev, _lm, fisheye, pnp
 from .corner_pool import _pool_rows, pack_keypoints
 from .pnp import (PNP_BAD_ID, PNP_OK, PNP_TOO_FEW, _bad_id_error, _camera, _dist, _jacobi, _pool_ptrs, _right_jacobian, _rodrigues,
                   _rvec_of, _skew, _solve)
@@ -71,7 +71,7 @@ class StereoResult(NamedTuple):
     T: np.ndarray                # [3]
     rvec: np.ndarray             # [3] Rodrigues vector of R
     E: np.ndarray                # 3x3 [T]x R
-    F: np.ndarray                # 3x3 K1^-T E K0^-1, F[2, 2] = 1 where it is not zero
+    F: Optional[np.ndarray]      # 3x3 K1^-T E K0^-1, F[2, 2] = 1 where it is not zero; None for a pair with a fisheye camera
     view_status: np.ndarray      # int32 [T, 2], pnp.PNP_* per camera
     rvecs: np.ndarray            # [T, 3] the board's pose P_t in camera 0's frame; zeros unless the pair was used
     tvecs: np.ndarray            # [T, 3]
@@ -111,6 +111,41 @@ def _project_q(Q: np.ndarray, img: np.ndarray, K: np.ndarray, k: np.ndarray, jac
     D[:, 0, 0], D[:, 0, 1], D[:, 0, 2] = a0 * iz, a1 * iz, -(a0 * x + a1 * y) * iz
     D[:, 1, 0], D[:, 1, 1], D[:, 1, 2] = b0 * iz, b1 * iz, -(b0 * x + b1 * y) * iz
     return res, D
+
+
+MODELS = ("pinhole", "fisheye")      # DCX_CAMERA_PINHOLE, DCX_CAMERA_FISHEYE of include/deepcharuco_amd.h, in that order
+# what the steps need of a camera model: its pose solve and its projection of camera-frame points
+_MODEL = {"pinhole": (_solve, _project_q), "fisheye": (fisheye._solve, fisheye._project_q)}
+
+
+def _model_of(cam):
+    """A camera of the steps is (K, k), a pinhole, or (K, k, model) -> (solve, project_q) of its model."""
+    return _MODEL[cam[2] if len(cam) > 2 else "pinhole"]
+
+
+def _models(models, n_cams):
+    """``models`` of the entry points -> None, or the model names, one per camera."""
+    if models is None:
+        return None
+    models = list(models)
+    if len(models) != n_cams or any(m not in MODELS for m in models):
+        raise ValueError(f"models must be None or one of {MODELS} per camera")
+    return models
+
+
+def _model_cameras(cameras, dists, models):
+    """-> the cameras of the steps: (K, k) for a pinhole (and for every camera without ``models``), (K, k1..k4, model) else."""
+    if models is None:
+        return [(_camera(K), _dist(d)) for K, d in zip(cameras, dists)]
+    return [(_camera(K), _dist(d)) if m == "pinhole" else (_camera(K), fisheye._dist4(d), m) for K, d, m in zip(cameras, dists, models)]
+
+
+def _model_args(camera, dist, model):
+    """One camera's (camera9, dist, n_dist) of the C entries that take a model: a fisheye camera's k1..k4 ride in dist[0..3]."""
+    if model != "fisheye":
+        return pnp._camera_args(camera, dist)
+    cam9, d4 = fisheye._camera_args(camera, dist)
+    return cam9, (_ctypes.c_double * 8)(*d4), 0 if dist is None else 4
 
 
 class _Rows(NamedTuple):
@@ -159,9 +194,9 @@ def _evaluate(rows: _Rows, cams, X: np.ndarray, P: np.ndarray, jac: bool):
         return None
     M = rows.obj.shape[0]
     res, D = np.empty((M, 2)), (np.empty((M, 2, 3)) if jac else None)
-    for c, (K, k) in enumerate(cams):
+    for c, cam in enumerate(cams):
         sel = rows.cam == c
-        r, d = _project_q(Q[sel], rows.img[sel], K, k, jac)
+        r, d = _model_of(cam)[1](Q[sel], rows.img[sel], cam[0], cam[1], jac)
         res[sel] = r
         if jac:
             D[sel] = d
@@ -255,7 +290,7 @@ def essential_fundamental(R, T, camera0, camera1):
     return E, F
 
 
-def _result(status, X, K0, K1, view_status, view_points, used, P, vc, iters, attempts) -> StereoResult:
+def _result(status, X, K0, K1, view_status, view_points, used, P, vc, iters, attempts, pinholes=True) -> StereoResult:
     B = view_status.shape[0]
     rv, tv, pr, vr = np.zeros((B, 3)), np.zeros((B, 3)), np.zeros(B), np.zeros((B, 2))
     pp = np.zeros(B, np.int64)
@@ -270,7 +305,7 @@ def _result(status, X, K0, K1, view_status, view_points, used, P, vc, iters, att
         vr[used] = np.sqrt(vc / view_points[used])
         pr[used] = np.sqrt(vc.sum(1) / pp[used])
         rms = math.sqrt(_total(vc) / points)
-    return StereoResult(int(status), float(rms), R, T, rvec, E, F, view_status.astype(np.int32), rv, tv, pr, pp, vr,
+    return StereoResult(int(status), float(rms), R, T, rvec, E, F if pinholes else None, view_status.astype(np.int32), rv, tv, pr, pp, vr,
                         view_points.astype(np.int64), int(iters), int(attempts), int(used.size), points)
 
 
@@ -283,7 +318,7 @@ def _mask_pair(masks):
 
 
 def stereo_calibrate_host_full(keypoints_list0, keypoints_list1, col_count, row_count, square_len, camera0, dist0, camera1, dist1,
-                               masks=None, pool_order=False, with_margin=False):
+                               masks=None, pool_order=False, with_margin=False, models=None):
     """The definition (module docstring) -> ``StereoResult`` (with ``with_margin``: ``(result, margin)``).
 
     ``keypoints_list0`` / ``keypoints_list1``: per timestamp an array of [x, y, id] rows of camera 0 / 1 (an empty array for a
@@ -291,12 +326,18 @@ def stereo_calibrate_host_full(keypoints_list0, keypoints_list1, col_count, row_
     ``pnp.solve_pnp_ransac_host_full``: id-sorted stably, or as they stand with ``pool_order=True``.  Object points are
     ``pnp.object_points`` (float32 -> float64), image points float32 -> float64.  ``masks``: None, or a pair (camera 0's,
     camera 1's) of None or per-timestamp bool arrays in the caller's row order (None: keep every row) that drop rows before the
-    checks.  Nothing raises for unusable views; ValueError for a refused camera or lists of different lengths.
+    checks.  ``models``: None, or ("pinhole" | "fisheye", "pinhole" | "fisheye"): a fisheye camera is ``fisheye.py``'s model with
+    k1..k4 (or None) as its ``dist``, its views are solved by ``fisheye._solve`` (a pixel outside the model: PNP_DEGENERATE) and
+    its rows enter the joint solve through ``fisheye._project_q``; F, which relates pixels of two pinholes, is then None.  With
+    None or two pinholes the result is what it has always been, bit for bit.  Nothing raises for unusable views; ValueError for
+    a refused camera or lists of different lengths.
 
     ``with_margin``: the smallest relative distance of a discrete decision of steps 3 - 5 from its threshold: the sine term of
     the rig init's matrix -> vector conversion from its switch at 1e-5, and the depth of every used row at the solution from 0
     (relative to its distance from the camera centre)."""
-    cams = [(_camera(camera0), _dist(dist0)), (_camera(camera1), _dist(dist1))]
+    models = _models(models, 2)
+    cams = _model_cameras((camera0, camera1), (dist0, dist1), models)
+    pinholes = models is None or "fisheye" not in models
     lists = (keypoints_list0, keypoints_list1)
     if len(lists[0]) != len(lists[1]):
         raise ValueError(f"{len(lists[0])} views of camera 0 but {len(lists[1])} of camera 1")
@@ -325,13 +366,13 @@ def stereo_calibrate_host_full(keypoints_list0, keypoints_list1, col_count, row_
                 continue
             obj_l[t][c] = pnp.object_points(ids, col_count, row_count, square_len)
             img_l[t][c] = kp[:, :2].astype(np.float32)
-            st, pose = _solve(obj_l[t][c], img_l[t][c], *cams[c])
+            st, pose = _model_of(cams[c])[0](obj_l[t][c], img_l[t][c], cams[c][0], cams[c][1])
             view_status[t, c] = st
             poses[t, c] = pose[:6]
     used = np.flatnonzero((view_status == PNP_OK).all(1))
 
     def done(status, X=None, P=None, vc=None, iters=0, attempts=0, margin=math.inf):
-        r = _result(status, X, cams[0][0], cams[1][0], view_status, view_points, used, P, vc, iters, attempts)
+        r = _result(status, X, cams[0][0], cams[1][0], view_status, view_points, used, P, vc, iters, attempts, pinholes)
         return (r, margin) if with_margin else r
 
     if not used.size:
@@ -362,12 +403,12 @@ def _raise_like_cv2(r: StereoResult, col_count, row_count):
 
 
 def stereo_calibrate_host(keypoints_list0, keypoints_list1, col_count, row_count, square_len, camera0, dist0, camera1, dist1,
-                          masks=None):
+                          masks=None, models=None):
     """cv2.stereoCalibrate's 9-tuple ``(rms, K0, d0, K1, d1, R, T (3, 1), E, F)`` with the intrinsics as they were given
     (CALIB_FIX_INTRINSIC).  Raises where cv2 would: ValueError for a view that cannot be used (too few rows, degenerate) or a failed
-    calibration, IndexError for an id outside the board."""
+    calibration, IndexError for an id outside the board.  ``models`` as for the definition (F is then None)."""
     r = stereo_calibrate_host_full(keypoints_list0, keypoints_list1, col_count, row_count, square_len, camera0, dist0, camera1,
-                                   dist1, masks)
+                                   dist1, masks, models=models)
     _raise_like_cv2(r, col_count, row_count)
     d0 = np.zeros((1, 0)) if dist0 is None else np.asarray(dist0, np.float64).reshape(1, -1).copy()
     d1 = np.zeros((1, 0)) if dist1 is None else np.asarray(dist1, np.float64).reshape(1, -1).copy()
@@ -386,12 +427,13 @@ def workspace_bytes(batch: int, pool0: int, pool1: int) -> int:
 
 
 def stereo_calibrate_pool(packed0, packed1, batch: int, pool0: int, pool1: int, refined: bool, col_count, row_count, square_len,
-                          camera0, dist0, camera1, dist1, masks=None) -> StereoResult:
+                          camera0, dist0, camera1, dist1, masks=None, models=None) -> StereoResult:
     """The rig of two cameras from two ``infer_batch_device`` results of ``batch`` frames each, read in place from the two corner
     pools (the conventions of ``pnp.solve_pnp_pool``; frame t of ``packed0`` and frame t of ``packed1`` were taken at the same
     instant).  ``masks``: None, or a pair of None / contiguous uint8 device tensors of at least ``pool0`` / ``pool1`` values by
     SLOT, the ``inliers`` that ``pnp.solve_pnp_ransac_pool`` and ``calib.calibrate_charuco_ransac_pool`` write: rows with 0 are
-    dropped before the checks.  With a mask the slot ranges of that pool's views must not overlap (DcxError).  The call
+    dropped before the checks.  With a mask the slot ranges of that pool's views must not overlap (DcxError).  ``models``: None
+    (``dcx_stereo_calibrate_pool``) or the two cameras' models (``dcx_stereo_calibrate_models_pool``).  The call
     synchronises the current stream (the rig init's median and the LM loop's state word are read on the host) and cannot be
     captured in a graph."""
     import torch
@@ -405,19 +447,24 @@ def stereo_calibrate_pool(packed0, packed1, batch: int, pool0: int, pool1: int, 
         if mk[c] is not None:
             _dev.tensor(mk[c], dev, torch.uint8, (pool,), f"mask {c} must be a contiguous uint8 tensor of at least {pool} values on {dev}",
                         "min")
-    cam0, d0, n0 = pnp._camera_args(camera0, dist0)
-    cam1, d1, n1 = pnp._camera_args(camera1, dist1)
+    models = _models(models, 2)
+    cam0, d0, n0 = _model_args(camera0, dist0, models and models[0])
+    cam1, d1, n1 = _model_args(camera1, dist1, models and models[1])
     st = torch.empty((batch, 2), dtype=torch.int32, device=dev)
     pose = torch.empty((batch, pnp.POSE_WORDS), dtype=torch.float64, device=dev)
     info = torch.empty((batch, 2, 2), dtype=torch.float64, device=dev)
     nbytes = workspace_bytes(batch, pool0, pool1)
     ws = _dev.workspace(None, dev, nbytes)
     res = (_ctypes.c_double * RESULT_WORDS)()
+    head = (*p0, _lib.ptr(mk[0]), *p1, _lib.ptr(mk[1]), int(batch), int(pool0), int(pool1), int(col_count), int(row_count),
+            float(square_len), cam0, d0, n0, cam1, d1, n1)
+    tail = (ws.data_ptr(), nbytes, st.data_ptr(), pose.data_ptr(), info.data_ptr(), res)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().dcx_stereo_calibrate_pool(
-            *p0, _lib.ptr(mk[0]), *p1, _lib.ptr(mk[1]), int(batch), int(pool0), int(pool1), int(col_count), int(row_count),
-            float(square_len), cam0, d0, n0, cam1, d1, n1, ws.data_ptr(), nbytes, st.data_ptr(), pose.data_ptr(), info.data_ptr(),
-            res, _lib.current_stream()), "dcx_stereo_calibrate_pool")
+        if models is None:
+            _lib.check(_lib.lib().dcx_stereo_calibrate_pool(*head, *tail, _lib.current_stream()), "dcx_stereo_calibrate_pool")
+        else:
+            _lib.check(_lib.lib().dcx_stereo_calibrate_models_pool(*head, MODELS.index(models[0]), MODELS.index(models[1]), *tail,
+                                                                   _lib.current_stream()), "dcx_stereo_calibrate_models_pool")
         st_h, pose_h, info_h = st.cpu().numpy(), pose.cpu().numpy(), info.cpu().numpy()
     r = np.array(res[:], np.float64)
     status = int(r[11])
@@ -425,6 +472,8 @@ def stereo_calibrate_pool(packed0, packed1, batch: int, pool0: int, pool1: int, 
     if status == STEREO_OK:
         R = _rodrigues(r[0:3])
         E, F = essential_fundamental(R, r[3:6], _camera(camera0), _camera(camera1))
+    if models is not None and "fisheye" in models:
+        F = None
     return StereoResult(status, float(r[6]), R, r[3:6].copy(), r[0:3].copy(), E, F, st_h.astype(np.int32), pose_h[:, 0:3].copy(),
                         pose_h[:, 3:6].copy(), pose_h[:, 6].copy(), pose_h[:, 7].astype(np.int64), info_h[:, :, 0].copy(),
                         info_h[:, :, 1].astype(np.int64), int(r[7]), int(r[8]), int(r[9]), int(r[10]))
@@ -448,15 +497,16 @@ def _slot_mask(keypoints_list, masks, pool, dev):
 
 
 def stereo_calibrate_device(keypoints_list0: Sequence, keypoints_list1: Sequence, col_count, row_count, square_len, camera0, dist0,
-                            camera1, dist1, masks=None, device="cuda") -> StereoResult:
+                            camera1, dist1, masks=None, device="cuda", models=None) -> StereoResult:
     """``stereo_calibrate_host_full`` on the GPU from ``infer_image``-format keypoint arrays ([x, y, id] rows; one list per
-    camera, equally long) -> ``StereoResult``.  ``masks`` as for the host definition.  IndexError if a view with >= 4 rows carries
+    camera, equally long) -> ``StereoResult``.  ``masks`` and ``models`` as for the host definition.  IndexError if a view with >= 4 rows carries
     an id outside the board."""
     import torch
     from .models._handles import require_cuda
     dev = require_cuda(device)
-    pnp._camera_args(camera0, dist0)                          # ValueError before anything is uploaded
-    pnp._camera_args(camera1, dist1)
+    models = _models(models, 2)
+    _model_args(camera0, dist0, models and models[0])         # ValueError before anything is uploaded
+    _model_args(camera1, dist1, models and models[1])
     if len(keypoints_list0) != len(keypoints_list1):
         raise ValueError(f"{len(keypoints_list0)} views of camera 0 but {len(keypoints_list1)} of camera 1")
     if len(keypoints_list0) == 0:
@@ -468,7 +518,7 @@ def stereo_calibrate_device(keypoints_list0: Sequence, keypoints_list1: Sequence
           for kl, m, pool in ((keypoints_list0, mk[0], pool0), (keypoints_list1, mk[1], pool1))]
     with torch.cuda.device(dev):
         r = stereo_calibrate_pool(packed0, packed1, b, pool0, pool1, True, col_count, row_count, square_len, camera0, dist0,
-                                  camera1, dist1, None if masks is None else tuple(dm))
+                                  camera1, dist1, None if masks is None else tuple(dm), models)
     if (r.view_status == PNP_BAD_ID).any():
         raise _bad_id_error(col_count, row_count)
     return r

@@ -384,6 +384,25 @@ int dcx_stereo_calibrate_pool(const int32_t* d_counts0, const int32_t* d_starts0
                               int32_t* d_view_status /* [B][2] DCX_PNP_* */, double* d_pose /* [B][8] */,
                               double* d_view_info /* [B][2][2] */, double* h_result /* [16] */, void* stream);
 
+/* dcx_stereo_calibrate_pool over a pair whose cameras need not be pinholes: model0, model1 are DCX_CAMERA_*.  A
+ * DCX_CAMERA_FISHEYE camera is the model of the dcx_fisheye_* entries: its h_dist holds k1..k4 with n_dist = 4, or n_dist = 0 for
+ * zeros; its views are solved by dcx_fisheye_solve_pnp_pool's solver (a view with a pixel outside the model is
+ * DCX_PNP_DEGENERATE) and its rows enter the joint solve through that model's projection.  Everything else (steps, outputs,
+ * statuses, h_result, synchronisation, the bits' repeatability) is dcx_stereo_calibrate_pool's, and
+ * dcx_stereo_calibrate_workspace_bytes serves this entry too: the workspace layout does not depend on the models.  With both
+ * models DCX_CAMERA_PINHOLE the call IS dcx_stereo_calibrate_pool: the same kernels, the same bits.  DCX_E_ARG also for a model
+ * other than these two and for a fisheye camera with n_dist of 5 or 8.                                                          */
+#define DCX_CAMERA_PINHOLE 0
+#define DCX_CAMERA_FISHEYE 1
+int dcx_stereo_calibrate_models_pool(const int32_t* d_counts0, const int32_t* d_starts0, const int32_t* d_rows0, const float* d_xy0,
+                                     const uint8_t* d_mask0, const int32_t* d_counts1, const int32_t* d_starts1,
+                                     const int32_t* d_rows1, const float* d_xy1, const uint8_t* d_mask1, int batch, int pool0,
+                                     int pool1, int col_count, int row_count, double square_len, const double* h_camera9_0,
+                                     const double* h_dist0, int n_dist0, const double* h_camera9_1, const double* h_dist1,
+                                     int n_dist1, int model0, int model1, void* d_workspace, size_t workspace_bytes,
+                                     int32_t* d_view_status /* [B][2] */, double* d_pose /* [B][8] */,
+                                     double* d_view_info /* [B][2][2] */, double* h_result /* [16] */, void* stream);
+
 /* ---- joint extrinsic calibration of a rig of 2 .. 8 cameras from their corner pools -------------------------------------------
  * dcx_stereo_calibrate_pool over n_cams rigidly mounted cameras with known models and one corner pool each (DcxRigCamera), all
  * with the same `batch`: frame t of every pool shows the same board at the same instant, and a camera that did not see it then
@@ -437,6 +456,21 @@ int dcx_rig_calibrate_pool(int n_cams, const DcxRigCamera* h_cams, int batch, in
                            void* d_workspace, size_t workspace_bytes, int32_t* d_view_status /* [B][n_cams] DCX_PNP_* */,
                            double* d_pose /* [B][8] */, double* d_view_info /* [B][n_cams][2] */, int32_t* h_parents /* [n_cams] */,
                            double* h_result /* [8 + 6 (n_cams - 1)] */, void* stream);
+
+/* dcx_rig_calibrate_pool over a rig whose cameras need not all be pinholes: h_models [n_cams] holds DCX_CAMERA_* per camera (NULL
+ * = all pinhole).  A DCX_CAMERA_FISHEYE camera is the model of the dcx_fisheye_* entries: its DcxRigCamera carries k1..k4 in
+ * dist[0..3] with n_dist = 4, or n_dist = 0 for zeros; its views are solved by dcx_fisheye_solve_pnp_pool's solver (a view with a
+ * pixel outside the model is DCX_PNP_DEGENERATE) and its rows enter the joint solve through that model's projection.  Everything
+ * else (steps, outputs, statuses, h_result, synchronisation, the bits' repeatability) is dcx_rig_calibrate_pool's, and
+ * dcx_rig_calibrate_workspace_bytes serves this entry too: the workspace layout does not depend on the models.  With h_models
+ * NULL or all DCX_CAMERA_PINHOLE the call IS dcx_rig_calibrate_pool: the same kernels, the same bits.  DCX_E_ARG also for a
+ * model other than these two and for a fisheye camera with n_dist of 5 or 8.  deepcharuco_amd/rig.py states the steps
+ * (rig_calibrate_host_full with `models`).                                                                                     */
+int dcx_rig_calibrate_models_pool(int n_cams, const DcxRigCamera* h_cams, const int* h_models /* [n_cams]; NULL = all pinhole */,
+                                  int batch, int col_count, int row_count, double square_len, void* d_workspace,
+                                  size_t workspace_bytes, int32_t* d_view_status /* [B][n_cams] DCX_PNP_* */,
+                                  double* d_pose /* [B][8] */, double* d_view_info /* [B][n_cams][2] */,
+                                  int32_t* h_parents /* [n_cams] */, double* h_result /* [8 + 6 (n_cams - 1)] */, void* stream);
 
 /* ---- stereo rectification: the undistort + rectify map, the remap of u8 frames, the corner pool in rectified coordinates ------
  * What follows dcx_stereo_calibrate_pool: with the rig's rectifying transforms (R1, R2, P1, P2 of
@@ -513,6 +547,18 @@ int dcx_fisheye_solve_pnp_pool(const int32_t* d_counts, const int32_t* d_starts,
                                int col_count, int row_count, double square_len,
                                const double* h_camera9, const double* h_dist4 /* NULL = zeros */,
                                int32_t* d_status, double* d_pose /* [B][8] */, void* stream);
+
+/* dcx_solve_pnp_ransac_pool on a fisheye camera (h_camera9, h_dist4 as for dcx_fisheye_solve_pnp_pool): the same sampler, score
+ * order, mask format, info words, statuses, workspace (dcx_solve_pnp_ransac_workspace_bytes serves this entry too) and capture
+ * rules.  The sample's four pixels go through the model's undistort; a sample with a pixel outside the model has no hypothesis
+ * (score -1); rows are scored by forward projection through the model; the winner's inliers go to the unchanged solver, which
+ * answers DCX_PNP_DEGENERATE if one of them lies outside the model.  No allocation, no sync, capturable.  A workspace smaller
+ * than dcx_solve_pnp_ransac_workspace_bytes is DCX_E_WS here (dcx_solve_pnp_ransac_pool answers DCX_E_ARG).                   */
+int dcx_fisheye_solve_pnp_ransac_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows, const float* d_xy,
+                                      int batch, int pool, int col_count, int row_count, double square_len,
+                                      const double* h_camera9, const double* h_dist4, int iterations, double reproj_error,
+                                      int min_inliers, unsigned seed, void* d_workspace, size_t workspace_bytes, int32_t* d_status,
+                                      double* d_pose, int32_t* d_info, uint8_t* d_inliers, void* stream);
 size_t dcx_fisheye_calibrate_workspace_bytes(int batch);
 int dcx_fisheye_calibrate_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows,
                                const float* d_xy /* NULL = use integer rows x,y */, int batch, int pool,

@@ -60,6 +60,10 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-host", action="store_true", help="skip the host definition (for a profiler run)")
     ap.add_argument("--host-max-pairs", type=int, default=4096, help="run the host definition only up to this many pairs")
+    ap.add_argument("--models", default=None, metavar="M0,M1",
+                    help="the two cameras' models, pinhole or fisheye, e.g. fisheye,pinhole: tests/fisheye_rig_exact.py's scenes of two "
+                         "cameras 30 degrees apart (fisheye: the lenses F, F0; pinhole: P, P0) through stereo_calibrate_pool(models=...); "
+                         "the calibration yardstick is left out.  Unset: the all-pinhole run")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.kernel_stats:
@@ -70,12 +74,36 @@ def main():
     assert torch.cuda.is_available(), "stereo_probe measures the GPU kernels: no GPU visible"
     dev = torch.device("cuda", 0)
     size0 = (320, 240)
+    models = a.models.split(",") if a.models else None
+    if models is not None:
+        import fisheye_rig_exact as frx
+        assert len(models) == 2 and all(m in stereo.MODELS for m in models), f"--models takes two of {stereo.MODELS}"
+        names = tuple({"fisheye": ("F", "F0"), "pinhole": ("P", "P0")}[m][c] for c, m in enumerate(models))
     result = {"device": torch.cuda.get_device_name(dev), "board": list(sx.BOARD_S), "rig": "toe90", "cameras": "A/B", "sigma_px": 0.5,
               "reps": a.reps, "stereo_ms": {}, "lm_steps": {}, "lm_attempts": {}, "calib_cam0_ms": {}, "calib_lm_steps": {},
               "calib_lm_attempts": {}, "stereo_over_calib": {}, "host_ms": {}, "device_host_gap": {}}
     for n_rows in (16, 49):
         for n_pairs in (64, 512, 4096):
             key = f"T{n_pairs}_n{n_rows}"
+            if models is not None:
+                m = frx.scene(3000 + n_pairs + n_rows, n_pairs, (0, 30), names, sigma=0.5, rows=n_rows)
+                (K0, K1), (d0, d1) = frx.cam_args(m)
+                kps0, kps1, cams, board = m.kps[0], m.kps[1], (K0, d0, K1, d1), m.board
+                (p0, b, pool0), (p1, _, pool1) = corner_pool.pack_keypoints(kps0, dev), corner_pool.pack_keypoints(kps1, dev)
+                ms, d = timed(lambda: stereo.stereo_calibrate_pool(p0, p1, b, pool0, pool1, True, *board, *cams, models=models), a.reps)
+                assert d.status == stereo.STEREO_OK, (key, d.status)
+                result["cameras"], result["rig"] = "/".join(names), "30 degrees"
+                result["stereo_ms"][key], result["lm_steps"][key], result["lm_attempts"][key] = ms, d.iterations, d.attempts
+                if not a.no_host and n_pairs <= a.host_max_pairs:
+                    t0 = time.perf_counter()
+                    h = stereo.stereo_calibrate_host_full(kps0, kps1, *board, *cams, models=models)
+                    result["host_ms"][key] = (time.perf_counter() - t0) * 1e3
+                    result["device_host_gap"][key] = {
+                        "R_abs": float(np.abs(d.R - h.R).max()), "T_rel": float(np.linalg.norm(d.T - h.T) / np.linalg.norm(h.T)),
+                        "rms_rel": abs(d.rms - h.rms) / h.rms, "host_steps": h.iterations, "host_attempts": h.attempts,
+                        "pairs": [d.pairs_used, h.pairs_used]}
+                print(key, json.dumps({k: v.get(key) for k, v in result.items() if isinstance(v, dict)}), flush=True)
+                continue
             s = sx.scene(3000 + n_pairs + n_rows, n_pairs, "toe90", sx.BOARD_S, "A", "B", sigma=0.5, rows=n_rows)
             cams = sx.cam_args(s)
             (p0, b, pool0), (p1, _, pool1) = corner_pool.pack_keypoints(s.kps0, dev), corner_pool.pack_keypoints(s.kps1, dev)
