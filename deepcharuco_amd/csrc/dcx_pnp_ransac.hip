@@ -14,9 +14,10 @@
 // two runs give the same bits and the call can be captured in a hipGraph.
 // The pool type and its host check (CornerPool, corner_pool), frame_status, the sampler, the four-point homography, row_error2,
 // best_hypothesis and solve() are dcx_pnp_dev.h's; append_kept is dcx_mat_dev.h's.
-// The same two kernels on FisheyeCamera (dcx_fisheye_solve_pnp_ransac_pool): the sample's four pixels go through that model's
-// undistort, a sample with a pixel outside the model has no hypothesis, the rows are scored by forward projection through the
-// model, and solve() may answer DCX_PNP_DEGENERATE for a winner's inlier outside it.  Sampler, score order, mask and info are the same.
+// Both kernels are templates on the camera's class.  On FisheyeCamera (dcx_fisheye_solve_pnp_ransac_pool) the sample's four pixels
+// go through that model's undistort, a sample with a pixel outside the model has no hypothesis, the rows are scored by forward
+// projection through the model, and solve() may answer DCX_PNP_DEGENERATE for a winner's inlier outside it.  Sampler, score order,
+// mask and info are the same.
 #include "dcx_fisheye_dev.h"
 #include "dcx_pnp_dev.h"
 
@@ -60,11 +61,11 @@ __device__ __forceinline__ int hypothesis(const Frame& f, const CAM& cam, bool d
 }
 
 // Both kernels take the pool as loose __restrict__ parameters and make the CornerPool in their first line, as dcx_solve_pnp_kernel
-// does and for its reason (see there).
-// (restated on FisheyeCamera as dcx_fisheye_ransac_hypotheses_kernel below: a change here is a change there)
+// does and for its reason (see there).  CAM: PnpCamera or FisheyeCamera.
+template <class CAM>
 __global__ __launch_bounds__(kLanes) void dcx_pnp_ransac_hypotheses_kernel(
     const int32_t* __restrict__ counts, const int32_t* __restrict__ starts, const int32_t* __restrict__ rows,
-    const float* __restrict__ xy, int pool, int n_ids, int rm1, double square_len, PnpCamera cam, int iterations, double thr2,
+    const float* __restrict__ xy, int pool, int n_ids, int rm1, double square_len, CAM cam, int iterations, double thr2,
     uint32_t seed, int32_t* __restrict__ scores, double* __restrict__ poses) {
     const int b = blockIdx.x, h = blockIdx.y * kLanes + threadIdx.x;
     const CornerPool pl{counts, starts, rows, xy, pool, n_ids, rm1, square_len};
@@ -80,92 +81,10 @@ __global__ __launch_bounds__(kLanes) void dcx_pnp_ransac_hypotheses_kernel(
     for (int i = 0; i < 6; ++i) poses[6 * at + i] = p0[i];
 }
 
-// (restated on FisheyeCamera as dcx_fisheye_ransac_select_kernel below: a change here is a change there)
+template <class CAM>
 __global__ __launch_bounds__(kLanes) void dcx_pnp_ransac_select_kernel(
     const int32_t* __restrict__ counts, const int32_t* __restrict__ starts, const int32_t* __restrict__ rows,
-    const float* __restrict__ xy, int pool, int n_ids, int rm1, double square_len, PnpCamera cam, int iterations, double thr2,
-    int min_inliers, const int32_t* __restrict__ scores, const double* __restrict__ poses, int32_t* idx,
-    int32_t* __restrict__ status, double* __restrict__ pose, int32_t* __restrict__ info, uint8_t* __restrict__ inliers) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const CornerPool pl{counts, starts, rows, xy, pool, n_ids, rm1, square_len};
-    int n, s0;
-    int st = frame_status(pl, b, n, s0);
-    double out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int winner = -1, count = 0;
-    if (st == DCX_PNP_OK) {
-        int best, bh;
-        best_hypothesis(scores + (long long)b * iterations, iterations, best, bh);
-        if (best < 0) {
-            st = DCX_PNP_DEGENERATE;
-        } else {
-            winner = bh;
-            const Frame f = pl.frame(n, s0);
-            double p[6], R[9];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) p[i] = poses[6 * ((long long)b * iterations + winner) + i];
-            rodrigues(p, R);
-            int32_t* list = idx + s0;                      // this frame's share of the index list: its own slots
-            for (int base = 0; base < n; base += kLanes) {
-                const int i = base + lane;
-                bool in = false;
-                if (i < n) {
-                    double bx, by, u, v;
-                    f.load(i, bx, by, u, v);
-                    in = row_error2(R, p + 3, cam, bx, by, u, v) <= thr2;
-                    if (inliers) inliers[(long long)s0 + i] = in ? 1 : 0;
-                }
-                const int at = append_kept(in, lane, count);
-                if (in) list[at] = i;
-            }
-            __syncthreads();                               // one wave: the list is read below by other lanes than wrote it
-            if (count < max(min_inliers, 4)) {
-                st = DCX_PNP_NO_CONSENSUS;
-            } else {
-                const IndexedFrame g{f, list, count};
-                st = solve(g, cam, out);
-            }
-        }
-    }
-    if (st != DCX_PNP_OK) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) out[i] = 0.0;
-        count = 0;
-        // no pose, no inliers: every slot of the frame that lies in the pool (the lane that wrote a slot above rewrites it)
-        if (inliers && n > 0 && s0 >= 0)
-            for (long long i = lane; i < n && s0 + i < pl.pool; i += kLanes) inliers[s0 + i] = 0;
-    }
-    if (lane == 0) {
-        status[b] = st;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) pose[8 * (long long)b + i] = out[i];
-        info[2 * (long long)b] = count;
-        info[2 * (long long)b + 1] = winner;
-    }
-}
-
-// The two kernels on FisheyeCamera: the kernels above, text for text, with the camera's class changed (kernels of their own and not
-// one template for both, so that the pinhole kernels keep their names and their code).
-__global__ __launch_bounds__(kLanes) void dcx_fisheye_ransac_hypotheses_kernel(
-    const int32_t* __restrict__ counts, const int32_t* __restrict__ starts, const int32_t* __restrict__ rows,
-    const float* __restrict__ xy, int pool, int n_ids, int rm1, double square_len, FisheyeCamera cam, int iterations, double thr2,
-    uint32_t seed, int32_t* __restrict__ scores, double* __restrict__ poses) {
-    const int b = blockIdx.x, h = blockIdx.y * kLanes + threadIdx.x;
-    const CornerPool pl{counts, starts, rows, xy, pool, n_ids, rm1, square_len};
-    int n, s0;
-    if (frame_status(pl, b, n, s0) != DCX_PNP_OK) return;   // select reports it and reads no score
-    if (h >= iterations) return;
-    const Frame f = pl.frame(n, s0);
-    double p0[6] = {0, 0, 0, 0, 0, 0};
-    const int score = hypothesis(f, cam, has_distortion(cam), seed, h, thr2, p0);
-    const long long at = (long long)b * iterations + h;
-    scores[at] = score;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) poses[6 * at + i] = p0[i];
-}
-
-__global__ __launch_bounds__(kLanes) void dcx_fisheye_ransac_select_kernel(
-    const int32_t* __restrict__ counts, const int32_t* __restrict__ starts, const int32_t* __restrict__ rows,
-    const float* __restrict__ xy, int pool, int n_ids, int rm1, double square_len, FisheyeCamera cam, int iterations, double thr2,
+    const float* __restrict__ xy, int pool, int n_ids, int rm1, double square_len, CAM cam, int iterations, double thr2,
     int min_inliers, const int32_t* __restrict__ scores, const double* __restrict__ poses, int32_t* idx,
     int32_t* __restrict__ status, double* __restrict__ pose, int32_t* __restrict__ info, uint8_t* __restrict__ inliers) {
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -226,10 +145,10 @@ __global__ __launch_bounds__(kLanes) void dcx_fisheye_ransac_select_kernel(
 }
 
 // What the two entries share once their camera is made: the checks, the workspace's parts, the two launches.
-template <class CAM, class KH, class KS>
-int ransac_launch(const CornerPool& pl, const CAM& cam, KH hypotheses, KS select, int batch, int pool, int iterations,
-                  double reproj_error, int min_inliers, unsigned seed, void* d_workspace, size_t workspace_bytes, int32_t* d_status,
-                  double* d_pose, int32_t* d_info, uint8_t* d_inliers, void* stream) {
+template <class CAM>
+int ransac_launch(const CornerPool& pl, const CAM& cam, int batch, int pool, int iterations, double reproj_error, int min_inliers,
+                  unsigned seed, void* d_workspace, size_t workspace_bytes, int32_t* d_status, double* d_pose, int32_t* d_info,
+                  uint8_t* d_inliers, void* stream) {
     if (iterations < 1 || iterations > kMaxIterations || !isfinite(reproj_error) || !(reproj_error > 0)) return DCX_E_ARG;
     if (workspace_bytes < dcx_solve_pnp_ransac_workspace_bytes(batch, pool, iterations) || ((uintptr_t)d_workspace & 7)) return DCX_E_ARG;
     const size_t hyp = (size_t)batch * (size_t)iterations;
@@ -237,12 +156,12 @@ int ransac_launch(const CornerPool& pl, const CAM& cam, KH hypotheses, KS select
     int32_t* scores = (int32_t*)(poses + 6 * hyp);
     int32_t* idx = scores + hyp;
     const double thr2 = reproj_error * reproj_error;
-    hipLaunchKernelGGL(hypotheses, dim3((unsigned)batch, (unsigned)((iterations + kLanes - 1) / kLanes)), dim3(kLanes), 0,
-                       (hipStream_t)stream, pl.counts, pl.starts, pl.rows, pl.xy, pl.pool, pl.n_ids, pl.rm1, pl.square_len, cam,
-                       iterations, thr2, (uint32_t)seed, scores, poses);
-    hipLaunchKernelGGL(select, dim3((unsigned)batch), dim3(kLanes), 0, (hipStream_t)stream, pl.counts, pl.starts, pl.rows, pl.xy,
-                       pl.pool, pl.n_ids, pl.rm1, pl.square_len, cam, iterations, thr2, min_inliers, scores, poses, idx, d_status,
-                       d_pose, d_info, d_inliers);
+    hipLaunchKernelGGL(dcx_pnp_ransac_hypotheses_kernel<CAM>, dim3((unsigned)batch, (unsigned)((iterations + kLanes - 1) / kLanes)),
+                       dim3(kLanes), 0, (hipStream_t)stream, pl.counts, pl.starts, pl.rows, pl.xy, pl.pool, pl.n_ids, pl.rm1,
+                       pl.square_len, cam, iterations, thr2, (uint32_t)seed, scores, poses);
+    hipLaunchKernelGGL(dcx_pnp_ransac_select_kernel<CAM>, dim3((unsigned)batch), dim3(kLanes), 0, (hipStream_t)stream, pl.counts,
+                       pl.starts, pl.rows, pl.xy, pl.pool, pl.n_ids, pl.rm1, pl.square_len, cam, iterations, thr2, min_inliers, scores,
+                       poses, idx, d_status, d_pose, d_info, d_inliers);
     return (int)hipGetLastError();
 }
 
@@ -258,8 +177,8 @@ extern "C" int dcx_solve_pnp_ransac_pool(const int32_t* d_counts, const int32_t*
     PnpCamera cam;
     if (!corner_pool(d_counts, d_starts, d_rows, d_xy, batch, pool, col_count, row_count, square_len, pl)) return DCX_E_ARG;
     if (!h_camera9 || !d_status || !d_pose || !d_info || !d_workspace || !pnp_camera(h_camera9, h_dist, n_dist, cam)) return DCX_E_ARG;
-    return ransac_launch(pl, cam, dcx_pnp_ransac_hypotheses_kernel, dcx_pnp_ransac_select_kernel, batch, pool, iterations,
-                         reproj_error, min_inliers, seed, d_workspace, workspace_bytes, d_status, d_pose, d_info, d_inliers, stream);
+    return ransac_launch(pl, cam, batch, pool, iterations, reproj_error, min_inliers, seed, d_workspace, workspace_bytes, d_status,
+                         d_pose, d_info, d_inliers, stream);
 }
 
 extern "C" int dcx_fisheye_solve_pnp_ransac_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows,
@@ -275,8 +194,8 @@ extern "C" int dcx_fisheye_solve_pnp_ransac_pool(const int32_t* d_counts, const 
     // (a short workspace has its own code here, as in the entries after dcx_solve_pnp_ransac_pool, which keeps answering DCX_E_ARG)
     if (iterations >= 1 && iterations <= kMaxIterations && workspace_bytes < dcx_solve_pnp_ransac_workspace_bytes(batch, pool, iterations))
         return DCX_E_WS;
-    return ransac_launch(pl, cam, dcx_fisheye_ransac_hypotheses_kernel, dcx_fisheye_ransac_select_kernel, batch, pool, iterations,
-                         reproj_error, min_inliers, seed, d_workspace, workspace_bytes, d_status, d_pose, d_info, d_inliers, stream);
+    return ransac_launch(pl, cam, batch, pool, iterations, reproj_error, min_inliers, seed, d_workspace, workspace_bytes, d_status,
+                         d_pose, d_info, d_inliers, stream);
 }
 
 // workspace: poses f64 [B][iterations][6] | scores int32 [B][iterations] | inlier index list int32 [pool]

@@ -36,8 +36,10 @@
 //   trial           grid (timestamp, camera): dP_t = z - sum_c Y_c dX_c (cameras ascending), the view's trial cost; camera 0's block
 //                   also writes the trial pose and the timestamp's share of |dp|^2 and |p|^2
 //   decide          (one workgroup) lm_decide_block with STOP_FORCED
-// A rig with a fisheye camera in it (dcx_rig_calibrate_models_pool) runs init_views, evaluate and trial as their *_mixed_kernel
-// forms on a table of AnyCamera (dcx_stereo_dev.h); the other launches never see a camera and are the same.
+// init_views, evaluate and trial, the three that meet a camera, are templates on the camera table: RigCams, or MixedCams for a rig
+// with a fisheye camera in it (dcx_rig_calibrate_models_pool).  The kernels' text knows no model: on a table of AnyCamera the model is
+// chosen per view, inside the step (the AnyCamera overloads of view_solve, accumulate_view and view_cost in dcx_stereo_dev.h), and
+// uniformly per workgroup, which works on camera blockIdx.y alone.  The other launches never see a camera.
 // The LM loop runs on the host (lm_run): the call synchronises its stream and cannot be captured in a graph.  Every sum has a fixed
 // order (no atomics): two calls on the same input give the same bits.  No device memory is allocated.
 // The state is LmState<42, 48> whatever C is: the parameters past n stay zero, which adds exact zeros to lm_decide's two norms.
@@ -161,9 +163,10 @@ __device__ __forceinline__ void unpkn(int n, int e, int& a, int& b) {
 
 // ---------------------------------------------------------------------------------------------------------------- init
 
-// (restated on MixedCams as rig_init_views_mixed_kernel below: a change here is a change there)
-__global__ __launch_bounds__(kLanes) void rig_init_views_kernel(RigCams cams, int32_t* __restrict__ status,
-                                                                double* __restrict__ view_info, Ws ws) {
+// CAMS, here and in evaluate and trial: RigCams or MixedCams
+template <class CAMS>
+__global__ __launch_bounds__(kLanes) void rig_init_views_kernel(CAMS cams, int32_t* __restrict__ status, double* __restrict__ view_info,
+                                                                Ws ws) {
     const int t = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
     double out[8];
     int kept;
@@ -326,8 +329,8 @@ __device__ __forceinline__ void camera_x(const double* g, int c, double* x) {
     for (int i = 0; i < 6; ++i) x[i] = c ? g[6 * (c - 1) + i] : 0.0;
 }
 
-// (restated on MixedCams as rig_evaluate_mixed_kernel below: a change here is a change there)
-__global__ __launch_bounds__(kLanes) void rig_evaluate_kernel(RigCams cams, const int32_t* __restrict__ status, Ws ws) {
+template <class CAMS>
+__global__ __launch_bounds__(kLanes) void rig_evaluate_kernel(CAMS cams, const int32_t* __restrict__ status, Ws ws) {
     __shared__ double sj[2 * kLanes][kLdsStride];
     const int t = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
     if (ws.st->code != kNextEvaluate || !ws.used[t] || !usable(status, ws, t, c)) return;
@@ -543,8 +546,8 @@ __global__ __launch_bounds__(kSlices * kLanes) void rig_reduce_solve_kernel(int 
     }
 }
 
-// (restated on MixedCams as rig_trial_mixed_kernel below: a change here is a change there)
-__global__ __launch_bounds__(kLanes) void rig_trial_kernel(RigCams cams, const int32_t* __restrict__ status, Ws ws) {
+template <class CAMS>
+__global__ __launch_bounds__(kLanes) void rig_trial_kernel(CAMS cams, const int32_t* __restrict__ status, Ws ws) {
     const int t = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
     if (ws.st->code == kFinished || !ws.used[t]) return;
     const int C = ws.C;
@@ -621,116 +624,10 @@ __global__ __launch_bounds__(kRedThreads) void rig_decide_kernel(int batch, int 
         });
 }
 
-// ---------------------------------------------------------------------------------------------------------------- mixed rigs
-
-// init_views, evaluate and trial, the three kernels that meet a camera, on a table with model tags.  They restate the all-pinhole
-// kernels above line for line around with_camera(); a block works on camera blockIdx.y alone, so its branch on the model is uniform.
-// They are kernels of their own, after every other kernel of this file, and not one body shared with the kernels above: compiled
-// through a shared body the all-pinhole kernels come out scheduled differently, and they are to stay the code they were.
-__global__ __launch_bounds__(kLanes) void rig_init_views_mixed_kernel(MixedCams cams, int32_t* __restrict__ status,
-                                                                      double* __restrict__ view_info, Ws ws) {
-    const int t = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
-    double out[8];
-    int kept;
-    const int st = with_camera(cams.cam[c], [&](const auto& cam) { return view_solve(cams.pl[c], cam, t, ws.idx[c], ws.ident, out, kept); });
-    if (lane == 0) {
-        const long long v = (long long)t * ws.C + c;
-        status[v] = st;
-        view_info[2 * v] = 0.0;
-        view_info[2 * v + 1] = (double)kept;
-        ws.count[v] = kept;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) ws.vpose[6 * v + i] = st == DCX_PNP_OK ? out[i] : 0.0;
-    }
-}
-
-__global__ __launch_bounds__(kLanes) void rig_evaluate_mixed_kernel(MixedCams cams, const int32_t* __restrict__ status, Ws ws) {
-    __shared__ double sj[2 * kLanes][kLdsStride];
-    const int t = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
-    if (ws.st->code != kNextEvaluate || !ws.used[t] || !usable(status, ws, t, c)) return;
-    double x[6], p[6];
-    camera_x(ws.st->g, c, x);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) p[i] = ws.pose[(long long)t * 6 + i];
-    PairBasis B;
-    pair_basis<true>(x, p, B);
-    int ea[2], eb[2];
-    lane_entries<13, 2>(lane, ea, eb);
-    double acc[2] = {0, 0};
-    bool behind = false;
-    const IndexedFrame f = view_frame(cams.pl[c], ws, t, c);
-    with_camera(cams.cam[c], [&](const auto& cam) {
-        if (c) accumulate_view<true>(f, cam, B, sj, ea, eb, acc, behind);
-        else accumulate_view<false>(f, cam, B, sj, ea, eb, acc, behind);
-        return 0;
-    });
-    const bool inf = __any(behind);
-    double* m = ws.m + ((long long)t * ws.C + c) * kEntries;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int e = lane + kLanes * q;
-        if (e < kEntries) m[e] = (e == kCost && inf) ? INFINITY : acc[q];
-    }
-}
-
-__global__ __launch_bounds__(kLanes) void rig_trial_mixed_kernel(MixedCams cams, const int32_t* __restrict__ status, Ws ws) {
-    const int t = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
-    if (ws.st->code == kFinished || !ws.used[t]) return;
-    const int C = ws.C;
-    // the timestamp's trial pose p = pose - (z - sum_c Y_c dX_c), the same in every block of the timestamp
-    double p[6], dn = 0.0, pn = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        double s = ws.z[(long long)t * 6 + k];
-        for (int cc = 1; cc < C; ++cc) {         // (a camera that is not there: schur left Y_c = 0, which takes off exact zeros)
-            const double* y = ws.y + ((long long)t * (C - 1) + cc - 1) * 36 + k * 6;
-#pragma unroll
-            for (int j = 0; j < 6; ++j) s -= y[j] * ws.st->dg[6 * (cc - 1) + j];
-        }
-        const double p0 = ws.pose[(long long)t * 6 + k];
-        p[k] = p0 - s;
-        dn += (p[k] - p0) * (p[k] - p0);
-        pn += p0 * p0;
-    }
-    double cost = 0.0;
-    if (usable(status, ws, t, c)) {
-        double x[6];
-        camera_x(ws.st->g_trial, c, x);
-        PairBasis B;
-        pair_basis<false>(x, p, B);
-        const IndexedFrame f = view_frame(cams.pl[c], ws, t, c);
-        cost = with_camera(cams.cam[c], [&](const auto& cam) { return c ? view_cost<true>(f, cam, B) : view_cost<false>(f, cam, B); });
-    }
-    if (lane == 0) {
-        double* tr = ws.trial + (long long)t * (C + 2);
-        tr[c] = cost;
-        if (c == 0) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) ws.trial_pose[(long long)t * 6 + k] = p[k];
-            tr[C] = dn;
-            tr[C + 1] = pn;
-        }
-    }
-}
-
-// The kernels of a camera table
-template <class CAMS> struct Kernels;
-template <> struct Kernels<RigCams> {
-    static constexpr auto init_views = rig_init_views_kernel;
-    static constexpr auto evaluate = rig_evaluate_kernel;
-    static constexpr auto trial = rig_trial_kernel;
-};
-template <> struct Kernels<MixedCams> {
-    static constexpr auto init_views = rig_init_views_mixed_kernel;
-    static constexpr auto evaluate = rig_evaluate_mixed_kernel;
-    static constexpr auto trial = rig_trial_mixed_kernel;
-};
-
 // Everything after the camera table is made: the entry points' common body.
 template <class CAMS>
 int rig_calibrate(const CAMS& cams, const int* pools, int C, int batch, void* d_workspace, size_t workspace_bytes,
                   int32_t* d_view_status, double* d_pose, double* d_view_info, int32_t* h_parents, double* h_result, void* stream) {
-    using K = Kernels<CAMS>;
     const int n = 6 * (C - 1);
     if (!d_workspace || !d_view_status || !d_pose || !d_view_info || !h_parents || !h_result || ((uintptr_t)d_workspace & 7))
         return DCX_E_ARG;
@@ -750,7 +647,7 @@ int rig_calibrate(const CAMS& cams, const int* pools, int C, int batch, void* d_
         else if (pools[c] > n_ident) n_ident = pools[c];
     }
     if (n_ident > 0) hipLaunchKernelGGL(stereo_ident_kernel, dim3((unsigned)((n_ident + 255) / 256)), dim3(256), 0, s, n_ident, ws.ident);
-    hipLaunchKernelGGL(K::init_views, views, wave, 0, s, cams, d_view_status, d_view_info, ws);
+    hipLaunchKernelGGL(rig_init_views_kernel<CAMS>, views, wave, 0, s, cams, d_view_status, d_view_info, ws);
     hipLaunchKernelGGL(rig_stamps_kernel, per_lane, wave, 0, s, batch, d_view_status, d_pose, ws);
     DCX_CHECK_HIP(hipGetLastError());
 
@@ -825,15 +722,15 @@ int rig_calibrate(const CAMS& cams, const int* pools, int C, int batch, void* d_
         }
     }
     hipLaunchKernelGGL(rig_start_kernel, one, wave, 0, s, med, tree, n_stamps, (double)points, batch, d_view_status, ws);
-    hipLaunchKernelGGL(K::evaluate, views, wave, 0, s, cams, d_view_status, ws);
+    hipLaunchKernelGGL(rig_evaluate_kernel<CAMS>, views, wave, 0, s, cams, d_view_status, ws);
     hipLaunchKernelGGL(rig_decide_kernel, one, red, 0, s, batch, 1, d_view_status, d_pose, d_view_info, ws);
     DCX_CHECK_HIP(hipGetLastError());
     DCX_CHECK_HIP(lm_run(s, &ws.st->code, kJointMaxIter, [&](bool evaluate) {
-        if (evaluate) hipLaunchKernelGGL(K::evaluate, views, wave, 0, s, cams, d_view_status, ws);
+        if (evaluate) hipLaunchKernelGGL(rig_evaluate_kernel<CAMS>, views, wave, 0, s, cams, d_view_status, ws);
         hipLaunchKernelGGL(rig_schur_kernel, stamps, wave, 0, s, d_view_status, ws);
         hipLaunchKernelGGL(rig_reduce_kernel, blocks, dim3(kReduceThreads), 0, s, batch, d_view_status, ws);
         hipLaunchKernelGGL(rig_reduce_solve_kernel, one, solve_threads, 0, s, chunks, ws);
-        hipLaunchKernelGGL(K::trial, views, wave, 0, s, cams, d_view_status, ws);
+        hipLaunchKernelGGL(rig_trial_kernel<CAMS>, views, wave, 0, s, cams, d_view_status, ws);
         hipLaunchKernelGGL(rig_decide_kernel, one, red, 0, s, batch, 0, d_view_status, d_pose, d_view_info, ws);
     }));
     double res[kResWords];

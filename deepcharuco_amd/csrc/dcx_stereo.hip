@@ -115,8 +115,11 @@ __device__ __forceinline__ IndexedFrame view_frame(const MaskedPool& pl, const W
 
 // ---------------------------------------------------------------------------------------------------------------- init
 
-// (restated on AnyCamera as stereo_init_views_mixed_kernel below: a change here is a change there)
-__global__ __launch_bounds__(kLanes) void stereo_init_views_kernel(MaskedPool pl0, MaskedPool pl1, PnpCamera cam0, PnpCamera cam1,
+// CAM, here and in evaluate and trial: PnpCamera, or AnyCamera for a pair with a fisheye camera in it
+// (dcx_stereo_calibrate_models_pool).  The kernels' text knows no model: on AnyCamera it is chosen inside the step, by the AnyCamera
+// overloads of view_solve, accumulate_view and view_cost (dcx_stereo_dev.h); the tags are kernel arguments, so every branch is uniform.
+template <class CAM>
+__global__ __launch_bounds__(kLanes) void stereo_init_views_kernel(MaskedPool pl0, MaskedPool pl1, CAM cam0, CAM cam1,
                                                                    int32_t* __restrict__ status, double* __restrict__ view_info,
                                                                    Ws ws) {
     const int t = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
@@ -197,9 +200,8 @@ __global__ __launch_bounds__(kLanes) void stereo_rig_kernel(Med med, int npairs,
 
 // ---------------------------------------------------------------------------------------------------------------- LM
 
-// (restated on AnyCamera as stereo_evaluate_mixed_kernel below: a change here is a change there)
-__global__ __launch_bounds__(kLanes) void stereo_evaluate_kernel(MaskedPool pl0, MaskedPool pl1, PnpCamera cam0, PnpCamera cam1,
-                                                                 Ws ws) {
+template <class CAM>
+__global__ __launch_bounds__(kLanes) void stereo_evaluate_kernel(MaskedPool pl0, MaskedPool pl1, CAM cam0, CAM cam1, Ws ws) {
     __shared__ double sj[2 * kLanes][kLdsStride];
     const int t = blockIdx.x, lane = threadIdx.x;
     if (ws.st->code != kNextEvaluate || !ws.pair[t]) return;
@@ -300,8 +302,8 @@ __global__ __launch_bounds__(kSlices * kLanes) void stereo_reduce_solve_kernel(i
     }
 }
 
-// (restated on AnyCamera as stereo_trial_mixed_kernel below: a change here is a change there)
-__global__ __launch_bounds__(kLanes) void stereo_trial_kernel(MaskedPool pl0, MaskedPool pl1, PnpCamera cam0, PnpCamera cam1, Ws ws) {
+template <class CAM>
+__global__ __launch_bounds__(kLanes) void stereo_trial_kernel(MaskedPool pl0, MaskedPool pl1, CAM cam0, CAM cam1, Ws ws) {
     const int t = blockIdx.x, lane = threadIdx.x;
     if (ws.st->code == kFinished || !ws.pair[t]) return;
     double x[6], p[6], dn, pn;
@@ -346,99 +348,11 @@ __global__ __launch_bounds__(kRedThreads) void stereo_decide_kernel(int batch, i
         });
 }
 
-// ---------------------------------------------------------------------------------------------------------------- mixed pairs
-
-// init_views, evaluate and trial, the three kernels that meet a camera, with a model tag on either camera.  They restate the
-// all-pinhole kernels above line for line around with_camera() (the tags are kernel arguments, so every branch is uniform).  They
-// are kernels of their own, after every other kernel of this file, and not one body shared with the kernels above: compiled through
-// a shared body all-pinhole kernels come out scheduled differently (seen in dcx_rig.hip), and they are to stay the code they were.
-__global__ __launch_bounds__(kLanes) void stereo_init_views_mixed_kernel(MaskedPool pl0, MaskedPool pl1, AnyCamera cam0, AnyCamera cam1,
-                                                                   int32_t* __restrict__ status, double* __restrict__ view_info,
-                                                                   Ws ws) {
-    const int t = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
-    const MaskedPool pl = c ? pl1 : pl0;
-    double out[8];
-    int kept;
-    const int st = with_camera(c ? cam1 : cam0, [&](const auto& cam) { return view_solve(pl, cam, t, c ? ws.idx1 : ws.idx0, ws.ident, out, kept); });
-    if (lane == 0) {
-        const long long v = 2 * (long long)t + c;
-        status[v] = st;
-        view_info[2 * v] = 0.0;
-        view_info[2 * v + 1] = (double)kept;
-        ws.count[v] = kept;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) ws.vpose[6 * v + i] = st == DCX_PNP_OK ? out[i] : 0.0;
-    }
-}
-
-__global__ __launch_bounds__(kLanes) void stereo_evaluate_mixed_kernel(MaskedPool pl0, MaskedPool pl1, AnyCamera cam0, AnyCamera cam1,
-                                                                 Ws ws) {
-    __shared__ double sj[2 * kLanes][kLdsStride];
-    const int t = blockIdx.x, lane = threadIdx.x;
-    if (ws.st->code != kNextEvaluate || !ws.pair[t]) return;
-    double x[6], p[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        x[i] = ws.st->g[i];
-        p[i] = ws.pose[(long long)t * 6 + i];
-    }
-    PairBasis B;
-    pair_basis<true>(x, p, B);
-    int ea[2], eb[2];
-    lane_entries<13, 2>(lane, ea, eb);
-    double acc[2] = {0, 0};
-    bool behind = false;
-    with_camera(cam0, [&](const auto& cam) { accumulate_view<false>(view_frame(pl0, ws, t, 0), cam, B, sj, ea, eb, acc, behind); return 0; });
-    with_camera(cam1, [&](const auto& cam) { accumulate_view<true>(view_frame(pl1, ws, t, 1), cam, B, sj, ea, eb, acc, behind); return 0; });
-    const bool inf = __any(behind);
-    double* m = ws.m + (long long)t * kEntries;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int e = lane + kLanes * q;
-        if (e < kEntries) m[e] = (e == kCost && inf) ? INFINITY : acc[q];
-    }
-}
-
-__global__ __launch_bounds__(kLanes) void stereo_trial_mixed_kernel(MaskedPool pl0, MaskedPool pl1, AnyCamera cam0, AnyCamera cam1, Ws ws) {
-    const int t = blockIdx.x, lane = threadIdx.x;
-    if (ws.st->code == kFinished || !ws.pair[t]) return;
-    double x[6], p[6], dn, pn;
-    lm_trial_pose<6>(ws.yz + (long long)t * kYZ, ws.st->dg, ws.pose + (long long)t * 6, p, dn, pn);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) x[k] = ws.st->g_trial[k];
-    PairBasis B;
-    pair_basis<false>(x, p, B);
-    const double c0 = with_camera(cam0, [&](const auto& cam) { return view_cost<false>(view_frame(pl0, ws, t, 0), cam, B); });
-    const double c1 = with_camera(cam1, [&](const auto& cam) { return view_cost<true>(view_frame(pl1, ws, t, 1), cam, B); });
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) ws.trial_pose[(long long)t * 6 + k] = p[k];
-        ws.trial[(long long)t * 4 + 0] = c0;
-        ws.trial[(long long)t * 4 + 1] = c1;
-        ws.trial[(long long)t * 4 + 2] = dn;
-        ws.trial[(long long)t * 4 + 3] = pn;
-    }
-}
-
-// The kernels of a camera class
-template <class CAM> struct Kernels;
-template <> struct Kernels<PnpCamera> {
-    static constexpr auto init_views = stereo_init_views_kernel;
-    static constexpr auto evaluate = stereo_evaluate_kernel;
-    static constexpr auto trial = stereo_trial_kernel;
-};
-template <> struct Kernels<AnyCamera> {
-    static constexpr auto init_views = stereo_init_views_mixed_kernel;
-    static constexpr auto evaluate = stereo_evaluate_mixed_kernel;
-    static constexpr auto trial = stereo_trial_mixed_kernel;
-};
-
 // Everything after the two cameras are made: the entry points' common body.
 template <class CAM>
 int stereo_calibrate(MaskedPool pl0, MaskedPool pl1, const CAM& cam0, const CAM& cam1, int batch, int pool0, int pool1,
                      void* d_workspace, size_t workspace_bytes, int32_t* d_view_status, double* d_pose, double* d_view_info,
                      double* h_result, void* stream) {
-    using K = Kernels<CAM>;
     const uint8_t *d_mask0 = pl0.mask, *d_mask1 = pl1.mask;
     if (workspace_bytes < ws_layout(nullptr, batch, pool0, pool1, nullptr)) return DCX_E_WS;
     Ws ws;
@@ -453,7 +367,7 @@ int stereo_calibrate(MaskedPool pl0, MaskedPool pl1, const CAM& cam0, const CAM&
     if (d_mask1) hipLaunchKernelGGL(stereo_overlap_kernel, stamps, wave, 0, s, pl1.p, batch, ws.head);
     const int n_ident = !d_mask0 && !d_mask1 ? (pool0 > pool1 ? pool0 : pool1) : !d_mask0 ? pool0 : !d_mask1 ? pool1 : 0;
     if (n_ident > 0) hipLaunchKernelGGL(stereo_ident_kernel, dim3((unsigned)((n_ident + 255) / 256)), dim3(256), 0, s, n_ident, ws.ident);
-    hipLaunchKernelGGL(K::init_views, views, wave, 0, s, pl0, pl1, cam0, cam1, d_view_status, d_view_info, ws);
+    hipLaunchKernelGGL(stereo_init_views_kernel<CAM>, views, wave, 0, s, pl0, pl1, cam0, cam1, d_view_status, d_view_info, ws);
     hipLaunchKernelGGL(stereo_pairs_kernel, per_lane, wave, 0, s, batch, d_view_status, d_pose, ws);
     DCX_CHECK_HIP(hipGetLastError());
 
@@ -484,20 +398,32 @@ int stereo_calibrate(MaskedPool pl0, MaskedPool pl1, const CAM& cam0, const CAM&
         }
     }
     hipLaunchKernelGGL(stereo_rig_kernel, one, wave, 0, s, med, npairs, batch, ws);
-    hipLaunchKernelGGL(K::evaluate, stamps, wave, 0, s, pl0, pl1, cam0, cam1, ws);
+    hipLaunchKernelGGL(stereo_evaluate_kernel<CAM>, stamps, wave, 0, s, pl0, pl1, cam0, cam1, ws);
     hipLaunchKernelGGL(stereo_decide_kernel, one, red, 0, s, batch, 1, d_pose, d_view_info, ws);
     DCX_CHECK_HIP(hipGetLastError());
     DCX_CHECK_HIP(lm_run(s, &ws.st->code, kJointMaxIter, [&](bool evaluate) {
-        if (evaluate) hipLaunchKernelGGL(K::evaluate, stamps, wave, 0, s, pl0, pl1, cam0, cam1, ws);
+        if (evaluate) hipLaunchKernelGGL(stereo_evaluate_kernel<CAM>, stamps, wave, 0, s, pl0, pl1, cam0, cam1, ws);
         hipLaunchKernelGGL(stereo_schur_kernel, stamps, wave, 0, s, ws);
         hipLaunchKernelGGL(stereo_reduce_kernel, blocks, wave, 0, s, batch, ws);
         hipLaunchKernelGGL(stereo_reduce_solve_kernel, one, solve_threads, 0, s, chunks, ws);
-        hipLaunchKernelGGL(K::trial, stamps, wave, 0, s, pl0, pl1, cam0, cam1, ws);
+        hipLaunchKernelGGL(stereo_trial_kernel<CAM>, stamps, wave, 0, s, pl0, pl1, cam0, cam1, ws);
         hipLaunchKernelGGL(stereo_decide_kernel, one, red, 0, s, batch, 0, d_pose, d_view_info, ws);
     }));
     DCX_CHECK_HIP(hipMemcpyAsync(h_result, ws.st->result, 16 * sizeof(double), hipMemcpyDeviceToHost, s));
     DCX_CHECK_HIP(hipStreamSynchronize(s));
     return 0;
+}
+
+// The two pools and the pointers every entry point checks before it makes its cameras -> false if anything is refused
+bool pools_and_outputs(const int32_t* d_counts0, const int32_t* d_starts0, const int32_t* d_rows0, const float* d_xy0,
+                       const int32_t* d_counts1, const int32_t* d_starts1, const int32_t* d_rows1, const float* d_xy1, int batch,
+                       int pool0, int pool1, int col_count, int row_count, double square_len, const void* d_workspace,
+                       const int32_t* d_view_status, const double* d_pose, const double* d_view_info, const double* h_result,
+                       CornerPool& p0, CornerPool& p1) {
+    if (!corner_pool(d_counts0, d_starts0, d_rows0, d_xy0, batch, pool0, col_count, row_count, square_len, p0) ||
+        !corner_pool(d_counts1, d_starts1, d_rows1, d_xy1, batch, pool1, col_count, row_count, square_len, p1))
+        return false;
+    return d_workspace && d_view_status && d_pose && d_view_info && h_result && !((uintptr_t)d_workspace & 7);
 }
 
 }  // namespace
@@ -516,10 +442,9 @@ extern "C" int dcx_stereo_calibrate_pool(const int32_t* d_counts0, const int32_t
                                          size_t workspace_bytes, int32_t* d_view_status, double* d_pose, double* d_view_info,
                                          double* h_result, void* stream) {
     MaskedPool pl0{{}, d_mask0}, pl1{{}, d_mask1};
-    if (!corner_pool(d_counts0, d_starts0, d_rows0, d_xy0, batch, pool0, col_count, row_count, square_len, pl0.p) ||
-        !corner_pool(d_counts1, d_starts1, d_rows1, d_xy1, batch, pool1, col_count, row_count, square_len, pl1.p))
+    if (!pools_and_outputs(d_counts0, d_starts0, d_rows0, d_xy0, d_counts1, d_starts1, d_rows1, d_xy1, batch, pool0, pool1, col_count,
+                           row_count, square_len, d_workspace, d_view_status, d_pose, d_view_info, h_result, pl0.p, pl1.p))
         return DCX_E_ARG;
-    if (!d_workspace || !d_view_status || !d_pose || !d_view_info || !h_result || ((uintptr_t)d_workspace & 7)) return DCX_E_ARG;
     PnpCamera cam0, cam1;
     if (!pnp_camera(h_camera9_0, h_dist0, n_dist0, cam0) || !pnp_camera(h_camera9_1, h_dist1, n_dist1, cam1)) return DCX_E_ARG;
     return stereo_calibrate(pl0, pl1, cam0, cam1, batch, pool0, pool1, d_workspace, workspace_bytes, d_view_status, d_pose,
@@ -543,10 +468,9 @@ extern "C" int dcx_stereo_calibrate_models_pool(const int32_t* d_counts0, const 
                                          h_camera9_1, h_dist1, n_dist1, d_workspace, workspace_bytes, d_view_status, d_pose,
                                          d_view_info, h_result, stream);
     MaskedPool pl0{{}, d_mask0}, pl1{{}, d_mask1};
-    if (!corner_pool(d_counts0, d_starts0, d_rows0, d_xy0, batch, pool0, col_count, row_count, square_len, pl0.p) ||
-        !corner_pool(d_counts1, d_starts1, d_rows1, d_xy1, batch, pool1, col_count, row_count, square_len, pl1.p))
+    if (!pools_and_outputs(d_counts0, d_starts0, d_rows0, d_xy0, d_counts1, d_starts1, d_rows1, d_xy1, batch, pool0, pool1, col_count,
+                           row_count, square_len, d_workspace, d_view_status, d_pose, d_view_info, h_result, pl0.p, pl1.p))
         return DCX_E_ARG;
-    if (!d_workspace || !d_view_status || !d_pose || !d_view_info || !h_result || ((uintptr_t)d_workspace & 7)) return DCX_E_ARG;
     AnyCamera cam0, cam1;
     if (!any_camera(model0, h_camera9_0, h_dist0, n_dist0, cam0) || !any_camera(model1, h_camera9_1, h_dist1, n_dist1, cam1))
         return DCX_E_ARG;

@@ -7,8 +7,10 @@
 //                                                [J_X (6) | J_P (6)]; the reference camera's rows (SECOND = false) have J_X = 0
 //   accumulate_view, view_cost                   a view's rows added to its packed 13 x 13 / its trial cost
 //   AnyCamera, any_camera, with_camera           a camera of either model behind a tag, for rigs whose cameras differ
+//   view_solve, accumulate_view, view_cost       on AnyCamera: the same step on the camera's own class, through with_camera
 // view_solve, stereo_row, accumulate_view and view_cost are templates on the camera class, as dcx_pnp_dev.h's solver is: PnpCamera
-// (dcx_camera_dev.h) or FisheyeCamera (dcx_fisheye_dev.h).
+// (dcx_camera_dev.h) or FisheyeCamera (dcx_fisheye_dev.h).  The three that a kernel calls have an AnyCamera overload each, so a
+// kernel is one text for a plain camera and for a tagged one: the model is chosen inside the step, not around the kernel's body.
 // Everything is force-inlined and has internal linkage, so each translation unit compiles its own copy.
 #pragma once
 #include "dcx_fisheye_dev.h"
@@ -213,6 +215,24 @@ __device__ __forceinline__ double view_cost(const IndexedFrame& f, const CAM& ca
     }
     wave_sum(c);
     return c[0];
+}
+
+// The three steps that take a camera, on a camera of either model: the same step on the camera's own class.  Partial ordering
+// prefers these to the templates on CAM, so a kernel that is a template on its camera type reads the same for both.
+__device__ __forceinline__ int view_solve(const MaskedPool& pl, const AnyCamera& cam, int t, int32_t* lists, const int32_t* ident,
+                                          double (&out)[8], int& kept) {
+    return with_camera(cam, [&](const auto& k) { return view_solve(pl, k, t, lists, ident, out, kept); });
+}
+
+template <bool SECOND>
+__device__ __forceinline__ void accumulate_view(const IndexedFrame& f, const AnyCamera& cam, const PairBasis& B,
+                                                double (*sj)[kLdsStride], const int* ea, const int* eb, double* acc, bool& behind) {
+    with_camera(cam, [&](const auto& k) { accumulate_view<SECOND>(f, k, B, sj, ea, eb, acc, behind); return 0; });
+}
+
+template <bool SECOND>
+__device__ __forceinline__ double view_cost(const IndexedFrame& f, const AnyCamera& cam, const PairBasis& B) {
+    return with_camera(cam, [&](const auto& k) { return view_cost<SECOND>(f, k, B); });
 }
 
 }  // namespace

@@ -1,12 +1,17 @@
 """Refactoring aid: is the gfx950 device code of this tree the same as REV's?  Compiles the named translation units of
 deepcharuco_amd/csrc (default dcx_conv_mfma.hip) to assembly with the Makefile's flags, once from this tree and once from
-`git archive REV`, and compares kernel by kernel after dropping the __hip_cuid_ lines (a hash of the source text).  No GPU.
+`git archive REV`, and compares kernel by kernel after dropping the __hip_cuid_ lines (a hash of the source text), the `;` comments
+(`Loop: Header=BB7_5` names the kernel's position in the file) and, for the same reason, the position in local labels (.LBB7_5).  No GPU.
 For a kernel that DIFFERS it also says whether every floating-point arithmetic opcode (the v_*_f64 and v_*_f32 instructions but
 compares and moves) is used as often on both sides: the same counts mean rescheduled, other counts mean recomputed.  The encoding
 suffixes (_e32, _e64, _dpp, _sdwa) are dropped, and v_fmac counts as v_fma: the same operation with the addend's register tied.
 A kernel whose parameter list changed has another mangled name: such kernels are paired by their unmangled function name
-(where that is unique on both sides) and compared like the rest.
-usage: python tools/isa_same.py REV [file.hip ...]      exit status 0 only if every kernel is identical"""
+(where that is unique on both sides) and compared like the rest.  A kernel that became a template has several instantiations of
+that name here: the one whose template argument names a class of the base symbol's own parameter list is its pair
+(f(RigCams, ...) with f<RigCams>).  A renamed kernel is paired by hand: --pair BASE_NAME=SUBSTRING[+SUBSTRING ...] pairs the base's
+kernel of that unmangled name with the one kernel here whose symbol holds every SUBSTRING.
+usage: python tools/isa_same.py REV [--pair BASE_NAME=SUB[+SUB]] ... [file.hip ...]
+exit status 0 only if every kernel is identical"""
 import collections, os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,7 +58,8 @@ def kernels(s):
     for m in re.finditer(r"^\t\.amdhsa_kernel (\S+)\n.*?\.end_amdhsa_kernel\n", s, re.M | re.S):
         sym = m.group(1)
         start = re.search(r"^%s:[^\n]*\n" % re.escape(sym), s, re.M).end()
-        body = s[start:s.index(".Lfunc_end", start)]
+        body = "\n".join(l for l in (l.split(";")[0].rstrip() for l in s[start:s.index(".Lfunc_end", start)].split("\n")) if l)
+        body = re.sub(r"\.LBB\d+_", ".LBB_", body)
         n_ins = sum(1 for l in body.split("\n") if l.startswith("\t") and not l.strip().startswith((".", ";")))
         res[sym] = (body + m.group(0), meta.get(sym, {}), n_ins, fp_ops(body))
     return res
@@ -68,10 +74,43 @@ def bare_name(sym):
     return parts[-1] if parts else sym
 
 
+def name_end(sym):
+    """where the function name inside a mangled symbol ends"""
+    at = sym.find(bare_name(sym))
+    return len(sym) if at < 0 else at + len(bare_name(sym))
+
+
+def template_classes(sym):
+    """the class names in the template argument list of a mangled function symbol ([] if it is no template's instantiation)"""
+    rest, names, at, depth = sym[name_end(sym):], [], 1, 0
+    if not rest.startswith("I"):
+        return names
+    while at < len(rest):
+        if (m := re.compile(r"\d+").match(rest, at)):
+            at = m.end() + int(m.group())
+            names.append(rest[m.end():at])
+        elif (m := re.compile(r"S[0-9A-Z]*_").match(rest, at)):
+            at = m.end()
+        elif rest[at] == "E" and depth == 0:
+            break
+        else:
+            depth += {"N": 1, "E": -1}.get(rest[at], 0)
+            at += 1
+    return names
+
+
 def main():
-    if len(sys.argv) < 2:
+    args, by_hand = sys.argv[1:], {}
+    while "--pair" in args:
+        at = args.index("--pair")
+        if at + 1 >= len(args) or "=" not in args[at + 1]:
+            sys.exit(__doc__)
+        name, subs = args[at + 1].split("=", 1)
+        by_hand[name] = subs.split("+")
+        del args[at:at + 2]
+    if not args:
         sys.exit(__doc__)
-    rev, units = sys.argv[1], sys.argv[2:] or ["dcx_conv_mfma.hip"]
+    rev, units = args[0], args[1:] or ["dcx_conv_mfma.hip"]
     dirty = git("status", "--porcelain", "--", CSRC, "include") != ""
     print("base  %s (%s)" % (git("rev-parse", rev), rev))
     print("this  %s%s" % (git("rev-parse", "HEAD"), " + working-tree changes" if dirty else ""))
@@ -88,11 +127,20 @@ def main():
                 fb = ex.submit(compile_s, ROOT, unit, os.path.join(tmp, "b.s"))
                 ka, kb = kernels(fa.result()), kernels(fb.result())
             print("%s: %d kernels at the base, %d here" % (unit, len(ka), len(kb)))
-            # a kernel with a new parameter list: this tree's symbol is compared under the base's, if the function name is unique
+            # a kernel with a new parameter list or a new name: this tree's symbol is compared under the base's, if one answers
             only_a, only_b = [k for k in ka if k not in kb], [k for k in kb if k not in ka]
             for k in only_a:
-                here = [o for o in only_b if bare_name(o) == bare_name(k)]
-                if len(here) == 1 and sum(bare_name(o) == bare_name(k) for o in only_a) == 1:
+                if sum(bare_name(o) == bare_name(k) for o in only_a) != 1:
+                    continue
+                if bare_name(k) in by_hand:
+                    here = [o for o in only_b if all(sub in o for sub in by_hand[bare_name(k)])]
+                else:
+                    here = [o for o in only_b if bare_name(o) == bare_name(k)]
+                    if len(here) > 1:
+                        own = k[name_end(k):]
+                        here = [o for o in here if (c := template_classes(o)) and all("%d%s" % (len(n), n) in own for n in c)]
+                if len(here) == 1:
+                    only_b.remove(here[0])
                     body, *rest = kb.pop(here[0])
                     kb[k] = (body.replace(here[0], k), *rest)
                     print("  paired     %s  <-  %s" % (k, here[0]))

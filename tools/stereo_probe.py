@@ -6,8 +6,8 @@ on the same inputs, and, in the same process, the yardstick: the intrinsics cali
 Scenes: tests/stereo_exact.py's, sigma = 0.5 px, the 7x11 board (60 ids), cameras A (no distortion) and B (five coefficients), the
 90 degree toe-in rig; "16 rows" = a random 16 of the 60 ids per view, drawn independently for the two cameras.  Device wall time:
 the whole call (it synchronises: the rig init's medians and the LM loop's state word are read on the host), median of `--reps`
-calls after one warm-up, the pools already on the device.  `rocprofv3 --kernel-trace --stats -- python tools/stereo_probe.py
---no-host` gives the per-kernel times.  Prints one JSON object and writes it to --out.
+calls after one warm-up, the pools already on the device; "bits" is the result's rms and T as hex, to compare two builds (DCX_LIB
+selects one).  `rocprofv3 --kernel-trace --stats -- python tools/stereo_probe.py --no-host` gives the per-kernel times.  Prints one JSON object and writes it to --out.
 
     python tools/stereo_probe.py --out profiles/stereo_probe.json
 """
@@ -80,7 +80,7 @@ def main():
         assert len(models) == 2 and all(m in stereo.MODELS for m in models), f"--models takes two of {stereo.MODELS}"
         names = tuple({"fisheye": ("F", "F0"), "pinhole": ("P", "P0")}[m][c] for c, m in enumerate(models))
     result = {"device": torch.cuda.get_device_name(dev), "board": list(sx.BOARD_S), "rig": "toe90", "cameras": "A/B", "sigma_px": 0.5,
-              "reps": a.reps, "stereo_ms": {}, "lm_steps": {}, "lm_attempts": {}, "calib_cam0_ms": {}, "calib_lm_steps": {},
+              "reps": a.reps, "stereo_ms": {}, "lm_steps": {}, "lm_attempts": {}, "bits": {}, "calib_cam0_ms": {}, "calib_lm_steps": {},
               "calib_lm_attempts": {}, "stereo_over_calib": {}, "host_ms": {}, "device_host_gap": {}}
     for n_rows in (16, 49):
         for n_pairs in (64, 512, 4096):
@@ -94,6 +94,7 @@ def main():
                 assert d.status == stereo.STEREO_OK, (key, d.status)
                 result["cameras"], result["rig"] = "/".join(names), "30 degrees"
                 result["stereo_ms"][key], result["lm_steps"][key], result["lm_attempts"][key] = ms, d.iterations, d.attempts
+                result["bits"][key] = {"rms": float(d.rms).hex(), "T": [float(v).hex() for v in np.ravel(d.T)]}
                 if not a.no_host and n_pairs <= a.host_max_pairs:
                     t0 = time.perf_counter()
                     h = stereo.stereo_calibrate_host_full(kps0, kps1, *board, *cams, models=models)
@@ -112,6 +113,7 @@ def main():
             cms, c = timed(lambda: calib.calibrate_charuco_pool(p0, b, pool0, True, *s.board, size0), a.reps)
             assert c.status == calib.CALIB_OK, (key, c.status)
             result["stereo_ms"][key], result["lm_steps"][key], result["lm_attempts"][key] = ms, d.iterations, d.attempts
+            result["bits"][key] = {"rms": float(d.rms).hex(), "T": [float(v).hex() for v in np.ravel(d.T)]}
             result["calib_cam0_ms"][key], result["calib_lm_steps"][key], result["calib_lm_attempts"][key] = cms, c.iterations, c.attempts
             result["stereo_over_calib"][key] = ms / cms
             if not a.no_host and n_pairs <= a.host_max_pairs:
