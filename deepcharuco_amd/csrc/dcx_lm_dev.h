@@ -1,5 +1,5 @@
-// dcx_lm_dev.h -- the joint Levenberg-Marquardt driver of the calibrations (dcx_calib.hip over NG = 9 intrinsics,
-// dcx_stereo.hip over NG = 6 rig parameters, dcx_rig.hip over NG = 42 of which a rig of C cameras uses 6 (C - 1); every unit -- a
+// dcx_lm_dev.h -- the joint Levenberg-Marquardt driver of the calibrations (dcx_calib_dev.h over NG = 9 pinhole or 8 fisheye
+// intrinsics, dcx_stereo.hip over NG = 6 rig parameters, dcx_rig.hip over NG = 42 of which a rig of C cameras uses 6 (C - 1); every unit -- a
 // view, a pair, a timestamp -- adds 6 pose parameters that couple only to the NG global ones), one copy.  deepcharuco_amd/_lm.py restates it for the host definitions.  Three parts:
 //   1. the automaton (CvLevMarq's rules), plain C++17 that a host compiler takes without any HIP header, so a stand-alone program
 //      can walk its branches (tests/lm_host_main.cpp): LmState, lm_reset, lm_fail, lm_decide;
@@ -13,8 +13,9 @@
 // STOP_FORCED is the one policy the two solvers do not share: a step forced with a cost that is not finite (a point behind a
 // camera) ends the stereo solve with DEGENERATE / NONFINITE, while calibration goes on from prev_cost = inf as it always has.
 // Deliberately NOT in here: the reductions in front of the global solve (calibration 8 slices x 128 added serially, stereo the
-// two fan-ins kChunk / kSlices: the order of a sum is part of the output bits), calibration's rolled 9x9 Cholesky on LDS and its
-// spelt-out evaluate loop (both explained where they stand).  calib_trial_kernel spells lm_trial_pose<9> out for its SGPR spills.
+// two fan-ins kChunk / kSlices: the order of a sum is part of the output bits), calibration's rolled NG x NG Cholesky on LDS and
+// its spelt-out evaluate loop (both explained where they stand, in dcx_calib_dev.h).  calib_trial_kernel there spells
+// lm_trial_pose<NG> out for the pinhole instantiation's SGPR spills.
 #pragma once
 #include "../../include/deepcharuco_amd.h"
 

@@ -1,6 +1,6 @@
 // dcx_mat_dev.h -- the small fp64 matrix steps and fixed-order reductions of the pose and calibration kernels, one copy each:
 // packed symmetric storage (pk, unpk), the wave butterfly, the one-workgroup tree, the ballot compaction, cyclic Jacobi, the polar
-// factor, the packed Cholesky (factor, substitute, both), the 3x3 adjugate, and what the two joint solves (dcx_calib.hip,
+// factor, the packed Cholesky (factor, substitute, both), the 3x3 adjugate, and what the joint solves (dcx_calib_dev.h,
 // dcx_stereo.hip) run per view: the LDS-staged Gram accumulation of [J | r] and the view's Schur part.  Also the workspace carver of
 // their hosts.  No camera and no pool in here: those are dcx_camera_dev.h and dcx_pnp_dev.h.
 // Everything is force-inlined and has internal linkage, so each translation unit compiles its own copy.
@@ -198,7 +198,7 @@ __device__ __forceinline__ void adjugate(const double* m, double* a) {
     a[6] = m[3] * m[7] - m[4] * m[6]; a[7] = m[1] * m[6] - m[0] * m[7]; a[8] = m[0] * m[4] - m[1] * m[3];
 }
 
-// ---- the joint solves' per-view steps (dcx_calib.hip, dcx_stereo.hip).  A view's rows of [J | r] (NC columns, the residual last)
+// ---- the joint solves' per-view steps (dcx_calib_dev.h, dcx_stereo.hip).  A view's rows of [J | r] (NC columns, the residual last)
 // give a packed symmetric NC x NC; one 64-lane wave per view, lane l owns its entries l, l + 64, ... (NQ of them at the most).
 
 // the entries this lane owns: e = lane + 64 q, (ea, eb) its row and column in the packed NC x NC, -1 past the end

@@ -6,98 +6,15 @@
 //
 // Map and points are fp64 and agree with the host to rounding; the remap is integer and agrees bit for bit.  K, the distortion
 // coefficients, R and P are kernel arguments (a captured hipGraph keeps them).  No allocation, no synchronisation, no atomics, no
-// LDS in any of the three.  The distortion model and its derivative (distort<>) are dcx_camera_dev.h's, the one copy the pose and
-// calibration kernels project through.
-#include "dcx_camera_dev.h"
+// LDS in any of the three.  The map and points kernels are dcx_rectify_dev.h's, one text for this unit's pinhole and
+// dcx_fisheye.hip's fisheye; the distortion model and its derivative (distort<>) are dcx_camera_dev.h's, the one copy the pose and
+// calibration kernels project through.  The remap reads a map whichever model made it.
+#include "dcx_rectify_dev.h"
 
 namespace {
 
-constexpr int kMapShift = 5;                 // fractional bits of a map entry
-constexpr double kMapLimit = 32768.0;        // a source position beyond this many px is outside
-constexpr int kNewtonMaxIter = 20;           // rectify.NEWTON_MAX_ITER
-constexpr double kNewtonEps = 1e-15;         // rectify.NEWTON_EPS
 constexpr int kFrameGroup = 8;               // rectify.REMAP_FRAME_GROUP: frames one remap thread serves with its map entries held
 constexpr int kPix = 4;                      // output pixels of one remap thread: 32 B of map (two 16-B loads), one dword of gray
-
-struct RectXform {
-    double R[9];                             // row major
-    double fx, fy, cx, cy;                   // the left 3x3 of P
-};
-
-// R (NULL: identity) and P (3x4 row major, NULL: K) from the host -> the kernel argument; false if refused
-inline bool rect_xform(const double* h_R9, const double* h_P12, const PnpCamera& cam, RectXform& x) {
-    for (int i = 0; i < 9; ++i) {
-        x.R[i] = h_R9 ? h_R9[i] : (i % 4 == 0 ? 1.0 : 0.0);
-        if (!isfinite(x.R[i])) return false;
-    }
-    if (h_P12) {
-        if (h_P12[1] != 0.0) return false;
-        x.fx = h_P12[0]; x.cx = h_P12[2]; x.fy = h_P12[5]; x.cy = h_P12[6];
-    } else {
-        x.fx = cam.fx; x.fy = cam.fy; x.cx = cam.cx; x.cy = cam.cy;
-    }
-    return isfinite(x.fx) && isfinite(x.fy) && isfinite(x.cx) && isfinite(x.cy) && x.fx != 0.0 && x.fy != 0.0;
-}
-
-// ---- the map: one thread per output pixel
-
-__global__ __launch_bounds__(256) void dcx_rectify_map_kernel(PnpCamera cam, RectXform xf, int width, int height,
-                                                                int32_t* __restrict__ map) {
-    const int u = blockIdx.x * 64 + (threadIdx.x & 63), v = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (u >= width || v >= height) return;
-    const double x = ((double)u - xf.cx) / xf.fx, y = ((double)v - xf.cy) / xf.fy;
-    const double qx = xf.R[0] * x + xf.R[3] * y + xf.R[6];          // R^T (x, y, 1)
-    const double qy = xf.R[1] * x + xf.R[4] * y + xf.R[7];
-    const double qz = xf.R[2] * x + xf.R[5] * y + xf.R[8];
-    double xd, yd, a, b, d;
-    distort<false>(cam.k, qx / qz, qy / qz, xd, yd, a, b, d);
-    const double mx = cam.fx * xd + cam.cx, my = cam.fy * yd + cam.cy;
-    int2 e = make_int2(INT32_MIN, INT32_MIN);
-    if (qz > 0 && fabs(mx) <= kMapLimit && fabs(my) <= kMapLimit)    // (NaN and inf compare false)
-        e = make_int2((int)rint((double)(1 << kMapShift) * mx), (int)rint((double)(1 << kMapShift) * my));
-    reinterpret_cast<int2*>(map)[(size_t)v * width + u] = e;
-}
-
-// ---- the points: one lane per slot of the pool
-
-__global__ __launch_bounds__(kLanes) void dcx_rectify_points_kernel(const int32_t* __restrict__ rows, const float* __restrict__ xy,
-                                                                      int pool, PnpCamera cam, RectXform xf,
-                                                                      double* __restrict__ out) {
-    const int i = blockIdx.x * kLanes + threadIdx.x;
-    if (i >= pool) return;
-    double u, v;
-    if (xy) {
-        u = (double)xy[2 * (size_t)i];
-        v = (double)xy[2 * (size_t)i + 1];
-    } else {
-        u = (double)rows[4 * (size_t)i];
-        v = (double)rows[4 * (size_t)i + 1];
-    }
-    const double x0 = (u - cam.cx) / cam.fx, y0 = (v - cam.cy) / cam.fy;
-    double x = x0, y = y0;
-    bool done = false;
-#pragma unroll 1
-    for (int it = 0; it < kNewtonMaxIter && !done; ++it) {
-        double xd, yd, a, b, d;
-        distort<true>(cam.k, x, y, xd, yd, a, b, d);
-        const double ex = xd - x0, ey = yd - y0;
-        const double det = a * d - b * b;
-        const double sx = (d * ex - b * ey) / det, sy = (a * ey - b * ex) / det;
-        x -= sx;
-        y -= sy;
-        done = fabs(sx) < kNewtonEps && fabs(sy) < kNewtonEps;
-    }
-    const double X = xf.R[0] * x + xf.R[1] * y + xf.R[2];
-    const double Y = xf.R[3] * x + xf.R[4] * y + xf.R[5];
-    const double Z = xf.R[6] * x + xf.R[7] * y + xf.R[8];
-    double ou = NAN, ov = NAN;
-    if (done && Z > 0) {
-        ou = xf.fx * (X / Z) + xf.cx;
-        ov = xf.fy * (Y / Z) + xf.cy;
-    }
-    out[2 * (size_t)i] = ou;
-    out[2 * (size_t)i + 1] = ov;
-}
 
 // ---- the remap
 //
@@ -192,7 +109,7 @@ extern "C" int dcx_undistort_rectify_map(const double* h_camera9, const double* 
     if (!pnp_camera(h_camera9, h_dist, n_dist, cam) || !rect_xform(h_R9, h_P12, cam, xf)) return DCX_E_ARG;
     const dim3 grid((unsigned)((width + 63) / 64), (unsigned)((height + 3) / 4));
     if (grid.y > 65535u) return DCX_E_ARG;
-    hipLaunchKernelGGL(dcx_rectify_map_kernel, grid, dim3(256), 0, (hipStream_t)stream, cam, xf, width, height, d_map);
+    hipLaunchKernelGGL(dcx_rectify_map_kernel<PnpCamera>, grid, dim3(256), 0, (hipStream_t)stream, cam, xf, width, height, d_map);
     return (int)hipGetLastError();
 }
 
@@ -204,7 +121,7 @@ extern "C" int dcx_rectify_points_pool(const int32_t* d_rows, const float* d_xy,
     RectXform xf;
     if (!pnp_camera(h_camera9, h_dist, n_dist, cam) || !rect_xform(h_R9, h_P12, cam, xf)) return DCX_E_ARG;
     if (pool == 0) return 0;
-    hipLaunchKernelGGL(dcx_rectify_points_kernel, dim3((unsigned)((pool + kLanes - 1) / kLanes)), dim3(kLanes), 0,
+    hipLaunchKernelGGL(dcx_rectify_points_kernel<PnpCamera>, dim3((unsigned)((pool + kLanes - 1) / kLanes)), dim3(kLanes), 0,
                        (hipStream_t)stream, d_rows, d_xy, pool, cam, xf, d_out);
     return (int)hipGetLastError();
 }

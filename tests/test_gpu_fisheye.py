@@ -155,9 +155,10 @@ def _truth(d, K, k, poses, name):
 
 
 @pytest.mark.parametrize("seed,n_views,sigma,K,k,focal0", [(101, 8, 0.0, K150, fx.K_LENS, None), (102, 64, 0.3, K150, fx.K_LENS, None),
-                                                          (103, 8, 0.0, K400, fx.K_ZERO, 300.0)])
+                                                          (103, 8, 0.0, K400, fx.K_ZERO, 300.0), (104, 9, 0.0, K150, fx.K_LENS, None)])
 def test_calibration_matches_host(dev, seed, n_views, sigma, K, k, focal0):
-    """The noisy 64-view set is taken through the 150 px lens, whose corners reach 56 degrees.  Through the 400 px lens (38 degrees
+    """Nine views put two views into reduce_solve's slice 0 (8 slices), so the serial adds inside a slice run; 8, 64 and 7 views
+    never do that at NG = 8.  The noisy 64-view set is taken through the 150 px lens, whose corners reach 56 degrees.  Through the 400 px lens (38 degrees
     at the most) it is not a case: the column of k4 goes with theta^9, 0.027 at 0.67 rad against 0.83 at 0.98 rad, and runs nearly
     parallel to k3's, so k3 and k4 are weakly observed, host and device walk that flat valley a different number of steps (host
     11 steps / 30 attempts, device 15 / 36) and end 2.5e-7 apart in k while agreeing to 5.3e-10 in K, 8.5e-9 in rvec and 5.6e-16 in

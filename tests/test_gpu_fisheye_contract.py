@@ -1,8 +1,8 @@
 """The memory contract of the fisheye entries (include/deepcharuco_amd.h), on tests/guarded.py arenas through the harness of
 tests/test_gpu_workspace_contract.py (its ``drive``: exact-size workspace and outputs between guards; workspace bodies of zeros,
 another call's leftovers, 0x7F and 0xFF; the same bits as the call on roomy buffers each time; guards intact), and DCX_E_WS for a
-workspace one byte short.  The state words of the calibration (LmState<8>::code, lg, iters, attempts) are written by
-fcal_init_state_kernel before the first launch that tests them."""
+workspace one byte short.  The state words of the calibration (LmState<8>::code, lg, iters, attempts, in Ws<FisheyeCalib>::st of
+dcx_calib_dev.h) are written by dcx_fisheye.hip's fcal_init_state_kernel before the first launch that tests them."""
 import ctypes
 
 import numpy as np

@@ -35,9 +35,10 @@ from the code; a word that were read first would be a wild index under 0xFF):
   scores int32 [B][iterations]             dcx_pnp_ransac.hip / calib_ransac       hypotheses / consensus kernel, every h    select, OK frames
                                                                                    of every OK frame                         only
   head[kOverlap], head[kChanged]           dcx_calib_ransac.hip, dcx_stereo.hip    hipMemsetAsync at entry; changed_sum      host copies
-  LmState::code, lg, iters, attempts       Ws::st of dcx_calib.hip, dcx_stereo.hip calib_init_reduce_kernel / the stereo     every later launch,
-                                                                                   init writer (lm_reset + code) -- before   lm_run on the host
-                                                                                   the first kernel that tests code
+  LmState::code, lg, iters, attempts       Ws<M>::st of dcx_calib_dev.h (both      calib_init_reduce_kernel (dcx_calib.hip)  every later launch,
+                                           calibrations), Ws::st of dcx_stereo.hip / the stereo init writer (lm_reset +      lm_run on the host
+                                                                                   code) -- before the first kernel that
+                                                                                   tests code
   counts' starts' vstat winner changed     RWs of dcx_calib_ransac.hip             select_compact kernel, every view         inner solve, merge
   filtered rows / xy / mask                the same                                keep_rows / exclude_view, a view's slots  inner solve, remask
   pair, count[2B], idx0 / idx1, ident      Ws of dcx_stereo.hip                    init_views (count, idx), ident kernel,    every later launch
