@@ -78,12 +78,16 @@ class CalibResult(NamedTuple):
 
 # ------------------------------------------------------------------------------------------------ the fp64 steps
 
+def _camera_matrix(theta: np.ndarray) -> np.ndarray:
+    """theta = (fx, fy, cx, cy, ...) -> K 3x3."""
+    return np.array([[theta[0], 0.0, theta[2]], [0.0, theta[1], theta[3]], [0.0, 0.0, 1.0]])
+
+
 def _camera_of(theta: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
     """theta (9) -> (K 3x3, pnp's 8 distortion coefficients k1 k2 p1 p2 k3 0 0 0)."""
-    K = np.array([[theta[0], 0.0, theta[2]], [0.0, theta[1], theta[3]], [0.0, 0.0, 1.0]])
     k = np.zeros(8)
     k[:5] = theta[4:9]
-    return K, k
+    return _camera_matrix(theta), k
 
 
 def _project_full(obj: np.ndarray, img: np.ndarray, theta: np.ndarray, p: np.ndarray, jac: bool):
@@ -184,18 +188,19 @@ def _initialise(views, image_size):
     return status, theta, poses
 
 
-def _normal_blocks(views, theta: np.ndarray, poses: np.ndarray):
-    """The blocks of JtJ and Jtr over the used views: U [N, 6, 6] (pose-pose), W [N, 9, 6] (intrinsics-pose), V [9, 9]
-    (intrinsics-intrinsics, summed), ga [9], gb [N, 6], the per-view costs [N].  None if a point is behind the camera."""
-    n = len(views)
-    U, W, gb, costs = np.zeros((n, 6, 6)), np.zeros((n, N_INTR, 6)), np.zeros((n, 6)), np.zeros(n)
-    V, ga = np.zeros((N_INTR, N_INTR)), np.zeros(N_INTR)
+def _normal_blocks(views, theta: np.ndarray, poses: np.ndarray, project_full=_project_full):
+    """The blocks of JtJ and Jtr over the used views, for a camera model given by its ``project_full`` (this module's, or
+    ``fisheye._project_full``) with n = theta.size intrinsics: U [N, 6, 6] (pose-pose), W [N, n, 6] (intrinsics-pose), V [n, n]
+    (intrinsics-intrinsics, summed), ga [n], gb [N, 6], the per-view costs [N].  None if a point is behind the camera."""
+    N, n = len(views), theta.size
+    U, W, gb, costs = np.zeros((N, 6, 6)), np.zeros((N, n, 6)), np.zeros((N, 6)), np.zeros(N)
+    V, ga = np.zeros((n, n)), np.zeros(n)
     for i, (obj, img) in enumerate(views):
-        res, cost, J = _project_full(obj, img, theta, poses[i], True)
+        res, cost, J = project_full(obj, img, theta, poses[i], True)
         if res is None:
             return None
         r = res.ravel()
-        A, Bm = J[:, :N_INTR], J[:, N_INTR:]
+        A, Bm = J[:, :n], J[:, n:]
         U[i], W[i], gb[i], costs[i] = Bm.T @ Bm, A.T @ Bm, Bm.T @ r, cost
         V += A.T @ A
         ga += A.T @ r
@@ -205,8 +210,8 @@ def _normal_blocks(views, theta: np.ndarray, poses: np.ndarray):
 _schur_step = _lm.schur_step     # one copy, generic in the global block's size
 
 
-def _view_costs(views, theta, poses) -> np.ndarray:
-    return np.array([_project_full(obj, img, theta, poses[i], False)[1] for i, (obj, img) in enumerate(views)])
+def _view_costs(views, theta, poses, project_full=_project_full) -> np.ndarray:
+    return np.array([project_full(obj, img, theta, poses[i], False)[1] for i, (obj, img) in enumerate(views)])
 
 
 def _total(costs: np.ndarray) -> float:
@@ -216,10 +221,10 @@ def _total(costs: np.ndarray) -> float:
     return c
 
 
-def _refine(views, theta: np.ndarray, poses: np.ndarray):
+def _refine(views, theta: np.ndarray, poses: np.ndarray, project_full=_project_full, max_iter=CALIB_MAX_ITER):
     """Joint LM (module docstring, step 4) -> (status, theta, poses, per-view costs, accepted steps, attempts)."""
-    return _lm.refine(theta, poses, lambda t, p: _normal_blocks(views, t, p), lambda t, p: _view_costs(views, t, p), _total,
-                      False, CALIB_MAX_ITER, CALIB_EPS)
+    return _lm.refine(theta, poses, lambda t, p: _normal_blocks(views, t, p, project_full),
+                      lambda t, p: _view_costs(views, t, p, project_full), _total, False, max_iter, CALIB_EPS)
 
 
 def _views(object_points, image_points):
@@ -246,15 +251,16 @@ def _image_size(image_size) -> Tuple[int, int]:
     return w, h
 
 
-def _result(status, theta, view_status, poses, vc, counts, iters, attempts) -> CalibResult:
+def _result(status, theta, view_status, poses, vc, counts, iters, attempts, n_dist=5) -> CalibResult:
+    """``n_dist``: the model's distortion coefficients, theta[4:4 + n_dist] (5 here, the fisheye model's 4)."""
     B = len(view_status)
     used = np.flatnonzero(view_status == PNP_OK)
-    K, dist = np.zeros((3, 3)), np.zeros((1, 5))
+    K, dist = np.zeros((3, 3)), np.zeros((1, n_dist))
     rv, tv, vr = np.zeros((B, 3)), np.zeros((B, 3)), np.zeros(B)
     rms = 0.0
     if status == CALIB_OK:
-        K, _ = _camera_of(theta)
-        dist = theta[4:9].reshape(1, 5).copy()
+        K = _camera_matrix(theta)
+        dist = theta[4:4 + n_dist].reshape(1, n_dist).copy()
         rv[used], tv[used] = poses[:, :3], poses[:, 3:]
         vr[used] = np.sqrt(vc / counts[used])
         rms = math.sqrt(_total(vc) / int(counts[used].sum()))
@@ -278,10 +284,8 @@ def calibrate_camera_host_full(object_points, image_points, image_size) -> Calib
     return _result(st, theta, view_status, poses, vc, counts, iters, attempts)
 
 
-def calibrate_camera_host(object_points, image_points, image_size):
-    """cv2's 5-tuple ``(rms, K 3x3, dist 1x5, rvecs, tvecs)`` (rvecs / tvecs: one (3, 1) array per view).  ValueError, as cv2
-    errors out, on non-planar objects, a view that cannot be used (fewer than 4 points, degenerate) or a failed calibration."""
-    r = calibrate_camera_host_full(object_points, image_points, image_size)
+def _cv2_tuple(r):
+    """A ``CalibResult`` or ``RobustCalibResult`` -> cv2's 5-tuple, or the ValueError cv2 would end with."""
     bad = np.flatnonzero(r.view_status != PNP_OK)
     if bad.size:
         raise ValueError(f"view {int(bad[0])} cannot be used (status {int(r.view_status[bad[0]])})")
@@ -289,6 +293,19 @@ def calibrate_camera_host(object_points, image_points, image_size):
         raise ValueError(f"calibration failed (status {r.status})")
     return (r.rms, r.camera_matrix, r.dist_coeffs, tuple(v.reshape(3, 1).copy() for v in r.rvecs),
             tuple(v.reshape(3, 1).copy() for v in r.tvecs))
+
+
+def _no_bad_id(r, col_count, row_count):
+    """``r``, or IndexError if one of its views carries an id outside the board."""
+    if (r.view_status == PNP_BAD_ID).any():
+        raise _bad_id_error(col_count, row_count)
+    return r
+
+
+def calibrate_camera_host(object_points, image_points, image_size):
+    """cv2's 5-tuple ``(rms, K 3x3, dist 1x5, rvecs, tvecs)`` (rvecs / tvecs: one (3, 1) array per view).  ValueError, as cv2
+    errors out, on non-planar objects, a view that cannot be used (fewer than 4 points, degenerate) or a failed calibration."""
+    return _cv2_tuple(calibrate_camera_host_full(object_points, image_points, image_size))
 
 
 # ------------------------------------------------------------------------------------------------ consensus: the definition
@@ -469,15 +486,7 @@ def calibrate_camera_ransac_host(keypoints_list, col_count, row_count, square_le
     id outside the board."""
     r = calibrate_camera_ransac_host_full(keypoints_list, col_count, row_count, square_len, image_size, iterations,
                                           consensus_error, reproj_error, min_inliers, rounds, seed)
-    if (r.view_status == PNP_BAD_ID).any():
-        raise _bad_id_error(col_count, row_count)
-    bad = np.flatnonzero(r.view_status != PNP_OK)
-    if bad.size:
-        raise ValueError(f"view {int(bad[0])} cannot be used (status {int(r.view_status[bad[0]])})")
-    if r.status != CALIB_OK:
-        raise ValueError(f"calibration failed (status {r.status})")
-    return (r.rms, r.camera_matrix, r.dist_coeffs, tuple(v.reshape(3, 1).copy() for v in r.rvecs),
-            tuple(v.reshape(3, 1).copy() for v in r.tvecs), r.inliers)
+    return _cv2_tuple(_no_bad_id(r, col_count, row_count)) + (r.inliers,)
 
 
 # ------------------------------------------------------------------------------------------------ the device solver
@@ -487,14 +496,27 @@ def workspace_bytes(batch: int) -> int:
     return int(_lib.lib().dcx_calibrate_workspace_bytes(int(batch)))
 
 
-def _common_fields(res, view_status, pose) -> tuple:
-    """The 16-double result of either device calibration and the host copies of its per-view outputs -> the fields that
-    ``CalibResult`` and ``RobustCalibResult`` share, in their order."""
+def _common_fields(res, view_status, pose, n_dist=5) -> tuple:
+    """The 16-double result of a device calibration (``n_dist`` distortion coefficients from word 4: 5, the fisheye model's 4) and
+    the host copies of its per-view outputs -> the fields that ``CalibResult`` and ``RobustCalibResult`` share, in their order."""
     r = np.array(res[:], np.float64)
     status = int(r[14])
-    K = np.array([[r[0], 0.0, r[2]], [0.0, r[1], r[3]], [0.0, 0.0, 1.0]]) if status == CALIB_OK else np.zeros((3, 3))
-    return (status, float(r[9]), K, r[4:9].reshape(1, 5).copy(), view_status.astype(np.int32), pose[:, 0:3].copy(),
+    K = _camera_matrix(r) if status == CALIB_OK else np.zeros((3, 3))
+    return (status, float(r[9]), K, r[4:4 + n_dist].reshape(1, n_dist).copy(), view_status.astype(np.int32), pose[:, 0:3].copy(),
             pose[:, 3:6].copy(), pose[:, 6].copy(), pose[:, 7].astype(np.int64), int(r[10]), int(r[11]), int(r[12]), int(r[13]))
+
+
+def _view_outputs(batch, dev):
+    """-> what a calibration writes per view on the device: status int32 [B], pose float64 [B, POSE_WORDS]."""
+    import torch
+    return torch.empty((batch,), dtype=torch.int32, device=dev), torch.empty((batch, pnp.POSE_WORDS), dtype=torch.float64, device=dev)
+
+
+def _upload(keypoints_list, dev):
+    """The ``calibrate_*_device`` calls' views -> ``pack_keypoints``' (packed, batch, pool).  ValueError for no views."""
+    if len(keypoints_list) == 0:
+        raise ValueError("no views")
+    return pack_keypoints(keypoints_list, dev)
 
 
 def calibrate_charuco_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len,
@@ -508,8 +530,7 @@ def calibrate_charuco_pool(packed, batch: int, pool: int, refined: bool, col_cou
     w, h = _image_size(image_size)
     dev = packed.device
     ptrs = pnp._pool_ptrs(packed, batch, pool, refined)
-    st = torch.empty((batch,), dtype=torch.int32, device=dev)
-    pose = torch.empty((batch, pnp.POSE_WORDS), dtype=torch.float64, device=dev)
+    st, pose = _view_outputs(batch, dev)
     nbytes = workspace_bytes(batch)
     ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
     res = (_ctypes.c_double * RESULT_WORDS)()
@@ -529,14 +550,10 @@ def calibrate_charuco_device(keypoints_list: Sequence, col_count, row_count, squ
     from .models._handles import require_cuda
     dev = require_cuda(device)
     _image_size(image_size)
-    if len(keypoints_list) == 0:
-        raise ValueError("no views")
-    packed, b, pool = pack_keypoints(keypoints_list, dev)
+    packed, b, pool = _upload(keypoints_list, dev)
     with torch.cuda.device(dev):
         r = calibrate_charuco_pool(packed, b, pool, True, col_count, row_count, square_len, image_size)
-    if (r.view_status == PNP_BAD_ID).any():
-        raise _bad_id_error(col_count, row_count)
-    return r
+    return _no_bad_id(r, col_count, row_count)
 
 
 # ------------------------------------------------------------------------------------------------ consensus on the device
@@ -567,8 +584,7 @@ def calibrate_charuco_ransac_pool(packed, batch: int, pool: int, refined: bool, 
     ptrs = pnp._pool_ptrs(packed, batch, pool, refined)
     out_inliers = _dev.tensor(out_inliers, dev, torch.uint8, (pool,),
                               f"out_inliers must be a contiguous uint8 tensor of at least {pool} values on {dev}", "min", zeros=True)
-    st = torch.empty((batch,), dtype=torch.int32, device=dev)
-    pose = torch.empty((batch, pnp.POSE_WORDS), dtype=torch.float64, device=dev)
+    st, pose = _view_outputs(batch, dev)
     info = torch.empty((batch, 2), dtype=torch.int32, device=dev)
     nbytes = ransac_workspace_bytes(batch, pool, iterations)
     ws = _dev.workspace(None, dev, nbytes)
@@ -598,13 +614,10 @@ def calibrate_charuco_ransac_device(keypoints_list: Sequence, col_count, row_cou
     dev = require_cuda(device)
     _image_size(image_size)
     _calib_ransac_args(iterations, consensus_error, reproj_error, min_inliers, rounds)
-    if len(keypoints_list) == 0:
-        raise ValueError("no views")
-    packed, b, pool = pack_keypoints(keypoints_list, dev)
+    packed, b, pool = _upload(keypoints_list, dev)
     with torch.cuda.device(dev):
         r = calibrate_charuco_ransac_pool(packed, b, pool, True, col_count, row_count, square_len, image_size, iterations,
                                           consensus_error, reproj_error, min_inliers, rounds, seed)
-    if (r.view_status == PNP_BAD_ID).any():
-        raise _bad_id_error(col_count, row_count)
+    _no_bad_id(r, col_count, row_count)
     # undo pack_keypoints' stable id sort
     return r._replace(inliers=[mask[_caller_order(kp)] for kp, mask in zip(keypoints_list, r.inliers)])

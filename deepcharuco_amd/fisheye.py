@@ -39,13 +39,15 @@ with cv2 is not claimed.
 from __future__ import annotations
 
 import ctypes as _ctypes
+import functools
 import math
 from typing import Sequence, Tuple
 
 import numpy as np
 
-from . import _dev, _lm, pnp
-from .calib import (CALIB_DEGENERATE, CALIB_EPS, CALIB_NO_VIEWS, CALIB_OK, RESULT_WORDS, CalibResult, _image_size, _total, _views)
+from . import _dev, pnp
+from .calib import (CALIB_NO_VIEWS, RESULT_WORDS, CalibResult, _camera_matrix, _common_fields, _cv2_tuple, _image_size, _no_bad_id, _refine,
+                    _result, _upload, _view_outputs, _views)
 from .corner_pool import pack_keypoints
 from .pnp import (LM_EPS, LM_MAX_ITER, PNP_BAD_ID, PNP_DEGENERATE, PNP_NONFINITE, PNP_OK, PNP_TOO_FEW, POSE_WORDS, _as_cv2,
                   _bad_id_error, _camera, _cholesky_solve, _init_pose, _pool_ptrs, _right_jacobian, _rodrigues, _skew, object_points,
@@ -56,6 +58,7 @@ from .rectify import (MAP_BITS, MAP_LIMIT, MAP_SENTINEL, NEWTON_EPS, NEWTON_MAX_
 SMALL_R = 1e-4                 # below it theta_d / r and its derivative come from their series
 SMALL_THETA_D = 1e-8           # below it tan(theta) / theta_d = 1 to the last bit
 N_INTR = 8                     # fx, fy, cx, cy, k1, k2, k3, k4
+N_DIST = 4                     # k1, k2, k3, k4
 CALIB_MAX_ITER = 100           # accepted steps of the joint LM
 
 __all__ = ["project_points_host", "undistort_points_host", "solve_pnp_fisheye_host", "solve_pnp_fisheye_host_full",
@@ -310,7 +313,7 @@ def solve_pnp_fisheye_ransac_host(keypoints, col_count, row_count, square_len, c
 # ------------------------------------------------------------------------------------------------ calibration
 
 def _camera_of(theta: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
-    return np.array([[theta[0], 0.0, theta[2]], [0.0, theta[1], theta[3]], [0.0, 0.0, 1.0]]), np.array(theta[4:8], np.float64)
+    return _camera_matrix(theta), np.array(theta[4:8], np.float64)
 
 
 def _project_full(obj, img, theta, p, jac: bool):
@@ -318,48 +321,11 @@ def _project_full(obj, img, theta, p, jac: bool):
     return _project(obj, img, p, K, k, jac, True)
 
 
-def _normal_blocks(views, theta: np.ndarray, poses: np.ndarray):
-    """``calib._normal_blocks`` at 8 intrinsics."""
-    n = len(views)
-    U, W, gb, costs = np.zeros((n, 6, 6)), np.zeros((n, N_INTR, 6)), np.zeros((n, 6)), np.zeros(n)
-    V, ga = np.zeros((N_INTR, N_INTR)), np.zeros(N_INTR)
-    for i, (obj, img) in enumerate(views):
-        res, cost, J = _project_full(obj, img, theta, poses[i], True)
-        if res is None:
-            return None
-        r = res.ravel()
-        A, Bm = J[:, :N_INTR], J[:, N_INTR:]
-        U[i], W[i], gb[i], costs[i] = Bm.T @ Bm, A.T @ Bm, Bm.T @ r, cost
-        V += A.T @ A
-        ga += A.T @ r
-    return U, W, V, ga, gb, costs
-
-
-def _view_costs(views, theta, poses) -> np.ndarray:
-    return np.array([_project_full(obj, img, theta, poses[i], False)[1] for i, (obj, img) in enumerate(views)])
-
-
 def _theta0(w: int, h: int, focal0) -> np.ndarray:
     f = float(focal0) if focal0 is not None and float(focal0) > 0 else max(w, h) / 2.0
     if not math.isfinite(f):
         raise ValueError("focal0 must be finite")
     return np.array([f, f, (w - 1) * 0.5, (h - 1) * 0.5, 0, 0, 0, 0], np.float64)
-
-
-def _result(status, theta, view_status, poses, vc, counts, iters, attempts) -> CalibResult:
-    B = len(view_status)
-    used = np.flatnonzero(view_status == PNP_OK)
-    K, dist = np.zeros((3, 3)), np.zeros((1, 4))
-    rv, tv, vr = np.zeros((B, 3)), np.zeros((B, 3)), np.zeros(B)
-    rms = 0.0
-    if status == CALIB_OK:
-        K, k = _camera_of(theta)
-        dist = k.reshape(1, 4).copy()
-        rv[used], tv[used] = poses[:, :3], poses[:, 3:]
-        vr[used] = np.sqrt(vc / counts[used])
-        rms = math.sqrt(_total(vc) / int(counts[used].sum()))
-    return CalibResult(int(status), float(rms), K, dist, view_status.astype(np.int32), rv, tv, vr, counts.astype(np.int64),
-                       int(iters), int(attempts), int(used.size), int(counts[used].sum()))
 
 
 def calibrate_fisheye_host_full(object_points_, image_points, image_size, focal0=None) -> CalibResult:
@@ -382,24 +348,15 @@ def calibrate_fisheye_host_full(object_points_, image_points, image_size, focal0
         poses0[i] = pose[:6]
     used = np.flatnonzero(view_status == PNP_OK)
     if not used.size:
-        return _result(CALIB_NO_VIEWS, theta, view_status, None, None, counts, 0, 0)
-    vs = [views[i] for i in used]
-    st, theta, poses, vc, iters, attempts = _lm.refine(theta, poses0[used], lambda t, p: _normal_blocks(vs, t, p),
-                                                       lambda t, p: _view_costs(vs, t, p), _total, False, CALIB_MAX_ITER, CALIB_EPS)
-    return _result(st, theta, view_status, poses, vc, counts, iters, attempts)
+        return _result(CALIB_NO_VIEWS, theta, view_status, None, None, counts, 0, 0, N_DIST)
+    st, theta, poses, vc, iters, attempts = _refine([views[i] for i in used], theta, poses0[used], _project_full, CALIB_MAX_ITER)
+    return _result(st, theta, view_status, poses, vc, counts, iters, attempts, N_DIST)
 
 
 def calibrate_fisheye_host(object_points_, image_points, image_size, focal0=None):
     """cv2's 5-tuple ``(rms, K 3x3, D 1x4, rvecs, tvecs)``.  ValueError, as cv2 errors out, on a view that cannot be used or a
     failed calibration."""
-    r = calibrate_fisheye_host_full(object_points_, image_points, image_size, focal0)
-    bad = np.flatnonzero(r.view_status != PNP_OK)
-    if bad.size:
-        raise ValueError(f"view {int(bad[0])} cannot be used (status {int(r.view_status[bad[0]])})")
-    if r.status != CALIB_OK:
-        raise ValueError(f"calibration failed (status {r.status})")
-    return (r.rms, r.camera_matrix, r.dist_coeffs, tuple(v.reshape(3, 1).copy() for v in r.rvecs),
-            tuple(v.reshape(3, 1).copy() for v in r.tvecs))
+    return _cv2_tuple(calibrate_fisheye_host_full(object_points_, image_points, image_size, focal0))
 
 
 # ------------------------------------------------------------------------------------------------ map and points
@@ -570,13 +527,7 @@ def workspace_bytes(batch: int) -> int:
     return int(_lib.lib().dcx_fisheye_calibrate_workspace_bytes(int(batch)))
 
 
-def _calib_fields(res, view_status, pose) -> tuple:
-    """``dcx_fisheye_calibrate_pool``'s 16 doubles and the host copies of its per-view outputs -> ``CalibResult``'s fields."""
-    r = np.array(res[:], np.float64)
-    status = int(r[14])
-    K = np.array([[r[0], 0.0, r[2]], [0.0, r[1], r[3]], [0.0, 0.0, 1.0]]) if status == CALIB_OK else np.zeros((3, 3))
-    return (status, float(r[9]), K, r[4:8].reshape(1, 4).copy(), view_status.astype(np.int32), pose[:, 0:3].copy(),
-            pose[:, 3:6].copy(), pose[:, 6].copy(), pose[:, 7].astype(np.int64), int(r[10]), int(r[11]), int(r[12]), int(r[13]))
+_calib_fields = functools.partial(_common_fields, n_dist=N_DIST)     # ``dcx_fisheye_calibrate_pool``'s 16 doubles -> ``CalibResult``'s fields
 
 
 def calibrate_fisheye_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len, image_size,
@@ -591,8 +542,7 @@ def calibrate_fisheye_pool(packed, batch: int, pool: int, refined: bool, col_cou
     _theta0(w, h, focal0)                                     # ValueError for an infinite one
     dev = packed.device
     ptrs = _pool_ptrs(packed, batch, pool, refined)
-    st = torch.empty((batch,), dtype=torch.int32, device=dev)
-    pose = torch.empty((batch, POSE_WORDS), dtype=torch.float64, device=dev)
+    st, pose = _view_outputs(batch, dev)
     nbytes = workspace_bytes(batch)
     ws = _dev.workspace(workspace, dev, nbytes, f"workspace must be a contiguous tensor of at least {nbytes} bytes on {dev}")
     res = (_ctypes.c_double * RESULT_WORDS)()
@@ -613,14 +563,10 @@ def calibrate_fisheye_device(keypoints_list: Sequence, col_count, row_count, squ
     from .models._handles import require_cuda
     dev = require_cuda(device)
     _image_size(image_size)
-    if len(keypoints_list) == 0:
-        raise ValueError("no views")
-    packed, b, pool = pack_keypoints(keypoints_list, dev)
+    packed, b, pool = _upload(keypoints_list, dev)
     with torch.cuda.device(dev):
         r = calibrate_fisheye_pool(packed, b, pool, True, col_count, row_count, square_len, image_size, focal0)
-    if (r.view_status == PNP_BAD_ID).any():
-        raise _bad_id_error(col_count, row_count)
-    return r
+    return _no_bad_id(r, col_count, row_count)
 
 
 def undistort_rectify_map_fisheye_device(camera_matrix, dist_coeffs, R, P, width: int, height: int, device="cuda", out=None):

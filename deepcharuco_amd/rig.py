@@ -57,19 +57,21 @@ from typing import NamedTuple, Sequence
 
 import numpy as np
 
-from . import _dev, _lm, pnp
-from .corner_pool import _pool_rows, pack_keypoints
-from .pnp import (PNP_BAD_ID, PNP_OK, PNP_TOO_FEW, _bad_id_error, _camera, _dist, _pool_ptrs, _right_jacobian, _rodrigues, _rvec_of,
-                  _solve)
-from .stereo import (MODELS, _model_args, _model_cameras, _model_of, _models, _project_q, _rig_init, _skews, _slot_mask,
+from . import _dev, _lm
+from .calib import _no_bad_id
+from .pnp import PNP_OK, _camera, _pool_ptrs, _rodrigues, _rvec_of
+# every step that does not depend on the number of cameras is stereo.py's, kept once
+from .stereo import (MODELS, STEREO_EPS, STEREO_MAX_ITER, _call, _depth_margin, _device_masks, _model_args, _model_cameras, _models,
+                     _outputs, _raise_like_cv2, _refine, _rig_init, _sine, _total, _unpack, _upload, _view_poses, _view_segments,
                      essential_fundamental)
+from .stereo import _rig_rows as _rows_of
+from .stereo import _dist, _evaluate, _model_of     # noqa: F401  (the names the tests reach through this module)
 
 # overall status (include/deepcharuco_amd.h); per-view statuses are pnp's PNP_*
 RIG_OK, RIG_NO_STAMPS, RIG_DEGENERATE, RIG_NONFINITE = _lm.LM_OK, _lm.LM_NO_UNITS, _lm.LM_DEGENERATE, _lm.LM_NONFINITE
 RIG_DISCONNECTED = 4
 RIG_MAX_CAMERAS = 8
-RIG_MAX_ITER = 30
-RIG_EPS = float(np.finfo(np.float64).eps)
+RIG_MAX_ITER, RIG_EPS = STEREO_MAX_ITER, STEREO_EPS      # step 4's rules are stereo's: ``stereo._refine`` runs both
 RESULT_HEAD = 8                # h_result of dcx_rig_calibrate_pool: 8 words, then X_1 .. X_{C-1}
 REDUCE_CHUNK, REDUCE_SLICES = 16, 16   # csrc/dcx_rig.hip's kChunk, kSlices: the two fan-ins of the per-attempt reduction
 
@@ -98,145 +100,6 @@ class RigResult(NamedTuple):
 
 
 # ------------------------------------------------------------------------------------------------ the fp64 steps
-
-class _Rows(NamedTuple):
-    """Every row of every used timestamp: timestamp by timestamp, its usable cameras ascending, each view's rows in pool order."""
-    obj: np.ndarray              # (M, 3) board points
-    img: np.ndarray              # (M, 2)
-    cam: np.ndarray              # (M,) the row's camera
-    stamp: np.ndarray            # (M,) index of the row's timestamp among the used ones
-    starts: np.ndarray           # (N,) first row of every timestamp
-    vstarts: np.ndarray          # (NV,) first row of every view
-    vstamp: np.ndarray           # (NV,) the view's timestamp (index among the used ones) ...
-    vcam: np.ndarray             # (NV,) ... and camera
-    n_cams: int
-
-
-def _rows_of(stamps, n_cams: int) -> _Rows:
-    """Per used timestamp a list of (camera, obj, img) of its usable views, cameras ascending -> the rows, in float64."""
-    obj, img, cam, stamp, counts, vstamp, vcam, per_stamp = [], [], [], [], [], [], [], []
-    for i, views in enumerate(stamps):
-        per_stamp.append(sum(o.shape[0] for _, o, _ in views))
-        for c, o, m in views:
-            n = o.shape[0]
-            obj.append(np.asarray(o, np.float64))
-            img.append(np.asarray(m, np.float64))
-            cam.append(np.full(n, c))
-            stamp.append(np.full(n, i))
-            counts.append(n)
-            vstamp.append(i)
-            vcam.append(c)
-    vstarts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
-    starts = np.concatenate([[0], np.cumsum(per_stamp)[:-1]]).astype(np.int64)
-    return _Rows(np.concatenate(obj), np.concatenate(img), np.concatenate(cam), np.concatenate(stamp), starts, vstarts,
-                 np.array(vstamp), np.array(vcam), n_cams)
-
-
-def _points(rows: _Rows, X: np.ndarray, P: np.ndarray):
-    """-> (q_0 (M, 3): the rows' board points in camera 0's frame, q (M, 3): in their own camera's, R(X_c) [C - 1, 3, 3])."""
-    RP = np.stack([_rodrigues(p[:3]) for p in P])
-    RX = np.stack([_rodrigues(x[:3]) for x in X])
-    Q0 = np.einsum("mij,mj->mi", RP[rows.stamp], rows.obj) + P[rows.stamp, 3:]
-    Q = Q0.copy()
-    for c in range(1, rows.n_cams):
-        sel = rows.cam == c
-        Q[sel] = Q0[sel] @ RX[c - 1].T + X[c - 1, 3:]
-    return Q0, Q, RX, RP
-
-
-def _evaluate(rows: _Rows, cams, X: np.ndarray, P: np.ndarray, jac: bool):
-    """Residuals (M, 2) at the rig X [C - 1, 6] and the board poses P [N, 6], and with ``jac`` the rows' Jacobians J_X (M, 2, 6) with
-    respect to the row's OWN camera's X_c (zero for camera 0's rows) and J_P (M, 2, 6) with respect to the row's own P_t:
-    ``stereo._evaluate`` per camera.  None if a point is not in front of its camera."""
-    Q0, Q, RX, RP = _points(rows, X, P)
-    if not (Q[:, 2] > 0).all():
-        return None
-    M = rows.obj.shape[0]
-    res, D = np.empty((M, 2)), (np.empty((M, 2, 3)) if jac else None)
-    for c, cam in enumerate(cams):
-        sel = rows.cam == c
-        if not sel.any():
-            continue
-        r, d = _model_of(cam)[1](Q[sel], rows.img[sel], cam[0], cam[1], jac)
-        res[sel] = r
-        if jac:
-            D[sel] = d
-    if not jac:
-        return res, None, None
-    JrP = np.stack([_right_jacobian(p[:3]) for p in P])
-    dQ0_dr = -np.einsum("mij,mjk,mkl->mil", RP[rows.stamp], _skews(rows.obj), JrP[rows.stamp])    # -R_P [o]x Jr(r_P)
-    Dp = D.copy()
-    JX = np.zeros((M, 2, 6))
-    for c in range(1, rows.n_cams):
-        sel = rows.cam == c
-        if not sel.any():
-            continue
-        Dp[sel] = D[sel] @ RX[c - 1]                           # camera c sees q_0 through R_c: d(u, v)/dq_0 = d(u, v)/dq R_c
-        dQ_drx = -np.einsum("ij,mjk,kl->mil", RX[c - 1], _skews(Q0[sel]), _right_jacobian(X[c - 1, :3]))   # -R_c [q_0]x Jr(r_c)
-        JX[sel, :, :3] = D[sel] @ dQ_drx
-        JX[sel, :, 3:] = D[sel]
-    JP = np.concatenate([Dp @ dQ0_dr, Dp], 2)
-    return res, JX, JP
-
-
-def _view_costs(rows: _Rows, res: np.ndarray) -> np.ndarray:
-    """-> [N, C]: the cost of every usable view, zero elsewhere."""
-    out = np.zeros((rows.starts.size, rows.n_cams))
-    out[rows.vstamp, rows.vcam] = np.add.reduceat((res * res).sum(1), rows.vstarts)
-    return out
-
-
-def _total(costs: np.ndarray) -> float:
-    """Per timestamp over the cameras ascending, then over the timestamps in order."""
-    per = np.zeros(costs.shape[0])
-    for c in range(costs.shape[1]):
-        per = per + costs[:, c]
-    s = 0.0
-    for v in per.tolist():
-        s += v
-    return s
-
-
-def _normal_blocks(rows: _Rows, cams, X, P):
-    """The blocks of JtJ and Jtr as ``_lm.schur_step`` takes them with n = 6 (C - 1): U [N, 6, 6], W [N, n, 6], V [n, n] (block
-    diagonal), ga [n], gb [N, 6], the per-view costs [N, C]; the sums in the module docstring's order.  None if a point is behind
-    a camera."""
-    ev = _evaluate(rows, cams, X.reshape(-1, 6), P, True)
-    if ev is None:
-        return None
-    res, JX, JP = ev
-    N, n = rows.starts.size, 6 * (rows.n_cams - 1)
-    U = np.add.reduceat(np.einsum("mai,maj->mij", JP, JP), rows.starts, 0)
-    gb = np.add.reduceat(np.einsum("mai,ma->mi", JP, res), rows.starts, 0)
-    Wv = np.add.reduceat(np.einsum("mai,maj->mij", JX, JP), rows.vstarts, 0)
-    Vv = np.add.reduceat(np.einsum("mai,maj->mij", JX, JX), rows.vstarts, 0)
-    gv = np.add.reduceat(np.einsum("mai,ma->mi", JX, res), rows.vstarts, 0)
-    W, V, ga = np.zeros((N, n, 6)), np.zeros((n, n)), np.zeros(n)
-    for v, (t, c) in enumerate(zip(rows.vstamp.tolist(), rows.vcam.tolist())):     # timestamps in order
-        if c == 0:
-            continue
-        s = slice(6 * (c - 1), 6 * c)
-        W[t, s] = Wv[v]
-        V[s, s] += Vv[v]
-        ga[s] += gv[v]
-    return U, W, V, ga, gb, _view_costs(rows, res)
-
-
-def _refine(rows: _Rows, cams, X: np.ndarray, P: np.ndarray):
-    """Joint LM (module docstring, step 4) -> (status, X [C - 1, 6], P, per-view costs [N, C], accepted steps, attempts)."""
-    def trial_costs(g, p):
-        ev = _evaluate(rows, cams, g.reshape(-1, 6), p, False)
-        return _view_costs(rows, ev[0]) if ev is not None else None
-
-    st, g, P, vc, iters, attempts = _lm.refine(X.ravel().copy(), P, lambda g, p: _normal_blocks(rows, cams, g, p), trial_costs,
-                                               _total, True, RIG_MAX_ITER, RIG_EPS)
-    return st, g.reshape(-1, 6), P, vc, iters, attempts
-
-
-def _sine(R: np.ndarray) -> float:
-    """The sine term of ``pnp._rvec_of`` at R: its branch switches at 1e-5."""
-    return 0.5 * math.sqrt((R[2, 1] - R[1, 2]) ** 2 + (R[0, 2] - R[2, 0]) ** 2 + (R[1, 0] - R[0, 1]) ** 2)
-
 
 def _tree(usable: np.ndarray):
     """Step 2's graph walk over usable [T, C] (bool) -> (parents [C] with -1 for camera 0 and the cameras not placed, the placed
@@ -352,34 +215,8 @@ def rig_calibrate_host_full(keypoints_lists, col_count, row_count, square_len, c
     for c in range(C):
         if len(keypoints_lists[c]) != B:
             raise ValueError(f"{B} views of camera 0 but {len(keypoints_lists[c])} of camera {c}")
-    n_ids = (col_count - 1) * (row_count - 1)
-    mk = _mask_lists(masks, C)
-    view_status = np.full((B, C), PNP_OK, np.int32)
-    view_points = np.zeros((B, C), np.int64)
-    poses = np.zeros((B, C, 6))
-    obj_l, img_l = [[None] * C for _ in range(B)], [[None] * C for _ in range(B)]
-    for t in range(B):
-        for c in range(C):
-            kp, order = _pool_rows(keypoints_lists[c][t], pool_order)
-            keep = np.ones(kp.shape[0], bool)
-            if mk[c] is not None and mk[c][t] is not None:
-                keep = np.asarray(mk[c][t]).astype(bool).ravel()
-                if keep.size != kp.shape[0]:
-                    raise ValueError(f"view ({c}, {t}) has {kp.shape[0]} rows but its mask {keep.size}")
-            kp = kp[order][keep[order]]
-            view_points[t, c] = kp.shape[0]
-            if kp.shape[0] < 4:
-                view_status[t, c] = PNP_TOO_FEW
-                continue
-            ids = kp[:, 2].astype(np.int64)
-            if ids.min() < 0 or ids.max() >= n_ids:
-                view_status[t, c] = PNP_BAD_ID
-                continue
-            obj_l[t][c] = pnp.object_points(ids, col_count, row_count, square_len)
-            img_l[t][c] = kp[:, :2].astype(np.float32)
-            st, pose = _model_of(cams[c])[0](obj_l[t][c], img_l[t][c], cams[c][0], cams[c][1])
-            view_status[t, c] = st
-            poses[t, c] = pose[:6]
+    view_status, view_points, poses, obj_l, img_l = _view_poses(keypoints_lists, _mask_lists(masks, C), cams,
+                                                                (col_count, row_count, square_len), pool_order)
     usable = view_status == PNP_OK
     used = np.flatnonzero(usable.sum(1) >= 2)
     parents = np.full(C, -1, np.int32)
@@ -397,22 +234,10 @@ def rig_calibrate_host_full(keypoints_lists, col_count, row_count, square_len, c
     if st != RIG_OK:
         return done(st, margin=margin)
     rows = _rows_of([[(c, obj_l[t][c], img_l[t][c]) for c in range(C) if usable[t, c]] for t in used], C)
-    st, X, P, vc, iters, attempts = _refine(rows, cams, X0, P0)
+    st, X, P, vc, iters, attempts = _refine(rows, cams, X0, P0, _view_segments(rows))
     if st == RIG_OK and with_margin:
-        Q = _points(rows, X, P)[1]
-        margin = min(margin, float((Q[:, 2] / np.linalg.norm(Q, axis=1)).min()))
+        margin = min(margin, _depth_margin(rows, X, P))
     return done(st, X, P, vc, iters, attempts, margin)
-
-
-def _raise_like_cv2(r: RigResult, col_count, row_count):
-    if (r.view_status == PNP_BAD_ID).any():
-        raise _bad_id_error(col_count, row_count)
-    bad = np.argwhere((r.view_status != PNP_OK) & (r.view_points > 0))        # (an empty view: the camera did not see the board)
-    if bad.size:
-        t, c = (int(v) for v in bad[0])
-        raise ValueError(f"view {t} of camera {c} cannot be used (status {int(r.view_status[t, c])})")
-    if r.status != RIG_OK:
-        raise ValueError(f"rig calibration failed (status {r.status})")
 
 
 def rig_calibrate_host(keypoints_lists, col_count, row_count, square_len, cameras, dists, masks=None, models=None):
@@ -420,7 +245,7 @@ def rig_calibrate_host(keypoints_lists, col_count, row_count, square_len, camera
     that has rows and cannot be used (too few, degenerate) or a failed calibration (no timestamp with two views, a camera that
     shares no view with the others), IndexError for an id outside the board.  An empty view is not an error."""
     r = rig_calibrate_host_full(keypoints_lists, col_count, row_count, square_len, cameras, dists, masks, models=models)
-    _raise_like_cv2(r, col_count, row_count)
+    _raise_like_cv2(r, col_count, row_count, "rig", empty_ok=True)
     return r.rms, r.R, r.T.reshape(-1, 3, 1).copy()
 
 
@@ -482,17 +307,13 @@ def rig_calibrate_pools(packed_list, batch: int, pools, refined: bool, col_count
     if any(p.device != dev for p in packed_list):
         raise ValueError("the pools must be on one device")
     mk = _mask_lists(masks, C)
+    _device_masks(mk, pools, dev)
     table = (_RigCamera * C)()
     for c in range(C):
-        if mk[c] is not None:
-            _dev.tensor(mk[c], dev, torch.uint8, (pools[c],),
-                        f"mask {c} must be a contiguous uint8 tensor of at least {pools[c]} values on {dev}", "min")
         counts_p, starts_p, rows_p, xy_p = _pool_ptrs(packed_list[c], batch, pools[c], refined)
         cam9, d8, nd = _model_args(cameras[c], dists[c], models and models[c])
         table[c] = _RigCamera(counts_p, starts_p, rows_p, xy_p, pools[c], _lib.ptr(mk[c]), cam9, d8, nd)
-    st = torch.empty((batch, C), dtype=torch.int32, device=dev)
-    pose = torch.empty((batch, pnp.POSE_WORDS), dtype=torch.float64, device=dev)
-    info = torch.empty((batch, C, 2), dtype=torch.float64, device=dev)
+    st, pose, info = _outputs(batch, C, dev)
     nbytes = workspace_bytes(C, batch, pools)
     ws = _dev.workspace(None, dev, nbytes)
     res = (_ctypes.c_double * (RESULT_HEAD + 6 * (C - 1)))()
@@ -500,13 +321,8 @@ def rig_calibrate_pools(packed_list, batch: int, pools, refined: bool, col_count
     tail = (int(batch), int(col_count), int(row_count), float(square_len), ws.data_ptr(), nbytes, st.data_ptr(), pose.data_ptr(),
             info.data_ptr(), par, res)
     with torch.cuda.device(dev):
-        if models is None:
-            _lib.check(_lib.lib().dcx_rig_calibrate_pool(C, table, *tail, _lib.current_stream()), "dcx_rig_calibrate_pool")
-        else:
-            tags = (_ctypes.c_int * C)(*(MODELS.index(m) for m in models))
-            _lib.check(_lib.lib().dcx_rig_calibrate_models_pool(C, table, tags, *tail, _lib.current_stream()),
-                       "dcx_rig_calibrate_models_pool")
-        st_h, pose_h, info_h = st.cpu().numpy(), pose.cpu().numpy(), info.cpu().numpy()
+        _call("rig_calibrate", (C, table), models and [(_ctypes.c_int * C)(*(MODELS.index(m) for m in models))], tail)
+        view_status, rvecs, tvecs, stamp_rms, stamp_points, view_rms, view_points = _unpack(st, pose, info)
     r = np.array(res[:], np.float64)
     status = int(r[5])
     R, T, rvec = np.zeros((C, 3, 3)), np.zeros((C, 3)), np.zeros((C, 3))
@@ -514,9 +330,8 @@ def rig_calibrate_pools(packed_list, batch: int, pools, refined: bool, col_count
         X = r[RESULT_HEAD:].reshape(C - 1, 6)
         rvec[1:], T[1:] = X[:, :3], X[:, 3:]
         R = np.stack([_rodrigues(v) for v in rvec])
-    return RigResult(status, float(r[0]), R, T, rvec, np.array(par[:], np.int32), st_h.astype(np.int32),
-                     info_h[:, :, 1].astype(np.int64), info_h[:, :, 0].copy(), pose_h[:, 0:3].copy(), pose_h[:, 3:6].copy(),
-                     pose_h[:, 6].copy(), pose_h[:, 7].astype(np.int64), int(r[1]), int(r[2]), int(r[3]), int(r[4]))
+    return RigResult(status, float(r[0]), R, T, rvec, np.array(par[:], np.int32), view_status, view_points, view_rms, rvecs, tvecs,
+                     stamp_rms, stamp_points, int(r[1]), int(r[2]), int(r[3]), int(r[4]))
 
 
 def rig_calibrate_device(keypoints_lists: Sequence, col_count, row_count, square_len, cameras, dists, masks=None,
@@ -534,14 +349,8 @@ def rig_calibrate_device(keypoints_lists: Sequence, col_count, row_count, square
     B = len(keypoints_lists[0])
     if any(len(k) != B for k in keypoints_lists):
         raise ValueError("every camera needs as many views as camera 0")
-    if B == 0:
-        raise ValueError("no views")
-    mk = _mask_lists(masks, C)
-    packs = [pack_keypoints(k, dev) for k in keypoints_lists]
-    dm = [None if mk[c] is None else _slot_mask(keypoints_lists[c], mk[c], packs[c][2], dev) for c in range(C)]
+    packs, dm = _upload(keypoints_lists, _mask_lists(masks, C), dev)
     with torch.cuda.device(dev):
         r = rig_calibrate_pools([p[0] for p in packs], B, [p[2] for p in packs], True, col_count, row_count, square_len, cameras,
                                 dists, None if masks is None else dm, models)
-    if (r.view_status == PNP_BAD_ID).any():
-        raise _bad_id_error(col_count, row_count)
-    return r
+    return _no_bad_id(r, col_count, row_count)

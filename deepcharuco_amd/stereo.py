@@ -48,6 +48,7 @@ from typing import NamedTuple, Optional, Sequence
 import numpy as np
 
 from . import _dev, _lm, fisheye, pnp
+from .calib import _no_bad_id
 from .corner_pool import _pool_rows, pack_keypoints
 from .pnp import (PNP_BAD_ID, PNP_OK, PNP_TOO_FEW, _bad_id_error, _camera, _dist, _jacobi, _pool_ptrs, _right_jacobian, _rodrigues,
                   _rvec_of, _skew, _solve)
@@ -86,6 +87,8 @@ class StereoResult(NamedTuple):
 
 
 # ------------------------------------------------------------------------------------------------ the fp64 steps
+# Every step that does not depend on the number of cameras is written for C of them and kept here once; ``rig.py`` runs these same
+# functions, and a pair is a rig of two cameras whose timestamps all have both views (``_rows_of`` through ``_rig_rows``, ``_pair_segments``).
 
 def _project_q(Q: np.ndarray, img: np.ndarray, K: np.ndarray, k: np.ndarray, jac: bool):
     """Points Q (n, 3) in a camera's frame -> residuals (projected - observed, px) and, with ``jac``, d(u, v)/dQ (n, 2, 3):
@@ -149,28 +152,56 @@ def _model_args(camera, dist, model):
 
 
 class _Rows(NamedTuple):
-    """Every row of every used pair, pair by pair, camera 0's rows of a pair before camera 1's."""
+    """Every row of every used timestamp: timestamp by timestamp, its usable cameras ascending, each view's rows in pool order."""
     obj: np.ndarray              # (M, 3) board points
     img: np.ndarray              # (M, 2)
-    cam: np.ndarray              # (M,) 0 / 1
-    pair: np.ndarray             # (M,) index of the row's pair
-    starts: np.ndarray           # (N,) first row of every pair
-    vstarts: np.ndarray          # (2N,) first row of every view (pair-major)
+    cam: np.ndarray              # (M,) the row's camera
+    stamp: np.ndarray            # (M,) index of the row's timestamp among the used ones
+    starts: np.ndarray           # (N,) first row of every timestamp
+    vstarts: np.ndarray          # (NV,) first row of every view
+    vstamp: np.ndarray           # (NV,) the view's timestamp (index among the used ones) ...
+    vcam: np.ndarray             # (NV,) ... and camera
+    n_cams: int
+
+    @property
+    def pair(self) -> np.ndarray:
+        """``stamp`` under the name it has for two cameras."""
+        return self.stamp
 
 
-def _rows_of(views) -> _Rows:
-    """Per pair (obj0, img0, obj1, img1) -> the rows of all pairs, pair by pair, camera 0's rows first, in float64."""
-    cam, pair, obj, img, counts = [], [], [], [], []
-    for i, v in enumerate(views):
-        for c in range(2):
-            n = v[2 * c].shape[0]
-            obj.append(np.asarray(v[2 * c], np.float64))
-            img.append(np.asarray(v[2 * c + 1], np.float64))
+def _rig_rows(stamps, n_cams: int) -> _Rows:
+    """Per used timestamp a list of (camera, obj, img) of its usable views, cameras ascending -> the rows, in float64."""
+    obj, img, cam, stamp, counts, vstamp, vcam, per_stamp = [], [], [], [], [], [], [], []
+    for i, views in enumerate(stamps):
+        per_stamp.append(sum(o.shape[0] for _, o, _ in views))
+        for c, o, m in views:
+            n = o.shape[0]
+            obj.append(np.asarray(o, np.float64))
+            img.append(np.asarray(m, np.float64))
             cam.append(np.full(n, c))
-            pair.append(np.full(n, i))
+            stamp.append(np.full(n, i))
             counts.append(n)
+            vstamp.append(i)
+            vcam.append(c)
     vstarts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
-    return _Rows(np.concatenate(obj), np.concatenate(img), np.concatenate(cam), np.concatenate(pair), vstarts[0::2], vstarts)
+    starts = np.concatenate([[0], np.cumsum(per_stamp)[:-1]]).astype(np.int64)
+    return _Rows(np.concatenate(obj), np.concatenate(img), np.concatenate(cam), np.concatenate(stamp), starts, vstarts,
+                 np.array(vstamp), np.array(vcam), n_cams)
+
+
+def _rows_of(pairs) -> _Rows:
+    """Per pair (obj0, img0, obj1, img1) -> the rows of a rig of two cameras whose timestamps all have both views."""
+    return _rig_rows([[(0, v[0], v[1]), (1, v[2], v[3])] for v in pairs], 2)
+
+
+def _view_segments(rows: _Rows):
+    """``_normal_blocks``' segments with one per view: the rig's."""
+    return rows.vstarts, rows.vstamp.tolist(), rows.vcam.tolist()
+
+
+def _pair_segments(rows: _Rows):
+    """``_normal_blocks``' segments with one per pair, camera 0's rows (whose J_X is zero) before camera 1's: the stereo solve's."""
+    return rows.starts, list(range(rows.starts.size)), [1] * rows.starts.size
 
 
 def _skews(v: np.ndarray) -> np.ndarray:
@@ -181,21 +212,32 @@ def _skews(v: np.ndarray) -> np.ndarray:
     return S
 
 
-def _evaluate(rows: _Rows, cams, X: np.ndarray, P: np.ndarray, jac: bool):
-    """Residuals (M, 2) at rig X = (rvec, T) and board poses P (N, 6), and with ``jac`` the rows' Jacobians J_X (M, 2, 6) (zero for
-    camera 0's rows) and J_P (M, 2, 6) with respect to the row's own P_t.  None if a point is not in front of its camera."""
-    RX = _rodrigues(X[:3])
+def _points(rows: _Rows, X: np.ndarray, P: np.ndarray):
+    """-> (q_0 (M, 3): the rows' board points in camera 0's frame, q (M, 3): in their own camera's, R(X_c) [C - 1, 3, 3], R(P_t))."""
     RP = np.stack([_rodrigues(p[:3]) for p in P])
-    Q0 = np.einsum("mij,mj->mi", RP[rows.pair], rows.obj) + P[rows.pair, 3:]
-    c1 = rows.cam == 1
+    RX = np.stack([_rodrigues(x[:3]) for x in X])
+    Q0 = np.einsum("mij,mj->mi", RP[rows.stamp], rows.obj) + P[rows.stamp, 3:]
     Q = Q0.copy()
-    Q[c1] = Q0[c1] @ RX.T + X[3:]
+    for c in range(1, rows.n_cams):
+        sel = rows.cam == c
+        Q[sel] = Q0[sel] @ RX[c - 1].T + X[c - 1, 3:]
+    return Q0, Q, RX, RP
+
+
+def _evaluate(rows: _Rows, cams, X: np.ndarray, P: np.ndarray, jac: bool):
+    """Residuals (M, 2) at the rig X [C - 1, 6] (or, for two cameras, [6]) of (rvec, T) and the board poses P [N, 6], and with
+    ``jac`` the rows' Jacobians J_X (M, 2, 6) with respect to the row's OWN camera's X_c (zero for camera 0's rows) and J_P
+    (M, 2, 6) with respect to the row's own P_t.  None if a point is not in front of its camera."""
+    X = X.reshape(-1, 6)
+    Q0, Q, RX, RP = _points(rows, X, P)
     if not (Q[:, 2] > 0).all():
         return None
     M = rows.obj.shape[0]
     res, D = np.empty((M, 2)), (np.empty((M, 2, 3)) if jac else None)
     for c, cam in enumerate(cams):
         sel = rows.cam == c
+        if not sel.any():
+            continue
         r, d = _model_of(cam)[1](Q[sel], rows.img[sel], cam[0], cam[1], jac)
         res[sel] = r
         if jac:
@@ -203,61 +245,130 @@ def _evaluate(rows: _Rows, cams, X: np.ndarray, P: np.ndarray, jac: bool):
     if not jac:
         return res, None, None
     JrP = np.stack([_right_jacobian(p[:3]) for p in P])
-    dQ0_dr = -np.einsum("mij,mjk,mkl->mil", RP[rows.pair], _skews(rows.obj), JrP[rows.pair])      # -R_P [o]x Jr(r_P)
+    dQ0_dr = -np.einsum("mij,mjk,mkl->mil", RP[rows.stamp], _skews(rows.obj), JrP[rows.stamp])    # -R_P [o]x Jr(r_P)
     Dp = D.copy()
-    Dp[c1] = D[c1] @ RX                                        # camera 1 sees Q0 through R_X: d(u, v)/dQ0 = d(u, v)/dQ R_X
-    JP = np.concatenate([Dp @ dQ0_dr, Dp], 2)
     JX = np.zeros((M, 2, 6))
-    dQ_drx = -np.einsum("ij,mjk,kl->mil", RX, _skews(Q0[c1]), _right_jacobian(X[:3]))              # -R_X [Q0]x Jr(r_X)
-    JX[c1, :, :3] = D[c1] @ dQ_drx
-    JX[c1, :, 3:] = D[c1]
+    for c in range(1, rows.n_cams):
+        sel = rows.cam == c
+        if not sel.any():
+            continue
+        Dp[sel] = D[sel] @ RX[c - 1]                           # camera c sees q_0 through R_c: d(u, v)/dq_0 = d(u, v)/dq R_c
+        dQ_drx = -np.einsum("ij,mjk,kl->mil", RX[c - 1], _skews(Q0[sel]), _right_jacobian(X[c - 1, :3]))   # -R_c [q_0]x Jr(r_c)
+        JX[sel, :, :3] = D[sel] @ dQ_drx
+        JX[sel, :, 3:] = D[sel]
+    JP = np.concatenate([Dp @ dQ0_dr, Dp], 2)
     return res, JX, JP
 
 
-def _normal_blocks(rows: _Rows, cams, X, P):
-    """The blocks of JtJ and Jtr: U [N, 6, 6] (P_t - P_t), W [N, 6, 6] (X - P_t), V [6, 6] (X - X, summed over the pairs in order),
-    ga [6], gb [N, 6], the per-view costs [N, 2].  None if a point is behind a camera."""
+def _view_costs(rows: _Rows, res: np.ndarray) -> np.ndarray:
+    """-> [N, C]: the cost of every usable view, zero elsewhere."""
+    out = np.zeros((rows.starts.size, rows.n_cams))
+    out[rows.vstamp, rows.vcam] = np.add.reduceat((res * res).sum(1), rows.vstarts)
+    return out
+
+
+def _total(costs: np.ndarray) -> float:
+    """Per timestamp over the cameras ascending, then over the timestamps in order."""
+    per = np.zeros(costs.shape[0])
+    for c in range(costs.shape[1]):
+        per = per + costs[:, c]
+    s = 0.0
+    for v in per.tolist():
+        s += v
+    return s
+
+
+def _normal_blocks(rows: _Rows, cams, X, P, segments):
+    """The blocks of JtJ and Jtr as ``_lm.schur_step`` takes them with n = 6 (C - 1): U [N, 6, 6] (P_t - P_t), W [N, n, 6]
+    (X - P_t), V [n, n] (X - X, block diagonal, summed over the timestamps in order), ga [n], gb [N, 6], the per-view costs
+    [N, C].  ``segments`` = (first row, timestamp, camera) of every run of rows whose J_X products are summed by one reduction,
+    ``_view_segments`` or ``_pair_segments``: numpy does not add a longer run in the same order, so a pair's sum and its two
+    views' differ by rounding, and each definition keeps the bits it has.  None if a point is behind a camera."""
     ev = _evaluate(rows, cams, X, P, True)
     if ev is None:
         return None
     res, JX, JP = ev
-    s = rows.starts
-    U = np.add.reduceat(np.einsum("mai,maj->mij", JP, JP), s, 0)
-    W = np.add.reduceat(np.einsum("mai,maj->mij", JX, JP), s, 0)
-    Vt = np.add.reduceat(np.einsum("mai,maj->mij", JX, JX), s, 0)
-    gb = np.add.reduceat(np.einsum("mai,ma->mi", JP, res), s, 0)
-    gat = np.add.reduceat(np.einsum("mai,ma->mi", JX, res), s, 0)
-    V, ga = np.zeros((6, 6)), np.zeros(6)
-    for i in range(len(s)):
-        V += Vt[i]
-        ga += gat[i]
+    N, n = rows.starts.size, 6 * (rows.n_cams - 1)
+    first, stamp, cam = segments
+    U = np.add.reduceat(np.einsum("mai,maj->mij", JP, JP), rows.starts, 0)
+    gb = np.add.reduceat(np.einsum("mai,ma->mi", JP, res), rows.starts, 0)
+    Ws = np.add.reduceat(np.einsum("mai,maj->mij", JX, JP), first, 0)
+    Vs = np.add.reduceat(np.einsum("mai,maj->mij", JX, JX), first, 0)
+    gs = np.add.reduceat(np.einsum("mai,ma->mi", JX, res), first, 0)
+    W, V, ga = np.zeros((N, n, 6)), np.zeros((n, n)), np.zeros(n)
+    for i, (t, c) in enumerate(zip(stamp, cam)):               # timestamps in order
+        if c == 0:
+            continue
+        s = slice(6 * (c - 1), 6 * c)
+        W[t, s] = Ws[i]
+        V[s, s] += Vs[i]
+        ga[s] += gs[i]
     return U, W, V, ga, gb, _view_costs(rows, res)
 
 
-def _view_costs(rows: _Rows, res: np.ndarray) -> np.ndarray:
-    return np.add.reduceat((res * res).sum(1), rows.vstarts).reshape(-1, 2)
-
-
-def _total(costs: np.ndarray) -> float:
-    c = 0.0
-    for v in costs.sum(1).tolist():
-        c += v
-    return c
-
-
-def _refine(rows: _Rows, cams, X: np.ndarray, P: np.ndarray):
-    """Joint LM (module docstring, step 4) -> (status, X, P, per-view costs [N, 2], accepted steps, attempts)."""
-    def trial_costs(x, p):
-        ev = _evaluate(rows, cams, x, p, False)
+def _refine(rows: _Rows, cams, X: np.ndarray, P: np.ndarray, segments):
+    """Joint LM (module docstring, step 4) -> (status, X in the shape it came in, P, per-view costs [N, C], accepted steps,
+    attempts)."""
+    def trial_costs(g, p):
+        ev = _evaluate(rows, cams, g, p, False)
         return _view_costs(rows, ev[0]) if ev is not None else None
 
-    return _lm.refine(X, P, lambda x, p: _normal_blocks(rows, cams, x, p), trial_costs, _total, True, STEREO_MAX_ITER, STEREO_EPS)
+    st, g, P, vc, iters, attempts = _lm.refine(X.ravel().copy(), P, lambda g, p: _normal_blocks(rows, cams, g, p, segments),
+                                               trial_costs, _total, True, STEREO_MAX_ITER, STEREO_EPS)
+    return st, g.reshape(X.shape), P, vc, iters, attempts
+
+
+def _depth_margin(rows: _Rows, X: np.ndarray, P: np.ndarray) -> float:
+    """The smallest depth of a row at (X, P), relative to its distance from its camera's centre."""
+    Q = _points(rows, X.reshape(-1, 6), P)[1]
+    return float((Q[:, 2] / np.linalg.norm(Q, axis=1)).min())
+
+
+def _view_poses(keypoints_lists, masks, cams, board, pool_order):
+    """Steps 1 and 2 for C cameras: ``keypoints_lists[c][t]`` and ``masks[c]`` (None, or per timestamp None or a bool array in the
+    caller's row order) -> (view_status [T, C], view_points [T, C], poses [T, C, 6], and per [t][c] the object and the image
+    points of a view that passed its checks, else None)."""
+    C, B = len(cams), len(keypoints_lists[0])
+    col_count, row_count, square_len = board
+    n_ids = (col_count - 1) * (row_count - 1)
+    view_status = np.full((B, C), PNP_OK, np.int32)
+    view_points = np.zeros((B, C), np.int64)
+    poses = np.zeros((B, C, 6))
+    obj_l, img_l = [[None] * C for _ in range(B)], [[None] * C for _ in range(B)]
+    for t in range(B):
+        for c in range(C):
+            kp, order = _pool_rows(keypoints_lists[c][t], pool_order)
+            keep = np.ones(kp.shape[0], bool)
+            if masks[c] is not None and masks[c][t] is not None:
+                keep = np.asarray(masks[c][t]).astype(bool).ravel()
+                if keep.size != kp.shape[0]:
+                    raise ValueError(f"view ({c}, {t}) has {kp.shape[0]} rows but its mask {keep.size}")
+            kp = kp[order][keep[order]]
+            view_points[t, c] = kp.shape[0]
+            if kp.shape[0] < 4:
+                view_status[t, c] = PNP_TOO_FEW
+                continue
+            ids = kp[:, 2].astype(np.int64)
+            if ids.min() < 0 or ids.max() >= n_ids:
+                view_status[t, c] = PNP_BAD_ID
+                continue
+            obj_l[t][c] = pnp.object_points(ids, col_count, row_count, square_len)
+            img_l[t][c] = kp[:, :2].astype(np.float32)
+            st, pose = _model_of(cams[c])[0](obj_l[t][c], img_l[t][c], cams[c][0], cams[c][1])
+            view_status[t, c] = st
+            poses[t, c] = pose[:6]
+    return view_status, view_points, poses, obj_l, img_l
 
 
 def lower_median(values) -> float:
     """Element (n - 1) // 2 of the sorted values."""
     v = np.sort(np.asarray(values, np.float64))
     return float(v[(v.size - 1) // 2])
+
+
+def _sine(R: np.ndarray) -> float:
+    """The sine term of ``pnp._rvec_of`` at R: its branch switches at 1e-5."""
+    return 0.5 * math.sqrt((R[2, 1] - R[1, 2]) ** 2 + (R[0, 2] - R[2, 0]) ** 2 + (R[1, 0] - R[0, 1]) ** 2)
 
 
 def _rig_init(poses0: np.ndarray, poses1: np.ndarray):
@@ -275,7 +386,7 @@ def _rig_init(poses0: np.ndarray, poses1: np.ndarray):
         return STEREO_DEGENERATE, None, math.inf
     Q = M @ (W @ np.diag(1.0 / np.sqrt(ws)) @ W.T)
     X0 = np.r_[_rvec_of(Q), T]
-    sine = 0.5 * math.sqrt((Q[2, 1] - Q[1, 2]) ** 2 + (Q[0, 2] - Q[2, 0]) ** 2 + (Q[1, 0] - Q[0, 1]) ** 2)
+    sine = _sine(Q)
     if not np.isfinite(X0).all():
         return STEREO_NONFINITE, None, sine
     return STEREO_OK, X0, sine
@@ -341,34 +452,8 @@ def stereo_calibrate_host_full(keypoints_list0, keypoints_list1, col_count, row_
     lists = (keypoints_list0, keypoints_list1)
     if len(lists[0]) != len(lists[1]):
         raise ValueError(f"{len(lists[0])} views of camera 0 but {len(lists[1])} of camera 1")
-    B, n_ids = len(lists[0]), (col_count - 1) * (row_count - 1)
-    mk = _mask_pair(masks)
-    view_status = np.full((B, 2), PNP_OK, np.int32)
-    view_points = np.zeros((B, 2), np.int64)
-    poses = np.zeros((B, 2, 6))
-    obj_l, img_l = [[None, None] for _ in range(B)], [[None, None] for _ in range(B)]
-    for t in range(B):
-        for c in range(2):
-            kp, order = _pool_rows(lists[c][t], pool_order)
-            keep = np.ones(kp.shape[0], bool)
-            if mk[c] is not None and mk[c][t] is not None:
-                keep = np.asarray(mk[c][t]).astype(bool).ravel()
-                if keep.size != kp.shape[0]:
-                    raise ValueError(f"view ({c}, {t}) has {kp.shape[0]} rows but its mask {keep.size}")
-            kp = kp[order][keep[order]]
-            view_points[t, c] = kp.shape[0]
-            if kp.shape[0] < 4:
-                view_status[t, c] = PNP_TOO_FEW
-                continue
-            ids = kp[:, 2].astype(np.int64)
-            if ids.min() < 0 or ids.max() >= n_ids:
-                view_status[t, c] = PNP_BAD_ID
-                continue
-            obj_l[t][c] = pnp.object_points(ids, col_count, row_count, square_len)
-            img_l[t][c] = kp[:, :2].astype(np.float32)
-            st, pose = _model_of(cams[c])[0](obj_l[t][c], img_l[t][c], cams[c][0], cams[c][1])
-            view_status[t, c] = st
-            poses[t, c] = pose[:6]
+    view_status, view_points, poses, obj_l, img_l = _view_poses(lists, _mask_pair(masks), cams, (col_count, row_count, square_len),
+                                                                pool_order)
     used = np.flatnonzero((view_status == PNP_OK).all(1))
 
     def done(status, X=None, P=None, vc=None, iters=0, attempts=0, margin=math.inf):
@@ -382,24 +467,26 @@ def stereo_calibrate_host_full(keypoints_list0, keypoints_list1, col_count, row_
     if st != STEREO_OK:
         return done(st, margin=margin)
     rows = _rows_of([(obj_l[t][0], img_l[t][0], obj_l[t][1], img_l[t][1]) for t in used])
-    st, X, P, vc, iters, attempts = _refine(rows, cams, X0, poses[used, 0].copy())
+    st, X, P, vc, iters, attempts = _refine(rows, cams, X0, poses[used, 0].copy(), _pair_segments(rows))
     if st == STEREO_OK and with_margin:
-        RX = _rodrigues(X[:3])
-        Q0 = np.einsum("mij,mj->mi", np.stack([_rodrigues(p[:3]) for p in P])[rows.pair], rows.obj) + P[rows.pair, 3:]
-        Q = np.where((rows.cam == 1)[:, None], Q0 @ RX.T + X[3:], Q0)
-        margin = min(margin, float((Q[:, 2] / np.linalg.norm(Q, axis=1)).min()))
+        margin = min(margin, _depth_margin(rows, X, P))
     return done(st, X, P, vc, iters, attempts, margin)
 
 
-def _raise_like_cv2(r: StereoResult, col_count, row_count):
+def _raise_like_cv2(r, col_count, row_count, what="stereo", empty_ok=False):
+    """Raise where cv2's calibrations would, for a ``StereoResult`` or a ``RigResult``.  ``empty_ok``: a view without rows is a
+    camera that did not see the board, not an error (the rig's rule)."""
     if (r.view_status == PNP_BAD_ID).any():
         raise _bad_id_error(col_count, row_count)
-    bad = np.argwhere(r.view_status != PNP_OK)
+    unusable = r.view_status != PNP_OK
+    if empty_ok:
+        unusable &= r.view_points > 0
+    bad = np.argwhere(unusable)
     if bad.size:
         t, c = (int(v) for v in bad[0])
         raise ValueError(f"view {t} of camera {c} cannot be used (status {int(r.view_status[t, c])})")
-    if r.status != STEREO_OK:
-        raise ValueError(f"stereo calibration failed (status {r.status})")
+    if r.status != _lm.LM_OK:
+        raise ValueError(f"{what} calibration failed (status {r.status})")
 
 
 def stereo_calibrate_host(keypoints_list0, keypoints_list1, col_count, row_count, square_len, camera0, dist0, camera1, dist1,
@@ -426,6 +513,39 @@ def workspace_bytes(batch: int, pool0: int, pool1: int) -> int:
     return n
 
 
+def _device_masks(masks, pools, dev):
+    """Every mask that is given must be a contiguous uint8 tensor on ``dev`` of at least its pool's size (ValueError)."""
+    import torch
+    for c, (m, pool) in enumerate(zip(masks, pools)):
+        if m is not None:
+            _dev.tensor(m, dev, torch.uint8, (pool,), f"mask {c} must be a contiguous uint8 tensor of at least {pool} values on {dev}",
+                        "min")
+
+
+def _outputs(batch, n_cams, dev):
+    """-> what a joint solve writes on the device: view status int32 [B, C], pose float64 [B, POSE_WORDS], info float64 [B, C, 2]."""
+    import torch
+    return (torch.empty((batch, n_cams), dtype=torch.int32, device=dev),
+            torch.empty((batch, pnp.POSE_WORDS), dtype=torch.float64, device=dev),
+            torch.empty((batch, n_cams, 2), dtype=torch.float64, device=dev))
+
+
+def _call(entry, head, tags, tail):
+    """``dcx_<entry>_pool(*head, *tail, stream)``, or with ``tags``, the cameras' models as the C entry takes them,
+    ``dcx_<entry>_models_pool(*head, *tags, *tail, stream)``."""
+    from . import _lib
+    name = f"dcx_{entry}_pool" if tags is None else f"dcx_{entry}_models_pool"
+    _lib.check(getattr(_lib.lib(), name)(*head, *(tags or ()), *tail, _lib.current_stream()), name)
+
+
+def _unpack(st, pose, info):
+    """``_outputs`` after the call -> host arrays: view status [B, C], rvecs, tvecs [B, 3], the timestamps' rms and rows [B], the
+    views' rms and rows [B, C]."""
+    st_h, pose_h, info_h = st.cpu().numpy(), pose.cpu().numpy(), info.cpu().numpy()
+    return (st_h.astype(np.int32), pose_h[:, 0:3].copy(), pose_h[:, 3:6].copy(), pose_h[:, 6].copy(), pose_h[:, 7].astype(np.int64),
+            info_h[:, :, 0].copy(), info_h[:, :, 1].astype(np.int64))
+
+
 def stereo_calibrate_pool(packed0, packed1, batch: int, pool0: int, pool1: int, refined: bool, col_count, row_count, square_len,
                           camera0, dist0, camera1, dist1, masks=None, models=None) -> StereoResult:
     """The rig of two cameras from two ``infer_batch_device`` results of ``batch`` frames each, read in place from the two corner
@@ -442,17 +562,12 @@ def stereo_calibrate_pool(packed0, packed1, batch: int, pool0: int, pool1: int, 
     if packed1.device != dev:
         raise ValueError("the two pools must be on one device")
     p0, p1 = _pool_ptrs(packed0, batch, pool0, refined), _pool_ptrs(packed1, batch, pool1, refined)
-    mk = list(_mask_pair(masks))
-    for c, pool in enumerate((pool0, pool1)):
-        if mk[c] is not None:
-            _dev.tensor(mk[c], dev, torch.uint8, (pool,), f"mask {c} must be a contiguous uint8 tensor of at least {pool} values on {dev}",
-                        "min")
+    mk = _mask_pair(masks)
+    _device_masks(mk, (pool0, pool1), dev)
     models = _models(models, 2)
     cam0, d0, n0 = _model_args(camera0, dist0, models and models[0])
     cam1, d1, n1 = _model_args(camera1, dist1, models and models[1])
-    st = torch.empty((batch, 2), dtype=torch.int32, device=dev)
-    pose = torch.empty((batch, pnp.POSE_WORDS), dtype=torch.float64, device=dev)
-    info = torch.empty((batch, 2, 2), dtype=torch.float64, device=dev)
+    st, pose, info = _outputs(batch, 2, dev)
     nbytes = workspace_bytes(batch, pool0, pool1)
     ws = _dev.workspace(None, dev, nbytes)
     res = (_ctypes.c_double * RESULT_WORDS)()
@@ -460,12 +575,8 @@ def stereo_calibrate_pool(packed0, packed1, batch: int, pool0: int, pool1: int, 
             float(square_len), cam0, d0, n0, cam1, d1, n1)
     tail = (ws.data_ptr(), nbytes, st.data_ptr(), pose.data_ptr(), info.data_ptr(), res)
     with torch.cuda.device(dev):
-        if models is None:
-            _lib.check(_lib.lib().dcx_stereo_calibrate_pool(*head, *tail, _lib.current_stream()), "dcx_stereo_calibrate_pool")
-        else:
-            _lib.check(_lib.lib().dcx_stereo_calibrate_models_pool(*head, MODELS.index(models[0]), MODELS.index(models[1]), *tail,
-                                                                   _lib.current_stream()), "dcx_stereo_calibrate_models_pool")
-        st_h, pose_h, info_h = st.cpu().numpy(), pose.cpu().numpy(), info.cpu().numpy()
+        _call("stereo_calibrate", head, models and [MODELS.index(m) for m in models], tail)
+        view_status, rvecs, tvecs, pair_rms, pair_points, view_rms, view_points = _unpack(st, pose, info)
     r = np.array(res[:], np.float64)
     status = int(r[11])
     R, E, F = np.zeros((3, 3)), np.zeros((3, 3)), np.zeros((3, 3))
@@ -474,9 +585,8 @@ def stereo_calibrate_pool(packed0, packed1, batch: int, pool0: int, pool1: int, 
         E, F = essential_fundamental(R, r[3:6], _camera(camera0), _camera(camera1))
     if models is not None and "fisheye" in models:
         F = None
-    return StereoResult(status, float(r[6]), R, r[3:6].copy(), r[0:3].copy(), E, F, st_h.astype(np.int32), pose_h[:, 0:3].copy(),
-                        pose_h[:, 3:6].copy(), pose_h[:, 6].copy(), pose_h[:, 7].astype(np.int64), info_h[:, :, 0].copy(),
-                        info_h[:, :, 1].astype(np.int64), int(r[7]), int(r[8]), int(r[9]), int(r[10]))
+    return StereoResult(status, float(r[6]), R, r[3:6].copy(), r[0:3].copy(), E, F, view_status, rvecs, tvecs, pair_rms, pair_points,
+                        view_rms, view_points, int(r[7]), int(r[8]), int(r[9]), int(r[10]))
 
 
 def _slot_mask(keypoints_list, masks, pool, dev):
@@ -496,6 +606,15 @@ def _slot_mask(keypoints_list, masks, pool, dev):
     return torch.from_numpy(out).to(dev)
 
 
+def _upload(keypoints_lists, masks, dev):
+    """The ``*_device`` calls' views, one list per camera, and ``masks`` (per camera None or its per-view masks) -> (per camera
+    ``pack_keypoints``' (packed, batch, pool), per camera None or its mask by slot).  ValueError for no views."""
+    if len(keypoints_lists[0]) == 0:
+        raise ValueError("no views")
+    packs = [pack_keypoints(k, dev) for k in keypoints_lists]
+    return packs, [None if m is None else _slot_mask(k, m, p[2], dev) for k, m, p in zip(keypoints_lists, masks, packs)]
+
+
 def stereo_calibrate_device(keypoints_list0: Sequence, keypoints_list1: Sequence, col_count, row_count, square_len, camera0, dist0,
                             camera1, dist1, masks=None, device="cuda", models=None) -> StereoResult:
     """``stereo_calibrate_host_full`` on the GPU from ``infer_image``-format keypoint arrays ([x, y, id] rows; one list per
@@ -509,16 +628,8 @@ def stereo_calibrate_device(keypoints_list0: Sequence, keypoints_list1: Sequence
     _model_args(camera1, dist1, models and models[1])
     if len(keypoints_list0) != len(keypoints_list1):
         raise ValueError(f"{len(keypoints_list0)} views of camera 0 but {len(keypoints_list1)} of camera 1")
-    if len(keypoints_list0) == 0:
-        raise ValueError("no views")
-    mk = _mask_pair(masks)
-    packed0, b, pool0 = pack_keypoints(keypoints_list0, dev)
-    packed1, _, pool1 = pack_keypoints(keypoints_list1, dev)
-    dm = [None if m is None else _slot_mask(kl, m, pool, dev)
-          for kl, m, pool in ((keypoints_list0, mk[0], pool0), (keypoints_list1, mk[1], pool1))]
+    ((packed0, b, pool0), (packed1, _, pool1)), dm = _upload((keypoints_list0, keypoints_list1), _mask_pair(masks), dev)
     with torch.cuda.device(dev):
         r = stereo_calibrate_pool(packed0, packed1, b, pool0, pool1, True, col_count, row_count, square_len, camera0, dist0,
                                   camera1, dist1, None if masks is None else tuple(dm), models)
-    if (r.view_status == PNP_BAD_ID).any():
-        raise _bad_id_error(col_count, row_count)
-    return r
+    return _no_bad_id(r, col_count, row_count)

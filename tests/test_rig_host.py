@@ -322,3 +322,61 @@ def test_argument_errors():
     with pytest.raises(ValueError):
         _solve(s, masks=[None, None])
     assert rig.RIG_DISCONNECTED == 4 and (rig.RIG_OK, rig.RIG_NO_STAMPS, rig.RIG_DEGENERATE, rig.RIG_NONFINITE) == (0, 1, 2, 3)
+
+
+# ------------------------------------------------------------------------------------------------ one text for both definitions
+
+def test_stereo_and_rig_tables_run_through_one_evaluate_and_one_normal_blocks():
+    """Two timestamps, four rows per view, a distorted pinhole and a plain one.  The row table built the stereo way (per pair) and
+    the rig way (per timestamp its views) is one table, res / J_X / J_P come out of the one ``_evaluate`` equal bit for bit
+    whether X is stereo's [6] or the rig's [1, 6], and ``_normal_blocks`` under the two segmentations of the J_X sums (per pair,
+    per view) gives the same bits wherever no J_X enters: U, g_b and the costs.  (W, V and g_a may differ by rounding: numpy adds a
+    pair's rows in another order than its two views' rows, which is why the segmentation is an argument.)"""
+    s = rx.scene(21, 2, (0, 30), ("B", "A"), rows=4)
+    stamps = rx.pool_views(s, range(2))
+    by_view = rig._rows_of(stamps, 2)
+    by_pair = stereo._rows_of([(v[0][1], v[0][2], v[1][1], v[1][2]) for v in stamps])
+    assert by_view.obj.shape == (16, 3) and by_view.n_cams == by_pair.n_cams == 2
+    for a, b in zip(by_view[:-1], by_pair[:-1]):
+        assert a.dtype == b.dtype and np.array_equal(a, b)
+    cams = [(stereo._camera(K), stereo._dist(d)) for K, d in zip(*rx.cam_args(s))]
+    rng = np.random.default_rng(6)
+    X = s.X[0] + rng.normal(scale=1e-3, size=6)
+    P = s.P + rng.normal(scale=1e-3, size=s.P.shape)
+    one, two = stereo._evaluate(by_pair, cams, X, P, True), stereo._evaluate(by_view, cams, X[None], P, True)
+    assert all(np.array_equal(a, b) for a, b in zip(one, two))
+    assert not one[1][by_pair.cam == 0].any() and one[1][by_pair.cam == 1].any()
+    pair = stereo._normal_blocks(by_pair, cams, X, P, stereo._pair_segments(by_pair))
+    view = stereo._normal_blocks(by_view, cams, X[None], P, stereo._view_segments(by_view))
+    for i, name in ((0, "U"), (4, "gb"), (5, "costs")):
+        assert np.array_equal(pair[i], view[i]), name
+    gaps = {name: float(np.abs(pair[i] - view[i]).max()) for i, name in ((1, "W"), (2, "V"), (3, "ga"))}
+    print(f"per pair against per view: U, gb, costs equal; largest gaps {gaps}")
+    assert pair[1].shape == (2, 6, 6) and pair[2].shape == (6, 6) and pair[5].shape == (2, 2)
+
+
+def test_the_row_table_of_a_rig_with_absent_cameras():
+    """Three cameras, three timestamps; camera 1 is absent at timestamp 1 and camera 0 at timestamp 2.  The per-view loop and
+    ``_rows_of`` that both definitions call give the table ``rig_calibrate_host_full`` has always built: written out here."""
+    vis = np.ones((3, 3), bool)
+    vis[1, 1] = vis[2, 0] = False
+    s = rx.scene(22, 3, visible=vis, rows=[[4, 5, 6], [5, 4, 6], [6, 5, 4]], **FAN3)
+    cams = rig._cameras(*rx.cam_args(s))[0]
+    view_status, view_points, poses, obj_l, img_l = stereo._view_poses(s.kps, [None] * 3, cams, s.board, False)
+    few = pnp.PNP_TOO_FEW
+    assert view_status.tolist() == [[0, 0, 0], [0, few, 0], [few, 0, 0]] and view_status.dtype == np.int32
+    assert view_points.tolist() == [[4, 5, 6], [5, 0, 6], [0, 5, 4]]
+    assert obj_l[1][1] is None and img_l[2][0] is None and not poses[1, 1].any() and not poses[2, 0].any()
+    assert poses.shape == (3, 3, 6) and all(poses[t, c].any() for t in range(3) for c in range(3) if vis[t, c])
+    usable = view_status == pnp.PNP_OK
+    rows = rig._rows_of([[(c, obj_l[t][c], img_l[t][c]) for c in range(3) if usable[t, c]] for t in range(3)], 3)
+    assert rows.vstamp.tolist() == [0, 0, 0, 1, 1, 2, 2] and rows.vcam.tolist() == [0, 1, 2, 0, 2, 1, 2]
+    assert rows.starts.tolist() == [0, 15, 26] and rows.vstarts.tolist() == [0, 4, 9, 15, 20, 26, 31]
+    assert rows.cam.tolist() == [0] * 4 + [1] * 5 + [2] * 6 + [0] * 5 + [2] * 6 + [1] * 5 + [2] * 4
+    assert rows.stamp.tolist() == [0] * 15 + [1] * 11 + [2] * 9 and rows.n_cams == 3
+    assert rows.obj.dtype == rows.img.dtype == np.float64 and rows.obj.shape == (35, 3) and rows.img.shape == (35, 2)
+    want = rx.pool_views(s, range(3))                                     # the rows themselves, in pool order
+    assert np.array_equal(rows.obj, np.concatenate([o for v in want for _, o, _ in v]).astype(np.float64))
+    assert np.array_equal(rows.img, np.concatenate([m for v in want for _, _, m in v]))
+    r = _solve(s)
+    assert r.status == rig.RIG_OK and r.stamps_used == 3 and r.points_used == 35 and r.view_status.tolist() == view_status.tolist()
