@@ -95,6 +95,9 @@ SIGNATURES = {
                                    C.POINTER(C.c_double), _vp]),
     "dcx_rig_calibrate_models_pool": (_i, [_i, _vp, C.POINTER(C.c_int), _i, _i, _i, C.c_double, _vp, _sz, _vp, _vp, _vp,
                                           C.POINTER(C.c_int32), C.POINTER(C.c_double), _vp]),
+    "dcx_rig_pose_workspace_bytes": (_sz, [_i, _i, C.POINTER(C.c_int)]),
+    "dcx_rig_pose_pool": (_i, [_i, _vp, C.POINTER(C.c_int), C.POINTER(C.c_double), _i, _i, _i, C.c_double, _vp, _sz, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _vp]),
     "dcx_undistort_rectify_map": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double), _i, C.POINTER(C.c_double),
                                       C.POINTER(C.c_double), _i, _i, _vp, _vp]),
     "dcx_rectify_points_pool": (_i, [_vp, _vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), _i, C.POINTER(C.c_double),

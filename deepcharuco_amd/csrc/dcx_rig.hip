@@ -36,8 +36,8 @@
 //   trial           grid (timestamp, camera): dP_t = z - sum_c Y_c dX_c (cameras ascending), the view's trial cost; camera 0's block
 //                   also writes the trial pose and the timestamp's share of |dp|^2 and |p|^2
 //   decide          (one workgroup) lm_decide_block with STOP_FORCED
-// init_views, evaluate and trial, the three that meet a camera, are templates on the camera table: RigCams, or MixedCams for a rig
-// with a fisheye camera in it (dcx_rig_calibrate_models_pool).  The kernels' text knows no model: on a table of AnyCamera the model is
+// init_views, evaluate and trial, the three that meet a camera, are templates on the camera table (dcx_stereo_dev.h): RigCams, or
+// MixedCams for a rig with a fisheye camera in it (dcx_rig_calibrate_models_pool).  The kernels' text knows no model: on a table of AnyCamera the model is
 // chosen per view, inside the step (the AnyCamera overloads of view_solve, accumulate_view and view_cost in dcx_stereo_dev.h), and
 // uniformly per workgroup, which works on camera blockIdx.y alone.  The other launches never see a camera.
 // The LM loop runs on the host (lm_run): the call synchronises its stream and cannot be captured in a graph.  Every sum has a fixed
@@ -50,7 +50,6 @@
 
 namespace {
 
-constexpr int kMaxCams = DCX_RIG_MAX_CAMERAS;
 constexpr int kMaxG = 6 * (kMaxCams - 1);                 // 42 shared parameters at the most
 constexpr int kResWords = 48;                             // LmState::result: g (42), rms, steps, attempts, stamps, points, status
 constexpr int kRedThreads = kLmThreads;                   // decide's one-workgroup reduction over timestamps
@@ -66,17 +65,6 @@ enum : int { kOverlap = 0, kHeadWords = 2 };
 using RigState = LmState<kMaxG, kResWords>;
 constexpr int kState = 1536;             // bytes reserved for RigState
 static_assert(sizeof(RigState) <= kState, "state");
-
-struct RigCams {                         // every camera a pinhole: what dcx_rig_calibrate_pool has always passed
-    MaskedPool pl[kMaxCams];
-    PnpCamera cam[kMaxCams];
-};
-
-struct MixedCams {                       // a model tag per camera (dcx_rig_calibrate_models_pool with a fisheye camera in the rig)
-    MaskedPool pl[kMaxCams];
-    AnyCamera cam[kMaxCams];
-};
-static_assert(sizeof(MixedCams) <= 2048, "kernel arguments");
 
 struct Tree {
     int parent[kMaxCams];                // -1 for camera 0
@@ -744,22 +732,6 @@ int rig_calibrate(const CAMS& cams, const int* pools, int C, int batch, void* d_
     h_result[5] = res[kMaxG + 5];
     for (int i = 0; i < n; ++i) h_result[8 + i] = res[i];
     return 0;
-}
-
-// The pools and, per camera, what `camera` makes of its model fields -> false if anything is refused
-template <class CAMS, class F>
-bool camera_table(int n_cams, const DcxRigCamera* h_cams, int batch, int col_count, int row_count, double square_len, CAMS& cams,
-                  int* pools, F&& camera) {
-    if (n_cams < 2 || n_cams > kMaxCams || !h_cams) return false;
-    for (int c = 0; c < n_cams; ++c) {
-        const DcxRigCamera& h = h_cams[c];
-        cams.pl[c].mask = h.d_mask;
-        if (!corner_pool(h.d_counts, h.d_starts, h.d_rows, h.d_xy, batch, h.pool, col_count, row_count, square_len, cams.pl[c].p))
-            return false;
-        if (!camera(c, h, cams.cam[c])) return false;
-        pools[c] = h.pool;
-    }
-    return true;
 }
 
 }  // namespace

@@ -8,6 +8,7 @@
 //   accumulate_view, view_cost                   a view's rows added to its packed 13 x 13 / its trial cost
 //   AnyCamera, any_camera, with_camera           a camera of either model behind a tag, for rigs whose cameras differ
 //   view_solve, accumulate_view, view_cost       on AnyCamera: the same step on the camera's own class, through with_camera
+//   RigCams, MixedCams, camera_table             a rig's cameras and pools as one kernel argument, all pinholes or tagged
 // view_solve, stereo_row, accumulate_view and view_cost are templates on the camera class, as dcx_pnp_dev.h's solver is: PnpCamera
 // (dcx_camera_dev.h) or FisheyeCamera (dcx_fisheye_dev.h).  The three that a kernel calls have an AnyCamera overload each, so a
 // kernel is one text for a plain camera and for a tagged one: the model is chosen inside the step, not around the kernel's body.
@@ -233,6 +234,38 @@ __device__ __forceinline__ void accumulate_view(const IndexedFrame& f, const Any
 template <bool SECOND>
 __device__ __forceinline__ double view_cost(const IndexedFrame& f, const AnyCamera& cam, const PairBasis& B) {
     return with_camera(cam, [&](const auto& k) { return view_cost<SECOND>(f, k, B); });
+}
+
+// ---- the camera table of a rig of up to DCX_RIG_MAX_CAMERAS cameras, as the kernels of dcx_rig.hip and dcx_rigpose.hip take it by
+// value, and the one host-side check that fills it from the C ABI's DcxRigCamera array
+
+constexpr int kMaxCams = DCX_RIG_MAX_CAMERAS;
+
+struct RigCams {                         // every camera a pinhole: what dcx_rig_calibrate_pool has always passed
+    MaskedPool pl[kMaxCams];
+    PnpCamera cam[kMaxCams];
+};
+
+struct MixedCams {                       // a model tag per camera (dcx_rig_calibrate_models_pool with a fisheye camera in the rig)
+    MaskedPool pl[kMaxCams];
+    AnyCamera cam[kMaxCams];
+};
+static_assert(sizeof(MixedCams) <= 2048, "kernel arguments");
+
+// The pools and, per camera, what `camera` makes of its model fields -> false if anything is refused
+template <class CAMS, class F>
+bool camera_table(int n_cams, const DcxRigCamera* h_cams, int batch, int col_count, int row_count, double square_len, CAMS& cams,
+                  int* pools, F&& camera) {
+    if (n_cams < 2 || n_cams > kMaxCams || !h_cams) return false;
+    for (int c = 0; c < n_cams; ++c) {
+        const DcxRigCamera& h = h_cams[c];
+        cams.pl[c].mask = h.d_mask;
+        if (!corner_pool(h.d_counts, h.d_starts, h.d_rows, h.d_xy, batch, h.pool, col_count, row_count, square_len, cams.pl[c].p))
+            return false;
+        if (!camera(c, h, cams.cam[c])) return false;
+        pools[c] = h.pool;
+    }
+    return true;
 }
 
 }  // namespace

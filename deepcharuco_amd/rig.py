@@ -48,6 +48,8 @@ what it has always been, bit for bit.
 
 What it gives over C - 1 stereo solves: one consistent rig from one call, and cameras that never see the board together with
 camera 0.  Where every camera shares views with camera 0 it is not measurably more accurate than the pairwise solves.
+With the rig solved, ``rig_pose_host_full`` / ``rig_pose_pools`` / ``rig_pose_device`` (second half of this module) find the board's
+pose per timestamp from every camera's rows, the rig held fixed.
 """
 from __future__ import annotations
 
@@ -59,7 +61,9 @@ import numpy as np
 
 from . import _dev, _lm
 from .calib import _no_bad_id
-from .pnp import PNP_OK, _camera, _pool_ptrs, _rodrigues, _rvec_of
+from .corner_pool import _pool_rows
+from .pnp import (LM_EPS, LM_MAX_ITER, PNP_DEGENERATE, PNP_NONFINITE, PNP_OK, PNP_TOO_FEW, PNP_TRUNCATED, _bad_id_error, _camera,
+                  _cholesky_solve, _pool_ptrs, _rodrigues, _rvec_of, object_points)
 # every step that does not depend on the number of cameras is stereo.py's, kept once
 from .stereo import (MODELS, STEREO_EPS, STEREO_MAX_ITER, _call, _depth_margin, _device_masks, _model_args, _model_cameras, _models,
                      _outputs, _raise_like_cv2, _refine, _rig_init, _sine, _total, _unpack, _upload, _view_poses, _view_segments,
@@ -76,7 +80,9 @@ RESULT_HEAD = 8                # h_result of dcx_rig_calibrate_pool: 8 words, th
 REDUCE_CHUNK, REDUCE_SLICES = 16, 16   # csrc/dcx_rig.hip's kChunk, kSlices: the two fan-ins of the per-attempt reduction
 
 __all__ = ["RigResult", "rig_calibrate_host", "rig_calibrate_host_full", "rig_calibrate_pools", "rig_calibrate_device", "rig_pair",
-           "workspace_bytes", "RIG_OK", "RIG_NO_STAMPS", "RIG_DEGENERATE", "RIG_NONFINITE", "RIG_DISCONNECTED"]
+           "workspace_bytes", "RIG_OK", "RIG_NO_STAMPS", "RIG_DEGENERATE", "RIG_NONFINITE", "RIG_DISCONNECTED",
+           "RigPoseResult", "rig_pose_host", "rig_pose_host_full", "rig_pose_pools", "unpack_rig_poses", "rig_pose_device",
+           "rig_pose_workspace_bytes"]
 
 
 class RigResult(NamedTuple):
@@ -119,6 +125,14 @@ def _tree(usable: np.ndarray):
     return parents, order
 
 
+def _seed_pose(x, pose):
+    """X_c^-1 o pose, a view's own pose taken into camera 0's frame (step 3 of the calibration and of the rig pose solve) -> (P, the
+    sine term of its ``_rvec_of``)."""
+    Rc = _rodrigues(x[:3])
+    R = Rc.T @ _rodrigues(pose[:3])
+    return np.r_[_rvec_of(R), Rc.T @ (pose[3:] - x[3:])], _sine(R)
+
+
 def _initial_rig(usable, poses, parents, order):
     """Steps 2 (the edges and their composition) and 3 -> (status, X [C - 1, 6], P [N, 6], the smallest relative distance of a sine
     term of ``_rvec_of`` from its switch)."""
@@ -147,10 +161,8 @@ def _initial_rig(usable, poses, parents, order):
         if c == 0:
             P[i] = poses[t, 0]
         else:
-            Rc = _rodrigues(X[c, :3])
-            R = Rc.T @ _rodrigues(poses[t, c, :3])
-            margin = min(margin, abs(_sine(R) - 1e-5) / 1e-5)
-            P[i] = np.r_[_rvec_of(R), Rc.T @ (poses[t, c, 3:] - X[c, 3:])]
+            P[i], sine = _seed_pose(X[c], poses[t, c])
+            margin = min(margin, abs(sine - 1e-5) / 1e-5)
     return RIG_OK, X[1:], P, margin
 
 
@@ -354,3 +366,321 @@ def rig_calibrate_device(keypoints_lists: Sequence, col_count, row_count, square
         r = rig_calibrate_pools([p[0] for p in packs], B, [p[2] for p in packs], True, col_count, row_count, square_len, cameras,
                                 dists, None if masks is None else dm, models)
     return _no_bad_id(r, col_count, row_count)
+
+
+# ------------------------------------------------------------------------------------------------ rig pose: one board pose from every camera
+# With the rig held fixed (X_c known, from a ``RigResult`` or as R, T), the board's pose P_t in camera 0's frame from everything
+# the C cameras saw at instant t.  Every timestamp is solved on its own.  Steps, all in float64:
+#
+# 1. per view (t, c): ``stereo._view_poses``, unchanged: the status, the rows after the mask, the view's own pose.  ``view_status`` and
+#    ``view_points`` are what ``rig_calibrate_host_full`` reports for the same input;
+# 2. which rows CONTRIBUTE, judged on the rows and not on the status: the rows of a view do if the view is not TRUNCATED, has at
+#    least one kept row, every kept id is on the board and, for a fisheye camera, every kept pixel is inside the model (the test
+#    of ``fisheye._solve``).  So a TOO_FEW view with 1 to 3 good rows contributes, and so does a DEGENERATE view of collinear rows:
+#    every row is a constraint once another camera fixes the pose.  Otherwise none of the view's rows do;
+# 3. seeds: every PNP_OK view is one.  Seed c is P = X_c^-1 o pose_{c,t} by ``_initial_rig``'s step 3 (c = 0: the view's own pose,
+#    unchanged); its score is the JOINT COST there: the squared pixel residual over every contributing row of every camera
+#    (cameras ascending, rows in pool order), +inf if a row is not in front of its camera.  The start is the seed with the lowest
+#    score, the lowest camera among equals.  No seed -> PNP_TOO_FEW (no view solves on its own); every score +inf ->
+#    PNP_DEGENERATE.  There is NO minimal solver for an instant at which no camera alone has four usable rows;
+# 4. Levenberg-Marquardt over the 6 parameters of P_t on the joint cost with ``pnp._solve``'s rules, unchanged (damping
+#    1 + 10^lg from lg = -3, a step accepted on cost <= prev_cost, a row behind its camera makes a trial's cost +inf and so a
+#    rejection, lg + 1 on a rejection up to 16, at most 20 accepted steps, stop at |dp| / |p| < FLT_EPSILON, the same NONFINITE /
+#    DEGENERATE endings).  The Jacobians are ``stereo._evaluate``'s P columns: a row of camera c >= 1 sees P through R(X_c);
+# 5. outputs (``RigPoseResult``); everything continuous, and ``iterations``, is zero unless the timestamp's status is PNP_OK.
+#
+# ``rig_pose_host_full`` is the readable definition and the test pin; ``rig_pose_pools`` / ``rig_pose_device`` run the same steps on
+# the GPU (csrc/dcx_rigpose.hip), without a host synchronisation, so the call can be captured in a graph.  The two agree to
+# rounding (summation order), not bit for bit.
+
+class RigPoseResult(NamedTuple):
+    status: np.ndarray           # int32 [T], pnp.PNP_* per timestamp
+    rvec: np.ndarray             # [T, 3] the board's pose P_t in camera 0's frame; zeros unless the status is PNP_OK
+    tvec: np.ndarray             # [T, 3]
+    rms: np.ndarray              # [T] sqrt(cost / rows) at the solution (px)
+    iterations: np.ndarray       # int64 [T] accepted LM steps
+    rows: np.ndarray             # int64 [T] the contributing rows of the timestamp, whatever the status
+    seed: np.ndarray             # int32 [T] the camera whose pose started the solve, -1 if none did
+    view_status: np.ndarray      # int32 [T, C], pnp.PNP_* per view: the view solved on its own
+    view_points: np.ndarray      # int64 [T, C] rows the view brings (after its mask), contributing or not
+    view_rms: np.ndarray         # [T, C] rms of the view at the solution; zero where it did not contribute
+
+
+def _rig_x(rig):
+    """``rig``: a solved ``RigResult`` or ``(R [C, 3, 3], T [C, 3])`` with camera 0 the identity -> (X [C - 1, 6] of (rvec, T), the
+    sine term of every ``_rvec_of`` taken).  Both forms go through R, so they give the same bits."""
+    if isinstance(rig, RigResult):
+        if rig.status != RIG_OK:
+            raise ValueError(f"the rig was not solved (status {rig.status})")
+        R, T = rig.R, rig.T
+    else:
+        R, T = rig
+    R, T = np.asarray(R, np.float64), np.asarray(T, np.float64)
+    if R.ndim != 3 or R.shape[1:] != (3, 3) or not 2 <= R.shape[0] <= RIG_MAX_CAMERAS:
+        raise ValueError(f"R must be [C, 3, 3] with C = 2 .. {RIG_MAX_CAMERAS}")
+    T = T.reshape(R.shape[0], 3)
+    if not (np.isfinite(R).all() and np.isfinite(T).all()):
+        raise ValueError("the rig must be finite")
+    if not np.array_equal(R[0], np.eye(3)) or T[0].any():
+        raise ValueError("camera 0 must be the identity")
+    return np.array([np.r_[_rvec_of(R[c]), T[c]] for c in range(1, R.shape[0])]), [_sine(R[c]) for c in range(1, R.shape[0])]
+
+
+def _kept_rows(keypoints, mask, pool_order):
+    """A view's rows after its mask, in pool order: the rows ``stereo._view_poses`` judges."""
+    kp, order = _pool_rows(keypoints, pool_order)
+    keep = np.ones(kp.shape[0], bool) if mask is None else np.asarray(mask).astype(bool).ravel()
+    return kp[order][keep[order]]
+
+
+def _contributes(kp, cam, n_ids):
+    """Step 2 for the kept rows of a view that is not TRUNCATED."""
+    if kp.shape[0] < 1:
+        return False
+    ids = kp[:, 2].astype(np.int64)
+    if ids.min() < 0 or ids.max() >= n_ids:
+        return False
+    if len(cam) > 2 and cam[2] == "fisheye":
+        from . import fisheye
+        return bool(np.isfinite(fisheye._undistort(kp[:, :2].astype(np.float32).astype(np.float64), cam[0], cam[1])).all())
+    return True
+
+
+def _joint(rows, cams, X, p, jac):
+    """The joint cost at P = p -> (residuals (M, 2), cost, J (2M, 6)): ``stereo._evaluate``'s residuals and P columns over one
+    timestamp's contributing rows.  cost = +inf (and no residuals) if a row is not in front of its camera."""
+    ev = _evaluate(rows, cams, X, p[None], jac)
+    if ev is None:
+        return None, math.inf, None
+    return ev[0], float((ev[0] * ev[0]).sum()), ev[2].reshape(-1, 6) if jac else None
+
+
+def _refine_pose(project, p):
+    """Step 4: ``pnp._solve``'s loop from the start p on ``project(p, jac) -> (res, cost, J)`` -> (status, p, cost, accepted steps).
+    The start's cost is finite (the caller chose it so)."""
+    res, cost, J = project(p, True)
+    prev_cost, lg, iters = cost, -3, 0
+    while True:
+        JtJ, Jtr = J.T @ J, J.T @ res.ravel()
+        prev = p
+        while True:
+            A = JtJ.copy()
+            A[np.diag_indices(6)] *= 1.0 + 10.0 ** lg
+            x = _cholesky_solve(A, Jtr)
+            if x is None:
+                return PNP_DEGENERATE, p, cost, iters
+            p = prev - x
+            _, cost, _ = project(p, False)
+            if not cost <= prev_cost:
+                lg += 1
+                if lg <= 16:
+                    continue
+            break
+        lg = max(lg - 1, -16)
+        iters += 1
+        if iters >= LM_MAX_ITER or math.sqrt(float((p - prev) @ (p - prev))) < LM_EPS * math.sqrt(float(prev @ prev)):
+            break
+        prev_cost = cost
+        res, cost, J = project(p, True)
+    if not np.isfinite(p).all() or math.isnan(cost):
+        return PNP_NONFINITE, p, cost, iters
+    if not math.isfinite(cost):
+        return PNP_DEGENERATE, p, cost, iters
+    return PNP_OK, p, cost, iters
+
+
+def rig_pose_host_full(keypoints_lists, col_count, row_count, square_len, cameras, dists, rig, masks=None, pool_order=False,
+                       with_margin=False, models=None):
+    """The definition (the comment above) -> ``RigPoseResult`` (with ``with_margin``: ``(result, margin)``).
+
+    ``keypoints_lists``, ``cameras``, ``dists``, ``masks``, ``pool_order`` and ``models`` as ``rig_calibrate_host_full`` takes them;
+    ``rig``: a ``RigResult`` (ValueError unless it is RIG_OK) or ``(R [C, 3, 3], T [C, 3])`` with camera 0 the identity.  Nothing
+    raises for a timestamp that cannot be solved.
+
+    ``with_margin``: the smallest relative distance of a discrete decision from its threshold: the gap between the best and the
+    second-best seed score relative to the best (infinite with one seed), the sine term of every ``_rvec_of`` of step 3 and of the
+    rig's own rotations from its switch at 1e-5, and the depth of every contributing row at the solution from 0 (relative to its
+    distance from the camera centre)."""
+    cams, _ = _cameras(cameras, dists, models)
+    C = len(cams)
+    X, sines = _rig_x(rig)
+    if X.shape[0] != C - 1:
+        raise ValueError(f"a rig of {X.shape[0] + 1} cameras for {C} cameras")
+    if len(keypoints_lists) != C:
+        raise ValueError(f"{len(keypoints_lists)} keypoint lists for {C} cameras")
+    B = len(keypoints_lists[0])
+    for c in range(C):
+        if len(keypoints_lists[c]) != B:
+            raise ValueError(f"{B} views of camera 0 but {len(keypoints_lists[c])} of camera {c}")
+    mk = _mask_lists(masks, C)
+    view_status, view_points, poses, _, _ = _view_poses(keypoints_lists, mk, cams, (col_count, row_count, square_len), pool_order)
+    n_ids = (col_count - 1) * (row_count - 1)
+    margin = min([math.inf] + [abs(s - 1e-5) / 1e-5 for s in sines])
+    status = np.full(B, PNP_TOO_FEW, np.int32)
+    rv, tv, rms, vr = np.zeros((B, 3)), np.zeros((B, 3)), np.zeros(B), np.zeros((B, C))
+    iters, nrows, seed = np.zeros(B, np.int64), np.zeros(B, np.int64), np.full(B, -1, np.int32)
+    for t in range(B):
+        views = []
+        for c in range(C):
+            kp = _kept_rows(keypoints_lists[c][t], None if mk[c] is None else mk[c][t], pool_order)
+            if view_status[t, c] != PNP_TRUNCATED and _contributes(kp, cams[c], n_ids):
+                views.append((c, object_points(kp[:, 2].astype(np.int64), col_count, row_count, square_len), kp[:, :2].astype(np.float32)))
+        nrows[t] = sum(v[1].shape[0] for v in views)
+        seeds = [c for c in range(C) if view_status[t, c] == PNP_OK]
+        if not seeds:
+            continue                                             # PNP_TOO_FEW: no view solves on its own
+        rows = _rows_of([views], C)                              # (a seed's view contributes: there are rows)
+        best, second, start = math.inf, math.inf, None
+        for c in seeds:
+            p0, sine = (poses[t, 0].copy(), None) if c == 0 else _seed_pose(X[c - 1], poses[t, c])
+            if sine is not None:
+                margin = min(margin, abs(sine - 1e-5) / 1e-5)
+            score = _joint(rows, cams, X, p0, False)[1]
+            if score < best:
+                best, second, start, seed[t] = score, best, p0, c
+            elif score < second:
+                second = score
+        if start is None:
+            status[t] = PNP_DEGENERATE
+            continue
+        if second < math.inf:
+            margin = min(margin, (second - best) / best if best > 0 else math.inf)
+        st, p, cost, it = _refine_pose(lambda q, jac: _joint(rows, cams, X, q, jac), start)
+        status[t] = st
+        if st != PNP_OK:
+            continue
+        rv[t], tv[t], rms[t], iters[t] = p[:3], p[3:], math.sqrt(cost / nrows[t]), it
+        res = _joint(rows, cams, X, p, False)[0]
+        for (c, o, _), a in zip(views, rows.vstarts):
+            r = res[a:a + o.shape[0]]
+            vr[t, c] = math.sqrt(float((r * r).sum()) / o.shape[0])
+        if with_margin:
+            margin = min(margin, _depth_margin(rows, X, p[None]))
+    r = RigPoseResult(status, rv, tv, rms, iters, nrows, seed, view_status.astype(np.int32), view_points.astype(np.int64), vr)
+    return (r, margin) if with_margin else r
+
+
+def rig_pose_host(keypoints_lists, col_count, row_count, square_len, cameras, dists, rig, masks=None, models=None):
+    """``(ok bool [T], rvecs [T, 3], tvecs [T, 3])``: the board's pose in camera 0's frame per timestamp (zeros where ``ok`` is
+    False).  Raises where ``rig_calibrate_host`` raises: IndexError for an id outside the board, ValueError for a view that has
+    rows none of which can be used (a fisheye view with a pixel outside the model) and for refused arguments.  A view of 1 to 3 rows
+    or of collinear rows is used here and no error; a timestamp that cannot be solved is ``ok`` = False, not an error."""
+    r = rig_pose_host_full(keypoints_lists, col_count, row_count, square_len, cameras, dists, rig, masks, models=models)
+    cams, _ = _cameras(cameras, dists, models)
+    mk = _mask_lists(masks, len(cams))
+    n_ids = (col_count - 1) * (row_count - 1)
+    for t, c in np.argwhere(r.view_points > 0):
+        kp = _kept_rows(keypoints_lists[c][t], None if mk[c] is None else mk[c][t], False)
+        ids = kp[:, 2].astype(np.int64)
+        if ids.min() < 0 or ids.max() >= n_ids:
+            raise _bad_id_error(col_count, row_count)
+        if not _contributes(kp, cams[c], n_ids):
+            raise ValueError(f"view {int(t)} of camera {int(c)} cannot be used (status {int(r.view_status[t, c])})")
+    return r.status == PNP_OK, r.rvec, r.tvec
+
+
+# ------------------------------------------------------------------------------------------------ rig pose on the device
+
+POSE_HEAD_WORDS = 2            # d_head of dcx_rig_pose_pool: {a masked pool's views share slots, reserved (0)}
+
+
+def rig_pose_workspace_bytes(n_cams: int, batch: int, pools) -> int:
+    """Bytes of device workspace ``rig_pose_pools`` needs."""
+    from . import _lib
+    pools = [int(p) for p in pools]
+    if len(pools) != int(n_cams):
+        raise ValueError("one pool size per camera is required")
+    n = int(_lib.lib().dcx_rig_pose_workspace_bytes(int(n_cams), int(batch), (_ctypes.c_int * len(pools))(*pools)))
+    if n == 0:
+        raise ValueError(f"2 to {RIG_MAX_CAMERAS} cameras, batch >= 1 and pools >= 0 are required")
+    return n
+
+
+def _pose_outputs(out, batch, n_cams, dev):
+    """-> (head int32 [2], status int32 [B], pose float64 [B, 8], info int32 [B, 2], view_status int32 [B, C], view_info float64
+    [B, C, 2]): the caller's ``out`` checked, or new tensors."""
+    import torch
+    specs = ((torch.int32, (POSE_HEAD_WORDS,)), (torch.int32, (batch,)), (torch.float64, (batch, 8)), (torch.int32, (batch, 2)),
+             (torch.int32, (batch, n_cams)), (torch.float64, (batch, n_cams, 2)))
+    if out is not None and len(out) != len(specs):
+        raise ValueError("out must be the six tensors rig_pose_pools returns")
+    msg = (f"out must be (int32 [2], int32 [{batch}], float64 [{batch}, 8], int32 [{batch}, 2], int32 [{batch}, {n_cams}], float64 "
+           f"[{batch}, {n_cams}, 2]) contiguous tensors on {dev}")
+    return tuple(_dev.tensor(None if out is None else out[i], dev, dt, shape, msg, "numel") for i, (dt, shape) in enumerate(specs))
+
+
+def rig_pose_pools(packed_list, batch: int, pools, refined: bool, col_count, row_count, square_len, cameras, dists, rig, masks=None,
+                   models=None, workspace=None, out=None):
+    """The board's pose per timestamp from C ``infer_batch_device`` results of ``batch`` frames each and a fixed rig, read in place
+    from the C corner pools (the conventions of ``rig_calibrate_pools``: ``pools``, ``masks``, ``models``).  ``rig``: a
+    ``RigResult`` (ValueError unless RIG_OK) or ``(R, T)``.  Enqueued on the current stream: no host synchronisation, and nothing
+    allocated when ``workspace`` (at least ``rig_pose_workspace_bytes`` bytes) and ``out`` are given, so the call can be captured
+    in a graph.  Returns the device tensors ``(head, status, pose, info, view_status, view_info)`` (``out`` = those six,
+    preallocated); ``unpack_rig_poses`` makes a ``RigPoseResult`` of them and raises DcxError if a masked pool's views share
+    slots, which only the device can see."""
+    import torch
+    from . import _lib
+    cams, dists = _cameras(cameras, dists, models)
+    C = len(cams)
+    models = _models(models, C)
+    X, _ = _rig_x(rig)
+    pools = [int(p) for p in pools]
+    if X.shape[0] != C - 1 or len(packed_list) != C or len(pools) != C:
+        raise ValueError(f"{C} cameras need a rig of {C} cameras, {C} pools and {C} pool sizes")
+    dev = packed_list[0].device
+    if any(p.device != dev for p in packed_list):
+        raise ValueError("the pools must be on one device")
+    mk = _mask_lists(masks, C)
+    _device_masks(mk, pools, dev)
+    table = (_RigCamera * C)()
+    for c in range(C):
+        counts_p, starts_p, rows_p, xy_p = _pool_ptrs(packed_list[c], batch, pools[c], refined)
+        cam9, d8, nd = _model_args(cameras[c], dists[c], models and models[c])
+        table[c] = _RigCamera(counts_p, starts_p, rows_p, xy_p, pools[c], _lib.ptr(mk[c]), cam9, d8, nd)
+    outs = _pose_outputs(out, batch, C, dev)
+    nbytes = rig_pose_workspace_bytes(C, batch, pools)
+    ws = _dev.workspace(workspace, dev, nbytes, f"workspace must be a contiguous tensor of at least {nbytes} bytes on {dev}")
+    tags = None if models is None else (_ctypes.c_int * C)(*(MODELS.index(m) for m in models))
+    x = (_ctypes.c_double * (6 * (C - 1)))(*X.ravel().tolist())
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().dcx_rig_pose_pool(C, table, tags, x, int(batch), int(col_count), int(row_count), float(square_len),
+                                                ws.data_ptr(), ws.numel() * ws.element_size(), *(o.data_ptr() for o in outs),
+                                                _lib.current_stream()), "dcx_rig_pose_pool")
+    return outs
+
+
+def unpack_rig_poses(head, status, pose, info, view_status, view_info) -> RigPoseResult:
+    """``rig_pose_pools``' device tensors -> a ``RigPoseResult`` on the host (this synchronises).  DcxError (DCX_E_ARG) if the
+    call found a masked pool whose views share slots, as ``rig_calibrate_pools`` raises for the same breach."""
+    from . import _lib
+    head, status, pose, info, view_status, view_info = (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
+                                                        for v in (head, status, pose, info, view_status, view_info))
+    if int(head.ravel()[0]):
+        raise _lib.DcxError(-1, "dcx_rig_pose_pool (two views of a masked pool share slots)")
+    B = status.size
+    pose, info, view_info = pose.reshape(B, 8), info.reshape(B, 2), view_info.reshape(B, -1, 2)
+    return RigPoseResult(status.reshape(B).astype(np.int32), pose[:, 0:3].copy(), pose[:, 3:6].copy(), pose[:, 6].copy(),
+                         pose[:, 7].astype(np.int64), info[:, 1].astype(np.int64), info[:, 0].astype(np.int32),
+                         view_status.reshape(B, -1).astype(np.int32), view_info[:, :, 1].astype(np.int64), view_info[:, :, 0].copy())
+
+
+def rig_pose_device(keypoints_lists: Sequence, col_count, row_count, square_len, cameras, dists, rig, masks=None, device="cuda",
+                    models=None) -> RigPoseResult:
+    """``rig_pose_host_full`` on the GPU from ``infer_image``-format keypoint arrays ([x, y, id] rows; one list per camera, equally
+    long) -> ``RigPoseResult``.  ``rig``, ``masks`` and ``models`` as for the host definition."""
+    import torch
+    from .models._handles import require_cuda
+    dev = require_cuda(device)
+    cams, dists = _cameras(cameras, dists, models)            # ValueError before anything is uploaded
+    C = len(cams)
+    _rig_x(rig)
+    if len(keypoints_lists) != C:
+        raise ValueError(f"{len(keypoints_lists)} keypoint lists for {C} cameras")
+    B = len(keypoints_lists[0])
+    if any(len(k) != B for k in keypoints_lists):
+        raise ValueError("every camera needs as many views as camera 0")
+    packs, dm = _upload(keypoints_lists, _mask_lists(masks, C), dev)
+    with torch.cuda.device(dev):
+        outs = rig_pose_pools([p[0] for p in packs], B, [p[2] for p in packs], True, col_count, row_count, square_len, cameras, dists,
+                              rig, None if masks is None else dm, models)
+        return unpack_rig_poses(*outs)
