@@ -115,6 +115,7 @@ SIGNATURES = {
     "dcx_fisheye_rectify_points_pool": (_i, [_vp, _vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                             C.POINTER(C.c_double), _vp, _vp]),
     "dcx_resize_u8": (_i, [_vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "dcx_resize_area_u8": (_i, [_vp, _l, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "dcx_sgm_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "dcx_sgm_u8": (_i, [_vp, _l, _i, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "dcx_sgm_u8_paths": (_i, [_vp, _l, _i, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),

@@ -1,7 +1,8 @@
 // dcx_resize.hip -- cv2.resize of a batch of u8 gray or interleaved BGR frames: INTER_NEAREST, INTER_LINEAR (cv2's 11-bit fixed
-// point scheme, with its rule that an exact 2 x 2 reduction is INTER_AREA's) and INTER_AREA by integer factors.  The step in front
-// of the detector: camera frames -> the 320 x 240 the networks are trained on.  deepcharuco_amd/resize.py:resize_host states every
-// formula and is the pin of this file, bit for bit; the formulas are cv2's as published and are not pinned against cv2.
+// point scheme, with its rule that an exact 2 x 2 reduction is INTER_AREA's), INTER_AREA by integer factors and, through an entry
+// of its own, INTER_AREA for shrinking by any factor.  The step in front of the detector: camera frames -> the 320 x 240 the
+// networks are trained on.  deepcharuco_amd/resize.py:resize_host states every formula and is the pin of this file, bit for bit;
+// the formulas are cv2's as published and are not pinned against cv2.
 //
 // Shape.  The work is memory bound: a 6 x 6 reduction reads 36 source bytes per byte it writes.  One workgroup makes `tw`
 // consecutive pixels of ONE output row of one frame (grid: tiles of a row, output rows, frames).  The source bytes these pixels
@@ -25,6 +26,14 @@
 // definition: every fp64 / fp32 step through an _rn intrinsic, so nothing contracts into a fused multiply-add.  The scales
 // 1.0 / (dn / sn) are computed by the host entry in double and are kernel arguments.
 //
+// "area_any" (dcx_resize_area_u8: cv2's general INTER_AREA, a box filter with fractional end taps) routes integer factors on both
+// axes to the "area" kernels above and takes everything else through dcx_resize_u8_kernel<CH, kAreaAny>: the rows of the output
+// row's y-taps (at most 66) and the span from the first x-tap of the tile's first pixel to the last x-tap of its last one are
+// staged as bytes; a thread evaluates the tap table of its own pixel in x and of the output row in y (area_taps: a first tap, a
+// run of whole pixels of one weight, a last tap) and then, per staged row, the float32 sum over its x-taps in order, weighted
+// and added in row order, every product and sum rounded on its own (compiled with contraction off).  The u16 column sums of
+// dcx_resize_area_kernel do not carry over: the definition rounds every row's horizontal sum before it is weighted.
+//
 // No workspace, no atomics, no allocation, no synchronisation: one launch on the stream, capturable in a hipGraph.
 #include "dcx_common.h"
 
@@ -38,7 +47,9 @@ constexpr int kLdsBytes = 40960;             // staged spans of one workgroup: f
 constexpr int kInFlight = 4;                 // 16-byte chunks a thread loads before it stores them
 constexpr int kCoefBits = 11;                // INTER_RESIZE_COEF_BITS: the coefficients are rint(w * 2048)
 
-enum { kNearest = 0, kLinear = 1, kArea = 2 };
+enum { kNearest = 0, kLinear = 1, kArea = 2 };  // dcx_resize_u8's codes
+constexpr int kAreaAny = 3;                  // the general path of dcx_resize_area_u8: a kernel mode, no code of dcx_resize_u8
+constexpr double kAreaEps = 1e-3;            // "area_any": an end tap that covers no more of its pixel is dropped
 
 struct ResizeArgs {
     const uint8_t* src;
@@ -48,6 +59,7 @@ struct ResizeArgs {
     int tw;                                  // output pixels of one workgroup
     int lrow;                                // chunks of one staged row * 16: at least 16 more than the longest span
     int fx, fy;                              // "area"
+    int rows;                                // "area_any": the staged rows of one workgroup (the y-taps of an output row are fewer)
     float inv_area;                          // "area": float32(1.0 / (fx fy))
     double scale_x, scale_y;                 // 1.0 / (dn / sn)
 };
@@ -77,6 +89,35 @@ __device__ __forceinline__ void linear_taps(int d, double scale, int sn, int& s0
     c1 = (int)rintf(__fmul_rn(f, one));
 }
 
+// "area_any" along one axis (resize_host's roundings, step by step): the taps of output index d are the n source pixels s0,
+// s0 + 1, ...: the fractional first one if there is one, the whole ones, the fractional last one if there is one.  Held as the
+// loops take them (no weight is looked up by position): tap 0 has weight w0, taps 1 .. body - 1 are whole pixels of weight w_mid,
+// and where n > max(body, 1) tap n - 1 is the last one, of weight w_last.
+struct AreaTaps {
+    int s0, n, body;
+    float w0, w_mid, w_last;
+    __device__ __forceinline__ bool has_last() const { return n > max(body, 1); }
+};
+
+__device__ __forceinline__ AreaTaps area_taps(int d, double scale, int sn) {
+    // Plain operators with contraction off: the _rn intrinsics are plain operators compiled with contraction allowed, and once
+    // they are inlined a product and the sum behind it do fuse (f1 + scale became fma(d, scale, scale)).
+#pragma clang fp contract(off)
+    const double f1 = (double)d * scale, f2 = f1 + scale;
+    const double cell = fmin(scale, (double)sn - f1);
+    const int s2 = min((int)floor(f2), sn - 1), s1 = min((int)ceil(f1), s2);
+    const double head = (double)s1 - f1, tail = f2 - (double)s2;
+    const int first = head > kAreaEps, last = tail > kAreaEps;
+    AreaTaps t;
+    t.s0 = s1 - first;
+    t.body = first + (s2 - s1);
+    t.n = t.body + last;
+    t.w_mid = (float)(1.0 / cell);
+    t.w_last = (float)(fmin(fmin(tail, 1.0), cell) / cell);
+    t.w0 = first ? (float)(head / cell) : (t.body ? t.w_mid : t.w_last);
+    return t;
+}
+
 // Bytes [lo, lo + 16) of the span that begins at g (g + lo is a multiple of 16), of which only [0, span) exist (a chunk that an end
 // of the span cuts): the existing ones byte by byte (sixteen independent predicated loads, no loop), zeros for the others.
 __device__ __forceinline__ uint4 load_cut_chunk(const uint8_t* g, int lo, int span) {
@@ -104,7 +145,15 @@ __global__ __launch_bounds__(kThreads) void dcx_resize_u8_kernel(ResizeArgs a) {
 
     // the source rows this output row needs, and the pixels [xlo, xhi] of them that its npx pixels need
     int nr, y0 = 0, y1 = 0, b0 = 0, b1 = 0, xlo, xhi;
-    if (MODE == kArea) {
+    AreaTaps ty{};
+    if (MODE == kAreaAny) {
+        ty = area_taps(oy, a.scale_y, a.src_h);                                 // (the same for every thread)
+        nr = min(ty.n, a.rows);
+        y0 = ty.s0;
+        xlo = area_taps(px0, a.scale_x, a.src_w).s0;                            // the taps never decrease along the row
+        const AreaTaps t = area_taps(px0 + npx - 1, a.scale_x, a.src_w);
+        xhi = t.s0 + t.n - 1;
+    } else if (MODE == kArea) {
         nr = a.fy;
         y0 = oy * a.fy;
         xlo = px0 * a.fx;
@@ -124,7 +173,7 @@ __global__ __launch_bounds__(kThreads) void dcx_resize_u8_kernel(ResizeArgs a) {
     const int span = min((xhi - xlo + 1) * CH, a.lrow - 16);                    // (the host sized lrow for the longest span)
     const int nchunk = a.lrow >> 4;
     auto row_start = [&](int r) -> const uint8_t* {
-        const int y = MODE == kArea ? y0 + r : (r ? y1 : y0);
+        const int y = MODE == kArea || MODE == kAreaAny ? y0 + r : (r ? y1 : y0);
         return frame + (size_t)y * a.pitch + (size_t)xlo * CH;
     };
 
@@ -157,7 +206,23 @@ __global__ __launch_bounds__(kThreads) void dcx_resize_u8_kernel(ResizeArgs a) {
     for (int e = tid; e < npx * CH; e += kThreads) {
         const int p = e / CH, c = e - p * CH;
         unsigned o;
-        if (MODE == kArea) {
+        if (MODE == kAreaAny) {
+#pragma clang fp contract(off)                                                   // (as in area_taps: every product and sum on its own)
+            const AreaTaps tx = area_taps(px0 + p, a.scale_x, a.src_w);
+            const int i0 = (tx.s0 - xlo) * CH + c;
+            auto hsum = [&](int r) -> float {                                   // staged row r over the x-taps in order
+#pragma clang fp contract(off)
+                const uint8_t* row = lds + r * a.lrow + (int)((uintptr_t)row_start(r) & 15) + i0;
+                float h = (float)row[0] * tx.w0;
+                for (int k = 1; k < tx.body; ++k) h = h + (float)row[k * CH] * tx.w_mid;
+                if (tx.has_last()) h = h + (float)row[(tx.n - 1) * CH] * tx.w_last;
+                return h;
+            };
+            float v = ty.w0 * hsum(0);                                          // horizontal first, then vertical: the host's order
+            for (int r = 1; r < ty.body; ++r) v = v + ty.w_mid * hsum(r);
+            if (ty.has_last()) v = v + ty.w_last * hsum(ty.n - 1);
+            o = (unsigned)(int)fminf(fmaxf(rintf(v), 0.f), 255.f);
+        } else if (MODE == kArea) {
             unsigned sum = 0;
             for (int r = 0; r < a.fy; ++r) {
                 const uint8_t* row = lds + r * a.lrow + (int)((uintptr_t)row_start(r) & 15) + p * a.fx * CH + c;
@@ -238,18 +303,21 @@ __global__ __launch_bounds__(kThreads) void dcx_resize_area_kernel(ResizeArgs a)
 // LDS bytes of one staged row that holds up to `pixels` pixels at any alignment
 inline int lds_row(long long pixels, int ch) { return (int)((pixels * ch + 15 + 15) & ~15LL) + 16; }
 
-}  // namespace
-
-extern "C" int dcx_resize_u8(const uint8_t* d_src, long frame_stride, int pitch, int src_h, int src_w, int channels, int out_h,
-                             int out_w, int batch, int interpolation, uint8_t* d_out, void* stream) {
+// both entries: `mode` is a code of dcx_resize_u8 or kAreaAny
+int resize_u8(const uint8_t* d_src, long frame_stride, int pitch, int src_h, int src_w, int channels, int out_h, int out_w, int batch,
+              int mode, uint8_t* d_out, void* stream) {
     if (!d_src || !d_out || frame_stride < 0) return DCX_E_ARG;
     if (channels != 1 && channels != 3) return DCX_E_ARG;
-    if (interpolation != kNearest && interpolation != kLinear && interpolation != kArea) return DCX_E_ARG;
+    if (mode != kNearest && mode != kLinear && mode != kArea && mode != kAreaAny) return DCX_E_ARG;
     for (int v : {src_h, src_w, out_h, out_w, batch})
         if (v < 1 || v > kMaxSide) return DCX_E_SHAPE;
     if ((long long)pitch < (long long)src_w * channels || (long long)pitch * src_h > 0x7fffffffLL) return DCX_E_SHAPE;
-    int mode = interpolation;
     if (mode == kLinear && src_w == 2 * out_w && src_h == 2 * out_h) mode = kArea;           // cv2's rule
+    if (mode == kAreaAny) {
+        if (out_h > src_h || out_w > src_w) return DCX_E_SHAPE;                               // area does not enlarge
+        if (src_h > kMaxFactor * out_h || src_w > kMaxFactor * out_w) return DCX_E_SHAPE;
+        if (src_w % out_w == 0 && src_h % out_h == 0) mode = kArea;                           // cv2's fast-path rule
+    }
     ResizeArgs a{};
     a.src = d_src; a.out = d_out; a.frame_stride = frame_stride;
     a.pitch = pitch; a.src_h = src_h; a.src_w = src_w; a.out_h = out_h; a.out_w = out_w;
@@ -264,14 +332,20 @@ extern "C" int dcx_resize_u8(const uint8_t* d_src, long frame_stride, int pitch,
         a.inv_area = (float)(1.0 / (double)(a.fx * a.fy));
         sums = pitch % 16 == 0;
         rows = sums ? 2 : a.fy;                                                               // (u16 sums: two bytes per column)
+    } else if (mode == kAreaAny) {
+        // the rows s1 - 1 .. s2 of a cell: s2 - s1 <= f2 - f1, and ceil() covers a scale within an ulp of the integer above it
+        rows = (int)ceil(a.scale_y) + 2;
+        if (rows > src_h) rows = src_h;
+        a.rows = rows;
     } else {
         rows = mode == kLinear ? 2 : 1;
     }
     // the widest tile whose staged rows fit: (tw - 1) * scale + 4 bounds the pixels between the first tap of a tile's first pixel
-    // and the last tap of its last one ("linear": floor(f_last) + 1 - floor(f_first) + 1, and one more for f's float rounding)
+    // and the last tap of its last one ("linear": floor(f_last) + 1 - floor(f_first) + 1, and one more for f's float rounding;
+    // "area_any": floor(f2_last) - floor(f1_first) + 1 with f2_last - f1_first = tw * scale, and one more for their roundings)
     auto span_px = [&](int tw) -> long long {
         if (mode == kArea) return (long long)tw * a.fx;
-        const long long n = (long long)ceil((double)(tw - 1) * a.scale_x) + 4;
+        const long long n = (long long)ceil((double)(mode == kAreaAny ? tw : tw - 1) * a.scale_x) + (mode == kAreaAny ? 3 : 4);
         return n < src_w ? n : src_w;
     };
     int tw = out_w < kMaxElems / channels ? out_w : kMaxElems / channels;
@@ -286,14 +360,29 @@ extern "C" int dcx_resize_u8(const uint8_t* d_src, long frame_stride, int pitch,
     if (channels == 1) {
         if (sums) DCX_RESIZE((dcx_resize_area_kernel<1>));
         else if (mode == kArea) DCX_RESIZE((dcx_resize_u8_kernel<1, kArea>));
+        else if (mode == kAreaAny) DCX_RESIZE((dcx_resize_u8_kernel<1, kAreaAny>));
         else if (mode == kLinear) DCX_RESIZE((dcx_resize_u8_kernel<1, kLinear>));
         else DCX_RESIZE((dcx_resize_u8_kernel<1, kNearest>));
     } else {
         if (sums) DCX_RESIZE((dcx_resize_area_kernel<3>));
         else if (mode == kArea) DCX_RESIZE((dcx_resize_u8_kernel<3, kArea>));
+        else if (mode == kAreaAny) DCX_RESIZE((dcx_resize_u8_kernel<3, kAreaAny>));
         else if (mode == kLinear) DCX_RESIZE((dcx_resize_u8_kernel<3, kLinear>));
         else DCX_RESIZE((dcx_resize_u8_kernel<3, kNearest>));
     }
 #undef DCX_RESIZE
     return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int dcx_resize_u8(const uint8_t* d_src, long frame_stride, int pitch, int src_h, int src_w, int channels, int out_h,
+                             int out_w, int batch, int interpolation, uint8_t* d_out, void* stream) {
+    if (interpolation == kAreaAny) return DCX_E_ARG;                                          // (the other entry's mode)
+    return resize_u8(d_src, frame_stride, pitch, src_h, src_w, channels, out_h, out_w, batch, interpolation, d_out, stream);
+}
+
+extern "C" int dcx_resize_area_u8(const uint8_t* d_src, long frame_stride, int pitch, int src_h, int src_w, int channels, int out_h,
+                                  int out_w, int batch, uint8_t* d_out, void* stream) {
+    return resize_u8(d_src, frame_stride, pitch, src_h, src_w, channels, out_h, out_w, batch, kAreaAny, d_out, stream);
 }

@@ -634,6 +634,30 @@ int dcx_resize_u8(const uint8_t* d_src, long frame_stride, int pitch, int src_h,
                   int out_h, int out_w, int batch, int interpolation /* 0 nearest, 1 linear, 2 area */, uint8_t* d_out,
                   void* stream);
 
+/* dcx_resize_area_u8: cv2's general INTER_AREA for shrinking ("area_any": a box filter with fractional end taps), frames and
+ * output laid out as for dcx_resize_u8.  Bit-exact against deepcharuco_amd/resize.py:resize_host(..., "area_any"); cv2's formula
+ * as published (imgproc resize.cpp: computeResizeAreaTab and the general area invoker), NOT pinned against cv2.
+ *
+ * 1. Routing (cv2's fast-path rule): sw = fx dw AND sh = fy dh with integer factors gives dcx_resize_u8's "area", bit for bit,
+ *    through the same kernels (identity and 2 x 2 included).  Otherwise BOTH axes take the general path, also one whose own factor
+ *    is an integer.
+ * 2. The tap table of an axis, all in double, each operation rounded once, no fused multiply-add, scale = 1.0 / (dn / sn).  For
+ *    output index d: f1 = d * scale, f2 = f1 + scale, cell = min(scale, sn - f1); s1 = ceil(f1), s2 = min(floor(f2), sn - 1),
+ *    s1 = min(s1, s2).  Taps in this order: if s1 - f1 > 1e-3: (s1 - 1, float((s1 - f1) / cell)); for s in s1 .. s2 - 1:
+ *    (s, float(1.0 / cell)); if f2 - s2 > 1e-3: (s2, float(min(min(f2 - s2, 1.0), cell) / cell)).
+ * 3. A pixel, channels independent, float32 throughout, every product and every sum rounded on its own.  For each y-tap (sy, b)
+ *    in order: h = the sum over the x-taps (sx, a) in order of float(S[sy][sx]) * a, starting from the first product; v = b * h
+ *    for the first y-tap, v = v + b * h for the others; out = clip(rint(v), 0, 255), ties to even.  Horizontal first, then
+ *    vertical: cv2's order, and part of the definition.
+ *
+ * DCX_E_ARG: a null pointer, channels not 1 or 3, a negative frame_stride.  DCX_E_SHAPE: src_h, src_w, out_h, out_w or batch
+ * outside 1 .. 32768, pitch < src_w * channels, pitch * src_h beyond an int32, out_h > src_h or out_w > src_w (area does not
+ * enlarge), src_h > 64 out_h or src_w > 64 out_w.  Every refusal comes before anything is launched.  One launch on `stream`: no
+ * workspace, no allocation, no synchronisation, no atomics, so two calls give the same bits and a call can be captured in a
+ * hipGraph.                                                                                                                    */
+int dcx_resize_area_u8(const uint8_t* d_src, long frame_stride, int pitch, int src_h, int src_w, int channels /* 1 or 3 */,
+                       int out_h, int out_w, int batch, uint8_t* d_out, void* stream);
+
 /* ---- dense stereo matching on a rectified pair, and the disparity map as 3-D points ------------------------------------------
  * What follows dcx_remap_u8: semi-global matching (what cv2.StereoSGBM is called for) over 9 x 7 census costs, integer throughout
  * and bit-exact against deepcharuco_amd/disparity.py:sgm_host, which states every step.  d_left is rectified camera 0 and d_right

@@ -13,6 +13,11 @@ Timing: device events around `inner` back-to-back calls, rounds repeated until t
 0.5 s) after three warm-up calls of each; the figure is the median round's time per call.  Each shape is also checked against
 resize_host on its first two frames.  Prints one JSON object and writes it to --out.
 
+The 1080p case ("window_1080p"): 32 x 1080 x 1920 BGR frames whose 1440 x 1080 window is read in place (rows of 1,440 * 3 bytes at
+a 5,760-byte pitch) -> 240 x 320 with "area_any" (a factor of 4.5, dcx_resize_area_u8), alternating with a device copy of the
+bytes that call must read plus write (every row of the window), with "linear" on the same window (what such a user had before)
+and with "area" 4 x from dense 960 x 1280 frames; two frames of each are compared with resize_host.
+
     python tools/resize_probe.py --out profiles/resize_probe.json
 """
 import argparse
@@ -40,6 +45,38 @@ def rows_read(mode, sh, dh):
         return len(set(rz._nearest_axis(dh, sh).tolist()))
     y0, y1, _, _ = rz._linear_axis(dh, sh, False)
     return len(set(y0.tolist()) | set(y1.tolist()))
+
+
+def window_1080p(torch, rz, weights, dev, batch, dh, dw, seconds):
+    """The 1080p case of the module docstring -> its figures."""
+    def frames_of(sh, sw):
+        base = torch.from_numpy(weights.synthetic_frames("board", 21, 4, sh, sw)).to(dev)
+        gray = base.repeat(-(-batch // 4), 1, 1)[:batch] + torch.arange(batch, device=dev, dtype=torch.uint8)[:, None, None]
+        return torch.stack([gray, 255 - gray, gray // 2], 3).contiguous()
+
+    full = frames_of(1080, 1920)
+    window = full[:, :, 240:1680]                                              # 1440 x 1080, read in place
+    dense = frames_of(960, 1280)
+    assert not window.is_contiguous() and window.stride(1) == 5760
+    out = {k: torch.empty((batch, dh, dw, 3), dtype=torch.uint8, device=dev) for k in ("area_any", "linear", "area_4x")}
+    need = batch * (1080 * 1440 * 3 + dh * dw * 3)
+    cs, cd = torch.zeros(need // 2, dtype=torch.uint8, device=dev), torch.empty(need // 2, dtype=torch.uint8, device=dev)
+    fns = {"area_any": lambda: rz.resize_device(window, (dh, dw), "area_any", out=out["area_any"]),
+           "copy": lambda: cd.copy_(cs),
+           "linear": lambda: rz.resize_device(window, (dh, dw), "linear", out=out["linear"]),
+           "area_4x": lambda: rz.resize_device(dense, (dh, dw), "area", out=out["area_4x"])}
+    ms, inner, rounds = alternate(fns, seconds)
+    host_ok = {}
+    for k, src, mode in (("area_any", window, "area_any"), ("linear", window, "linear"), ("area_4x", dense, "area")):
+        fns[k]()
+        host_ok[k] = bool(np.array_equal(out[k][:2].cpu().numpy(), rz.resize_host(src[:2].cpu().numpy(), (dh, dw), mode)))
+    res = {"case": f"{batch}x1080x1920x3[:, :, 240:1680]->{dh}x{dw}", "area_any_ms": ms["area_any"], "copy_ms": ms["copy"],
+           "linear_ms": ms["linear"], "area_4x_960x1280_ms": ms["area_4x"], "bytes_needed": need,
+           "area_any_GBps": need / ms["area_any"] / 1e6, "copy_GBps": 2 * (need // 2) / ms["copy"] / 1e6,
+           "area_any_over_copy": ms["area_any"] / ms["copy"], "area_any_over_linear": ms["area_any"] / ms["linear"],
+           "inner": inner, "rounds": rounds, "equals_resize_host": host_ok}
+    print("window_1080p", json.dumps(res), flush=True)
+    return res
 
 
 def main():
@@ -89,6 +126,7 @@ def main():
             print(key, json.dumps(result["resize"][key]), flush=True)
             del cs, cd
         del frames, out
+    result["window_1080p"] = window_1080p(torch, rz, weights, dev, batch, dh, dw, a.seconds)
     print(json.dumps(result))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
