@@ -228,6 +228,15 @@ struct dcx_refiner {
 
 namespace {
 
+// the workspaces' parts lie one behind the other, each at a multiple of 256 bytes
+struct Carve {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t at = off; off = align_up(off + bytes, 256); return at; }
+};
+
+// the capacity of a corner pool = of RefineNet's patch table
+int check_pool(int pool) { return pool <= 0 || pool > (1 << 22) ? DCX_E_SHAPE : 0; }
+
 struct DetWs {
     size_t buf0, buf1, loc, ids, codes, conf, total;
     int ids_quads;
@@ -236,14 +245,14 @@ DetWs det_layout(int n_ids, int b, int h, int w) {
     DetWs L;
     const size_t hw = (size_t)h * w, cells = (size_t)(h / 8) * (w / 8);
     L.ids_quads = (n_ids + 1 + 3) / 4;
-    size_t off = 0;
-    L.buf0 = off; off = align_up(off + (size_t)b * 64 * hw * 4, 256);
-    L.buf1 = off; off = align_up(off + (size_t)b * 16 * hw * 4, 256);
-    L.loc = off;  off = align_up(off + (size_t)b * 68 * cells * 4, 256);
-    L.ids = off;  off = align_up(off + (size_t)b * L.ids_quads * 4 * cells * 4, 256);
-    L.codes = off; off = align_up(off + (size_t)b * cells * 4, 256);    // decode scratch: packed arg-max per cell
-    L.conf = off; off = align_up(off + (size_t)b * cells * 8, 256);     // soft-max probability of the winning (loc, ids) class per cell
-    L.total = off;
+    Carve c;
+    L.buf0 = c.take((size_t)b * 64 * hw * 4);
+    L.buf1 = c.take((size_t)b * 16 * hw * 4);
+    L.loc = c.take((size_t)b * 68 * cells * 4);
+    L.ids = c.take((size_t)b * L.ids_quads * 4 * cells * 4);
+    L.codes = c.take((size_t)b * cells * 4);    // decode scratch: packed arg-max per cell
+    L.conf = c.take((size_t)b * cells * 8);     // soft-max probability of the winning (loc, ids) class per cell
+    L.total = c.off;
     return L;
 }
 
@@ -253,12 +262,12 @@ struct RefWs {
 constexpr int kRefTiles = 32;     // capacity: 64x64 heat-map in 4x32 tiles (Winograd head; 16 tiles of 8x32 for the direct head)
 RefWs ref_layout(int p) {
     RefWs L;
-    size_t off = 0;
-    L.buf0 = off; off = align_up(off + (size_t)p * 65536 * 4, 256);
-    L.buf1 = off; off = align_up(off + (size_t)p * 65536 * 4, 256);
-    L.pval = off; off = align_up(off + (size_t)p * kRefTiles * 4, 256);
-    L.pidx = off; off = align_up(off + (size_t)p * kRefTiles * 4, 256);
-    L.total = off;
+    Carve c;
+    L.buf0 = c.take((size_t)p * 65536 * 4);
+    L.buf1 = c.take((size_t)p * 65536 * 4);
+    L.pval = c.take((size_t)p * kRefTiles * 4);
+    L.pidx = c.take((size_t)p * kRefTiles * 4);
+    L.total = c.off;
     return L;
 }
 
@@ -348,24 +357,6 @@ extern "C" size_t dcx_detector_workspace_bytes(const dcx_detector* det, int batc
 }
 
 namespace {
-// conv1a .. convPa|convDa; with_heads: also the two raw 1x1 heads into the workspace's C4 logit buffers (dcModel.forward).
-// Without them the 512-channel activation is left in buf0 for the fused tail kernel (dcx_tail.hip).
-// act0 (nullable): conv1a's output is already there (detector_front ran for this batch, which also cleared the control words);
-// conv1a is not launched, conv1b reads act0 and never writes it -- the later layers alternate between the workspace's two buffers
-int detector_run(const dcx_detector* det, const uint8_t* d_frames_u8, long frame_stride, int pitch, int pix,
-                 const float* d_images_f32, int batch, int height, int width, void* d_ws, size_t ws_bytes,
-                 bool with_heads, float* d_loc_nchw, float* d_ids_nchw, int32_t* zero_words, int n_zero, const float* act0,
-                 void* stream);
-}  // namespace
-
-extern "C" int dcx_detector_forward(const dcx_detector* det, const uint8_t* d_frames_u8, long frame_stride, int pitch,
-                                    const float* d_images_f32, int batch, int height, int width, void* d_ws,
-                                    size_t ws_bytes, float* d_loc_nchw, float* d_ids_nchw, void* stream) {
-    return detector_run(det, d_frames_u8, frame_stride, pitch, DCX_PIX_GRAY8, d_images_f32, batch, height, width, d_ws, ws_bytes, true,
-                        d_loc_nchw, d_ids_nchw, nullptr, 0, nullptr, stream);
-}
-
-namespace {
 // conv1a + bn1a + relu (net.py:60) of a batch into out; workgroup (0, 0) also clears zero_words
 int detector_front(const dcx_detector* det, const uint8_t* d_frames_u8, long frame_stride, int pitch, int pix,
                    const float* d_images_f32, int batch, int h, int w, float* out, int32_t* zero_words, int n_zero, hipStream_t s) {
@@ -381,6 +372,10 @@ int detector_front(const dcx_detector* det, const uint8_t* d_frames_u8, long fra
     return dcx_prof_end(pt0, s);
 }
 
+// conv1a .. convPa|convDa; with_heads: also the two raw 1x1 heads into the workspace's C4 logit buffers (dcModel.forward).
+// Without them the 512-channel activation is left in buf0 for the fused tail kernel (dcx_tail.hip).
+// act0 (nullable): conv1a's output is already there (detector_front ran for this batch, which also cleared the control words);
+// conv1a is not launched, conv1b reads act0 and never writes it -- the later layers alternate between the workspace's two buffers
 int detector_run(const dcx_detector* det, const uint8_t* d_frames_u8, long frame_stride, int pitch, int pix,
                  const float* d_images_f32, int batch, int height, int width, void* d_ws, size_t ws_bytes,
                  bool with_heads, float* d_loc_nchw, float* d_ids_nchw, int32_t* zero_words, int n_zero, const float* act0,
@@ -436,6 +431,13 @@ int detector_run(const dcx_detector* det, const uint8_t* d_frames_u8, long frame
     return 0;
 }
 }  // namespace
+
+extern "C" int dcx_detector_forward(const dcx_detector* det, const uint8_t* d_frames_u8, long frame_stride, int pitch,
+                                    const float* d_images_f32, int batch, int height, int width, void* d_ws,
+                                    size_t ws_bytes, float* d_loc_nchw, float* d_ids_nchw, void* stream) {
+    return detector_run(det, d_frames_u8, frame_stride, pitch, DCX_PIX_GRAY8, d_images_f32, batch, height, width, d_ws, ws_bytes, true,
+                        d_loc_nchw, d_ids_nchw, nullptr, 0, nullptr, stream);
+}
 
 extern "C" int dcx_detector_decode(const dcx_detector* det, int batch, int height, int width, void* d_ws,
                                    int dust_bin, int kmax, int32_t* d_counts, int32_t* d_rows, int32_t* d_loc_argmax,
@@ -502,23 +504,11 @@ namespace {
 struct FrameSrc { const uint8_t* frames; long frame_stride; int pitch, pix, height, width; };   // pipeline: patches come out of the frames
 int refiner_run(const dcx_refiner* rf, const float* d_patches, const FrameSrc* fsrc, int max_patches, int n_hint,
                 const int32_t* d_total, const int32_t* d_table, void* d_ws, size_t ws_bytes, int32_t* d_corners, float* d_xy,
-                float* d_heat, void* stream);
-}  // namespace
-
-extern "C" int dcx_refiner_forward(const dcx_refiner* rf, const float* d_patches, int max_patches,
-                                   const int32_t* d_total, const int32_t* d_table, void* d_ws, size_t ws_bytes,
-                                   int32_t* d_corners, float* d_xy, float* d_heat, void* stream) {
-    return refiner_run(rf, d_patches, nullptr, max_patches, 0, d_total, d_table, d_ws, ws_bytes, d_corners, d_xy, d_heat, stream);
-}
-
-namespace {
-int refiner_run(const dcx_refiner* rf, const float* d_patches, const FrameSrc* fsrc, int max_patches, int n_hint,
-                const int32_t* d_total, const int32_t* d_table, void* d_ws, size_t ws_bytes, int32_t* d_corners, float* d_xy,
                 float* d_heat, void* stream) {
     if (!rf || !d_ws || ((d_patches == nullptr) == (fsrc == nullptr))) return DCX_E_ARG;
     if (fsrc != nullptr && (d_total == nullptr || d_table == nullptr)) return DCX_E_ARG;
     if (d_xy != nullptr && d_table == nullptr) return DCX_E_ARG;
-    if (max_patches <= 0 || max_patches > (1 << 22)) return DCX_E_SHAPE;
+    if (const int rc = check_pool(max_patches)) return rc;
     const RefWs L = ref_layout(max_patches);
     if (ws_bytes < L.total) return DCX_E_WS;
     hipStream_t s = (hipStream_t)stream;
@@ -580,6 +570,12 @@ int refiner_run(const dcx_refiner* rf, const float* d_patches, const FrameSrc* f
 }
 }  // namespace
 
+extern "C" int dcx_refiner_forward(const dcx_refiner* rf, const float* d_patches, int max_patches,
+                                   const int32_t* d_total, const int32_t* d_table, void* d_ws, size_t ws_bytes,
+                                   int32_t* d_corners, float* d_xy, float* d_heat, void* stream) {
+    return refiner_run(rf, d_patches, nullptr, max_patches, 0, d_total, d_table, d_ws, ws_bytes, d_corners, d_xy, d_heat, stream);
+}
+
 // ---- whole pipeline -----------------------------------------------------------------------------
 namespace {
 // ctrl: int32 words cleared by the detector's first kernel: [0] = pool cursor (ends as the batch's firing-cell count = RefineNet's
@@ -590,22 +586,22 @@ inline int ctrl_word_count(int b) { return 64 + b; }
 struct FrontWs { size_t act, ctrl, total; int ctrl_words; };
 FrontWs front_layout(int b, int h, int w) {
     FrontWs F;
-    size_t off = 0;
-    F.act = off; off = align_up(off + (size_t)b * 64 * h * w * 4, 256);
+    Carve c;
+    F.act = c.take((size_t)b * 64 * h * w * 4);
     F.ctrl_words = ctrl_word_count(b);
-    F.ctrl = off; off = align_up(off + (size_t)F.ctrl_words * 4, 256);
-    F.total = off;
+    F.ctrl = c.take((size_t)F.ctrl_words * 4);
+    F.total = c.off;
     return F;
 }
 PipeWs pipe_layout(const dcx_detector* det, const dcx_refiner* rf, int b, int h, int w, int pool) {
     PipeWs L;
-    size_t off = 0;
-    L.det = off; off = align_up(off + det_layout(det->n_ids, b, h, w).total, 256);
-    L.table = off; off = align_up(off + (size_t)pool * 16, 256);
+    Carve c;
+    L.det = c.take(det_layout(det->n_ids, b, h, w).total);
+    L.table = c.take((size_t)pool * 16);
     L.ctrl_words = ctrl_word_count(b);
-    L.ctrl = off; off = align_up(off + (size_t)L.ctrl_words * 4, 256);
-    L.ref = off; off = align_up(off + (rf ? ref_layout(pool).total : 0), 256);
-    L.total = off;
+    L.ctrl = c.take((size_t)L.ctrl_words * 4);
+    L.ref = c.take(rf ? ref_layout(pool).total : 0);
+    L.total = c.off;
     return L;
 }
 }  // namespace
@@ -622,13 +618,13 @@ extern "C" size_t dcx_front_bytes(const dcx_detector* det, int batch, int height
 }
 
 namespace {
-// dcx_infer_batch's checks of the frames and the shape, for the two prefetch entries
+// the three pipeline entries' checks of the frames and the shape
 int check_batch_args(const dcx_detector* det, const uint8_t* d_frames_u8, int pitch, int pixel_format, int batch, int height,
                      int width) {
     if (!det || !d_frames_u8) return DCX_E_ARG;
-    if (pixel_format != DCX_PIX_GRAY8 && pixel_format != DCX_PIX_BGR8 && pixel_format != DCX_PIX_BGR8_LEGACY14) return DCX_E_ARG;
+    if (!dcx_pix_valid(pixel_format)) return DCX_E_ARG;
     if (batch <= 0 || batch > (1 << 20) || height < 8 || width < 8) return DCX_E_SHAPE;      // any size >= 8: the three poolings floor (net.py:16)
-    if (pitch < width * (pixel_format == DCX_PIX_GRAY8 ? 1 : 3)) return DCX_E_SHAPE;
+    if (pitch < width * dcx_pix_bpp(pixel_format)) return DCX_E_SHAPE;
     return 0;
 }
 }  // namespace
@@ -701,13 +697,11 @@ extern "C" int dcx_infer_batch(const dcx_detector* det, const dcx_refiner* rf, c
                                long frame_stride, int pitch, int pixel_format, int batch, int height, int width, int dust_bin,
                                int pool, void* d_ws, size_t ws_bytes, int32_t* d_counts, int32_t* d_starts, int32_t* d_rows,
                                float* d_xy, float* d_conf, void* stream) {
-    if (!det || !d_frames_u8 || !d_ws || !d_counts || !d_starts || !d_rows) return DCX_E_ARG;
+    if (!d_ws || !d_counts || !d_starts || !d_rows) return DCX_E_ARG;
     if (rf != nullptr && d_xy == nullptr) return DCX_E_ARG;
-    if (pixel_format != DCX_PIX_GRAY8 && pixel_format != DCX_PIX_BGR8 && pixel_format != DCX_PIX_BGR8_LEGACY14) return DCX_E_ARG;
-    if (pool <= 0 || pool > (1 << 22)) return DCX_E_SHAPE;
-    if (batch <= 0 || batch > (1 << 20) || height < 8 || width < 8) return DCX_E_SHAPE;      // any size >= 8: the three poolings floor (net.py:16)
-    if (pitch < width * (pixel_format == DCX_PIX_GRAY8 ? 1 : 3)) return DCX_E_SHAPE;
-    if (dust_bin < 0 || dust_bin > 255) return DCX_E_NIDS;
+    if (const int rc = check_batch_args(det, d_frames_u8, pitch, pixel_format, batch, height, width)) return rc;
+    if (const int rc = check_pool(pool)) return rc;
+    if (const int rc = dcx_check_dust_bin(dust_bin)) return rc;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)d_ws;
     // (A fork/join two-stream variant -- two half-batches of one call on two streams -- was measured and dropped: -1 % at
@@ -725,8 +719,8 @@ extern "C" int dcx_infer_batch_prefetched(const dcx_detector* det, const dcx_ref
     if (!d_ws || !d_front || !d_counts || !d_starts || !d_rows) return DCX_E_ARG;
     if (rf != nullptr && d_xy == nullptr) return DCX_E_ARG;
     if (const int rc = check_batch_args(det, d_frames_u8, pitch, pixel_format, batch, height, width)) return rc;
-    if (pool <= 0 || pool > (1 << 22)) return DCX_E_SHAPE;
-    if (dust_bin < 0 || dust_bin > 255) return DCX_E_NIDS;
+    if (const int rc = check_pool(pool)) return rc;
+    if (const int rc = dcx_check_dust_bin(dust_bin)) return rc;
     if (front_bytes < front_layout(batch, height, width).total) return DCX_E_WS;
     return infer_range(det, rf, d_frames_u8, frame_stride, pitch, pixel_format, batch, height, width, dust_bin, pool, (char*)d_ws,
                        ws_bytes, (char*)d_front, (hipEvent_t)detector_done_event, d_counts, d_starts, d_rows, d_xy, d_conf,

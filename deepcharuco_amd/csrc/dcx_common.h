@@ -89,10 +89,12 @@ int dcx_prof_begin(int kernel_id, int n, hipStream_t s);   // -> token, -1 when 
 int dcx_prof_end(int token, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
-// everything else (dcx_misc.hip)
+// everything else (dcx_misc.hip; its first-layer steps and pixel formats: dcx_first_dev.h, the packed cell code: dcx_cell_dev.h)
 
-// pix: DCX_PIX_GRAY8 / DCX_PIX_BGR8 / DCX_PIX_BGR8_LEGACY14 (BGR -> gray in the load, the integer formula of dcx_bgr2gray);
-// frame_stride / pitch in BYTES.  zero_words / n_zero (nullable): int32 words workgroup (0, 0) clears -- the pipeline's pool
+// pix: DCX_PIX_GRAY8 / DCX_PIX_BGR8 / DCX_PIX_BGR8_LEGACY14 (BGR -> gray in the load, the integer formula of dcx_bgr2gray)
+constexpr bool dcx_pix_valid(int pix) { return pix == DCX_PIX_GRAY8 || pix == DCX_PIX_BGR8 || pix == DCX_PIX_BGR8_LEGACY14; }
+constexpr int dcx_pix_bpp(int pix) { return pix == DCX_PIX_GRAY8 ? 1 : 3; }       // bytes per pixel of a valid pix
+// frame_stride / pitch in BYTES. zero_words / n_zero (nullable): int32 words workgroup (0, 0) clears -- the pipeline's pool
 // cursor and frame tickets, which the tail kernel nine launches later expects to be 0.
 int dcx_launch_conv1_u8(const uint8_t* frames, long frame_stride, int pitch, int pix, int n, int h, int w, int pad,
                         const float* w9x64, const float* bias, const float* alpha, const float* beta,
@@ -106,6 +108,10 @@ struct DcxLogitView {
     const float* p;
     long sb, sq, sp, sc;
 };
+// dust_bin is the reference's free parameter `dust_bin_ids` (model_utils.py:76,111): cells whose (masked) id equals it
+// do not fire.  Any value in [0, 255] has exactly the reference's semantics here (it need not equal n_ids); values
+// outside cannot be an id at all and would not survive the packed (loc | id << 8) code (dcx_cell_dev.h).
+inline int dcx_check_dust_bin(int dust_bin, int last = 255) { return dust_bin < 0 || dust_bin > last ? DCX_E_NIDS : 0; }
 int dcx_launch_decode(DcxLogitView loc, DcxLogitView ids, int batch, int n_loc, int n_ids1, int hc, int wc,
                       int dust_bin, int kmax, int32_t* counts, int32_t* rows,
                       int32_t* loc_argmax, int32_t* ids_argmax, int32_t* codes_scratch, hipStream_t s);

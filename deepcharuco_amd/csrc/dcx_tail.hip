@@ -26,6 +26,7 @@
 // frames in the pool depends on which frame finishes first (the host unpacks by starts[]); a frame's own rows never do.
 // Optional (CONF): the soft-max probability of the winning loc / ids class of every cell (log-sum-exp over the 65 / n_ids+1
 // logits while they are in the accumulators), delivered per corner -- the "confidences" model_utils.py:81-84 mentions.
+#include "dcx_cell_dev.h"
 #include "dcx_common.h"
 
 int dcx_device_cu_count();   // dcx_conv_mfma.hip
@@ -57,11 +58,11 @@ __device__ __forceinline__ void dcx_tail_compact_frame(const int32_t* codes, int
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nsuper = (cells + 2047) / 2048;
     const int32_t* fc = codes + (size_t)b * cells;
-    const int idle = dust_bin << 8;                  // a code that does not fire
+    const int idle = dcx_cell_pack(0, dust_bin);     // a code that does not fire
     int total = 0;
     if (nsuper > 1) {                                // big frames: the frame's count first (the pool slots are reserved before any row is written)
         int c = 0;
-        for (int i = tid; i < cells; i += 256) c += ((dcx_ld_agent(fc + i) >> 8) != dust_bin) ? 1 : 0;
+        for (int i = tid; i < cells; i += 256) c += dcx_cell_fires(dcx_ld_agent(fc + i), dust_bin) ? 1 : 0;
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off);
         if (lane == 0) s_cnt[wave] = c;
@@ -80,7 +81,7 @@ __device__ __forceinline__ void dcx_tail_compact_frame(const int32_t* codes, int
         unsigned long long m[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            m[c] = __ballot((code[c] >> 8) != dust_bin);
+            m[c] = __ballot(dcx_cell_fires(code[c], dust_bin));
             if (lane == 0) s_cnt[c * 4 + wave] = __popcll(m[c]);
         }
         __syncthreads();
@@ -104,16 +105,13 @@ __device__ __forceinline__ void dcx_tail_compact_frame(const int32_t* codes, int
         }
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            if ((code[c] >> 8) != dust_bin) {
+            if (dcx_cell_fires(code[c], dust_bin)) {
                 const int pos = start + run + base[c] + __popcll(m[c] & ((1ull << lane) - 1ull));
                 if (pos < po.pool) {
                     const int cell = sc * 2048 + c * 256 + tid;
-                    const int la = code[c] & 255, ia = code[c] >> 8;
-                    const int cy = cell / po.wc, cx = cell - cy * po.wc;
-                    const int x = 8 * cx + (la & 7);              // xs = 8*ix + loc % 8    (model_utils.py:121)
-                    const int y = 8 * cy + (la >> 3);             // ys = 8*iy + loc // 8   (model_utils.py:122)
-                    reinterpret_cast<int4*>(po.rows)[pos] = make_int4(x, y, ia, cell);
-                    if (po.table) reinterpret_cast<int4*>(po.table)[pos] = make_int4(b, x, y, pos);
+                    const int4 r = dcx_cell_row(code[c], cell, po.wc);
+                    reinterpret_cast<int4*>(po.rows)[pos] = r;
+                    if (po.table) reinterpret_cast<int4*>(po.table)[pos] = make_int4(b, r.x, r.y, pos);
                     if (CONF && po.conf) {
                         const unsigned long long cv = __hip_atomic_load(reinterpret_cast<unsigned long long*>(po.conf_cells) + (size_t)b * cells + cell,
                                                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -270,10 +268,10 @@ __global__ __launch_bounds__(256) void dcx_tail_kernel(const float4* __restrict_
                 __hip_atomic_store(reinterpret_cast<unsigned long long*>(po.conf_cells) + o, *reinterpret_cast<const unsigned long long*>(&cf2),
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-            if (la == 64) ia = dust_bin;         // where(loc_argmax == 64, dust_bin, ids_argmax)  model_utils.py:76
+            ia = dcx_cell_masked_id(la, 64, ia, dust_bin);
             // write-through (sc1) store: the frame's last work item -- possibly on another XCD, whose L2 is not coherent with this
             // one -- reads the code without anybody paying for a release fence (MI355X_MICROARCH.md, inter-workgroup visibility)
-            __hip_atomic_store(codes + o, la | (ia << 8), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(codes + o, dcx_cell_pack(la, ia), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (loc_argmax) loc_argmax[o] = la;
             if (ids_argmax) ids_argmax[o] = ia;
         }
@@ -316,7 +314,7 @@ int dcx_launch_tail(const float* act, int batch, int cells, const float* w_loc, 
                     int32_t* ids_argmax, const DcxPoolOut* po_in, hipStream_t s) {
     if (!act || !w_loc || !b_loc || !w_ids || !b_ids || !codes) return DCX_E_ARG;
     if (batch <= 0 || cells <= 0 || n_ids1 < 2 || n_ids1 > 64 || ids_cout_pad < n_ids1) return DCX_E_SHAPE;
-    if (dust_bin < 0 || dust_bin > 255) return DCX_E_NIDS;
+    if (const int rc = dcx_check_dust_bin(dust_bin)) return rc;
     DcxPoolOut po;
     memset(&po, 0, sizeof(po));
     if (po_in != nullptr) {

@@ -5,7 +5,8 @@ logits, heat-maps and arg-max decisions can be compared bit for bit (no toleranc
 
 The layer tables follow deepcharuco_amd/csrc/dcx_api.hip (detector_run, refiner_run); which restatement a layer takes follows
 family_of (dcx_conv_mfma.hip), restated in :func:`family_of`.  First layers (cin = 1) take the direct chain on the normalised
-image, zero-padded after normalisation (dcx_misc.hip: dcx_conv1_kernel / dcx_conv1_tile_kernel / dcx_conv1_patches_kernel).
+image, zero-padded after normalisation (dcx_first_dev.h: dcx_px_padded and dcx_conv1_quad, which dcx_misc.hip's dcx_conv1_kernel /
+dcx_conv1_tile_kernel / dcx_conv1_patches_kernel all call).
 The detector's convPa | convDa run on the GPU as one 512-channel layer; every output channel is independent, so restating the
 two 256-channel halves separately gives the same bits.
 """

@@ -2,7 +2,7 @@
 label maps into capped per-frame rows, the patch table over a batch, and the 24x24 gather out of u8 frames.
 
 Written from the header's words and from the reference's functions they cite (model_utils.py:19-36, :46-50, :91-124), not from
-csrc/dcx_misc.hip: plain loops and slices over the cells in raster order, no scan, no ballot, no clamped addressing.  tests/test_staged_abi_host.py pins each
+csrc/dcx_misc.hip or the device headers it calls (dcx_cell_dev.h, dcx_first_dev.h): plain loops and slices over the cells in raster order, no scan, no ballot, no clamped addressing.  tests/test_staged_abi_host.py pins each
 function to the oracle's stage functions; tests/test_gpu_staged_abi.py compares the kernels with it by exact equality.
 
 Everything is integer arithmetic except gather_u8, whose one float32 expression ((float32(g) - 128) / 255, IEEE division) is

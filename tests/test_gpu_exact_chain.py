@@ -293,7 +293,104 @@ def test_pipeline_patch_gather_bit_exact(dev, tiny, pix):
             assert np.array_equal(got[where[c], :2], exy), (pix, f, c, got[where[c]], exy)
 
 
-# --------------------------------------------------------------------------- 6. runtime switch sweep
+# --------------------------------------------------------------------------- 6. the detector's first layer in every pixel format
+
+PIX_IDS = {"gray": 0, "bgr": 1, "legacy14": 2}            # DCX_PIX_GRAY8 / DCX_PIX_BGR8 / DCX_PIX_BGR8_LEGACY14
+# (B, H, W, restated frames): one partial 16x16 tile; 2x3 tiles with the image index folded into blockIdx.y (both
+# dcx_conv1_tile_kernel, or dcx_conv1_kernel<PX,4> under DCX_CONV1_TILE=0); gx * gy = 1024 is not < 1024: dcx_conv1_kernel<PX,1>
+FRONT_SHAPES = [(1, 9, 15, [0]), (2, 17, 33, [0, 1]), (1024, 8, 9, [0, 511, 1023])]
+
+
+def _windowed_frames(pix, b, h, w, seed):
+    """(frames (B,H,W[,3]) u8, buffer, byte offset, frame stride, pitch): the frames as windows of a larger byte buffer whose
+    other bytes are 255 (pitch = W bpp + 5, frame stride = pitch (H + 1) + 3, offset 7).  Colour pixels are drawn from the
+    committed colours on which the two OpenCV generations give different gray levels."""
+    rng = np.random.default_rng(seed)
+    if pix == "gray":
+        frames = rng.integers(0, 256, (b, h, w), dtype=np.uint8)
+    else:
+        differ = np.load(os.path.join(REPO, "tests", "golden", "bgr2gray_formula.npz"))["bgr_differ"].reshape(-1, 3)
+        frames = differ[rng.integers(0, differ.shape[0], (b, h, w))]
+    bpp = 1 if pix == "gray" else 3
+    pitch, off = w * bpp + 5, 7
+    stride = pitch * (h + 1) + 3
+    buf = np.full(off + b * stride, 255, np.uint8)
+    for f in range(b):
+        rows = buf[off + f * stride: off + f * stride + h * pitch].reshape(h, pitch)
+        rows[:, :w * bpp] = frames[f].reshape(h, w * bpp)
+    return np.ascontiguousarray(frames), buf, off, stride, pitch
+
+
+def _front_act(det, buf, off, stride, pitch, pix, b, h, w, dev):
+    """dcx_detector_front on the windowed frames -> conv1a's output (B, 64, H, W) float32, read from the front set's act offset
+    (0), where it lies as C4 [B][16][H W][4]."""
+    from deepcharuco_amd import _lib
+    L = _lib.lib()
+    nb = L.dcx_front_bytes(det.handle, b, h, w)
+    assert nb >= b * 64 * h * w * 4
+    front = torch.full((nb,), 0xA5, dtype=torch.uint8, device=dev)
+    d = torch.from_numpy(buf).to(dev)
+    rc = L.dcx_detector_front(det.handle, d.data_ptr() + off, stride, pitch, PIX_IDS[pix], b, h, w, front.data_ptr(), nb,
+                              _lib.current_stream())
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    c4 = front[:b * 64 * h * w * 4].view(torch.float32).reshape(b, 16, h * w, 4)
+    return c4.permute(0, 1, 3, 2).reshape(b, 64, h, w).cpu().numpy()
+
+
+_FRONT_SCRIPT = r"""
+import sys
+sys.path.insert(0, {repo!r}); sys.path.insert(0, {tests!r})
+import numpy as np, torch
+import test_gpu_exact_chain as T
+from conftest import GoldenCase
+from deepcharuco_amd.models.net import dcModel
+c = GoldenCase("tiny_noise_64x96")
+dev = torch.device("cuda", 0)
+dc = dcModel(c.n_ids, c.sd_dc, dev)
+out = {{}}
+for i, (b, h, w, _) in enumerate(T.FRONT_SHAPES[:2]):
+    for pix in T.PIX_IDS:
+        _, buf, off, stride, pitch = T._windowed_frames(pix, b, h, w, 640 + i)
+        out["%s_%d" % (pix, i)] = T._front_act(dc, buf, off, stride, pitch, pix, b, h, w, dev)
+np.savez({outputs!r}, **out)
+print("FRONT ok")
+"""
+
+
+def test_detector_first_layer_bit_exact_in_every_pixel_format(dev, tiny, tmp_path):
+    """conv1a + bn1a + ReLU as dcx_detector_front leaves it == first_layer(normalised(frames, pix), pad 1), every value by its
+    bits, in gray / BGR / BGR-legacy14, at the shapes that reach dcx_conv1_tile_kernel and dcx_conv1_kernel<PX,1>; the first two
+    shapes once more in a child process under DCX_CONV1_TILE=0 (dcx_conv1_kernel<PX,4>).  The frames are windows of a larger
+    buffer full of 255, so a wrong bytes-per-pixel, pitch or stride shows; their colours are ones on which the two OpenCV
+    generations differ, and the two expected outputs do differ, so a swapped format cannot pass."""
+    from deepcharuco_amd.models.net import dcModel
+    dc = dcModel(tiny.n_ids, tiny.sd_dc, dev)
+    sd = N._np(tiny.sd_dc)
+    expect = {}
+    for i, (b, h, w, sel) in enumerate(FRONT_SHAPES):
+        for pix in PIX_IDS:
+            frames, buf, off, stride, pitch = _windowed_frames(pix, b, h, w, 640 + i)
+            exp = expect[pix, i] = N.first_layer(sd, N.normalised(frames[sel], pix), pad=1)
+            got = _front_act(dc, buf, off, stride, pitch, pix, b, h, w, dev)
+            assert got.shape == (b, 64, h, w)
+            nbad = _same_bits(got[sel], exp)
+            assert nbad == 0, f"{pix} {b}x{h}x{w}: {nbad} of {exp.size} values differ from the restatement"
+        assert _same_bits(expect["bgr", i], expect["legacy14", i]) > 0, (b, h, w)
+    outputs = str(tmp_path / "front_outputs.npz")
+    script = _FRONT_SCRIPT.format(repo=REPO, tests=os.path.join(REPO, "tests"), outputs=outputs)
+    env = dict(os.environ)
+    env["DCX_CONV1_TILE"] = "0"
+    out = subprocess.run([sys.executable, "-c", script], env=env, capture_output=True, text=True, timeout=240)
+    assert out.returncode == 0 and "FRONT ok" in out.stdout, f"DCX_CONV1_TILE=0 (rc {out.returncode}): {out.stderr[-2000:]}"
+    child = np.load(outputs)
+    for i, (b, h, w, _) in enumerate(FRONT_SHAPES[:2]):
+        for pix in PIX_IDS:
+            nbad = _same_bits(child[f"{pix}_{i}"], expect[pix, i])
+            assert nbad == 0, f"DCX_CONV1_TILE=0, {pix} {b}x{h}x{w}: {nbad} of {expect[pix, i].size} values differ from the restatement"
+
+
+# --------------------------------------------------------------------------- 7. runtime switch sweep
 
 _SWEEP_SCRIPT = r"""
 import hashlib, sys

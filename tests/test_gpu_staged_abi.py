@@ -409,7 +409,7 @@ def _window_buffer(dev, frames, pitch, fstride, offset):
 
 @pytest.mark.parametrize("hw", [(64, 96), (8, 8), (9, 15), (40, 56)], ids=lambda v: f"{v[0]}x{v[1]}")
 def test_gather_u8_from_windows(dev, L, hw):
-    """dcx_extract_patches_u8 (dcx_gather_kernel<uint8_t>) on three different frames that are windows of a larger buffer (pitch >
+    """dcx_extract_patches_u8 (dcx_gather_kernel on gray DcxPix) on three different frames that are windows of a larger buffer (pitch >
     width, frame stride > height * pitch, a byte offset; the padding holds 255) == gather_u8 == the oracle's extract_patches of
     the normalised frame, for key-points on the corners, the edges, around (11, 11) / (12, 12) and inside; patches at and beyond
     *d_total keep the sentinel; dcx_extract_patches_f32 on the normalised images gives the same bits."""

@@ -19,8 +19,9 @@ from the code; a word that were read first would be a wild index under 0xFF):
 
   word                                     where                                   written first by                          read by
   ---------------------------------------  --------------------------------------  ----------------------------------------  ----------------
-  pool cursor ctrl[0]                      pipe_layout.ctrl / front_layout.ctrl    conv1a of the detector (dcx_misc.hip:     tail's atomicAdd;
-                                                                                   workgroup (0,0,0) clears ctrl_words) --   RefineNet's n_limit
+  pool cursor ctrl[0]                      pipe_layout.ctrl / front_layout.ctrl    conv1a of the detector (dcx_zero_words,   tail's atomicAdd;
+                                                                                   dcx_first_dev.h: workgroup (0,0,0)        RefineNet's n_limit
+                                                                                   clears ctrl_words) --
                                                                                    dcx_detector_front for a prefetch set
   frame tickets ctrl[64 .. 64+B)           the same words                          the same launch                           tail's last-item test
   codes [B][cells] (packed arg-max)        det_layout.codes                        tail kernel's items (agent-scope stores)  tail's last item of

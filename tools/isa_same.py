@@ -9,8 +9,9 @@ A kernel whose parameter list changed has another mangled name: such kernels are
 (where that is unique on both sides) and compared like the rest.  A kernel that became a template has several instantiations of
 that name here: the one whose template argument names a class of the base symbol's own parameter list is its pair
 (f(RigCams, ...) with f<RigCams>).  A renamed kernel is paired by hand: --pair BASE_NAME=SUBSTRING[+SUBSTRING ...] pairs the base's
-kernel of that unmangled name with the one kernel here whose symbol holds every SUBSTRING.
-usage: python tools/isa_same.py REV [--pair BASE_NAME=SUB[+SUB]] ... [file.hip ...]
+kernel of that unmangled name with the one kernel here whose symbol holds every SUBSTRING.  Where the base has several kernels of
+that name (a template's instantiations), BASE_NAME+SUBSTRING[+SUBSTRING ...] names the one whose symbol holds every SUBSTRING.
+usage: python tools/isa_same.py REV [--pair BASE_NAME[+SUB]=SUB[+SUB]] ... [file.hip ...]
 exit status 0 only if every kernel is identical"""
 import collections, os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
@@ -100,13 +101,13 @@ def template_classes(sym):
 
 
 def main():
-    args, by_hand = sys.argv[1:], {}
+    args, by_hand = sys.argv[1:], []
     while "--pair" in args:
         at = args.index("--pair")
         if at + 1 >= len(args) or "=" not in args[at + 1]:
             sys.exit(__doc__)
         name, subs = args[at + 1].split("=", 1)
-        by_hand[name] = subs.split("+")
+        by_hand.append((name.split("+"), subs.split("+")))
         del args[at:at + 2]
     if not args:
         sys.exit(__doc__)
@@ -130,10 +131,12 @@ def main():
             # a kernel with a new parameter list or a new name: this tree's symbol is compared under the base's, if one answers
             only_a, only_b = [k for k in ka if k not in kb], [k for k in kb if k not in ka]
             for k in only_a:
-                if sum(bare_name(o) == bare_name(k) for o in only_a) != 1:
+                mine = [(b, h) for b, h in by_hand if b[0] == bare_name(k) and all(sub in k for sub in b[1:])]
+                hand = [h for _, h in mine]
+                if sum(bare_name(o) == bare_name(k) for o in only_a) != 1 and not any(len(b) > 1 for b, _ in mine):
                     continue
-                if bare_name(k) in by_hand:
-                    here = [o for o in only_b if all(sub in o for sub in by_hand[bare_name(k)])]
+                if hand:
+                    here = [o for o in only_b if all(sub in o for sub in hand[0])]
                 else:
                     here = [o for o in only_b if bare_name(o) == bare_name(k)]
                     if len(here) > 1:
