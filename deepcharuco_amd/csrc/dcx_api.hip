@@ -361,7 +361,7 @@ namespace {
 int detector_front(const dcx_detector* det, const uint8_t* d_frames_u8, long frame_stride, int pitch, int pix,
                    const float* d_images_f32, int batch, int h, int w, float* out, int32_t* zero_words, int n_zero, hipStream_t s) {
     int rc;
-    const int pt0 = dcx_prof_begin(DCX_PROF_CONV1A, batch, s);
+    const int pt0 = dcx_prof_begin(DCX_PROF_CONV1A, batch, 0, s);
     if (d_frames_u8)
         rc = dcx_launch_conv1_u8(d_frames_u8, frame_stride, pitch, pix, batch, h, w, 1, det->first.w, det->first.bias,
                                  det->first.alpha, det->first.beta, out, nullptr, zero_words, n_zero, s);
@@ -518,7 +518,7 @@ int refiner_run(const dcx_refiner* rf, const float* d_patches, const FrameSrc* f
     const int p = max_patches;
     const int* lim = d_total;
     // conv1a (pad 0) 24 -> 22 (refinenet.py:56); in the pipeline fused with extract_patches (model_utils.py:19-36)
-    const int pt0 = dcx_prof_begin(DCX_PROF_PATCHES, p, s);
+    const int pt0 = dcx_prof_begin(DCX_PROF_PATCHES, p, lim != nullptr, s);
     int rc = fsrc != nullptr
         ? dcx_launch_conv1_patches_u8(fsrc->frames, fsrc->frame_stride, fsrc->pitch, fsrc->pix, fsrc->height, fsrc->width, d_table, d_total, p, n_hint,
                                       rf->first.w, rf->first.bias, rf->first.alpha, rf->first.beta, buf0, s)
@@ -562,7 +562,7 @@ int refiner_run(const dcx_refiner* rf, const float* d_patches, const FrameSrc* f
     // (finalising inside the head kernel -- per-patch tickets, the last work item reduces -- was built and measured in round 5: the
     //  device-scope fence ahead of the ticket drains the item's software pipeline, 0.359 -> 0.693 ms at bs=32;
     //  profiles/experiments/r05_fused_finalize.md)
-    const int pt1 = dcx_prof_begin(DCX_PROF_FINALIZE, p, s);
+    const int pt1 = dcx_prof_begin(DCX_PROF_FINALIZE, p, lim != nullptr, s);
     rc = dcx_launch_refine_finalize((const float*)(ws + L.pval), (const int*)(ws + L.pidx), heat_tiles, 64, p, lim,
                                     d_table, d_corners, d_xy, s);
     if (rc) return rc;
@@ -675,7 +675,7 @@ int infer_range(const dcx_detector* det, const dcx_refiner* rf, const uint8_t* d
         po.tickets = ctrl + 64; po.cursor = ctrl; po.counts = d_counts; po.starts = d_starts; po.rows = d_rows;
         po.table = rf ? table : nullptr; po.conf = d_conf; po.conf_cells = (float*)(ws + L.det + D.conf);
         po.wc = wc; po.pool = pool;
-        const int pt = dcx_prof_begin(DCX_PROF_TAIL, batch, s);
+        const int pt = dcx_prof_begin(DCX_PROF_TAIL, batch, 0, s);
         rc = dcx_launch_tail(act, batch, hc * wc, det->head_loc.w, det->head_loc.bias, det->head_ids.w, det->head_ids.bias,
                              det->head_ids.cout_pad, det->n_ids + 1, dust_bin, codes, nullptr, nullptr, &po, s);
         if (rc) return rc;

@@ -85,7 +85,7 @@ int dcx_conv_heat_tiles(int ho, int wo, int ups);
 // per-launch profiling of the pipeline's launches outside the convolution families (dcx_conv_mfma.hip keeps the record list;
 // bench.py's step_breakdown): kernel ids >= 100, bracketed by dcx_api.hip
 enum { DCX_PROF_CONV1A = 100, DCX_PROF_PATCHES = 101, DCX_PROF_TAIL = 102, DCX_PROF_FINALIZE = 103 };
-int dcx_prof_begin(int kernel_id, int n, hipStream_t s);   // -> token, -1 when not recording
+int dcx_prof_begin(int kernel_id, int n, int limited, hipStream_t s);   // limited: the launch takes a device-side count; -> token, -1 when not recording
 int dcx_prof_end(int token, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------

@@ -231,7 +231,17 @@ extern "C" int dcx_get_deterministic(void) { return dcx_deterministic_enabled();
 
 extern "C" int dcx_profile_enable(int enabled) {
     g_prof = enabled != 0;
-    if (g_prof) { g_recs.clear(); g_pool_used = 0; }
+    if (g_prof) {
+        g_recs.clear(); g_pool_used = 0;
+        // A session starts from cleared probe slots: a record whose launch writes no probes (the ids >= 100, a convolution whose
+        // workgroup 0 has no item) must read as clock 0, not as the clock of the launch that had its slot in an earlier session.
+        // Here and not per record: this is set-up code outside every timed region, a clear in front of each bracket would not be.
+        // Waited for, so that the clear is over before any launch on any stream (non-blocking ones included) can probe.
+        if (g_clk_dev != nullptr) {
+            DCX_CHECK_HIP(hipMemset(g_clk_dev, 0, sizeof(unsigned long long) * kClkWords * kClkSlots));
+            DCX_CHECK_HIP(hipStreamSynchronize(nullptr));
+        }
+    }
     return 0;
 }
 extern "C" int dcx_profile_enabled(void) { return g_prof ? 1 : 0; }
@@ -252,10 +262,10 @@ extern "C" const char* dcx_profile_kernel_name(int id) {
 
 // hipEvent bracket around one non-conv launch of the pipeline (same record list as the convolutions; flops = 0).  Only while
 // profiling is on and unfiltered (a filter selects one convolution instantiation).  -> token for dcx_prof_end, -1 = not recording
-int dcx_prof_begin(int kernel_id, int n, hipStream_t stream) {
+int dcx_prof_begin(int kernel_id, int n, int limited, hipStream_t stream) {
     if (!g_prof || g_prof_filter >= 0) return -1;
     ProfRec r;
-    r.kernel_id = kernel_id; r.n = n; r.limited = 0; r.flops_per_image = 0.0;
+    r.kernel_id = kernel_id; r.n = n; r.limited = limited ? 1 : 0; r.flops_per_image = 0.0;
     r.e0 = prof_event();
     r.e1 = prof_event();
     r.slot = (int)g_recs.size();

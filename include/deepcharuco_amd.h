@@ -791,7 +791,20 @@ int dcx_get_xcd_weights(float* w8);
  * synchronised the stream(s), dcx_profile_fetch() returns up to max_records records:
  * kernel_ids[i] (index into the instantiation table, see dcx_profile_kernel_name), n_images[i]
  * (images the grid covered), limited[i] (1 if a device-side patch count may have skipped some
- * of them), flops_per_image[i] = 2*cout*cin*ks*ks*Ho*Wo (algorithmic, un-padded), ms[i].      */
+ * of them), flops_per_image[i] = 2*cout*cin*ks*ks*Ho*Wo (algorithmic, un-padded), ms[i].
+ * Ho x Wo is the convolution's own output: after an up-sampling on the read, before a pooling in the epilogue.
+ * What a call records, in launch order (tests/instrument_cases.py derives the list from the oracle's layers):
+ *   dcx_infer_batch          100 (detector conv1a, n = batch), conv1b .. conv4b, convPa|convDa as ONE launch (cout = 512,
+ *                            flops of both), 102 (tail: the 1x1 heads convPb / convDb + arg-max + compaction, n = batch); with a
+ *                            refiner: 101 (RefineNet conv1a + patch gather), conv1b .. conv5b, convPa (its 1x1 convPb and the tile
+ *                            arg-max run in the same launch and are not counted), 103 (finalize) -- all with n = pool, limited = 1
+ *   dcx_detector_forward     100, conv1b .. conv4b, convPa|convDa, then convPb and convDb as 1x1 launches (Ho x Wo = 1 x cells)
+ *   dcx_refiner_forward      101 (conv1a on caller patches), conv1b .. conv5b, convPa, 103; n = max_patches, limited = 1 iff
+ *                            d_total is given
+ * The ids >= 100 carry flops_per_image = 0: the two conv1a layers, the detector's 1x1 heads inside the tail and RefineNet's convPb
+ * are in no record's flops (0.156 of the 26.816 GFLOP of a 320x240 frame with 16 corners).
+ * dcx_profile_enable(1) starts a session: it clears the record list and the clock probes of every slot (a synchronous call: set-up
+ * code, not for a timed region).  dcx_profile_enable(0) stops recording and keeps the session's records.                  */
 int dcx_profile_enable(int enabled);
 int dcx_profile_enabled(void);       /* 1 while per-launch profiling is on */
 int dcx_profile_count(void);
@@ -799,17 +812,26 @@ int dcx_profile_count(void);
 int dcx_profile_filter(int kernel_id);
 int dcx_profile_sample(int every);   /* bracket only every `every`-th matching launch (1 = all): the two hipEvent records of a
                                         bracket keep the GPU idle for ~11 us, which a throughput measurement should not pay on
-                                        every launch */
+                                        every launch; every <= 1 is 1).  The count of matching launches is restarted by THIS call
+                                        alone -- dcx_profile_enable(1) does not restart it, and launches that match while
+                                        profiling is on count whether or not they are recorded: the first matching launch after
+                                        dcx_profile_sample() is recorded, then every `every`-th, across sessions */
 int dcx_profile_fetch(int* kernel_ids, int* n_images, int* limited, double* flops_per_image, float* ms,
                       int max_records);
 /* kernel_id < 100: the convolution instantiation table; 100..103: the pipeline's other launches (detector conv1a, RefineNet
  * conv1a + patch gather, detector tail, refine finalize), recorded with flops_per_image = 0 while no filter is set */
 const char* dcx_profile_kernel_name(int kernel_id);
 /* effective shader clock (GHz) seen by workgroup 0 of each recorded launch: s_memtime ticks per
- * s_memrealtime (100 MHz) tick between its first and last instruction.  Same order as _fetch. */
+ * s_memrealtime (100 MHz) tick between its first and last instruction.  Same order as _fetch.
+ * Only workgroup 0 of a launch writes probes, and only the first 1,024 records of a session own a probe slot: ghz[i] is 0 for
+ * every later record (complete otherwise), for the ids >= 100, and for a convolution whose workgroup 0 had no work item (a
+ * device-side patch count of 0, or fewer than 8 items under the XCD-aware walk) -- a mean over a session's clocks must leave
+ * the zeros out.  One table per process, allocated on the device of the first profiled launch.                       */
 int dcx_profile_clocks(float* ghz, int max_records);
 /* raw 64 probe words of one recorded launch (kernel-tuning aid): [0..3] start/end {s_memtime, s_memrealtime},
- * then for the first 20 units of workgroup 0: s_memtime before the unit barrier, after it, after the MFMA loop */
+ * then for the first 20 units of workgroup 0: s_memtime before the unit barrier, after it, after the MFMA loop (the small-launch
+ * kernels dcx_conv_wino2hs / wino2ps write words 0..3 only).  DCX_E_ARG: NULL, record outside [0, 1024), or no table yet
+ * (nothing has been profiled in this process)                                                                       */
 int dcx_profile_probe_words(int record, unsigned long long* out64);
 
 #ifdef __cplusplus
