@@ -110,6 +110,9 @@ SIGNATURES = {
     "dcx_fisheye_calibrate_workspace_bytes": (_sz, [_i]),
     "dcx_fisheye_calibrate_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _i, _i, C.c_double, _vp, _sz, _vp, _vp,
                                        C.POINTER(C.c_double), _vp]),
+    "dcx_calibrate_uncertainty_workspace_bytes": (_sz, [_i]),
+    "dcx_calibrate_uncertainty_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _i, C.POINTER(C.c_double), _vp, _vp, _vp,
+                                           _vp, _sz, _vp, _vp, _vp]),
     "dcx_fisheye_undistort_rectify_map": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                               C.POINTER(C.c_double), _i, _i, _vp, _vp]),
     "dcx_fisheye_rectify_points_pool": (_i, [_vp, _vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),

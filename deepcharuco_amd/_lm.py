@@ -43,6 +43,42 @@ def schur_step(U, W, V, ga, gb, lg: int):
     return dg, z - np.einsum("nij,j->ni", Y, dg)
 
 
+def _spd_inverse(A):
+    """The inverse of symmetric positive definite matrices [..., n, n] through their Cholesky factors (L^-T L^-1: symmetric to the
+    bit), or None if one of them is not positive definite or not finite."""
+    if not np.isfinite(A).all():
+        return None
+    try:
+        Li = np.linalg.inv(np.linalg.cholesky(A))
+    except np.linalg.LinAlgError:
+        return None
+    inv = np.swapaxes(Li, -1, -2) @ Li
+    return inv if np.isfinite(inv).all() else None
+
+
+def schur_covariance(U, W, V, costs):
+    """The covariance blocks of a solved joint problem from its UNDAMPED normal blocks (``schur_step``'s U [N, 6, 6], W [N, n, 6],
+    V [n, n]; ``costs`` the units' costs), by the elimination ``schur_step`` solves with: S = V - sum W_i U_i^-1 W_i^T,
+    Y_i = U_i^-1 W_i^T; the inverse of the full normal matrix has S^-1 as its global corner and U_i^-1 + Y_i S^-1 Y_i^T as unit i's
+    6x6 diagonal block.  -> (S^-1 [n, n], the units' blocks [N, 6, 6]), both without the factor sigma^2 (the caller's: its degrees
+    of freedom are its own), or None if a U_i or S is not positive definite or something is not finite.  csrc/dcx_calib_cov.hip
+    runs the same steps per camera model; the stereo and rig solvers have the same block structure."""
+    if not np.isfinite(np.asarray(costs, np.float64)).all() or not np.isfinite(W).all():
+        return None
+    Ui = _spd_inverse(U)
+    if Ui is None:
+        return None
+    Y = Ui @ W.transpose(0, 2, 1)                                  # U_i^-1 W_i^T  [N, 6, n]
+    Si = _spd_inverse(V - np.einsum("nij,njk->ik", W, Y))
+    if Si is None:
+        return None
+    P = Ui + Y @ Si @ Y.transpose(0, 2, 1)
+    P = 0.5 * (P + P.transpose(0, 2, 1))
+    if not np.isfinite(P).all():
+        return None
+    return Si, P
+
+
 def refine(g, P, normal_blocks, trial_costs, total, stop_forced: bool, max_iter: int, eps: float):
     """-> (status LM_*, g, P, the units' costs at the solution or None, accepted steps, attempts).
 

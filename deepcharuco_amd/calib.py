@@ -31,6 +31,10 @@ it: a corner with a wrong id sits a board square away from its label, the joint 
 computed later inherits the wrong model.  ``calibrate_camera_ransac_host_full`` is the definition and carries the steps;
 ``calibrate_charuco_ransac_pool`` / ``_device`` run them in csrc/dcx_calib_ransac.hip.  The discrete results (winners, masks,
 number of solves) are equal on host and device wherever no row stands within rounding of a threshold.
+
+``calibration_uncertainty_*`` say how well a solved model is determined: the covariances of the intrinsics and of every used view's
+pose (cv2.calibrateCameraExtended's standard deviations).  ``calibration_uncertainty_host`` is the definition;
+``calibration_uncertainty_pool`` / ``_device`` run it in csrc/dcx_calib_cov.hip, without a host loop or a synchronisation.
 """
 from __future__ import annotations
 
@@ -57,7 +61,9 @@ RANSAC_MAX_ROUNDS = 8          # re-mask rounds of the robust calibration
 __all__ = ["CalibResult", "calibrate_camera_host", "calibrate_camera_host_full", "calibrate_charuco_pool",
            "calibrate_charuco_device", "CALIB_OK", "CALIB_NO_VIEWS", "CALIB_DEGENERATE", "CALIB_NONFINITE",
            "RobustCalibResult", "calibrate_camera_ransac_host", "calibrate_camera_ransac_host_full",
-           "calibrate_charuco_ransac_pool", "calibrate_charuco_ransac_device", "ransac_workspace_bytes"]
+           "calibrate_charuco_ransac_pool", "calibrate_charuco_ransac_device", "ransac_workspace_bytes",
+           "CalibUncertainty", "calibration_uncertainty_host", "calibration_uncertainty_pool", "calibration_uncertainty_device",
+           "unpack_uncertainty", "uncertainty_workspace_bytes", "COV_OK", "COV_NO_VIEWS", "COV_NO_DOF", "COV_SINGULAR"]
 
 
 class CalibResult(NamedTuple):
@@ -621,3 +627,288 @@ def calibrate_charuco_ransac_device(keypoints_list: Sequence, col_count, row_cou
     _no_bad_id(r, col_count, row_count)
     # undo pack_keypoints' stable id sort
     return r._replace(inliers=[mask[_caller_order(kp)] for kp, mask in zip(keypoints_list, r.inliers)])
+
+
+# ------------------------------------------------------------------------------------------------ how well the model is determined
+
+COV_OK, COV_NO_VIEWS, COV_NO_DOF, COV_SINGULAR = range(4)       # DCX_COV_* of include/deepcharuco_amd.h
+COV_GLOBAL_WORDS, COV_POSE_WORDS = 96, 42                       # d_global, a view of d_pose_cov (DCX_COV_GLOBAL_WORDS, DCX_COV_POSE_WORDS)
+_COV_STD, _COV_SIGMA2 = 81, 90                                  # DCX_COV_STD; DCX_COV_SIGMA2, then dof, points, views, status
+CAMERA_PINHOLE, CAMERA_FISHEYE = 0, 1                           # DCX_CAMERA_*
+
+
+class CalibUncertainty(NamedTuple):
+    status: int                  # COV_*
+    sigma2: float                # sum |r|^2 / dof (px^2): the variance of one image coordinate the residuals imply
+    dof: int                     # 2 * points - intrinsics - 6 * views
+    points: int                  # kept rows of the views used
+    views: int                   # views used
+    std_intrinsics: np.ndarray   # [NG]: fx fy cx cy, then the model's distortion coefficients (cv2's stdDeviationsIntrinsics)
+    cov_intrinsics: np.ndarray   # [NG, NG]
+    std_extrinsics: np.ndarray   # [B, 6]: rvec then tvec (cv2's order); zeros unless the view was used
+    cov_extrinsics: np.ndarray   # [B, 6, 6]
+
+
+def _uncertainty(views, view_status, theta: np.ndarray, poses: np.ndarray, project_full) -> CalibUncertainty:
+    """The definition (``calibration_uncertainty_host``) on checked arguments: ``views`` with their masks applied, ``poses``
+    [B, 6], ``project_full`` the camera model's."""
+    B, n = len(views), theta.size
+    used = np.flatnonzero(view_status == PNP_OK)
+    points = int(sum(views[i][0].shape[0] for i in used))
+    dof = 2 * points - n - 6 * int(used.size)
+
+    def out(status, sigma2=0.0, cov=None, blocks=None):
+        ci, ce = np.zeros((n, n)), np.zeros((B, 6, 6))
+        if status == COV_OK:
+            ci, ce[used] = cov, blocks
+        return CalibUncertainty(status, float(sigma2), dof, points, int(used.size), np.sqrt(np.diag(ci)), ci,
+                                np.sqrt(np.diagonal(ce, axis1=1, axis2=2)), ce)
+
+    if not used.size:
+        return out(COV_NO_VIEWS)
+    if dof <= 0:
+        return out(COV_NO_DOF)
+    if not (np.isfinite(theta).all() and np.isfinite(poses[used]).all()):
+        return out(COV_SINGULAR)
+    nb = _normal_blocks([views[i] for i in used], theta, poses[used], project_full)
+    if nb is None:
+        return out(COV_SINGULAR)
+    U, W, V, _, _, costs = nb
+    inv = _lm.schur_covariance(U, W, V, costs)
+    if inv is None:
+        return out(COV_SINGULAR)
+    sigma2 = _total(costs) / dof
+    cov, blocks = sigma2 * inv[0], sigma2 * inv[1]
+    if not (math.isfinite(sigma2) and np.isfinite(cov).all() and np.isfinite(blocks).all()):
+        return out(COV_SINGULAR)
+    return out(COV_OK, sigma2, cov, blocks)
+
+
+def _is_result(x) -> bool:
+    return hasattr(x, "camera_matrix") and hasattr(x, "view_status")
+
+
+def _free_model(camera_matrix, dist_coeffs, n_dist: int) -> np.ndarray:
+    """(K, the model's ``n_dist`` free distortion coefficients) -> theta.  ValueError for any other number of coefficients: one
+    that the solver held fixed has no variance to report."""
+    K = pnp._camera(camera_matrix)
+    d = np.zeros(0) if dist_coeffs is None else np.asarray(dist_coeffs, dtype=np.float64).ravel()
+    if d.size != n_dist:
+        raise ValueError(f"{d.size} distortion coefficients: the uncertainty is that of the solvers' free parameters, fx fy cx cy and "
+                         f"{n_dist} coefficients; a coefficient held fixed has no variance to report")
+    if not np.isfinite(d).all():
+        raise ValueError("distortion coefficients must be finite")
+    return np.r_[K[0, 0], K[1, 1], K[0, 2], K[1, 2], d]
+
+
+def _poses(rvecs, tvecs, B: int) -> np.ndarray:
+    r = np.asarray(rvecs, dtype=np.float64).reshape(-1, 3) if B else np.zeros((0, 3))
+    t = np.asarray(tvecs, dtype=np.float64).reshape(-1, 3) if B else np.zeros((0, 3))
+    if r.shape[0] != B or t.shape[0] != B:
+        raise ValueError(f"{B} views but {r.shape[0]} rvecs and {t.shape[0]} tvecs")
+    return np.concatenate([r, t], 1)
+
+
+def _view_status(view_status, B: int) -> np.ndarray:
+    st = np.full(B, PNP_OK, np.int32) if view_status is None else np.asarray(view_status).astype(np.int32).ravel()
+    if st.size != B:
+        raise ValueError(f"{B} views but {st.size} view statuses")
+    return st
+
+
+def _model_args(camera_matrix, dist_coeffs, rvecs, tvecs, view_status, inliers):
+    """The explicit arguments, or those of the ``CalibResult`` / ``RobustCalibResult`` given in ``camera_matrix``'s place (its
+    ``inliers`` where it has them and none are given).  ValueError for a result whose calibration failed."""
+    if not _is_result(camera_matrix):
+        if rvecs is None or tvecs is None:
+            raise ValueError("rvecs and tvecs are required with an explicit camera model")
+        return camera_matrix, dist_coeffs, rvecs, tvecs, view_status, inliers
+    r = camera_matrix
+    if r.status != CALIB_OK:
+        raise ValueError(f"the calibration failed (status {r.status}): there is no solution to take an uncertainty at")
+    return r.camera_matrix, r.dist_coeffs, r.rvecs, r.tvecs, r.view_status, inliers if inliers is not None else getattr(r, "inliers", None)
+
+
+def _uncertainty_host(object_points, image_points, camera_matrix, dist_coeffs, rvecs, tvecs, view_status, inliers, n_dist,
+                      project_full) -> CalibUncertainty:
+    camera_matrix, dist_coeffs, rvecs, tvecs, view_status, inliers = _model_args(camera_matrix, dist_coeffs, rvecs, tvecs,
+                                                                                 view_status, inliers)
+    theta = _free_model(camera_matrix, dist_coeffs, n_dist)
+    views = _views(object_points, image_points)
+    B = len(views)
+    if inliers is not None:
+        if len(inliers) != B:
+            raise ValueError(f"{B} views but {len(inliers)} inlier masks")
+        for i, m in enumerate(inliers):
+            m = np.asarray(m).astype(bool).ravel()
+            if m.size != views[i][0].shape[0]:
+                raise ValueError(f"view {i} has {views[i][0].shape[0]} rows but its mask {m.size}")
+            views[i] = (views[i][0][m], views[i][1][m])            # a dropped row is a row that is not there
+    return _uncertainty(views, _view_status(view_status, B), theta, _poses(rvecs, tvecs, B), project_full)
+
+
+def calibration_uncertainty_host(object_points, image_points, camera_matrix, dist_coeffs=None, rvecs=None, tvecs=None,
+                                 view_status=None, inliers=None) -> CalibUncertainty:
+    """How well a solved pinhole calibration is determined: the covariance of theta = (fx, fy, cx, cy, k1, k2, p1, p2, k3) and of
+    every used view's (rvec, tvec), cv2.calibrateCameraExtended's ``stdDeviationsIntrinsics`` / ``stdDeviationsExtrinsics``.  In
+    float64 on the host; the definition and the pin of ``dcx_calibrate_uncertainty_pool``.
+
+    ``camera_matrix``, ``dist_coeffs`` (exactly the solver's 5: ValueError otherwise, a coefficient held fixed has no variance),
+    ``rvecs``, ``tvecs`` [B, 3]: the solution; ``view_status`` [B]: a view takes part where it is ``PNP_OK`` (None: every view);
+    ``inliers``: per view a mask over its rows (None: every row).  In ``camera_matrix``'s place a ``CalibResult`` or a
+    ``RobustCalibResult`` stands for all of them (its ``inliers`` included, in the row order of the points given here).
+
+    With the undamped normal blocks of ``_normal_blocks`` at the solution, over the used views' kept rows:
+    S = V - sum W_i U_i^-1 W_i^T, Y_i = U_i^-1 W_i^T, dof = 2 points - 9 - 6 views, sigma^2 = sum |r|^2 / dof,
+    cov_intrinsics = sigma^2 S^-1, cov_pose_i = sigma^2 (U_i^-1 + Y_i S^-1 Y_i^T) (``_lm.schur_covariance``: the corner and the
+    diagonal blocks of the inverse of the full normal matrix); the standard deviations are the roots of the diagonals.
+
+    The dof convention: sigma^2 is the textbook estimator, residuals (two per point) minus parameters.  cv2 is believed to divide
+    by (points - parameters) instead; that could not be checked against cv2 here, so ``sigma2``, ``dof``, ``points`` and ``views``
+    are returned for a caller who wants another convention: covariances scale with sigma^2, standard deviations with its root.
+
+    Statuses, in this order: ``COV_NO_VIEWS`` (no used view), ``COV_NO_DOF`` (dof <= 0), ``COV_SINGULAR`` (a U_i or S not positive
+    definite, a point not in front of the camera, a value not finite).  Everything but the status and the counts is zero unless
+    ``COV_OK``; views that were not used get zeros.  Not reported: the intrinsics-pose cross-covariances."""
+    return _uncertainty_host(object_points, image_points, camera_matrix, dist_coeffs, rvecs, tvecs, view_status, inliers, 5,
+                             _project_full)
+
+
+# ---- on the device
+
+def uncertainty_workspace_bytes(batch: int) -> int:
+    """Bytes of device workspace ``calibration_uncertainty_pool`` needs (one size for both camera models)."""
+    from . import _lib
+    return int(_lib.lib().dcx_calibrate_uncertainty_workspace_bytes(int(batch)))
+
+
+def _device_or_upload(x, dev, dtype, shape, what):
+    """A device tensor is taken as it is (checked); anything else is an array to upload."""
+    import torch
+    if isinstance(x, torch.Tensor):
+        if x.device != dev or x.dtype != dtype or tuple(x.shape) != tuple(shape) or not x.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}")
+        return x
+    a = np.ascontiguousarray(np.asarray(x), dtype={torch.int32: np.int32, torch.float64: np.float64}[dtype])
+    if a.shape != tuple(shape):
+        raise ValueError(f"{what} must have shape {tuple(shape)}, not {a.shape}")
+    return torch.from_numpy(a).to(dev)
+
+
+def _slot_mask(inliers, packed, batch, pool, dev):
+    """``inliers`` -> the mask by pool slot the entry takes (uint8 [>= pool]) or None: a device tensor in the format of
+    ``calibrate_charuco_ransac_pool``'s ``out_inliers`` is taken as it is; per-view masks in SLOT order (``RobustCalibResult.inliers``
+    of that call) are laid at their views' slots (this reads the pool's head: a copy to the host)."""
+    import torch
+    if inliers is None:
+        return None
+    if isinstance(inliers, torch.Tensor):
+        if inliers.device != dev or inliers.dtype != torch.uint8 or inliers.numel() < pool or not inliers.is_contiguous():
+            raise ValueError(f"inliers must be a contiguous uint8 tensor of at least {pool} values on {dev}")
+        return inliers
+    if len(inliers) != batch:
+        raise ValueError(f"{batch} views but {len(inliers)} inlier masks")
+    counts, starts = views(packed[:layout(batch, pool).rows].cpu().numpy(), batch, pool)[:2]
+    mask = np.zeros(max(pool, 1), np.uint8)
+    for m, n, s0 in zip(inliers, counts.tolist(), starts.tolist()):
+        m = np.asarray(m).astype(np.uint8).ravel()
+        if n > 0 and s0 >= 0 and s0 + n <= pool:
+            if m.size != n:
+                raise ValueError(f"a view has {n} rows but its mask {m.size}")
+            mask[s0:s0 + n] = m
+    return torch.from_numpy(mask).to(dev)
+
+
+def _uncertainty_pool(model, n_dist, packed, batch, pool, refined, col_count, row_count, square_len, result_or_model, inliers,
+                      workspace, out):
+    import torch
+    from . import _lib
+    dev = packed.device
+    ptrs = pnp._pool_ptrs(packed, batch, pool, refined)
+    if _is_result(result_or_model):
+        K, dist, rv, tv, st, inliers = _model_args(result_or_model, None, None, None, None, inliers)
+        pose = np.zeros((batch, pnp.POSE_WORDS))
+        pose[:, :6] = _poses(rv, tv, batch)
+    else:
+        try:
+            K, dist, st, pose = result_or_model
+        except (TypeError, ValueError):
+            raise ValueError("result_or_model must be a CalibResult, a RobustCalibResult or (camera_matrix, dist_coeffs, view_status "
+                             "[B], pose [B, 8])") from None
+    theta = _free_model(K, dist, n_dist)
+    st_d = _device_or_upload(st, dev, torch.int32, (batch,), "view_status")
+    pose_d = _device_or_upload(pose, dev, torch.float64, (batch, pnp.POSE_WORDS), "pose")
+    mask = _slot_mask(inliers, packed, batch, pool, dev)
+    nbytes = uncertainty_workspace_bytes(batch)
+    ws = _dev.workspace(workspace, dev, nbytes, f"workspace must be a contiguous tensor of at least {nbytes} bytes on {dev}")
+    if out is None:
+        out = (torch.empty((COV_GLOBAL_WORDS,), dtype=torch.float64, device=dev),
+               torch.empty((batch, COV_POSE_WORDS), dtype=torch.float64, device=dev))
+    glob = _dev.tensor(out[0], dev, torch.float64, (COV_GLOBAL_WORDS,), f"out[0] must be a contiguous float64 tensor of "
+                       f"{COV_GLOBAL_WORDS} values on {dev}")
+    pcov = _dev.tensor(out[1], dev, torch.float64, (batch, COV_POSE_WORDS), f"out[1] must be a contiguous float64 tensor "
+                       f"[{batch}, {COV_POSE_WORDS}] on {dev}")
+    th = (_ctypes.c_double * 9)(*theta.tolist())
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().dcx_calibrate_uncertainty_pool(
+            *ptrs, int(batch), int(pool), int(col_count), int(row_count), float(square_len), model, th, st_d.data_ptr(),
+            pose_d.data_ptr(), None if mask is None else mask.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
+            glob.data_ptr(), pcov.data_ptr(), _lib.current_stream()), "dcx_calibrate_uncertainty_pool")
+    return glob, pcov
+
+
+def calibration_uncertainty_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len, result_or_model,
+                                 inliers=None, workspace=None, out=None):
+    """``calibration_uncertainty_host`` on the GPU, read in place from the corner pool the calibration read (the conventions of
+    ``calibrate_charuco_pool``) -> device tensors ``(global_ float64 [COV_GLOBAL_WORDS], pose_cov float64 [B, COV_POSE_WORDS])``,
+    which ``unpack_uncertainty`` turns into a ``CalibUncertainty``.
+
+    ``result_or_model``: the ``CalibResult`` / ``RobustCalibResult`` of a calibration of this pool, or ``(camera_matrix,
+    dist_coeffs, view_status [B] int32, pose [B, 8] float64)`` with the last two as arrays or as the device tensors the calibration
+    wrote.  ``inliers``: a uint8 device tensor by slot (``calibrate_charuco_ransac_pool``'s ``out_inliers``), or per-view masks in
+    slot order; None takes a ``RobustCalibResult``'s own.  ``workspace``: at least ``uncertainty_workspace_bytes(batch)`` bytes;
+    ``out``: the two output tensors.  Four launches on the current stream.  Given device tensors throughout the call neither
+    allocates nor synchronises and can be captured in a graph (a result tuple or per-view masks are uploaded first)."""
+    return _uncertainty_pool(CAMERA_PINHOLE, 5, packed, batch, pool, refined, col_count, row_count, square_len, result_or_model,
+                             inliers, workspace, out)
+
+
+def unpack_uncertainty(global_, pose_cov, n_intr: int = N_INTR) -> CalibUncertainty:
+    """The two tensors of ``calibration_uncertainty_pool`` (``n_intr`` = 9) or ``fisheye.calibration_uncertainty_fisheye_pool``
+    (8) -> ``CalibUncertainty`` on the host."""
+    g, p = global_.cpu().numpy(), pose_cov.cpu().numpy()
+    s2, dof, points, nviews, status = g[_COV_SIGMA2:_COV_SIGMA2 + 5]
+    return CalibUncertainty(int(status), float(s2), int(dof), int(points), int(nviews), g[_COV_STD:_COV_STD + n_intr].copy(),
+                            g[:n_intr * n_intr].reshape(n_intr, n_intr).copy(), p[:, 36:42].copy(), p[:, :36].reshape(-1, 6, 6).copy())
+
+
+def _uncertainty_device(model, n_dist, keypoints_list, col_count, row_count, square_len, result_or_model, inliers, device):
+    import torch
+    from .models._handles import require_cuda
+    dev = require_cuda(device)
+    packed, b, pool = _upload(keypoints_list, dev)
+    if inliers is None and _is_result(result_or_model):
+        inliers = getattr(result_or_model, "inliers", None)
+    if inliers is not None:                                    # the caller's row order -> the pool's (pack_keypoints' id sort)
+        if len(inliers) != b:
+            raise ValueError(f"{b} views but {len(inliers)} inlier masks")
+        by_slot = []
+        for kp, m in zip(keypoints_list, inliers):
+            m, order = np.asarray(m).astype(bool).ravel(), _pool_rows(kp)[1]
+            if m.size != order.size:
+                raise ValueError(f"a view has {order.size} rows but its mask {m.size}")
+            by_slot.append(m[order])
+        inliers = by_slot
+    with torch.cuda.device(dev):
+        g, p = _uncertainty_pool(model, n_dist, packed, b, pool, True, col_count, row_count, square_len, result_or_model, inliers,
+                                 None, None)
+        return unpack_uncertainty(g, p, 4 + n_dist)
+
+
+def calibration_uncertainty_device(keypoints_list: Sequence, col_count, row_count, square_len, result_or_model, inliers=None,
+                                   device="cuda") -> CalibUncertainty:
+    """``calibration_uncertainty_host`` on the GPU from ``infer_image``-format keypoint arrays ([x, y, id] rows), the views the
+    calibration was given -> ``CalibUncertainty``.  ``result_or_model`` as for ``calibration_uncertainty_pool``; ``inliers``: per
+    view a mask in the caller's row order (None takes a ``RobustCalibResult``'s own, as ``calibrate_charuco_ransac_device`` returns
+    them)."""
+    return _uncertainty_device(CAMERA_PINHOLE, 5, keypoints_list, col_count, row_count, square_len, result_or_model, inliers, device)

@@ -46,8 +46,9 @@ from typing import Sequence, Tuple
 import numpy as np
 
 from . import _dev, pnp
-from .calib import (CALIB_NO_VIEWS, RESULT_WORDS, CalibResult, _camera_matrix, _common_fields, _cv2_tuple, _image_size, _no_bad_id, _refine,
-                    _result, _upload, _view_outputs, _views)
+from .calib import (CALIB_NO_VIEWS, CAMERA_FISHEYE, RESULT_WORDS, CalibResult, CalibUncertainty, _camera_matrix, _common_fields, _cv2_tuple,
+                    _image_size, _no_bad_id, _refine, _result, _uncertainty_device, _uncertainty_host, _uncertainty_pool, _upload,
+                    _view_outputs, _views)
 from .corner_pool import pack_keypoints
 from .pnp import (LM_EPS, LM_MAX_ITER, PNP_BAD_ID, PNP_DEGENERATE, PNP_NONFINITE, PNP_OK, PNP_TOO_FEW, POSE_WORDS, _as_cv2,
                   _bad_id_error, _camera, _cholesky_solve, _init_pose, _pool_ptrs, _right_jacobian, _rodrigues, _skew, object_points,
@@ -68,7 +69,8 @@ __all__ = ["project_points_host", "undistort_points_host", "solve_pnp_fisheye_ho
            "solve_pnp_fisheye_ransac_host", "solve_pnp_fisheye_ransac_pool", "solve_pnp_fisheye_ransac_batch_device",
            "solve_pnp_fisheye_ransac_device",
            "calibrate_fisheye_pool", "calibrate_fisheye_device", "workspace_bytes", "undistort_rectify_map_fisheye_device",
-           "rectify_points_fisheye_pool", "SMALL_R", "CALIB_MAX_ITER"]
+           "rectify_points_fisheye_pool", "SMALL_R", "CALIB_MAX_ITER", "calibration_uncertainty_fisheye_host",
+           "calibration_uncertainty_fisheye_pool", "calibration_uncertainty_fisheye_device"]
 
 
 # ------------------------------------------------------------------------------------------------ arguments
@@ -567,6 +569,32 @@ def calibrate_fisheye_device(keypoints_list: Sequence, col_count, row_count, squ
     with torch.cuda.device(dev):
         r = calibrate_fisheye_pool(packed, b, pool, True, col_count, row_count, square_len, image_size, focal0)
     return _no_bad_id(r, col_count, row_count)
+
+
+# ------------------------------------------------------------------------------------------------ how well the model is determined
+
+def calibration_uncertainty_fisheye_host(object_points_, image_points, camera_matrix, dist_coeffs=None, rvecs=None, tvecs=None,
+                                         view_status=None, inliers=None) -> CalibUncertainty:
+    """``calib.calibration_uncertainty_host`` for the fisheye model: theta = (fx, fy, cx, cy, k1, k2, k3, k4), exactly 4
+    coefficients (ValueError otherwise), dof = 2 points - 8 - 6 views; everything else (arguments, the ``CalibResult`` in
+    ``camera_matrix``'s place, statuses, the dof convention) as said there."""
+    return _uncertainty_host(object_points_, image_points, camera_matrix, dist_coeffs, rvecs, tvecs, view_status, inliers, N_DIST,
+                             _project_full)
+
+
+def calibration_uncertainty_fisheye_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len,
+                                         result_or_model, inliers=None, workspace=None, out=None):
+    """``calib.calibration_uncertainty_pool`` for the fisheye model -> the same two device tensors;
+    ``calib.unpack_uncertainty(global_, pose_cov, N_INTR)`` unpacks them."""
+    return _uncertainty_pool(CAMERA_FISHEYE, N_DIST, packed, batch, pool, refined, col_count, row_count, square_len, result_or_model,
+                             inliers, workspace, out)
+
+
+def calibration_uncertainty_fisheye_device(keypoints_list: Sequence, col_count, row_count, square_len, result_or_model, inliers=None,
+                                           device="cuda") -> CalibUncertainty:
+    """``calib.calibration_uncertainty_device`` for the fisheye model."""
+    return _uncertainty_device(CAMERA_FISHEYE, N_DIST, keypoints_list, col_count, row_count, square_len, result_or_model, inliers,
+                               device)
 
 
 def undistort_rectify_map_fisheye_device(camera_matrix, dist_coeffs, R, P, width: int, height: int, device="cuda", out=None):

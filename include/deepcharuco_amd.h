@@ -608,6 +608,49 @@ int dcx_fisheye_rectify_points_pool(const int32_t* d_rows, const float* d_xy /* 
                                     const double* h_R9 /* NULL = identity */, const double* h_P12 /* NULL = K */,
                                     double* d_out /* [pool][2] */, void* stream);
 
+/* ---- how well a calibration is determined: the covariances of the intrinsics and of the views' poses -------------------------
+ * cv2.calibrateCameraExtended's stdDeviationsIntrinsics / stdDeviationsExtrinsics, for a model solved by dcx_calibrate_pool,
+ * dcx_calibrate_ransac_pool (model DCX_CAMERA_PINHOLE, h_theta [9] = fx fy cx cy k1 k2 p1 p2 k3) or dcx_fisheye_calibrate_pool
+ * (DCX_CAMERA_FISHEYE, h_theta [8] = fx fy cx cy k1 k2 k3 k4); another model code is DCX_E_ARG.  Pool arguments, object and image
+ * points as for dcx_calibrate_pool.  d_view_status [B]: a view takes part where it is DCX_PNP_OK; d_pose [B][8] as the calibrations
+ * write it (words 0..5 = rvec, tvec are read); d_mask [pool] by slot, the format of dcx_calibrate_ransac_pool's d_inliers, drops the
+ * rows whose byte is 0 (NULL: every row).  None of the inputs is written.  h_theta is read at the call and passed to the kernels
+ * by value.  All fp64; deepcharuco_amd/calib.py restates the definition (calibration_uncertainty_host).  With the undamped normal
+ * blocks of the calibration at (theta, poses), U_i 6x6, W_i NG x 6 per used view and V NG x NG over their kept rows:
+ *   S = V - sum W_i U_i^-1 W_i^T, Y_i = U_i^-1 W_i^T, dof = 2 points - NG - 6 views, sigma^2 = sum |r|^2 / dof (the textbook
+ *   estimator: residuals minus parameters; rescale by dof / another divisor for another convention),
+ *   cov_intrinsics = sigma^2 S^-1, cov_pose_i = sigma^2 (U_i^-1 + Y_i S^-1 Y_i^T), standard deviations = the diagonals' roots.
+ * d_global f64 [DCX_COV_GLOBAL_WORDS], every word written: cov_intrinsics NG x NG row major (row stride NG) from DCX_COV_COV, the NG
+ * standard deviations from DCX_COV_STD, then sigma^2, dof, points (kept rows of the used views), views used, the DCX_COV_* status
+ * and 0.  d_pose_cov f64 [B][DCX_COV_POSE_WORDS]: cov_pose_i 6x6 row major in the order rvec, tvec (cv2's), then its 6 standard
+ * deviations; zeros for a view that was not used.  Everything but the status, dof, points and views is zero unless DCX_COV_OK.
+ * A used view whose slots leave the pool counts as DCX_COV_SINGULAR (its slots are not read).
+ * d_workspace: dcx_calibrate_uncertainty_workspace_bytes(batch) bytes of device memory (DCX_E_WS if smaller; one size for both
+ * models); nothing is allocated and nothing but the workspace and the two outputs is written.  Four launches on `stream`, every
+ * sum in a fixed order, no atomics: two calls give the same bits.  UNLIKE the calibrations there is no host loop and NO
+ * synchronisation: the call can be captured in a graph.                                                                      */
+#define DCX_COV_OK        0
+#define DCX_COV_NO_VIEWS  1   /* no view is DCX_PNP_OK */
+#define DCX_COV_NO_DOF    2   /* dof <= 0: no more residuals than parameters */
+#define DCX_COV_SINGULAR  3   /* a U_i or S is not positive definite, a point is not in front of the camera, or a value is not finite */
+#define DCX_COV_COV       0   /* offsets into d_global */
+#define DCX_COV_STD       81
+#define DCX_COV_SIGMA2    90
+#define DCX_COV_DOF       91
+#define DCX_COV_POINTS    92
+#define DCX_COV_VIEWS     93
+#define DCX_COV_STATUS    94
+#define DCX_COV_GLOBAL_WORDS 96
+#define DCX_COV_POSE_WORDS   42
+size_t dcx_calibrate_uncertainty_workspace_bytes(int batch);
+int dcx_calibrate_uncertainty_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows,
+                                   const float* d_xy /* NULL = use integer rows x,y */, int batch, int pool,
+                                   int col_count, int row_count, double square_len, int model /* DCX_CAMERA_* */,
+                                   const double* h_theta /* [9] or [8] */, const int32_t* d_view_status /* [B] */,
+                                   const double* d_pose /* [B][8] */, const uint8_t* d_mask /* [pool] or NULL */,
+                                   void* d_workspace, size_t workspace_bytes, double* d_global /* [DCX_COV_GLOBAL_WORDS] */,
+                                   double* d_pose_cov /* [B][DCX_COV_POSE_WORDS] */, void* stream);
+
 /* ---- image resizing (cv2.resize): what stands in front of the detector ---------------------------------------------------------
  * dcx_resize_u8: batch frames d_src (u8, `channels` = 1 or 3 interleaved, rows `pitch` bytes apart, frames `frame_stride` bytes
  * apart, any base address: a cropped view costs nothing) -> d_out u8 [batch][out_h][out_w][channels], dense.  Channels are
