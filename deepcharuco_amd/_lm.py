@@ -1,6 +1,8 @@
 """The joint Levenberg-Marquardt driver of the two calibration definitions (``calib.py`` over 9 intrinsics, ``stereo.py`` over the 6
 rig parameters), one copy: g holds the global parameters, P [N, 6] one pose per unit (a view, a pair) that couples only to g.
-csrc/dcx_lm_dev.h is the same driver for the kernels; tests/test_lm_host.py walks both through the same scripts.
+csrc/dcx_lm_dev.h is the same driver for the kernels; tests/test_lm_host.py walks both through the same scripts.  ``refine_pose`` is
+the same loop over one pose alone (``pnp._solve``, ``fisheye._solve``, ``rig.rig_pose_host_full``), and the small Cholesky solve
+both loops use is here too: this module imports no solver.
 
 The CvLevMarq rules: damping diag * (1 + 10^lg), lg from -3; a step whose cost is not <= the cost before is rejected: lg + 1 and
 the same point is tried again, up to lg = 16; at 17 the step is taken whatever it costs (forced); an accepted or forced step takes
@@ -12,10 +14,30 @@ import math
 
 import numpy as np
 
-from .pnp import _cholesky_solve
-
 # the overall status: calib's CALIB_* and stereo's STEREO_* are these numbers (include/deepcharuco_amd.h)
 LM_OK, LM_NO_UNITS, LM_DEGENERATE, LM_NONFINITE = range(4)
+
+
+def _cholesky_solve(A: np.ndarray, b: np.ndarray):
+    """A x = b by the Cholesky factor of A, in the kernels' order of operations -> x, or None if A is not positive definite."""
+    n = A.shape[0]
+    L = np.zeros_like(A)
+    for i in range(n):
+        for j in range(i + 1):
+            s = A[i, j] - float(L[i, :j] @ L[j, :j])
+            if i == j:
+                if not s > 0:
+                    return None
+                L[i, i] = math.sqrt(s)
+            else:
+                L[i, j] = s / L[j, j]
+    y = np.zeros(n)
+    for i in range(n):
+        y[i] = (b[i] - float(L[i, :i] @ y[:i])) / L[i, i]
+    x = np.zeros(n)
+    for i in reversed(range(n)):
+        x[i] = (y[i] - float(L[i + 1:, i] @ x[i + 1:])) / L[i, i]
+    return x
 
 
 def schur_step(U, W, V, ga, gb, lg: int):
@@ -124,3 +146,40 @@ def refine(g, P, normal_blocks, trial_costs, total, stop_forced: bool, max_iter:
     if not math.isfinite(cost):
         return LM_DEGENERATE, g, P, None, iters, attempts
     return LM_OK, g, P, vc, iters, attempts
+
+
+def refine_pose(project, p, max_iter: int, eps: float):
+    """The rules above over one pose p (6) alone -> (status LM_*, p, cost, accepted steps).  ``project(p, jac)`` -> (residuals,
+    cost, J [2N, 6] with ``jac``); a cost of inf (a point behind its camera) rejects a trial like an increase.  A start whose cost
+    is not finite and a damped matrix that is not positive definite are DEGENERATE."""
+    res, cost, J = project(p, True)
+    if not math.isfinite(cost):
+        return LM_DEGENERATE, p, cost, 0
+    prev_cost, lg, iters = cost, -3, 0
+    while True:
+        JtJ, Jtr = J.T @ J, J.T @ res.ravel()
+        prev = p
+        while True:
+            A = JtJ.copy()
+            A[np.diag_indices(6)] *= 1.0 + 10.0 ** lg
+            x = _cholesky_solve(A, Jtr)
+            if x is None:
+                return LM_DEGENERATE, p, cost, iters
+            p = prev - x
+            _, cost, _ = project(p, False)
+            if not cost <= prev_cost:
+                lg += 1
+                if lg <= 16:
+                    continue
+            break
+        lg = max(lg - 1, -16)
+        iters += 1
+        if iters >= max_iter or math.sqrt(float((p - prev) @ (p - prev))) < eps * math.sqrt(float(prev @ prev)):
+            break
+        prev_cost = cost
+        res, cost, J = project(p, True)
+    if not np.isfinite(p).all() or math.isnan(cost):
+        return LM_NONFINITE, p, cost, iters
+    if not math.isfinite(cost):
+        return LM_DEGENERATE, p, cost, iters
+    return LM_OK, p, cost, iters

@@ -46,8 +46,7 @@ import numpy as np
 
 from . import _dev, _lm, pnp
 from .corner_pool import _caller_order, _pool_rows, layout, pack_keypoints, views
-from .pnp import (PNP_BAD_ID, PNP_DEGENERATE, PNP_NO_CONSENSUS, PNP_NONFINITE, PNP_OK, PNP_TOO_FEW, _bad_id_error, _homography,
-                  _project, _rodrigues, _solve)
+from .pnp import PNP_BAD_ID, PNP_DEGENERATE, PNP_NO_CONSENSUS, PNP_NONFINITE, PNP_OK, PNP_TOO_FEW, _bad_id_error, _homography, _solve
 
 # overall status (include/deepcharuco_amd.h); per-view statuses are pnp's PNP_*
 CALIB_OK, CALIB_NO_VIEWS, CALIB_DEGENERATE, CALIB_NONFINITE = _lm.LM_OK, _lm.LM_NO_UNITS, _lm.LM_DEGENERATE, _lm.LM_NONFINITE
@@ -100,18 +99,11 @@ def _project_full(obj: np.ndarray, img: np.ndarray, theta: np.ndarray, p: np.nda
     """Residuals (projected - observed, px), cost and with ``jac`` the 2N x 15 Jacobian [d/dtheta (9) | d/d(rvec, tvec) (6)].
     The residuals and the pose columns are ``pnp._project``'s; cost = inf when a point is not in front of the camera."""
     K, k = _camera_of(theta)
-    res, cost, Je = _project(obj, img, p, K, k, jac)
-    if not jac or res is None:
+    res, cost, Je, m = pnp._project_through(pnp._distort, obj, img, p, K, k, jac)
+    if Je is None:
         return res, cost, None
-    R = _rodrigues(p[:3])
-    X = obj @ R.T + p[3:]
-    iz = 1.0 / X[:, 2]
-    x, y = X[:, 0] * iz, X[:, 1] * iz
-    r2 = x * x + y * y
+    x, y, xd, yd, r2 = m[:5]
     r4, r6 = r2 * r2, r2 * r2 * r2
-    g = 1 + r2 * (k[0] + r2 * (k[1] + r2 * k[4]))
-    xd = x * g + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x)
-    yd = y * g + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y
     fx, fy = theta[0], theta[1]
     n = obj.shape[0]
     Ji = np.zeros((n, 2, N_INTR))

@@ -49,12 +49,9 @@ from . import _dev, pnp
 from .calib import (CALIB_NO_VIEWS, CAMERA_FISHEYE, RESULT_WORDS, CalibResult, CalibUncertainty, _camera_matrix, _common_fields, _cv2_tuple,
                     _image_size, _no_bad_id, _refine, _result, _uncertainty_device, _uncertainty_host, _uncertainty_pool, _upload,
                     _view_outputs, _views)
-from .corner_pool import pack_keypoints
-from .pnp import (LM_EPS, LM_MAX_ITER, PNP_BAD_ID, PNP_DEGENERATE, PNP_NONFINITE, PNP_OK, PNP_TOO_FEW, POSE_WORDS, _as_cv2,
-                  _bad_id_error, _camera, _cholesky_solve, _init_pose, _pool_ptrs, _right_jacobian, _rodrigues, _skew, object_points,
-                  unpack_poses)
-from .rectify import (MAP_BITS, MAP_LIMIT, MAP_SENTINEL, NEWTON_EPS, NEWTON_MAX_ITER, Rectification, _newcam, _projections,
-                      _rectifying_rotations, _rot, _rp_args)
+from .pnp import PNP_OK, PNP_TOO_FEW, POSE_WORDS, _as_cv2, _camera, _pool_ptrs, _rodrigues, object_points
+from .rectify import (NEWTON_EPS, NEWTON_MAX_ITER, Rectification, _map_device, _points_pool, _projections, _rectify_map,
+                      _rectify_points, _rectifying_rotations)
 
 SMALL_R = 1e-4                 # below it theta_d / r and its derivative come from their series
 SMALL_THETA_D = 1e-8           # below it tan(theta) / theta_d = 1 to the last bit
@@ -147,37 +144,12 @@ def undistort_points_host(pix, camera_matrix, dist_coeffs) -> np.ndarray:
 def _project(obj: np.ndarray, img: np.ndarray, p: np.ndarray, K: np.ndarray, k: np.ndarray, jac: bool, intr: bool = False):
     """``pnp._project`` through this model: residuals (projected - observed, px) at pose p, their cost, and with ``jac`` the
     2N x 6 Jacobian (with ``intr`` 2N x 14: the 8 intrinsic columns first).  cost = inf when a point is not in front of the camera."""
-    R = _rodrigues(p[:3])
-    X = obj @ R.T + p[3:]
-    if not (X[:, 2] > 0).all():
-        return None, math.inf, None
-    iz = 1.0 / X[:, 2]
-    a, b = X[:, 0] * iz, X[:, 1] * iz
+    res, cost, J, m = pnp._project_through(_distort, obj, img, p, K, k, jac)
+    if J is None or not intr:
+        return res, cost, J
+    a, b, xd, yd, tt, t2 = m[:6]
     fx, fy = K[0, 0], K[1, 1]
-    d = _distort(a, b, k, jac)
-    xd, yd, tt, t2 = d[:4]
-    res = np.stack([fx * xd + K[0, 2] - img[:, 0], fy * yd + K[1, 2] - img[:, 1]], 1)
-    cost = float((res * res).sum())
-    if not jac:
-        return res, cost, None
-    dxa, dxb, dyb = d[4:]
     n = obj.shape[0]
-    dab_dX = np.zeros((n, 2, 3))
-    dab_dX[:, 0, 0] = iz
-    dab_dX[:, 0, 2] = -a * iz
-    dab_dX[:, 1, 1] = iz
-    dab_dX[:, 1, 2] = -b * iz
-    duv_dab = np.empty((n, 2, 2))
-    duv_dab[:, 0, 0], duv_dab[:, 0, 1] = fx * dxa, fx * dxb
-    duv_dab[:, 1, 0], duv_dab[:, 1, 1] = fy * dxb, fy * dyb
-    duv_dX = duv_dab @ dab_dX
-    Jr = _right_jacobian(p[:3])
-    dX_dr = -np.einsum("ij,njk->nik", R, np.einsum("nij,jk->nik", np.stack([_skew(o) for o in obj]), Jr))
-    J = np.empty((n, 2, 6))
-    J[:, :, :3] = duv_dX @ dX_dr
-    J[:, :, 3:] = duv_dX
-    if not intr:
-        return res, cost, J.reshape(2 * n, 6)
     Ji = np.zeros((n, 2, N_INTR))
     Ji[:, 0, 0] = xd
     Ji[:, 1, 1] = yd
@@ -187,26 +159,14 @@ def _project(obj: np.ndarray, img: np.ndarray, p: np.ndarray, K: np.ndarray, k: 
     for j in range(4):
         pw = pw * t2
         Ji[:, 0, 4 + j], Ji[:, 1, 4 + j] = fx * (a * pw), fy * (b * pw)
-    return res, cost, np.concatenate([Ji.reshape(2 * n, N_INTR), J.reshape(2 * n, 6)], 1)
+    return res, cost, np.concatenate([Ji.reshape(2 * n, N_INTR), J], 1)
 
 
 def _project_q(Q: np.ndarray, img: np.ndarray, K: np.ndarray, k: np.ndarray, jac: bool):
     """``stereo._project_q`` through this model: points Q (n, 3) in the camera's frame -> residuals (projected - observed, px)
     and, with ``jac``, d(u, v)/dQ (n, 2, 3): ``_project``'s model and derivatives with the pose taken out, which is what a camera
     behind a rig transform needs.  Every Z must be positive (the caller checks)."""
-    iz = 1.0 / Q[:, 2]
-    a, b = Q[:, 0] * iz, Q[:, 1] * iz
-    fx, fy = K[0, 0], K[1, 1]
-    d = _distort(a, b, k, jac)
-    res = np.stack([fx * d[0] + K[0, 2] - img[:, 0], fy * d[1] + K[1, 2] - img[:, 1]], 1)
-    if not jac:
-        return res, None
-    dxa, dxb, dyb = d[4:]
-    a0, a1, b0, b1 = fx * dxa, fx * dxb, fy * dxb, fy * dyb
-    D = np.empty((Q.shape[0], 2, 3))
-    D[:, 0, 0], D[:, 0, 1], D[:, 0, 2] = a0 * iz, a1 * iz, -(a0 * a + a1 * b) * iz
-    D[:, 1, 0], D[:, 1, 1], D[:, 1, 2] = b0 * iz, b1 * iz, -(b0 * a + b1 * b) * iz
-    return res, D
+    return pnp._project_q_through(_distort, Q, img, K, k, jac)
 
 
 def project_points_host(object_points_, rvec, tvec, camera_matrix, dist_coeffs, jacobian: bool = False):
@@ -233,49 +193,7 @@ def project_points_host(object_points_, rvec, tvec, camera_matrix, dist_coeffs, 
 
 def _solve(obj: np.ndarray, img: np.ndarray, K: np.ndarray, k: np.ndarray) -> Tuple[int, np.ndarray]:
     """``pnp._solve`` through this model: obj (N, 3) board points, img (N, 2) pixels -> (status, pose[8])."""
-    pose = np.zeros(POSE_WORDS)
-    obj = obj.astype(np.float64)
-    img = img.astype(np.float64)
-    mn = _undistort(img, K, k)
-    if not np.isfinite(mn).all():                # a pixel outside the model
-        return PNP_DEGENERATE, pose
-    st, p = _init_pose(obj, mn)
-    if st != PNP_OK:
-        return st, pose
-    res, cost, J = _project(obj, img, p, K, k, True)
-    if not math.isfinite(cost):
-        return PNP_DEGENERATE, pose
-    prev_cost, lg, iters = cost, -3, 0
-    while True:
-        JtJ, Jtr = J.T @ J, J.T @ res.ravel()
-        prev = p
-        while True:
-            A = JtJ.copy()
-            A[np.diag_indices(6)] *= 1.0 + 10.0 ** lg
-            x = _cholesky_solve(A, Jtr)
-            if x is None:
-                return PNP_DEGENERATE, pose
-            p = prev - x
-            _, cost, _ = _project(obj, img, p, K, k, False)
-            if not cost <= prev_cost:
-                lg += 1
-                if lg <= 16:
-                    continue
-            break
-        lg = max(lg - 1, -16)
-        iters += 1
-        if iters >= LM_MAX_ITER or math.sqrt(float((p - prev) @ (p - prev))) < LM_EPS * math.sqrt(float(prev @ prev)):
-            break
-        prev_cost = cost
-        res, cost, J = _project(obj, img, p, K, k, True)
-    if not np.isfinite(p).all() or math.isnan(cost):
-        return PNP_NONFINITE, pose
-    if not math.isfinite(cost):
-        return PNP_DEGENERATE, pose
-    pose[:6] = p
-    pose[6] = math.sqrt(cost / obj.shape[0])
-    pose[7] = iters
-    return PNP_OK, pose
+    return pnp._solve_through(_undistort, _project, obj, img, K, k)
 
 
 def solve_pnp_fisheye_host_full(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs):
@@ -367,42 +285,13 @@ def undistort_rectify_map_fisheye_host(camera_matrix, dist_coeffs, R, P, width: 
     """``rectify.undistort_rectify_map_host`` with the ray through this model (``cv2.fisheye.initUndistortRectifyMap``) -> int32
     [height, width, 2] (x, y in 1/32 px, MAP_SENTINEL outside: q_z <= 0, a non-finite position or one beyond +-2^15 px); with
     ``quantised=False`` float64 source pixels, NaN outside."""
-    K, k = _camera(camera_matrix), _dist4(dist_coeffs)
-    Rm, f = _rot(R), _newcam(P, K)
-    width, height = int(width), int(height)
-    if width < 1 or height < 1:
-        raise ValueError("width and height must be >= 1")
-    x = ((np.arange(width, dtype=np.float64) - f[2]) / f[0])[None, :]
-    y = ((np.arange(height, dtype=np.float64) - f[3]) / f[1])[:, None]
-    qx = Rm[0, 0] * x + Rm[1, 0] * y + Rm[2, 0]
-    qy = Rm[0, 1] * x + Rm[1, 1] * y + Rm[2, 1]
-    qz = Rm[0, 2] * x + Rm[1, 2] * y + Rm[2, 2]
-    with np.errstate(all="ignore"):
-        xd, yd, _, _ = _distort(qx / qz, qy / qz, k, False)
-        mx, my = K[0, 0] * xd + K[0, 2], K[1, 1] * yd + K[1, 2]
-        ok = (qz > 0) & (np.abs(mx) <= MAP_LIMIT) & (np.abs(my) <= MAP_LIMIT)          # (NaN and inf compare false)
-    if not quantised:
-        return np.stack([np.where(ok, mx, np.nan), np.where(ok, my, np.nan)], 2)
-    scale = float(1 << MAP_BITS)
-    out = np.full((height, width, 2), MAP_SENTINEL, np.int32)
-    out[..., 0][ok] = np.rint(scale * mx[ok]).astype(np.int32)
-    out[..., 1][ok] = np.rint(scale * my[ok]).astype(np.int32)
-    return out
+    return _rectify_map(_distort, _camera(camera_matrix), _dist4(dist_coeffs), R, P, width, height, quantised)
 
 
 def rectify_points_fisheye_host(pix, camera_matrix, dist_coeffs, R=None, P=None) -> np.ndarray:
     """``rectify.rectify_points_host`` through this model (``cv2.fisheye.undistortPoints`` with R and P): pixels (N, 2) ->
     rectified pixels (N, 2), NaN rows for pixels outside the model or with a rotated z <= 0."""
-    K = _camera(camera_matrix)
-    f, Rm = _newcam(P, K), _rot(R)
-    n = undistort_points_host(pix, camera_matrix, dist_coeffs)
-    X = Rm[0, 0] * n[:, 0] + Rm[0, 1] * n[:, 1] + Rm[0, 2]
-    Y = Rm[1, 0] * n[:, 0] + Rm[1, 1] * n[:, 1] + Rm[1, 2]
-    Z = Rm[2, 0] * n[:, 0] + Rm[2, 1] * n[:, 1] + Rm[2, 2]
-    with np.errstate(all="ignore"):
-        out = np.stack([f[0] * (X / Z) + f[2], f[1] * (Y / Z) + f[3]], 1)
-    out[~(Z > 0)] = np.nan
-    return out
+    return _rectify_points(undistort_points_host, pix, camera_matrix, dist_coeffs, R, P)
 
 
 def stereo_rectify_fisheye_host(camera0, dist0, camera1, dist1, image_size, R, T, focal=None) -> Rectification:
@@ -433,94 +322,44 @@ def solve_pnp_fisheye_pool(packed, batch: int, pool: int, refined: bool, col_cou
                            dist_coeffs, out=None):
     """``pnp.solve_pnp_pool`` on a fisheye camera (``dcx_fisheye_solve_pnp_pool``): one launch on the current stream, no host sync,
     nothing allocated when ``out`` is given (capture-safe).  Returns device tensors ``(status int32 [B], pose float64 [B, 8])``."""
-    import torch
-    from . import _lib
-    dev = packed.device
-    ptrs = _pool_ptrs(packed, batch, pool, refined)
-    st, pose = (None, None) if out is None else out
-    msg = f"out must be (int32 [{batch}], float64 [{batch}, 8]) contiguous tensors on {dev}"
-    st = _dev.tensor(st, dev, torch.int32, (batch,), msg, "numel")
-    pose = _dev.tensor(pose, dev, torch.float64, (batch, POSE_WORDS), msg, "numel")
-    cam, dist = _camera_args(camera_matrix, dist_coeffs)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().dcx_fisheye_solve_pnp_pool(*ptrs, int(batch), int(pool), int(col_count), int(row_count),
-                                                         float(square_len), cam, dist, st.data_ptr(), pose.data_ptr(),
-                                                         _lib.current_stream()), "dcx_fisheye_solve_pnp_pool")
-    return st, pose
+    return pnp._solve_pool(_camera_args, "dcx_fisheye_solve_pnp_pool", packed, batch, pool, refined, col_count, row_count, square_len,
+                           camera_matrix, dist_coeffs, out)
 
 
 def solve_pnp_fisheye_batch_device(keypoints_list, col_count, row_count, square_len, camera_matrix, dist_coeffs, device="cuda"):
     """``solve_pnp_fisheye_host`` of every frame of a list of keypoint arrays in one launch -> list of ``(ret, rvec, tvec)``.
     IndexError if any frame with >= 4 points carries an id outside the board."""
-    import torch
-    from .models._handles import require_cuda
-    dev = require_cuda(device)
-    _camera_args(camera_matrix, dist_coeffs)                  # ValueError before anything is uploaded
-    if len(keypoints_list) == 0:
-        return []
-    packed, b, pool = pack_keypoints(keypoints_list, dev)
-    with torch.cuda.device(dev):
-        st, pose = solve_pnp_fisheye_pool(packed, b, pool, True, col_count, row_count, square_len, camera_matrix, dist_coeffs)
-        st_h, pose_h = st.cpu().numpy(), pose.cpu().numpy()
-    if (st_h == PNP_BAD_ID).any():
-        raise _bad_id_error(col_count, row_count)
-    return unpack_poses(st_h, pose_h)
+    return pnp._solve_batch_device(_camera_args, solve_pnp_fisheye_pool, keypoints_list, col_count, row_count, square_len,
+                                   camera_matrix, dist_coeffs, device)
 
 
 def solve_pnp_fisheye_device(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs, device="cuda"):
     """``solve_pnp_fisheye_host`` on the GPU -> ``(ret, rvec, tvec)``."""
-    kp = np.asarray(keypoints)
-    if kp.ndim != 2 or kp.shape[0] < 4:
-        _camera_args(camera_matrix, dist_coeffs)
-        return False, None, None
-    return solve_pnp_fisheye_batch_device([kp], col_count, row_count, square_len, camera_matrix, dist_coeffs, device)[0]
+    return pnp._solve_device(_camera_args, solve_pnp_fisheye_batch_device, keypoints, col_count, row_count, square_len,
+                             camera_matrix, dist_coeffs, device)
 
 
 def solve_pnp_fisheye_ransac_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len, camera_matrix,
                                   dist_coeffs, iterations=100, reproj_error=8.0, min_inliers=4, seed=0, out=None, workspace=None):
     """``pnp.solve_pnp_ransac_pool`` on a fisheye camera (``dcx_fisheye_solve_pnp_ransac_pool``): the same two launches, outputs
     ``(status, pose, info, inliers)``, ``out`` / ``workspace`` conventions (``pnp.ransac_workspace_bytes``) and capture safety."""
-    import torch
-    from . import _lib
-    dev = packed.device
-    iterations, reproj_error, min_inliers = pnp._ransac_args(iterations, reproj_error, min_inliers)
-    ptrs = _pool_ptrs(packed, batch, pool, refined)
-    need = pnp.ransac_workspace_bytes(batch, pool, iterations)
-    workspace = _dev.workspace(workspace, dev, need, f"workspace must be a contiguous tensor of at least {need} bytes on {dev}")
-    msg = f"out must be (int32 [{batch}], float64 [{batch}, 8], int32 [{batch}, 2], uint8 [{pool}]) contiguous tensors on {dev}"
-    want = ((torch.int32, (batch,)), (torch.float64, (batch, POSE_WORDS)), (torch.int32, (batch, 2)), (torch.uint8, (pool,)))
-    if out is not None and len(out) != 4:
-        raise ValueError(msg)
-    st, pose, info, inl = (_dev.tensor(t, dev, dt, shape, msg, "min", zeros=dt is torch.uint8)
-                           for t, (dt, shape) in zip(out or (None,) * 4, want))
-    cam, dist = _camera_args(camera_matrix, dist_coeffs)
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().dcx_fisheye_solve_pnp_ransac_pool(
-            *ptrs, int(batch), int(pool), int(col_count), int(row_count), float(square_len), cam, dist, iterations, reproj_error,
-            min_inliers, int(seed) & 0xFFFFFFFF, workspace.data_ptr(), workspace.numel() * workspace.element_size(), st.data_ptr(),
-            pose.data_ptr(), info.data_ptr(), inl.data_ptr(), _lib.current_stream()), "dcx_fisheye_solve_pnp_ransac_pool")
-    return st, pose, info, inl
+    return pnp._ransac_pool(_camera_args, "dcx_fisheye_solve_pnp_ransac_pool", packed, batch, pool, refined, col_count, row_count,
+                            square_len, camera_matrix, dist_coeffs, iterations, reproj_error, min_inliers, seed, out, workspace)
 
 
 def solve_pnp_fisheye_ransac_batch_device(keypoints_list, col_count, row_count, square_len, camera_matrix, dist_coeffs,
                                           iterations=100, reproj_error=8.0, min_inliers=4, seed=0, device="cuda", full=False):
     """``pnp.solve_pnp_ransac_batch_device`` on a fisheye camera -> list of ``(ret, rvec, tvec, inliers)`` (``full=True``: of
     ``(status, pose[8], inliers, winner)``), the masks in the caller's row order."""
-    return pnp.solve_pnp_ransac_batch_device(keypoints_list, col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations,
-                                             reproj_error, min_inliers, seed, device, full,
-                                             _model=(_camera_args, solve_pnp_fisheye_ransac_pool))
+    return pnp._ransac_batch_device(_camera_args, solve_pnp_fisheye_ransac_pool, keypoints_list, col_count, row_count, square_len,
+                                    camera_matrix, dist_coeffs, iterations, reproj_error, min_inliers, seed, device, full)
 
 
 def solve_pnp_fisheye_ransac_device(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations=100,
                                     reproj_error=8.0, min_inliers=4, seed=0, device="cuda"):
     """``pnp.solve_pnp_ransac_device`` on a fisheye camera -> ``(ret, rvec, tvec, inliers bool[N])``."""
-    kp = np.asarray(keypoints)
-    if kp.ndim != 2 or kp.shape[0] < 4:
-        _camera_args(camera_matrix, dist_coeffs)
-        pnp._ransac_args(iterations, reproj_error, min_inliers)
-        return False, None, None, np.zeros(kp.shape[0] if kp.ndim == 2 else 0, bool)
-    return solve_pnp_fisheye_ransac_batch_device([kp], col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations,
-                                                 reproj_error, min_inliers, seed, device)[0]
+    return pnp._ransac_device(_camera_args, solve_pnp_fisheye_ransac_batch_device, keypoints, col_count, row_count, square_len,
+                              camera_matrix, dist_coeffs, iterations, reproj_error, min_inliers, seed, device)
 
 
 def workspace_bytes(batch: int) -> int:
@@ -601,36 +440,11 @@ def undistort_rectify_map_fisheye_device(camera_matrix, dist_coeffs, R, P, width
     """``undistort_rectify_map_fisheye_host`` on the GPU -> int32 device tensor [height, width, 2] (``out``: that tensor,
     preallocated and contiguous); ``rectify.remap_device`` warps through it.  Enqueued on the current stream; nothing is allocated
     when ``out`` is given.  Equal to the host map except where 32 m is within rounding of a half-integer, and there by 1."""
-    import torch
-    from . import _lib
-    from .models._handles import require_cuda
-    cam, d = _camera_args(camera_matrix, dist_coeffs)
-    r, p = _rp_args(R, P, _camera(camera_matrix))
-    width, height = int(width), int(height)
-    if width < 1 or height < 1:
-        raise ValueError("width and height must be >= 1")
-    if out is None:
-        out = torch.empty((height, width, 2), dtype=torch.int32, device=require_cuda(device))
-    if out.dtype != torch.int32 or tuple(out.shape) != (height, width, 2) or not out.is_contiguous() or out.device.type != "cuda":
-        raise ValueError(f"out must be a contiguous int32 [{height}, {width}, 2] GPU tensor")
-    with torch.cuda.device(out.device):
-        _lib.check(_lib.lib().dcx_fisheye_undistort_rectify_map(cam, d, r, p, width, height, out.data_ptr(), _lib.current_stream()),
-                   "dcx_fisheye_undistort_rectify_map")
-    return out
+    return _map_device(_camera_args, "dcx_fisheye_undistort_rectify_map", camera_matrix, dist_coeffs, R, P, width, height, device, out)
 
 
 def rectify_points_fisheye_pool(packed, batch: int, pool: int, refined: bool, camera_matrix, dist_coeffs, R=None, P=None, out=None):
     """``rectify.rectify_points_pool`` through this model: every slot of a corner pool in rectified coordinates -> float64 device
     tensor [pool, 2] by slot; NaN where ``rectify_points_fisheye_host`` gives NaN.  Capture-safe when ``out`` is given."""
-    import torch
-    from . import _lib
-    dev = packed.device
-    batch, pool = int(batch), int(pool)
-    rows_p, xy_p = _pool_ptrs(packed, batch, pool, refined)[2:]
-    cam, d = _camera_args(camera_matrix, dist_coeffs)
-    r, p = _rp_args(R, P, _camera(camera_matrix))
-    out = _dev.tensor(out, dev, torch.float64, (pool, 2), f"out must be a contiguous float64 [{pool}, 2] tensor on {dev}", "numel")
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().dcx_fisheye_rectify_points_pool(rows_p, xy_p, pool, cam, d, r, p, out.data_ptr() if pool else None,
-                                                              _lib.current_stream()), "dcx_fisheye_rectify_points_pool")
-    return out
+    return _points_pool(_camera_args, "dcx_fisheye_rectify_points_pool", packed, batch, pool, refined, camera_matrix, dist_coeffs, R, P,
+                        out)

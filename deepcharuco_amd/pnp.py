@@ -36,8 +36,9 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
-from . import _dev
+from . import _dev, _lm
 from ._dev import pool_ptrs as _pool_ptrs
+from ._lm import _cholesky_solve     # noqa: F401  (its home is _lm.py; the name it has always had here stays importable)
 from .corner_pool import _caller_order, layout, pack_keypoints, views
 
 # per-frame status (include/deepcharuco_amd.h)
@@ -208,31 +209,41 @@ def _right_jacobian(r: np.ndarray) -> np.ndarray:
     return np.eye(3) - a * S + b * (S @ S)
 
 
-def _project(obj: np.ndarray, img: np.ndarray, p: np.ndarray, K: np.ndarray, k: np.ndarray, jac: bool):
-    """Residuals (projected - observed, px) at pose p = (rvec, tvec), their cost, and with ``jac`` the 2N x 6 Jacobian.
-    cost = inf when a point is not in front of the camera."""
-    R = _rodrigues(p[:3])
-    X = obj @ R.T + p[3:]
-    if not (X[:, 2] > 0).all():
-        return None, math.inf, None
-    iz = 1.0 / X[:, 2]
-    x, y = X[:, 0] * iz, X[:, 1] * iz
+def _distort(x, y, k, jac: bool):
+    """The rational + tangential model, the one text of it: normalised (x, y) (arrays) -> (xd, yd, r2) and with ``jac`` also
+    (dxd/dx, dxd/dy = dyd/dx, dyd/dy).  ``fisheye._distort`` is the other model in the same shape."""
     r2 = x * x + y * y
     num = 1 + r2 * (k[0] + r2 * (k[1] + r2 * k[4]))
     den = 1 + r2 * (k[5] + r2 * (k[6] + r2 * k[7]))
     g = num / den
     xd = x * g + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x)
     yd = y * g + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y
-    fx, fy = K[0, 0], K[1, 1]
-    res = np.stack([fx * xd + K[0, 2] - img[:, 0], fy * yd + K[1, 2] - img[:, 1]], 1)
-    cost = float((res * res).sum())
     if not jac:
-        return res, cost, None
+        return xd, yd, r2
     dg = ((k[0] + r2 * (2 * k[1] + 3 * k[4] * r2)) * den - num * (k[5] + r2 * (2 * k[6] + 3 * k[7] * r2))) / (den * den)
     dxd_dx = g + 2 * x * x * dg + 2 * k[2] * y + 6 * k[3] * x
     dxd_dy = 2 * x * y * dg + 2 * k[2] * x + 2 * k[3] * y
-    dyd_dx = 2 * x * y * dg + 2 * k[2] * x + 2 * k[3] * y
     dyd_dy = g + 2 * y * y * dg + 6 * k[2] * y + 2 * k[3] * x
+    return xd, yd, r2, dxd_dx, dxd_dy, dyd_dy
+
+
+def _project_through(distort, obj: np.ndarray, img: np.ndarray, p: np.ndarray, K: np.ndarray, k: np.ndarray, jac: bool):
+    """``_project`` for the camera model whose ``distort`` is given -> (residuals, cost, J, (x, y) + what ``distort`` returned, for
+    the caller that goes on to the intrinsic columns); the last three of ``distort``'s values with ``jac`` are the model's
+    d(xd, yd)/d(x, y) entries (a, b = the off-diagonal pair, d).  (None, inf, None, None) when a point is not in front."""
+    R = _rodrigues(p[:3])
+    X = obj @ R.T + p[3:]
+    if not (X[:, 2] > 0).all():
+        return None, math.inf, None, None
+    iz = 1.0 / X[:, 2]
+    x, y = X[:, 0] * iz, X[:, 1] * iz
+    m = distort(x, y, k, jac)
+    fx, fy = K[0, 0], K[1, 1]
+    res = np.stack([fx * m[0] + K[0, 2] - img[:, 0], fy * m[1] + K[1, 2] - img[:, 1]], 1)
+    cost = float((res * res).sum())
+    if not jac:
+        return res, cost, None, None
+    a, b, d = m[-3:]
     # d(x, y)/dX, X = (X, Y, Z) in the camera frame
     n = obj.shape[0]
     dxy_dX = np.zeros((n, 2, 3))
@@ -241,15 +252,40 @@ def _project(obj: np.ndarray, img: np.ndarray, p: np.ndarray, K: np.ndarray, k: 
     dxy_dX[:, 1, 1] = iz
     dxy_dX[:, 1, 2] = -y * iz
     duv_dxy = np.empty((n, 2, 2))
-    duv_dxy[:, 0, 0], duv_dxy[:, 0, 1] = fx * dxd_dx, fx * dxd_dy
-    duv_dxy[:, 1, 0], duv_dxy[:, 1, 1] = fy * dyd_dx, fy * dyd_dy
+    duv_dxy[:, 0, 0], duv_dxy[:, 0, 1] = fx * a, fx * b
+    duv_dxy[:, 1, 0], duv_dxy[:, 1, 1] = fy * b, fy * d
     duv_dX = duv_dxy @ dxy_dX                                        # (n, 2, 3)
     Jr = _right_jacobian(p[:3])
     dX_dr = -np.einsum("ij,njk->nik", R, np.einsum("nij,jk->nik", np.stack([_skew(o) for o in obj]), Jr))
     J = np.empty((n, 2, 6))
     J[:, :, :3] = duv_dX @ dX_dr
     J[:, :, 3:] = duv_dX
-    return res, cost, J.reshape(2 * n, 6)
+    return res, cost, J.reshape(2 * n, 6), (x, y) + m
+
+
+def _project(obj: np.ndarray, img: np.ndarray, p: np.ndarray, K: np.ndarray, k: np.ndarray, jac: bool):
+    """Residuals (projected - observed, px) at pose p = (rvec, tvec), their cost, and with ``jac`` the 2N x 6 Jacobian.
+    cost = inf when a point is not in front of the camera."""
+    return _project_through(_distort, obj, img, p, K, k, jac)[:3]
+
+
+def _project_q_through(distort, Q: np.ndarray, img: np.ndarray, K: np.ndarray, k: np.ndarray, jac: bool):
+    """Points Q (n, 3) in a camera's frame -> residuals (projected - observed, px) and, with ``jac``, d(u, v)/dQ (n, 2, 3):
+    ``_project_through``'s model and derivatives with the pose taken out (and d(u, v)/dQ by its spelt-out products, not that
+    function's matrix product: the two round differently).  Every Z must be positive (the caller checks)."""
+    iz = 1.0 / Q[:, 2]
+    x, y = Q[:, 0] * iz, Q[:, 1] * iz
+    m = distort(x, y, k, jac)
+    fx, fy = K[0, 0], K[1, 1]
+    res = np.stack([fx * m[0] + K[0, 2] - img[:, 0], fy * m[1] + K[1, 2] - img[:, 1]], 1)
+    if not jac:
+        return res, None
+    a, b, d = m[-3:]
+    a0, a1, b0, b1 = fx * a, fx * b, fy * b, fy * d
+    D = np.empty((Q.shape[0], 2, 3))
+    D[:, 0, 0], D[:, 0, 1], D[:, 0, 2] = a0 * iz, a1 * iz, -(a0 * x + a1 * y) * iz
+    D[:, 1, 0], D[:, 1, 1], D[:, 1, 2] = b0 * iz, b1 * iz, -(b0 * x + b1 * y) * iz
+    return res, D
 
 
 def _homography(obj: np.ndarray, mn: np.ndarray) -> Tuple[int, Optional[np.ndarray], np.ndarray]:
@@ -314,69 +350,33 @@ def _init_pose(obj: np.ndarray, mn: np.ndarray) -> Tuple[int, Optional[np.ndarra
     return _pose_of_homography(H, mc)
 
 
-def _cholesky_solve(A: np.ndarray, b: np.ndarray) -> Optional[np.ndarray]:
-    n = A.shape[0]
-    L = np.zeros_like(A)
-    for i in range(n):
-        for j in range(i + 1):
-            s = A[i, j] - float(L[i, :j] @ L[j, :j])
-            if i == j:
-                if not s > 0:
-                    return None
-                L[i, i] = math.sqrt(s)
-            else:
-                L[i, j] = s / L[j, j]
-    y = np.zeros(n)
-    for i in range(n):
-        y[i] = (b[i] - float(L[i, :i] @ y[:i])) / L[i, i]
-    x = np.zeros(n)
-    for i in reversed(range(n)):
-        x[i] = (y[i] - float(L[i + 1:, i] @ x[i + 1:])) / L[i, i]
-    return x
+LM_STATUS = (PNP_OK, None, PNP_DEGENERATE, PNP_NONFINITE)      # ``_lm.refine_pose``'s LM_* status -> this module's
 
 
-def _solve(obj: np.ndarray, img: np.ndarray, K: np.ndarray, k: np.ndarray) -> Tuple[int, np.ndarray]:
-    """obj (N,3) float32 board points, img (N,2) float32 pixels -> (status, pose[8])."""
+def _solve_through(undistort, project, obj: np.ndarray, img: np.ndarray, K: np.ndarray, k: np.ndarray) -> Tuple[int, np.ndarray]:
+    """``_solve`` for the camera model whose (undistort, project) are given: the planar start on the undistorted points, then
+    ``_lm.refine_pose`` on the model's reprojection error."""
     pose = np.zeros(POSE_WORDS)
     obj = obj.astype(np.float64)
     img = img.astype(np.float64)
-    st, p = _init_pose(obj, _undistort(img, K, k))
+    mn = undistort(img, K, k)
+    if not np.isfinite(mn).all():                # a pixel outside the fisheye model (a pinhole's non-finite point would fail the
+        return PNP_DEGENERATE, pose              # homography's rank test with this same answer)
+    st, p = _init_pose(obj, mn)
     if st != PNP_OK:
         return st, pose
-    res, cost, J = _project(obj, img, p, K, k, True)
-    if not math.isfinite(cost):
-        return PNP_DEGENERATE, pose
-    prev_cost, lg, iters = cost, -3, 0
-    while True:
-        JtJ, Jtr = J.T @ J, J.T @ res.ravel()
-        prev = p
-        while True:
-            A = JtJ.copy()
-            A[np.diag_indices(6)] *= 1.0 + 10.0 ** lg
-            x = _cholesky_solve(A, Jtr)
-            if x is None:
-                return PNP_DEGENERATE, pose
-            p = prev - x
-            _, cost, _ = _project(obj, img, p, K, k, False)
-            if not cost <= prev_cost:           # (a point behind the camera: cost = inf, rejected like an increase)
-                lg += 1
-                if lg <= 16:
-                    continue
-            break
-        lg = max(lg - 1, -16)
-        iters += 1
-        if iters >= LM_MAX_ITER or math.sqrt(float((p - prev) @ (p - prev))) < LM_EPS * math.sqrt(float(prev @ prev)):
-            break
-        prev_cost = cost
-        res, cost, J = _project(obj, img, p, K, k, True)
-    if not np.isfinite(p).all() or math.isnan(cost):
-        return PNP_NONFINITE, pose
-    if not math.isfinite(cost):
-        return PNP_DEGENERATE, pose
+    st, p, cost, iters = _lm.refine_pose(lambda q, jac: project(obj, img, q, K, k, jac), p, LM_MAX_ITER, LM_EPS)
+    if st != _lm.LM_OK:
+        return LM_STATUS[st], pose
     pose[:6] = p
     pose[6] = math.sqrt(cost / obj.shape[0])
     pose[7] = iters
     return PNP_OK, pose
+
+
+def _solve(obj: np.ndarray, img: np.ndarray, K: np.ndarray, k: np.ndarray) -> Tuple[int, np.ndarray]:
+    """obj (N,3) float32 board points, img (N,2) float32 pixels -> (status, pose[8])."""
+    return _solve_through(_undistort, _project, obj, img, K, k)
 
 
 def solve_pnp_host_full(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs):
@@ -588,13 +588,24 @@ def _camera_args(camera_matrix, dist_coeffs):
     return (_ctypes.c_double * 9)(*K.ravel().tolist()), (_ctypes.c_double * 8)(*k.tolist()), n
 
 
-def _launch(counts_p, starts_p, rows_p, xy_p, batch, pool, col_count, row_count, square_len, camera_matrix, dist_coeffs,
-            status_p, pose_p):
+# Every wrapper below has one body for both camera models.  A model is given as what differs: its ``_camera_args`` (this module's
+# returns (camera9, dist8, n_dist), ``fisheye``'s (camera9, dist4): the arguments its C entries take at that place, in that order)
+# and the C entry, or the model's own wrapper one level down.
+
+def _solve_pool(camera_args, entry, packed, batch, pool, refined, col_count, row_count, square_len, camera_matrix, dist_coeffs, out):
+    import torch
     from . import _lib
-    cam, dist, n_dist = _camera_args(camera_matrix, dist_coeffs)
-    _lib.check(_lib.lib().dcx_solve_pnp_pool(counts_p, starts_p, rows_p, xy_p, int(batch), int(pool), int(col_count),
-                                             int(row_count), float(square_len), cam, dist, n_dist, status_p, pose_p,
-                                             _lib.current_stream()), "dcx_solve_pnp_pool")
+    dev = packed.device
+    ptrs = _pool_ptrs(packed, batch, pool, refined)
+    st, pose = (None, None) if out is None else out
+    msg = f"out must be (int32 [{batch}], float64 [{batch}, 8]) contiguous tensors on {dev}"
+    st = _dev.tensor(st, dev, torch.int32, (batch,), msg, "numel")
+    pose = _dev.tensor(pose, dev, torch.float64, (batch, POSE_WORDS), msg, "numel")
+    cam = camera_args(camera_matrix, dist_coeffs)
+    with torch.cuda.device(dev):
+        _lib.check(getattr(_lib.lib(), entry)(*ptrs, int(batch), int(pool), int(col_count), int(row_count), float(square_len), *cam,
+                                              st.data_ptr(), pose.data_ptr(), _lib.current_stream()), entry)
+    return st, pose
 
 
 def solve_pnp_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len, camera_matrix, dist_coeffs,
@@ -603,16 +614,8 @@ def solve_pnp_pool(packed, batch: int, pool: int, refined: bool, col_count, row_
     stream, no host sync, nothing allocated when ``out`` is given (capture-safe).  ``refined``: the pool carries RefineNet's xy
     (else the integer rows' x, y are the image points).  Returns device tensors ``(status int32 [B], pose float64 [B, 8])``
     (``out`` = that pair, preallocated); ``unpack_poses`` turns them into per-frame ``(ret, rvec, tvec)``."""
-    import torch
-    dev = packed.device
-    ptrs = _pool_ptrs(packed, batch, pool, refined)
-    st, pose = (None, None) if out is None else out
-    msg = f"out must be (int32 [{batch}], float64 [{batch}, 8]) contiguous tensors on {dev}"
-    st = _dev.tensor(st, dev, torch.int32, (batch,), msg, "numel")
-    pose = _dev.tensor(pose, dev, torch.float64, (batch, POSE_WORDS), msg, "numel")
-    with torch.cuda.device(dev):
-        _launch(*ptrs, batch, pool, col_count, row_count, square_len, camera_matrix, dist_coeffs, st.data_ptr(), pose.data_ptr())
-    return st, pose
+    return _solve_pool(_camera_args, "dcx_solve_pnp_pool", packed, batch, pool, refined, col_count, row_count, square_len,
+                       camera_matrix, dist_coeffs, out)
 
 
 def unpack_poses(status, pose) -> List[tuple]:
@@ -625,32 +628,42 @@ def unpack_poses(status, pose) -> List[tuple]:
     return [_as_cv2(int(s), p) for s, p in zip(status.tolist(), pose)]
 
 
-def solve_pnp_batch_device(keypoints_list, col_count, row_count, square_len, camera_matrix, dist_coeffs, device="cuda"):
-    """``solve_pnp`` of every frame of a list of keypoint arrays in one kernel launch -> list of ``(ret, rvec, tvec)`` like
-    ``solve_pnp_batch``'s (without OpenCV).  IndexError if any frame with >= 4 points carries an id outside the board."""
+def _solve_batch_device(camera_args, pool_call, keypoints_list, col_count, row_count, square_len, camera_matrix, dist_coeffs, device):
     import torch
     from .models._handles import require_cuda
     dev = require_cuda(device)
-    _camera_args(camera_matrix, dist_coeffs)                  # ValueError before anything is uploaded
+    camera_args(camera_matrix, dist_coeffs)                   # ValueError before anything is uploaded
     if len(keypoints_list) == 0:
         return []
     packed, b, pool = pack_keypoints(keypoints_list, dev)
     with torch.cuda.device(dev):
-        st, pose = solve_pnp_pool(packed, b, pool, True, col_count, row_count, square_len, camera_matrix, dist_coeffs)
+        st, pose = pool_call(packed, b, pool, True, col_count, row_count, square_len, camera_matrix, dist_coeffs)
         st_h, pose_h = st.cpu().numpy(), pose.cpu().numpy()
     if (st_h == PNP_BAD_ID).any():
         raise _bad_id_error(col_count, row_count)
     return unpack_poses(st_h, pose_h)
 
 
+def solve_pnp_batch_device(keypoints_list, col_count, row_count, square_len, camera_matrix, dist_coeffs, device="cuda"):
+    """``solve_pnp`` of every frame of a list of keypoint arrays in one kernel launch -> list of ``(ret, rvec, tvec)`` like
+    ``solve_pnp_batch``'s (without OpenCV).  IndexError if any frame with >= 4 points carries an id outside the board."""
+    return _solve_batch_device(_camera_args, solve_pnp_pool, keypoints_list, col_count, row_count, square_len, camera_matrix,
+                               dist_coeffs, device)
+
+
+def _solve_device(camera_args, batch_call, keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs, device):
+    kp = np.asarray(keypoints)
+    if kp.ndim != 2 or kp.shape[0] < 4:
+        camera_args(camera_matrix, dist_coeffs)
+        return False, None, None
+    return batch_call([kp], col_count, row_count, square_len, camera_matrix, dist_coeffs, device)[0]
+
+
 def solve_pnp_device(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs, device="cuda"):
     """``solve_pnp`` (inference.py:15-29) on the GPU, without OpenCV: same signature, returns ``(ret, rvec, tvec)`` shaped like
     cv2's (bool, (3,1) float64, (3,1) float64); ``(False, None, None)`` for fewer than 4 points or a refused input."""
-    kp = np.asarray(keypoints)
-    if kp.ndim != 2 or kp.shape[0] < 4:
-        _camera_args(camera_matrix, dist_coeffs)
-        return False, None, None
-    return solve_pnp_batch_device([kp], col_count, row_count, square_len, camera_matrix, dist_coeffs, device)[0]
+    return _solve_device(_camera_args, solve_pnp_batch_device, keypoints, col_count, row_count, square_len, camera_matrix,
+                         dist_coeffs, device)
 
 
 # ------------------------------------------------------------------------------------------------ RANSAC on the device
@@ -664,13 +677,8 @@ def ransac_workspace_bytes(batch: int, pool: int, iterations: int = 100) -> int:
     return n
 
 
-def solve_pnp_ransac_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len, camera_matrix,
-                          dist_coeffs, iterations=100, reproj_error=8.0, min_inliers=4, seed=0, out=None, workspace=None):
-    """``solve_pnp_pool`` behind a consensus search (``solve_pnp_ransac_host_full`` is the definition): two kernel launches on the
-    current stream, no host sync, nothing allocated when ``out`` and ``workspace`` are given (capture-safe).  Returns device
-    tensors ``(status int32 [B], pose float64 [B, 8], info int32 [B, 2] = inlier count and winning hypothesis (-1: none),
-    inliers uint8 [pool] in slot order)``; ``out`` = that tuple, ``workspace`` = a contiguous device tensor of at least
-    ``ransac_workspace_bytes(batch, pool, iterations)`` bytes.  Slots of the mask that belong to no frame are not written."""
+def _ransac_pool(camera_args, entry, packed, batch, pool, refined, col_count, row_count, square_len, camera_matrix, dist_coeffs,
+                 iterations, reproj_error, min_inliers, seed, out, workspace):
     import torch
     from . import _lib
     dev = packed.device
@@ -684,13 +692,24 @@ def solve_pnp_ransac_pool(packed, batch: int, pool: int, refined: bool, col_coun
         raise ValueError(msg)
     st, pose, info, inl = (_dev.tensor(t, dev, dt, shape, msg, "min", zeros=dt is torch.uint8)
                            for t, (dt, shape) in zip(out or (None,) * 4, want))
-    cam, dist, n_dist = _camera_args(camera_matrix, dist_coeffs)
+    cam = camera_args(camera_matrix, dist_coeffs)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().dcx_solve_pnp_ransac_pool(
-            *ptrs, int(batch), int(pool), int(col_count), int(row_count), float(square_len), cam, dist, n_dist, iterations,
+        _lib.check(getattr(_lib.lib(), entry)(
+            *ptrs, int(batch), int(pool), int(col_count), int(row_count), float(square_len), *cam, iterations,
             reproj_error, min_inliers, int(seed) & _M32, workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-            st.data_ptr(), pose.data_ptr(), info.data_ptr(), inl.data_ptr(), _lib.current_stream()), "dcx_solve_pnp_ransac_pool")
+            st.data_ptr(), pose.data_ptr(), info.data_ptr(), inl.data_ptr(), _lib.current_stream()), entry)
     return st, pose, info, inl
+
+
+def solve_pnp_ransac_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len, camera_matrix,
+                          dist_coeffs, iterations=100, reproj_error=8.0, min_inliers=4, seed=0, out=None, workspace=None):
+    """``solve_pnp_pool`` behind a consensus search (``solve_pnp_ransac_host_full`` is the definition): two kernel launches on the
+    current stream, no host sync, nothing allocated when ``out`` and ``workspace`` are given (capture-safe).  Returns device
+    tensors ``(status int32 [B], pose float64 [B, 8], info int32 [B, 2] = inlier count and winning hypothesis (-1: none),
+    inliers uint8 [pool] in slot order)``; ``out`` = that tuple, ``workspace`` = a contiguous device tensor of at least
+    ``ransac_workspace_bytes(batch, pool, iterations)`` bytes.  Slots of the mask that belong to no frame are not written."""
+    return _ransac_pool(_camera_args, "dcx_solve_pnp_ransac_pool", packed, batch, pool, refined, col_count, row_count, square_len,
+                        camera_matrix, dist_coeffs, iterations, reproj_error, min_inliers, seed, out, workspace)
 
 
 def unpack_ransac(status, pose, inliers, counts, starts, ids=None) -> List[tuple]:
@@ -709,16 +728,11 @@ def unpack_ransac(status, pose, inliers, counts, starts, ids=None) -> List[tuple
     return out
 
 
-def solve_pnp_ransac_batch_device(keypoints_list, col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations=100,
-                                  reproj_error=8.0, min_inliers=4, seed=0, device="cuda", full=False, _model=None):
-    """``solve_pnp_ransac_host`` of every frame of a list of keypoint arrays on the GPU -> list of
-    ``(ret, rvec, tvec, inliers)``, ``inliers`` a bool array in the caller's row order.  ``full=True``: list of
-    ``(status, pose[8], inliers, winner)`` like ``solve_pnp_ransac_host_full``.  IndexError if any frame with >= 4 points carries
-    an id outside the board.  (``_model``: another camera model's (camera_args, pool call), ``fisheye``'s.)"""
+def _ransac_batch_device(camera_args, pool_call, keypoints_list, col_count, row_count, square_len, camera_matrix, dist_coeffs,
+                         iterations, reproj_error, min_inliers, seed, device, full):
     import torch
     from .models._handles import require_cuda
     dev = require_cuda(device)
-    camera_args, pool_call = _model or (_camera_args, solve_pnp_ransac_pool)
     camera_args(camera_matrix, dist_coeffs)                   # ValueError before anything is uploaded
     _ransac_args(iterations, reproj_error, min_inliers)
     if len(keypoints_list) == 0:
@@ -737,14 +751,30 @@ def solve_pnp_ransac_batch_device(keypoints_list, col_count, row_count, square_l
     return out
 
 
+def solve_pnp_ransac_batch_device(keypoints_list, col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations=100,
+                                  reproj_error=8.0, min_inliers=4, seed=0, device="cuda", full=False):
+    """``solve_pnp_ransac_host`` of every frame of a list of keypoint arrays on the GPU -> list of
+    ``(ret, rvec, tvec, inliers)``, ``inliers`` a bool array in the caller's row order.  ``full=True``: list of
+    ``(status, pose[8], inliers, winner)`` like ``solve_pnp_ransac_host_full``.  IndexError if any frame with >= 4 points carries
+    an id outside the board."""
+    return _ransac_batch_device(_camera_args, solve_pnp_ransac_pool, keypoints_list, col_count, row_count, square_len, camera_matrix,
+                                dist_coeffs, iterations, reproj_error, min_inliers, seed, device, full)
+
+
+def _ransac_device(camera_args, batch_call, keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations,
+                   reproj_error, min_inliers, seed, device):
+    kp = np.asarray(keypoints)
+    if kp.ndim != 2 or kp.shape[0] < 4:
+        camera_args(camera_matrix, dist_coeffs)
+        _ransac_args(iterations, reproj_error, min_inliers)
+        return False, None, None, np.zeros(kp.shape[0] if kp.ndim == 2 else 0, bool)
+    return batch_call([kp], col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations, reproj_error, min_inliers,
+                      seed, device)[0]
+
+
 def solve_pnp_ransac_device(keypoints, col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations=100,
                             reproj_error=8.0, min_inliers=4, seed=0, device="cuda"):
     """``cv2.solvePnPRansac``'s role on the GPU, without OpenCV -> ``(ret, rvec, tvec, inliers bool[N])``;
     ``(False, None, None, all False)`` for fewer than 4 points, a refused input or no consensus."""
-    kp = np.asarray(keypoints)
-    if kp.ndim != 2 or kp.shape[0] < 4:
-        _camera_args(camera_matrix, dist_coeffs)
-        _ransac_args(iterations, reproj_error, min_inliers)
-        return False, None, None, np.zeros(kp.shape[0] if kp.ndim == 2 else 0, bool)
-    return solve_pnp_ransac_batch_device([kp], col_count, row_count, square_len, camera_matrix, dist_coeffs, iterations,
-                                         reproj_error, min_inliers, seed, device)[0]
+    return _ransac_device(_camera_args, solve_pnp_ransac_batch_device, keypoints, col_count, row_count, square_len, camera_matrix,
+                          dist_coeffs, iterations, reproj_error, min_inliers, seed, device)

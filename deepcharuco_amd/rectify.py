@@ -49,7 +49,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from . import _dev, pnp
-from .pnp import _camera, _dist, _rodrigues, _rvec_of
+from .pnp import _camera, _dist, _distort, _rodrigues, _rvec_of
 
 MAP_SENTINEL = int(np.iinfo(np.int32).min)     # both components of a map entry that is outside
 MAP_BITS = 5                                   # fractional bits of a map entry
@@ -75,22 +75,6 @@ class Rectification(NamedTuple):
 
 # ------------------------------------------------------------------------------------------------ the fp64 steps
 
-def _distort_jac(x, y, k):
-    """Normalised (x, y) -> distorted normalised (xd, yd) and the Jacobian entries (dxd/dx, dxd/dy = dyd/dx, dyd/dy): the model
-    and derivatives of ``pnp._project``."""
-    r2 = x * x + y * y
-    num = 1 + r2 * (k[0] + r2 * (k[1] + r2 * k[4]))
-    den = 1 + r2 * (k[5] + r2 * (k[6] + r2 * k[7]))
-    g = num / den
-    xd = x * g + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x)
-    yd = y * g + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y
-    dg = ((k[0] + r2 * (2 * k[1] + 3 * k[4] * r2)) * den - num * (k[5] + r2 * (2 * k[6] + 3 * k[7] * r2))) / (den * den)
-    a = g + 2 * x * x * dg + 2 * k[2] * y + 6 * k[3] * x
-    b = 2 * x * y * dg + 2 * k[2] * x + 2 * k[3] * y
-    d = g + 2 * y * y * dg + 6 * k[2] * y + 2 * k[3] * x
-    return xd, yd, a, b, d
-
-
 def undistort_points_newton(pix, camera_matrix, dist_coeffs) -> np.ndarray:
     """Pixels (N, 2) -> normalised undistorted coordinates (N, 2) by Newton (module docstring, step 3); NaN rows where it has not
     converged within 20 steps."""
@@ -102,7 +86,7 @@ def undistort_points_newton(pix, camera_matrix, dist_coeffs) -> np.ndarray:
     done = np.zeros(x.shape[0], bool)
     with np.errstate(all="ignore"):
         for _ in range(NEWTON_MAX_ITER):
-            xd, yd, a, b, d = _distort_jac(x, y, k)
+            xd, yd, _, a, b, d = _distort(x, y, k, True)
             ex, ey = xd - x0, yd - y0
             det = a * d - b * b
             sx, sy = (d * ex - b * ey) / det, (a * ey - b * ex) / det
@@ -138,9 +122,10 @@ def _newcam(P, K) -> np.ndarray:
     return np.array([P[0, 0], P[1, 1], P[0, 2], P[1, 2]])
 
 
-def _rectify_normalised(pix, camera_matrix, dist_coeffs, R) -> np.ndarray:
-    """Pixels -> R undistort(pixel) divided by its z: (N, 2), NaN where Newton has not converged or z <= 0."""
-    n = undistort_points_newton(pix, camera_matrix, dist_coeffs)
+def _rectify_normalised(pix, camera_matrix, dist_coeffs, R, undistort=undistort_points_newton) -> np.ndarray:
+    """Pixels -> R undistort(pixel) divided by its z: (N, 2), NaN where Newton has not converged or z <= 0.  ``undistort``: the
+    camera model's (pixels, camera_matrix, dist_coeffs) -> normalised points, NaN rows where there is none."""
+    n = undistort(pix, camera_matrix, dist_coeffs)
     R = _rot(R)
     X = R[0, 0] * n[:, 0] + R[0, 1] * n[:, 1] + R[0, 2]
     Y = R[1, 0] * n[:, 0] + R[1, 1] * n[:, 1] + R[1, 2]
@@ -151,12 +136,17 @@ def _rectify_normalised(pix, camera_matrix, dist_coeffs, R) -> np.ndarray:
     return out
 
 
-def rectify_points_host(pix, camera_matrix, dist_coeffs, R=None, P=None) -> np.ndarray:
-    """The definition of step 3: pixels (N, 2) -> rectified pixels (N, 2), float64, NaN rows where undefined."""
+def _rectify_points(undistort, pix, camera_matrix, dist_coeffs, R, P) -> np.ndarray:
+    """Step 3 for the camera model whose ``undistort`` is given (``_rectify_normalised``)."""
     K = _camera(camera_matrix)
     f = _newcam(P, K)
-    n = _rectify_normalised(pix, camera_matrix, dist_coeffs, R)
+    n = _rectify_normalised(pix, camera_matrix, dist_coeffs, R, undistort)
     return np.stack([f[0] * n[:, 0] + f[2], f[1] * n[:, 1] + f[3]], 1)
+
+
+def rectify_points_host(pix, camera_matrix, dist_coeffs, R=None, P=None) -> np.ndarray:
+    """The definition of step 3: pixels (N, 2) -> rectified pixels (N, 2), float64, NaN rows where undefined."""
+    return _rectify_points(undistort_points_newton, pix, camera_matrix, dist_coeffs, R, P)
 
 
 def _border_pixels(W: int, H: int):
@@ -288,10 +278,8 @@ def reproject_to_3d(Q, xy0, xy1, axis: int) -> np.ndarray:
         return h[:, :3] / h[:, 3:4]
 
 
-def undistort_rectify_map_host(camera_matrix, dist_coeffs, R, P, width: int, height: int, quantised: bool = True) -> np.ndarray:
-    """The definition of step 2 -> int32 [height, width, 2] (x, y in 1/32 px, MAP_SENTINEL outside); with ``quantised=False``
-    float64 [height, width, 2] source pixels, NaN outside."""
-    K, k = _camera(camera_matrix), _dist(dist_coeffs)
+def _rectify_map(distort, K, k, R, P, width, height, quantised) -> np.ndarray:
+    """Step 2 for the camera (K, k) of the model whose ``distort`` (x, y, k, False) -> (xd, yd, ...) is given."""
     Rm, f = _rot(R), _newcam(P, K)
     width, height = int(width), int(height)
     if width < 1 or height < 1:
@@ -302,8 +290,7 @@ def undistort_rectify_map_host(camera_matrix, dist_coeffs, R, P, width: int, hei
     qy = Rm[0, 1] * x + Rm[1, 1] * y + Rm[2, 1]
     qz = Rm[0, 2] * x + Rm[1, 2] * y + Rm[2, 2]
     with np.errstate(all="ignore"):
-        xn, yn = qx / qz, qy / qz
-        xd, yd, _, _, _ = _distort_jac(xn, yn, k)
+        xd, yd = distort(qx / qz, qy / qz, k, False)[:2]
         mx, my = K[0, 0] * xd + K[0, 2], K[1, 1] * yd + K[1, 2]
         ok = (qz > 0) & (np.abs(mx) <= MAP_LIMIT) & (np.abs(my) <= MAP_LIMIT)          # (NaN and inf compare false)
     if not quantised:
@@ -313,6 +300,12 @@ def undistort_rectify_map_host(camera_matrix, dist_coeffs, R, P, width: int, hei
     out[..., 0][ok] = np.rint(scale * mx[ok]).astype(np.int32)
     out[..., 1][ok] = np.rint(scale * my[ok]).astype(np.int32)
     return out
+
+
+def undistort_rectify_map_host(camera_matrix, dist_coeffs, R, P, width: int, height: int, quantised: bool = True) -> np.ndarray:
+    """The definition of step 2 -> int32 [height, width, 2] (x, y in 1/32 px, MAP_SENTINEL outside); with ``quantised=False``
+    float64 [height, width, 2] source pixels, NaN outside."""
+    return _rectify_map(_distort, _camera(camera_matrix), _dist(dist_coeffs), R, P, width, height, quantised)
 
 
 def remap_host(src, map_, border: int = 0) -> np.ndarray:
@@ -360,14 +353,13 @@ def _rp_args(R, P, K):
     return r, p
 
 
-def undistort_rectify_map_device(camera_matrix, dist_coeffs, R, P, width: int, height: int, device="cuda", out=None):
-    """``undistort_rectify_map_host`` on the GPU -> int32 device tensor [height, width, 2] (``out``: that tensor, preallocated and
-    contiguous).  Enqueued on the current stream; nothing is allocated when ``out`` is given.  Equal to the host map except where
-    32 m is within rounding of a half-integer (the two sum in different orders), and there by 1."""
+# One body per wrapper for both camera models, given as ``pnp``'s wrappers take a model: its ``_camera_args`` and its C entry.
+
+def _map_device(camera_args, entry, camera_matrix, dist_coeffs, R, P, width, height, device, out):
     import torch
     from . import _lib
     from .models._handles import require_cuda
-    cam, d, n = pnp._camera_args(camera_matrix, dist_coeffs)
+    cam = camera_args(camera_matrix, dist_coeffs)
     r, p = _rp_args(R, P, _camera(camera_matrix))
     width, height = int(width), int(height)
     if width < 1 or height < 1:
@@ -377,8 +369,29 @@ def undistort_rectify_map_device(camera_matrix, dist_coeffs, R, P, width: int, h
     if out.dtype != torch.int32 or tuple(out.shape) != (height, width, 2) or not out.is_contiguous() or out.device.type != "cuda":
         raise ValueError(f"out must be a contiguous int32 [{height}, {width}, 2] GPU tensor")
     with torch.cuda.device(out.device):
-        _lib.check(_lib.lib().dcx_undistort_rectify_map(cam, d, n, r, p, width, height, out.data_ptr(), _lib.current_stream()),
-                   "dcx_undistort_rectify_map")
+        _lib.check(getattr(_lib.lib(), entry)(*cam, r, p, width, height, out.data_ptr(), _lib.current_stream()), entry)
+    return out
+
+
+def undistort_rectify_map_device(camera_matrix, dist_coeffs, R, P, width: int, height: int, device="cuda", out=None):
+    """``undistort_rectify_map_host`` on the GPU -> int32 device tensor [height, width, 2] (``out``: that tensor, preallocated and
+    contiguous).  Enqueued on the current stream; nothing is allocated when ``out`` is given.  Equal to the host map except where
+    32 m is within rounding of a half-integer (the two sum in different orders), and there by 1."""
+    return _map_device(pnp._camera_args, "dcx_undistort_rectify_map", camera_matrix, dist_coeffs, R, P, width, height, device, out)
+
+
+def _points_pool(camera_args, entry, packed, batch, pool, refined, camera_matrix, dist_coeffs, R, P, out):
+    import torch
+    from . import _lib
+    dev = packed.device
+    batch, pool = int(batch), int(pool)
+    rows_p, xy_p = pnp._pool_ptrs(packed, batch, pool, refined)[2:]
+    cam = camera_args(camera_matrix, dist_coeffs)
+    r, p = _rp_args(R, P, _camera(camera_matrix))
+    out = _dev.tensor(out, dev, torch.float64, (pool, 2), f"out must be a contiguous float64 [{pool}, 2] tensor on {dev}", "numel")
+    with torch.cuda.device(dev):
+        _lib.check(getattr(_lib.lib(), entry)(rows_p, xy_p, pool, *cam, r, p, out.data_ptr() if pool else None,
+                                              _lib.current_stream()), entry)
     return out
 
 
@@ -387,19 +400,8 @@ def rectify_points_pool(packed, batch: int, pool: int, refined: bool, camera_mat
     the rows) in rectified coordinates, read in place -> float64 device tensor [pool, 2] by slot (``out``: that tensor,
     preallocated); NaN where ``rectify_points_host`` gives NaN.  Slots of no frame are converted too (whatever they hold).
     Enqueued on the current stream, no host sync, nothing allocated when ``out`` is given (capture-safe)."""
-    import torch
-    from . import _lib
-    dev = packed.device
-    batch, pool = int(batch), int(pool)
-    rows_p, xy_p = pnp._pool_ptrs(packed, batch, pool, refined)[2:]
-    cam, d, n = pnp._camera_args(camera_matrix, dist_coeffs)
-    r, p = _rp_args(R, P, _camera(camera_matrix))
-    out = _dev.tensor(out, dev, torch.float64, (pool, 2), f"out must be a contiguous float64 [{pool}, 2] tensor on {dev}", "numel")
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().dcx_rectify_points_pool(rows_p, xy_p, pool, cam, d, n, r, p,
-                                                      out.data_ptr() if pool else None, _lib.current_stream()),
-                   "dcx_rectify_points_pool")
-    return out
+    return _points_pool(pnp._camera_args, "dcx_rectify_points_pool", packed, batch, pool, refined, camera_matrix, dist_coeffs, R, P,
+                        out)
 
 
 def remap_device(frames, map_, border: int = 0, out=None):

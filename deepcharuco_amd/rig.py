@@ -62,14 +62,13 @@ import numpy as np
 from . import _dev, _lm
 from .calib import _no_bad_id
 from .corner_pool import _pool_rows
-from .pnp import (LM_EPS, LM_MAX_ITER, PNP_DEGENERATE, PNP_NONFINITE, PNP_OK, PNP_TOO_FEW, PNP_TRUNCATED, _bad_id_error, _camera,
-                  _cholesky_solve, _pool_ptrs, _rodrigues, _rvec_of, object_points)
+from .pnp import (LM_EPS, LM_MAX_ITER, LM_STATUS, PNP_DEGENERATE, PNP_OK, PNP_TOO_FEW, PNP_TRUNCATED, _bad_id_error, _camera,
+                  _pool_ptrs, _rodrigues, _rvec_of, object_points)
 # every step that does not depend on the number of cameras is stereo.py's, kept once
-from .stereo import (MODELS, STEREO_EPS, STEREO_MAX_ITER, _call, _depth_margin, _device_masks, _model_args, _model_cameras, _models,
-                     _outputs, _raise_like_cv2, _refine, _rig_init, _sine, _total, _unpack, _upload, _view_poses, _view_segments,
-                     essential_fundamental)
+from .stereo import (MODELS, STEREO_EPS, STEREO_MAX_ITER, _call, _depth_margin, _device_masks, _evaluate, _model_args, _model_cameras,
+                     _models, _outputs, _raise_like_cv2, _refine, _rig_init, _sine, _total, _unpack, _upload, _view_poses,
+                     _view_segments, essential_fundamental)
 from .stereo import _rig_rows as _rows_of
-from .stereo import _dist, _evaluate, _model_of     # noqa: F401  (the names the tests reach through this module)
 
 # overall status (include/deepcharuco_amd.h); per-view statuses are pnp's PNP_*
 RIG_OK, RIG_NO_STAMPS, RIG_DEGENERATE, RIG_NONFINITE = _lm.LM_OK, _lm.LM_NO_UNITS, _lm.LM_DEGENERATE, _lm.LM_NONFINITE
@@ -455,40 +454,6 @@ def _joint(rows, cams, X, p, jac):
     return ev[0], float((ev[0] * ev[0]).sum()), ev[2].reshape(-1, 6) if jac else None
 
 
-def _refine_pose(project, p):
-    """Step 4: ``pnp._solve``'s loop from the start p on ``project(p, jac) -> (res, cost, J)`` -> (status, p, cost, accepted steps).
-    The start's cost is finite (the caller chose it so)."""
-    res, cost, J = project(p, True)
-    prev_cost, lg, iters = cost, -3, 0
-    while True:
-        JtJ, Jtr = J.T @ J, J.T @ res.ravel()
-        prev = p
-        while True:
-            A = JtJ.copy()
-            A[np.diag_indices(6)] *= 1.0 + 10.0 ** lg
-            x = _cholesky_solve(A, Jtr)
-            if x is None:
-                return PNP_DEGENERATE, p, cost, iters
-            p = prev - x
-            _, cost, _ = project(p, False)
-            if not cost <= prev_cost:
-                lg += 1
-                if lg <= 16:
-                    continue
-            break
-        lg = max(lg - 1, -16)
-        iters += 1
-        if iters >= LM_MAX_ITER or math.sqrt(float((p - prev) @ (p - prev))) < LM_EPS * math.sqrt(float(prev @ prev)):
-            break
-        prev_cost = cost
-        res, cost, J = project(p, True)
-    if not np.isfinite(p).all() or math.isnan(cost):
-        return PNP_NONFINITE, p, cost, iters
-    if not math.isfinite(cost):
-        return PNP_DEGENERATE, p, cost, iters
-    return PNP_OK, p, cost, iters
-
-
 def rig_pose_host_full(keypoints_lists, col_count, row_count, square_len, cameras, dists, rig, masks=None, pool_order=False,
                        with_margin=False, models=None):
     """The definition (the comment above) -> ``RigPoseResult`` (with ``with_margin``: ``(result, margin)``).
@@ -545,8 +510,8 @@ def rig_pose_host_full(keypoints_lists, col_count, row_count, square_len, camera
             continue
         if second < math.inf:
             margin = min(margin, (second - best) / best if best > 0 else math.inf)
-        st, p, cost, it = _refine_pose(lambda q, jac: _joint(rows, cams, X, q, jac), start)
-        status[t] = st
+        st, p, cost, it = _lm.refine_pose(lambda q, jac: _joint(rows, cams, X, q, jac), start, LM_MAX_ITER, LM_EPS)
+        status[t] = st = LM_STATUS[st]
         if st != PNP_OK:
             continue
         rv[t], tv[t], rms[t], iters[t] = p[:3], p[3:], math.sqrt(cost / nrows[t]), it

@@ -93,27 +93,7 @@ class StereoResult(NamedTuple):
 def _project_q(Q: np.ndarray, img: np.ndarray, K: np.ndarray, k: np.ndarray, jac: bool):
     """Points Q (n, 3) in a camera's frame -> residuals (projected - observed, px) and, with ``jac``, d(u, v)/dQ (n, 2, 3):
     ``pnp._project``'s model and derivatives with the pose taken out.  Every Z must be positive (the caller checks)."""
-    iz = 1.0 / Q[:, 2]
-    x, y = Q[:, 0] * iz, Q[:, 1] * iz
-    r2 = x * x + y * y
-    num = 1 + r2 * (k[0] + r2 * (k[1] + r2 * k[4]))
-    den = 1 + r2 * (k[5] + r2 * (k[6] + r2 * k[7]))
-    g = num / den
-    xd = x * g + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x)
-    yd = y * g + k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y
-    fx, fy = K[0, 0], K[1, 1]
-    res = np.stack([fx * xd + K[0, 2] - img[:, 0], fy * yd + K[1, 2] - img[:, 1]], 1)
-    if not jac:
-        return res, None
-    dg = ((k[0] + r2 * (2 * k[1] + 3 * k[4] * r2)) * den - num * (k[5] + r2 * (2 * k[6] + 3 * k[7] * r2))) / (den * den)
-    dxd_dx = g + 2 * x * x * dg + 2 * k[2] * y + 6 * k[3] * x
-    dxd_dy = 2 * x * y * dg + 2 * k[2] * x + 2 * k[3] * y
-    dyd_dy = g + 2 * y * y * dg + 6 * k[2] * y + 2 * k[3] * x
-    a0, a1, b0, b1 = fx * dxd_dx, fx * dxd_dy, fy * dxd_dy, fy * dyd_dy
-    D = np.empty((Q.shape[0], 2, 3))
-    D[:, 0, 0], D[:, 0, 1], D[:, 0, 2] = a0 * iz, a1 * iz, -(a0 * x + a1 * y) * iz
-    D[:, 1, 0], D[:, 1, 1], D[:, 1, 2] = b0 * iz, b1 * iz, -(b0 * x + b1 * y) * iz
-    return res, D
+    return pnp._project_q_through(pnp._distort, Q, img, K, k, jac)
 
 
 MODELS = ("pinhole", "fisheye")      # DCX_CAMERA_PINHOLE, DCX_CAMERA_FISHEYE of include/deepcharuco_amd.h, in that order

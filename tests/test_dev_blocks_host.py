@@ -16,7 +16,7 @@ import camera_exact as cx
 import dev_blocks as DB
 import dev_blocks_cases as Z
 import fisheye_exact as fe
-from deepcharuco_amd import fisheye, pnp
+from deepcharuco_amd import _lm, fisheye, pnp
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "deepcharuco_amd", "csrc")
@@ -127,7 +127,7 @@ def h_cholesky_solve(x):
     for row in x:
         A = Z.unpack(row[:21], 6)
         A[np.diag_indices(6)] *= row[27]
-        s = pnp._cholesky_solve(A, row[21:27])
+        s = _lm._cholesky_solve(A, row[21:27])
         out.append(np.full(6, np.nan) if s is None else s)
     return np.array(out)
 
@@ -448,8 +448,8 @@ def schur_numpy(na, m, scale):
     U = M[na:na + 6, na:na + 6].copy()
     U[np.diag_indices(6)] *= scale
     W, gb = M[:na, na:na + 6], M[na:na + 6, nc - 1]
-    Y = np.stack([pnp._cholesky_solve(U, W[j]) for j in range(na)], 1)
-    z = pnp._cholesky_solve(U, gb)
+    Y = np.stack([_lm._cholesky_solve(U, W[j]) for j in range(na)], 1)
+    z = _lm._cholesky_solve(U, gb)
     return np.r_[Z.pack(W @ Y), W @ z], np.r_[Y.ravel(), z]
 
 

@@ -46,7 +46,7 @@ def solve(s, **kw):
 
 
 def pose_errors(r, s, used):
-    eR = max(float(np.abs(stereo._rodrigues(r.rvecs[t]) - cx.f64(cx.rotation(s.P[t, :3]))).max()) for t in used)
+    eR = max(float(np.abs(pnp._rodrigues(r.rvecs[t]) - cx.f64(cx.rotation(s.P[t, :3]))).max()) for t in used)
     eT = max(float(np.linalg.norm(r.tvecs[t] - s.P[t, 3:]) / np.linalg.norm(s.P[t, 3:])) for t in used)
     return eR, eT
 
@@ -64,9 +64,9 @@ def test_no_models_and_all_pinhole_are_the_definition_as_it_was():
     for x, y in zip(a, b):
         assert np.array_equal(x, y)
     for cams in (rig._cameras(cameras, dists)[0], rig._cameras(cameras, dists, ["pinhole"] * 3)[0]):
-        assert all(rig._model_of(c) == (pnp._solve, stereo._project_q) for c in cams)
+        assert all(stereo._model_of(c) == (pnp._solve, stereo._project_q) for c in cams)
     mixed = rig._cameras(cameras, [None, dists[1], np.zeros(4)], ["fisheye", "pinhole", "fisheye"])[0]
-    assert [rig._model_of(c) for c in mixed] == [(fisheye._solve, fisheye._project_q), (pnp._solve, stereo._project_q),
+    assert [stereo._model_of(c) for c in mixed] == [(fisheye._solve, fisheye._project_q), (pnp._solve, stereo._project_q),
                                                  (fisheye._solve, fisheye._project_q)]
     for bad in (["pinhole"] * 2, ["pinhole", "fisheye", "equidistant"]):
         with pytest.raises(ValueError):
@@ -114,7 +114,7 @@ def test_mixed_rig_jacobian_matches_exact_finite_differences():
     views = rx.pool_views(s, range(3))
     rows = rig._rows_of(views, 3)
     cams = rig._cameras(*frx.cam_args(s), frx.models(s))[0]
-    res, JX, JP = rig._evaluate(rows, cams, X, P, True)
+    res, JX, JP = stereo._evaluate(rows, cams, X, P, True)
     M, N = rows.obj.shape[0], len(views)
     J = np.zeros((2 * M, 12 + 6 * N))
     for c in (1, 2):

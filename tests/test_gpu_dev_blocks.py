@@ -168,7 +168,7 @@ def test_polar_factor_and_cholesky():
         L, ok = DB.run("cholesky_factor", np.c_[z.x[:, :21], z.x[:, 27]])
         assert (ok == 1).all()
         want = np.array([Z.lower_packed_to_pk(l) for l in z.expect])
-        # L against the factor in mpmath, relative to the factor's size; the host side of this gate is pnp._cholesky_solve's
+        # L against the factor in mpmath, relative to the factor's size; the host side of this gate is _lm._cholesky_solve's
         # solution gap of the same zone (the factor's error is what the solution's is made of)
         g_dev = float((np.abs(L - want).max(1) / np.abs(want).max(1)).max())
         g_host = z.measure(HT.h_cholesky_solve(z.x))

@@ -91,7 +91,7 @@ def test_rig_calibrate_models_pool(dev):
     X = r[8:].reshape(2, 6)
     rvec, T = np.zeros((3, 3)), np.zeros((3, 3))
     rvec[1:], T[1:] = X[:, :3], X[:, 3:]
-    d = rig.RigResult(int(r[5]), float(r[0]), np.stack([stereo._rodrigues(v) for v in rvec]), T, rvec, want["parents"], st,
+    d = rig.RigResult(int(r[5]), float(r[0]), np.stack([pnp._rodrigues(v) for v in rvec]), T, rvec, want["parents"], st,
                       info[:, :, 1].astype(np.int64), info[:, :, 0].copy(), pose[:, :3].copy(), pose[:, 3:6].copy(), pose[:, 6].copy(),
                       pose[:, 7].astype(np.int64), int(r[1]), int(r[2]), int(r[3]), int(r[4]))
     h = rig.rig_calibrate_host_full(kps, *s.board, cameras, dists, models=models)
@@ -158,7 +158,7 @@ def test_stereo_calibrate_models_pool(dev):
     exp[5, 0], exp[1, 1], exp[6, 0] = pnp.PNP_TOO_FEW, pnp.PNP_BAD_ID, pnp.PNP_DEGENERATE
     r, pose, info = want["result"], want["pose"], want["view_info"]
     assert want["view_status"].tolist() == exp.tolist() and int(r[11]) == stereo.STEREO_OK and int(r[9]) == 5
-    R = stereo._rodrigues(r[0:3])
+    R = pnp._rodrigues(r[0:3])
     d = stereo.StereoResult(0, float(r[6]), R, r[3:6].copy(), r[0:3].copy(), pnp._skew(r[3:6]) @ R, np.zeros((3, 3)), want["view_status"],
                             pose[:, 0:3].copy(), pose[:, 3:6].copy(), pose[:, 6].copy(), pose[:, 7].astype(np.int64), info[:, :, 0].copy(),
                             info[:, :, 1].astype(np.int64), int(r[7]), int(r[8]), int(r[9]), int(r[10]))

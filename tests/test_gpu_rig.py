@@ -380,7 +380,7 @@ def test_memory_contract(dev):
     X = r[8:].reshape(2, 6)
     rvec, T = np.zeros((3, 3)), np.zeros((3, 3))
     rvec[1:], T[1:] = X[:, :3], X[:, 3:]
-    d = rig.RigResult(int(r[5]), float(r[0]), np.stack([stereo._rodrigues(v) for v in rvec]), T, rvec, par.astype(np.int32), st,
+    d = rig.RigResult(int(r[5]), float(r[0]), np.stack([pnp._rodrigues(v) for v in rvec]), T, rvec, par.astype(np.int32), st,
                       info[:, :, 1].astype(np.int64), info[:, :, 0].copy(), pose[:, :3].copy(), pose[:, 3:6].copy(), pose[:, 6].copy(),
                       pose[:, 7].astype(np.int64), int(r[1]), int(r[2]), int(r[3]), int(r[4]))
     h = rig.rig_calibrate_host_full(kps, *s.board, cameras, dists)

@@ -828,8 +828,8 @@ def test_stereo_calibrate_pool(dev, L):
     assert want["view_status"].tolist() == exp
     r = want["result"]
     assert int(r[11]) == stereo.STEREO_OK and int(r[9]) == 5
-    R = stereo._rodrigues(r[0:3])
-    E, F = stereo.essential_fundamental(R, r[3:6], *(stereo._camera(c) for c in sx.cam_args(s)[::2]))
+    R = pnp._rodrigues(r[0:3])
+    E, F = stereo.essential_fundamental(R, r[3:6], *(pnp._camera(c) for c in sx.cam_args(s)[::2]))
     pose, info = want["pose"], want["view_info"]
     dres = stereo.StereoResult(0, float(r[6]), R, r[3:6].copy(), r[0:3].copy(), E, F, want["view_status"], pose[:, 0:3].copy(),
                                pose[:, 3:6].copy(), pose[:, 6].copy(), pose[:, 7].astype(np.int64), info[:, :, 0].copy(),

@@ -202,3 +202,88 @@ def test_host_driver_forced_non_finite(monkeypatch, ng):
 def test_host_driver_init(monkeypatch, stop_forced):
     (status, _, _, vc, iters, att), lgs = _drive(6, stop_forced, [], monkeypatch, init_cost=INF)
     assert (status, iters, att, vc, lgs) == (DEGENERATE, 0, 0, None, [])
+
+
+# ------------------------------------------------------------------------------------------------ the single-pose loop
+
+EPS32 = 2.0 ** -23                             # FLT_EPSILON, the stop test of the pose solvers
+BELOW = math.nextafter(EPS32, 0.0)             # sqrt(fl(s s)) == s for every double s (no over- or underflow): |dp| is the step itself
+
+
+def _drive_pose(monkeypatch, trials, max_iter, init_cost=INIT_COST, jacobian=None):
+    """_lm.refine_pose from p = (1, 0, 0, 0, 0, 0) (|p| = 1) through a toy ``project`` of three points whose J is the identity, so
+    the damped matrix is diag(1 + 10^lg).  Trial k = (cost, step, bad): the solve of that trial (as _drive's Schur step) moves
+    the pose's second coordinate by ``step`` from the committed point (to NaN for ``bad``), and the toy answers the scripted cost.
+    With ``jacobian`` the toy's J is that and _lm's own Cholesky solve runs.  -> (status, accepted steps, trial evaluations,
+    evaluations with the Jacobian, the damping of every solve, the final pose, the final cost)."""
+    count = {"trial": 0, "jac": 0}
+    damp = []
+
+    def solve(A, b):
+        damp.append(float(A[0, 0]))
+        assert np.array_equal(A, np.diag(np.diag(A))) and np.ptp(np.diag(A)) == 0.0          # every diagonal entry, equally
+        _, step, bad = trials[count["trial"]]
+        x = np.zeros(6)
+        x[1] = NAN if bad else step
+        return x
+
+    def project(p, jac):
+        if jac:
+            count["jac"] += 1
+            cost = init_cost if count["trial"] == 0 else trials[count["trial"] - 1][0]
+            return np.zeros((3, 2)), cost, np.eye(6) if jacobian is None else jacobian
+        count["trial"] += 1
+        return None, trials[count["trial"] - 1][0], None
+
+    if jacobian is None:
+        monkeypatch.setattr(_lm, "_cholesky_solve", solve)
+    status, p, cost, iters = _lm.refine_pose(project, np.array([1.0, 0.0, 0.0, 0.0, 0.0, 0.0]), max_iter, EPS32)
+    return status, iters, count["trial"], count["jac"], damp, p, cost
+
+
+def _damping(lgs):
+    return [1.0 + 10.0 ** lg for lg in lgs]
+
+
+def test_refine_pose_walks_the_rules(monkeypatch):
+    """Expected (status, accepted steps, trials) and the damping of every solve, from the rules in _lm's docstring: lg starts at -3;
+    a cost that is not <= the cost before takes lg + 1 and the same point is tried again while lg <= 16; the trial that takes lg
+    to 17 is committed whatever it costs; a committed step takes lg - 1, not below -16; ``max_iter`` committed steps at the most;
+    stop when |dp| < eps |p| at the point the step left; a damped matrix that is not positive definite, a start whose cost is not
+    finite and a final cost of inf are DEGENERATE; a final pose or cost that is NaN is NONFINITE."""
+    drive = lambda *a, **kw: _drive_pose(monkeypatch, *a, **kw)
+    acc, rej = (9.0, 1.0, False), (11.0, 1.0, False)
+    # _lm's own Cholesky solve on J = 0 (a zero pivot): DEGENERATE before anything is tried
+    assert drive([], 20, jacobian=np.zeros((6, 6)))[:4] == (DEGENERATE, 0, 0, 1)
+    # rejected three times (a higher cost, inf, higher), accepted on an EQUAL cost at lg 0, then the stop test
+    st, iters, n, njac, damp, p, cost = drive([(12.0, 1.0, False), (INF, 1.0, False), rej, (10.0, 1.0, False), (9.0, 0.0, False)], 20)
+    assert (st, iters, n) == (OK, 2, 5) and damp == _damping([-3, -2, -1, 0, -1]) and njac == 2 and cost == 9.0
+    assert p.tolist() == [1.0, -1.0, 0.0, 0.0, 0.0, 0.0]                  # the rejected trials left nothing behind
+    # lg -3 .. 16 is twenty trials; the twentieth rejection takes lg to 17 and that trial is the step; then lg 16
+    st, iters, n, _, damp, _, cost = drive([rej] * 20 + [(8.0, 0.0, False)], 20)
+    assert (st, iters, n) == (OK, 2, 21) and damp == _damping(list(range(-3, 17)) + [16]) and cost == 8.0
+    # four rejections and a step accepted at lg 1 leave lg at 0: sixteen rejections (lg 0 .. 15) reach 16, the trial there is
+    # rejected too, lg is 17 and it is the step
+    st, iters, n, _, damp, _, _ = drive([rej] * 4 + [acc] + [rej] * 17 + [(8.0, 0.0, False)], 20)
+    assert (st, iters, n) == (OK, 3, 23) and damp == _damping([-3, -2, -1, 0, 1] + list(range(0, 17)) + [16])
+    # the lower clamp: the 14th accepted step is solved at lg -16, and so is the trial after it (from -17 the forced trial would
+    # be the 34th, not the 33rd); then five accepted steps reach the cap of 20
+    st, iters, n, njac, damp, _, _ = drive([acc] * 14 + [rej] * 33 + [acc] * 5 + [rej], 20)
+    assert (st, iters, n, njac) == (OK, 20, 52, 20)
+    assert damp == _damping(list(range(-3, -17, -1)) + list(range(-16, 17)) + [16, 15, 14, 13, 12])
+    assert damp[12] != damp[13] == 1.0                                    # 1 + 1e-15 is not 1; 1 + 1e-16 is
+    # the iteration cap alone, at two sizes; the trial after it is never asked for
+    assert drive([acc] * 21, 20)[:3] == (OK, 20, 20) and drive([acc] * 4, 3)[:3] == (OK, 3, 3)
+    # the stop test, |p| = 1 at the start: a step of exactly eps is not < eps |p| and the solve goes on; the next double below stops it
+    assert drive([(9.0, EPS32, False), (8.0, 1.0, False), (7.0, 0.0, False)], 20)[:3] == (OK, 3, 3)
+    assert drive([(9.0, BELOW, False), (8.0, 1.0, False)], 20)[:3] == (OK, 1, 1)
+    assert drive([(9.0, 0.0, False)], 20)[:3] == (OK, 1, 1)
+    # the endings: a NaN pose, a forced step whose cost is NaN, one whose cost is inf (with the cap and with the stop test ending
+    # the solve), a start whose cost is not finite
+    st, iters, n, _, _, p, _ = drive([(9.0, 1.0, True)], 1)
+    assert (st, iters, n) == (NONFINITE, 1, 1) and np.isnan(p[1])
+    assert drive([rej] * 19 + [(NAN, 1.0, False)], 1)[:3] == (NONFINITE, 1, 20)
+    assert drive([rej] * 19 + [(INF, 1.0, False)], 1)[:3] == (DEGENERATE, 1, 20)
+    assert drive([rej] * 19 + [(INF, 0.0, False)], 20)[:3] == (DEGENERATE, 1, 20)
+    for c in (INF, NAN):
+        assert drive([], 20, init_cost=c)[:5] == (DEGENERATE, 0, 0, 1, [])

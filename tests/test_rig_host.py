@@ -48,8 +48,8 @@ def test_analytic_jacobian_matches_exact_finite_differences():
     P = s.P + rng.normal(scale=1e-2, size=s.P.shape) * np.r_[1, 1, 1, [np.linalg.norm(s.P[0, 3:])] * 3]
     views = rx.pool_views(s, range(3))
     rows = rig._rows_of(views, 3)
-    cams = [(rig._camera(K), rig._dist(d)) for K, d in zip(*rx.cam_args(s))]
-    res, JX, JP = rig._evaluate(rows, cams, X, P, True)
+    cams = [(pnp._camera(K), pnp._dist(d)) for K, d in zip(*rx.cam_args(s))]
+    res, JX, JP = stereo._evaluate(rows, cams, X, P, True)
     M, N = rows.obj.shape[0], len(views)
     J = np.zeros((2 * M, 12 + 6 * N))
     for c in (1, 2):
@@ -69,7 +69,7 @@ def test_analytic_jacobian_matches_exact_finite_differences():
 # ------------------------------------------------------------------------------------------------ truth
 
 def _pose_errors(r, s, used):
-    eR = max(float(np.abs(stereo._rodrigues(r.rvecs[t]) - cx.f64(cx.rotation(s.P[t, :3]))).max()) for t in used)
+    eR = max(float(np.abs(pnp._rodrigues(r.rvecs[t]) - cx.f64(cx.rotation(s.P[t, :3]))).max()) for t in used)
     eT = max(float(np.linalg.norm(r.tvecs[t] - s.P[t, 3:]) / np.linalg.norm(s.P[t, 3:])) for t in used)
     return eR, eT
 
@@ -339,7 +339,7 @@ def test_stereo_and_rig_tables_run_through_one_evaluate_and_one_normal_blocks():
     assert by_view.obj.shape == (16, 3) and by_view.n_cams == by_pair.n_cams == 2
     for a, b in zip(by_view[:-1], by_pair[:-1]):
         assert a.dtype == b.dtype and np.array_equal(a, b)
-    cams = [(stereo._camera(K), stereo._dist(d)) for K, d in zip(*rx.cam_args(s))]
+    cams = [(pnp._camera(K), pnp._dist(d)) for K, d in zip(*rx.cam_args(s))]
     rng = np.random.default_rng(6)
     X = s.X[0] + rng.normal(scale=1e-3, size=6)
     P = s.P + rng.normal(scale=1e-3, size=s.P.shape)

@@ -13,7 +13,7 @@ import fisheye_rig_exact as frx
 import rig_exact as rx
 import rigpose_exact as px
 import stereo_exact as sx
-from deepcharuco_amd import fisheye, pnp, rig
+from deepcharuco_amd import _lm, fisheye, pnp, rig
 from test_fisheye_rig_host import CLASSES as MIXED
 from test_fisheye_rig_host import outside_scene
 from test_gpu_stereo import MARGIN, REL
@@ -231,7 +231,7 @@ def test_a_weak_camera_0_does_not_seed_the_solve(seed):
     views = px.views_of(s, 0)
     rows = rig._rows_of([[(c, o, i.astype(np.float32)) for c, o, i in views]], 3)
     p0 = pnp.solve_pnp_host_full(s.kps[0][0], *s.board, *sx.CAMS["A"])[1][:6]
-    st0, q0, _, _ = rig._refine_pose(lambda q, jac: rig._joint(rows, cams, s.X, q, jac), p0)
+    st0, q0, _, _ = _lm.refine_pose(lambda q, jac: rig._joint(rows, cams, s.X, q, jac), p0, pnp.LM_MAX_ITER, pnp.LM_EPS)
     c_res = px.cost(views, s, s.X, np.r_[r.rvec[0], r.tvec[0]])
     c_0 = px.cost(views, s, s.X, q0) if st0 == OK else math.inf
     print(f"weak camera 0, seed {seed}: started from camera {int(r.seed[0])}, margin {margin:.2e}; exact cost {c_res:.6f}, from camera 0's pose "

@@ -44,7 +44,7 @@ def test_analytic_jacobian_matches_exact_finite_differences(rig, c0, c1):
     P = s.P + rng.normal(scale=1e-2, size=s.P.shape) * np.r_[1, 1, 1, [np.linalg.norm(s.P[0, 3:])] * 3]
     views = sx.pool_views(s)
     rows = stereo._rows_of(views)
-    cams = [(stereo._camera(K), stereo._dist(d)) for K, d in (sx.CAMS[c0], sx.CAMS[c1])]
+    cams = [(pnp._camera(K), pnp._dist(d)) for K, d in (sx.CAMS[c0], sx.CAMS[c1])]
     res, JX, JP = stereo._evaluate(rows, cams, X, P, True)
     M, N = rows.obj.shape[0], len(views)
     J = np.zeros((2 * M, 6 + 6 * N))
@@ -163,10 +163,10 @@ def test_rig_init_takes_the_lower_median(n):
     assert stereo.lower_median([7.0]) == 7.0 and stereo.lower_median([2.0, 1.0]) == 1.0
     rng = np.random.default_rng(n)
     rx = np.array([0.1, -0.7, 0.2])
-    RX = stereo._rodrigues(rx)
+    RX = pnp._rodrigues(rx)
     Tt = rng.normal(size=(n, 3))
     p0 = np.c_[rng.normal(scale=0.3, size=(n, 3)), rng.normal(size=(n, 3))]
-    p1 = np.array([np.r_[pnp._rvec_of(RX @ stereo._rodrigues(p[:3])), RX @ p[3:] + T] for p, T in zip(p0, Tt)])
+    p1 = np.array([np.r_[pnp._rvec_of(RX @ pnp._rodrigues(p[:3])), RX @ p[3:] + T] for p, T in zip(p0, Tt)])
     st, X0, _ = stereo._rig_init(p0, p1)
     want = np.sort(Tt, 0)[(n - 1) // 2]
     print(f"{n} pairs: init T {X0[3:]}, lower medians {want}")
