@@ -95,13 +95,25 @@ def distort(x, y, K, k):
     return np.stack([K[0, 0] * xd + K[0, 2], K[1, 1] * yd + K[1, 2]], 1)
 
 
-def project(obj, p, K, dist):
+def camera_points(obj, P, X=None):
+    """Board points (N, 3) through the pose P = (rvec, tvec) and, with X, on through a second transform X (a rig's: P is then the
+    board's pose in camera 0's frame and X takes that frame to the camera's) -> [X, Y, Z], working precision.  The one statement
+    of this step: every projection of the *_exact modules, of either camera model, goes through it."""
+    obj, P = _w(obj), _w(P)
+    R = rotation(P[:3])
+    Q = [R[i, 0] * obj[:, 0] + R[i, 1] * obj[:, 1] + R[i, 2] * obj[:, 2] + P[3 + i] for i in range(3)]
+    if X is not None:
+        X = _w(X)
+        Rx = rotation(X[:3])
+        Q = [Rx[i, 0] * Q[0] + Rx[i, 1] * Q[1] + Rx[i, 2] * Q[2] + X[3 + i] for i in range(3)]
+    return Q
+
+
+def project(obj, p, K, dist, X=None):
     """Board points (N, 3), pose p = (rvec, tvec) -> pixels (N, 2) in the working precision; every Z must be positive."""
-    obj, p = _w(obj), _w(p)
-    R = rotation(p[:3])
-    X = [R[i, 0] * obj[:, 0] + R[i, 1] * obj[:, 1] + R[i, 2] * obj[:, 2] + p[3 + i] for i in range(3)]
-    assert all(z > 0 for z in X[2]), "a point is not in front of the camera"
-    return distort(X[0] / X[2], X[1] / X[2], K, dist8(dist))
+    Q = camera_points(obj, p, X)
+    assert all(z > 0 for z in Q[2]), "a point is not in front of the camera"
+    return distort(Q[0] / Q[2], Q[1] / Q[2], K, dist8(dist))
 
 
 def residuals(obj, img, p, K, dist):
@@ -114,26 +126,43 @@ def cost(obj, img, p, K, dist):
     return float((r * r).sum())
 
 
+def fd_step(v, j):
+    """The central-difference step of entry j of a pose block v = (rvec, tvec): 1e-6 rad, 1e-6 |t|."""
+    return _w(1e-6) * (1 if j < 3 else _sqrt(v[3] * v[3] + v[4] * v[4] + v[5] * v[5]))
+
+
+def jacobian_of(f, *blocks):
+    """Jacobian of the residuals f(*blocks) with respect to every entry of every pose block ([n, 6] or [6]), block by block and
+    row-major within one, by central differences in the working precision -> float64 [2M, entries].  Steps ``fd_step``:
+    truncation ~1e-12 and rounding ~1e-13 of a column's size with a 64-bit mantissa.  The one finite-difference routine of the
+    pose costs; fisheye_exact.jacobian_fd, which also differentiates by the intrinsics, has its own scales."""
+    blocks = [_w(b) for b in blocks]
+    cols = []
+    for k, b in enumerate(blocks):
+        for idx in np.ndindex(b.shape):
+            h = fd_step(b[idx[:-1]], idx[-1])
+            d = _w(np.zeros(b.shape))
+            d[idx] = h
+            hi, lo = f(*blocks[:k], b + d, *blocks[k + 1:]), f(*blocks[:k], b - d, *blocks[k + 1:])
+            cols.append(f64(((hi - lo) / (2 * h)).ravel()))
+    return np.stack(cols, 1)
+
+
+def stationarity_of(r, J):
+    """Working-precision residuals r and their Jacobian J -> (cost, |J^T r| / (|J| |r|)); 0 for the gradient where r = 0."""
+    r = f64(r).ravel()
+    nr = np.linalg.norm(r)
+    return float(r @ r), (float(np.linalg.norm(J.T @ r) / (np.linalg.norm(J) * nr)) if nr > 0 else 0.0)
+
+
 def jacobian_fd(obj, img, p, K, dist):
-    """2N x 6 Jacobian of the residuals with respect to the pose by central differences in the working precision -> float64.
-    Steps 1e-6 rad and 1e-6 |t|: truncation ~1e-12 and rounding ~1e-13 of a column's size with a 64-bit mantissa."""
-    p = _w(p)
-    tn = _sqrt(p[3] * p[3] + p[4] * p[4] + p[5] * p[5])
-    J = np.empty((2 * len(obj), 6))
-    for j in range(6):
-        h = _w(1e-6) * (1 if j < 3 else tn)
-        d = _w(np.zeros(6))
-        d[j] = h
-        J[:, j] = f64(((residuals(obj, img, p + d, K, dist) - residuals(obj, img, p - d, K, dist)) / (2 * h)).ravel())
-    return J
+    """2N x 6 Jacobian of the residuals with respect to the pose (``jacobian_of``) -> float64."""
+    return jacobian_of(lambda q: residuals(obj, img, q, K, dist), p)
 
 
 def stationarity(obj, img, p, K, dist):
     """-> (cost, |J^T r| / (|J| |r|)) at pose p, both from this module's residuals and finite differences."""
-    r = f64(residuals(obj, img, p, K, dist)).ravel()
-    J = jacobian_fd(obj, img, p, K, dist)
-    nr = np.linalg.norm(r)
-    return float(r @ r), (float(np.linalg.norm(J.T @ r) / (np.linalg.norm(J) * nr)) if nr > 0 else 0.0)
+    return stationarity_of(residuals(obj, img, p, K, dist), jacobian_fd(obj, img, p, K, dist))
 
 
 def undistort5(pix, K, dist, rounds=5):

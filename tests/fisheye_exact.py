@@ -47,23 +47,18 @@ def distort(a, b, K, k):
     return np.stack([K[0, 0] * xd + K[0, 2], K[1, 1] * yd + K[1, 2]], 1)
 
 
-def camera_points(obj, p):
-    obj, p = _w(obj), _w(p)
-    R = cx.rotation(p[:3])
-    return [R[i, 0] * obj[:, 0] + R[i, 1] * obj[:, 1] + R[i, 2] * obj[:, 2] + p[3 + i] for i in range(3)]
+def project(obj, p, K, k, X=None):
+    """Board points (N, 3), pose p = (rvec, tvec) [and on through X, as camera_exact.camera_points] -> pixels (N, 2) in the
+    working precision; every Z must be positive."""
+    Q = cx.camera_points(obj, p, X)
+    assert all(z > 0 for z in Q[2]), "a point is not in front of the camera"
+    return distort(Q[0] / Q[2], Q[1] / Q[2], K, k)
 
 
-def project(obj, p, K, k):
-    """Board points (N, 3), pose p = (rvec, tvec) -> pixels (N, 2) in the working precision; every Z must be positive."""
-    X = camera_points(obj, p)
-    assert all(z > 0 for z in X[2]), "a point is not in front of the camera"
-    return distort(X[0] / X[2], X[1] / X[2], K, k)
-
-
-def theta_max(obj, p):
+def theta_max(obj, p, X=None):
     """The largest angle from the optical axis of any point, radians."""
-    X = camera_points(obj, p)
-    return float(np.max(np.arctan2(f64(np.sqrt(X[0] * X[0] + X[1] * X[1])), f64(X[2]))))
+    Q = cx.camera_points(obj, p, X)
+    return float(np.max(np.arctan2(f64(np.sqrt(Q[0] * Q[0] + Q[1] * Q[1])), f64(Q[2]))))
 
 
 def project_mp(obj, p, K, k, dps=40):
@@ -146,8 +141,7 @@ def make_views(seed, n_views, K, k, size=SIZE, board=BOARD, rows=None, sigma=0.0
                 break
         obj = cx.board_points(ids, *board)
         p = random_pose(rng, board, z_range)
-        X = camera_points(obj, p)
-        if not all(z > 0.02 for z in X[2]):
+        if not all(z > 0.02 for z in cx.camera_points(obj, p)[2]):
             continue
         img = f64(project(obj, p, K, k))
         inside = (img[:, 0] >= 0) & (img[:, 0] <= w - 1) & (img[:, 1] >= 0) & (img[:, 1] <= h - 1)

@@ -26,7 +26,7 @@ def rig(kind, cam0, cam1):
     at a 15 degree vergence, "vertical" camera 1 7 cm above camera 0."""
     if kind in _FIXED:
         return _FIXED[kind].copy()
-    return sx.make_rig(kind, sx.BOARD_S, sx.CAMS[cam0][0], sx.CAMS[cam1][0])
+    return sx.make_rig(kind, sx.BOARD_S, sx.cam_K(cam0), sx.cam_K(cam1))
 
 
 def rig_RT(kind, cam0, cam1):
@@ -76,7 +76,7 @@ def scene(kind, cam0, cam1, seed=0, n_pairs=6):
         return sx.scene(700 + seed, n_pairs, kind, sx.BOARD_S, cam0, cam1)
     rng = np.random.default_rng([9200, seed, RIGS.index(kind), PAIRS.index((cam0, cam1))])
     board = sx.BOARD_S
-    (K0, d0), (K1, d1) = sx.CAMS[cam0], sx.CAMS[cam1]
+    (K0, d0), (K1, d1) = sx.cam(cam0), sx.cam(cam1)
     X = rig(kind, cam0, cam1)
     Rx = f64(cx.rotation(X[:3]))
     N = cx.n_ids(board)

@@ -1,18 +1,11 @@
-"""The exact statement of the rig pose cost for the rig pose tests: with the rig X held fixed, the residuals of one timestamp's
-rows of every camera as tests/rig_exact.py (pinholes) or tests/fisheye_rig_exact.py (cameras with a model each) state them in long
-double, a finite-difference Jacobian over the 6 parameters of the board pose alone, and stationarity.  Nothing here imports
-deepcharuco_amd."""
+"""The exact statement of the rig pose cost for the rig pose tests: tests/rig_exact.py's cost (cameras of either model) with the rig
+X held fixed and a single timestamp, so a finite-difference Jacobian over the 6 parameters of the board pose alone, and
+stationarity.  Nothing here imports deepcharuco_amd."""
 import numpy as np
 
 import camera_exact as cx
-import fisheye_rig_exact as frx
 import rig_exact as rx
-from camera_exact import _w, f64
-
-
-def _residuals(s):
-    """The scene's own statement: fisheye_rig_exact's for a scene whose cameras are named there, else rig_exact's."""
-    return frx.residuals if all(n in frx.CAMS for n in s.cams) else rx.residuals
+from camera_exact import f64
 
 
 def views_of(s, t, masks=None, keep=None):
@@ -23,7 +16,7 @@ def views_of(s, t, masks=None, keep=None):
 
 def residuals(views, s, X, p):
     """projected - observed of one timestamp's rows at the board pose p (6), cameras ascending -> (M, 2), working precision."""
-    return _residuals(s)([views], s, np.asarray(X), np.asarray(p)[None])
+    return rx.residuals([views], s, np.asarray(X), np.asarray(p)[None])
 
 
 def cost(views, s, X, p):
@@ -32,24 +25,13 @@ def cost(views, s, X, p):
 
 
 def jacobian_fd(views, s, X, p):
-    """2M x 6 Jacobian of ``residuals`` with respect to p by central differences in the working precision -> float64; X is fixed.
-    Steps as rig_exact.jacobian_fd: 1e-6 rad, 1e-6 |t|."""
-    p = _w(p)
-    cols = []
-    for j in range(6):
-        h = rx._step(p, j)
-        d = _w(np.zeros(6))
-        d[j] = h
-        cols.append(f64(((residuals(views, s, X, p + d) - residuals(views, s, X, p - d)) / (2 * h)).ravel()))
-    return np.stack(cols, 1)
+    """2M x 6 Jacobian of ``residuals`` with respect to p -> float64 (camera_exact.jacobian_of); X is fixed."""
+    return cx.jacobian_of(lambda q: residuals(views, s, X, q), p)
 
 
 def stationarity(views, s, X, p):
     """-> (cost, |J^T r| / (|J| |r|)) at the board pose p with X fixed."""
-    r = f64(residuals(views, s, X, p)).ravel()
-    J = jacobian_fd(views, s, X, p)
-    nr = np.linalg.norm(r)
-    return float(r @ r), (float(np.linalg.norm(J.T @ r) / (np.linalg.norm(J) * nr)) if nr > 0 else 0.0)
+    return cx.stationarity_of(residuals(views, s, X, p), jacobian_fd(views, s, X, p))
 
 
 def rig_rt(X):

@@ -1,23 +1,64 @@
-"""Two-camera scenes for the stereo calibration tests, made by the exact camera model of tests/camera_exact.py (long double), and
-that model's own statement of the stereo cost: residuals of both cameras, a finite-difference Jacobian over all 6 + 6N
-parameters, stationarity.  Nothing here imports deepcharuco_amd: the rig convention is cv2's, q1 = R q0 + T.
+"""The cameras of the multi-camera tests and the exact cost of their views, and the two-camera scenes of the stereo calibration
+tests.  Nothing here imports deepcharuco_amd: the rig convention is cv2's, q_c = R_c q_0 + T_c.
 
-A scene: a true rig X = (rvec, T), per timestamp a true board pose P_t in camera 0's frame, and per camera an id subset drawn
-independently of the other camera's (or, with ``disjoint``, two subsets without a common id)."""
+This is the lowest module that sees both camera models (tests/camera_exact.py, tests/fisheye_exact.py), so the statements that
+serve cameras of either live here, once: the table ``CAMS`` with its accessors (and which names state models), ``project_view``, and ``view_residuals`` /
+``view_cost`` over ``rig_exact.pool_views``' layout (per timestamp a list of (camera, obj, img)).  The stereo cost below is that
+statement at C = 2, rig_exact's is it as it stands, rigpose_exact's is it with X held fixed and one timestamp.  The
+finite-difference routine and the stationarity measure of all of them are camera_exact's ``jacobian_of`` and ``stationarity_of``.
+
+A stereo scene: a true rig X = (rvec, T), per timestamp a true board pose P_t in camera 0's frame, and per camera an id subset
+drawn independently of the other camera's (or, with ``disjoint``, two subsets without a common id)."""
 from collections import namedtuple
 
 import numpy as np
 
 import camera_exact as cx
+import fisheye_exact as fx
 from camera_exact import _w, f64
 
 K_A = cx.K_EDGE                                                                    # fx / fy = 1.08
 K_B = np.array([[352.0, 0, 203.1], [0, 371.0, 116.2], [0, 0, 1]])                 # fx != fy, another principal point
 K_C = np.array([[298.0, 0, 161.0], [0, 325.0, 118.5], [0, 0, 1]])
-CAMS = {"A": (K_A, None), "B": (K_B, cx.CALIB_DIST), "C": (K_C, cx.DIST8), "A4": (K_A, cx.DIST8[:4])}
+# name -> (model, K, coefficients); read through cam_model / cam_K / cam_coeffs / cam, never by position
+CAMS = {
+    "A": ("pinhole", K_A, None), "B": ("pinhole", K_B, cx.CALIB_DIST), "C": ("pinhole", K_C, cx.DIST8), "A4": ("pinhole", K_A, cx.DIST8[:4]),
+    # the cameras of the rigs with fisheye cameras in them: two wide lenses of a few pixels per degree, and B and A again
+    "F": ("fisheye", fx.camera(230.0, off=(3.0, -2.0)), fx.K_LENS),
+    "F0": ("fisheye", fx.camera(150.0, 163.0), None),                     # k = 0: the equidistant lens
+    "P": ("pinhole", K_B, cx.CALIB_DIST),
+    "P0": ("pinhole", K_A, None),
+    # theta_d = theta - 0.2 theta^3 has its maximum, 0.8607, at theta = 1.291 (74 degrees): a pixel further than 0.8607 f from the
+    # principal point is the image of no direction, so the model's inverse does not exist there
+    "FN": ("fisheye", fx.camera(230.0), np.array([-0.2, 0.0, 0.0, 0.0])),
+}
+# a scene of these names states its cameras' models to the entry points (models=...), all-pinhole rigs of "P" / "P0" included;
+# a scene of "A" / "B" / "C" / "A4" calls them without
+STATES_MODELS = frozenset(("F", "F0", "P", "P0", "FN"))
 BOARD_S, BOARD_L = cx.CALIB_BOARD, cx.BOARDS[3]                                    # 7x11 (60 ids) and 24x17 (368 ids)
 
+# the gates of device against host in the stereo, rig and rig pose tests: poses within REL, or within FALLBACK with an equal cost
+# where the last LM step is decided by rounding; the host definition at least MARGIN from every discrete decision
+REL, FALLBACK, MARGIN = 1e-9, 1e-6, 1e-6
+
 Scene = namedtuple("Scene", "kps0 kps1 X P board cam0 cam1 tag")
+
+
+def cam_model(name):
+    return CAMS[name][0]
+
+
+def cam_K(name):
+    return CAMS[name][1]
+
+
+def cam_coeffs(name):
+    return CAMS[name][2]
+
+
+def cam(name):
+    """(K, coefficients): the two camera arguments of a single-camera entry point."""
+    return cam_K(name), cam_coeffs(name)
 
 
 def _unit(v):
@@ -63,21 +104,21 @@ def _compose(ra, rb):
 def project_rig(obj, P, X, K, dist):
     """Board points through the board pose P (camera 0's frame) and, with X, on through the rig into camera 1 -> pixels (N, 2) in
     the working precision.  Every Z must be positive."""
-    obj, P = _w(obj), _w(P)
-    R = cx.rotation(P[:3])
-    Q = [R[i, 0] * obj[:, 0] + R[i, 1] * obj[:, 1] + R[i, 2] * obj[:, 2] + P[3 + i] for i in range(3)]
-    if X is not None:
-        X = _w(X)
-        Rx = cx.rotation(X[:3])
-        Q = [Rx[i, 0] * Q[0] + Rx[i, 1] * Q[1] + Rx[i, 2] * Q[2] + X[3 + i] for i in range(3)]
-    assert all(z > 0 for z in Q[2]), "a point is not in front of the camera"
-    return cx.distort(Q[0] / Q[2], Q[1] / Q[2], K, cx.dist8(dist))
+    return cx.project(obj, P, K, dist, X)
+
+
+def project_view(obj, P, X, name):
+    """Pixels (N, 2) of camera ``name`` behind the rig transform X (None: the reference camera), by its own model."""
+    K, k = cam(name)
+    if cam_model(name) == "pinhole":
+        return cx.project(obj, P, K, k, X)
+    return fx.project(obj, P, K, fx.K_ZERO if k is None else k, X)
 
 
 def scene(seed, n_pairs, rig="small", board=BOARD_S, cam0="A", cam1="B", sigma=0.0, rows=None, disjoint=False, tag=""):
     """-> Scene.  ``rows``: None (6 .. all ids, drawn per view), an int, or per timestamp a pair (n0, n1)."""
     rng = np.random.default_rng([9100, seed])
-    (K0, d0), (K1, d1) = CAMS[cam0], CAMS[cam1]
+    (K0, d0), (K1, d1) = cam(cam0), cam(cam1)
     X = make_rig(rig, board, K0, K1)
     N = cx.n_ids(board)
     centre = cx.board_points(np.arange(N), *board).astype(np.float64).mean(0)
@@ -109,7 +150,7 @@ def scene(seed, n_pairs, rig="small", board=BOARD_S, cam0="A", cam1="B", sigma=0
 
 def cam_args(s):
     """The four camera arguments of the stereo entry points, in order."""
-    return CAMS[s.cam0][0], CAMS[s.cam0][1], CAMS[s.cam1][0], CAMS[s.cam1][1]
+    return (*cam(s.cam0), *cam(s.cam1))
 
 
 # ------------------------------------------------------------------------------------------------ the exact cost
@@ -130,46 +171,39 @@ def pool_views(s, used=None, masks=None):
     return out
 
 
-def residuals(views, s, X, P):
-    """projected - observed of every row, pair by pair, camera 0's rows first -> (M, 2), working precision."""
-    (K0, d0), (K1, d1) = CAMS[s.cam0], CAMS[s.cam1]
-    parts = []
-    for (o0, i0, o1, i1), p in zip(views, P):
-        parts.append(project_rig(o0, p, None, K0, d0) - _w(i0))
-        parts.append(project_rig(o1, p, X, K1, d1) - _w(i1))
-    return np.concatenate(parts)
+def view_residuals(views, cams, X, P):
+    """projected - observed of every row, timestamp by timestamp, cameras ascending -> (M, 2), working precision.  ``views``: per
+    timestamp a list of (camera, obj, img), ``cams`` the cameras' names, X [C - 1, 6] the rig, P [N, 6] the board poses."""
+    return np.concatenate([project_view(o, p, X[c - 1] if c else None, cams[c]) - _w(i) for vs, p in zip(views, P) for c, o, i in vs])
 
 
-def cost(views, s, X, P):
-    r = residuals(views, s, X, P)
+def view_cost(views, cams, X, P):
+    r = view_residuals(views, cams, X, P)
     return float((r * r).sum())
 
 
+def _rig_form(views, s, X):
+    """The stereo layout (obj0, img0, obj1, img1) and X (6) as ``view_residuals`` takes them."""
+    return [[(0, o0, i0), (1, o1, i1)] for o0, i0, o1, i1 in views], (s.cam0, s.cam1), X[None]
+
+
+def residuals(views, s, X, P):
+    """projected - observed of every row, pair by pair, camera 0's rows first -> (M, 2), working precision."""
+    return view_residuals(*_rig_form(views, s, np.asarray(X)), P)
+
+
+def cost(views, s, X, P):
+    return view_cost(*_rig_form(views, s, np.asarray(X)), P)
+
+
 def jacobian_fd(views, s, X, P):
-    """2M x (6 + 6N) Jacobian of ``residuals`` with respect to (X, P_0, ..., P_N-1) by central differences in the working
-    precision -> float64.  Steps as camera_exact.jacobian_fd: 1e-6 rad, 1e-6 |t|."""
-    X, P = _w(X), _w(P)
-    cols = []
-    for j in range(6):
-        h = _w(1e-6) * (1 if j < 3 else cx._sqrt(X[3] * X[3] + X[4] * X[4] + X[5] * X[5]))
-        d = _w(np.zeros(6))
-        d[j] = h
-        cols.append(f64(((residuals(views, s, X + d, P) - residuals(views, s, X - d, P)) / (2 * h)).ravel()))
-    for i in range(len(P)):
-        for j in range(6):
-            h = _w(1e-6) * (1 if j < 3 else cx._sqrt(P[i, 3] * P[i, 3] + P[i, 4] * P[i, 4] + P[i, 5] * P[i, 5]))
-            d = _w(np.zeros(P.shape))
-            d[i, j] = h
-            cols.append(f64(((residuals(views, s, X, P + d) - residuals(views, s, X, P - d)) / (2 * h)).ravel()))
-    return np.stack(cols, 1)
+    """2M x (6 + 6N) Jacobian of ``residuals`` with respect to (X, P_0, ..., P_N-1) -> float64 (camera_exact.jacobian_of)."""
+    return cx.jacobian_of(lambda x, p: residuals(views, s, x, p), X, P)
 
 
 def stationarity(views, s, X, P):
     """-> (cost, |J^T r| / (|J| |r|)) at (X, P), from this module's residuals and finite differences."""
-    r = f64(residuals(views, s, X, P)).ravel()
-    J = jacobian_fd(views, s, X, P)
-    nr = np.linalg.norm(r)
-    return float(r @ r), (float(np.linalg.norm(J.T @ r) / (np.linalg.norm(J) * nr)) if nr > 0 else 0.0)
+    return cx.stationarity_of(residuals(views, s, X, P), jacobian_fd(views, s, X, P))
 
 
 def rig_error(r, s):

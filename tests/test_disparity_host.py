@@ -215,7 +215,7 @@ def test_host_accuracy_two_planes():
 # ------------------------------------------------------------------------------------------------ the points
 
 def test_points_against_the_corner_path():
-    (K0, d0), (K1, d1) = sx.CAMS["A"], sx.CAMS["B"]
+    (K0, d0), (K1, d1) = sx.cam("A"), sx.cam("B")
     R, T = rx.rig_RT("small", "A", "B")
     r = rc.stereo_rectify_host(K0, d0, K1, d1, rx.SIZE, R, T)
     assert r.axis == 0

@@ -69,7 +69,7 @@ def test_undistort_inverts_project(K, k):
     assert gap[-1].max() <= 1e-12 / np.cos(np.deg2rad(80.0)) ** 2            # 80 degrees: d tan / d theta = 33
     objs, _, _, poses = fx.make_views(6, 4, K, k)
     for o, p in zip(objs, poses):
-        X = fx.camera_points(o, p)
+        X = cx.camera_points(o, p)
         n = fe.undistort_points_host(f64(fx.project(o, p, K, k)), K, k)
         assert np.abs(n - np.stack([f64(X[0] / X[2]), f64(X[1] / X[2])], 1)).max() <= 1e-12
 

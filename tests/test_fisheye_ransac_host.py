@@ -10,6 +10,7 @@ import camera_exact as cx
 import fisheye_exact as fx
 import fisheye_rig_exact as frx
 import rig_exact as rx
+import stereo_exact as sx
 from deepcharuco_amd import fisheye, pnp, rig
 from test_fisheye_rig_host import class_scene, solve
 from test_stereo_host import RANSAC
@@ -75,7 +76,7 @@ def test_three_exchanged_ids_are_found_and_the_pose_is_recovered():
 
 def _outside_view():
     """A view through the lens whose theta_d has a maximum, 12 rows, row 0 (lowest id) moved to a pixel no direction projects to."""
-    _, Kn, kn = frx.CAMS["FN"]
+    Kn, kn = sx.cam("FN")
     _, imgs, ids_l, _ = fx.make_views(11, 1, Kn, kn, rows=12)
     kp = fx.keypoints(imgs, ids_l)[0]
     kp[0, :2] = [Kn[0, 2] + 1.02 * frx.THETA_D_MAX_FN * Kn[0, 0], Kn[1, 2]]

@@ -26,7 +26,7 @@ TRUTH_POSE_R = 1.12e-6      # 4 x 2.79e-7: max |R(P_t) - R_true| (the pair: a P_
 TRUTH_POSE_T = 4.8e-7       # 4 x 1.18e-7 (the chain)
 MARGIN = 1e-6               # test_gpu_stereo's: the host definition's distance from every discrete decision
 
-# five classes of rigs: (angles, cameras of fisheye_rig_exact.CAMS, and what else the scene takes)
+# five classes of rigs: (angles, cameras of stereo_exact.CAMS, and what else the scene takes)
 CLASSES = {
     "fan3 F/P/F": dict(angles=(0, 25, -25), cams=("F", "P", "F0")),                       # a fisheye reference camera
     "pair P/F": dict(angles=(0, 30), cams=("P", "F")),
@@ -86,7 +86,7 @@ def test_project_q_jacobian_matches_exact_finite_differences():
     Q[0, :2] = 0.0
     Q[1, :2] = [1e-12 * Q[1, 2], 0.0]
     for name in ("F", "F0"):
-        _, K, k = frx.CAMS[name]
+        K, k = sx.cam(name)
         k = fx.K_ZERO if k is None else k
         res, D = fisheye._project_q(Q, np.zeros((12, 2)), K, k, True)
         exact = lambda q: fx.distort(q[:, 0] / q[:, 2], q[:, 1] / q[:, 2], K, k)
@@ -180,7 +180,7 @@ def outside_scene(sigma=0.0):
     vis = np.ones((4, 3), bool)
     vis[2, 1] = False
     s = frx.scene(7, 4, (0, 25, -25), ("FN", "P", "FN"), visible=vis, sigma=sigma, rows=12)
-    K = frx.CAMS["FN"][1]
+    K = sx.cam_K("FN")
     far = 1.02 * frx.THETA_D_MAX_FN * K[0, 0]
     kps = [[k.copy() for k in kl] for kl in s.kps]
     kps[0][1][5, :2] = [K[0, 2] + far, K[1, 2]]
@@ -194,7 +194,7 @@ def test_a_fisheye_view_with_a_pixel_outside_the_model():
     """The view is PNP_DEGENERATE, whatever its other rows say; its timestamp goes on with the two other cameras (1), or is left
     with one usable view, which is reported and takes no part (2).  The rig is the one the other views give, to the bit."""
     s, expect = outside_scene()
-    assert np.isnan(fisheye.undistort_points_host(s.kps[0][1][5:6, :2], *frx.CAMS["FN"][1:])).all()
+    assert np.isnan(fisheye.undistort_points_host(s.kps[0][1][5:6, :2], *sx.cam("FN"))).all()
     r, margin = solve(s, with_margin=True)
     assert r.view_status.tolist() == expect.tolist() and (r.view_points == np.where(s.visible, 12, 0)).all()
     assert r.status == rig.RIG_OK and r.stamps_used == 3 and r.points_used == 12 * 8 and margin >= MARGIN
@@ -260,7 +260,7 @@ def wide_scene(sigma=0.0):
 
 def test_the_edges_of_the_model():
     s = on_axis_scene()
-    K = frx.CAMS[s.cams[2]][1]
+    K = sx.cam_K(s.cams[2])
     for t in range(6):
         assert s.kps[2][t][3, :2].tolist() == [K[0, 2], K[1, 2]]          # the pixel is the principal point, exactly
     r, margin = solve(s, with_margin=True)

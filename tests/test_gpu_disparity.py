@@ -197,7 +197,7 @@ def _ulps(a, b):
 @pytest.mark.parametrize("shape", [(1, 1), (23, 131), (2, 23, 131)])
 def test_points_device_matches_host(dev, shape):
     R, T = rx.rig_RT("verge15", "B", "C")
-    r = rc.stereo_rectify_host(*sx.CAMS["B"], *sx.CAMS["C"], rx.SIZE, R, T)
+    r = rc.stereo_rectify_host(*sx.cam("B"), *sx.cam("C"), rx.SIZE, R, T)
     m = -16
     rng = np.random.default_rng(9)
     disp = rng.integers(16 * m, 16 * 64, shape).astype(np.int16)
@@ -258,7 +258,7 @@ def test_chain_from_distorted_frames_to_points(dev):
     of d), so the plane lies at a whole disparity, where the parabola's sub-pixel step has no bias by symmetry; between whole and
     half disparities a parabola through census costs is pulled towards the whole one (measured on the host at 1.0 m, 19.72 px: the
     median comes out at 19.875 px, 0.992 m), which is the definition's property and DESIGN 3.13's to state, not this gate's."""
-    (K0, d0), (K1, d1) = sx.CAMS["B"], sx.CAMS["C"]
+    (K0, d0), (K1, d1) = sx.cam("B"), sx.cam("C")
     R, T = rx.rig_RT("verge15", "B", "C")
     r = rc.stereo_rectify_host(K0, d0, K1, d1, rx.SIZE, R, T)
     assert r.axis == 0 and r.Tn < 0

@@ -126,7 +126,7 @@ def test_the_matcher_the_filter_and_the_points_replay_from_one_graph(dev):
     m = -3
     kw = dict(min_disparity=m, paths=8, **lc.SPECKLE)
     R, T = rx.rig_RT("verge15", "B", "C")
-    Q = rc.stereo_rectify_host(*sx.CAMS["B"], *sx.CAMS["C"], rx.SIZE, R, T).Q
+    Q = rc.stereo_rectify_host(*sx.cam("B"), *sx.cam("C"), rx.SIZE, R, T).Q
     first, swapped = lc.two_plane_batch(), lc.two_plane_batch(lc.REORDER)
     want_first, want_swapped = dp.sgm_host(*first, **kw), dp.sgm_host(*swapped, **kw)
     assert not np.array_equal(want_first, want_swapped)

@@ -15,6 +15,7 @@ import camera_exact as cx
 import fisheye_rig_exact as frx
 import fisheye_exact as fx
 import pool_cases
+import stereo_exact as sx
 from deepcharuco_amd import _lib, corner_pool, fisheye, pnp, rig, stereo
 from staged_exact import SENTINEL
 from test_fisheye_rig_host import class_scene
@@ -42,7 +43,7 @@ def test_rig_calibrate_models_pool(dev):
     kps = [[k.copy() for k in kl] for kl in s.kps]
     kps[0][5] = kps[0][5][:3]
     kps[1][1][4, 2] = cx.n_ids(s.board)
-    K = frx.CAMS["FN"][1]
+    K = sx.cam_K("FN")
     kps[0][6][2, :2] = [K[0, 2] - 1.02 * frx.THETA_D_MAX_FN * K[0, 0], K[1, 2]]
     cameras, dists = frx.cam_args(s)
     models = frx.models(s)
@@ -108,7 +109,7 @@ def test_stereo_calibrate_models_pool(dev):
     kps = [[k.copy() for k in kl] for kl in s.kps]
     kps[0][5] = kps[0][5][:3]
     kps[1][1][4, 2] = cx.n_ids(s.board)
-    K = frx.CAMS["FN"][1]
+    K = sx.cam_K("FN")
     kps[0][6][2, :2] = [K[0, 2] - 1.02 * frx.THETA_D_MAX_FN * K[0, 0], K[1, 2]]
     (K0, K1), (d0, d1) = frx.cam_args(s)
     B = 8

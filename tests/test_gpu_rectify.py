@@ -28,7 +28,7 @@ def dev():
 
 def _rectify(kind, c0, c1, alpha=None):
     R, T = rx.rig_RT(kind, c0, c1)
-    (K0, d0), (K1, d1) = sx.CAMS[c0], sx.CAMS[c1]
+    (K0, d0), (K1, d1) = sx.cam(c0), sx.cam(c1)
     return rc.stereo_rectify_host(K0, d0, K1, d1, rx.SIZE, R, T, alpha)
 
 
@@ -63,7 +63,7 @@ def test_map_device_matches_host(dev, i, kind):
     c0, c1 = rx.PAIRS[i % 3]
     r = _rectify(kind, c0, c1)
     for cam, Rc, P in ((c0, r.R1, r.P1), (c1, r.R2, r.P2)):
-        K, d = sx.CAMS[cam]
+        K, d = sx.cam(cam)
         _map_agrees(dev, K, d, Rc, P, W, H, f"{kind} camera {cam} 320x240")
         Ks = K.copy()
         Ks[:2] *= 41.0 / W                                                   # the camera of a 41 x 23 source
@@ -73,12 +73,12 @@ def test_map_device_matches_host(dev, i, kind):
 
 
 def test_map_sentinels_and_defaults(dev):
-    K, d = sx.CAMS["B"]
+    K, d = sx.cam("B")
     host, _ = _map_agrees(dev, K, d, R100, P_WIDE, 64, 48, "R of 100 degrees")
     out = host == rc.MAP_SENTINEL
     assert out.any() and not out.all()
     for cam in ("A", "B", "C"):                                              # R = NULL, P = NULL: cv2.undistort's map
-        K, d = sx.CAMS[cam]
+        K, d = sx.cam(cam)
         _map_agrees(dev, K, d, None, None, W, H, f"camera {cam}, R = NULL, P = NULL")
         _map_agrees(dev, K, d, None, np.c_[K, np.zeros(3)], 65, 3, f"camera {cam}, P = K as 3x4")
     pre = torch.full((19, 37, 2), 7, dtype=torch.int32, device=dev)
@@ -154,7 +154,7 @@ def test_remap_real_map_on_frames(dev):
     """A real rectification map (alpha = 0.5: some output pixels read outside) over nine 240 x 320 frames: 75 workgroups by two
     frame groups."""
     r = _rectify("verge15", "B", "C", alpha=0.5)
-    K, d = sx.CAMS["B"]
+    K, d = sx.cam("B")
     m = rc.undistort_rectify_map_host(K, d, r.R1, r.P1, W, H)
     frames = weights.synthetic_frames("board", 11, F + 1, H, W)
     got = rc.remap_device(torch.from_numpy(frames).to(dev), torch.from_numpy(m).to(dev), border=0)
@@ -215,7 +215,7 @@ def test_points_device_matches_host(dev, n):
         xy[0] = (40000.0, 30000.0)
     packed = _pool(dev, xy)
     for cam, R, P in (("B", r.R1, r.P1), ("C", r.R2, r.P2), ("A", r.R1, r.P1), ("B", None, None)):
-        K, d = sx.CAMS[cam]
+        K, d = sx.cam(cam)
         want = rc.rectify_points_host(xy.astype(np.float64), K, d, R, P)
         got = rc.rectify_points_pool(packed, 1, n, True, K, d, R, P)
         assert got.dtype == torch.float64 and tuple(got.shape) == (n, 2)
@@ -229,7 +229,7 @@ def test_points_behind_the_rectified_camera(dev):
     horizon z = 0 are left out of the pool: there the rectified pixel grows as 1 / z and its rounding as 1 / z^2, and 1e-9 px
     is a gate for pixels, not for points at infinity."""
     rng = np.random.default_rng(67)
-    K, d = sx.CAMS["C"]
+    K, d = sx.cam("C")
     xy = np.stack([rng.uniform(0, W, 400), rng.uniform(0, H, 400)], 1).astype(np.float32)
     n = rc.undistort_points_newton(xy.astype(np.float64), K, d)
     z = R100[2, 0] * n[:, 0] + R100[2, 1] * n[:, 1] + R100[2, 2]
@@ -246,7 +246,7 @@ def test_points_from_the_integer_rows(dev):
     n = 70
     cells = np.stack([rng.integers(0, W, n), rng.integers(0, H, n)], 1)
     packed = _pool(dev, rng.uniform(0, 200, (n, 2)), rows_xy=cells)
-    K, d = sx.CAMS["C"]
+    K, d = sx.cam("C")
     r = _rectify("small", "C", "A")
     got = rc.rectify_points_pool(packed, 1, n, False, K, d, r.R1, r.P1)
     _points_agree(got, rc.rectify_points_host(cells.astype(np.float64), K, d, r.R1, r.P1), "integer rows")
@@ -299,7 +299,7 @@ def test_chain_from_pools_to_epipolar_rows(dev, kind, c0, c1):
 
 def test_two_calls_give_equal_bits(dev):
     rng = np.random.default_rng(65)
-    K, d = sx.CAMS["C"]
+    K, d = sx.cam("C")
     r = _rectify("toe90", "C", "A")
     maps = [rc.undistort_rectify_map_device(K, d, r.R1, r.P1, W, H, device=dev) for _ in range(2)]
     assert torch.equal(maps[0], maps[1])
@@ -316,7 +316,7 @@ def test_remap_and_points_replay_from_a_graph(dev):
     """remap_device and rectify_points_pool captured in one linear graph replay to the eager bits (neither synchronises nor
     allocates when given its output)."""
     rng = np.random.default_rng(66)
-    K, d = sx.CAMS["B"]
+    K, d = sx.cam("B")
     r = _rectify("verge15", "B", "C", alpha=0.0)
     md = rc.undistort_rectify_map_device(K, d, r.R1, r.P1, W, H, device=dev)
     frames = torch.from_numpy(weights.synthetic_frames("board", 12, F + 1, H, W)).to(dev)

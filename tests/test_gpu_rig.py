@@ -293,7 +293,7 @@ def test_two_cameras_are_the_stereo_solver(dev):
     for sigma in (0.0, 0.3):
         s = rx.scene(63, 6, (0, 30), ("A", "B"), sigma=sigma)
         d = _device(s)
-        st = stereo.stereo_calibrate_device(s.kps[0], s.kps[1], *s.board, *sx.CAMS["A"], *sx.CAMS["B"])
+        st = stereo.stereo_calibrate_device(s.kps[0], s.kps[1], *s.board, *sx.cam("A"), *sx.cam("B"))
         g = {"R": float(np.abs(d.R[1] - st.R).max()), "T": float(np.linalg.norm(d.T[1] - st.T) / np.linalg.norm(st.T)),
              "P rot": max(cx.rot_gap(a, b) for a, b in zip(d.rvecs, st.rvecs)),
              "P t": float(np.max(np.linalg.norm(d.tvecs - st.tvecs, axis=1) / np.linalg.norm(st.tvecs, axis=1))),

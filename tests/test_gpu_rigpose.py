@@ -35,20 +35,13 @@ def dev():
     return torch.device("cuda", 0)
 
 
-def _args(s):
-    """(cameras, dists), and the models of a scene whose cameras have one each."""
-    if all(n in frx.CAMS for n in s.cams):
-        return frx.cam_args(s), dict(models=frx.models(s))
-    return rx.cam_args(s), {}
-
-
 def _host(s, **kw):
-    a, m = _args(s)
+    a, m = rx.entry_args(s)
     return rig.rig_pose_host_full(s.kps, *s.board, *a, px.rig_rt(s.X), with_margin=True, **m, **kw)
 
 
 def _device(s, **kw):
-    a, m = _args(s)
+    a, m = rx.entry_args(s)
     return rig.rig_pose_device(s.kps, *s.board, *a, px.rig_rt(s.X), **m, **kw)
 
 
@@ -140,7 +133,7 @@ def test_statuses_and_views_that_cannot_stand_alone(dev):
     kps[1][3] = np.zeros((0, 3))
     rm1 = s.board[1] - 1
     ids = np.arange(5) * rm1 + 2                                         # one board row: collinear
-    kps[1][4] = np.c_[cx.f64(sx.project_rig(cx.board_points(ids, *s.board), s.P[4], s.X[0], *sx.CAMS["B"])).astype(np.float32), ids]
+    kps[1][4] = np.c_[cx.f64(sx.project_rig(cx.board_points(ids, *s.board), s.P[4], s.X[0], *sx.cam("B"))).astype(np.float32), ids]
     s = s._replace(kps=kps)
     h, margin = _host(s)
     assert margin >= MARGIN

@@ -19,10 +19,10 @@ import camera_exact as cx
 import pool_cases
 import stereo_exact as sx
 from deepcharuco_amd import calib, corner_pool, pnp, stereo
+from stereo_exact import FALLBACK, MARGIN, REL
 
 pytestmark = pytest.mark.gpu
 
-REL, FALLBACK, MARGIN = 1e-9, 1e-6, 1e-6
 OK, FELL = 0, 1
 
 
@@ -165,7 +165,7 @@ def test_masks_made_on_the_device_compose(dev):
     straight into stereo_calibrate_pool; the host's come from solve_pnp_ransac_host_full."""
     from test_stereo_host import RANSAC, planted_scene
     s, good = planted_scene()
-    cams = (sx.CAMS[s.cam0], sx.CAMS[s.cam1])
+    cams = (sx.cam(s.cam0), sx.cam(s.cam1))
     packs, dmasks, hmasks = [], [], ([], [])
     for c, kps in enumerate((s.kps0, s.kps1)):
         packed, b, pool = corner_pool.pack_keypoints(kps, dev)

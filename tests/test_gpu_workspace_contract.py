@@ -907,7 +907,7 @@ def test_remap_map_and_rectified_points(dev):
     guards, against the host definitions by test_gpu_rectify's own comparisons."""
     from test_gpu_rectify import F, _map_agrees, _points_agree, _pool, _random_map, _rectify, _strided_source
     r = _rectify("verge15", "B", "C")
-    K, d = sx.CAMS["B"]
+    K, d = sx.cam("B")
     bufs = Bufs(dev, True)
     Ks, Ps = K.copy(), r.P1.copy()
     Ks[:2] *= 41.0 / rx.SIZE[0]

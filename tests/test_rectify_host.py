@@ -28,7 +28,7 @@ CASES = [(k, c0, c1) for k in rx.RIGS for c0, c1 in rx.PAIRS]
 
 def _rectify(kind, c0, c1, alpha=None):
     R, T = rx.rig_RT(kind, c0, c1)
-    (K0, d0), (K1, d1) = sx.CAMS[c0], sx.CAMS[c1]
+    (K0, d0), (K1, d1) = sx.cam(c0), sx.cam(c1)
     return rc.stereo_rectify_host(K0, d0, K1, d1, rx.SIZE, R, T, alpha), R, T
 
 
@@ -48,19 +48,19 @@ def test_rectify_properties(kind, c0, c1):
     assert r.axis == (1 if kind == "vertical" else 0)
     assert r.Tn == t[r.axis] and abs(abs(r.Tn) - np.linalg.norm(T)) <= 1e-14 * np.linalg.norm(T)
     assert r.P2[r.axis, 3] == r.Tn * r.P1[0, 0] and np.array_equal(np.delete(r.P2.ravel(), 4 * r.axis + 3), np.delete(r.P1.ravel(), 4 * r.axis + 3))
-    assert r.P1[0, 0] == r.P1[1, 1] == min(sx.CAMS[c0][0][1, 1], sx.CAMS[c1][0][1, 1])
+    assert r.P1[0, 0] == r.P1[1, 1] == min(sx.cam_K(c0)[1, 1], sx.cam_K(c1)[1, 1])
 
 
 def test_parallel_rig_is_left_alone():
     """R = I with T along x: both rectifying rotations are the identity, exactly."""
     for tx in (-0.06, 0.11):
-        r = rc.stereo_rectify_host(sx.K_A, None, sx.K_B, sx.CAMS["B"][1], rx.SIZE, np.eye(3), [tx, 0.0, 0.0])
+        r = rc.stereo_rectify_host(sx.K_A, None, sx.K_B, sx.cam_coeffs("B"), rx.SIZE, np.eye(3), [tx, 0.0, 0.0])
         assert np.array_equal(r.R1, np.eye(3)) and np.array_equal(r.R2, np.eye(3))
         assert r.axis == 0 and r.Tn == tx
 
 
 def test_refused_arguments():
-    K, d = sx.CAMS["B"]
+    K, d = sx.cam("B")
     with pytest.raises(ValueError):
         rc.stereo_rectify_host(K, d, K, d, rx.SIZE, np.eye(3), [0.0, 0.0, 0.0])
     with pytest.raises(ValueError):
@@ -77,7 +77,7 @@ def test_refused_arguments():
 def test_newton_undistortion_round_trip(cam):
     """Newton's result, pushed through the exact distortion model, returns to the pixel within 1e-12 px on a 7-px grid over the
     frame; the documented 5 fixed-point rounds, held to the same assertion, miss it by nine orders of magnitude."""
-    K, d = sx.CAMS[cam]
+    K, d = sx.cam(cam)
     g = rx.pixel_grid(7)
     n = rc.undistort_points_newton(g, K, d)
     assert np.isfinite(n).all()
@@ -93,7 +93,7 @@ def test_newton_without_distortion_and_out_of_reach():
     g = rx.pixel_grid(31)
     n = rc.undistort_points_newton(g, sx.K_A, None)
     assert np.array_equal(n, np.stack([(g[:, 0] - sx.K_A[0, 2]) / sx.K_A[0, 0], (g[:, 1] - sx.K_A[1, 2]) / sx.K_A[1, 1]], 1))
-    K, d = sx.CAMS["B"]                         # far outside the frame the model of camera B has no inverse near the start
+    K, d = sx.cam("B")                          # far outside the frame the model of camera B has no inverse near the start
     out = rc.rectify_points_host(np.array([[40000.0, 30000.0], [100.0, 100.0]]), K, d)
     assert np.isnan(out[0]).all() and np.isfinite(out[1]).all()
     behind = rc.rectify_points_host(np.array([[160.0, 120.0]]), K, d, f64(cx.rotation([0.0, np.deg2rad(100.0), 0.0])))
@@ -105,7 +105,7 @@ def test_rectified_projection_against_exact(cam):
     """Exact pixels of known normalised points -> rectify_points_host returns the exact rectified projection of those points.
     1e-11 px: the pixels are rounded to float64 (4e-14 px at 320), Newton returns through the model to 8e-14 px, and the rectified
     camera magnifies by at most P00 / fx * (1 + tan^2) < 4 on this grid and rotation."""
-    K, d = sx.CAMS[cam]
+    K, d = sx.cam(cam)
     r, _, _ = _rectify("verge15", cam, "A" if cam != "A" else "B")
     n = np.stack([(g - c) / f for g, c, f in zip(rx.pixel_grid(13).T, (K[0, 2], K[1, 2]), (K[0, 0], K[1, 1]))], 1) * 0.8
     pix = f64(cx.distort(_w(n[:, 0]), _w(n[:, 1]), K, cx.dist8(d)))
@@ -121,7 +121,7 @@ def test_rectified_projection_against_exact(cam):
 def test_epipolar_rows_and_depth_under_the_true_rig(kind, c0, c1):
     s = rx.scene(kind, c0, c1)
     r, _, _ = _rectify(kind, c0, c1)
-    (K0, d0), (K1, d1) = sx.CAMS[c0], sx.CAMS[c1]
+    (K0, d0), (K1, d1) = sx.cam(c0), sx.cam(c1)
     gap, err = rx.epipolar_and_depth(s, r, rc.reproject_to_3d, lambda t, i, p: rc.rectify_points_host(p, K0, d0, r.R1, r.P1),
                                      lambda t, i, p: rc.rectify_points_host(p, K1, d1, r.R2, r.P2))
     print(f"{kind} {c0}/{c1}: epipolar gap {gap:.3e} px, 3-D error {err:.3e}")
@@ -143,7 +143,7 @@ def test_q_is_the_depth_of_a_disparity():
 def test_alpha(kind, c0, c1):
     """alpha = 0: no output pixel reads outside the source; alpha = 1: no source border pixel falls outside the output; f falls
     monotonically in between."""
-    cams = (sx.CAMS[c0], sx.CAMS[c1])
+    cams = (sx.cam(c0), sx.cam(c1))
     r0, _, _ = _rectify(kind, c0, c1, 0.0)
     for (K, d), Rc, P in zip(cams, (r0.R1, r0.R2), (r0.P1, r0.P2)):
         m = rc.undistort_rectify_map_host(K, d, Rc, P, W, H, quantised=False)
@@ -173,7 +173,7 @@ MAP_CASES = [("small", "A", "B"), ("verge15", "B", "C"), ("vertical", "C", "A")]
 @pytest.mark.parametrize("kind,c0,c1", MAP_CASES)
 def test_map_against_exact(kind, c0, c1):
     r, _, _ = _rectify(kind, c0, c1)
-    for (K, d), Rc, P in zip((sx.CAMS[c0], sx.CAMS[c1]), (r.R1, r.R2), (r.P1, r.P2)):
+    for (K, d), Rc, P in zip((sx.cam(c0), sx.cam(c1)), (r.R1, r.R2), (r.P1, r.P2)):
         m = rc.undistort_rectify_map_host(K, d, Rc, P, W, H, quantised=False)
         q = rc.undistort_rectify_map_host(K, d, Rc, P, W, H)
         ex = rx.map_exact(K, d, Rc, P, W, H)
@@ -186,7 +186,7 @@ def test_map_against_exact(kind, c0, c1):
 
 
 def test_map_identity_sentinel_and_sizes():
-    K, d = sx.CAMS["B"]
+    K, d = sx.cam("B")
     m = rc.undistort_rectify_map_host(sx.K_A, None, None, None, 37, 19)             # no distortion, R = I, P = K: the identity
     u, v = np.meshgrid(np.arange(37), np.arange(19))
     assert np.array_equal(m[..., 0], 32 * u) and np.array_equal(m[..., 1], 32 * v)

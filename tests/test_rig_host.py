@@ -120,7 +120,7 @@ def test_two_cameras_are_the_stereo_definition(sigma):
     kps = [list(s.kps[0]), list(s.kps[1])]
     kps[0][2] = kps[0][2][:3]                                            # TOO_FEW: the timestamp is not used by either
     r = rig.rig_calibrate_host_full(kps, *s.board, *rx.cam_args(s))
-    h = stereo.stereo_calibrate_host_full(kps[0], kps[1], *s.board, *sx.CAMS["A"], *sx.CAMS["B"])
+    h = stereo.stereo_calibrate_host_full(kps[0], kps[1], *s.board, *sx.cam("A"), *sx.cam("B"))
     g = {"R": float(np.abs(r.R[1] - h.R).max()), "T": float(np.linalg.norm(r.T[1] - h.T) / np.linalg.norm(h.T)),
          "P": float(max(np.abs(r.rvecs - h.rvecs).max(), (np.linalg.norm(r.tvecs - h.tvecs, axis=1)).max() / np.linalg.norm(h.tvecs[0]))),
          "rms": abs(r.rms - h.rms) / h.rms, "view rms": float(np.abs(r.view_rms - h.view_rms).max())}
@@ -227,7 +227,7 @@ def test_rig_pair_meets_the_epipolar_constraint():
     same board points in both, their distance from the other's epipolar line through rig_pair's F, in pixels."""
     s = chain_scene()
     r = _solve(s)
-    K1, K2 = sx.CAMS[s.cams[1]][0], sx.CAMS[s.cams[2]][0]
+    K1, K2 = sx.cam_K(s.cams[1]), sx.cam_K(s.cams[2])
     R, T, E, F = rig.rig_pair(r, 1, 2, K1, K2)
     obj = cx.board_points(np.arange(cx.n_ids(s.board)), *s.board)
     w = 0.0

@@ -14,24 +14,18 @@ import rig_exact as rx
 import rigpose_exact as px
 import stereo_exact as sx
 from deepcharuco_amd import _lm, fisheye, pnp, rig
+from stereo_exact import MARGIN, REL
 from test_fisheye_rig_host import CLASSES as MIXED
 from test_fisheye_rig_host import outside_scene
-from test_gpu_stereo import MARGIN, REL
 from test_rig_host import CHAIN4, FAN3, FAN4, TRUTH_R, TRUTH_T, chain_scene
 
 CAMS8 = dict(angles=tuple(np.linspace(-35, 35, 8).tolist()), cams=("A", "B", "C", "A4") * 2)
 FEW, DEG, OK = pnp.PNP_TOO_FEW, pnp.PNP_DEGENERATE, pnp.PNP_OK
 
 
-def _args(s):
-    if all(n in frx.CAMS for n in s.cams):
-        return frx.cam_args(s), dict(models=frx.models(s))
-    return rx.cam_args(s), {}
-
-
 def _solve(s, X=None, **kw):
     """rig_pose_host_full on the scene with its true rig (or X) as (R, T)."""
-    a, m = _args(s)
+    a, m = rx.entry_args(s)
     return rig.rig_pose_host_full(s.kps, *s.board, *a, px.rig_rt(s.X if X is None else X), **m, **kw)
 
 
@@ -125,7 +119,7 @@ def test_the_calibration_s_own_board_poses_come_back(name):
     worst = 0.0
     for seed in (2, 3, 4):
         s = CALIBRATED[name](seed)
-        a, m = _args(s)
+        a, m = rx.entry_args(s)
         c = rig.rig_calibrate_host_full(s.kps, *s.board, *a, **m)
         assert c.status == rig.RIG_OK
         r = rig.rig_pose_host_full(s.kps, *s.board, *a, c, **m)
@@ -145,7 +139,7 @@ def test_camera_0_alone_is_its_pnp():
     s = rx.scene(5, 4, sigma=0.3, rows=15, **FAN3)
     for t in range(4):
         r = _solve(_only(s, t, {0}))
-        st, pose = pnp.solve_pnp_host_full(s.kps[0][t], *s.board, *sx.CAMS["A"])
+        st, pose = pnp.solve_pnp_host_full(s.kps[0][t], *s.board, *sx.cam("A"))
         gap = max(cx.rot_gap(r.rvec[0], pose[:3]), float(np.linalg.norm(r.tvec[0] - pose[3:6]) / np.linalg.norm(pose[3:6])))
         print(f"camera 0 alone, timestamp {t}: gap to solve_pnp_host_full {gap:.2e}, steps {int(r.iterations[0])} after its {int(pose[7])}")
         assert r.status[0] == st == OK and r.seed[0] == 0 and r.rows[0] == 15 and gap <= REL
@@ -155,10 +149,10 @@ def test_camera_0_alone_is_its_pnp():
 @pytest.mark.parametrize("mixed", [False, True])
 def test_another_camera_alone_is_its_pnp_taken_through_the_rig(mixed):
     s = frx.scene(5, 3, sigma=0.3, rows=15, **MIXED["fan3 F/P/F"]) if mixed else rx.scene(5, 3, sigma=0.3, rows=15, **FAN3)
-    (cameras, dists), m = _args(s)
+    (cameras, dists), m = rx.entry_args(s)
     for t, c in ((0, 1), (1, 2), (2, 1)):
         r = _solve(_only(s, t, {c}))
-        if mixed and frx.CAMS[s.cams[c]][0] == "fisheye":
+        if mixed and sx.cam_model(s.cams[c]) == "fisheye":
             st, pose = fisheye.solve_pnp_fisheye_host_full(s.kps[c][t], *s.board, cameras[c], dists[c])
         else:
             st, pose = pnp.solve_pnp_host_full(s.kps[c][t], *s.board, cameras[c], dists[c])
@@ -176,7 +170,7 @@ def test_another_camera_alone_is_its_pnp_taken_through_the_rig(mixed):
 def _collinear_view(s, t, c, n=5):
     """n noisy rows of one board line for view (c, t), c >= 1 of a pinhole scene."""
     ids = np.arange(n) * (s.board[1] - 1) + 2
-    img = cx.f64(sx.project_rig(cx.board_points(ids, *s.board), s.P[t], s.X[c - 1], *sx.CAMS[s.cams[c]]))
+    img = cx.f64(sx.project_rig(cx.board_points(ids, *s.board), s.P[t], s.X[c - 1], *sx.cam(s.cams[c])))
     img = img + np.random.default_rng([5, t, c]).normal(scale=0.3, size=img.shape)
     return np.c_[img.astype(np.float32).astype(np.float64), ids]
 
@@ -230,7 +224,7 @@ def test_a_weak_camera_0_does_not_seed_the_solve(seed):
     cams = rig._cameras(*rx.cam_args(s))[0]
     views = px.views_of(s, 0)
     rows = rig._rows_of([[(c, o, i.astype(np.float32)) for c, o, i in views]], 3)
-    p0 = pnp.solve_pnp_host_full(s.kps[0][0], *s.board, *sx.CAMS["A"])[1][:6]
+    p0 = pnp.solve_pnp_host_full(s.kps[0][0], *s.board, *sx.cam("A"))[1][:6]
     st0, q0, _, _ = _lm.refine_pose(lambda q, jac: rig._joint(rows, cams, s.X, q, jac), p0, pnp.LM_MAX_ITER, pnp.LM_EPS)
     c_res = px.cost(views, s, s.X, np.r_[r.rvec[0], r.tvec[0]])
     c_0 = px.cost(views, s, s.X, q0) if st0 == OK else math.inf
@@ -248,7 +242,7 @@ def test_the_joint_pose_is_no_worse_than_camera_0_s():
     for seed in range(24):
         s = rx.scene(100 + seed, 1, sigma=0.3, **FAN3)
         r = _solve(s)
-        ok, _, tv = pnp.solve_pnp_host(s.kps[0][0], *s.board, *sx.CAMS["A"])
+        ok, _, tv = pnp.solve_pnp_host(s.kps[0][0], *s.board, *sx.cam("A"))
         assert r.status[0] == OK and ok
         joint.append(float(np.linalg.norm(r.tvec[0] - s.P[0, 3:])))
         own.append(float(np.linalg.norm(tv.ravel() - s.P[0, 3:])))
@@ -293,7 +287,7 @@ def test_a_fisheye_view_with_a_pixel_outside_the_model_does_not_contribute():
     """test_fisheye_rig_host's scene: view (camera 0, timestamp 1) and view (camera 2, timestamp 2) hold a pixel no direction
     projects to.  Neither contributes a row; their timestamps are solved from the other cameras."""
     s, expect = outside_scene(sigma=0.3)
-    (cameras, dists), m = _args(s)
+    (cameras, dists), m = rx.entry_args(s)
     r = _solve(s)
     assert r.view_status.tolist() == expect.tolist() and (r.view_points == np.where(s.visible, 12, 0)).all()
     assert (r.status == OK).all() and r.rows.tolist() == [36, 24, 12, 36] and r.seed[1] != 0 and r.seed[2] == 0

@@ -44,7 +44,7 @@ def test_analytic_jacobian_matches_exact_finite_differences(rig, c0, c1):
     P = s.P + rng.normal(scale=1e-2, size=s.P.shape) * np.r_[1, 1, 1, [np.linalg.norm(s.P[0, 3:])] * 3]
     views = sx.pool_views(s)
     rows = stereo._rows_of(views)
-    cams = [(pnp._camera(K), pnp._dist(d)) for K, d in (sx.CAMS[c0], sx.CAMS[c1])]
+    cams = [(pnp._camera(K), pnp._dist(d)) for K, d in (sx.cam(c0), sx.cam(c1))]
     res, JX, JP = stereo._evaluate(rows, cams, X, P, True)
     M, N = rows.obj.shape[0], len(views)
     J = np.zeros((2 * M, 6 + 6 * N))
@@ -188,7 +188,7 @@ def test_epipolar_constraint_on_noise_free_points():
     off on this scene."""
     s = sx.scene(1, 6, "toe90", sx.BOARD_S, "A", "B")
     r = _solve(s)
-    (K0, _), (K1, _) = sx.CAMS[s.cam0], sx.CAMS[s.cam1]
+    (K0, _), (K1, _) = sx.cam(s.cam0), sx.cam(s.cam1)
     obj = cx.board_points(np.arange(cx.n_ids(s.board)), *s.board)
 
     def worst(F):
@@ -244,7 +244,7 @@ def planted_scene():
 def test_masks_from_the_consensus_solver():
     s, good = planted_scene()
     masks = ([], [])
-    for c, (kps, (K, d)) in enumerate(zip((s.kps0, s.kps1), (sx.CAMS[s.cam0], sx.CAMS[s.cam1]))):
+    for c, (kps, (K, d)) in enumerate(zip((s.kps0, s.kps1), (sx.cam(s.cam0), sx.cam(s.cam1)))):
         for kp in kps:
             ret, _, _, m = pnp.solve_pnp_ransac_host(kp, *s.board, K, d, **RANSAC)
             assert ret

@@ -8,7 +8,10 @@ and are the device wrappers as fast through this tree's Python as through that o
              models with a fisheye camera, every failure status those tests reach, the cv2-style tuples; and (pose_scenes) those of
              tests/test_{pnp,pnp_ransac,fisheye_ransac,rectify,rigpose,pose_exact}_host.py: the single-view pose solvers of both
              models plain and behind the consensus search, the rig pose, the maps, the rectified points, the rectifications, and the
-             projection texts called directly with their Jacobians.
+             projection texts called directly with their Jacobians.  A second block, "oracles" (oracle_scenes), does the same for
+             the exact modules those tests are held to: their scene builders and their residuals, costs, finite-difference Jacobians
+             and stationarity.  With --suite it also holds the wall time of the six host test files that use them, three runs of
+             each tree, alternating; this tree's median must be inside the parent's own spread.
   --time     on a GPU: stereo_calibrate_pool, rig_calibrate_pools (C = 2, 4, 8), calibrate_charuco_pool and calibrate_fisheye_pool end
              to end on tools/rig_old_new.py's shapes, and the per-batch wrappers of both models (solve_pnp_*pool, solve_pnp_*ransac_pool,
              rectify_points_*pool, undistort_rectify_map_*device) on its 4,096 views with out / workspace preallocated, through both
@@ -16,7 +19,7 @@ and are the device wrappers as fast through this tree's Python as through that o
              the same), seven rounds each, alternating; per process the median of 9 calls after a warm-up.  The margin is the spread
              (max - min) of the parent's own process medians.
 The other tree is --base-tree, or without it the parent commit unpacked with git archive into a scratch directory.  Prints a
-summary and merges its block ("host" or "time") into --out.
+summary and merges its blocks ("host" and "oracles", or "time") into --out.
 
     python tools/host_old_new.py --out profiles/host_old_new.json
     git archive HEAD^ | tar -x -C build/parent && python tools/host_old_new.py --time --base-tree build/parent --out profiles/host_old_new.json
@@ -36,6 +39,8 @@ def flat(key, v, out):
         for i, x in enumerate(v):
             flat(f"{key}/{i}", x, out)
     elif isinstance(v, np.ndarray):
+        if v.dtype == np.longdouble and v.itemsize == 16:      # an x87 long double is 10 bytes of value and 6 of padding
+            v = np.ascontiguousarray(v).view(np.uint8).reshape(v.shape + (16,))[..., :10]
         out[key] = f"{v.dtype} {v.shape} {hashlib.sha256(np.ascontiguousarray(v).tobytes()).hexdigest()}"
     elif isinstance(v, (float, np.floating)):
         out[key] = "float " + float(v).hex()
@@ -168,6 +173,7 @@ def pose_scenes(add):
     import test_fisheye_host as tf, test_fisheye_ransac_host as tfa, test_fisheye_rig_host as tfr, test_pnp_host as tp
     import test_pnp_ransac_host as tpa, test_pose_exact_host as tpe, test_rectify_host as trc, test_rigpose_host as trp
     from deepcharuco_amd import calib, fisheye as fe, pnp, rectify as rc, rig, stereo
+    pin = lambda c: sx.cam_args(sx.Scene(*[None] * 5, c, c, ""))[:2]     # (K, dist) of a name, by a function both trees have
     # ---- pnp: 0 / 4 / 5 / 8 coefficients, clean, 0.5 px and 30 px noise, plain and behind the consensus search
     for name, dist in (("none", None), ("0", np.zeros(0)), ("4", tp.DIST5[:4]), ("5", tp.DIST5), ("8", tp.DIST8)):
         for j, sigma in enumerate((0.0, 0.5, 30.0)):
@@ -284,19 +290,19 @@ def pose_scenes(add):
     for kind, c0, c1 in trc.MAP_CASES:
         r = trc._rectify(kind, c0, c1)[0]
         for c, Rc, P in ((c0, r.R1, r.P1), (c1, r.R2, r.P2)):
-            K, d = sx.CAMS[c]
+            K, d = pin(c)
             for q in (True, False):
                 add(f"map/{kind}/{c}/{q}", lambda K=K, d=d, Rc=Rc, P=P, q=q: rc.undistort_rectify_map_host(K, d, Rc, P, 64, 48, quantised=q))
             add(f"points/{kind}/{c}", lambda K=K, d=d, Rc=Rc, P=P: rc.rectify_points_host(pix, K, d, Rc, P))
     for c in ("A", "B", "C", "A4"):
-        K, d = sx.CAMS[c]
+        K, d = pin(c)
         for q in (True, False):
             add(f"map/plain/{c}/{q}", lambda K=K, d=d, q=q: rc.undistort_rectify_map_host(K, d, None, None, 64, 48, quantised=q))
             add(f"map/behind/{c}/{q}", lambda K=K, d=d, q=q: rc.undistort_rectify_map_host(K, d, R100, Pw, 64, 48, quantised=q))
         add(f"points/plain/{c}", lambda K=K, d=d: (rc.rectify_points_host(pix, K, d), rc.rectify_points_host(pix, K, d, R100), rc.undistort_points_newton(pix, K, d)))
     add("map/ties", lambda: rc.undistort_rectify_map_host(np.eye(3), None, None, np.diag([64.0, 64.0, 1.0]), 8, 1))
-    add("map/raises/P", lambda: rc.undistort_rectify_map_host(*sx.CAMS["B"], None, np.eye(4), 8, 8))
-    add("map/raises/size", lambda: rc.undistort_rectify_map_host(*sx.CAMS["B"], None, None, 0, 8))
+    add("map/raises/P", lambda: rc.undistort_rectify_map_host(*pin("B"), None, np.eye(4), 8, 8))
+    add("map/raises/size", lambda: rc.undistort_rectify_map_host(*pin("B"), None, None, 0, 8))
     add("points/raises/dist", lambda: rc.rectify_points_host(pix, sx.K_A, np.zeros(12)))
     fpix = np.concatenate([pix, [[250.0, 240.0], [400.0, 240.0], [319.5 + 150.0 * 1.6, 239.5]]])
     for cam, (K, k) in zip(tf.CAM_IDS, tf.CAMS):
@@ -315,7 +321,7 @@ def pose_scenes(add):
         Rr, Tr = trc.rx.rig_RT(kind, c0, c1)
         add(f"fisheye/rectify/{kind}", lambda Rr=Rr, Tr=Tr: (fe.stereo_rectify_fisheye_host(*tf.CAMS[1], *tf.CAMS[3], fx.SIZE, Rr, Tr),
                                                              fe.stereo_rectify_fisheye_host(*tf.CAMS[0], *tf.CAMS[1], fx.SIZE, Rr, Tr, focal=120.0)))
-    add("rectify/raises/T", lambda: rc.stereo_rectify_host(*sx.CAMS["B"], *sx.CAMS["B"], trc.rx.SIZE, np.eye(3), [0.0, 0.0, 0.0]))
+    add("rectify/raises/T", lambda: rc.stereo_rectify_host(*pin("B"), *pin("B"), trc.rx.SIZE, np.eye(3), [0.0, 0.0, 0.0]))
     add("fisheye/rectify/raises/focal", lambda: fe.stereo_rectify_fisheye_host(*tf.CAMS[1], *tf.CAMS[3], fx.SIZE, np.eye(3), [0.1, 0, 0], focal=0.0))
     # ---- the texts that move, called directly with the Jacobian on 40 random points
     rng = np.random.default_rng(2718)
@@ -346,16 +352,89 @@ def pose_scenes(add):
         add(f"text/fisheye.project_points_host/{cam}", lambda K=K, k=k: (fe.project_points_host(obj, p[:3], p[3:], K, k, jacobian=True),
                                                                           fe.project_points_host(np.r_[obj, [[0, 0, -9.0]]], p[:3], p[3:], K, k)))
 
+def oracle_scenes():
+    """The exact modules of tests/ themselves, which scenes() never calls: their scene builders on small scenes (three timestamps,
+    8 rows), and residuals, cost, jacobian_fd and stationarity of every module at the scene's truth and at one perturbed point,
+    long-double arrays by their bytes.  Only names and signatures that both trees have."""
+    import camera_exact as cx, fisheye_rig_exact as frx, rig_exact as rx, rigpose_exact as px, stereo_exact as sx
+    import test_fisheye_rig_host as tfr, test_rig_host as tr
+    out = []
+    add = lambda name, call: out.append((name, call))
+    rng = np.random.default_rng(99)
+    off = lambda v: v + 1e-3 * rng.uniform(-1, 1, np.shape(v)) * np.r_[1, 1, 1, [np.linalg.norm(np.reshape(v, (-1, 6))[0, 3:])] * 3]
+
+    def costs(key, mod, views, s, X, P):
+        for at, x, p in (("truth", X, P), ("off", off(X), off(P))):
+            for f in ("residuals", "cost", "jacobian_fd", "stationarity"):
+                add(f"{key}/{f}/{at}", lambda f=f, x=x, p=p: getattr(mod, f)(views, s, x, p))
+
+    stereo = {"small": sx.scene(1, 3, "small", rows=8), "toe90": sx.scene(2, 3, "toe90", sx.BOARD_S, "B", "C", rows=8, disjoint=True),
+              "r170": sx.scene(3, 3, "r170", sx.BOARD_L, "C", "A4", sigma=0.3, rows=[(8, 6), (7, 8), (8, 8)])}
+    for name, s in stereo.items():
+        masks = ([np.arange(len(k)) % 3 > 0 for k in s.kps0], None)
+        views = sx.pool_views(s)
+        add(f"stereo/{name}/scene", lambda s=s: s)
+        add(f"stereo/{name}/pool_views", lambda s=s, masks=masks: (sx.pool_views(s), sx.pool_views(s, [2, 0], masks)))
+        costs(f"stereo/{name}", sx, views, s, s.X, s.P)
+        (o, i), (K, d) = views[1][:2], sx.cam_args(s)[:2]
+        for at, p in (("truth", s.P[1]), ("off", off(s.P[1]))):
+            for f in ("residuals", "cost", "jacobian_fd", "stationarity"):
+                add(f"camera/{name}/{f}/{at}", lambda f=f, a=(o, i, p, K, d): getattr(cx, f)(*a))
+    rigs = {"fan3": (rx, rx.scene(1, 3, rows=8, **tr.FAN3)),
+            "chain4": (rx, rx.scene(2, 3, rows=8, visible=rx.chain_visibility(4, 1), **tr.CHAIN4)),
+            "fan3/rows": (rx, rx.scene(3, 3, sigma=0.3, rows=[[8, 6, 7], [7, 8, 6], [6, 7, 8]], **tr.FAN3)),
+            "models/rig=": (frx, frx.scene(4, 3, rows=8, rig=frx.make_rig((0, 20, -20), sx.BOARD_S, tfr.FAN3["cams"]), **tfr.FAN3))}
+    for name, kw in tfr.CLASSES.items():
+        rigs[f"models/{name}"] = (frx, tfr.class_scene(name, 1, n_stamps=3, rows=8, **({"visible": rx.chain_visibility(4, 1)} if "visible" in kw else {})))
+    for name, (mod, s) in rigs.items():
+        used = list(range(3))
+        views = rx.pool_views(s, used)
+        masks = [None] + [[np.arange(len(k)) % 3 > 0 for k in kl] for kl in s.kps[1:]]
+        add(f"rig/{name}/scene", lambda s=s: s)
+        add(f"rig/{name}/pool_views", lambda s=s, masks=masks: (rx.pool_views(s, [0, 1, 2]), rx.pool_views(s, [2, 0], masks)))
+        costs(f"rig/{name}", mod, views, s, s.X, s.P)
+        v1 = px.views_of(s, 1)
+        add(f"rigpose/{name}/views_of", lambda s=s, masks=masks: (px.views_of(s, 1), px.views_of(s, 2, masks, keep=(0, 1))))
+        for at, p in (("truth", s.P[1]), ("off", off(s.P[1]))):
+            for f in ("residuals", "cost", "jacobian_fd", "stationarity"):
+                add(f"rigpose/{name}/{f}/{at}", lambda f=f, a=(v1, s, s.X, p): getattr(px, f)(*a))
+    s = rigs["models/fan3 F/P/F"][1]
+    moved = frx.with_pose(s, 1, off(s.P[1]))
+    add("rig/with_pose", lambda: moved)
+    add("rig/on_axis", lambda: frx.on_axis(s, 2, 1, 3))
+    add("rig/theta_max", lambda: [frx.theta_max(s, t, c) for t in range(3) for c in range(3)])
+    return out
+
 def host_worker(path):
-    got, names = {}, []
-    for name, call in scenes():
-        try:
-            r = call()
-        except Exception as e:                       # what a scene raises is part of what it returns
-            r = ("raised", type(e).__name__, str(e))
-        flat(name, r, got)
-        names.append(name)
-    json.dump({"scenes": names, "fields": got}, open(path, "w"))
+    doc = {}
+    for block, build in (("host", scenes), ("oracles", oracle_scenes)):
+        got, names = {}, []
+        for name, call in build():
+            try:
+                r = call()
+            except Exception as e:                       # what a scene raises is part of what it returns
+                r = ("raised", type(e).__name__, str(e))
+            flat(name, r, got)
+            names.append(name)
+        doc[block] = {"scenes": names, "fields": got}
+    json.dump(doc, open(path, "w"))
+
+SUITE = ["tests/test_stereo_host.py", "tests/test_rig_host.py", "tests/test_fisheye_rig_host.py", "tests/test_rigpose_host.py",
+         "tests/test_fisheye_ransac_host.py", "tests/test_rectify_host.py"]
+
+def suite_seconds(trees, runs=3):
+    """Wall seconds of the host tests that live on these oracles, ``runs`` of each tree, alternating -> block"""
+    got = {n: [] for n in trees}
+    for _ in range(runs):
+        for name, tree in trees.items():
+            t0 = time.perf_counter()
+            r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", *SUITE], cwd=tree, capture_output=True, text=True)
+            got[name].append(round(time.perf_counter() - t0, 2))
+            print(name, got[name][-1], r.stdout.strip().splitlines()[-1], flush=True)
+            assert r.returncode == 0, r.stdout[-2000:]
+    p, t = got["parent"], got["this"]
+    return {"parent_s": p, "this_s": t, "parent_spread_s": round(max(p) - min(p), 2),
+            "inside": float(np.median(t)) <= float(np.median(p)) + (max(p) - min(p))}
 
 def timed(call):
     import torch
@@ -404,6 +483,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--base-tree", default=None, help="the other tree (default: the parent commit, unpacked with git archive)")
     ap.add_argument("--time", action="store_true", help="time the device wrappers instead (needs a GPU)")
+    ap.add_argument("--suite", action="store_true", help="also time the host tests of the multi-camera oracles in both trees, three runs each")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     tmp = tempfile.mkdtemp()
@@ -414,20 +494,25 @@ def main():
         subprocess.run(f"git -C {REPO} archive HEAD^ | tar -x -C {base}", shell=True, check=True)
     trees = {"parent": base, "this": REPO}
     if not a.time:
-        got, names = {}, {}
+        docs, blocks, moved = {}, {}, []
         for name, tree in trees.items():
             child(tree, "--host-worker", os.path.join(tmp, name + ".json"))
-            doc = json.load(open(os.path.join(tmp, name + ".json")))
-            got[name], names[name] = doc["fields"], doc["scenes"]
-        assert names["parent"] == names["this"]
-        keys = sorted(set(got["parent"]) | set(got["this"]))
-        moved = [k for k in keys if got["parent"].get(k) != got["this"].get(k)]
-        block = {"scenes": len(names["this"]), "fields": len(keys),
-                 "fields_moved": moved, "raised": sorted(k[:-2] for k in keys if k.endswith("/0") and got["this"].get(k) == "str 'raised'"),
-                 "numpy": np.__version__}
-        for k in moved:
-            print("MOVED", k, got["parent"].get(k), got["this"].get(k))
-        print(json.dumps({k: v for k, v in block.items()}, indent=1))
+            docs[name] = json.load(open(os.path.join(tmp, name + ".json")))
+        for key in ("host", "oracles"):
+            got, names = {n: d[key]["fields"] for n, d in docs.items()}, {n: d[key]["scenes"] for n, d in docs.items()}
+            assert names["parent"] == names["this"]
+            keys = sorted(set(got["parent"]) | set(got["this"]))
+            differ = [k for k in keys if got["parent"].get(k) != got["this"].get(k)]
+            blocks[key] = {"scenes": len(names["this"]), "fields": len(keys),
+                           "fields_moved": differ, "raised": sorted(k[:-2] for k in keys if k.endswith("/0") and got["this"].get(k) == "str 'raised'"),
+                           "numpy": np.__version__}
+            for k in differ:
+                print("MOVED", k, got["parent"].get(k), got["this"].get(k))
+            moved += differ
+        if a.suite:
+            blocks["oracles"]["host_tests"] = suite_seconds(trees)
+            moved += [] if blocks["oracles"]["host_tests"]["inside"] else ["host_tests"]
+        print(json.dumps(blocks, indent=1))
     else:
         sys.path[:0] = [REPO, os.path.join(REPO, "tests"), os.path.join(REPO, "tools")]
         import fisheye_probe as fp, rig_old_new as ron
@@ -452,7 +537,7 @@ def main():
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         doc = json.load(open(a.out)) if os.path.exists(a.out) else {}
-        doc["time" if a.time else "host"] = block
+        doc.update({"time": block} if a.time else blocks)
         json.dump(doc, open(a.out, "w"), indent=1)
     sys.exit(1 if moved else 0)
 

@@ -96,17 +96,17 @@ def main():
     assert torch.cuda.is_available(), "rectify_probe measures the GPU kernels: no GPU visible"
     dev = torch.device("cuda", 0)
     F = rc.REMAP_FRAME_GROUP
-    K320, dist = sx.CAMS["B"]
+    K320, dist = sx.cam("B")
     R, T = rx.rig_RT("verge15", "B", "C")
     result = {"device": torch.cuda.get_device_name(dev), "seconds": a.seconds, "frame_group": F, "remap": {}}
     batch = 32
     for h, w, ch in ((240, 320, 1), (480, 640, 1), (960, 1280, 1), (960, 1280, 3)):
         key = f"{batch}x{h}x{w}x{ch}"
         s = w / 320.0
-        K0, K1 = K320.copy(), sx.CAMS["C"][0].copy()
+        K0, K1 = K320.copy(), sx.cam_K("C").copy()
         K0[:2] *= s
         K1[:2] *= s
-        r = rc.stereo_rectify_host(K0, dist, K1, sx.CAMS["C"][1], (w, h), R, T, alpha=0.5)
+        r = rc.stereo_rectify_host(K0, dist, K1, sx.cam_coeffs("C"), (w, h), R, T, alpha=0.5)
         md = rc.undistort_rectify_map_device(K0, dist, r.R1, r.P1, w, h, device=dev)
         base = torch.from_numpy(weights.synthetic_frames("board", 21, 4, h, w)).to(dev)
         frames = base.repeat(batch // 4, 1, 1)
@@ -159,9 +159,9 @@ def main():
     w, h = 1280, 960
     K0 = K320.copy()
     K0[:2] *= 4.0
-    K1 = sx.CAMS["C"][0].copy()
+    K1 = sx.cam_K("C").copy()
     K1[:2] *= 4.0
-    r = rc.stereo_rectify_host(K0, dist, K1, sx.CAMS["C"][1], (w, h), R, T)
+    r = rc.stereo_rectify_host(K0, dist, K1, sx.cam_coeffs("C"), (w, h), R, T)
     mo = torch.empty((h, w, 2), dtype=torch.int32, device=dev)
     result["map_1280x960"] = {"device_ms": wall(lambda: rc.undistort_rectify_map_device(K0, dist, r.R1, r.P1, w, h, out=mo))}
     rng = np.random.default_rng(5)
