@@ -80,6 +80,9 @@ SIGNATURES = {
     "dcx_calibrate_workspace_bytes": (_sz, [_i]),
     "dcx_calibrate_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _i, _i, _vp, _sz, _vp, _vp,
                                C.POINTER(C.c_double), _vp]),
+    "dcx_calibrate_flags_workspace_bytes": (_sz, [_i, _i]),
+    "dcx_calibrate_flags_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _i, _i, _i, C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), _i, _vp, _sz, _vp, _vp, C.POINTER(C.c_double), _vp]),
     "dcx_calibrate_ransac_workspace_bytes": (_sz, [_i, _i, _i]),
     "dcx_calibrate_ransac_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _i, _i, _i, C.c_double, C.c_double, _i, _i,
                                       C.c_uint, _vp, _sz, _vp, _vp, _vp, _vp, C.POINTER(C.c_double), _vp]),

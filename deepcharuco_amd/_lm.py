@@ -101,14 +101,15 @@ def schur_covariance(U, W, V, costs):
     return Si, P
 
 
-def refine(g, P, normal_blocks, trial_costs, total, stop_forced: bool, max_iter: int, eps: float):
+def refine(g, P, normal_blocks, trial_costs, total, stop_forced: bool, max_iter: int, eps: float, constrain=None):
     """-> (status LM_*, g, P, the units' costs at the solution or None, accepted steps, attempts).
 
     ``normal_blocks(g, P)`` -> (U, W, V, ga, gb, costs) as ``schur_step`` takes them, or None if a point is behind a camera;
     ``trial_costs(g, P)`` -> the units' costs, or None for the same reason (the cost is then inf); ``total(costs)`` adds them up
     in the caller's order.  ``stop_forced``: a step forced at lg > 16 that leaves a point behind a camera ends the solve
     (DEGENERATE, NONFINITE if a parameter is not finite): there are no normal equations to go on from.  Without it that case is
-    not handled here (``normal_blocks`` must not answer None after an accepted step)."""
+    not handled here (``normal_blocks`` must not answer None after an accepted step).  ``constrain(g)`` -> the trial g with the
+    caller's ties between global parameters restored (calibration's fx = a fy); None: the trial g is taken as it is."""
     blocks = normal_blocks(g, P)
     if blocks is None or not math.isfinite(total(blocks[5])):
         return LM_DEGENERATE, g, P, None, 0, 0
@@ -122,6 +123,8 @@ def refine(g, P, normal_blocks, trial_costs, total, stop_forced: bool, max_iter:
             if step is None:
                 return LM_DEGENERATE, g, P, None, iters, attempts
             g, P = prev_g - step[0], prev_p - step[1]
+            if constrain is not None:
+                g = constrain(g)
             vc = trial_costs(g, P)
             cost = total(vc) if vc is not None else math.inf
             attempts += 1

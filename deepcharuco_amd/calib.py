@@ -1,4 +1,5 @@
-"""Camera calibration without OpenCV: ``cv2.calibrateCamera`` (default flags) from ChArUco corners, on the host and on the GPU.
+"""Camera calibration without OpenCV: ``cv2.calibrateCamera`` (default flags, or the ``CALIB_*`` flags below and the rational
+model) from ChArUco corners, on the host and on the GPU.
 
 The reference gets the camera model its poses need from ``cv2.calibrateCamera(object_points, image_points, size, None, None)``
 (the reference's src/calib_intrinsics.py:44) on chessboard corners.  This project already has id-labelled sub-pixel corners of a
@@ -25,6 +26,24 @@ calibrates from; this module restates the solve for a planar (z = 0) target and 
 Deviations from ``cv2.calibrateCamera``: the homographies of the init are not refined by LM; each LM step is solved by Cholesky
 of the reduced system instead of an SVD of the dense one; unusable views are reported instead of raising (``calibrate_camera_host``
 raises like cv2).
+
+``flags`` (cv2's numeric values, ``CALIB_USE_INTRINSIC_GUESS`` ... ``CALIB_RATIONAL_MODEL``; any other bit is a ValueError) with the
+optional guess ``camera_matrix`` / ``dist_coeffs`` select what is solved for.  The parameter vector is then always theta12 = (fx, fy,
+cx, cy, k1, k2, p1, p2, k3, k4, k5, k6) with a mask of free entries (``_flag_model``):
+- start: without ``USE_INTRINSIC_GUESS`` steps 2 and 3 above; with ``FIX_ASPECT_RATIO`` OpenCV's rule is applied to K0 before step 3
+  (a = camera_matrix[0, 0] / camera_matrix[1, 1], tf = (fx + fy) / (a + 1), fx = a tf, fy = tf).  With the guess, theta is the given
+  model (missing coefficients 0) and every view that passes step 1's checks gets its pose by ``pnp._solve`` through that model,
+  distortion included;
+- ``FIX_PRINCIPAL_POINT`` fixes cx cy, ``FIX_FOCAL_LENGTH`` fx fy, ``ZERO_TANGENT_DIST`` sets p1 = p2 = 0 and fixes them, ``FIX_Ki`` fixes
+  ki at its start value; without ``RATIONAL_MODEL`` k4 k5 k6 stay at their start values (0 unless an 8-coefficient guess was given).  A
+  fixed parameter has a zero Jacobian column, a 1 on its diagonal of V and a zero gradient entry, hence a zero step: it comes back
+  with the bits it started with;
+- ``FIX_ASPECT_RATIO``: fx = a fy.  The fy column is d/dfy + a d/dfx, fx is not a free parameter, and every trial step writes
+  fx = a * fy, one multiplication (``_lm.refine``'s ``constrain``; the device's reduce_solve does the same);
+- the stop rule, the caps and the damping are step 4's, |dp| / |p| over all 12 + 6N entries.
+``flags = 0`` is the call without the keyword: the same code path and bits.  Rational models are compared by where they project,
+never coefficient by coefficient (numerator and denominator trade against each other).  The flags are not offered by the robust
+calibration (its step C stays the default solve), the fisheye, stereo and rig solvers; thin-prism and tilted terms are refused.
 
 ``calibrate_camera_ransac_*`` / ``calibrate_charuco_ransac_*`` put a consensus search in front of that solve and a re-check behind
 it: a corner with a wrong id sits a board square away from its label, the joint least squares has no defence, and every pose
@@ -54,22 +73,34 @@ CALIB_MAX_ITER = 30
 CALIB_EPS = float(np.finfo(np.float64).eps)
 N_INTR = 9                     # fx, fy, cx, cy, k1, k2, p1, p2, k3
 RESULT_WORDS = 16              # h_result of dcx_calibrate_pool
+N_FULL = 12                    # theta12: N_INTR, then k4, k5, k6
+FLAGS_RESULT_WORDS = 20        # h_result of dcx_calibrate_flags_pool
+
+# cv2's values.  Any other bit (thin prism, tilted, FIX_S*, FIX_TANGENT_DIST, USE_LU / USE_QR) is refused
+CALIB_USE_INTRINSIC_GUESS, CALIB_FIX_ASPECT_RATIO, CALIB_FIX_PRINCIPAL_POINT, CALIB_ZERO_TANGENT_DIST = 1, 2, 4, 8
+CALIB_FIX_FOCAL_LENGTH, CALIB_FIX_K1, CALIB_FIX_K2, CALIB_FIX_K3 = 16, 32, 64, 128
+CALIB_FIX_K4, CALIB_FIX_K5, CALIB_FIX_K6, CALIB_RATIONAL_MODEL = 0x800, 0x1000, 0x2000, 0x4000
+CALIB_FLAGS_KNOWN = 0x1 | 0x2 | 0x4 | 0x8 | 0x10 | 0x20 | 0x40 | 0x80 | 0x800 | 0x1000 | 0x2000 | 0x4000
+_FIX_K = ((CALIB_FIX_K1, 4), (CALIB_FIX_K2, 5), (CALIB_FIX_K3, 8), (CALIB_FIX_K4, 9), (CALIB_FIX_K5, 10), (CALIB_FIX_K6, 11))
 
 RANSAC_MAX_ROUNDS = 8          # re-mask rounds of the robust calibration
 
 __all__ = ["CalibResult", "calibrate_camera_host", "calibrate_camera_host_full", "calibrate_charuco_pool",
            "calibrate_charuco_device", "CALIB_OK", "CALIB_NO_VIEWS", "CALIB_DEGENERATE", "CALIB_NONFINITE",
+           "CALIB_USE_INTRINSIC_GUESS", "CALIB_FIX_ASPECT_RATIO", "CALIB_FIX_PRINCIPAL_POINT", "CALIB_ZERO_TANGENT_DIST",
+           "CALIB_FIX_FOCAL_LENGTH", "CALIB_FIX_K1", "CALIB_FIX_K2", "CALIB_FIX_K3", "CALIB_FIX_K4", "CALIB_FIX_K5", "CALIB_FIX_K6",
+           "CALIB_RATIONAL_MODEL", "flags_workspace_bytes",
            "RobustCalibResult", "calibrate_camera_ransac_host", "calibrate_camera_ransac_host_full",
            "calibrate_charuco_ransac_pool", "calibrate_charuco_ransac_device", "ransac_workspace_bytes",
            "CalibUncertainty", "calibration_uncertainty_host", "calibration_uncertainty_pool", "calibration_uncertainty_device",
            "unpack_uncertainty", "uncertainty_workspace_bytes", "COV_OK", "COV_NO_VIEWS", "COV_NO_DOF", "COV_SINGULAR"]
 
 
-class CalibResult(NamedTuple):
+class _CalibFields(NamedTuple):
     status: int                  # CALIB_*
     rms: float                   # sqrt(sum |r|^2 / points used): cv2.calibrateCamera's return value
     camera_matrix: np.ndarray    # 3x3
-    dist_coeffs: np.ndarray      # 1x5: k1 k2 p1 p2 k3
+    dist_coeffs: np.ndarray      # 1x5: k1 k2 p1 p2 k3; 1x8 (k4 k5 k6) with CALIB_RATIONAL_MODEL or an 8-coefficient guess
     view_status: np.ndarray      # int32 [B], pnp.PNP_*
     rvecs: np.ndarray            # [B, 3]; zeros unless the view was used
     tvecs: np.ndarray            # [B, 3]
@@ -79,6 +110,24 @@ class CalibResult(NamedTuple):
     attempts: int                # LM trial steps (accepted + rejected)
     views_used: int
     points_used: int
+
+
+class CalibResult(_CalibFields):
+    """The 13 fields above, which ``RobustCalibResult`` begins with in the same order, and beside them the attribute ``flags``: the
+    CALIB_* flags the model was solved with (0: the default model).  ``flags`` is a keyword of the constructor and of ``_replace``
+    and no member of the tuple, whose length and layout other code relies on."""
+    flags = 0
+
+    def __new__(cls, *args, flags: int = 0, **kw):
+        self = super().__new__(cls, *args, **kw)
+        self.flags = int(flags)
+        return self
+
+    def _replace(self, **kw):
+        flags = kw.pop("flags", self.flags)
+        r = super()._replace(**kw)
+        r.flags = int(flags)
+        return r
 
 
 # ------------------------------------------------------------------------------------------------ the fp64 steps
@@ -154,9 +203,10 @@ def _init_focal(rows: np.ndarray) -> Optional[Tuple[float, float]]:
     return fx, fy
 
 
-def _initialise(views, image_size):
+def _initialise(views, image_size, adjust=None):
     """-> (view status [B], theta0 (9) or None, initial poses [B, 6]).  Statuses as the module docstring; theta0 None when no
-    view is left (status NO_VIEWS) or the init's 2x2 system is singular."""
+    view is left (status NO_VIEWS) or the init's 2x2 system is singular.  ``adjust(theta0)`` -> the theta0 the poses are solved
+    with and the solve starts from (FIX_ASPECT_RATIO's rule); None: Zhang's as it is."""
     w, h = image_size
     cx, cy = (w - 1) * 0.5, (h - 1) * 0.5
     B = len(views)
@@ -177,6 +227,8 @@ def _initialise(views, image_size):
     if f is None:
         return status, None, poses
     theta = np.array([f[0], f[1], cx, cy, 0, 0, 0, 0, 0], np.float64)
+    if adjust is not None:
+        theta = adjust(theta)
     K0, k0 = _camera_of(theta)
     for i, (obj, img) in enumerate(views):
         if status[i] == PNP_OK:
@@ -266,10 +318,190 @@ def _result(status, theta, view_status, poses, vc, counts, iters, attempts, n_di
                        int(iters), int(attempts), int(used.size), int(counts[used].sum()))
 
 
-def calibrate_camera_host_full(object_points, image_points, image_size) -> CalibResult:
-    """``cv2.calibrateCamera(object_points, image_points, image_size, None, None)`` for a planar (z = 0) target, in float64 on the
-    host, with every output of ``dcx_calibrate_pool`` (``CalibResult``).  Views that fail their checks are left out and reported
-    in ``view_status``; ValueError for non-planar or mismatched input or a non-positive image size."""
+# ------------------------------------------------------------------------------------------------ the flags
+
+class _FlagModel(NamedTuple):
+    flags: int
+    free: np.ndarray             # bool [12]: the entries of theta12 the solve moves (fx is not free under the aspect tie)
+    aspect: Optional[float]      # a of fx = a fy while fy is free, else None
+    ratio: Optional[float]       # a of FIX_ASPECT_RATIO's rule on Zhang's K0 (the start without a guess), else None
+    guess: Optional[np.ndarray]  # theta12 of USE_INTRINSIC_GUESS, else None
+    n_dist: int                  # coefficients reported: 8 with RATIONAL_MODEL or an 8-coefficient guess, else 5
+    rational: bool               # k4 k5 k6 are live: the device runs its 12-parameter model
+
+
+def _flag_model(flags, camera_matrix, dist_coeffs) -> Optional[_FlagModel]:
+    """The checked arguments of a flagged call (module docstring), or None for ``flags == 0``: today's call, in which a
+    ``camera_matrix`` has no role.  ValueError for an unknown bit, a missing or unusable ``camera_matrix``, a number of coefficients
+    other than 0, 4, 5 or 8, values that are not finite, or ``dist_coeffs`` without ``CALIB_USE_INTRINSIC_GUESS``."""
+    if int(flags) != flags:
+        raise ValueError(f"flags must be an integer, not {flags!r}")
+    flags = int(flags)
+    if flags & ~CALIB_FLAGS_KNOWN:
+        raise ValueError(f"flags {flags:#x}: the bits {flags & ~CALIB_FLAGS_KNOWN:#x} are not supported (known: {CALIB_FLAGS_KNOWN:#x})")
+    use_guess = bool(flags & CALIB_USE_INTRINSIC_GUESS)
+    if dist_coeffs is not None and not use_guess:
+        raise ValueError("dist_coeffs is part of the guess: it needs CALIB_USE_INTRINSIC_GUESS")
+    if flags == 0:
+        return None
+    K = None if camera_matrix is None else pnp._camera(camera_matrix)
+    if K is None and flags & (CALIB_USE_INTRINSIC_GUESS | CALIB_FIX_ASPECT_RATIO):
+        raise ValueError("CALIB_USE_INTRINSIC_GUESS and CALIB_FIX_ASPECT_RATIO need a camera_matrix")
+    d = np.zeros(0) if dist_coeffs is None else np.asarray(dist_coeffs, dtype=np.float64).ravel()
+    k8 = pnp._dist(dist_coeffs)
+    free = np.ones(N_FULL, bool)
+    if not flags & CALIB_RATIONAL_MODEL:
+        free[9:] = False
+    if flags & CALIB_FIX_PRINCIPAL_POINT:
+        free[2:4] = False
+    if flags & CALIB_FIX_FOCAL_LENGTH:
+        free[0:2] = False
+    if flags & CALIB_ZERO_TANGENT_DIST:
+        free[6:8] = False
+    for bit, j in _FIX_K:
+        if flags & bit:
+            free[j] = False
+    guess = None
+    if use_guess:
+        guess = np.r_[K[0, 0], K[1, 1], K[0, 2], K[1, 2], k8]
+        if flags & CALIB_ZERO_TANGENT_DIST:
+            guess[6:8] = 0.0
+    ratio = float(K[0, 0] / K[1, 1]) if flags & CALIB_FIX_ASPECT_RATIO else None
+    if ratio is not None and not (math.isfinite(ratio) and ratio > 0):
+        raise ValueError(f"CALIB_FIX_ASPECT_RATIO: camera_matrix gives the ratio {ratio}, which must be finite and positive")
+    aspect = ratio if free[1] else None
+    if aspect is not None:
+        free[0] = False
+    rational = bool(flags & CALIB_RATIONAL_MODEL) or bool(guess is not None and guess[9:].any())
+    return _FlagModel(flags, free, aspect, ratio if guess is None else None, guess,
+                      8 if flags & CALIB_RATIONAL_MODEL or d.size == 8 else 5, rational)
+
+
+def _camera_of12(theta: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """theta12 -> (K 3x3, pnp's 8 distortion coefficients)."""
+    return _camera_matrix(theta), theta[4:12].copy()
+
+
+def _project_full12(obj: np.ndarray, img: np.ndarray, theta: np.ndarray, p: np.ndarray, jac: bool):
+    """``_project_full`` over theta12 with the denominator live: the 2N x 18 Jacobian [d/dtheta12 | d/d(rvec, tvec)].  The k1 k2 k3
+    columns are ``_project_full``'s divided by den = 1 + k4 r^2 + k5 r^4 + k6 r^6, the k4 k5 k6 columns -f (x, y) r^2j num / den^2."""
+    K, k = _camera_of12(theta)
+    res, cost, Je, m = pnp._project_through(pnp._distort, obj, img, p, K, k, jac)
+    if Je is None:
+        return res, cost, None
+    x, y, xd, yd, r2 = m[:5]
+    r4, r6 = r2 * r2, r2 * r2 * r2
+    num = 1 + r2 * (k[0] + r2 * (k[1] + r2 * k[4]))
+    den = 1 + r2 * (k[5] + r2 * (k[6] + r2 * k[7]))
+    iden = 1.0 / den
+    gq = -(num * iden) * iden                     # d(num / den) / d den
+    fx, fy = theta[0], theta[1]
+    n = obj.shape[0]
+    Ji = np.zeros((n, 2, N_FULL))
+    Ji[:, 0, 0] = xd
+    Ji[:, 1, 1] = yd
+    Ji[:, 0, 2] = 1.0
+    Ji[:, 1, 3] = 1.0
+    for j, pw in ((4, r2), (5, r4), (8, r6)):                                       # k1 k2 k3
+        Ji[:, 0, j], Ji[:, 1, j] = fx * (x * pw * iden), fy * (y * pw * iden)
+    Ji[:, 0, 6], Ji[:, 1, 6] = fx * (2 * x * y), fy * (r2 + 2 * y * y)              # p1
+    Ji[:, 0, 7], Ji[:, 1, 7] = fx * (r2 + 2 * x * x), fy * (2 * x * y)              # p2
+    for j, pw in ((9, r2), (10, r4), (11, r6)):                                     # k4 k5 k6
+        Ji[:, 0, j], Ji[:, 1, j] = fx * (x * pw * gq), fy * (y * pw * gq)
+    return res, cost, np.concatenate([Ji.reshape(2 * n, N_FULL), Je], 1)
+
+
+def _masked_project(free: np.ndarray, aspect: Optional[float], project_full=_project_full12):
+    """``project_full`` with the flags' linear map on its intrinsic columns: a times the fx column added to the fy column under the
+    aspect tie, then every column that is not free zeroed."""
+    fixed = np.flatnonzero(~free)
+
+    def project(obj, img, theta, p, jac):
+        res, cost, J = project_full(obj, img, theta, p, jac)
+        if J is not None:
+            if aspect is not None:
+                J[:, 1] += aspect * J[:, 0]
+            J[:, fixed] = 0.0
+        return res, cost, J
+    return project
+
+
+def _masked_blocks(views, theta, poses, free, aspect):
+    """``_normal_blocks`` of the masked model; a fixed parameter gets a 1 on its diagonal of V (its row, column and gradient entry
+    are zero), so the reduced system stays positive definite and its step is zero."""
+    nb = _normal_blocks(views, theta, poses, _masked_project(free, aspect))
+    if nb is not None:
+        fixed = np.flatnonzero(~free)
+        nb[2][fixed, fixed] = 1.0
+    return nb
+
+
+def _refine_flags(views, theta: np.ndarray, poses: np.ndarray, fm: _FlagModel, max_iter=CALIB_MAX_ITER):
+    """``_refine`` over theta12 with ``fm``'s mask and aspect tie."""
+    a = fm.aspect
+
+    def constrain(g):
+        g = g.copy()
+        g[0] = a * g[1]
+        return g
+    return _lm.refine(theta, poses, lambda t, p: _masked_blocks(views, t, p, fm.free, a),
+                      lambda t, p: _view_costs(views, t, p, _project_full12), _total, False, max_iter, CALIB_EPS,
+                      constrain if a is not None else None)
+
+
+def _aspect_rule(theta: np.ndarray, a: float) -> np.ndarray:
+    """OpenCV's rule on Zhang's focal lengths: tf = (fx + fy) / (a + 1), fx = a tf, fy = tf."""
+    theta = theta.copy()
+    tf = (theta[0] + theta[1]) / (a + 1.0)
+    theta[0], theta[1] = a * tf, tf
+    return theta
+
+
+def _initialise_flags(views, image_size, fm: _FlagModel):
+    """``_initialise`` for a flagged call -> (view status [B], theta12 or None, initial poses [B, 6])."""
+    if fm.guess is None:
+        status, theta, poses = _initialise(views, image_size, None if fm.ratio is None else lambda t: _aspect_rule(t, fm.ratio))
+        return status, None if theta is None else np.r_[theta, 0.0, 0.0, 0.0], poses
+    B = len(views)
+    status = np.full(B, PNP_OK, np.int32)
+    poses = np.zeros((B, 6))
+    K, k = _camera_of12(fm.guess)
+    for i, (obj, img) in enumerate(views):
+        if obj.shape[0] < 4:
+            status[i] = PNP_TOO_FEW
+            continue
+        status[i] = _homography(obj, img)[0]          # the check of the default start, on the pixels as they are
+        if status[i] == PNP_OK:
+            st, pose = _solve(obj, img, K, k)
+            status[i] = st
+            if st == PNP_OK:
+                poses[i] = pose[:6]
+    return status, fm.guess.copy(), poses
+
+
+def _calibrate_flags_host(object_points, image_points, image_size, fm: _FlagModel) -> CalibResult:
+    w, h = _image_size(image_size)
+    views = _views(object_points, image_points)
+    counts = np.array([obj.shape[0] for obj, _ in views], np.int64)
+    view_status, theta, poses0 = _initialise_flags(views, (w, h), fm)
+    used = np.flatnonzero(view_status == PNP_OK)
+    if theta is None or not used.size:
+        st = CALIB_NO_VIEWS if not used.size else CALIB_DEGENERATE
+        return _result(st, theta, view_status, None, None, counts, 0, 0, fm.n_dist)._replace(flags=fm.flags)
+    st, theta, poses, vc, iters, attempts = _refine_flags([views[i] for i in used], theta, poses0[used], fm)
+    return _result(st, theta, view_status, poses, vc, counts, iters, attempts, fm.n_dist)._replace(flags=fm.flags)
+
+
+def calibrate_camera_host_full(object_points, image_points, image_size, flags: int = 0, camera_matrix=None,
+                               dist_coeffs=None) -> CalibResult:
+    """``cv2.calibrateCamera(object_points, image_points, image_size, camera_matrix, dist_coeffs, flags=flags)`` for a planar
+    (z = 0) target, in float64 on the host, with every output of ``dcx_calibrate_pool`` / ``dcx_calibrate_flags_pool``
+    (``CalibResult``).  ``flags``, ``camera_matrix``, ``dist_coeffs``: the module docstring; ``flags = 0`` is cv2's call with None,
+    None.  Views that fail their checks are left out and reported in ``view_status``; ValueError for non-planar or mismatched
+    input, a non-positive image size or refused flags."""
+    fm = _flag_model(flags, camera_matrix, dist_coeffs)
+    if fm is not None:
+        return _calibrate_flags_host(object_points, image_points, image_size, fm)
     w, h = _image_size(image_size)
     views = _views(object_points, image_points)
     counts = np.array([obj.shape[0] for obj, _ in views], np.int64)
@@ -300,10 +532,11 @@ def _no_bad_id(r, col_count, row_count):
     return r
 
 
-def calibrate_camera_host(object_points, image_points, image_size):
-    """cv2's 5-tuple ``(rms, K 3x3, dist 1x5, rvecs, tvecs)`` (rvecs / tvecs: one (3, 1) array per view).  ValueError, as cv2
-    errors out, on non-planar objects, a view that cannot be used (fewer than 4 points, degenerate) or a failed calibration."""
-    return _cv2_tuple(calibrate_camera_host_full(object_points, image_points, image_size))
+def calibrate_camera_host(object_points, image_points, image_size, flags: int = 0, camera_matrix=None, dist_coeffs=None):
+    """cv2's 5-tuple ``(rms, K 3x3, dist 1x5 or 1x8, rvecs, tvecs)`` (rvecs / tvecs: one (3, 1) array per view); ``flags``,
+    ``camera_matrix``, ``dist_coeffs`` as for ``calibrate_camera_host_full``.  ValueError, as cv2 errors out, on non-planar objects,
+    a view that cannot be used (fewer than 4 points, degenerate) or a failed calibration."""
+    return _cv2_tuple(calibrate_camera_host_full(object_points, image_points, image_size, flags, camera_matrix, dist_coeffs))
 
 
 # ------------------------------------------------------------------------------------------------ consensus: the definition
@@ -517,14 +750,62 @@ def _upload(keypoints_list, dev):
     return pack_keypoints(keypoints_list, dev)
 
 
-def calibrate_charuco_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len,
-                           image_size) -> CalibResult:
-    """Calibrate from every frame of an ``infer_batch_device`` result, read in place from the corner pool (the conventions of
-    ``pnp.solve_pnp_pool``: ``refined`` = the pool carries RefineNet's xy, else the integer rows are the image points).  Object
-    points are ``pnp.object_points``' float32 board corners.  ``image_size`` = (width, height) as in cv2.  The call synchronises
-    the current stream (the LM loop reads one state word per step) and cannot be captured in a graph."""
+def flags_workspace_bytes(batch: int, flags: int) -> int:
+    """Bytes of device workspace ``dcx_calibrate_flags_pool`` needs; a guess whose k4 k5 k6 are not all zero needs the size of
+    ``flags | CALIB_RATIONAL_MODEL``."""
+    from . import _lib
+    n = int(_lib.lib().dcx_calibrate_flags_workspace_bytes(int(batch), int(flags)))
+    if n == 0:
+        raise ValueError("batch >= 1 and known flags are required")
+    return n
+
+
+def _flags_result(res, view_status, pose, fm: _FlagModel) -> CalibResult:
+    """``dcx_calibrate_flags_pool``'s 20 doubles (theta12, then rms .. status) -> ``CalibResult``."""
+    r = np.array(res[:], np.float64)
+    r16 = np.r_[r[:9], r[12:18], 0.0]                     # dcx_calibrate_pool's places
+    f = list(_common_fields(r16, view_status, pose))
+    f[3] = r[4:4 + fm.n_dist].reshape(1, fm.n_dist).copy()
+    return CalibResult(*f, flags=fm.flags)
+
+
+def _calibrate_flags_pool(packed, batch, pool, refined, col_count, row_count, square_len, image_size, fm: _FlagModel) -> CalibResult:
     import torch
     from . import _lib
+    w, h = _image_size(image_size)
+    dev = packed.device
+    ptrs = pnp._pool_ptrs(packed, batch, pool, refined)
+    st, pose = _view_outputs(batch, dev)
+    nbytes = flags_workspace_bytes(batch, fm.flags | (CALIB_RATIONAL_MODEL if fm.rational else 0))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    res = (_ctypes.c_double * FLAGS_RESULT_WORDS)()
+    cam, dist, n_dist = None, None, 0
+    if fm.guess is not None:
+        cam = (_ctypes.c_double * 9)(*_camera_matrix(fm.guess).ravel().tolist())
+        dist, n_dist = (_ctypes.c_double * 8)(*fm.guess[4:].tolist()), 8
+    elif fm.ratio is not None:
+        cam = (_ctypes.c_double * 9)(fm.ratio, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0)      # only the ratio fx / fy is read
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().dcx_calibrate_flags_pool(*ptrs, int(batch), int(pool), int(col_count), int(row_count), float(square_len),
+                                                       w, h, fm.flags, cam, dist, n_dist, ws.data_ptr(), nbytes, st.data_ptr(),
+                                                       pose.data_ptr(), res, _lib.current_stream()), "dcx_calibrate_flags_pool")
+        st_h, pose_h = st.cpu().numpy(), pose.cpu().numpy()
+    return _flags_result(res, st_h, pose_h, fm)
+
+
+def calibrate_charuco_pool(packed, batch: int, pool: int, refined: bool, col_count, row_count, square_len,
+                           image_size, flags: int = 0, camera_matrix=None, dist_coeffs=None) -> CalibResult:
+    """Calibrate from every frame of an ``infer_batch_device`` result, read in place from the corner pool (the conventions of
+    ``pnp.solve_pnp_pool``: ``refined`` = the pool carries RefineNet's xy, else the integer rows are the image points).  Object
+    points are ``pnp.object_points``' float32 board corners.  ``image_size`` = (width, height) as in cv2.  ``flags``,
+    ``camera_matrix``, ``dist_coeffs`` as for ``calibrate_camera_host_full``: ``flags = 0`` is ``dcx_calibrate_pool``, anything else
+    ``dcx_calibrate_flags_pool``.  The call synchronises the current stream (the LM loop reads one state word per step) and cannot
+    be captured in a graph."""
+    import torch
+    from . import _lib
+    fm = _flag_model(flags, camera_matrix, dist_coeffs)
+    if fm is not None:
+        return _calibrate_flags_pool(packed, batch, pool, refined, col_count, row_count, square_len, image_size, fm)
     w, h = _image_size(image_size)
     dev = packed.device
     ptrs = pnp._pool_ptrs(packed, batch, pool, refined)
@@ -541,16 +822,19 @@ def calibrate_charuco_pool(packed, batch: int, pool: int, refined: bool, col_cou
 
 
 def calibrate_charuco_device(keypoints_list: Sequence, col_count, row_count, square_len, image_size,
-                             device="cuda") -> CalibResult:
+                             device="cuda", flags: int = 0, camera_matrix=None, dist_coeffs=None) -> CalibResult:
     """Calibrate from ``infer_image``-format keypoint arrays ([x, y, id] rows, any number of frames and of corners each) on the
-    GPU -> ``CalibResult``.  IndexError if a frame with >= 4 points carries an id outside the board."""
+    GPU -> ``CalibResult``; ``flags``, ``camera_matrix``, ``dist_coeffs`` as for ``calibrate_camera_host_full``.  IndexError if a
+    frame with >= 4 points carries an id outside the board."""
     import torch
     from .models._handles import require_cuda
+    _flag_model(flags, camera_matrix, dist_coeffs)
     dev = require_cuda(device)
     _image_size(image_size)
     packed, b, pool = _upload(keypoints_list, dev)
     with torch.cuda.device(dev):
-        r = calibrate_charuco_pool(packed, b, pool, True, col_count, row_count, square_len, image_size)
+        r = calibrate_charuco_pool(packed, b, pool, True, col_count, row_count, square_len, image_size, flags, camera_matrix,
+                                   dist_coeffs)
     return _no_bad_id(r, col_count, row_count)
 
 
@@ -718,6 +1002,9 @@ def _model_args(camera_matrix, dist_coeffs, rvecs, tvecs, view_status, inliers):
     r = camera_matrix
     if r.status != CALIB_OK:
         raise ValueError(f"the calibration failed (status {r.status}): there is no solution to take an uncertainty at")
+    if getattr(r, "flags", 0) & ~CALIB_USE_INTRINSIC_GUESS:
+        raise ValueError(f"a result solved with flags {r.flags:#x}: the uncertainty is that of the solvers' free parameters, and a "
+                         f"parameter held fixed has no variance to report (covariances of flagged models are not computed)")
     return r.camera_matrix, r.dist_coeffs, r.rvecs, r.tvecs, r.view_status, inliers if inliers is not None else getattr(r, "inliers", None)
 
 

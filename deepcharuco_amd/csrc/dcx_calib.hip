@@ -12,7 +12,8 @@
 //   init_poses      solve() with K0 and zero distortion
 // and the C entries.  The joint solve behind it (evaluate, schur, reduce_solve, trial, decide, the host loop, the workspace) is
 // dcx_calib_dev.h's, instantiated on PinholeCalib; what it shares with the other solvers, its fixed summation orders and why the
-// call synchronises its stream are said there.
+// call synchronises its stream are said there.  cv2's flags and the rational model are dcx_calib_flags.hip's entry, which shares the
+// start below (dcx_calib_zhang_start).
 #include "dcx_calib_dev.h"
 
 namespace {
@@ -140,6 +141,24 @@ __global__ __launch_bounds__(kLanes) void calib_init_poses_kernel(CornerPool pl,
 
 }  // namespace
 
+// Zhang's start up to K0 (init_views, init_reduce), queued on s: the state at d_state (kNextEvaluate with g = fx fy cx cy 0 .. 0,
+// or kFinished with the status in result[14]), the views' rows at d_rows [B][6], every view's status and zeroed pose words with its
+// point count.  For this unit's entry and for dcx_calib_flags.hip, which has its own poses kernel; not part of the C ABI.
+void dcx_calib_zhang_start(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows, const float* d_xy, int batch, int pool,
+                           int col_count, int row_count, double square_len, int image_width, int image_height, void* d_state,
+                           double* d_init_rows, int32_t* d_view_status, double* d_pose, void* stream) {
+    CornerPool pl;
+    if (!corner_pool(d_counts, d_starts, d_rows, d_xy, batch, pool, col_count, row_count, square_len, pl)) return;   // (checked by the caller)
+    CalibWs ws{};
+    ws.st = (CalibState*)d_state;
+    ws.rows = d_init_rows;
+    const double cx = (image_width - 1) * 0.5, cy = (image_height - 1) * 0.5;
+    hipLaunchKernelGGL(calib_init_views_kernel, dim3((unsigned)batch), dim3(kLanes), 0, (hipStream_t)stream, pl, cx, cy, d_view_status,
+                       d_pose, ws);
+    hipLaunchKernelGGL(calib_init_reduce_kernel, dim3(1), dim3(kRedThreads), 0, (hipStream_t)stream, batch, cx, cy, d_view_status, d_pose,
+                       ws);
+}
+
 extern "C" size_t dcx_calibrate_workspace_bytes(int batch) { return batch > 0 ? ws_layout<Model>(nullptr, batch, nullptr) : 0; }
 
 extern "C" int dcx_calibrate_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows, const float* d_xy,
@@ -152,11 +171,9 @@ extern "C" int dcx_calibrate_pool(const int32_t* d_counts, const int32_t* d_star
                                  image_height, d_workspace, workspace_bytes, d_view_status, d_pose, h_result, pl, ws))
         return e;
     hipStream_t s = (hipStream_t)stream;
-    const double cx = (image_width - 1) * 0.5, cy = (image_height - 1) * 0.5;
-    const dim3 views((unsigned)batch), wave(kLanes), one(1), red(kRedThreads);
-    hipLaunchKernelGGL(calib_init_views_kernel, views, wave, 0, s, pl, cx, cy, d_view_status, d_pose, ws);
-    hipLaunchKernelGGL(calib_init_reduce_kernel, one, red, 0, s, batch, cx, cy, d_view_status, d_pose, ws);
-    hipLaunchKernelGGL(calib_init_poses_kernel, views, wave, 0, s, pl, d_view_status, ws);
+    dcx_calib_zhang_start(d_counts, d_starts, d_rows, d_xy, batch, pool, col_count, row_count, square_len, image_width, image_height,
+                          ws.st, ws.rows, d_view_status, d_pose, stream);
+    hipLaunchKernelGGL(calib_init_poses_kernel, dim3((unsigned)batch), dim3(kLanes), 0, s, pl, d_view_status, ws);
     DCX_CHECK_HIP(calib_lm(s, pl, batch, d_view_status, d_pose, ws));
     DCX_CHECK_HIP(hipMemcpyAsync(h_result, ws.st->result, 16 * sizeof(double), hipMemcpyDeviceToHost, s));
     DCX_CHECK_HIP(hipStreamSynchronize(s));

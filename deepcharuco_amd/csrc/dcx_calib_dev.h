@@ -28,10 +28,21 @@
 // damping and the host loop (lm_run).  The reduction in front of the NG x NG solve (8 slices x 128, added serially) is this
 // header's own: its order is part of the output bits.  The pool is dcx_pnp_dev.h's CornerPool (frame(b), frame_status), which its
 // host check corner_pool() fills or refuses.
+// dcx_calib_flags.hip (cv2's calibration flags and the rational model, NG = 12) is the third unit on this header.  Its sizes do not
+// fit the two layout constants the other models share, so both are the model's: the LDS row stride of evaluate (17; 21 at NG = 12,
+// NC = 19) and reduce_solve's split of its 1024 threads into view slices x entry slots (8 x 128; 4 x 256 at NG = 12, kTot = 180).
+// The order of the view sum at NG = 12 is therefore: view b goes to slice b % 4, each slice adds its views in ascending b, the four
+// slices are added serially 0..3.  The flags themselves are a linear map on the intrinsic columns that commutes with the Schur
+// complement, so a flagged solve runs the per-view kernels as they are and only reduce_solve knows the mask (CalibMask below).
 #pragma once
 #include "dcx_fisheye_dev.h"
 #include "dcx_pnp_dev.h"
 #include "dcx_lm_dev.h"
+
+// dcx_calib.hip's: Zhang's start up to K0, shared with dcx_calib_flags.hip (plain pointers: the types below are each unit's own)
+__attribute__((visibility("hidden"))) void dcx_calib_zhang_start(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows, const float* d_xy, int batch, int pool,
+                           int col_count, int row_count, double square_len, int image_width, int image_height, void* d_state,
+                           double* d_init_rows, int32_t* d_view_status, double* d_pose, void* stream);
 
 namespace {
 
@@ -42,9 +53,13 @@ constexpr int kLdsStride = 17;                            // a row's NC <= 16 va
 
 // ---- the models.  A model names its camera class, NG, theta -> camera, the cap on accepted steps and the doubles per view its
 // start keeps in the workspace; every size of the solve follows from NG here and nowhere else.
-template <int NG_>
+template <int NG_, int STRIDE_ = kLdsStride, int SLICES_ = kSlices>
 struct CalibSizes {
     static constexpr int NG = NG_;
+    static constexpr int kLdsStride = STRIDE_;            // evaluate: a row's NC values, padded to an odd stride
+    static constexpr int kSlices = SLICES_;               // reduce_solve: view slices ...
+    static constexpr int kSlots = kRedThreads / SLICES_;  // ... x entry slots
+    static constexpr int kResult = NG_ + 6 <= 16 ? 16 : 20;   // h_result's words (LmState's NR)
     static constexpr int NC = NG + 7;                     // a row: [J_theta (NG) | J_pose (6) | r]
     static constexpr int kEntries = NC * (NC + 1) / 2;    // the view's packed NC x NC
     static constexpr int kCost = kEntries - 1;            // pk<NC>(NC - 1, NC - 1)
@@ -53,9 +68,9 @@ struct CalibSizes {
     static constexpr int kYZ = 6 * NG + 6;                // U*^-1 W^T (6 x NG, row major) and U*^-1 g_b (6)
     static constexpr int kSC = NS + NG;                   // the view's part of S (NS packed) and of the rhs (NG)
     static constexpr int kTot = 2 * kSC;                  // sum V (NS), sum g_a (NG), sum S_i (NS), sum W U*^-1 g_b (NG)
-    using State = LmState<NG>;                            // g = theta; result = h_result
+    using State = LmState<NG, kResult>;                   // g = theta; result = h_result
     static_assert(sizeof(State) <= kState, "state");
-    static_assert(NC < kLdsStride && kTot <= 128, "layout");
+    static_assert(NC < kLdsStride && kLdsStride % 2 == 1 && kTot <= kSlots && kSlices * kSlots == kRedThreads, "layout");
 };
 
 struct PinholeCalib : CalibSizes<9> {                     // fx fy cx cy k1 k2 p1 p2 k3
@@ -158,7 +173,7 @@ __device__ __forceinline__ bool project_point(const FisheyeCamera& cam, const do
 template <class M>
 __global__ __launch_bounds__(kLanes) void calib_evaluate_kernel(CornerPool pl, const int32_t* __restrict__ status, Ws<M> ws) {
     constexpr int NC = M::NC, NQ = M::NQ;
-    __shared__ double sj[2 * kLanes][kLdsStride];
+    __shared__ double sj[2 * kLanes][M::kLdsStride];
     const int b = blockIdx.x, lane = threadIdx.x;
     if (ws.st->code != kNextEvaluate || status[b] != DCX_PNP_OK) return;
     const Frame f = pl.frame(b);
@@ -234,9 +249,45 @@ __global__ __launch_bounds__(kLanes) void calib_schur_kernel(const int32_t* __re
     if (lane == 0) ws.fail[b] = ok ? 0 : 1;
 }
 
-template <class M>
-__global__ __launch_bounds__(kRedThreads) void calib_reduce_solve_kernel(int batch, const int32_t* __restrict__ status, Ws<M> ws) {
-    constexpr int NG = M::NG, NS = M::NS, kSC = M::kSC, kTot = M::kTot;
+// What a flagged solve holds fixed (dcx_calib_flags.hip; calib.py's module docstring has the rules).  Bit i of `free`: theta[i] moves.
+// tie: fx = a fy, with fy free and fx not.  The map T on the intrinsic columns (a times column fx added to column fy, fixed columns
+// dropped) is applied to the sums, T^T (sum V) T and T^T (sum W U*^-1 W^T) T and both right-hand sides likewise, before the damping;
+// a fixed parameter then gets a 1 on its diagonal, so its step is zero, and the step is scattered back to all NG slots.
+struct CalibMask {
+    unsigned free;
+    int tie;
+    double a;
+};
+
+// packed symmetric NG x NG P and the vector v under CalibMask's T, in place (thread 0's, on LDS)
+template <int NG>
+__device__ __forceinline__ void calib_mask_apply(double* P, double* v, const CalibMask& mk, double fixed_diag) {
+    if (mk.tie) {
+        const double p11 = P[pk<NG>(1, 1)] + mk.a * P[pk<NG>(0, 1)], p10 = P[pk<NG>(0, 1)] + mk.a * P[pk<NG>(0, 0)];
+        P[pk<NG>(1, 1)] = p11 + mk.a * p10;
+        for (int j = 2; j < NG; ++j) P[pk<NG>(1, j)] += mk.a * P[pk<NG>(0, j)];
+        v[1] += mk.a * v[0];
+    }
+    for (int i = 0; i < NG; ++i) {
+        if ((mk.free >> i) & 1u) continue;
+        for (int j = 0; j < NG; ++j) P[pk<NG>(i, j)] = 0.0;
+        P[pk<NG>(i, i)] = fixed_diag;
+        v[i] = 0.0;
+    }
+}
+
+__device__ __forceinline__ CalibMask calib_mask_of() { return CalibMask{}; }
+__device__ __forceinline__ CalibMask calib_mask_of(const CalibMask& mk) { return mk; }
+
+// Mask: nothing (the default solve: this kernel's argument block and code are the ones it has always had; the text stays in the
+// kernel, as a function called from two kernels it compiles otherwise) or one CalibMask (a flagged solve)
+template <class M, class... Mask>
+__global__ __launch_bounds__(kRedThreads) void calib_reduce_solve_kernel(int batch, const int32_t* __restrict__ status, Ws<M> ws,
+                                                                         Mask... mask) {
+    constexpr bool MASKED = sizeof...(Mask) > 0;
+    static_assert(sizeof...(Mask) <= 1, "mask");
+    [[maybe_unused]] const CalibMask mk = calib_mask_of(mask...);
+    constexpr int NG = M::NG, NS = M::NS, kSC = M::kSC, kTot = M::kTot, kSlices = M::kSlices;
     __shared__ double part[kSlices][kTot];
     __shared__ int bad[kSlices];
     // thread 0's small dense solve, indexed in loops: kept in LDS rather than in (scratch-backed) private arrays, and rolled, so it
@@ -244,7 +295,7 @@ __global__ __launch_bounds__(kRedThreads) void calib_reduce_solve_kernel(int bat
     __shared__ double tot[kTot], S[NS], L[NS], rhs[NG], y[NG], x[NG];
     typename M::State* st = ws.st;
     if (st->code == kFinished) return;
-    const int t = threadIdx.x, e = t % 128, sl = t / 128;
+    const int t = threadIdx.x, e = t % M::kSlots, sl = t / M::kSlots;
     if (e < kTot) {
         const int src = lm_source<NG>(e);    // where entry e lives: in the view's packed entries (m) or in its Schur part (sc)
         double s = 0.0;
@@ -271,6 +322,10 @@ __global__ __launch_bounds__(kRedThreads) void calib_reduce_solve_kernel(int bat
         return;
     }
     const double scale = lm_damping(st->lg);
+    if constexpr (MASKED) {
+        calib_mask_apply<NG>(tot, tot + NS, mk, 1.0);
+        calib_mask_apply<NG>(tot + kSC, tot + kSC + NS, mk, 0.0);
+    }
     for (int a = 0; a < NG; ++a) {
         for (int c = a; c < NG; ++c) S[pk<NG>(a, c)] = tot[pk<NG>(a, c)] * (a == c ? scale : 1.0) - tot[kSC + pk<NG>(a, c)];
         rhs[a] = tot[NS + a] - tot[kSC + NS + a];
@@ -300,11 +355,24 @@ __global__ __launch_bounds__(kRedThreads) void calib_reduce_solve_kernel(int bat
         for (int k = i + 1; k < NG; ++k) s -= L[pk<NG>(k, i)] * x[k];
         x[i] = s / L[pk<NG>(i, i)];
     }
-    for (int i = 0; i < NG; ++i) {
-        st->dg[i] = x[i];
-        st->g_trial[i] = st->g[i] - x[i];
+    if constexpr (!MASKED) {
+        for (int i = 0; i < NG; ++i) {
+            st->dg[i] = x[i];
+            st->g_trial[i] = st->g[i] - x[i];
+        }
+    } else {
+        for (int i = 0; i < NG; ++i) {           // a fixed parameter keeps its bits
+            const bool moves = (mk.free >> i) & 1u;
+            st->dg[i] = moves ? x[i] : 0.0;
+            st->g_trial[i] = moves ? st->g[i] - x[i] : st->g[i];
+        }
+        if (mk.tie) {
+            st->dg[0] = mk.a * st->dg[1];
+            st->g_trial[0] = mk.a * st->g_trial[1];
+        }
     }
 }
+
 
 template <class M>
 __global__ __launch_bounds__(kLanes) void calib_trial_kernel(CornerPool pl, const int32_t* __restrict__ status, Ws<M> ws) {
@@ -356,7 +424,7 @@ __global__ __launch_bounds__(kLanes) void calib_trial_kernel(CornerPool pl, cons
 template <class M>
 __global__ __launch_bounds__(kRedThreads) void calib_decide_kernel(int batch, int init, const int32_t* __restrict__ status,
                                                                    double* __restrict__ pose, Ws<M> ws) {
-    lm_decide_block<M::NG, false, 16, M::kMaxIter>(
+    lm_decide_block<M::NG, false, M::kResult, M::kMaxIter>(
         ws.st, batch, init, ws.pose, ws.trial_pose, [&](int b) { return status[b] == DCX_PNP_OK; },
         [&](int b) { return ws.m[(long long)b * M::kEntries + M::kCost]; },
         [&](int b, double* a) {
@@ -390,8 +458,10 @@ inline int calib_args(const int32_t* d_counts, const int32_t* d_starts, const in
 
 // The solve behind a model's start (the state at kNextEvaluate or kFinished, every used view's pose in ws.pose): evaluate and
 // decide(init) queued, then one attempt per turn of lm_run until the state word says finished.
-template <class M>
-inline hipError_t calib_lm(hipStream_t s, const CornerPool& pl, int batch, int32_t* d_view_status, double* d_pose, const Ws<M>& ws) {
+// launch_solve(): the attempt's reduce_solve, the default one or the masked one of a flagged call.
+template <class M, class Solve>
+inline hipError_t calib_lm(hipStream_t s, const CornerPool& pl, int batch, int32_t* d_view_status, double* d_pose, const Ws<M>& ws,
+                           const Solve& launch_solve) {
     const dim3 views((unsigned)batch), wave(kLanes), one(1), red(kRedThreads);
     hipLaunchKernelGGL(calib_evaluate_kernel<M>, views, wave, 0, s, pl, d_view_status, ws);
     hipLaunchKernelGGL(calib_decide_kernel<M>, one, red, 0, s, batch, 1, d_view_status, d_pose, ws);
@@ -400,9 +470,16 @@ inline hipError_t calib_lm(hipStream_t s, const CornerPool& pl, int batch, int32
     return lm_run(s, &ws.st->code, M::kMaxIter, [&](bool evaluate) {
         if (evaluate) hipLaunchKernelGGL(calib_evaluate_kernel<M>, views, wave, 0, s, pl, d_view_status, ws);
         hipLaunchKernelGGL(calib_schur_kernel<M>, views, wave, 0, s, d_view_status, ws);
-        hipLaunchKernelGGL(calib_reduce_solve_kernel<M>, one, red, 0, s, batch, d_view_status, ws);
+        launch_solve();
         hipLaunchKernelGGL(calib_trial_kernel<M>, views, wave, 0, s, pl, d_view_status, ws);
         hipLaunchKernelGGL(calib_decide_kernel<M>, one, red, 0, s, batch, 0, d_view_status, d_pose, ws);
+    });
+}
+
+template <class M>
+inline hipError_t calib_lm(hipStream_t s, const CornerPool& pl, int batch, int32_t* d_view_status, double* d_pose, const Ws<M>& ws) {
+    return calib_lm(s, pl, batch, d_view_status, d_pose, ws, [&] {
+        hipLaunchKernelGGL(calib_reduce_solve_kernel<M>, dim3(1), dim3(kRedThreads), 0, s, batch, d_view_status, ws);
     });
 }
 

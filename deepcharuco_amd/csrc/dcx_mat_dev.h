@@ -251,8 +251,8 @@ __device__ __forceinline__ void accumulate_rows(int n, const RowFn& row_fn, doub
 // The view's Schur part.  m is its packed symmetric [V W g_a; W^T U g_b; . . cost] over NA shared parameters, 6 pose parameters
 // and the residual.  Every lane factors U* (U, diagonal scaled) itself; lane j < NA solves column j of U*^-1 W^T (rhs = row j of
 // W), lane NA solves U*^-1 g_b: both to sy (LDS, NA + 1 rows) and to yz (U*^-1 W^T as 6 x NA row major, then U*^-1 g_b); then the
-// lanes < NA (NA + 1) / 2 + NA form sc: W U*^-1 W^T (packed NA x NA), then W U*^-1 g_b.  false (sc zeroed) if U* is not positive
-// definite.  Wave-wide.
+// lanes < NA (NA + 1) / 2 + NA form sc: W U*^-1 W^T (packed NA x NA), then W U*^-1 g_b (where there are more than 64 of them, the
+// lanes take a second one each).  false (sc zeroed) if U* is not positive definite.  Wave-wide.
 template <int NA>
 __device__ __forceinline__ bool schur_view(const double* m, double scale, int lane, double (*sy)[6], double* yz, double* sc) {
     constexpr int NC = NA + 7, NS = NA * (NA + 1) / 2;
@@ -263,6 +263,8 @@ __device__ __forceinline__ bool schur_view(const double* m, double scale, int la
         for (int j = i; j < 6; ++j) u[pk<6>(i, j)] = m[pk<NC>(NA + i, NA + j)];
     if (!cholesky_factor<6>(u, scale, L)) {
         if (lane < NS + NA) sc[lane] = 0.0;
+        if constexpr (NS + NA > kLanes)
+            if (lane + kLanes < NS + NA) sc[lane + kLanes] = 0.0;
         return false;
     }
     if (lane < NA + 1) {
@@ -285,6 +287,18 @@ __device__ __forceinline__ bool schur_view(const double* m, double scale, int la
 #pragma unroll
         for (int k = 0; k < 6; ++k) s += m[pk<NC>(a, NA + k)] * sy[c][k];
         sc[lane] = s;
+    }
+    if constexpr (NS + NA > kLanes) {        // a second round of entries (NA = 12: 90 of them)
+        static_assert(NS + NA <= 2 * kLanes, "rounds");
+        const int e = lane + kLanes;
+        if (e < NS + NA) {
+            int a = e - NS, c = NA;
+            if (e < NS) unpk<NA>(e, a, c);
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) s += m[pk<NC>(a, NA + k)] * sy[c][k];
+            sc[e] = s;
+        }
     }
     return true;
 }

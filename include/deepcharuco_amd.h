@@ -277,7 +277,8 @@ int dcx_solve_pnp_ransac_pool(const int32_t* d_counts, const int32_t* d_starts, 
                               int32_t* d_status, double* d_pose /* [B][8] */, int32_t* d_info /* [B][2] */,
                               uint8_t* d_inliers /* [pool], may be NULL */, void* stream);
 
-/* ---- camera calibration from the views of a ChArUco board in a pool (cv2.calibrateCamera with default flags, planar target) --
+/* ---- camera calibration from the views of a ChArUco board in a pool (cv2.calibrateCamera with default flags, planar target; ----
+ * ---- its flags and the rational model: dcx_calibrate_flags_pool below) -------------------------------------------------------
  * The camera model solve_pnp needs (calib_intrinsics.py:44, cv2.calibrateCamera) from the corners of
  * `batch` views, read in place from a corner pool laid out as for dcx_solve_pnp_pool (same object points, same image points, same
  * per-view checks and DCX_PNP_* codes in d_view_status).  All fp64: OpenCV's initIntrinsicParams2D (principal point at
@@ -304,6 +305,50 @@ int dcx_calibrate_pool(const int32_t* d_counts, const int32_t* d_starts, const i
                        void* d_workspace, size_t workspace_bytes,
                        int32_t* d_view_status /* [B] DCX_PNP_* */, double* d_pose /* [B][8] */,
                        double* h_result /* [16] */, void* stream);
+
+/* ---- the same calibration with cv2.calibrateCamera's flags and the rational model ----------------------------------------------
+ * dcx_calibrate_pool's pool, per-view checks, DCX_PNP_* / DCX_CALIB_* codes, d_view_status and d_pose; `flags` are cv2's values
+ * below, any other bit is DCX_E_ARG (thin prism, tilted, FIX_S*, FIX_TANGENT_DIST, USE_LU / USE_QR).  The parameter vector is always
+ * theta12 = fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6, and the flags say which entries the solve moves
+ * (deepcharuco_amd/calib.py restates every rule: calibrate_camera_host_full with flags).  Steps:
+ * 1. start.  Without USE_INTRINSIC_GUESS: dcx_calibrate_pool's (Zhang's focal lengths, the image centre, zero distortion); with
+ *    FIX_ASPECT_RATIO OpenCV's rule on it, a = h_camera9[0] / h_camera9[4], tf = (fx + fy) / (a + 1), fx = a tf, fy = tf.  With the
+ *    guess: theta12 = h_camera9 and h_dist (n_dist = 0, 4, 5 or 8, missing coefficients 0; h_dist must be NULL and n_dist 0 without
+ *    the guess), and the per-view checks of the default start without its init rows.  h_camera9 is required by either flag.
+ * 2. every view's pose by the PnP solver through the start model, distortion included.
+ * 3. dcx_calibrate_pool's joint Levenberg-Marquardt (same damping, caps and stop rule, |dp| / |p| over all parameters) in which
+ *    FIX_PRINCIPAL_POINT fixes cx cy, FIX_FOCAL_LENGTH fx fy, ZERO_TANGENT_DIST sets p1 = p2 = 0 and fixes them, FIX_Ki fixes ki at its
+ *    start value, k4 k5 k6 stay at their start values without RATIONAL_MODEL, and FIX_ASPECT_RATIO ties fx = a fy (fy moves, every
+ *    trial step writes fx = a * fy, one multiplication).  A fixed parameter comes back with the bits it started with.  The flags
+ *    are a linear map on the intrinsic columns that commutes with the block elimination, so only the reduced solve knows them.
+ *    While k4 k5 k6 are zero and fixed the 9-parameter kernels of dcx_calibrate_pool run; with RATIONAL_MODEL, or a guess whose
+ *    k4 k5 k6 are not all zero, the 12-parameter model's.
+ * d_workspace: dcx_calibrate_flags_workspace_bytes(batch, flags) bytes (0 for refused arguments; DCX_E_WS if smaller); a guess
+ * with non-zero k4 k5 k6 needs the size of flags | DCX_CALIB_RATIONAL_MODEL.  h_result f64 [20] = theta12, rms, accepted LM steps,
+ * attempts, views used, points used, DCX_CALIB_* status, 0, 0; the first 13 are zero unless DCX_CALIB_OK.  SYNCHRONISES `stream`
+ * like dcx_calibrate_pool; no atomics: two calls give the same bits; nothing is allocated.  Rational models are to be compared by
+ * where they project, not coefficient by coefficient.                                                                          */
+#define DCX_CALIB_USE_INTRINSIC_GUESS  0x0001
+#define DCX_CALIB_FIX_ASPECT_RATIO     0x0002
+#define DCX_CALIB_FIX_PRINCIPAL_POINT  0x0004
+#define DCX_CALIB_ZERO_TANGENT_DIST    0x0008
+#define DCX_CALIB_FIX_FOCAL_LENGTH     0x0010
+#define DCX_CALIB_FIX_K1               0x0020
+#define DCX_CALIB_FIX_K2               0x0040
+#define DCX_CALIB_FIX_K3               0x0080
+#define DCX_CALIB_FIX_K4               0x0800
+#define DCX_CALIB_FIX_K5               0x1000
+#define DCX_CALIB_FIX_K6               0x2000
+#define DCX_CALIB_RATIONAL_MODEL       0x4000
+size_t dcx_calibrate_flags_workspace_bytes(int batch, int flags);
+int dcx_calibrate_flags_pool(const int32_t* d_counts, const int32_t* d_starts, const int32_t* d_rows,
+                             const float* d_xy /* NULL = use integer rows x,y */, int batch, int pool,
+                             int col_count, int row_count, double square_len, int image_width, int image_height,
+                             int flags, const double* h_camera9 /* NULL without a guess or ratio */,
+                             const double* h_dist, int n_dist,
+                             void* d_workspace, size_t workspace_bytes,
+                             int32_t* d_view_status /* [B] DCX_PNP_* */, double* d_pose /* [B][8] */,
+                             double* h_result /* [20] */, void* stream);
 
 /* ---- the same calibration behind a consensus search: a camera model that survives mislabelled corners -----------------------
  * Pool, object points, image points and the per-view checks as for dcx_calibrate_pool; the views' slot ranges must not overlap
