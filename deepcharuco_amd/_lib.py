@@ -116,6 +116,9 @@ SIGNATURES = {
     "dcx_calibrate_uncertainty_workspace_bytes": (_sz, [_i]),
     "dcx_calibrate_uncertainty_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _i, C.POINTER(C.c_double), _vp, _vp, _vp,
                                            _vp, _sz, _vp, _vp, _vp]),
+    "dcx_rig_uncertainty_workspace_bytes": (_sz, [_i, _i, C.POINTER(C.c_int)]),
+    "dcx_rig_uncertainty_pool": (_i, [_i, _vp, C.POINTER(C.c_int), C.POINTER(C.c_double), _i, _i, _i, C.c_double, _vp, _vp, _vp, _sz,
+                                     _vp, _vp, _vp]),
     "dcx_fisheye_undistort_rectify_map": (_i, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                               C.POINTER(C.c_double), _i, _i, _vp, _vp]),
     "dcx_fisheye_rectify_points_pool": (_i, [_vp, _vp, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),

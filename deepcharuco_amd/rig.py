@@ -49,7 +49,9 @@ what it has always been, bit for bit.
 What it gives over C - 1 stereo solves: one consistent rig from one call, and cameras that never see the board together with
 camera 0.  Where every camera shares views with camera 0 it is not measurably more accurate than the pairwise solves.
 With the rig solved, ``rig_pose_host_full`` / ``rig_pose_pools`` / ``rig_pose_device`` (second half of this module) find the board's
-pose per timestamp from every camera's rows, the rig held fixed.
+pose per timestamp from every camera's rows, the rig held fixed, and ``rig_uncertainty_host`` / ``rig_uncertainty_pools`` /
+``rig_uncertainty_device`` (last part) say how well the rig is determined: the covariances of the X_c and of the P_t, given the
+camera models (csrc/dcx_rig_cov.hip, without a host loop or a synchronisation).
 """
 from __future__ import annotations
 
@@ -60,13 +62,13 @@ from typing import NamedTuple, Sequence
 import numpy as np
 
 from . import _dev, _lm
-from .calib import _no_bad_id
+from .calib import COV_NO_DOF, COV_NO_VIEWS, COV_OK, COV_SINGULAR, COV_POSE_WORDS, _device_or_upload, _no_bad_id
 from .corner_pool import _pool_rows
 from .pnp import (LM_EPS, LM_MAX_ITER, LM_STATUS, PNP_DEGENERATE, PNP_OK, PNP_TOO_FEW, PNP_TRUNCATED, _bad_id_error, _camera,
                   _pool_ptrs, _rodrigues, _rvec_of, object_points)
 # every step that does not depend on the number of cameras is stereo.py's, kept once
 from .stereo import (MODELS, STEREO_EPS, STEREO_MAX_ITER, _call, _depth_margin, _device_masks, _evaluate, _model_args, _model_cameras,
-                     _models, _outputs, _raise_like_cv2, _refine, _rig_init, _sine, _total, _unpack, _upload, _view_poses,
+                     _models, _normal_blocks, _outputs, _raise_like_cv2, _refine, _rig_init, _sine, _total, _unpack, _upload, _view_poses,
                      _view_segments, essential_fundamental)
 from .stereo import _rig_rows as _rows_of
 
@@ -81,7 +83,8 @@ REDUCE_CHUNK, REDUCE_SLICES = 16, 16   # csrc/dcx_rig.hip's kChunk, kSlices: the
 __all__ = ["RigResult", "rig_calibrate_host", "rig_calibrate_host_full", "rig_calibrate_pools", "rig_calibrate_device", "rig_pair",
            "workspace_bytes", "RIG_OK", "RIG_NO_STAMPS", "RIG_DEGENERATE", "RIG_NONFINITE", "RIG_DISCONNECTED",
            "RigPoseResult", "rig_pose_host", "rig_pose_host_full", "rig_pose_pools", "unpack_rig_poses", "rig_pose_device",
-           "rig_pose_workspace_bytes"]
+           "rig_pose_workspace_bytes", "RigUncertainty", "rig_uncertainty_host", "rig_uncertainty_pools", "unpack_rig_uncertainty",
+           "rig_uncertainty_device", "rig_uncertainty_workspace_bytes"]
 
 
 class RigResult(NamedTuple):
@@ -649,3 +652,291 @@ def rig_pose_device(keypoints_lists: Sequence, col_count, row_count, square_len,
         outs = rig_pose_pools([p[0] for p in packs], B, [p[2] for p in packs], True, col_count, row_count, square_len, cameras, dists,
                               rig, None if masks is None else dm, models)
         return unpack_rig_poses(*outs)
+
+
+# ------------------------------------------------------------------------------------------------ how well the rig is determined
+# The covariances of the rig's extrinsics X_c and of the board poses P_t at a solved rig, the intrinsics held fixed:
+# ``calib.calibration_uncertainty_host``'s definition with the rig's 6 (C - 1) shared parameters in the intrinsics' place.
+# ``rig_uncertainty_host`` is the definition and the pin of csrc/dcx_rig_cov.hip; ``stereo.stereo_uncertainty_*`` are the C = 2 case
+# through the same functions.
+
+RIGCOV_STRIDE = 42             # DCX_RIGCOV_STRIDE: the row stride of cov_rig in d_global, 6 (RIG_MAX_CAMERAS - 1)
+RIGCOV_STD, RIGCOV_SIGMA2 = 1764, 1806          # DCX_RIGCOV_STD; DCX_RIGCOV_SIGMA2, then dof, points, stamps, status, 0
+RIGCOV_GLOBAL_WORDS = 1812     # DCX_RIGCOV_GLOBAL_WORDS
+# csrc/dcx_rig_cov.hip's summation orders.  A view's 91 entries: its rows in pool order, 64 at a time (a masked row adds zeros).
+# U_t: the usable cameras ascending.  The timestamps' parts of V, of the Schur sum, of the cost and of the counts: chunks of
+# REDUCE_COV_CHUNK timestamps in order, one thread per entry; then slice s of REDUCE_COV_SLICES adds the chunks s, s + 16, ... in
+# order and the slices are added serially, 0 first.  The cost of a timestamp: its usable cameras ascending.  cov_pose_t: for a
+# ascending, Y[r, a] * (sum over k ascending of S^-1[a, k] Y[c, k]), added to U_t^-1[r, c].
+REDUCE_COV_CHUNK, REDUCE_COV_SLICES = 16, 16
+
+
+class RigUncertainty(NamedTuple):
+    status: int                  # calib.COV_*
+    cov_rig: np.ndarray          # [n, n], n = 6 (C - 1): rvec_c, T_c per camera, cameras 1 .. C - 1 ascending
+    std_rig: np.ndarray          # [C, 6]: the roots of cov_rig's diagonal; row 0 (the reference camera) is zeros
+    cov_poses: np.ndarray        # [T, 6, 6]: rvec then tvec of P_t; zeros for a timestamp that was not used
+    std_poses: np.ndarray        # [T, 6]
+    baseline_std: np.ndarray     # [C]: the standard deviation of |T_c|; 0 for camera 0
+    sigma2: float                # sum |r|^2 / dof (px^2)
+    dof: int                     # 2 * points - 6 (C - 1) - 6 * stamps
+    points: int                  # kept rows of the usable views of the used timestamps
+    stamps: int                  # timestamps used
+
+
+def _rig_model(result_or_model, n_cams: int, batch: int):
+    """``result_or_model`` of the uncertainty calls -> (X [C - 1, 6], P [T, 6], view_status int32 [T, C]).  A ``RigResult`` (or,
+    for two cameras, a ``StereoResult``) must be solved (ValueError); a tuple is taken as it stands."""
+    r = result_or_model
+    if hasattr(r, "view_status") and hasattr(r, "rvecs"):
+        if r.status != RIG_OK:
+            raise ValueError(f"the calibration failed (status {r.status}): there is no solution to take an uncertainty at")
+        rvec, T = np.asarray(r.rvec, np.float64).reshape(-1, 3), np.asarray(r.T, np.float64).reshape(-1, 3)
+        if rvec.shape[0] == n_cams - 1 == 1:                    # a StereoResult: X_1 alone
+            rvec, T = np.r_[np.zeros((1, 3)), rvec], np.r_[np.zeros((1, 3)), T]
+        R, rvecs, tvecs, vs = rvec, r.rvecs, r.tvecs, r.view_status
+    else:
+        try:
+            R, T, rvecs, tvecs, vs = r
+        except (TypeError, ValueError):
+            raise ValueError("result_or_model must be a RigResult or (R [C, 3, 3] or rvec [C, 3], T [C, 3], rvecs [T, 3], tvecs "
+                             "[T, 3], view_status [T, C])") from None
+    R = np.asarray(R, np.float64)
+    rvec = np.stack([_rvec_of(m) for m in R]) if R.ndim == 3 else R.reshape(-1, 3)
+    T = np.asarray(T, np.float64).reshape(-1, 3)
+    P = np.c_[np.asarray(rvecs, np.float64).reshape(-1, 3), np.asarray(tvecs, np.float64).reshape(-1, 3)]
+    vs = np.asarray(vs).astype(np.int32).reshape(P.shape[0], -1)
+    if rvec.shape[0] != n_cams or T.shape[0] != n_cams or vs.shape != (batch, n_cams):
+        raise ValueError(f"{n_cams} cameras and {batch} timestamps need a rig of {n_cams} cameras, {batch} board poses and view "
+                         f"statuses [{batch}, {n_cams}]")
+    return np.c_[rvec, T][1:], P, vs
+
+
+def _uncertainty_result(status, C, B, used, points, sigma2=0.0, cov=None, blocks=None, X=None) -> RigUncertainty:
+    n = 6 * (C - 1)
+    cr, cp, base = np.zeros((n, n)), np.zeros((B, 6, 6)), np.zeros(C)
+    if status == COV_OK:
+        cr, cp[used] = cov, blocks
+        for c in range(1, C):
+            t, s = X[c - 1, 3:], slice(6 * (c - 1) + 3, 6 * c)
+            norm = math.sqrt(float(t @ t))
+            if norm > 0:
+                u = t / norm
+                base[c] = math.sqrt(max(float(u @ cr[s, s] @ u), 0.0))
+    return RigUncertainty(int(status), cr, np.r_[np.zeros((1, 6)), np.sqrt(np.diag(cr)).reshape(C - 1, 6)], cp,
+                          np.sqrt(np.diagonal(cp, axis1=1, axis2=2)), base, float(sigma2), int(2 * points - n - 6 * len(used)),
+                          int(points), int(len(used)))
+
+
+def _uncertainty_host(keypoints_lists, board, cams, mk, X, P, view_status, pool_order=False) -> RigUncertainty:
+    """The definition (``rig_uncertainty_host``) on checked arguments."""
+    col_count, row_count, square_len = board
+    C, B = len(cams), len(keypoints_lists[0])
+    n_ids = (col_count - 1) * (row_count - 1)
+    usable = view_status == PNP_OK
+    used = np.flatnonzero(usable.sum(1) >= 2)
+    stamps, points, bad = [], 0, False
+    for t in used:
+        views = []
+        for c in np.flatnonzero(usable[t]):
+            kp = _kept_rows(keypoints_lists[c][t], None if mk[c] is None or mk[c][t] is None else mk[c][t], pool_order)
+            points += kp.shape[0]
+            ids = kp[:, 2].astype(np.int64)
+            if kp.shape[0] and (ids.min() < 0 or ids.max() >= n_ids):
+                bad = True                                        # (an id that is not on the board has no point to project)
+            elif kp.shape[0]:
+                views.append((int(c), object_points(ids, col_count, row_count, square_len), kp[:, :2].astype(np.float32)))
+        bad |= not views                                          # (no row at all: U_t = 0)
+        stamps.append(views)
+
+    def out(status, *a):
+        return _uncertainty_result(status, C, B, used, points, *a)
+
+    dof = 2 * points - 6 * (C - 1) - 6 * used.size
+    if not used.size:
+        return out(COV_NO_VIEWS)
+    if dof <= 0:
+        return out(COV_NO_DOF)
+    if bad or not (np.isfinite(X).all() and np.isfinite(P[used]).all()):
+        return out(COV_SINGULAR)
+    rows = _rows_of(stamps, C)
+    nb = _normal_blocks(rows, cams, X, P[used], _view_segments(rows))
+    if nb is None:
+        return out(COV_SINGULAR)
+    U, W, V, _, _, costs = nb
+    inv = _lm.schur_covariance(U, W, V, costs)
+    if inv is None:
+        return out(COV_SINGULAR)
+    sigma2 = _total(costs) / dof
+    cov, blocks = sigma2 * inv[0], sigma2 * inv[1]
+    if not (math.isfinite(sigma2) and np.isfinite(cov).all() and np.isfinite(blocks).all()):
+        return out(COV_SINGULAR)
+    return out(COV_OK, sigma2, cov, blocks, X)
+
+
+def rig_uncertainty_host(keypoints_lists, col_count, row_count, square_len, cameras, dists, result_or_model, masks=None,
+                         models=None, pool_order=False) -> RigUncertainty:
+    """How well a solved rig is determined: the covariance of the rig's extrinsics X_c = (rvec_c, T_c), c = 1 .. C - 1, and of every
+    used timestamp's board pose P_t, GIVEN THE CAMERA MODELS: the intrinsics and distortion coefficients are held fixed, as the rig
+    calibration holds them, so their own uncertainty (``calib.calibration_uncertainty_*``) is not propagated into these numbers.
+    In float64 on the host; the definition and the pin of ``dcx_rig_uncertainty_pool``.
+
+    ``keypoints_lists``, ``cameras``, ``dists``, ``masks``, ``models`` and ``pool_order`` as ``rig_calibrate_host_full`` takes them.
+    ``result_or_model``: the ``RigResult`` of a calibration of these views (ValueError unless it is ``RIG_OK``), or the tuple
+    ``(R [C, 3, 3] or rvec [C, 3], T [C, 3], rvecs [T, 3], tvecs [T, 3], view_status [T, C])`` with camera 0's entries ignored;
+    the tuple is not checked for connectivity.
+
+    A view is usable iff its ``view_status`` is ``PNP_OK``; a timestamp is used iff two of its views are usable.  The rows are the
+    usable views' rows after their masks, in pool order, exactly as ``rig_calibrate_host_full`` builds them.  With the UNDAMPED
+    normal blocks of ``stereo._normal_blocks`` at (X, P) (U_t 6 x 6, W_t n x 6, V n x n block diagonal, n = 6 (C - 1)):
+    S = V - sum W_t U_t^-1 W_t^T, Y_t = U_t^-1 W_t^T (``_lm.schur_covariance``), dof = 2 points - n - 6 stamps,
+    sigma^2 = sum |r|^2 / dof, cov_rig = sigma^2 S^-1 (in the order rvec_c, T_c per camera, cameras ascending),
+    cov_pose_t = sigma^2 (U_t^-1 + Y_t S^-1 Y_t^T); standard deviations are the roots of the diagonals.  ``baseline_std[c]`` is
+    the standard deviation of |T_c|, sqrt(u^T Cov(T_c) u) with u = T_c / |T_c| (first order; host arithmetic on ``cov_rig``).
+
+    The sigma^2 convention is ``calib.calibration_uncertainty_host``'s: residuals (two per point) minus parameters; ``sigma2``,
+    ``dof``, ``points`` and ``stamps`` are returned for a caller who wants another.  Not reported: the cross-covariances between
+    the X_c and the P_t.
+
+    Statuses, in this order: ``COV_NO_VIEWS`` (no used timestamp), ``COV_NO_DOF`` (dof <= 0), ``COV_SINGULAR`` (a U_t or S that is
+    not positive definite, which includes a camera c >= 1 without a usable view in any used timestamp; a point not in front of its
+    camera; an id outside the board in a used view; a value that is not finite; on the device also a used view whose slots leave
+    its pool).  Everything but the status and the counts is zero unless ``COV_OK``; unused timestamps get zeros."""
+    cams, _ = _cameras(cameras, dists, models)
+    C = len(cams)
+    if len(keypoints_lists) != C:
+        raise ValueError(f"{len(keypoints_lists)} keypoint lists for {C} cameras")
+    B = len(keypoints_lists[0])
+    if any(len(k) != B for k in keypoints_lists):
+        raise ValueError("every camera needs as many views as camera 0")
+    X, P, vs = _rig_model(result_or_model, C, B)
+    return _uncertainty_host(keypoints_lists, (col_count, row_count, square_len), cams, _mask_lists(masks, C), X, P, vs, pool_order)
+
+
+# ---- on the device
+
+def rig_uncertainty_workspace_bytes(n_cams: int, batch: int, pools) -> int:
+    """Bytes of device workspace ``rig_uncertainty_pools`` needs."""
+    from . import _lib
+    pools = [int(p) for p in pools]
+    if len(pools) != int(n_cams):
+        raise ValueError("one pool size per camera is required")
+    n = int(_lib.lib().dcx_rig_uncertainty_workspace_bytes(int(n_cams), int(batch), (_ctypes.c_int * len(pools))(*pools)))
+    if n == 0:
+        raise ValueError(f"2 to {RIG_MAX_CAMERAS} cameras, batch >= 1 and pools >= 0 are required")
+    return n
+
+
+def _device_model(result_or_model, n_cams, batch, dev):
+    """``result_or_model`` of ``rig_uncertainty_pools`` -> (X [C - 1, 6] on the host, view_status int32 [B, C] and pose float64
+    [B, 8] on ``dev``).  The four-entry tuple ``(R or rvec, T, view_status, pose)`` carries the last two as the calibration wrote
+    them, arrays or device tensors (taken as they are); everything else goes through ``_rig_model`` and is uploaded."""
+    import torch
+    r = result_or_model
+    if isinstance(r, (tuple, list)) and len(r) == 4:
+        R, T, vs, pose = r
+        X = _rig_model((R, T, np.zeros((batch, 3)), np.zeros((batch, 3)), np.zeros((batch, n_cams), np.int32)), n_cams, batch)[0]
+    else:
+        X, P, vs = _rig_model(r, n_cams, batch)
+        pose = np.zeros((batch, 8))
+        pose[:, :6] = P
+    return (X, _device_or_upload(vs, dev, torch.int32, (batch, n_cams), "view_status"),
+            _device_or_upload(pose, dev, torch.float64, (batch, 8), "pose"))
+
+
+def rig_uncertainty_pools(packed_list, batch: int, pools, refined: bool, col_count, row_count, square_len, cameras, dists,
+                          result_or_model, masks=None, models=None, workspace=None, out=None):
+    """``rig_uncertainty_host`` on the GPU, read in place from the C corner pools the calibration read (the conventions of
+    ``rig_calibrate_pools``: ``pools``, ``masks``, ``models``) -> device tensors ``(global_ float64 [RIGCOV_GLOBAL_WORDS], pose_cov
+    float64 [B, COV_POSE_WORDS])``, which ``unpack_rig_uncertainty`` turns into a ``RigUncertainty``.
+
+    ``result_or_model``: what ``rig_uncertainty_host`` takes, or ``(R [C, 3, 3] or rvec [C, 3], T [C, 3], view_status [B, C] int32,
+    pose [B, 8] float64)`` with the last two as arrays or as the device tensors ``dcx_rig_calibrate_pool`` wrote.  ``workspace``: at
+    least ``rig_uncertainty_workspace_bytes`` bytes; ``out``: the two output tensors.  Five launches on the current stream; no
+    synchronisation, and given device tensors throughout nothing is allocated and the call can be captured in a graph (a result or
+    host arrays are uploaded first).  Unlike the calibration, views of a masked pool may share slots here."""
+    import torch
+    from . import _lib
+    cams, dists = _cameras(cameras, dists, models)
+    C = len(cams)
+    models = _models(models, C)
+    pools = [int(p) for p in pools]
+    if len(packed_list) != C or len(pools) != C:
+        raise ValueError(f"{C} cameras need {C} pools and {C} pool sizes")
+    dev = packed_list[0].device
+    if any(p.device != dev for p in packed_list):
+        raise ValueError("the pools must be on one device")
+    X, vs_d, pose_d = _device_model(result_or_model, C, batch, dev)
+    mk = _mask_lists(masks, C)
+    _device_masks(mk, pools, dev)
+    table = (_RigCamera * C)()
+    for c in range(C):
+        counts_p, starts_p, rows_p, xy_p = _pool_ptrs(packed_list[c], batch, pools[c], refined)
+        cam9, d8, nd = _model_args(cameras[c], dists[c], models and models[c])
+        table[c] = _RigCamera(counts_p, starts_p, rows_p, xy_p, pools[c], _lib.ptr(mk[c]), cam9, d8, nd)
+    nbytes = rig_uncertainty_workspace_bytes(C, batch, pools)
+    ws = _dev.workspace(workspace, dev, nbytes, f"workspace must be a contiguous tensor of at least {nbytes} bytes on {dev}")
+    if out is None:
+        out = (torch.empty((RIGCOV_GLOBAL_WORDS,), dtype=torch.float64, device=dev),
+               torch.empty((batch, COV_POSE_WORDS), dtype=torch.float64, device=dev))
+    glob = _dev.tensor(out[0], dev, torch.float64, (RIGCOV_GLOBAL_WORDS,), f"out[0] must be a contiguous float64 tensor of "
+                       f"{RIGCOV_GLOBAL_WORDS} values on {dev}")
+    pcov = _dev.tensor(out[1], dev, torch.float64, (batch, COV_POSE_WORDS), f"out[1] must be a contiguous float64 tensor "
+                       f"[{batch}, {COV_POSE_WORDS}] on {dev}")
+    tags = None if models is None else (_ctypes.c_int * C)(*(MODELS.index(m) for m in models))
+    x = (_ctypes.c_double * (6 * (C - 1)))(*X.ravel().tolist())
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().dcx_rig_uncertainty_pool(C, table, tags, x, int(batch), int(col_count), int(row_count), float(square_len),
+                                                       vs_d.data_ptr(), pose_d.data_ptr(), ws.data_ptr(),
+                                                       ws.numel() * ws.element_size(), glob.data_ptr(), pcov.data_ptr(),
+                                                       _lib.current_stream()), "dcx_rig_uncertainty_pool")
+    return glob, pcov
+
+
+def unpack_rig_uncertainty(global_, pose_cov, T) -> RigUncertainty:
+    """The two tensors of ``rig_uncertainty_pools`` and the rig's T [C, 3] (a ``RigResult``'s, or the tuple's) -> a
+    ``RigUncertainty`` on the host (this synchronises).  ``baseline_std`` is host arithmetic on ``cov_rig``, as in the definition."""
+    g, p = global_.cpu().numpy(), pose_cov.cpu().numpy()
+    T = np.asarray(T, np.float64).reshape(-1, 3)
+    C = T.shape[0]
+    n = 6 * (C - 1)
+    s2, dof, points, stamps, status = g[RIGCOV_SIGMA2:RIGCOV_SIGMA2 + 5]
+    cov = g[:RIGCOV_STD].reshape(RIGCOV_STRIDE, RIGCOV_STRIDE)[:n, :n].copy()
+    base = np.zeros(C)
+    if int(status) == COV_OK:
+        for c in range(1, C):
+            s = slice(6 * (c - 1) + 3, 6 * c)
+            norm = math.sqrt(float(T[c] @ T[c]))
+            if norm > 0:
+                u = T[c] / norm
+                base[c] = math.sqrt(max(float(u @ cov[s, s] @ u), 0.0))
+    return RigUncertainty(int(status), cov, np.r_[np.zeros((1, 6)), g[RIGCOV_STD:RIGCOV_STD + n].reshape(C - 1, 6)],
+                          p[:, :36].reshape(-1, 6, 6).copy(), p[:, 36:42].copy(), base, float(s2), int(dof), int(points), int(stamps))
+
+
+def _model_T(result_or_model):
+    r = result_or_model
+    return r.T if hasattr(r, "view_status") else r[1]
+
+
+def rig_uncertainty_device(keypoints_lists: Sequence, col_count, row_count, square_len, cameras, dists, result_or_model, masks=None,
+                           device="cuda", models=None) -> RigUncertainty:
+    """``rig_uncertainty_host`` on the GPU from ``infer_image``-format keypoint arrays ([x, y, id] rows; one list per camera,
+    equally long), the views the calibration was given -> ``RigUncertainty``.  ``result_or_model``, ``masks`` and ``models`` as for
+    the host definition."""
+    import torch
+    from .models._handles import require_cuda
+    dev = require_cuda(device)
+    cams, dists = _cameras(cameras, dists, models)            # ValueError before anything is uploaded
+    C = len(cams)
+    if len(keypoints_lists) != C:
+        raise ValueError(f"{len(keypoints_lists)} keypoint lists for {C} cameras")
+    B = len(keypoints_lists[0])
+    if any(len(k) != B for k in keypoints_lists):
+        raise ValueError("every camera needs as many views as camera 0")
+    packs, dm = _upload(keypoints_lists, _mask_lists(masks, C), dev)
+    with torch.cuda.device(dev):
+        g, p = rig_uncertainty_pools([p[0] for p in packs], B, [p[2] for p in packs], True, col_count, row_count, square_len, cameras,
+                                     dists, result_or_model, None if masks is None else dm, models)
+        T = np.asarray(_model_T(result_or_model), np.float64).reshape(-1, 3)
+        return unpack_rig_uncertainty(g, p, T if T.shape[0] == C else np.r_[np.zeros((1, 3)), T])

@@ -28,7 +28,8 @@ of pi0(P_t o) to the rows of view (0, t) and of pi1(X P_t o) to the rows of view
 
 ``stereo_calibrate_host_full`` is the readable definition and the test pin; ``stereo_calibrate_pool`` /
 ``stereo_calibrate_device`` run the same steps on the GPU (csrc/dcx_stereo.hip).  The two agree to rounding (summation order), not
-bit for bit.
+bit for bit.  ``stereo_uncertainty_host`` / ``_pool`` / ``_device`` (end of the module) say how well the solved pair is determined:
+``rig.rig_uncertainty_*`` with two cameras.
 
 Deviations from ``cv2.stereoCalibrate``:
 * the rig initialisation takes the median over MATRIX entries (then the polar factor) where cv2 takes it over rotation VECTORS: a
@@ -62,7 +63,7 @@ REDUCE_CHUNK, REDUCE_SLICES = 16, 16   # csrc/dcx_stereo.hip's kChunk, kSlices: 
 
 __all__ = ["StereoResult", "stereo_calibrate_host", "stereo_calibrate_host_full", "stereo_calibrate_pool",
            "stereo_calibrate_device", "workspace_bytes", "essential_fundamental", "STEREO_OK", "STEREO_NO_PAIRS",
-           "STEREO_DEGENERATE", "STEREO_NONFINITE"]
+           "STEREO_DEGENERATE", "STEREO_NONFINITE", "stereo_uncertainty_host", "stereo_uncertainty_pool", "stereo_uncertainty_device"]
 
 
 class StereoResult(NamedTuple):
@@ -613,3 +614,37 @@ def stereo_calibrate_device(keypoints_list0: Sequence, keypoints_list1: Sequence
         r = stereo_calibrate_pool(packed0, packed1, b, pool0, pool1, True, col_count, row_count, square_len, camera0, dist0,
                                   camera1, dist1, None if masks is None else tuple(dm), models)
     return _no_bad_id(r, col_count, row_count)
+
+
+# ------------------------------------------------------------------------------------------------ how well the pair is determined
+# ``rig.rig_uncertainty_*`` with two cameras: the same functions and the same entry (csrc/dcx_rig_cov.hip with n_cams = 2), so the
+# results are those calls' bit for bit.  (``rig`` imports this module, so it is imported at the call.)
+
+def stereo_uncertainty_host(keypoints_list0, keypoints_list1, col_count, row_count, square_len, camera0, dist0, camera1, dist1,
+                            result_or_model, masks=None, models=None):
+    """``rig.rig_uncertainty_host`` on the two lists -> its ``RigUncertainty``: the covariance of X_1 = (rvec, T) (``cov_rig``
+    6 x 6) and of every used pair's board pose, given the two camera models.  ``result_or_model``: a ``StereoResult`` (ValueError
+    unless ``STEREO_OK``; it stands for X_1, its P_t and its view statuses) or that function's tuple with C = 2.  ``masks`` and
+    ``models`` as for ``stereo_calibrate_host_full``."""
+    from . import rig
+    return rig.rig_uncertainty_host((keypoints_list0, keypoints_list1), col_count, row_count, square_len, (camera0, camera1),
+                                    (dist0, dist1), result_or_model, None if masks is None else list(_mask_pair(masks)), models)
+
+
+def stereo_uncertainty_pool(packed0, packed1, batch: int, pool0: int, pool1: int, refined: bool, col_count, row_count, square_len,
+                            camera0, dist0, camera1, dist1, result_or_model, masks=None, models=None, workspace=None, out=None):
+    """``rig.rig_uncertainty_pools`` on the two pools of ``stereo_calibrate_pool`` -> its two device tensors
+    (``rig.unpack_rig_uncertainty`` makes a ``RigUncertainty`` of them).  No synchronisation; capturable as that call is."""
+    from . import rig
+    return rig.rig_uncertainty_pools([packed0, packed1], batch, [pool0, pool1], refined, col_count, row_count, square_len,
+                                     (camera0, camera1), (dist0, dist1), result_or_model,
+                                     None if masks is None else list(_mask_pair(masks)), models, workspace, out)
+
+
+def stereo_uncertainty_device(keypoints_list0: Sequence, keypoints_list1: Sequence, col_count, row_count, square_len, camera0, dist0,
+                              camera1, dist1, result_or_model, masks=None, device="cuda", models=None):
+    """``stereo_uncertainty_host`` on the GPU from ``infer_image``-format keypoint arrays -> ``RigUncertainty``."""
+    from . import rig
+    return rig.rig_uncertainty_device((keypoints_list0, keypoints_list1), col_count, row_count, square_len, (camera0, camera1),
+                                      (dist0, dist1), result_or_model, None if masks is None else list(_mask_pair(masks)), device,
+                                      models)

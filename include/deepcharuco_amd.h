@@ -696,6 +696,50 @@ int dcx_calibrate_uncertainty_pool(const int32_t* d_counts, const int32_t* d_sta
                                    void* d_workspace, size_t workspace_bytes, double* d_global /* [DCX_COV_GLOBAL_WORDS] */,
                                    double* d_pose_cov /* [B][DCX_COV_POSE_WORDS] */, void* stream);
 
+/* ---- how well a rig is determined: the covariances of the rig's extrinsics and of the board poses ------------------------------
+ * What dcx_calibrate_uncertainty_pool is to dcx_calibrate_pool, for a rig solved by dcx_stereo_calibrate_pool (n_cams = 2) or
+ * dcx_rig_calibrate_pool / _models_pool: the covariance of X_1 .. X_{n_cams - 1} (rvec, T each) and of every used timestamp's P_t,
+ * GIVEN THE CAMERA MODELS: the intrinsics and distortion coefficients are held fixed, as those calibrations hold them.  The
+ * cameras, pools, masks (DcxRigCamera.d_mask) and h_models are dcx_rig_calibrate_models_pool's, and what that entry refuses with
+ * DCX_E_ARG this one does; h_rig [n_cams - 1][6] is dcx_rig_pose_pool's (read at the call, passed to the kernels by value).
+ * d_view_status int32 [B][n_cams] and d_pose f64 [B][8] as the calibration wrote them (words 0..5 of a used timestamp are read): a
+ * view is usable where it is DCX_PNP_OK, a timestamp is used if two of its views are.  None of the inputs is written; connectivity
+ * is not checked.  All fp64; deepcharuco_amd/rig.py restates the definition (rig_uncertainty_host).  With the undamped normal blocks
+ * of the rig calibration at (X, P), U_t 6x6, W_t n x 6 per used timestamp and V n x n (block diagonal), n = 6 (n_cams - 1), over
+ * the kept rows of the usable views:
+ *   S = V - sum W_t U_t^-1 W_t^T, Y_t = U_t^-1 W_t^T, dof = 2 points - n - 6 stamps, sigma^2 = sum |r|^2 / dof (the convention of
+ *   dcx_calibrate_uncertainty_pool), cov_rig = sigma^2 S^-1, cov_pose_t = sigma^2 (U_t^-1 + Y_t S^-1 Y_t^T), standard deviations
+ *   = the diagonals' roots.  The X - P cross-covariances are not reported.
+ * d_global f64 [DCX_RIGCOV_GLOBAL_WORDS], ONE layout for every n_cams, every word written: cov_rig row major with row stride
+ * DCX_RIGCOV_STRIDE (42) from DCX_RIGCOV_COV, in the order rvec_c, T_c per camera, cameras ascending; DCX_RIGCOV_STRIDE standard
+ * deviations from DCX_RIGCOV_STD; then sigma^2, dof, points (kept rows of the usable views of the used timestamps), timestamps
+ * used, the DCX_COV_* status and 0.  Entries past n are zero.  d_pose_cov f64 [B][DCX_COV_POSE_WORDS]: cov_pose_t 6x6 row major
+ * (rvec, tvec), then its 6 standard deviations; zeros for a timestamp that was not used.  Everything but the status, dof, points
+ * and stamps is zero unless DCX_COV_OK.  Statuses in this order: DCX_COV_NO_VIEWS (no used timestamp), DCX_COV_NO_DOF,
+ * DCX_COV_SINGULAR (a U_t or S that is not positive definite, which includes a camera c >= 1 without a usable view in any used
+ * timestamp; a point not in front of its camera; a kept id outside the board; a value that is not finite; a used view whose slots
+ * leave its pool, which are then not read).
+ * d_workspace: dcx_rig_uncertainty_workspace_bytes(n_cams, batch, h_pools) bytes of device memory, 8-byte aligned (DCX_E_WS if
+ * smaller); nothing is allocated and nothing but the workspace and the two outputs is written.  Five launches on `stream`, every
+ * sum in a fixed order, no atomics: two calls give the same bits, and a masked pool gives the bits of the pool with the dropped
+ * rows removed (a dropped row is added as a row of zeros, so frames of a masked pool may share slots here).  No host loop and NO
+ * synchronisation: the call can be captured in a graph.                                                                       */
+#define DCX_RIGCOV_STRIDE  42     /* 6 (DCX_RIG_MAX_CAMERAS - 1) */
+#define DCX_RIGCOV_COV     0      /* offsets into d_global */
+#define DCX_RIGCOV_STD     1764
+#define DCX_RIGCOV_SIGMA2  1806
+#define DCX_RIGCOV_DOF     1807
+#define DCX_RIGCOV_POINTS  1808
+#define DCX_RIGCOV_STAMPS  1809
+#define DCX_RIGCOV_STATUS  1810
+#define DCX_RIGCOV_GLOBAL_WORDS 1812
+size_t dcx_rig_uncertainty_workspace_bytes(int n_cams, int batch, const int* h_pools);   /* 0 for refused arguments */
+int dcx_rig_uncertainty_pool(int n_cams, const DcxRigCamera* h_cams, const int* h_models /* NULL = all pinhole */,
+                             const double* h_rig /* [n_cams - 1][6]: rvec, T of X_1 .. */, int batch, int col_count, int row_count,
+                             double square_len, const int32_t* d_view_status /* [B][n_cams] */, const double* d_pose /* [B][8] */,
+                             void* d_workspace, size_t workspace_bytes, double* d_global /* [DCX_RIGCOV_GLOBAL_WORDS] */,
+                             double* d_pose_cov /* [B][DCX_COV_POSE_WORDS] */, void* stream);
+
 /* ---- image resizing (cv2.resize): what stands in front of the detector ---------------------------------------------------------
  * dcx_resize_u8: batch frames d_src (u8, `channels` = 1 or 3 interleaved, rows `pitch` bytes apart, frames `frame_stride` bytes
  * apart, any base address: a cropped view costs nothing) -> d_out u8 [batch][out_h][out_w][channels], dense.  Channels are
